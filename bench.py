@@ -42,6 +42,58 @@ def align_seconds(err, key="ALIGN_SECONDS"):
     return max(float([l for l in err.split("\n") if l.startswith(key)][-1].split()[1]), 1e-9)
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, engs, cuts, seed=0):
+    """--dump-outputs: the compact records of the last timed step (psvr_engine_download_compact -- what a caller of the C ABI receives)
+    of a fixed, seeded sample of read pairs, one float64 file per record field (every field is an integer that float64 holds exactly):
+      sample_pairs.npy          the sampled pairs' numbers in the input, ascending
+      pairs_<field>.npy         their pair results
+      reads_<field>.npy         both mates' read results, mate 1 then mate 2 of each pair
+      cands_<field>.npy         those reads' candidates, in read order
+      cigar.npy                 those candidates' CIGAR words (len << 4 | op), in candidate order
+    Offsets into the engine's arrays (cand_off, cigar_off) and reserved words are left out: n_result and n_cigar delimit the lists.
+    The sample is the first S pairs of one seeded permutation, with S halved from 65536 until the files fit in DUMP_BYTES."""
+    import numpy as np
+    from pansvr_amd import aln
+    per_eng = [e.download_compact() for e in engs]
+    P = cuts[-1]
+    perm = np.random.RandomState(seed).permutation(P)
+
+    def ranges(starts, counts):                            # concatenated [start, start + count) index ranges
+        ex = np.cumsum(counts) - counts
+        return np.repeat(starts - ex, counts) + np.arange(int(counts.sum()), dtype=np.int64)
+
+    def fields(dt, skip):
+        return [f for f in dt.names if f not in skip]
+    s = min(P, 65536)
+    while True:
+        pick = np.sort(perm[:s])
+        parts = {"pairs": [], "reads": [], "cands": [], "cigar": []}
+        for j, (hdr, pairs, cands, cig) in enumerate(per_eng):
+            p = pick[(pick >= cuts[j]) & (pick < cuts[j + 1])] - cuts[j]
+            r = np.stack([2 * p, 2 * p + 1], axis=1).reshape(-1)
+            c = cands[ranges(hdr["cand_off"][r].astype(np.int64), hdr["n_result"][r].astype(np.int64))]
+            parts["pairs"].append(pairs[p])
+            parts["reads"].append(hdr[r])
+            parts["cands"].append(c)
+            parts["cigar"].append(cig[ranges(c["cigar_off"].astype(np.int64), c["n_cigar"].astype(np.int64))])
+        rec = {k: np.concatenate(v) for k, v in parts.items()}
+        out = {"sample_pairs": pick.astype(np.float64), "cigar": rec["cigar"].astype(np.float64)}
+        for k, dt, skip in (("pairs", aln.PAIR_DTYPE, ()), ("reads", aln.HDR_DTYPE, ("reserved", "reserved2", "cand_off")),
+                            ("cands", aln.CAND_DTYPE, ("reserved", "cigar_off"))):
+            for f in fields(dt, skip):
+                out["%s_%s" % (k, f)] = rec[k][f].astype(np.float64)
+        if sum(a.nbytes + 128 for a in out.values()) <= DUMP_BYTES or s == 1:      # (128: a .npy header)
+            break
+        s //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "pairs_sampled": int(s), "of_pairs": int(P), "files": len(out), "bytes": int(sum(a.nbytes for a in out.values()))}
+
+
 def pipelined_abi(aln, index, params, pin_in, n_batches=8, slots=3):
     """The rate a caller of the public C ABI sustains when it overlaps the three steps of a batch the way the reference's kt_pipeline
     overlaps load / align / write (src/clib/kthread.c:157-197): `slots` job slots, each an engine of its own on its own HIP queue,
@@ -206,7 +258,11 @@ def main():
     ap.add_argument("--one-pass", action="store_true", help="profiling runs (rocprofv3 --pmc): the warm-up and timed steps only, none of the extra engine passes (per-kernel timing, "
                                                             "work counters, PCIe legs, e2e, cfg5): every kernel's counters then belong to exactly warmup + steps passes")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, rank -> device selection and one barrier only (no GPU is touched): the launch contract, testable on CPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records the last one computed, for a fixed seeded sample of pairs, "
+                                                          "as DIR/<name>.npy (float64, at most 64 MB in all; one process only)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import numpy as np
     import torch
@@ -231,6 +287,8 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: one process only (--gpus 1)")
     if torch.cuda.device_count() == 0:
         raise SystemExit("bench.py needs a GPU: the engine has no CPU path")
     # the engine library, the CLI (its `index` sub-command builds the bench index) and the checkers: built here if the tree is a
@@ -406,11 +464,13 @@ def main():
             gather_check = {"blocks": world, "bytes": int(sum(n for _, n, _ in gathered)), "blocks_differing": len(bad)}
     reads_per_step = 2 * args.pairs * world
     value = reads_per_step * args.steps / dt
+    dumped = dump_outputs(args.dump_outputs, engs, cuts) if args.dump_outputs else None
 
     if args.one_pass:
         if rank == 0:
             print(json.dumps({"one_pass": True, "value": round(value, 1), "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                              "engine_passes": args.steps + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3)}), flush=True)
+                              "engine_passes": args.steps + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+                              **({"dump_outputs": dumped} if dumped else {})}), flush=True)
         for e in engs:
             e.close()
         index.close()
@@ -727,6 +787,8 @@ def main():
                 "roofline": roofline, "cpu_baseline": cpu, "parity_check": parity, "multi_gpu": multi, "e2e": e2e, "pcie_inclusive": pcie, "cfg5": cfg5,
                 "engine": {k: st[k] for k in ("rounds", "pair_runs", "pair_only_runs", "shadow_runs", "sensitive_pairs", "window_misses", "adopted_pairs", "dp_problems", "dp_seq_bytes", "stale_open", "candidates", "walk_pairs", "walk_us", "n_special", "special_const", "special_nomove", "probes", "hits", "seeds", "dp_cells", "hbm_used_bytes") if k in st},
                 "kernels_ms_per_step": {k: round(v["ms"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms"])}}
+        if dumped:
+            line["dump_outputs"] = dumped
         if failed:
             # a fast result that differs from the reference's is not a result: the line says so and the run fails
             line["error"] = "parity check failed: %s" % json.dumps({"parity_check": parity, "gather_check": gather_check})

@@ -54,6 +54,12 @@ def index_dir(name):
     return _idx[name]
 
 
+def prefix_digests(test):
+    """Length and SHA-256 of the files the reference's objects wrote for a large test's prefix (tests/golden/gen_prefix_digests.py)."""
+    with open(os.path.join(HERE, "golden", "prefix_sha256.json")) as f:
+        return json.load(f)[test]
+
+
 def golden_lines(name, rname):
     with gzip.open(os.path.join(golden_dir(name), rname + ".jsonl.gz"), "rt") as f:
         return [l for l in f.read().split("\n") if l]

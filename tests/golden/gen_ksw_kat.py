@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Generates tests/golden/ksw_kat.json.gz: inputs from tests/ksw_cases.fixed_cases() and the
 outputs of the REFERENCE kswlib itself (oracle/_ref/libref_ksw.so, compiled from
-/root/reference/src/kswlib by oracle/Makefile).  Run in the build container only."""
+/root/reference/src/kswlib by oracle/Makefile), and tests/golden/ksw_random_kat.json.gz: the same
+library's outputs for the seeded tests/ksw_cases.random_cases() of tests/test_oracle_ksw.py (inputs
+are regenerated from the seed).  Run in the build container only."""
 import gzip
 import json
 import os
@@ -9,7 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
-from ksw_cases import fixed_cases  # noqa: E402
+from ksw_cases import fixed_cases, random_cases  # noqa: E402
 from ksw_ref import ref_available, run_ref  # noqa: E402
 
 assert ref_available(), "build oracle/_ref first: make -C oracle"
@@ -25,3 +27,10 @@ for c in fixed_cases():
 with gzip.open(os.path.join(HERE, "ksw_kat.json.gz"), "wt") as f:
     json.dump(out, f, separators=(",", ":"))
 print("wrote", len(out), "cases")
+
+seed, n, maxlen = 4242, 1500, 220
+cases = random_cases(seed, n, maxlen)
+rnd = {"seed": seed, "n": n, "maxlen": maxlen, "extd2": [run_ref(c, "extd2") for c in cases], "extz2": [run_ref(dict(c), "extz2") for c in cases]}
+with gzip.GzipFile(os.path.join(HERE, "ksw_random_kat.json.gz"), "wb", mtime=0) as f:
+    f.write(json.dumps(rnd, separators=(",", ":")).encode())
+print("wrote", n, "random cases")

@@ -1,6 +1,7 @@
 """The oracle restatement of the DP (oracle/ksw_oracle.c) is pinned against
 (1) the committed known-answer vectors produced by the reference kswlib itself, and
-(2) where oracle/_ref exists, the live reference objects on fresh random cases."""
+(2) that library's committed answers for seeded random cases (tests/golden/ksw_random_kat.json.gz, both written by
+tests/golden/gen_ksw_kat.py)."""
 import gzip
 import json
 import os
@@ -8,7 +9,7 @@ import os
 import pytest
 
 from ksw_cases import random_cases
-from ksw_ref import ref_available, run_oracle, run_ref
+from ksw_ref import run_oracle
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -38,12 +39,15 @@ def test_oracle_matches_reference_kat(kind):
     assert not bad, "%d mismatches, first: %r" % (len(bad), bad[:3])
 
 
-@pytest.mark.skipif(not ref_available(), reason="oracle/_ref not built (no /root/reference here)")
 @pytest.mark.parametrize("kind", ["extd2", "extz2"])
 def test_oracle_matches_live_reference_random(kind):
+    with gzip.open(os.path.join(HERE, "golden", "ksw_random_kat.json.gz"), "rt") as f:
+        kat = json.load(f)
+    cases = random_cases(kat["seed"], kat["n"], kat["maxlen"])
+    assert len(cases) == len(kat[kind]) == 1500
     bad = []
-    for i, c in enumerate(random_cases(4242, 1500, 220)):
-        a, b = run_ref(c, kind), run_oracle(c, kind)
+    for i, (c, a) in enumerate(zip(cases, kat[kind])):
+        b = run_oracle(c, kind)
         if a != b:
             bad.append((i, len(c["query"]), len(c["target"]), diff(a, b)))
     assert not bad, "%d mismatches, first: %r" % (len(bad), bad[:3])

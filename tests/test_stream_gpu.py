@@ -6,7 +6,8 @@ for 150 bp reads the second limit binds, at 333 334 pairs.  Both are exercised o
   B. the reference's own rule (default options): 18 batches of 333 334 pairs.
 Checked: A and B write identical files (the rand()/random_r positions, the carried text and the three pipeline slots are
 batch-size invariant); the first 400 000 pairs of B -- across its first batch boundary -- are byte for byte what the
-reference's objects write for that prefix (`ref_aln -t 1 -S -R 400000`); CIGAR / flag / tag invariants over a sample of all
+reference's objects write for that prefix (`ref_aln -t 1 -S -R 400000`, whose bytes are pinned by their length and SHA-256 in
+tests/golden/prefix_sha256.json, written by tests/golden/gen_prefix_digests.py); CIGAR / flag / tag invariants over a sample of all
 records; the HBM footprint after the last batch is the footprint after the first."""
 import hashlib
 import json
@@ -23,8 +24,27 @@ import bench_data
 
 pytestmark = pytest.mark.gpu
 CLI = os.path.join(ac.ROOT, "pansvr_amd", "bin", "panSVR")
-REF = os.path.join(ac.ROOT, "oracle", "_ref", "ref_aln")
 PARTS, PART_PAIRS, PREFIX = 3, 2000000, 400000
+
+
+def write_inputs(tmp, parts, dense=False):
+    """The index, `parts` x PART_PAIRS pairs of FASTQ and the header under tmp; returns the command's three positional arguments.
+    dense: also the 2 GiB first-level table, which only the reference's own loader reads."""
+    anc = bench_data.make_anchors(4000, seed=11)
+    ix = bench_data.build_index_cli(anc, dense=dense)
+    dense_hash = ix.pop("hash")
+    bench_data.write_index_dir(ix, os.path.join(tmp, "idx"), dense_hash=dense_hash)
+    del dense_hash, ix
+    fq = os.path.join(tmp, "reads.fq")
+    ncore = os.cpu_count() or 1
+    for part in range(parts):                                            # 6 M pairs, 5 GB of text
+        bases, base_off, ori, isize = bench_data.make_reads(anc, PART_PAIRS, seed=17 + part)
+        bench_data.write_fastq(fq, bases, base_off, ori, isize, procs=min(16, ncore), name_base=part * PART_PAIRS, append=part > 0,
+                               stat=(150, 200, 400, 600) if part == 0 else None)
+        del bases, base_off, ori, isize
+    with open(os.path.join(tmp, "header.sam"), "w") as f:
+        f.write("@SQ\tSN:chr1\tLN:250000000\n@SQ\tSN:chr2\tLN:250000000\n")
+    return [os.path.join(tmp, "idx"), fq, os.path.join(tmp, "header.sam")]
 
 
 def md5_of(path):
@@ -46,22 +66,8 @@ def test_six_million_pairs_streamed_in_batches():
         pytest.skip("needs 40 GB of RAM-backed storage for the input and the output files")
     tmp = tempfile.mkdtemp(prefix="psvr_stream_", dir=shm)
     try:
-        anc = bench_data.make_anchors(4000, seed=11)
-        ix = bench_data.build_index_cli(anc, dense=os.path.exists(REF))
-        dense = ix.pop("hash")
-        bench_data.write_index_dir(ix, os.path.join(tmp, "idx"), dense_hash=dense)
-        del dense, ix
-        fq = os.path.join(tmp, "reads.fq")
-        ncore = os.cpu_count() or 1
-        for part in range(PARTS):                                            # 6 M pairs, 5 GB of text
-            bases, base_off, ori, isize = bench_data.make_reads(anc, PART_PAIRS, seed=17 + part)
-            bench_data.write_fastq(fq, bases, base_off, ori, isize, procs=min(16, ncore), name_base=part * PART_PAIRS, append=part > 0,
-                                   stat=(150, 200, 400, 600) if part == 0 else None)
-            del bases, base_off, ori, isize
-        with open(os.path.join(tmp, "header.sam"), "w") as f:
-            f.write("@SQ\tSN:chr1\tLN:250000000\n@SQ\tSN:chr2\tLN:250000000\n")
-        base = [os.path.join(tmp, "idx"), fq, os.path.join(tmp, "header.sam")]
-        nt = str(min(16, ncore))
+        base = write_inputs(tmp, PARTS)
+        nt = str(min(16, os.cpu_count() or 1))
 
         def run(tag, extra):
             o = os.path.join(tmp, tag)
@@ -81,19 +87,15 @@ def test_six_million_pairs_streamed_in_batches():
         assert jb["hbm_used_last"] <= jb["hbm_used_first"] * 1.02, jb
         assert (md5_of(b + ".sam"), md5_of(b + ".ori.sam")) == sums_a and os.path.getsize(b + ".sam") == size_a
         print("stream: A %s  B %s" % (json.dumps(ja), json.dumps(jb)))
-        # the prefix across B's first batch boundary (pair 333 334) against the reference's own objects (oracle/_ref travels to the GPU
-        # box with the snapshot: a box without it has no checker, which is a failure of the test, not a reason to pass)
-        assert os.path.exists(REF), "oracle/_ref/ref_aln is missing: build it with `make -C oracle` where /root/reference exists"
-        if True:
-            r = subprocess.run([REF, "-t", "1", "-S", "-R", str(PREFIX), "-o", os.path.join(tmp, "ref.sam"), "-p", os.path.join(tmp, "ref.ori.sam")] + base + ["--quiet"],
-                               stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
-            assert r.returncode == 0, r.stderr.decode()[-1000:]
-            for ext in (".sam", ".ori.sam"):
-                want = open(os.path.join(tmp, "ref" + ext), "rb").read()
-                with open(b + ext, "rb") as f:
-                    got = f.read(len(want))
-                assert got == want, "prefix of %s differs from the reference's file" % ext
-                assert len(want) > 10 ** 6
+        # the prefix across B's first batch boundary (pair 333 334) against what the reference's own objects wrote for it
+        want = ac.prefix_digests("stream")
+        assert want["pairs"] == PREFIX
+        for ext in (".sam", ".ori.sam"):
+            with open(b + ext, "rb") as f:
+                got = f.read(want[ext]["bytes"])
+            assert len(got) == want[ext]["bytes"] and hashlib.sha256(got).hexdigest() == want[ext]["sha256"], \
+                "prefix of %s differs from the reference's file" % ext
+            assert want[ext]["bytes"] > 10 ** 6
         # invariants over a sample of ALL records of the main file (every 40th line)
         consumes_q = set("MIS=X")
         n_seen = 0
