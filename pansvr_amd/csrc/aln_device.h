@@ -595,17 +595,10 @@ template <bool LOCAL> PSVR_HD void seed_strand_t(const Ctx &c, long long rs, con
 					if (pass == 0) ++probes;
 					kmer = get_kmer(off, rb);
 					if (kmer_maybe_present(ix, kmer)) { stage = 1; break; }
-#if defined(PSVR_DIAG_SEED) && PSVR_DIAG_SEED == 2     /* timing experiment: a strand whose first k-mer is refused is done (results are wrong) */
-					if (n == 0) { off = kn; break; }
-#endif
 					off += kSeedStep;
 				}
 				if (stage != 1) break;
-#if defined(PSVR_DIAG_SEED) && PSVR_DIAG_SEED == 1     /* timing experiment: no hash gather, no MEMs (results are wrong) */
-				nh = 0;
-#else
 				nh = probe_kmer(ix, kmer, first_hit);     // stage 1
-#endif
 				if (nh == 0 || nh > (uint32_t)kUniPosNMax) { off += kSeedStep; stage = 0; }
 				else stage = 2;
 			}

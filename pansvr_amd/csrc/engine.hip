@@ -198,9 +198,7 @@ __device__ __forceinline__ void block_list_append2(int32_t *list, unsigned int *
 	if (e1 >= 0) list[at] = e1;
 }
 
-#ifndef PSVR_PREP_BITS
-#define PSVR_PREP_BITS 11            // log2 of the bits of a lane's STR-screen set, reads of up to 160 bases
-#endif
+static constexpr int kPrepBits = 11;        // log2 of the bits of a lane's STR-screen set, reads of up to 160 bases
 template <int W, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work, long long n, int bits_log2)
 {
@@ -221,7 +219,6 @@ __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work,
 	// 64 consecutive pairs (the first round: no work list) writes its 12 KB of them as twelve coalesced stores instead of twelve stores of
 	// a 16-byte piece per lane 192 bytes apart (64 lines each: the kernel is bound by such requests)
 	bool strands_done = false;
-#if !defined(PSVR_PREP_STRAND_FILL) || PSVR_PREP_STRAND_FILL
 	if (work == nullptr && wi - lane + 63 < n) {
 		const uint32_t hl = (uint32_t)1469598103934665603ULL, hh = (uint32_t)(1469598103934665603ULL >> 32);
 		uint4 *st = (uint4 *)(c.strand + (wi - lane) * 4);
@@ -232,7 +229,6 @@ __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work,
 		}
 		strands_done = true;
 	}
-#endif
 	// what both mates' turns start from, asked for once: the pair's three base offsets and the words of its two psvr_ori_t records (chr_id,
 	// ref_bg, read_bg, align_score, {mapq, direction, unmapped, -}) -- mate 1's turn then starts with its bases' loads instead of a round trip
 	// for their address -- and mate 1's first dword of bases, on its way while mate 0 is worked on
@@ -246,11 +242,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work,
 		oc0 = ow[0], os0 = ow[3], ou0 = ow[4], oc1 = ow[5], os1 = ow[8], ou1 = ow[9];
 		first1 = *(const uint32_t *)((uintptr_t)(c.bases + bo_1) & ~(uintptr_t)3);
 	}
-#if !defined(PSVR_PREP_WORDS_STAGE) || PSVR_PREP_WORDS_STAGE
 	const bool coalesced = work == nullptr && wi - lane + 63 < n && 64 * 16 * c.wmax <= nb * 64 * 4;
-#else
-	const bool coalesced = false;
-#endif
 #pragma unroll 1
 	for (int mate = 0; mate < 2; ++mate) {
 		const long long read = slot * 2 + mate, item = slot * 3 + mate;
@@ -409,12 +401,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work,
 		// 16 such events prove the read is not STR.  The few reads left (is_str = 2) get the exact count in k_str_detect.
 		const int kn = L - kLenKmer + 1;
 		int verdict = 2;
-#if defined(PSVR_DIAG_PREP) && PSVR_DIAG_PREP == 1     /* timing experiment: no STR screen (results are wrong) */
-		if (kn >= 15) verdict = 0;
-		if (false) {
-#else
 		if (kn >= 15) {
-#endif
 			uint32_t klo = 0, khi = 0;
 			int taken = 0;
 #pragma unroll
@@ -622,49 +609,23 @@ __global__ __launch_bounds__(kBlock) void k_mem_list(Ctx c, const int32_t *work,
 		return c.active[r] && c.has_mem[r];
 	});
 }
-__global__ __launch_bounds__(kBlock) void k_chain(Ctx c, const int32_t *list, const unsigned int *cnt)
-{
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	if (i < (long long)*cnt) chain_read(c, list[i]);
-}
-// chaining and chain selection of a read by the same thread, one launch: the selection walks what the chaining has just written
-__global__ __launch_bounds__(kBlock) void k_chain_select(Ctx c, const int32_t *list, const unsigned int *cnt)
-{
-	const long long n = (long long)*cnt;          // (what k_chain_small left over: a fixed grid walks the list)
-	const long long nwaves = (long long)gridDim.x * (blockDim.x >> 6);
-	if (n <= 2 * nwaves) {
-		// a handful of reads: one per wavefront at a time.  The lanes of a wavefront that walk different reads' loops take turns, so 64 of
-		// these reads in one wavefront last as long as 64 reads one after the other (~80 us for the ~800 reads a 1 M-pair round leaves over)
-		if (threadIdx.x & 63) return;
-		for (long long i = blockIdx.x * (long long)(blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += nwaves) { const long long r = list[i]; chain_read(c, r); select_read(c, r); }
-		return;
-	}
-	for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) { const long long r = list[i]; chain_read(c, r); select_read(c, r); }
-}
-// chain + select of the listed reads in registers (chain_select_small, aln_device.h); the few reads it declines -- MEMs on both strands,
-// more than two seeds, a unipath with several reference positions -- are listed for k_chain_select (one atomic per such read: a handful per
-// thousand)
-// `left` == nullptr: the thread takes the read through the generic pair of stages itself.  A handful of reads per thousand: their
-// wavefronts last ~50 us longer, beside 17 k others -- a launch of its own for them was ~50 us of a nearly empty chip per mate.
-__global__ __launch_bounds__(kBlock) void k_chain_small(Ctx c, const int32_t *list, const unsigned int *cnt, int32_t *left, unsigned int *left_cnt)
+// chain + select of the listed reads in registers (chain_select_small, aln_device.h); a read it declines -- MEMs on both strands, more
+// than two seeds, a unipath with several reference positions -- the thread takes through the generic pair of stages (chain_read,
+// select_read) itself.  A handful of reads per thousand: their wavefronts last ~50 us longer, beside 17 k others -- a launch of its own
+// for them was ~50 us of a nearly empty chip per mate.
+__global__ __launch_bounds__(kBlock) void k_chain_small(Ctx c, const int32_t *list, const unsigned int *cnt)
 {
 	const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
 	if (i >= (long long)*cnt) return;
 	const int32_t r = list[i];
 	if (chain_select_small(c, r)) return;
-	if (left) left[atomicAdd(left_cnt, 1u)] = r;
-	else chain_read(c, r), select_read(c, r);
+	chain_read(c, r), select_read(c, r);
 }
 // the pairing stage over a list whose length only the device knows yet (right behind k_dirty / k_reselect, before the host has read the counts)
 __global__ __launch_bounds__(kBlock) void k_pair_dev(Ctx c, const int32_t *list, const unsigned long long *cnt)
 {
 	const unsigned long long n = *cnt;
 	for (unsigned long long i = blockIdx.x * (unsigned long long)blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) pair_reads(c, list[i]);
-}
-__global__ __launch_bounds__(kBlock) void k_select(Ctx c, const int32_t *list, const unsigned int *cnt)
-{
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	if (i < (long long)*cnt) select_read(c, list[i]);
 }
 // the reads that have candidates (a third of the reads have none: their lanes would idle through the walk of the others)
 __global__ __launch_bounds__(kBlock) void k_walk_list(Ctx c, const int32_t *work, long long n, int32_t *list, unsigned int *cnt)
@@ -710,10 +671,8 @@ template <class T> __device__ __forceinline__ long long block_arena_alloc(const 
 	return b < 0 ? -1 : b + (long long)mine;
 }
 // (four wavefronts per SIMD: the rare scratch-buffer replay of stale_compare must not cost the common path a wavefront)
-#ifndef PSVR_WALK_WAVES
-#define PSVR_WALK_WAVES 4
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PSVR_WALK_WAVES, 8))) void k_walk(Ctx c, const int32_t *list, const unsigned int *cnt)
+static constexpr int kWalkWaves = 4;
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kWalkWaves, 8))) void k_walk(Ctx c, const int32_t *list, const unsigned int *cnt)
 {
 	const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;   // one thread per read, looping over its (few) candidates
 	const long long read = i < (long long)*cnt ? (long long)list[i] : -1;  // no early exit: the reservations are made by the whole workgroup
@@ -736,21 +695,14 @@ __global__ __launch_bounds__(kBlock) void k_assemble(Ctx c, long long begin, lon
 	const long long co = block_arena_alloc(c.cig, (unsigned long long)(m > 0 ? m : 0));
 	if (have) assemble_store(c, i, ar, co);
 }
-__global__ __launch_bounds__(kBlock) void k_finalize(Ctx c, const int32_t *work, long long n)
-{
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	if (i < 2 * n) finalize_read(c, pair_of(work, i >> 1) * 2 + (i & 1));
-}
 __global__ __launch_bounds__(kBlock) void k_pair(Ctx c, const int32_t *work, long long n)
 {
 	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
 	if (i < n) pair_reads(c, pair_of(work, i));
 }
 // tail of both reads (finalize_read) and the pairing in one pass: the thread pairs the records it has just written
-#ifndef PSVR_FIN_WAVES
-#define PSVR_FIN_WAVES 4
-#endif
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(PSVR_FIN_WAVES, 8))) void k_finalize_pair(Ctx c, const int32_t *work, long long n)
+static constexpr int kFinWaves = 4;
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kFinWaves, 8))) void k_finalize_pair(Ctx c, const int32_t *work, long long n)
 {
 	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
 	if (i >= n) return;
@@ -832,12 +784,6 @@ __global__ void k_copy_i32(int32_t *dst, long long at, const int32_t *src, long 
 	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
 	if (i < n) dst[at + i] = src[i];
 }
-// one wavefront per adopted pair (adopt_variant in aln_device.h)
-__global__ __launch_bounds__(kBlock) void k_adopt(Ctx c, const int32_t *pairs, const int32_t *slots, long long n, const long long *noff)
-{
-	const long long i = blockIdx.x * (long long)(kBlock / 64) + (threadIdx.x >> 6);
-	if (i < n) adopt_variant(c, pairs[i], slots[i], noff, threadIdx.x & 63, 64);
-}
 // which special pairs draw alike under every residue assignment (class 1: unmasked, resolved on the device from here on)
 __global__ void k_special_class(Ctx c, const SpecialPair *sp, long long n, uint8_t *mask, uint8_t *cls)
 {
@@ -848,10 +794,7 @@ __global__ void k_special_class(Ctx c, const SpecialPair *sp, long long n, uint8
 	if (k) mask[sp[i].pair] = 0;
 }
 // the special pairs of class 1 that are still predictable (not count-sensitive): adopt_auto in aln_device.h
-#ifndef PSVR_ADOPT_LANES
-#define PSVR_ADOPT_LANES 4
-#endif
-static const int kAdoptLanes = PSVR_ADOPT_LANES;
+static constexpr int kAdoptLanes = 4;
 __global__ __launch_bounds__(kBlock) void k_adopt_auto(Ctx c, const SpecialPair *sp, long long n, const uint8_t *cls, const uint8_t *mask, const long long *noff,
                                                        int32_t *adopted, long long *adopted_at, unsigned long long *count, const int32_t *host_pairs, const int32_t *host_slots, long long n_host)
 {
@@ -917,12 +860,6 @@ __global__ __launch_bounds__(kBlock) void k_run_init(RunInit r)
 {
 	run_init_slot(r, blockIdx.x * (long long)kBlock + threadIdx.x);
 }
-__global__ void k_fill_i64(long long *p, long long n, int stride, int off, long long v)
-{
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	if (i < n) p[off + i * stride] = v;
-}
-
 __global__ void k_iota(int32_t *w, long long at, long long start, long long n)
 {
 	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -1291,8 +1228,6 @@ struct GpuBE {
 	void *dalloc(size_t n) { void *p = nullptr; hipError_t e = hipMalloc(&p, n ? n : 16); note(e); return e == hipSuccess ? p : nullptr; }
 	void dfree(void *p) { if (p) (void)hipFree(p); }
 	void dzero(void *p, size_t n) { note(hipMemsetAsync(p, 0, n, stream)); }
-	void dfill(void *p, int byte, size_t n) { note(hipMemsetAsync(p, byte, n, stream)); }
-	void d2d(void *dst, const void *src, size_t n) { if (n) note(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, stream)); }
 	void scatter_u8_dev(uint8_t *a, const int32_t *d_idx, long long n, uint8_t v)
 	{
 		if (n > 0) hipLaunchKernelGGL(k_scatter_u8, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, d_idx, n, v);
@@ -1418,10 +1353,6 @@ struct GpuBE {
 		}
 		if (ev_fork) (void)hipEventDestroy(ev_fork);
 	}
-	void fill_i64(long long *p, long long n, int stride, int off, long long v)
-	{
-		if (n) hipLaunchKernelGGL(k_fill_i64, dim3(grid_for(n)), dim3(kBlock), 0, stream, p, n, stride, off, v);
-	}
 	void st_seed(const Ctx &c, const int32_t *w, long long n, int mate)
 	{
 		if (n > 0) {
@@ -1430,49 +1361,24 @@ struct GpuBE {
 			t0("k_seed");
 			hipLaunchKernelGGL(k_seed, dim3(grid_for(2 * n)), dim3(kBlock), (size_t)pitch * 8 * kBlock, stream, c, w, n, mate, pitch);
 			t1();
-			// the list k_chain / k_select of this mate run on
+			// the list k_chain_small of this mate runs on
 			note(mem_list.ensure((size_t)(n + 4) * 4));
 			note(hipMemsetAsync(mem_list.p, 0, 4, stream));
 			hipLaunchKernelGGL(k_mem_list, dim3(grid_for(n, kBlock * kListItems)), dim3(kBlock), 0, stream, c, w, n, mate, mem_list.as<int32_t>() + 4, (unsigned int *)mem_list.p);
 		}
 		note(hipGetLastError());
 	}
-	DevBuf mem_list, left_list;
-	static bool chain_small_on() { static const bool v = getenv("PSVR_NO_CHAIN_SMALL") == nullptr; return v; }   // (A/B runs and tests: the generic kernel for every read)
+	DevBuf mem_list;
+	// chaining and chain selection of the mate's listed reads, one launch
 	void st_chain(const Ctx &c, const int32_t *w, long long n, int mate)
 	{
 		(void)w, (void)mate;
 		if (n <= 0) return;
-		const int32_t *list = mem_list.as<int32_t>() + 4;
-		const unsigned int *cnt = (const unsigned int *)mem_list.p;
-		if (chain_small_on() && left_list.ensure((size_t)(n + 4) * 4) == hipSuccess) {
-			// the register-resident small case for (nearly) every read, then the generic pair of stages over what it left
-			// (PSVR_CHAIN_LEFT_LIST=1: the declined reads go to a list and a launch of their own, as until round 4 -- A/B runs)
-			static const bool left_launch = getenv("PSVR_CHAIN_LEFT_LIST") != nullptr;
-			if (!left_launch) {
-				t0("k_chain_small");
-				hipLaunchKernelGGL(k_chain_small, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, list, cnt, (int32_t *)nullptr, (unsigned int *)nullptr);
-				t1();
-				note(hipGetLastError());
-				return;
-			}
-			note(hipMemsetAsync(left_list.p, 0, 4, stream));
-			t0("k_chain_small");
-			hipLaunchKernelGGL(k_chain_small, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, list, cnt, left_list.as<int32_t>() + 4, (unsigned int *)left_list.p);
-			t1();
-			list = left_list.as<int32_t>() + 4, cnt = (const unsigned int *)left_list.p;
-			const unsigned g = grid_for(n);
-			t0("k_chain_select");
-			hipLaunchKernelGGL(k_chain_select, dim3(g < 512u ? g : 512u), dim3(kBlock), 0, stream, c, list, cnt);
-			t1();
-		} else {
-			t0("k_chain_select");
-			hipLaunchKernelGGL(k_chain_select, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, list, cnt);
-			t1();
-		}
+		t0("k_chain_small");
+		hipLaunchKernelGGL(k_chain_small, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, (const int32_t *)(mem_list.as<int32_t>() + 4), (const unsigned int *)mem_list.p);
+		t1();
 		note(hipGetLastError());
 	}
-	void st_select(const Ctx &, const int32_t *, long long, int) {}      // (done by k_chain_select)
 	void st_pair_dev(const Ctx &c, const int32_t *list, const unsigned long long *cnt)
 	{
 		const long long blocks = c.n_pairs / kBlock + 1;
@@ -1519,7 +1425,7 @@ struct GpuBE {
 				note(hipMemsetAsync(redo.p, 0, 4, stream));
 				hipLaunchKernelGGL(k_prep_mate1, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, w, n, redo.as<int32_t>() + 4, (unsigned int *)redo.p);
 				launch_prep_wave(c, (const int32_t *)(redo.as<int32_t>() + 4), 0, 1, (const unsigned int *)redo.p, 64);
-			} else if (c.lmax <= 160) hipLaunchKernelGGL((k_prep_pair<5, 256>), dim3(grid_for(n, 256)), dim3(256), (size_t)4 * 64 * (1 << (PSVR_PREP_BITS - 3)), stream, c, w, n, PSVR_PREP_BITS);
+			} else if (c.lmax <= 160) hipLaunchKernelGGL((k_prep_pair<5, 256>), dim3(grid_for(n, 256)), dim3(256), (size_t)4 * 64 * (1 << (kPrepBits - 3)), stream, c, w, n, kPrepBits);
 			else hipLaunchKernelGGL((k_prep_pair<9, 128>), dim3(grid_for(n, 128)), dim3(128), (size_t)2 * 64 * 512, stream, c, w, n, 12);
 			t1();
 			note(hipGetLastError());
@@ -1564,12 +1470,10 @@ struct GpuBE {
 		t1();
 		note(hipGetLastError());
 	}
-	PSVR_STAGE(st_finalize, k_finalize, 2, kBlock)
 	PSVR_STAGE(st_pair, k_pair, 1, kBlock)
 	PSVR_STAGE(st_finalize_pair, k_finalize_pair, 1, kBlock)
 #undef PSVR_STAGE
 	DevBuf tmp_idx, tmp_val, tmp_out;
-	void fill_iota(int32_t *p, long long n) { if (n) hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kBlock), 0, stream, p, 0ll, 0ll, n); }
 	void run_init(const RunInit &r)
 	{
 		long long n = r.S;
@@ -1638,14 +1542,6 @@ struct GpuBE {
 		                   (const int32_t *)tmp_idx.p, (const int32_t *)tmp_val.p, n_host);
 		note(hipGetLastError());
 	}
-	void st_adopt(const Ctx &c, const int32_t *pairs, const int32_t *slots, long long n, const long long *noff)
-	{
-		if (!n) return;
-		note(tmp_idx.ensure(n * 4)), note(tmp_val.ensure(n * 4));
-		h2d(tmp_idx.p, pairs, n * 4), h2d(tmp_val.p, slots, n * 4);
-		hipLaunchKernelGGL(k_adopt, dim3(grid_for(n, kBlock / 64)), dim3(kBlock), 0, stream, c, (const int32_t *)tmp_idx.p, (const int32_t *)tmp_val.p, n, noff);
-		note(hipGetLastError());
-	}
 	void copy_hoff_to_shadows(const Ctx &c, long long P, long long n) { if (n) hipLaunchKernelGGL(k_hoff_shadows, dim3(grid_for(n)), dim3(kBlock), 0, stream, c, P, n); }
 	void st_totals(const Ctx &c, const int32_t *w, long long n, int32_t *ctot, int32_t *hprev, uint8_t *sens, int32_t *slist, unsigned long long *cnt, bool detect)
 	{
@@ -1681,14 +1577,7 @@ struct GpuBE {
 		S.cnt[0] = cnt, S.out[0] = out, S.stride[0] = stride, S.off[0] = off, S.base[0] = base;
 		st_scan_set(S, 1, n);
 	}
-	// the same scan over two / three arrays of one length, in the same three launches
-	void st_scan2(const int32_t *c0, int stride0, int off0, long long base0, long long *o0, const int32_t *c1, int stride1, int off1, long long base1, long long *o1, long long n)
-	{
-		ScanSet S = {};
-		S.cnt[0] = c0, S.out[0] = o0, S.stride[0] = stride0, S.off[0] = off0, S.base[0] = base0;
-		S.cnt[1] = c1, S.out[1] = o1, S.stride[1] = stride1, S.off[1] = off1, S.base[1] = base1;
-		st_scan_set(S, 2, n);
-	}
+	// the same scan over three arrays of one length, in the same three launches
 	void st_scan3(const int32_t *c0, long long *o0, const int32_t *c1, long long *o1, const int32_t *c2, long long *o2, long long n)
 	{
 		ScanSet S = {};
@@ -1733,8 +1622,8 @@ struct GpuBE {
 			if (rc) return rc;
 			note(dp_allow_big_lds());
 			// the engine reads score, mqe and the CIGAR of its pieces, never ez.max / max_q / max_t: when the z-drop rule cannot trigger for these
-			// scoring parameters (the reference's defaults), the team kernel runs without the per-diagonal maximum (PSVR_DP_NO_LEAN=1: A/B runs)
-			dp_lean = dp_zdrop_inert(dpP) && getenv("PSVR_DP_NO_LEAN") == nullptr;
+			// scoring parameters (the reference's defaults), the team kernel runs without the per-diagonal maximum
+			dp_lean = dp_zdrop_inert(dpP);
 			dp_ready = true;
 		}
 		// upper bounds for the sequence buffers: every problem has qlen, tlen < 1600; size from the actual lens
@@ -1987,24 +1876,20 @@ static int index_upload(psvr_index *ix, const psvr_index_view_t *v, const uint32
 	PSVR_HIP(hipGetLastError());
 	PSVR_HIP(hipDeviceSynchronize());
 	d.occ = ix->occ.as<uint32_t>();
-	// the Bloom filter over the 20-mers, sized to ~10 bits per k-mer (a power of two of 64-bit words; PSVR_BLOOM_LOG2=<log2 bytes> fixes
-	// the size, 0 leaves the occupancy bitmap as the only filter)
+	// the Bloom filter over the 20-mers, sized to ~10 bits per k-mer (a power of two of 64-bit words, 1 MB to 1 GB)
 	{
-		int lg = 0;
-		if (const char *e = getenv("PSVR_BLOOM_LOG2")) lg = atoi(e);
-		else { lg = 20; while (lg < 30 && ((uint64_t)8 << lg) < v->n_kmer * 10) ++lg; }
-		if (lg >= 16 && lg <= 32) {
-			const size_t bytes = (size_t)1 << lg;
-			PSVR_HIP(ix->bloom.alloc(bytes));
-			ix->bytes += (int64_t)bytes;
-			PSVR_HIP(hipMemset(ix->bloom.p, 0, bytes));
-			const uint32_t shift = (uint32_t)(64 - (lg - 3));
-			const long long NB = (long long)1 << 28;
-			hipLaunchKernelGGL(k_build_bloom, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, nullptr, d.hash, d.kmer, NB, (unsigned long long *)ix->bloom.p, shift);
-			PSVR_HIP(hipGetLastError());
-			PSVR_HIP(hipDeviceSynchronize());
-			d.bloom = ix->bloom.as<uint64_t>(), d.bloom_shift = shift;
-		}
+		int lg = 20;
+		while (lg < 30 && ((uint64_t)8 << lg) < v->n_kmer * 10) ++lg;
+		const size_t bytes = (size_t)1 << lg;
+		PSVR_HIP(ix->bloom.alloc(bytes));
+		ix->bytes += (int64_t)bytes;
+		PSVR_HIP(hipMemset(ix->bloom.p, 0, bytes));
+		const uint32_t shift = (uint32_t)(64 - (lg - 3));
+		const long long NB = (long long)1 << 28;
+		hipLaunchKernelGGL(k_build_bloom, dim3((unsigned)((NB + 255) / 256)), dim3(256), 0, nullptr, d.hash, d.kmer, NB, (unsigned long long *)ix->bloom.p, shift);
+		PSVR_HIP(hipGetLastError());
+		PSVR_HIP(hipDeviceSynchronize());
+		d.bloom = ix->bloom.as<uint64_t>(), d.bloom_shift = shift;
 	}
 	// bracket table for the unipath-of-position search (aln_device.h mem_for_hit): one entry per 1024 positions
 	{
@@ -2027,8 +1912,8 @@ static int index_upload(psvr_index *ix, const psvr_index_view_t *v, const uint32
 		PSVR_HIP(up(ix->uid_hint, hint.data(), hint.size() * 4, 0));
 		d.uid_hint = ix->uid_hint.as<uint32_t>(), d.uid_shift = sh;
 	}
-	// the per-entry records of UNITIG_MEM_search's index-only part (32 B per 22-mer occurrence; PSVR_NO_HITREC=1: derived per hit as before)
-	if (v->n_off && !getenv("PSVR_NO_HITREC")) {
+	// the per-entry records of UNITIG_MEM_search's index-only part (32 B per 22-mer occurrence)
+	if (v->n_off) {
 		PSVR_HIP(ix->hitrec.alloc((size_t)v->n_off * sizeof(HitRec)));
 		ix->bytes += (int64_t)(v->n_off * sizeof(HitRec));
 		hipLaunchKernelGGL(k_build_hitrec, dim3((unsigned)((v->n_off + 255) / 256)), dim3(256), 0, nullptr, d, (uint64_t)v->n_off, ix->hitrec.as<HitRec>());

@@ -476,7 +476,6 @@ template <class BE> struct EngineCore {
 			be.st_str(c, work, nwork, mate);
 			be.st_seed(c, work, nwork, mate);
 			be.st_chain(c, work, nwork, mate);
-			be.st_select(c, work, nwork, mate);
 		}
 		be.st_walk(c, work, nwork + nwalk);
 		unsigned long long tops[kTopStride + 1];                             // from the dp counter to the cw counter
@@ -519,12 +518,8 @@ template <class BE> struct EngineCore {
 		void clear() { n = 0; }
 		int32_t *data() { return p; }
 		const int32_t &operator[](size_t i) const { return p[i]; }
-		// the table as a view of memory somebody else owns (the backend's page-locked readback region: no copy out of it)
-		bool alias = false;
-		void view(int32_t *ext, size_t want) { if (!alias) free(p); p = ext, n = want, cap = 0, alias = true; }
 		bool resize(size_t want)
 		{
-			if (alias) p = nullptr, cap = 0, alias = false;
 			if (want > cap) {
 				free(p);
 				cap = want + want / 4 + 1024;
@@ -534,7 +529,7 @@ template <class BE> struct EngineCore {
 			n = want;
 			return true;
 		}
-		~HostTable() { if (!alias) free(p); }
+		~HostTable() { free(p); }
 		HostTable() = default;
 		HostTable(const HostTable &) = delete;
 		HostTable &operator=(const HostTable &) = delete;
@@ -709,10 +704,8 @@ template <class BE> struct EngineCore {
 					be.d2h_late_done();                      // (the gather's synchronisation has brought the late copy in as well; no list, no gather: waits here)
 					// the table is read at random by the walk below: out of the page-locked region the DMA engine has just written every
 					// row is a miss to memory (~170 ns per pair measured: 0.45 ms for 2.9 k pairs); one streaming copy (1 MB, ~35 us) puts it in
-					// the CPU's caches (PSVR_VCNT_VIEW=1: read it in place, for A/B runs)
-					static const bool in_place = getenv("PSVR_VCNT_VIEW") != nullptr;
-					if (late && in_place) vcnt.view(late, (size_t)3 * V);
-					else if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
+					// the CPU's caches
+					if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
 					else if (late) memcpy(vcnt.data(), late, (size_t)3 * V * 4);
 					else be.d2h(vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4);
 					build_rows();

@@ -49,9 +49,6 @@ struct DpBatch { // device pointers of one batch
 
 #define PSVR_DP_NUM_LDS_CLASSES 13
 #define PSVR_DP_KIND_TINY 11
-#ifndef PSVR_DP_USE_TINY
-#define PSVR_DP_USE_TINY 1     /* 0 sends them to the team kernel instead: same total time on the bench workload */
-#endif
 #define PSVR_DP_KIND_STRIP 12
 #define PSVR_DP_STRIP 16               // extd2_team_kernel: size classes count 16-column strips
 #define PSVR_DP_TINY_MAX 16            // extd2_tiny_kernel: qlen, tlen <= 16, one thread per alignment
@@ -79,19 +76,14 @@ inline bool dp_zdrop_inert(const DpParams &P) { return P.e2 == 0 && (P.zdrop < 0
 // the tiny / team kernels need the lean regime (values fit int8, band never clips) and only the flags they implement
 __host__ __device__ inline bool dp_tiny_ok(const DpParams &P, bool fast_ok) { return fast_ok && P.nowrap_ok && !P.skip && (P.w < 0 || P.w >= PSVR_DP_TINY_MAX); }
 // lanes per alignment of the team kernel for the class of problems with n_strips16 16-column strips
-// A team = PSVR_DP_TEAM_LANES lanes, each with PSVR_DP_TEAM_CPL target columns of a strip in registers (strip width = their product).
+// A team = kDpTeamLanes lanes, each with kDpTeamCpl target columns of a strip in registers (strip width = their product).
 // 4 x 4 was the first shape; 2 x 8 keeps the 16-column strips but spends a step's fixed cost -- neighbour exchange, boundary records,
 // per-diagonal maximum -- on eight cells instead of four, and puts 32 alignments in a wavefront.  Other shapes of the row sweep on the
 // bench batch (profiles/r03e_team_kernel_row_sweep.txt): 1 x 16 at two wavefronts per SIMD as fast, 4 x 4 and 4 x 8 slower.
-#ifndef PSVR_DP_TEAM_LANES
-#define PSVR_DP_TEAM_LANES 2
-#endif
-#ifndef PSVR_DP_TEAM_CPL
-#define PSVR_DP_TEAM_CPL 8
-#endif
-__host__ __device__ inline int dp_team_lanes(int n_strips16) { return PSVR_DP_TEAM_LANES; }
+static constexpr int kDpTeamLanes = 2, kDpTeamCpl = 8;
+__host__ __device__ inline int dp_team_lanes(int n_strips16) { return kDpTeamLanes; }
 // scratch bytes one wavefront of the team kernel needs for alignments with at most qmax query bases in that class
-__host__ __device__ inline unsigned long long dp_team_ws_bytes(int qmax, int n_strips16, int lanes, int cpl = PSVR_DP_TEAM_CPL)
+__host__ __device__ inline unsigned long long dp_team_ws_bytes(int qmax, int n_strips16, int lanes, int cpl = kDpTeamCpl)
 {
 	const int sw = cpl * lanes, pb = 64 / lanes, n_strips = (n_strips16 * 16 + sw - 1) / sw;
 	// direction bytes (one per cell, 64 x cpl per step), then per row / diagonal and alignment: two boundary dwords (ping-pong), the key D and the
@@ -144,10 +136,10 @@ __host__ __device__ inline bool dp_kind_uses_slab(int kind) { return kind == 0 |
 // kind: 1..5 = extd2_reg_kernel<kind,false> (direction bytes in LDS), 6..10 = extd2_reg_kernel<kind-5,true> (in HBM), 13 / 14 = extd2_ring_kernel<3 / 4>,
 // 11 = extd2_tiny_kernel (one thread per alignment; *need = 512 x anti-diagonals, which bins the problems by size),
 // 0 = general kernel, -1 = unsupported; *need = dynamic LDS bytes
-__host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_ok, int variant, bool skip, int *need, bool tiny_ok = false, bool team_ok = true, bool ring_ok = true)
+__host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_ok, int variant, bool skip, int *need, bool tiny_ok = false, bool team_ok = true)
 {
 	if (qlen <= 0 || tlen <= 0 || skip) { *need = 0; return 1; }
-	if (PSVR_DP_USE_TINY && tiny_ok && qlen <= PSVR_DP_TINY_MAX && tlen <= PSVR_DP_TINY_MAX) { *need = (qlen + tlen - 1) * 512; return PSVR_DP_KIND_TINY; }
+	if (tiny_ok && qlen <= PSVR_DP_TINY_MAX && tlen <= PSVR_DP_TINY_MAX) { *need = (qlen + tlen - 1) * 512; return PSVR_DP_KIND_TINY; }
 	// one thread per alignment, 16-column strips in registers: whenever the band never clips the matrix (the lean regime).
 	// The size class is the number of strips (1..13), expressed through `need` as that class's byte threshold.
 	// (team_ok = false: a batch too small to fill the chip with 16 alignments per wavefront goes to the wavefront-per-alignment kernels,
@@ -163,7 +155,7 @@ __host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_
 		*need = ((qlen + 16 + 15) & ~15) + 16;
 		return 5 + (T + 63) / 64;
 	}
-	if (fast_ok && ring_ok) {
+	if (fast_ok) {
 		// wider than the register-resident kernels' 320 columns: the ring kernels, when the columns an anti-diagonal can touch -- the band,
 		// w + 1 wide at most (and never wider than the shorter sequence), plus the 16-lane rounding at both ends, the stale-score block and
 		// the left neighbour of its first column -- fit their ring.  LDS: the query image and the target.

@@ -121,7 +121,6 @@ extern "C" int psvr_dp_plan_create(int device, int64_t n, const int32_t *qlen, c
 	}
 	const int fast_flags = PSVR_EZ_EXTZ_ONLY | PSVR_EZ_REV_CIGAR | PSVR_EZ_SCORE_ONLY;
 	const bool fast_ok = variant == 0 && (par->flag & ~fast_flags) == 0;
-	const bool ring_ok = getenv("PSVR_DP_NO_RING") == nullptr;      // (A/B runs: wide shapes through the general kernel)
 	// bucket = kind * classes + lds class
 	std::vector<std::vector<int32_t>> bucket(PSVR_DP_NUM_KINDS * kNumLdsClasses);
 	std::vector<int64_t> poff(n, 0);
@@ -133,7 +132,7 @@ extern "C" int psvr_dp_plan_create(int device, int64_t n, const int32_t *qlen, c
 			return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld: qlen=%d tlen=%d exceeds %d", (long long)i, ql, tl, kMaxLen);
 		}
 		int need = 0;
-		int kind = dp_classify(ql, tl, par->w, fast_ok, variant, pl->P.skip != 0, &need, dp_tiny_ok(pl->P, fast_ok), true, ring_ok);
+		int kind = dp_classify(ql, tl, par->w, fast_ok, variant, pl->P.skip != 0, &need, dp_tiny_ok(pl->P, fast_ok), true);
 		if (kind < 0) { delete pl; return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld needs %d B of LDS", (long long)i, need); }
 		if (dp_kind_uses_slab(kind) && ql > 0 && tl > 0) {
 			poff[i] = pslab;

@@ -651,17 +651,16 @@ __global__ __launch_bounds__(64) void extd2_tiny_kernel(DpBatch B, DpParams P, i
 // vector issue: see the price list in profiles/r01j_valu_op_rates.txt (add/sub/logic/right shift ~2 cycles,
 // max/min/cmp/three-operand/DPP ~4) -- which is why the differences are kept x 8 with the candidate's priority in the low
 // bits (below): ~47 vector instructions per cell.
-#ifndef PSVR_TEAM_WAVES
-#define PSVR_TEAM_WAVES 3          /* wavefronts per SIMD the register allocation aims at: 2 lanes x 8 columns needs 168 VGPRs (3 per SIMD); 1 x 16 at two per
-                                      SIMD runs as fast (1.84 vs 1.88 ms), 2 x 8 at two 2.29 ms, 4 x 4 at five 2.17 ms, 4 x 8 at three 2.54 ms: profiles/r03e */
-#endif
+// wavefronts per SIMD the register allocation aims at: 2 lanes x 8 columns needs 168 VGPRs (3 per SIMD); 1 x 16 at two per SIMD runs as
+// fast (1.84 vs 1.88 ms), 2 x 8 at two 2.29 ms, 4 x 4 at five 2.17 ms, 4 x 8 at three 2.54 ms: profiles/r03e
+static constexpr int kTeamWaves = 3;
 // LEAN = 1: no per-anti-diagonal maximum (M[], K[], G[], the D[r] records).  That maximum feeds ksw_apply_zdrop and ez.max / max_q / max_t
 // only.  With e2 == 0 a gap of ANY length costs at most q2, so every anti-diagonal behind the cell that holds the running maximum has a cell
 // reachable from it by one insertion and one deletion: its maximum is at least max - 2 q2, and with zdrop >= 2 q2 (the reference's defaults:
 // 32 / 0, zdrop 400) the rule `max - H > zdrop + l * e2` can never hold -- dp_zdrop_inert().  The engine's own launches (seam B1 reads
 // score, mqe and the CIGAR of its pieces) then run this variant; psvr_extd2_batch, whose ksw_extz_t carries max / max_q / max_t, never does.
 template <int LANES, int CPL, int LEAN>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PSVR_TEAM_WAVES, 8))) void extd2_team_kernel(DpBatch B, DpParams P, TeamPlan T)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 8))) void extd2_team_kernel(DpBatch B, DpParams P, TeamPlan T)
 {
 	static_assert(CPL == 4 || CPL == 8 || CPL == 16, "columns per lane: direction bytes go out as dwords");
 	constexpr int SW = CPL * LANES, PB = 64 / LANES;                 // strip width, alignments per wavefront
@@ -816,11 +815,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(PSVR_TEAM_WA
 // dependent loads (a record per anti-diagonal, a direction byte per CIGAR step); inside the sweep kernel, one lane per team at three
 // wavefronts per SIMD, they took 0.39 of 2.21 ms on the DP micro-benchmark (profiles/r03e).  Thread t of block b serves team t % PB of the sweep's
 // block (b * 64 + t) / PB and finds that wavefront's scratch the way it did.
-#ifndef PSVR_FINISH_WAVES
-#define PSVR_FINISH_WAVES 8          // most wavefronts of the finish launch per SIMD (experiments)
-#endif
+static constexpr int kFinishWaves = 8;          // most wavefronts of the finish launch per SIMD
 template <int LANES, int CPL, int LEAN>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, PSVR_FINISH_WAVES))) void extd2_team_finish_kernel(DpBatch B, DpParams P, TeamPlan T)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, kFinishWaves))) void extd2_team_finish_kernel(DpBatch B, DpParams P, TeamPlan T)
 {
 	constexpr int SW = CPL * LANES, PB = 64 / LANES, kWinRows = 8;
 	__shared__ uint32_t win[kWinRows * (CPL / 4) * 64];              // the traceback's window of direction bytes: [row][dword][thread]
@@ -926,10 +923,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, PSVR_FINI
 	}
 	write_ez(out, ez, n_cigar);
 }
-template __global__ void extd2_team_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 0>(DpBatch, DpParams, TeamPlan);
-template __global__ void extd2_team_finish_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 0>(DpBatch, DpParams, TeamPlan);
-template __global__ void extd2_team_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 1>(DpBatch, DpParams, TeamPlan);
-template __global__ void extd2_team_finish_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 1>(DpBatch, DpParams, TeamPlan);
+template __global__ void extd2_team_kernel<kDpTeamLanes, kDpTeamCpl, 0>(DpBatch, DpParams, TeamPlan);
+template __global__ void extd2_team_finish_kernel<kDpTeamLanes, kDpTeamCpl, 0>(DpBatch, DpParams, TeamPlan);
+template __global__ void extd2_team_kernel<kDpTeamLanes, kDpTeamCpl, 1>(DpBatch, DpParams, TeamPlan);
+template __global__ void extd2_team_finish_kernel<kDpTeamLanes, kDpTeamCpl, 1>(DpBatch, DpParams, TeamPlan);
 
 // ------------------------------------------------------------------------------------------
 // general path: DP state in LDS laid out exactly like the reference's flat image

@@ -67,15 +67,15 @@ struct TeamLaunch {
 	void launch_sweep(hipStream_t stream, const DpBatch &B, const DpParams &P, bool lean = false) const
 	{
 		if (!T.n_classes) return;
-		if (lean) hipLaunchKernelGGL((extd2_team_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 1>), dim3((unsigned)T.first_block[T.n_classes]), dim3(64), 0, stream, B, P, T);
-		else hipLaunchKernelGGL((extd2_team_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 0>), dim3((unsigned)T.first_block[T.n_classes]), dim3(64), 0, stream, B, P, T);
+		if (lean) hipLaunchKernelGGL((extd2_team_kernel<kDpTeamLanes, kDpTeamCpl, 1>), dim3((unsigned)T.first_block[T.n_classes]), dim3(64), 0, stream, B, P, T);
+		else hipLaunchKernelGGL((extd2_team_kernel<kDpTeamLanes, kDpTeamCpl, 0>), dim3((unsigned)T.first_block[T.n_classes]), dim3(64), 0, stream, B, P, T);
 	}
 	void launch_finish(hipStream_t stream, const DpBatch &B, const DpParams &P, bool lean = false) const
 	{
 		if (!T.n_classes) return;
-		const unsigned blocks = (unsigned)T.first_block[T.n_classes], pb = 64u / PSVR_DP_TEAM_LANES;
-		if (lean) hipLaunchKernelGGL((extd2_team_finish_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 1>), dim3((blocks * pb + 63u) / 64u), dim3(64), 0, stream, B, P, T);
-		else hipLaunchKernelGGL((extd2_team_finish_kernel<PSVR_DP_TEAM_LANES, PSVR_DP_TEAM_CPL, 0>), dim3((blocks * pb + 63u) / 64u), dim3(64), 0, stream, B, P, T);
+		const unsigned blocks = (unsigned)T.first_block[T.n_classes], pb = 64u / kDpTeamLanes;
+		if (lean) hipLaunchKernelGGL((extd2_team_finish_kernel<kDpTeamLanes, kDpTeamCpl, 1>), dim3((blocks * pb + 63u) / 64u), dim3(64), 0, stream, B, P, T);
+		else hipLaunchKernelGGL((extd2_team_finish_kernel<kDpTeamLanes, kDpTeamCpl, 0>), dim3((blocks * pb + 63u) / 64u), dim3(64), 0, stream, B, P, T);
 	}
 	void launch(hipStream_t stream, const DpBatch &B, const DpParams &P, bool lean = false) const { launch_sweep(stream, B, P, lean), launch_finish(stream, B, P, lean); }
 };

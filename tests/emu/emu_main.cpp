@@ -31,8 +31,6 @@ struct CpuBE {
 	void *dalloc(size_t n) { return calloc(n ? n : 1, 1); }
 	void dfree(void *p) { free(p); }
 	void dzero(void *p, size_t n) { memset(p, 0, n); }
-	void dfill(void *p, int byte, size_t n) { memset(p, byte, n); }
-	void d2d(void *dst, const void *src, size_t n) { memcpy(dst, src, n); }
 	void scatter_u8_dev(uint8_t *a, const int32_t *idx, long long n, uint8_t v) { scatter_u8(a, idx, n, v); }
 	void h2d(void *d, const void *h, size_t n) { memcpy(d, h, n); }
 	void h2d_start(void *d, const void *h, size_t n) { memcpy(d, h, n); }
@@ -71,9 +69,7 @@ struct CpuBE {
 		return late_buf.data();
 	}
 	void d2h_late_done() {}
-	void fill_i64(long long *p, long long n, int stride, int off, long long v) { for (long long i = 0; i < n; ++i) p[off + i * stride] = v; }
 	static long long pr(const int32_t *w, long long i) { return w ? w[i] : i; }
-	void fill_iota(int32_t *p, long long n) { for (long long i = 0; i < n; ++i) p[i] = (int32_t)i; }
 	void run_init(const RunInit &r)
 	{
 		long long n = r.S;
@@ -125,7 +121,6 @@ struct CpuBE {
 			chain_read(c, r), select_read(c, r);
 		}
 	}
-	void st_select(const Ctx &, const int32_t *, long long, int) {}
 	void st_walk(const Ctx &c, const int32_t *w, long long n)
 	{
 		for (long long i = 0; i < 2 * n; ++i) walk_read(c, pr(w, i >> 1) * 2 + (i & 1));
@@ -146,7 +141,6 @@ struct CpuBE {
 		st_totals(c, list, (long long)*n_dev, ctot, hprev, sens, slist, cnt, true);
 	}
 	void st_assemble(const Ctx &c, long long b, long long e) { for (long long i = b; i < e; ++i) assemble_candidate(c, i); }
-	void st_finalize(const Ctx &c, const int32_t *w, long long n) { for (long long i = 0; i < 2 * n; ++i) finalize_read(c, pr(w, i >> 1) * 2 + (i & 1)); }
 	void st_pair(const Ctx &c, const int32_t *w, long long n) { for (long long i = 0; i < n; ++i) pair_reads(c, pr(w, i)); }
 	// as k_finalize_pair does it: both headers built in place, the pairing's items handed on from finalize_read
 	void st_finalize_pair(const Ctx &c, const int32_t *w, long long n)

@@ -7,7 +7,7 @@ import sys
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 ev = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("void ", "").replace("psvr::", "")[:28]) for r in rows]
-# a step starts with the k_fill_i64 triple that resets the offsets (run()); fall back to k_prep pairs
+# steps are split at the k_iota launches (the work list of a round with shadow slots, engine_core.h run())
 starts = [i for i, e in enumerate(ev) if e[2].startswith("k_iota")]
 k = int(sys.argv[2]) if len(sys.argv) > 2 else len(starts) - 2
 a, b = starts[k], starts[k + 1]
