@@ -10,16 +10,20 @@
 //   deCOY_CLASSIFY_MAIN::load_reads  kseq_read over xzopen, STAT_ parsing, batching limits               rr.cpp:121-152
 //   kt_for -> align_read_pair        incl. output_BAM / output_ori_bam -> sam_parse1 -> bam1_t           rr.cpp:745-803, kthread.c:61-86
 //   sam_format1                      the text sam_write1 writes for every b with core.tid != -1          rr.cpp:165-176
-// What this driver adds is init_run's glue (rr.cpp:26-108) minus hts_open: htslib's file layer (hts_open -> cram_open ->
-// cram_io.c, which needs <lzma.h>) cannot be built in this image, so the driver reads header.sam itself, hands the '@' lines to
-// sam_hdr_parse, and writes sam_format1's text with fputs.  -ffunction-sections + --gc-sections drops init_run and the
-// htslib functions nothing here reaches.  No stand-in header or library is involved.
+//   bgzf_open / bam_hdr_write /      (--bam) what hts_open(.., "wb") and sam_hdr_write / sam_write1 do    rr.cpp:89-90,165-176
+//     bam_write1 / bgzf_close        for a BAM file: sam.c:1079-1080, bam_write1 -> bgzf_write
+// What this driver adds is init_run's glue (rr.cpp:26-108) minus hts_open: hts_open reaches cram_open -> cram_io.c, which needs
+// <lzma.h>, so the driver reads header.sam itself, hands the '@' lines to sam_hdr_parse, and either writes sam_format1's text
+// with fputs (-S) or opens the two files with htslib's own bgzf_open (--bam; the mode "w" gives the default level that "wb"
+// gives through hts_open) and writes them with bam_hdr_write and bam_write1.  -ffunction-sections + --gc-sections drops
+// init_run and the htslib functions nothing here reaches.  No stand-in header or library is involved.
 //
 // Usage: ref_aln [fc_aln options] <IndexDir> <reads.fq> <header.sam> [--records FILE|-] [--trace] [--limit N] [--batch N] [--quiet]
 //                [--stream-pos G,H0,H1]
 //   --stream-pos       : (-t 1) the input is the continuation of a longer run: before the first pair, rand() is called until G draws
 //                        have been made in total and handler k's random_r until Hk -- where a shard of a sharded run stands
-//   -S -o FILE -p FILE : SAM text of the two output files (without -S nothing is formatted; BAM needs htslib's bgzf/hfile layer)
+//   -S -o FILE -p FILE : SAM text of the two output files (without -S or --bam nothing is formatted)
+//   --bam -o FILE -p FILE : the two output files as BAM, written by htslib's bam_hdr_write / bam_write1 (what `fc_aln` without -S writes)
 //   --records          : one JSON line per pair with what align_read_pair decided (default: stdout when no -S is given)
 //   -t N               : the reference's own kt_for over N threads (timing only: output is non-deterministic for N > 1)
 // stderr: "ALIGN_SECONDS s" = wall of the kt_for calls alone; "TOTAL_SECONDS s" = load_reads + kt_for + formatting.
@@ -30,6 +34,7 @@
 #include <string>
 #include <vector>
 #include "PanSVgenerateVCF/read_realignment.hpp"
+#include "htslib/bgzf.h"
 extern "C" {
 #include "clib/kthread.h"
 }
@@ -116,7 +121,7 @@ int main(int argc, char **argv)
 	// the driver's own switches are taken out; everything else is the reference parser's business
 	std::vector<char *> av;
 	const char *records = NULL;
-	bool trace = false, quiet = false;
+	bool trace = false, quiet = false, bam = false;
 	long limit = -1, batch = 200000;
 	long long spos[3] = {-1, -1, -1};
 	av.push_back(argv[0]);
@@ -124,6 +129,7 @@ int main(int argc, char **argv)
 	for (int a = 1; a < argc; ++a) {
 		if (!strcmp(argv[a], "--trace")) trace = true;
 		else if (!strcmp(argv[a], "--quiet")) quiet = true;
+		else if (!strcmp(argv[a], "--bam")) bam = true;
 		else if (!strcmp(argv[a], "--limit") && a + 1 < argc) limit = atol(argv[++a]);
 		else if (!strcmp(argv[a], "--batch") && a + 1 < argc) batch = atol(argv[++a]);
 		else if (!strcmp(argv[a], "--records") && a + 1 < argc) records = argv[++a];
@@ -136,7 +142,8 @@ int main(int argc, char **argv)
 	MAP_PARA *o = (MAP_PARA *)xcalloc(1, sizeof(MAP_PARA));
 	if (o->get_option((int)av.size() - 2, av.data() + 1) != 0) return 1;
 	if (limit >= 0 && limit < o->max_use_read) o->max_use_read = (int)limit;
-	if (!o->output_sam && !records) records = "-";
+	if (bam && o->output_sam) { fprintf(stderr, "--bam and -S exclude each other\n"); return 1; }
+	if (!o->output_sam && !bam && !records) records = "-";
 
 	deBGA_INDEX *idx = (deBGA_INDEX *)xcalloc(1, sizeof(deBGA_INDEX));
 	{   // init_run, rr.cpp:38-42, with the text handed to sam_hdr_parse directly (sam_hdr_read's SAM branch collects the '@' lines and does the same)
@@ -172,9 +179,14 @@ int main(int argc, char **argv)
 	B.frec = NULL;
 	if (records && nt == 1) B.frec = !strcmp(records, "-") ? stdout : xopen(records, "w");
 	FILE *fo = NULL, *fo_ori = NULL;
+	BGZF *bo = NULL, *bo_ori = NULL;
 	if (o->output_sam) {
 		fo = xopen(o->sam_path, "w"), fo_ori = xopen(o->sam_path_signal_ori, "w");
 		fputs(idx->ori_header->text, fo), fputs(idx->ori_header->text, fo_ori);       // sam_hdr_write's SAM branch: the header text as is
+	} else if (bam) {                                        // hts_open(.., "wb") -> bgzf_open; sam_hdr_write's BAM branch (sam.c:1079-1080)
+		bo = bgzf_open(o->sam_path, "w"), bo_ori = bgzf_open(o->sam_path_signal_ori, "w");
+		if (!bo || !bo_ori) { fprintf(real_stderr, "cannot open the BAM outputs\n"); return 1; }
+		if (bam_hdr_write(bo, idx->ori_header) < 0 || bam_hdr_write(bo_ori, idx->ori_header) < 0) { fprintf(real_stderr, "bam_hdr_write failed\n"); return 1; }
 	}
 	gzFile fp1 = xzopen(o->read_fastq1, "rb");
 	kstream_t *ks = ks_init(fp1);
@@ -196,10 +208,23 @@ int main(int argc, char **argv)
 				if (B.ori_b2[i].core.tid != -1) { sam_format1(idx->ori_header, B.ori_b2 + i, &str); fputs(str.s, fo_ori), fputc('\n', fo_ori); }
 			}
 		}
+		if (bo) {                                           // output_results with sam_write1's BAM branch: bam_write1, same order as above
+			bool ok = true;
+			for (int i = 0; i < n; i++) {
+				if (B.b1[i].core.tid != -1) ok = ok && bam_write1(bo, B.b1 + i) >= 0;
+				if (B.b2[i].core.tid != -1) ok = ok && bam_write1(bo, B.b2 + i) >= 0;
+			}
+			for (int i = 0; i < n; i++) {
+				if (B.ori_b1[i].core.tid != -1) ok = ok && bam_write1(bo_ori, B.ori_b1 + i) >= 0;
+				if (B.ori_b2[i].core.tid != -1) ok = ok && bam_write1(bo_ori, B.ori_b2 + i) >= 0;
+			}
+			if (!ok) { fprintf(real_stderr, "bam_write1 failed\n"); return 1; }
+		}
 		B.pair_base += n;
 	}
 	t_all = now() - t_all;
 	if (fo) fclose(fo), fclose(fo_ori);
+	if (bo && (bgzf_close(bo) < 0 || bgzf_close(bo_ori) < 0)) { fprintf(real_stderr, "bgzf_close failed\n"); return 1; }
 	if (B.frec && B.frec != stdout) fclose(B.frec);
 	fflush(stdout);
 	fprintf(real_stderr, "ALIGN_SECONDS %.6f\nTOTAL_SECONDS %.6f\nTHREADS %d\nPAIRS %ld\n", t_align, t_all, nt, B.pair_base);

@@ -5,11 +5,12 @@
 // The vendored htslib cannot be built in this image, so this encoder follows the published
 // format (SAM/BAM specification v1, sections 4.1 BGZF and 4.2 BAM) and the typing rules of htslib's sam_parse1:
 //   * integer tags take the smallest type that holds the value (c/C/s/S/i/I),
-//   * bin = reg2bin(pos, pos + reference length of the CIGAR, or +1 without one),
+//   * bin = reg2bin(pos, pos + reference length of the CIGAR), or reg2bin(pos, pos + 1) without a CIGAR or with FLAG 0x4
+//     (sam_parse1 takes a span of 1 for an unmapped record whatever its CIGAR, htslib sam.c:1270-1278),
 //   * sequence as 4-bit codes of "=ACMGRSVTWYHKDBN", qualities as phred (text - 33), '*' -> 0xff.
 // Byte-identity with htslib's BGZF blocks is not claimed (block boundaries and deflate output depend on the
-// zlib build); the records inside are what the specification prescribes.  tests/test_aln_gpu.py decodes the
-// BAM with an independent reader and compares it with the SAM text of the same run.
+// zlib build); the decompressed stream is pinned byte for byte against the reference's own htslib output
+// (tests/golden/<set>/<reads>.bam, written by bam_hdr_write / bam_write1: tests/test_bam_golden.py, tests/test_aln_gpu.py).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -52,6 +53,7 @@ class BgzfWriter {
 	int device_ = -1;                             // >= 0: BGZF members come from psvr_bgzf_compress on that device
 	uint8_t *pin_in_ = nullptr, *pin_out_ = nullptr;   // page-locked: the records of a batch, its members
 	size_t pin_n_ = 0, pin_out_cap_ = 0;
+	size_t gather_blocks_;                        // blocks of records gathered in page-locked memory per device call
 	// one member: gzip header with the BC extra field, raw deflate, CRC32, ISIZE (SAMv1 4.1); returns the member size
 	static size_t compress_block(const uint8_t *p, size_t n, uint8_t *out, int level = Z_DEFAULT_COMPRESSION)
 	{
@@ -132,6 +134,7 @@ private:
 		}
 	}
 public:
+	explicit BgzfWriter(size_t gather_blocks = 3072) : gather_blocks_(gather_blocks < 1 ? 1 : gather_blocks) {}
 	bool open(const char *fn, int threads = 1, int level = Z_DEFAULT_COMPRESSION) { f_ = fopen(fn, "wb"); threads_ = threads; level_ = level; return f_ != nullptr; }
 	// compress on HIP device `d` (psvr_bgzf_compress: a lane per block; the members decode like any other, their bytes are not zlib's)
 	void set_device(int d) { device_ = d; }
@@ -142,23 +145,25 @@ public:
 		if (device_ >= 0) {
 			// the records gather in page-locked memory (the transfer starts from where they lie: out of pageable memory the runtime copies
 			// them once more), whole batches go to the device, what is left at close() to the host's zlib
-			const size_t cap = kBlock * (size_t)3072;
+			const size_t cap = kBlock * gather_blocks_;
 			if (!pin_in_ && !(pin_in_ = (uint8_t *)psvr_host_alloc(cap))) { device_ = -1; }
 			else {
 				if (!buf_.empty()) { std::vector<uint8_t> first; first.swap(buf_); write(first.data(), first.size()); }   // (what was written before set_device: the BAM header)
-				while (n) {
+				while (n && device_ >= 0) {                   // (a failed device call turns device_ off: the rest of this call goes the host's way)
 					const size_t m = cap - pin_n_ < n ? cap - pin_n_ : n;
 					memcpy(pin_in_ + pin_n_, b, m), pin_n_ += m, b += m, n -= m;
 					if (pin_n_ == cap) flush_blocks(pin_in_, pin_n_), pin_n_ = 0;
 				}
-				return;
+				if (!n) return;
 			}
 		}
+		// records gathered for the device and not yet sent come before anything written from here on
+		if (pin_n_) buf_.insert(buf_.end(), pin_in_, pin_in_ + pin_n_), pin_n_ = 0;
 #endif
 		buf_.insert(buf_.end(), b, b + n);
 		// enough whole blocks to keep every thread busy; on the device a call lasts as long as ONE block takes a lane (tens of ms) however
 		// many blocks it holds, so the batches are large
-		const size_t batch = device_ >= 0 ? kBlock * (size_t)3072 : kBlock * (size_t)(threads_ < 1 ? 1 : threads_) * 8;
+		const size_t batch = device_ >= 0 ? kBlock * gather_blocks_ : kBlock * (size_t)(threads_ < 1 ? 1 : threads_) * 8;
 		if (buf_.size() < batch) return;
 		const size_t whole = buf_.size() / kBlock * kBlock;
 		flush_blocks(buf_.data(), whole);
@@ -217,6 +222,9 @@ struct SamFields {
 
 class BamWriter {
 	BgzfWriter z_;
+public:
+	explicit BamWriter(size_t gather_blocks = 3072) : z_(gather_blocks) {}      // gather_blocks: BgzfWriter's, per device call
+private:
 	template <class V> static void put32(V &v, uint32_t x) { for (int i = 0; i < 4; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
 	template <class V> static void put16(V &v, uint16_t x) { v.push_back((uint8_t)x), v.push_back((uint8_t)(x >> 8)); }
 	static int reg2bin(int64_t beg, int64_t end)             // SAMv1 section 5.3
@@ -307,7 +315,7 @@ public:
 			for (char ch : s.cigar) {
 				if (ch == '-') { neg = true; continue; }
 				if (ch >= '0' && ch <= '9') { n = n * 10 + (ch - '0'); continue; }
-				const char *ops = "MIDNSHP=X", *q = strchr(ops, ch);
+				const char *ops = "MIDNSHP=XB", *q = strchr(ops, ch);       // BAM_CIGAR_STR
 				if (!q) return false;
 				if (neg) n = -n;
 				const int op = (int)(q - ops);
@@ -322,7 +330,8 @@ public:
 		put32(rec_, 0);                                             // block_size, patched below
 		put32(rec_, (uint32_t)s.tid), put32(rec_, (uint32_t)(int32_t)pos0);
 		rec_.push_back((uint8_t)(s.qname.size() + 1)), rec_.push_back((uint8_t)s.mapq);
-		put16(rec_, (uint16_t)reg2bin(pos0 < 0 ? 0 : pos0, (pos0 < 0 ? 0 : pos0) + (rlen > 0 ? rlen : 1)));
+		const bool has_cigar = !s.cigar.empty() && s.cigar != "*";
+		put16(rec_, (uint16_t)reg2bin(pos0 < 0 ? 0 : pos0, (pos0 < 0 ? 0 : pos0) + (has_cigar && !(s.flag & 0x4) ? rlen : 1)));
 		if (cig.size() > 0xffff) { rec_.resize(base); return false; }     // n_cigar_op is 16 bits (no CG:B long-CIGAR tag is written)
 		put16(rec_, (uint16_t)cig.size()), put16(rec_, (uint16_t)s.flag);
 		put32(rec_, l_seq);

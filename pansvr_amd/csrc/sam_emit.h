@@ -235,10 +235,17 @@ private:
 		put(d, b + n, (size_t)(24 - n));
 	}
 	static void put_tag_int(Bytes &d, const char *tag5, long long v) { put(d, "\t", 1), put(d, tag5, 5), put_int(d, v); }
+	// an operator nibble beyond 'B' has no letter: printed as '?', which acceptable_cigar refuses as sam_parse1 does
+	static char cigar_op_char(uint32_t w) { return (w & 0xf) <= 9 ? "MIDNSHP=XB"[w & 0xf] : '?'; }
+	static bool cigar_ops_known(const psvr_cand_t &c, const uint32_t *cig)
+	{
+		for (uint32_t j = 0; j < c.n_cigar; ++j) if ((cig[c.cigar_off + j] & 0xf) > 9) return false;
+		return true;
+	}
 	static void cigar_text(const psvr_cand_t &c, const uint32_t *cig, std::string &s)
 	{
 		char b[32];
-		for (uint32_t j = 0; j < c.n_cigar; ++j) { const uint32_t w = cig[c.cigar_off + j]; const int n = snprintf(b, sizeof b, "%d%c", (int)(int16_t)(w >> 4), "MIDNSHP=XB"[w & 0xf]); s.append(b, (size_t)n); }
+		for (uint32_t j = 0; j < c.n_cigar; ++j) { const uint32_t w = cig[c.cigar_off + j]; const int n = snprintf(b, sizeof b, "%d%c", (int)(int16_t)(w >> 4), cigar_op_char(w)); s.append(b, (size_t)n); }
 	}
 	void drop(const char *what) const
 	{
@@ -276,6 +283,7 @@ private:
 		if (chr_id < 0 || chr_id >= (int)H->names.size()) return false;   // target_name[] would be indexed out of range in the reference
 		if (pos - 1 < 0) return false;                             // "mapped query cannot have zero coordinate; treated as unmapped" -> tid = -1 -> not written
 		if (!acceptable(name, cigar, seq, qual)) { drop(err_line); return false; }
+		if (cigar.empty() || cigar == "*") flag |= 0x4;              // "mapped query must have a CIGAR; treated as unmapped" (sets BAM_FUNMAP)
 		const char *rnext = "*";
 		long pnext = 0;
 		int mtid = -1;
@@ -442,7 +450,7 @@ public:
 				B.qual(r, qt, qn), B.name(r, nt, nn), B.comment(r, ct, cn);
 				const int pos = (int)ref_bg;
 				if (chr_id < 0 || chr_id >= (int)H->names.size() || pos - 1 < 0) continue;
-				if (nn <= 0 || nn > 254 || qn != read_l) { drop("@sam_parse1 ERROR"); continue; }
+				if (nn <= 0 || nn > 254 || qn != read_l || (pcd && !cigar_ops_known(*pcd, V.cig))) { drop("@sam_parse1 ERROR"); continue; }
 				const char *svs = sv->print_string(rr.prim_sv_id);
 				const char *mvs = rr.has_mate ? sv->print_string(rr.mate_sv_id) : nullptr;
 				const psvr_cand_t *sc = rr.secondary >= 0 ? &V.cands[rr.cand_off + rr.secondary] : nullptr;
@@ -454,7 +462,7 @@ public:
 				o.put(nt, (size_t)nn), o.ch('\t'), o.num(flag), o.ch('\t');
 				o.put(rn), o.ch('\t'), o.num(pos), o.ch('\t'), o.num(mapq), o.ch('\t');
 				if (pcd && pcd->n_cigar) {
-					for (uint32_t j = 0; j < pcd->n_cigar; ++j) { const uint32_t w = V.cig[pcd->cigar_off + j]; o.num((int)(int16_t)(w >> 4)), o.ch("MIDNSHP=XB"[w & 0xf]); }
+					for (uint32_t j = 0; j < pcd->n_cigar; ++j) { const uint32_t w = V.cig[pcd->cigar_off + j]; o.num((int)(int16_t)(w >> 4)), o.ch(cigar_op_char(w)); }
 				} else if (cg.empty()) o.ch('*'); else o.put(cg);
 				o.ch('\t');
 				if (rr.has_mate) {
@@ -544,7 +552,7 @@ public:
 					}
 					{
 						const int64_t p0 = pos - 1;
-						const int bin = bam_reg2bin(p0, p0 + (rlen > 0 ? rlen : 1));
+						const int bin = bam_reg2bin(p0, p0 + (flag & 0x4 ? 1 : rlen));      // sam_parse1's span: the CIGAR's, 1 when FLAG has 0x4
 						bin_at[0] = (uint8_t)bin, bin_at[1] = (uint8_t)(bin >> 8);
 					}
 					// SEQ: two 4-bit codes per byte; QUAL: phred values (the reverse strand through getReverseStr_char / getReverseStr_qual_char)
@@ -688,7 +696,8 @@ public:
 				const int mp = orr[k].mate_pos, mc = orr[k].mate_chr;
 				const bool mate_named = mc >= 0 && mc < (int)H->names.size();
 				RawOut o(dst, (size_t)nn + 2 * (size_t)n + orr[k].cigar.size() + orr[k].tags.size() + H->names[(size_t)chr_id].size() + (mate_named ? H->names[(size_t)mc].size() : 0) + 256);
-				o.put(nt, (size_t)nn), o.ch('\t'), o.num(orr[k].flag), o.ch('\t'), o.put(H->names[(size_t)chr_id]), o.ch('\t');
+				const int flag = orr[k].cigar.empty() || orr[k].cigar == "*" ? orr[k].flag | 0x4 : orr[k].flag;     // (emit: no CIGAR sets BAM_FUNMAP)
+				o.put(nt, (size_t)nn), o.ch('\t'), o.num(flag), o.ch('\t'), o.put(H->names[(size_t)chr_id]), o.ch('\t');
 				o.num(pos), o.ch('\t'), o.num(orr[k].mapq), o.ch('\t');
 				if (orr[k].cigar.empty()) o.ch('*'); else o.put(orr[k].cigar);
 				o.ch('\t');

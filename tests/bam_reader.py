@@ -4,7 +4,7 @@ import gzip
 import struct
 
 NT16 = "=ACMGRSVTWYHKDBN"
-CIGAR_OPS = "MIDNSHP=X"
+CIGAR_OPS = "MIDNSHP=XB"
 
 
 def check_bgzf(path):
@@ -26,7 +26,8 @@ def check_bgzf(path):
 
 
 def read_bam(path, check_bin=True):
-    """Returns (header_text, [(name, length)], [sam_line_fields]).  check_bin: the stored bin must be reg2bin of the record's interval."""
+    """Returns (header_text, [(name, length)], [sam_line_fields]).  check_bin: the stored bin must be reg2bin of the record's interval
+    (sam_parse1's rule: the span is 1 for a record without a CIGAR or with FLAG 0x4)."""
     raw = gzip.open(path, "rb").read()
     assert raw[:4] == b"BAM\x01"
     l_text = struct.unpack_from("<i", raw, 4)[0]
@@ -81,8 +82,8 @@ def read_bam(path, check_bin=True):
         rname = refs[tid][0] if tid >= 0 else "*"
         rnext = "*" if mtid < 0 else ("=" if mtid == tid else refs[mtid][0])
         cigar = "".join("%d%s" % (c >> 4, CIGAR_OPS[c & 15]) for c in cig) or "*"
-        # reg2bin of the record's own interval (section 5.3)
-        rlen = sum(c >> 4 for c in cig if (c & 15) in (0, 2, 3, 7, 8)) or 1
+        # reg2bin of the record's interval as htslib's sam_parse1 takes it: the CIGAR's reference length, 1 without a CIGAR or when FLAG has 0x4
+        rlen = 1 if flag & 0x4 or not cig else sum(c >> 4 for c in cig if (c & 15) in (0, 2, 3, 7, 8))
         assert not check_bin or bin_ == reg2bin(max(pos, 0), max(pos, 0) + rlen), (bin_, pos, rlen)
         recs.append([qname, str(flag), rname, str(pos + 1), str(mapq), cigar, rnext, str(mpos + 1), str(tlen), seq or "*", qual] + tags)
     return text, refs, recs

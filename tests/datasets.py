@@ -9,7 +9,10 @@ DATASETS = {
     "fx1": dict(anchors=dict(n_anchors=20, seed=7), reads={"reads150": dict(n_pairs=2000, seed=13),
                                                             # reads of the first three anchors, the FIRST included: the one the reference attributes to
                                                             # its neighbour (calloc'ed chr_file_n) -- reproduced, and pinned here
-                                                            "anchor0": dict(n_pairs=400, seed=77, anchors=(0, 3))}),
+                                                            "anchor0": dict(n_pairs=400, seed=77, anchors=(0, 3)),
+                                                            # ordinary pairs, then pairs for the second file whose comments hit the corners of
+                                                            # htslib's text -> BAM record conversion (synth.make_crafted_reads)
+                                                            "crafted": dict(kind="crafted", n_pairs=60, seed=91)}),
     # tie-breaks / STR / N bases / 250 bp: duplicated flanks and tandem-repeat alleles
     "fx2": dict(anchors=dict(n_anchors=30, seed=21, edge=600, allele=(60, 400), str_frac=0.2, dup_frac=0.3),
                 reads={"reads150": dict(n_pairs=1500, seed=23, str_frac=0.05, n_frac=0.05),
@@ -58,6 +61,8 @@ def reads_of(name, rname):
         return synth.make_sparse_long_reads(a[lo:hi], **kw)
     if kind == "clamp0":
         return synth.make_clamp0_reads(a, **kw)
+    if kind == "crafted":
+        return synth.make_crafted_reads(a[lo:hi], **kw)
     return synth.make_reads(a[lo:hi], **kw)
 
 

@@ -9,7 +9,11 @@
 // With --sam / --ori-sam it also runs the PRODUCT's host-side formatter (pansvr_amd/csrc/sam_emit.h, fastq_batch.h) over these
 // results, so the SAM text can be compared with the reference's own files without a GPU.
 //
-// Usage: emu_aln <fixture_index_dir> <reads.fq> <header.sam> [--trace] [--batch N] [--sam FILE --ori-sam FILE] [--threads N]
+// With --bam / --ori-bam (next to --sam / --ori-sam) the two files are written once more as whole BAM files through the product's
+// BamWriter (header, records of the direct encoder -- or of BamWriter::encode with --bam-via-text -- and BGZF), as `panSVR aln` does.
+//
+// Usage: emu_aln <fixture_index_dir> <reads.fq> <header.sam> [--trace] [--batch N] [--sam FILE --ori-sam FILE [--bam FILE --ori-bam FILE]]
+//                [--threads N]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -218,7 +222,7 @@ int main(int argc, char **argv)
 	bool trace = false, quiet = false, not_ori = false, sig_n = false, sig_d = false, sig_u = false;
 	long long batch = 1 << 20;
 	int threads = 1;
-	const char *sam_fn = nullptr, *ori_fn = nullptr, *bam_fn = nullptr;
+	const char *sam_fn = nullptr, *ori_fn = nullptr, *bam_fn = nullptr, *bam_out = nullptr, *bam_ori_out = nullptr;
 	bool bam_text = false;
 	int format_reps = 0;
 	long long pos[3] = {-1, -1, -1}, from[3] = {-1, -1, -1};
@@ -233,6 +237,8 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--threads") && i + 1 < argc) threads = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "--sam") && i + 1 < argc) sam_fn = argv[++i];
 		else if (!strcmp(argv[i], "--ori-sam") && i + 1 < argc) ori_fn = argv[++i];
+		else if (!strcmp(argv[i], "--bam") && i + 1 < argc) bam_out = argv[++i];                 // both files as BAM through BamWriter (needs --sam / --ori-sam)
+		else if (!strcmp(argv[i], "--ori-bam") && i + 1 < argc) bam_ori_out = argv[++i];
 		else if (!strcmp(argv[i], "--bam-records") && i + 1 < argc) bam_fn = argv[++i];      // the main file's records as BAM bytes (uncompressed, no header): direct encoder
 		else if (!strcmp(argv[i], "--format-reps") && i + 1 < argc) format_reps = atoi(argv[++i]);   // host stages timed on one thread: the batch formatted this many times (stderr)
 		else if (!strcmp(argv[i], "--bam-via-text")) bam_text = true;                          // ... through the SAM-line strings and BamWriter::encode instead
@@ -284,6 +290,13 @@ int main(int argc, char **argv)
 		if (!fsam || !fori) { fprintf(stderr, "cannot open the SAM outputs\n"); return 2; }
 		fputs(H.text.c_str(), fsam), fputs(H.text.c_str(), fori);
 		em.H = &H, em.sv = &svn, em.not_ori = not_ori;
+	}
+	BamWriter bw[2];
+	const bool whole_bam = bam_out && bam_ori_out && fsam;
+	if (whole_bam) {
+		std::vector<BamRef> refs;
+		for (size_t i = 0; i < H.names.size(); ++i) refs.push_back({H.names[i], H.lens[i]});
+		if (!bw[0].open(bam_out, H.text, refs) || !bw[1].open(bam_ori_out, H.text, refs)) { fprintf(stderr, "cannot open the BAM outputs\n"); return 2; }
 	}
 	bool first = true;
 	long long pair_base = 0;
@@ -337,6 +350,13 @@ int main(int argc, char **argv)
 				for (long long p = 0; p < fb.n_pairs(); ++p) eb.main_pair(fb, V, p, m);
 				fwrite(m.data(), 1, m.size(), fbam);
 			}
+			if (whole_bam) {
+				SamEmitter eb = em;
+				eb.as_bam = true, eb.bam_via_text = bam_text;
+				Bytes m, o;
+				for (long long p = 0; p < fb.n_pairs(); ++p) eb.main_pair(fb, V, p, m), eb.ori_pair(fb, V, p, o);
+				bw[0].write_raw(m.data(), m.size()), bw[1].write_raw(o.data(), o.size());
+			}
 		}
 		core.commit();
 		fprintf(stderr, "[emu] stream_end %lld %lld %lld\n", core.grand_pos, core.hrand_pos[0], core.hrand_pos[1]);
@@ -347,6 +367,7 @@ int main(int argc, char **argv)
 	}
 	if (fsam) fclose(fsam), fclose(fori);
 	if (fbam) fclose(fbam);
+	if (whole_bam && (!bw[0].close() || !bw[1].close())) { fprintf(stderr, "cannot write the BAM outputs\n"); return 2; }
 	feed.abort();
 	if (sig_thread.joinable()) sig_thread.join();
 	if (sig_rc) { fprintf(stderr, "the signal step failed\n"); return 4; }

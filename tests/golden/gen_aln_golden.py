@@ -9,6 +9,10 @@ with the reference deBGA (-k 22), run ref_aln --trace, and commit
     tests/golden/<name>/<reads>.jsonl.gz   one record per read pair, as printed by the reference objects
     tests/golden/<name>/<reads>.sam.gz, <reads>.ori.sam.gz   the two output files of `fc_aln -t 1 -S` (the reference's own
                                            output_BAM / output_ori_bam -> sam_parse1 -> sam_format1 text)
+    tests/golden/<name>/<reads>.bam, <reads>.ori.bam         the same two files as `fc_aln -t 1` writes them by default: BAM, through
+                                           htslib's bam_hdr_write / bam_write1 / BGZF (ref_aln --bam), committed as written
+and for the `-Q` sets <reads>.notori.{sam.gz,ori.sam.gz,bam,ori.bam}.  The BGZF blocks depend on the zlib that wrote them; tests compare
+the decompressed streams.  --only-bam writes the .bam files alone (the other fixtures stay as committed).
 """
 import gzip
 import os
@@ -37,7 +41,13 @@ def score_tag(s):
     return "score_" + "_".join(str(x) for x in s)
 
 
-def main(names, only_not_ori=False):
+def ref_bam(idx, work, rname, out_main, out_ori, extra=()):
+    """the reference's two BAM files of `fc_aln -t 1` (init_run's hts_open "wb" -> sam_write1 -> bam_write1)"""
+    subprocess.run([os.path.join(REF, "ref_aln"), "-t", "1", "--bam"] + list(extra) + ["-o", out_main, "-p", out_ori, idx, os.path.join(work, rname + ".fq"),
+                    os.path.join(work, "header.sam")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+
+
+def main(names, only_not_ori=False, only_bam=False):
     for name in names:
         ds = datasets.DATASETS[name]
         work = os.environ.get("PSVR_GOLDEN_WORK", tempfile.mkdtemp(prefix="psvr_" + name))
@@ -50,7 +60,7 @@ def main(names, only_not_ori=False):
                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         out = os.path.join(HERE, name)
         os.makedirs(out, exist_ok=True)
-        if only_not_ori:
+        if only_not_ori or only_bam:
             pass
         elif ds.get("index") == "sha256":
             # too large to commit: the compact form's SHA-256 per file; tests rebuild the index with `panSVR index` and compare
@@ -63,6 +73,9 @@ def main(names, only_not_ori=False):
         else:
             index_fixture.compact(idx, os.path.join(out, "idx"))
         for rname in ([] if only_not_ori else ds["reads"]):
+            ref_bam(idx, work, rname, os.path.join(out, rname + ".bam"), os.path.join(out, rname + ".ori.bam"))
+            if only_bam:
+                continue
             sam, ori, rec = (os.path.join(work, rname + e) for e in (".ref.sam", ".ref.ori.sam", ".ref.jsonl"))
             subprocess.run([os.path.join(REF, "ref_aln"), "-t", "1", "-S", "-o", sam, "-p", ori, idx, os.path.join(work, rname + ".fq"), os.path.join(work, "header.sam"),
                             "--trace", "--records", rec], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
@@ -78,6 +91,9 @@ def main(names, only_not_ori=False):
         for sname, rname in NOT_ORI_SETS:
             if sname != name:
                 continue
+            ref_bam(idx, work, rname, os.path.join(out, rname + ".notori.bam"), os.path.join(out, rname + ".notori.ori.bam"), ["-Q"])
+            if only_bam:
+                continue
             sam, ori = (os.path.join(work, rname + e) for e in (".refQ.sam", ".refQ.ori.sam"))
             subprocess.run([os.path.join(REF, "ref_aln"), "-t", "1", "-S", "-Q", "-o", sam, "-p", ori, idx, os.path.join(work, rname + ".fq"), os.path.join(work, "header.sam")],
                            stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
@@ -86,7 +102,7 @@ def main(names, only_not_ori=False):
                     f.write(open(src, "rb").read())
             print(name, rname, "-Q", os.path.getsize(sam), "B sam", os.path.getsize(ori), "B ori sam")
         for sname, rname, sc in SCORE_SETS:
-            if sname != name or only_not_ori:
+            if sname != name or only_not_ori or only_bam:
                 continue
             rec = os.path.join(work, rname + "." + score_tag(sc) + ".jsonl")
             M, m, O, E, P, F, z = sc
@@ -100,5 +116,5 @@ def main(names, only_not_ori=False):
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a != "--only-not-ori"]      # --only-not-ori: just the -Q files (the other fixtures stay as committed)
-    main(argv or list(datasets.DATASETS), only_not_ori="--only-not-ori" in sys.argv[1:])
+    argv = [a for a in sys.argv[1:] if a not in ("--only-not-ori", "--only-bam")]      # --only-not-ori: just the -Q files (the other fixtures stay as committed)
+    main(argv or list(datasets.DATASETS), only_not_ori="--only-not-ori" in sys.argv[1:], only_bam="--only-bam" in sys.argv[1:])

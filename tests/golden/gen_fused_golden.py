@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Regenerates tests/golden/fused/*.sam.gz: what the REFERENCE's two steps make of a BAM -- `fc_signal`'s per-pair function
+"""Regenerates tests/golden/fused/*.sam.gz and *.bam: what the REFERENCE's two steps make of a BAM -- `fc_signal`'s per-pair function
 (READ_SIGNAL_HANDLER::all_signal_records_read_pair through oracle/_ref/ref_signal) writes the FASTQ, the reference's `fc_aln`
 objects (oracle/_ref/ref_aln -t 1 -S) align it -- for the BAM tests/test_fused_signal.bam_of builds from a golden read set.
-`panSVR aln x.bam` (the fused route of this repo) must write these bytes.  BUILD CONTAINER ONLY.
+`panSVR aln x.bam` (the fused route of this repo) must write these bytes; the .bam / .ori.bam files are the same run's default output
+(ref_aln --bam: htslib's bam_hdr_write / bam_write1), of which the decompressed streams are compared.  BUILD CONTAINER ONLY.
 The STAT_ numbers are the ones `panSVR signal` reports for the file (the reference takes them from htslib's file layer)."""
 import gzip
 import os
@@ -47,6 +48,9 @@ def main():
             os.symlink(os.path.join(src, fn), os.path.join(idx, fn))
         index_fixture.expand_hash(src).tofile(os.path.join(idx, "unipath_g.hash"))
         subprocess.run([os.path.join(ROOT, "oracle", "_ref", "ref_aln"), "-t", "1", "-S", "-o", os.path.join(tmp, "o.sam"), "-p", os.path.join(tmp, "p.sam"), idx, fq, os.path.join(tmp, "h.sam"), "--quiet"],
+                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
+        subprocess.run([os.path.join(ROOT, "oracle", "_ref", "ref_aln"), "-t", "1", "--bam", "-o", os.path.join(out_dir, "%s_%s.bam" % (name, rname)),
+                        "-p", os.path.join(out_dir, "%s_%s.ori.bam" % (name, rname)), idx, fq, os.path.join(tmp, "h.sam"), "--quiet"],
                        stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
         os.remove(os.path.join(idx, "unipath_g.hash"))
         for src_fn, ext in (("o.sam", ".sam.gz"), ("p.sam", ".ori.sam.gz")):

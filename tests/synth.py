@@ -280,3 +280,42 @@ def write_fastq(path, recs):
     with open(path, "w") as f:
         for name, c, s, q in recs:
             f.write("@%s %s\n%s\n+\n%s\n" % (name, c, s, q))
+
+
+# integer tags at every boundary of sam_parse1's type choice (c/C/s/S/i/I)
+INT_TAG_EDGES = (-129, -128, 127, 128, 255, 256, 65535, 65536, -32769, -32768, 0, -1)
+
+
+def make_crafted_reads(anchors, n_pairs, seed, stat=(150, 200, 400, 600)):
+    """Ordinary pairs (make_reads) followed by pairs that no anchor explains: random bases, so they score nothing and land in the
+    second output file, whose records copy FLAG, CIGAR, mate and tags from the comment (output_ori_bam, read_realignment.cpp:656-717).
+    Their comments aim at the corners of htslib's sam_parse1 -> BAM record: FLAG 0x4 with a CIGAR close to a 16 kb bin boundary,
+    the `B`, `=`, `X` and `P` operators, integer tags at every type boundary, odd and even lengths on both strands, a mate on another
+    contig, query names of every length modulo 4.  The two reads of a pair sit on different contigs, so that the pair is not properly
+    mated and both records are written.  Every CIGAR's query length equals its read's length and no length is negative: sam_parse1
+    refuses such a record, and the reference still writes what it had parsed up to the error (read_realignment.cpp:713-714)."""
+    rng = np.random.RandomState(seed)
+    recs = make_reads(anchors, n_pairs, seed=seed, stat=stat)
+    tags = "_".join("X%s:i:%d" % ("0123456789ab"[i], v) for i, v in enumerate(INT_TAG_EDGES))
+    # (tid, pos0, flag, cigar, read length) per record, two per pair; each record's mate is the other one
+    B = 1 << 14
+    pairs = [
+        ((0, B - 100, 0x45, "150M", 150), (7, B + 300, 0x99, "150M", 150)),                  # FLAG 0x4 with a CIGAR across 16 kb
+        ((1, 2 * B - 70, 0xb5, "100M1I50M", 151), (8, 2 * B - 400, 0x69, "101M", 101)),
+        ((0, 5 * B - 1, 0x45, "60M40S", 100), (9, 5 * B + 2000, 0x99, "60M5B40M", 100)),
+        ((2, 3000, 0x61, "70=1X79=", 150), (10, 3200, 0x91, "60M5B91M", 151)),
+        ((3, 9000, 0x61, "75M5P75M", 150), (11, 7000, 0x91, "20M3N81M", 101)),
+        ((5, 40000, 0x41, "", 150), (12, 40400, 0x81, "*", 151)),                            # no CIGAR
+        ((6, 123456, 0x51, "10S130M10S", 150), (13, 123000, 0xa1, "5S96M", 101)),
+    ]
+    names = ["c", "cx", "cxy", "cxyz", "cxyzw", "cxyzwv", "cxyzwvu"]
+    for p, pair in enumerate(pairs):
+        for k, (tid, pos, flag, cigar, L) in enumerate(pair):
+            mtid, mpos = pair[1 - k][:2]
+            isize = 0 if tid != mtid else (mpos - pos if k == 0 else pos - mpos)
+            seq = rand_dna(rng, L)
+            c = "%d_%d_40_140_20_20_0_0_%d_%sNNY_%sNNY_" % (tid, pos, abs(isize), "R" if flag & 0x10 else "F", "F" if flag & 0x10 else "R")
+            c += "FLAG_%d_%d_CIGAR_%s_MATE_%d_%d_%d_TAG_%s_Y%d:i:%d_" % (flag, 20 + p, cigar, mtid, mpos, isize, tags, k, INT_TAG_EDGES[(p + k) % len(INT_TAG_EDGES)])
+            qual = bytes(33 + rng.randint(2, 41, size=L).astype(np.uint8))
+            recs.append((names[p], c, seq.decode(), qual.decode()))
+    return recs

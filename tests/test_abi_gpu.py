@@ -281,3 +281,84 @@ def test_bgzf_members_from_the_device_decode_to_their_input():
         pos += bsize
     assert b"".join(back) == data and all(len(b) == blk for b in back[:-1]) and len(back[-1]) == 1
     assert stored >= 3 and got.value < 0.75 * len(data)              # the random bytes are stored, the rest is compressed
+
+
+def _device_members(data):
+    """psvr_bgzf_compress on device 0: the members, side by side"""
+    from pansvr_amd._lib import check, lib
+    L = lib()
+    L.psvr_bgzf_bound.restype = C.c_int64
+    L.psvr_bgzf_bound.argtypes = [C.c_int64]
+    cap = L.psvr_bgzf_bound(len(data))
+    out = C.create_string_buffer(cap)
+    got = C.c_int64(0)
+    check(L.psvr_bgzf_compress(0, data, C.c_int64(len(data)), out, C.c_int64(cap), C.byref(got)))
+    return out.raw[:got.value]
+
+
+def _member_inputs(blk):
+    """random bytes, zeros, BAM records, 2-bit text; lengths of k blocks and k blocks +- 1; one input of 100 blocks (the last
+    workgroup of 64 lanes only partly used)"""
+    import gzip
+    rng = np.random.RandomState(11)
+    bam = gzip.open(os.path.join(ac.golden_dir("fx1"), "reads150.bam"), "rb").read()
+    out = [("random", bytes(rng.randint(0, 256, size=3 * blk, dtype=np.uint8))), ("zeros", b"\0" * (5 * blk + 1)),
+           ("bam", bam[:7 * blk - 1]), ("acgt", bytes(rng.randint(0, 4, size=4 * blk + 1, dtype=np.uint8) * 2 + 65)),
+           ("one block", bam[:blk]), ("one byte", b"x"),
+           ("100 blocks", (bam * (100 * blk // len(bam) + 1))[:100 * blk - 5])]
+    return out
+
+
+def _host_members(tool, blk, data, tmp, tag):
+    import subprocess
+    src, dst = os.path.join(tmp, tag + ".in"), os.path.join(tmp, tag + ".host")
+    open(src, "wb").write(data)
+    subprocess.check_call([tool, "--members", str(blk), src, dst])
+    return open(dst, "rb").read()
+
+
+def _first_member_difference(dev, host):
+    import struct
+    pos, k = 0, 0
+    while pos < min(len(dev), len(host)):
+        a, b = (struct.unpack_from("<H", x, pos + 16)[0] + 1 for x in (dev, host))
+        if dev[pos:pos + a] != host[pos:pos + b]:
+            return "member %d (byte %d): %d bytes on the device, %d from the host encoder" % (k, pos, a, b)
+        pos, k = pos + a, k + 1
+    return "%d vs %d bytes" % (len(dev), len(host))
+
+
+@pytest.fixture(scope="module")
+def deflate_tool():
+    import subprocess
+    import tempfile
+    exe = os.path.join(tempfile.mkdtemp(prefix="psvr_dmem_"), "deflate_check")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ac.HERE, "tools", "deflate_check.cpp"), "-lz"])
+    return exe
+
+
+def test_bgzf_device_members_equal_the_host_encoders(deflate_tool):
+    """k_bgzf_deflate runs deflate_device.h's encoder a lane per block with its tables in LDS; the same encoder compiled for the host
+    (tests/tools/deflate_check --members: 9 hash bits, the same output bound, zlib's CRC32) is an exact reference: every member must be
+    the same bytes.  A defect that only spoils the tables (lanes' tables overlapping, fewer hash bits) still inflates; only this sees it.
+    Default block size (16 KB) in this process; 1000 bytes (blocks not 16-byte aligned for the CRC loads) and 0xff00 (the largest legal
+    block) in fresh processes, since PSVR_BGZF_BLOCK is read once per process."""
+    import subprocess
+    import sys
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="psvr_dmem_")
+    for tag, data in _member_inputs(16384):
+        dev = _device_members(data)
+        host = _host_members(deflate_tool, 16384, data, tmp, tag)
+        assert dev == host, "%s, %d bytes: %s" % (tag, len(data), _first_member_difference(dev, host))
+    child = ("import sys; sys.path[:0] = [%r, %r]; import test_abi_gpu as t\n"
+             "for tag, data in t._member_inputs(int(sys.argv[1])): open(sys.argv[2] + '/' + tag + '.dev', 'wb').write(t._device_members(data))") % (ac.HERE, ac.ROOT)
+    for blk in (1000, 0xff00):
+        d = os.path.join(tmp, str(blk))
+        os.makedirs(d)
+        r = subprocess.run([sys.executable, "-c", child, str(blk), d], env=dict(os.environ, PSVR_BGZF_BLOCK=str(blk)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, "PSVR_BGZF_BLOCK=%d: exit %d\n%s" % (blk, r.returncode, r.stderr.decode()[-1500:])
+        for tag, data in _member_inputs(blk):
+            dev = open(os.path.join(d, tag + ".dev"), "rb").read()
+            host = _host_members(deflate_tool, blk, data, d, tag)
+            assert dev == host, "PSVR_BGZF_BLOCK=%d, %s, %d bytes: %s" % (blk, tag, len(data), _first_member_difference(dev, host))

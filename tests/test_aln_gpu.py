@@ -99,6 +99,42 @@ def test_gpu_cli_bam_output_equals_sam_text():
             assert a == b, "\nsam: %s\nbam: %s" % ("\t".join(a), "\t".join(b))
 
 
+def _cli_bam(name, rname, extra=(), env=None):
+    w = ac.workdir(name)
+    tmp = tempfile.mkdtemp(prefix="psvr_gbam_")
+    out = [os.path.join(tmp, "out.bam"), os.path.join(tmp, "ori.bam")]
+    r = subprocess.run([CLI, "aln"] + list(extra) + ["-o", out[0], "-p", out[1], ac.index_dir(name), os.path.join(w, rname + ".fq"), os.path.join(w, "header.sam")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, **(env or {})))
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert "BGZF on the device failed" not in r.stderr.decode()
+    return out
+
+
+def _check_against_bam_goldens(out, name, stem):
+    """both files' decompressed streams == the reference's BAM files (htslib's bam_hdr_write / bam_write1), record byte for record byte"""
+    import bam_reader
+    import bam_stream
+    for got, ext in zip(out, (".bam", ".ori.bam")):
+        bam_reader.check_bgzf(got)
+        diff = bam_stream.first_difference(bam_stream.stream(got), bam_stream.stream(os.path.join(ac.golden_dir(name), stem + ext)))
+        assert diff is None, "%s%s: %s" % (stem, ext, diff)
+
+
+@pytest.mark.parametrize("name,rname", CASES)
+def test_gpu_cli_bam_matches_the_reference_bam_files(name, rname):
+    """`panSVR aln` with its default output (BAM) == the reference's `fc_aln -t 1` BAM files (tests/golden/<set>/<reads>.bam, .ori.bam)"""
+    _check_against_bam_goldens(_cli_bam(name, rname), name, rname)
+
+
+@pytest.mark.parametrize("route,extra,env", [("level1", ["--compress-level", "1"], None), ("fast4", ["--bgzf-fast", "-t", "4"], None), ("t1", ["-t", "1"], None),
+                                             ("device", ["--bgzf-device"], {"PSVR_BGZF_DEVICE_MIN_BLOCKS": "1"}), ("notori", ["-Q"], None)])
+def test_gpu_cli_bam_encoder_routes_match_the_reference(route, extra, env):
+    """every route to the BGZF members -- zlib at another level, the built-in encoder on host threads, one thread, the device's
+    k_bgzf_deflate / k_bgzf_pack (--bgzf-device) -- and -Q give the decompressed stream of the reference's files"""
+    name, rname = "fx2", "reads150"
+    _check_against_bam_goldens(_cli_bam(name, rname, extra, env), name, rname + (".notori" if route == "notori" else ""))
+
+
 @pytest.mark.parametrize("score", [(3, 9, 12, 2, 24, 1, 200), (1, 4, 6, 1, 20, 0, 50), (2, 30, 40, 3, 60, 2, 400)])
 def test_gpu_cli_scoring_options_match_reference(score):
     """-M -m -O -E -P -F -z: the engine against what the REFERENCE's objects decided with the same options

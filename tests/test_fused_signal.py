@@ -139,3 +139,24 @@ def test_gpu_bam_input_writes_what_the_references_two_steps_write(name, rname, n
     want = _golden(name, rname)
     assert open(os.path.join(tmp, "o.sam"), "rb").read() == want[0]
     assert open(os.path.join(tmp, "p.sam"), "rb").read() == want[1]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,rname,n_pairs,flags", GOLDEN)
+def test_gpu_bam_input_writes_the_references_bam_files(name, rname, n_pairs, flags):
+    """The fused route with its default output: both BAM files' decompressed streams == the reference's `fc_aln -t 1` BAM files of the
+    same FASTQ (tests/golden/fused/*.bam, htslib's bam_hdr_write / bam_write1), record byte for record byte."""
+    import bam_reader
+    import bam_stream
+    tmp = tempfile.mkdtemp(prefix="psvr_fusedb_")
+    bam = os.path.join(tmp, "in.bam")
+    bam_of(name, rname, n_pairs, bam)
+    out = [os.path.join(tmp, "o.bam"), os.path.join(tmp, "p.bam")]
+    r = subprocess.run([CLI, "aln", "-N"] + flags + ["-o", out[0], "-p", out[1], ac.index_dir(name), bam, os.path.join(tmp, "h.sam")],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert r.returncode == 0, r.stderr.decode()[-1500:]
+    for got, ext in zip(out, (".bam", ".ori.bam")):
+        bam_reader.check_bgzf(got)
+        want = os.path.join(ac.HERE, "golden", "fused", "%s_%s%s" % (name, rname, ext))
+        diff = bam_stream.first_difference(bam_stream.stream(got), bam_stream.stream(want))
+        assert diff is None, "%s: %s" % (ext, diff)

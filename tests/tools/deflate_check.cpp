@@ -1,6 +1,8 @@
 // deflate_check.cpp -- the one-thread-per-block DEFLATE encoder of pansvr_amd/csrc/deflate_device.h, compiled for the host: every
 // 0xff00-byte block of the input files (and of a few synthetic buffers) is compressed and inflated again with zlib; prints the ratio.
 // usage: deflate_check [hash bits] [file ...]
+//        deflate_check --members <block bytes> <in> <out>: the BGZF members psvr_bgzf_compress must return for <in> (bgzf.hip: a member per
+//        <block bytes> of input, deflate_block with 9 hash bits into a slot of block + 64 bytes, CRC32 and ISIZE), written side by side
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -34,8 +36,41 @@ static bool check(const std::vector<uint8_t> &data, int hbits, const char *what)
 	return true;
 }
 
+// the members of k_bgzf_deflate, made on the host: same encoder, same hash bits, same output bound
+static int members(uint32_t blk, const char *in_fn, const char *out_fn)
+{
+	FILE *f = fopen(in_fn, "rb");
+	if (!f) return 2;
+	std::vector<uint8_t> v;
+	uint8_t buf[1 << 16];
+	size_t k;
+	while ((k = fread(buf, 1, sizeof buf, f)) > 0) v.insert(v.end(), buf, buf + k);
+	fclose(f);
+	if (blk < 256 || blk > kDfMaxIn) return 2;
+	const int hbits = 9;                                       // kBgzfHashBits
+	const uint32_t slot = blk + 64;
+	std::vector<uint8_t> fast(df_fast_bytes(hbits)), out(slot);
+	std::vector<uint32_t> tok(kDfMaxIn + 8);
+	FILE *o = fopen(out_fn, "wb");
+	if (!o) return 2;
+	for (size_t at = 0; at < v.size(); at += blk) {
+		const uint32_t n = (uint32_t)(v.size() - at < blk ? v.size() - at : blk);
+		const uint32_t c = deflate_block(v.data() + at, n, out.data() + 18, slot - 26, fast.data(), hbits, tok.data());
+		if (!c) return 3;
+		const uint32_t bsize = c + 18 + 8 - 1;
+		static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
+		memcpy(out.data(), hdr, 16);
+		out[16] = (uint8_t)bsize, out[17] = (uint8_t)(bsize >> 8);
+		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), v.data() + at, n);
+		for (int i = 0; i < 4; ++i) out[18 + c + i] = (uint8_t)(crc >> (8 * i)), out[18 + c + 4 + i] = (uint8_t)(n >> (8 * i));
+		if (fwrite(out.data(), 1, c + 26, o) != c + 26) return 2;
+	}
+	return fclose(o) == 0 ? 0 : 2;
+}
+
 int main(int argc, char **argv)
 {
+	if (argc == 5 && !strcmp(argv[1], "--members")) return members((uint32_t)atol(argv[2]), argv[3], argv[4]);
 	const int hbits = argc > 1 ? atoi(argv[1]) : 10;
 	bool ok = true;
 	srand(7);

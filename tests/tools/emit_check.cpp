@@ -1,7 +1,9 @@
 // emit_check.cpp -- TEST TOOL.  The record formatter's fast paths (pansvr_amd/csrc/sam_emit.h) against plain restatements:
 //   RawOut::num against snprintf("%lld"); put_seq_qual (16 bytes at a time) against the per-byte tables and getReverseStr_qual_char's
 //   loop; SamEmitter::parse_ori_record on a span against its sscanf / strstr version, on well-formed comments and on mutated ones
-//   (white space, signs, long digit runs, missing sections, NUL bytes).  Exit status 0 = every case agrees.
+//   (white space, signs, long digit runs, missing sections, NUL bytes); the CIGAR operator nibbles: the SAM path refuses a record with a
+//   nibble beyond 'B' (9), and the text the BAM path falls back to for it is one acceptable_cigar / BamWriter::encode refuse, so both
+//   output modes drop the same records.  Exit status 0 = every case agrees.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,6 +17,9 @@ struct EmitCheck {
 	typedef SamEmitter::OriRecord Rec;
 	static bool fast(const char *c, int n, Rec *r) { return SamEmitter::parse_ori_record(c, n, r); }
 	static bool slow(const std::string &c, Rec *r) { return SamEmitter::parse_ori_record(c, r); }
+	static bool ops_known(const psvr_cand_t &c, const uint32_t *cig) { return SamEmitter::cigar_ops_known(c, cig); }
+	static void cigar_text(const psvr_cand_t &c, const uint32_t *cig, std::string &s) { SamEmitter::cigar_text(c, cig, s); }
+	static bool acceptable_cigar(const std::string &s) { return SamEmitter::acceptable_cigar(s); }
 };
 }
 using namespace psvr;
@@ -120,6 +125,25 @@ int main()
 		thread_pool().run(6, [&](int t) { parallel_ranges(1000, 4, [&](long long a, long long b) { sum += (b - a) * (t + 1); }); });
 		++n_cases;
 		if (sum != 1000 * 21) { ++bad; fprintf(stderr, "nested pool calls: %lld\n", (long long)sum); }
+	}
+	// ---- CIGAR operator nibbles: 0-9 are "MIDNSHP=XB" in both modes, 10-15 make both modes drop the record
+	for (uint32_t op = 0; op < 16; ++op) {
+		const uint32_t cig[3] = {20u << 4, 7u << 4 | op, 30u << 4};
+		psvr_cand_t c;
+		memset(&c, 0, sizeof c);
+		c.n_cigar = 3, c.cigar_off = 0;
+		std::string text;
+		EmitCheck::cigar_text(c, cig, text);
+		SamFields f;
+		f.qname = "q", f.tid = 0, f.pos1 = 1, f.cigar = text, f.seq = "*", f.qual = "*";
+		Bytes rec;
+		const bool known = EmitCheck::ops_known(c, cig), text_ok = EmitCheck::acceptable_cigar(text), bam_ok = BamWriter::encode(f, rec);
+		++n_cases;
+		if (known != (op <= 9) || text_ok != known || bam_ok != known || (known && text != "20M7" + std::string(1, "MIDNSHP=XB"[op]) + "30M")) {
+			++bad;
+			fprintf(stderr, "CIGAR nibble %u: known %d, text %s accepted %d, encoded %d\n", op, (int)known, text.c_str(), (int)text_ok, (int)bam_ok);
+		}
+		if (bam_ok && (rec[4 + 32 + 2 + 4] & 0xf) != op) { ++bad; fprintf(stderr, "CIGAR nibble %u: encoded as %u\n", op, rec[4 + 32 + 2 + 4] & 0xf); }
 	}
 	printf("%lld cases, %lld differ\n", n_cases, bad);
 	return bad ? 1 : 0;
