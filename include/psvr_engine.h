@@ -92,6 +92,13 @@ static inline int64_t psvr_cigar_bound(int32_t qlen, int32_t tlen) { return (int
  * Host-buffer form: n independent problems; problem i has query  qseq[q_off[i] .. +qlen[i])  and
  * target tseq[t_off[i] .. +tlen[i]) with codes 0..m-1.  Results in ez[i]; CIGAR ops (BAM encoding
  * len<<4|op) in cigar_arena (capacity cigar_cap uint32).  Runs on HIP device `device`.
+ * Accepted domain: any 0 <= qlen, tlen < 2^28 (longer sequences: PSVR_ERR_UNSUPPORTED), bounded by device memory.
+ * A problem's workspace is its direction bytes, ((qlen + tlen - 1) * n_col + 1) * 16 bytes with
+ * n_col = (min(qlen, tlen, w + 1) + 15) / 16 + 1 (none under PSVR_EZ_SCORE_ONLY for sequences over 8000 bases),
+ * plus about 12 * tlen bytes when a sequence is longer than 8000 bases.  The batch runs in groups of
+ * consecutive problems whose workspace stays under min(4 GiB, half the free device memory); a problem
+ * larger than that runs alone, and if its workspace exceeds the free device memory the call returns
+ * PSVR_ERR_NOMEM with the byte count in psvr_last_error().
  */
 int psvr_extd2_batch(int device, int64_t n,
                      const uint8_t *qseq, const int64_t *q_off, const int32_t *qlen,
@@ -106,7 +113,7 @@ int psvr_extz2_batch(int device, int64_t n,
                      psvr_extz_t *ez, uint32_t *cigar_arena, int64_t cigar_cap);
 
 /*
- * Device-pointer form (all pointers are HIP device memory, `stream` is a hipStream_t or NULL):
+ * Device-pointer form (same domain; all pointers are HIP device memory, `stream` is a hipStream_t or NULL):
  * nothing is copied and nothing synchronises; `work` is a device workspace of at least
  * psvr_dp_plan_workspace_bytes(plan) bytes.  ez[i].cigar_off must be pre-set by the caller
  * (e.g. an exclusive scan of psvr_cigar_bound).  tools/dp_bench.py times this form; bench.py times

@@ -15,6 +15,8 @@
 //     keeps the reference's 16-lane block rounding of [st,en] bit for bit (lanes outside the band but inside the rounded
 //     block are computed and read back exactly as the SSE code does, 8-bit wrap included): needed when the band clips.
 //   * extd2_lds_kernel<VAR>  -- any shape and flag, and the single-affine extz2 variant: state in LDS in the reference's layout.
+//   * extd2_hbm_kernel<VAR>  -- the same recurrence for what LDS cannot hold (long sequences): the flat image and H in a per-problem
+//     HBM workspace, a workgroup of kDpHbmWaves wavefronts per alignment.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -56,6 +58,9 @@ static const int kDpWaves = 4;   // alignments (wavefronts) per workgroup of the
 template <int K, bool PG> __global__ void extd2_reg_kernel(DpBatch B, DpParams P);   // ksw_kernels.hip
 template <int K> __global__ void extd2_ring_kernel(DpBatch B, DpParams P);             // ksw_kernels.hip: the same sweep on a ring of 64 K columns that slides with the band
 template <int VAR> __global__ void extd2_lds_kernel(DpBatch B, DpParams P); // ksw_kernels.hip
+template <int K> __global__ void extd2_ring1_kernel(DpBatch B, DpParams P);            // ksw_kernels.hip: extd2_ring_kernel<K> with one wavefront per workgroup
+template <int VAR> __global__ void extd2_hbm_kernel(DpBatch B, DpParams P); // ksw_kernels.hip
+static const int kDpHbmWaves = 8;   // wavefronts per workgroup (= per alignment) of extd2_hbm_kernel
 __global__ void extd2_tiny_kernel(DpBatch B, DpParams P, int max_rows);        // ksw_kernels.hip
 // all size classes of the team kernel go out in ONE launch (a class alone rarely fills the chip): block b serves class c with
 // first_block[c] <= b < first_block[c + 1]; its alignments are idx[first_slot[c] + ...], count[c] of them
@@ -131,6 +136,11 @@ __host__ __device__ inline int dp_lds_kernel_need(int qlen, int tlen, int varian
 #define PSVR_DP_NUM_KINDS 15
 #define PSVR_DP_KIND_RING3 13          // extd2_ring_kernel<3>: any tlen, band (+ its 16-lane rounding) within 192 columns
 #define PSVR_DP_KIND_RING4 14          // extd2_ring_kernel<4>: ... within 256 columns
+// kinds only the host planner (ksw_host.hip) uses, for problems the kinds above cannot hold in LDS
+#define PSVR_DP_KIND_RING1_3 15        // extd2_ring1_kernel<3>: as RING3, one wavefront per workgroup (query + target image up to 160 KiB)
+#define PSVR_DP_KIND_RING1_4 16        // extd2_ring1_kernel<4>
+#define PSVR_DP_KIND_HBM 17            // extd2_hbm_kernel<VAR>: any shape, flag and variant
+#define PSVR_DP_NUM_HOST_KINDS 18
 // kinds whose direction bytes live in the HBM slab (DpBatch::pslab)
 __host__ __device__ inline bool dp_kind_uses_slab(int kind) { return kind == 0 || (kind > 5 && kind < PSVR_DP_KIND_TINY) || kind >= PSVR_DP_KIND_RING3; }
 // kind: 1..5 = extd2_reg_kernel<kind,false> (direction bytes in LDS), 6..10 = extd2_reg_kernel<kind-5,true> (in HBM), 13 / 14 = extd2_ring_kernel<3 / 4>,
@@ -169,6 +179,18 @@ __host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_
 	int g = dp_lds_kernel_need(qlen, tlen, variant);
 	*need = g;
 	return g <= PSVR_DP_MAX_LDS ? 0 : -1;
+}
+
+// extd2_hbm_kernel's slice of the slab: the direction bytes (none without a CIGAR), then the flat image of extd2_lds_kernel
+// (u|v|x|y|x2|y2|s|sf|qr, 16-aligned) and H (int32 per column)
+__host__ __device__ inline long long dp_hbm_img_off(int qlen, int tlen, int w_in, bool with_cigar)
+{
+	return with_cigar ? (dp_p_bytes(qlen, tlen, w_in) + 255) & ~255LL : 0;
+}
+__host__ __device__ inline long long dp_hbm_img_bytes(int qlen, int tlen, int variant)
+{
+	const long long T = (tlen + 15LL) / 16 * 16, QL = (qlen + 15LL) / 16 * 16;
+	return (((variant == 0 ? 8 : 6) * T + QL + 16 + 15) & ~15LL) + 4 * T;
 }
 
 __device__ __forceinline__ int s8(int v) { return (int)(int8_t)v; }

@@ -18,10 +18,52 @@ std::string &last_error_ref()
 	return s;
 }
 
-static const int kMaxLen = 8000;          // per-sequence limit of the general kernel
+static const int kLongLen = 8000;         // problems with a longer sequence take the long routes (dp_route)
+static const int kMaxSeqLen = 1 << 28;    // per-sequence limit: keeps rows, column offsets and extd2_hbm_kernel's ranks in 32 bits
 static const int kMaxLds = 160 * 1024;    // gfx950: 160 KiB LDS per CU / workgroup
 static const int kLdsClasses[] = {2048, 4096, 6144, 8192, 12288, 16384, 24576, 32768, 49152, 65536, 98304, 131072, kMaxLds};
 static const int kNumLdsClasses = sizeof(kLdsClasses) / sizeof(int);
+
+static int lds_class(long long need)
+{
+	int cls = 0;
+	while (cls < kNumLdsClasses - 1 && kLdsClasses[cls] < need) ++cls;
+	return cls;
+}
+
+struct DpRoute {
+	int kind, need;     // need: dynamic LDS bytes per alignment (dp_classify)
+	int64_t slab;       // bytes of the problem's slice of the slab (direction bytes, extd2_hbm_kernel's image)
+};
+
+// Problems with both sequences of at most kLongLen bases go where dp_classify puts them (the LDS of every kind holds them).  Longer ones:
+// the fast-flag banded shapes the ring kernels take when the query + target image fits LDS -- four alignments per workgroup while it
+// fits a quarter of it, one otherwise; everything else (wide or no band, the other flags, extz2, images beyond LDS) extd2_hbm_kernel.
+// A long problem without a CIGAR has no direction bytes.
+static DpRoute dp_route(int ql, int tl, const psvr_ksw_params_t *par, const DpParams &P, int variant, bool fast_ok)
+{
+	DpRoute R{0, 0, 0};
+	const bool with_cigar = !(par->flag & PSVR_EZ_SCORE_ONLY);
+	if (ql <= kLongLen && tl <= kLongLen) {
+		R.kind = dp_classify(ql, tl, par->w, fast_ok, variant, P.skip != 0, &R.need, dp_tiny_ok(P, fast_ok), true);
+		if (R.kind >= 0 && dp_kind_uses_slab(R.kind) && ql > 0 && tl > 0) R.slab = (dp_p_bytes(ql, tl, par->w) + 255) & ~(int64_t)255;
+		return R;
+	}
+	if (P.skip) { R.kind = 1; return R; }      // answered without a sweep (extd2_reg_kernel)
+	const int wf = par->w < 0 ? std::max(ql, tl) : par->w, sh = std::min(ql, tl);
+	const int span = std::min(wf, sh - 1) + 33;
+	const long long ring_need = ((ql + 16 + 15) & ~15LL) + ((tl + 15) & ~15LL) + 16;
+	if (fast_ok && span <= 256 && ring_need <= kMaxLds) {
+		R.need = (int)ring_need;
+		const bool four = (long long)kLdsClasses[lds_class(ring_need)] * kDpWaves <= kMaxLds;
+		R.kind = span <= 192 ? (four ? PSVR_DP_KIND_RING3 : PSVR_DP_KIND_RING1_3) : (four ? PSVR_DP_KIND_RING4 : PSVR_DP_KIND_RING1_4);
+		if (with_cigar) R.slab = (dp_p_bytes(ql, tl, par->w) + 255) & ~(int64_t)255;
+		return R;
+	}
+	R.kind = PSVR_DP_KIND_HBM;
+	R.slab = dp_hbm_img_off(ql, tl, par->w, with_cigar) + ((dp_hbm_img_bytes(ql, tl, variant) + 255) & ~(int64_t)255);
+	return R;
+}
 
 int make_dp_params(const psvr_ksw_params_t *par, int variant, DpParams *P)
 {
@@ -122,31 +164,28 @@ extern "C" int psvr_dp_plan_create(int device, int64_t n, const int32_t *qlen, c
 	const int fast_flags = PSVR_EZ_EXTZ_ONLY | PSVR_EZ_REV_CIGAR | PSVR_EZ_SCORE_ONLY;
 	const bool fast_ok = variant == 0 && (par->flag & ~fast_flags) == 0;
 	// bucket = kind * classes + lds class
-	std::vector<std::vector<int32_t>> bucket(PSVR_DP_NUM_KINDS * kNumLdsClasses);
+	std::vector<std::vector<int32_t>> bucket(PSVR_DP_NUM_HOST_KINDS * kNumLdsClasses);
 	std::vector<int64_t> poff(n, 0);
 	int64_t pslab = 0;
 	for (int64_t i = 0; i < n; ++i) {
 		int ql = qlen[i], tl = tlen[i];
-		if (ql > kMaxLen || tl > kMaxLen) {
+		if (ql >= kMaxSeqLen || tl >= kMaxSeqLen) {
 			delete pl;
-			return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld: qlen=%d tlen=%d exceeds %d", (long long)i, ql, tl, kMaxLen);
+			return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld: qlen=%d tlen=%d: sequences of 2^28 bases or more are not supported", (long long)i, ql, tl);
 		}
-		int need = 0;
-		int kind = dp_classify(ql, tl, par->w, fast_ok, variant, pl->P.skip != 0, &need, dp_tiny_ok(pl->P, fast_ok), true);
-		if (kind < 0) { delete pl; return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld needs %d B of LDS", (long long)i, need); }
-		if (dp_kind_uses_slab(kind) && ql > 0 && tl > 0) {
+		const DpRoute R = dp_route(ql, tl, par, pl->P, variant, fast_ok);
+		if (R.kind < 0) { delete pl; return set_error(PSVR_ERR_UNSUPPORTED, "problem %lld needs %d B of LDS", (long long)i, R.need); }
+		if (R.slab) {
 			poff[i] = pslab;
-			pslab += (dp_p_bytes(ql, tl, par->w) + 255) & ~(int64_t)255;
+			pslab += R.slab;
 		}
-		int cls = 0;
-		while (kLdsClasses[cls] < need) ++cls;
-		bucket[kind * kNumLdsClasses + cls].push_back((int32_t)i);
+		bucket[R.kind * kNumLdsClasses + lds_class(R.need)].push_back((int32_t)i);
 	}
 	std::vector<int32_t> idx;
 	idx.reserve(n);
-	// general kernel first, then the HBM-direction-byte kernels, then the LDS ones; large LDS classes first
-	const int kind_order[PSVR_DP_NUM_KINDS] = {0, 14, 13, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 12, 11};
-	for (int ko = 0; ko < PSVR_DP_NUM_KINDS; ++ko)
+	// the long problems' kernels first, then the general kernel, then the HBM-direction-byte kernels, then the LDS ones; large LDS classes first
+	const int kind_order[PSVR_DP_NUM_HOST_KINDS] = {17, 16, 15, 0, 14, 13, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 12, 11};
+	for (int ko = 0; ko < PSVR_DP_NUM_HOST_KINDS; ++ko)
 		for (int cls = kNumLdsClasses - 1; cls >= 0; --cls) {
 			auto &b = bucket[kind_order[ko] * kNumLdsClasses + cls];
 			if (b.empty()) continue;
@@ -245,29 +284,60 @@ static int dp_batch_host(int variant, int device, int64_t n,
 	const bool want_cigar = !(par->flag & PSVR_EZ_SCORE_ONLY);
 	if (want_cigar && (cig > cigar_cap || !cigar))
 		return set_error(PSVR_ERR_OVERFLOW, "cigar arena too small: need %lld uint32, have %lld", (long long)cig, (long long)cigar_cap);
-	psvr_dp_plan_t *pl = nullptr;
-	int rc = psvr_dp_plan_create(device, n, qlen, tlen, par, variant, &pl);
-	if (rc) return rc;
-	struct Guard { psvr_dp_plan_t *p; ~Guard() { psvr_dp_plan_destroy(p); } } guard{pl};
+	{
+		hipError_t he = hipSetDevice(device);
+		if (he != hipSuccess) return set_error(PSVR_ERR_DEVICE, "hipSetDevice(%d) failed: %s", device, hipGetErrorString(he));
+	}
 	DevBuf dq, dt, dqo, dto, dez, dcig, dwork;
 	PSVR_HIP(dq.alloc(qbytes + 16)); PSVR_HIP(dt.alloc(tbytes + 16));
 	PSVR_HIP(dqo.alloc(n * 8)); PSVR_HIP(dto.alloc(n * 8));
 	PSVR_HIP(dez.alloc(n * sizeof(psvr_extz_t)));
 	PSVR_HIP(dcig.alloc((want_cigar ? cig : 1) * 4));
-	PSVR_HIP(dwork.alloc(psvr_dp_plan_workspace_bytes(pl)));
 	PSVR_HIP(hipMemcpy(dq.p, qseq, qbytes, hipMemcpyHostToDevice));
 	PSVR_HIP(hipMemcpy(dt.p, tseq, tbytes, hipMemcpyHostToDevice));
 	PSVR_HIP(hipMemcpy(dqo.p, q_off, n * 8, hipMemcpyHostToDevice));
 	PSVR_HIP(hipMemcpy(dto.p, t_off, n * 8, hipMemcpyHostToDevice));
 	PSVR_HIP(hipMemcpy(dez.p, ez, n * sizeof(psvr_extz_t), hipMemcpyHostToDevice));
-	rc = psvr_dp_plan_launch(pl, dq.as<uint8_t>(), dqo.as<int64_t>(), dt.as<uint8_t>(), dto.as<int64_t>(),
-	                         dez.as<psvr_extz_t>(), dcig.as<uint32_t>(), dwork.p, nullptr);
+	// the plan runs in groups of consecutive problems whose slab slices (direction bytes, extd2_hbm_kernel's images) stay under
+	// min(4 GiB, free / 2); a problem beyond that budget runs alone if its workspace fits in free device memory
+	size_t free_b = 0, total_b = 0;
+	PSVR_HIP(hipMemGetInfo(&free_b, &total_b));
+	const int64_t budget = std::min<int64_t>(int64_t(4) << 30, (int64_t)(free_b / 2));
+	DpParams P;
+	int rc = make_dp_params(par, variant, &P);
 	if (rc) return rc;
-	PSVR_HIP(hipDeviceSynchronize());
-	{
+	const int fast_flags = PSVR_EZ_EXTZ_ONLY | PSVR_EZ_REV_CIGAR | PSVR_EZ_SCORE_ONLY;
+	const bool fast_ok = variant == 0 && (par->flag & ~fast_flags) == 0;
+	for (int64_t g0 = 0; g0 < n;) {
+		int64_t g1 = g0, acc = 0;
+		while (g1 < n) {
+			const int ql = std::max(qlen[g1], 0), tl = std::max(tlen[g1], 0);
+			const int64_t b = (ql < kMaxSeqLen && tl < kMaxSeqLen) ? dp_route(ql, tl, par, P, variant, fast_ok).slab : 0;
+			if (g1 > g0 && acc + b > budget) break;
+			acc += b, ++g1;
+		}
+		psvr_dp_plan_t *pl = nullptr;
+		rc = psvr_dp_plan_create(device, g1 - g0, qlen + g0, tlen + g0, par, variant, &pl);
+		if (rc) return rc;
+		struct Guard { psvr_dp_plan_t *p; ~Guard() { psvr_dp_plan_destroy(p); } } guard{pl};
+		const int64_t ws = psvr_dp_plan_workspace_bytes(pl);
+		if (ws > (int64_t)dwork.bytes) {
+			dwork.release();
+			PSVR_HIP(hipMemGetInfo(&free_b, &total_b));
+			if (ws > (int64_t)free_b || dwork.alloc(ws) != hipSuccess) {
+				(void)hipGetLastError();
+				return set_error(PSVR_ERR_NOMEM, "problems %lld..%lld need %lld bytes of device workspace, %zu bytes free",
+				                 (long long)g0, (long long)g1 - 1, (long long)ws, free_b);
+			}
+		}
+		rc = psvr_dp_plan_launch(pl, dq.as<uint8_t>(), dqo.as<int64_t>() + g0, dt.as<uint8_t>(), dto.as<int64_t>() + g0,
+		                         dez.as<psvr_extz_t>() + g0, dcig.as<uint32_t>(), dwork.p, nullptr);
+		if (rc) return rc;
+		PSVR_HIP(hipDeviceSynchronize());
 		int kerr = 0;
 		PSVR_HIP(hipMemcpy(&kerr, (char *)pl->d_wstop.p + 8, 4, hipMemcpyDeviceToHost));
 		if (kerr) return set_error(PSVR_ERR_OVERFLOW, "DP kernel scratch exhausted (internal error %d)", kerr);
+		g0 = g1;
 	}
 	PSVR_HIP(hipMemcpy(ez, dez.p, n * sizeof(psvr_extz_t), hipMemcpyDeviceToHost));
 	if (want_cigar) PSVR_HIP(hipMemcpy(cigar, dcig.p, cig * 4, hipMemcpyDeviceToHost));

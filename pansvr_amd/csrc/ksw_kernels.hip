@@ -431,14 +431,15 @@ __device__ __forceinline__ void dp_lean_loop(const DpParams &P, const uint8_t *t
 // run into the workgroups-per-CU limit long before the wave slots are full
 // RING: the matrix is wider than 64 K columns but its band is not (dp_ring_loop); the target is staged in LDS behind the query image
 // (a slot that is handed on fetches its new column's base from there), the direction bytes are in the HBM slab (PG)
-template <int K, bool PG, bool RING>
+// NW: wavefronts per workgroup (extd2_ring1_kernel: 1, so that a long problem's query + target image may take all 160 KiB)
+template <int K, bool PG, bool RING, int NW = kDpWaves>
 __device__ __forceinline__ void extd2_wave_body(const DpBatch &B, const DpParams &P)
 {
 	extern __shared__ __align__(16) uint8_t lds_all[];
 	// everything per-alignment is wave-uniform; threadIdx.x >> 6 is not provably so for the compiler, and without the
 	// readfirstlane all band / z-drop bookkeeping of the sweep is done per lane in VALU with exec-mask control flow
 	const int wave = uni(threadIdx.x >> 6);
-	const long long slot = (long long)blockIdx.x * kDpWaves + wave;
+	const long long slot = (long long)blockIdx.x * NW + wave;
 	if (slot >= B.n) return;
 	uint8_t *lds = lds_all + (size_t)wave * B.lds_per_wave;
 	const int pid = uni(B.idx[slot]);
@@ -461,7 +462,7 @@ __device__ __forceinline__ void extd2_wave_body(const DpBatch &B, const DpParams
 	uint8_t *QR = lds;                 // reversed query + >=16 zero bytes (the calloc'ed tail of `qr`, :100,121)
 	// direction bytes, row pitch rowb (:115): behind the query image in LDS, or (PG) in this problem's slice of the HBM slab
 	uint8_t *Pm = PG ? B.pslab + (uni64(B.p_off[pid]) << B.p_unit_shift) : lds + qimg;
-	const int p_end = n_rows * rowb + 16;
+	const int p_end = n_rows * rowb + 16;      // < 2^31: rows < 160 Ki, rowb <= 336 for every shape the planners send here
 	for (int i = lane; i < qimg; i += 64) QR[i] = i < qlen ? query[qlen - 1 - i] : 0;
 	if (RING) {
 		uint8_t *TG = lds + qimg;
@@ -506,6 +507,10 @@ template <int K>
 __global__ __launch_bounds__(64 * kDpWaves) void extd2_ring_kernel(DpBatch B, DpParams P) { extd2_wave_body<K, true, true>(B, P); }
 template __global__ void extd2_ring_kernel<3>(DpBatch, DpParams);
 template __global__ void extd2_ring_kernel<4>(DpBatch, DpParams);
+template <int K>
+__global__ __launch_bounds__(64) void extd2_ring1_kernel(DpBatch B, DpParams P) { extd2_wave_body<K, true, true, 1>(B, P); }
+template __global__ void extd2_ring1_kernel<3>(DpBatch, DpParams);
+template __global__ void extd2_ring1_kernel<4>(DpBatch, DpParams);
 
 template __global__ void extd2_reg_kernel<1, false>(DpBatch, DpParams);
 template __global__ void extd2_reg_kernel<2, false>(DpBatch, DpParams);
@@ -1187,5 +1192,275 @@ __global__ __launch_bounds__(64) void extd2_lds_kernel(DpBatch B, DpParams P)
 
 template __global__ void extd2_lds_kernel<0>(DpBatch, DpParams);
 template __global__ void extd2_lds_kernel<1>(DpBatch, DpParams);
+
+// ------------------------------------------------------------------------------------------
+// general path for what LDS cannot hold: extd2_lds_kernel's recurrence, cell for cell, with its flat image (and so every
+// artefact of the reference's unaligned 16-byte score stores) and H in this problem's slice of the HBM slab
+// (dp_hbm_img_off), query and target read from global memory once into that image.  Anti-diagonal r touches the columns
+// [st, max(en, fresh_end)] only -- contiguous, coalesced byte accesses that stay in L2.  A workgroup of kDpHbmWaves
+// wavefronts per alignment: an unbanded anti-diagonal has up to min(qlen, tlen) cells.  The in-place update of the column
+// arrays reads column t - 1 of the previous diagonal, which another wavefront may own, so a chunk of 64 kDpHbmWaves cells
+// (chunks from high t to low t, as in extd2_lds_kernel) computes everything, waits at a barrier, then stores.
+// ------------------------------------------------------------------------------------------
+template <int VAR>
+__global__ __launch_bounds__(64 * kDpHbmWaves) void extd2_hbm_kernel(DpBatch B, DpParams P)
+{
+	constexpr int NT = 64 * kDpHbmWaves;
+	constexpr int RS = 29;                          // rank = group << RS | (t - st0): t - st0 < 2^29 (the planner's length limit)
+	__shared__ int red_h[kDpHbmWaves];
+	__shared__ unsigned red_k[kDpHbmWaves];
+	const int pid = B.idx[blockIdx.x];
+	const int tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6);
+	const int qlen = B.qlen[pid], tlen = B.tlen[pid];
+	psvr_extz_t *out = B.ez + pid;
+	EzAcc ez;
+	ez.reset();
+	if (P.skip || qlen <= 0 || tlen <= 0) {
+		if (tid == 0) write_ez(out, ez, 0);
+		return;
+	}
+	const uint8_t *query = B.qseq + B.q_off[pid], *target = B.tseq + B.t_off[pid];
+	const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
+	int n_col = qlen < tlen ? qlen : tlen;
+	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
+	const long long rowb = n_col * 16;
+	const int n_rows = qlen + tlen - 1;
+	const long long T = ((tlen + 15LL) / 16) * 16, QL = ((qlen + 15LL) / 16) * 16;
+	constexpr int NARR = VAR == 0 ? 7 : 5;
+	const int flag = P.flag;
+	const int with_cigar = !(flag & PSVR_EZ_SCORE_ONLY), approx_max = !!(flag & PSVR_EZ_APPROX_MAX);
+	const int right = with_cigar && (flag & PSVR_EZ_RIGHT);
+	uint8_t *Pm = B.pslab + (B.p_off[pid] << B.p_unit_shift);
+	uint8_t *img8 = Pm + dp_hbm_img_off(qlen, tlen, P.w, with_cigar != 0);
+	int8_t *u8 = (int8_t*)img8, *v8 = u8 + T, *x8 = v8 + T, *y8 = x8 + T;
+	int8_t *x28 = VAR == 0 ? y8 + T : nullptr, *y28 = VAR == 0 ? x28 + T : nullptr;
+	int8_t *sa = VAR == 0 ? y28 + T : y8 + T;
+	uint8_t *sf = (uint8_t*)(sa + T), *qr = sf + T;
+	const long long img = NARR * T + T + QL + 16;
+	int32_t *H = (int32_t*)(img8 + ((img + 15) & ~15LL));
+
+	const int neg_qe = s8(-P.q - P.e), neg_qe2 = s8(-P.q2 - P.e2);
+	const int qe8 = s8(P.q + P.e), qe28 = s8(P.q2 + P.e2);
+	const int qe = P.q + P.e;
+	for (long long i = tid; i < img; i += NT) {
+		const long long a = i / T;
+		uint8_t val = 0;
+		if (VAR == 0) { if (a < 4) val = (uint8_t)neg_qe; else if (a < 6) val = (uint8_t)neg_qe2; }
+		if (a == NARR) { long long t = i - NARR * T; val = t < tlen ? target[t] : 0; }
+		if (a > NARR)  { long long k = i - (NARR + 1) * T; val = k < qlen ? query[qlen - 1 - k] : 0; }
+		img8[i] = val;
+	}
+	for (long long i = tid; i < T; i += NT) H[i] = PSVR_KSW_NEG_INF;
+	__syncthreads();
+
+	int last_st = -1, last_en = -1, H0 = 0, last_H0_t = 0;
+	const uint8_t qe2b = (uint8_t)((P.q + P.e) * 2), max_scb = (uint8_t)(P.mat[0] + (P.q + P.e) * 2), qb8 = (uint8_t)P.q;
+	for (int r = 0; r < n_rows; ++r) {
+		int st0, en0, st, en;
+		if (!band_limits(r, qlen, tlen, w, st0, en0, st, en)) { ez.zdropped = 1; break; }
+		int x1, x21 = 0, v1;
+		if (VAR == 0) {
+			if (st > 0) {
+				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], x21 = x28[st - 1], v1 = v8[st - 1];
+				else x1 = neg_qe, x21 = neg_qe2, v1 = neg_qe;
+			} else {
+				x1 = neg_qe, x21 = neg_qe2;
+				v1 = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
+			}
+		} else {
+			if (st > 0) {
+				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], v1 = v8[st - 1];
+				else x1 = v1 = 0;
+			} else x1 = 0, v1 = r ? s8(P.q) : 0;
+		}
+		__syncthreads();
+		if (en >= r && tid == 0) {
+			if (VAR == 0) {
+				y8[r] = neg_qe, y28[r] = neg_qe2;
+				u8[r] = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
+			} else y8[r] = 0, u8[r] = r ? (int8_t)qb8 : 0;
+		}
+		// scores
+		const uint8_t *qrr = qr + (qlen - 1 - r);
+		if (!(flag & PSVR_EZ_GENERIC_SC)) {
+			const int fresh_end = st0 + ((en0 - st0) / 16 + 1) * 16 - 1;
+			// the last 16-block may run past s into sf[0..14] (the reference's unaligned store): those columns were read
+			// above by lanes of other wavefronts, so that store waits for a barrier (at most one such cell per thread)
+			int ovr_t = -1, ovr_sc = 0;
+			for (int t = st0 + tid; t <= fresh_end; t += NT) {
+				uint8_t sq = sf[t], sq2 = qrr[t];
+				int sc = sq == sq2 ? P.sc_mch : P.sc_mis;
+				if (sq == (uint8_t)P.m1 || sq2 == (uint8_t)P.m1) sc = P.sc_N;
+				if (t < T) sa[t] = (int8_t)sc;
+				else ovr_t = t, ovr_sc = sc;
+			}
+			if (fresh_end >= T) {
+				__syncthreads();
+				if (ovr_t >= 0) sa[ovr_t] = (int8_t)ovr_sc;
+			}
+		} else {
+			for (int t = st0 + tid; t <= en0; t += NT) sa[t] = P.mat[sf[t] * P.m + qrr[t]];
+		}
+		__syncthreads();
+		// core: chunks of NT cells from high t to low t; a chunk reads nothing a later (lower) chunk writes
+		const int ngrp = (en - st) / NT + 1;
+		for (int g = ngrp - 1; g >= 0; --g) {
+			const int t = st + g * NT + tid;
+			const bool act = t <= en;
+			int nu = 0, nv = 0, nx = 0, ny = 0, nx2 = 0, ny2 = 0, d = 0;
+			if (act) {
+				if (VAR == 0) {
+					int xt1 = t == st ? x1 : (int)x8[t - 1], vt1 = t == st ? v1 : (int)v8[t - 1], x2t1 = t == st ? x21 : (int)x28[t - 1];
+					int z = sa[t], ut = u8[t];
+					int a = s8(xt1 + vt1), b = s8(y8[t] + ut), a2 = s8(x2t1 + vt1), b2 = s8(y28[t] + ut);
+					if (!right) {
+						if (a > z)  d = 1, z = a;
+						if (b > z)  d = 2, z = b;
+						if (a2 > z) d = 3, z = a2;
+						if (b2 > z) d = 4, z = b2;
+					} else {
+						d = z > a ? 0 : 1;  z = z > a ? z : a;
+						d = z > b ? d : 2;  z = z > b ? z : b;
+						d = z > a2 ? d : 3; z = z > a2 ? z : a2;
+						d = z > b2 ? d : 4; z = z > b2 ? z : b2;
+					}
+					z = min(z, P.sc_mch);
+					nu = z - vt1, nv = z - ut;
+					int tmp = s8(z - P.q);
+					a = s8(a - tmp), b = s8(b - tmp);
+					tmp = s8(z - P.q2);
+					a2 = s8(a2 - tmp), b2 = s8(b2 - tmp);
+					nx = max(a, 0) - qe8, ny = max(b, 0) - qe8, nx2 = max(a2, 0) - qe28, ny2 = max(b2, 0) - qe28;
+					if (!right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > 0 ? 0x20 : 0) | (b2 > 0 ? 0x40 : 0);
+					else d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= 0 ? 0x20 : 0) | (b2 >= 0 ? 0x40 : 0);
+				} else {
+					const int k = t - st;
+					unsigned x1w = (unsigned)x1, v1w = (unsigned)v1;   // sign-extended into lanes 1..3 (:147-148)
+					uint8_t xt1 = k == 0 ? 0 : (uint8_t)x8[t - 1], vt1 = k == 0 ? 0 : (uint8_t)v8[t - 1];
+					if (k < 4) xt1 |= (uint8_t)(x1w >> (8 * k)), vt1 |= (uint8_t)(v1w >> (8 * k));
+					uint8_t z = (uint8_t)((uint8_t)sa[t] + qe2b), a = (uint8_t)(xt1 + vt1), ut = (uint8_t)u8[t], b = (uint8_t)((uint8_t)y8[t] + ut);
+					if (!with_cigar) {
+						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+					} else if (!right) {
+						d = (int8_t)a > (int8_t)z ? 1 : 0;
+						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+						if ((int8_t)b > (int8_t)z) d = 2;
+					} else {
+						d = (int8_t)z > (int8_t)a ? 0 : 1;
+						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+						if (!((int8_t)z > (int8_t)b)) d = 2;
+					}
+					z = z > b ? z : b;
+					z = z < max_scb ? z : max_scb;
+					nu = (uint8_t)(z - vt1), nv = (uint8_t)(z - ut);
+					z = (uint8_t)(z - qb8);
+					a = (uint8_t)(a - z), b = (uint8_t)(b - z);
+					if (!right) {
+						nx = (int8_t)a > 0 ? (int8_t)a : 0; d |= (int8_t)a > 0 ? 0x08 : 0;
+						ny = (int8_t)b > 0 ? (int8_t)b : 0; d |= (int8_t)b > 0 ? 0x10 : 0;
+					} else {
+						nx = (int8_t)a < 0 ? 0 : (int8_t)a; d |= (int8_t)a < 0 ? 0 : 0x08;
+						ny = (int8_t)b < 0 ? 0 : (int8_t)b; d |= (int8_t)b < 0 ? 0 : 0x10;
+					}
+				}
+			}
+			__syncthreads();          // every read of this chunk's columns (t - 1 may belong to another wavefront) precedes its writes
+			if (act) {
+				u8[t] = (int8_t)nu, v8[t] = (int8_t)nv, x8[t] = (int8_t)nx, y8[t] = (int8_t)ny;
+				if (VAR == 0) x28[t] = (int8_t)nx2, y28[t] = (int8_t)ny2;
+				if (with_cigar) Pm[r * rowb + (t - st)] = (uint8_t)d;
+			}
+		}
+		__syncthreads();
+		const int e_drop = VAR == 0 ? P.e2 : P.e;
+		if (!approx_max) {
+			int max_H, max_t;
+			if (r > 0) {
+				const int en1 = st0 + (en0 - st0) / 4 * 4;
+				const int uen = VAR == 0 ? (int)u8[en0] : (int)(uint8_t)u8[en0] - qe;
+				const int ven = VAR == 0 ? (int)v8[en0] : (int)(uint8_t)v8[en0] - qe;
+				const int h_en0 = en0 > 0 ? H[en0 - 1] + uen : H[en0] + ven;
+				__syncthreads();
+				int bh = (int)0x80000000; unsigned bk = 0xffffffffu;
+				for (int t = st0 + tid; t <= en0; t += NT) {
+					int h;
+					if (t == en0) h = h_en0;
+					else h = H[t] + (VAR == 0 ? (int)v8[t] : (int)(uint8_t)v8[t] - qe);
+					H[t] = h;
+					unsigned rank = t == en0 ? 0u : t < en1 ? 1u + ((unsigned)((t - st0) & 3) << RS) + (unsigned)(t - st0)
+					                                        : 1u + (4u << RS) + (unsigned)(t - st0);
+					if (h > bh || (h == bh && rank < bk)) bh = h, bk = rank;
+				}
+				const int wm = wave_max_i32(bh);
+				const unsigned wk = wave_min_u32(bh == wm ? bk : 0xffffffffu);
+				if (lane == 0) red_h[wave] = wm, red_k[wave] = wk;
+				__syncthreads();
+				max_H = red_h[0];
+				unsigned rk = red_k[0];
+				for (int k = 1; k < kDpHbmWaves; ++k) {
+					const int h = red_h[k];
+					if (h > max_H) max_H = h, rk = red_k[k];
+					else if (h == max_H) rk = min(rk, red_k[k]);
+				}
+				max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & ((1u << RS) - 1u));
+			} else {
+				int h0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe;
+				if (tid == 0) H[0] = h0;
+				max_H = h0, max_t = 0;
+			}
+			__syncthreads();
+			const int H_en0 = H[en0], H_st0 = H[st0];
+			if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - en;
+			if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
+			if (ez.apply_zdrop(max_H, r, max_t, P.zdrop, e_drop)) break;
+			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H_en0;
+		} else {
+			const int bias = VAR == 0 ? 0 : qe;
+			if (r > 0) {
+				if (last_H0_t >= st0 && last_H0_t <= en0 && last_H0_t + 1 >= st0 && last_H0_t + 1 <= en0) {
+					int d0 = (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
+					int d1 = (VAR == 0 ? (int)u8[last_H0_t + 1] : (int)(uint8_t)u8[last_H0_t + 1]) - bias;
+					if (d0 > d1) H0 += d0;
+					else H0 += d1, ++last_H0_t;
+				} else if (last_H0_t >= st0 && last_H0_t <= en0) {
+					H0 += (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
+				} else {
+					++last_H0_t, H0 += (VAR == 0 ? (int)u8[last_H0_t] : (int)(uint8_t)u8[last_H0_t]) - bias;
+				}
+				if (VAR == 1 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
+			} else H0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe, last_H0_t = 0;
+			if (VAR == 0 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
+			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H0;
+		}
+		last_st = st, last_en = en;
+	}
+	// the traceback is one uniform walk: the first wavefront alone
+	if (wave != 0) return;
+	int n_cigar = 0;
+	if (with_cigar) {
+		__threadfence_block();
+		int i0 = -1, j0 = -1;
+		if (!ez.zdropped && !(flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
+		else if (!ez.zdropped && (flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
+		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
+		if (i0 >= 0 && j0 >= 0) {
+			uint32_t *dst = B.cigar + uni64(out->cigar_off);
+			n_cigar = traceback(i0, j0, qlen, tlen, w,
+				[&](int r, int k) { return (int)__builtin_nontemporal_load(Pm + r * rowb + k); },
+				[&](int k, uint32_t word) { if (lane == 0) dst[k] = word; });
+			if (!(flag & PSVR_EZ_REV_CIGAR)) {
+				__threadfence_block();
+				__builtin_amdgcn_wave_barrier();
+				for (int m = lane; m < (n_cigar >> 1); m += 64) {
+					uint32_t a = __builtin_nontemporal_load(dst + m), b = __builtin_nontemporal_load(dst + n_cigar - 1 - m);
+					dst[m] = b, dst[n_cigar - 1 - m] = a;
+				}
+			}
+		}
+	}
+	if (lane == 0) write_ez(out, ez, n_cigar);
+}
+template __global__ void extd2_hbm_kernel<0>(DpBatch, DpParams);
+template __global__ void extd2_hbm_kernel<1>(DpBatch, DpParams);
 
 } // namespace psvr

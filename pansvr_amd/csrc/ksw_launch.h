@@ -11,6 +11,9 @@ inline const char *dp_kind_name(int kind, int variant)
 	                                           "extd2_reg_kernel<5,lds>", "extd2_reg_kernel<1,hbm>", "extd2_reg_kernel<2,hbm>", "extd2_reg_kernel<3,hbm>", "extd2_reg_kernel<4,hbm>",
 	                                           "extd2_reg_kernel<5,hbm>", "extd2_tiny_kernel", "extd2_team_kernel", "extd2_ring_kernel<3>", "extd2_ring_kernel<4>"};
 	if (kind == 0 && variant == 1) return "extz2_lds_kernel";
+	if (kind == PSVR_DP_KIND_RING1_3) return "extd2_ring1_kernel<3>";
+	if (kind == PSVR_DP_KIND_RING1_4) return "extd2_ring1_kernel<4>";
+	if (kind == PSVR_DP_KIND_HBM) return variant == 0 ? "extd2_hbm_kernel" : "extz2_hbm_kernel";
 	return n[kind];
 }
 
@@ -21,6 +24,16 @@ inline void dp_launch_kind(int kind, int variant, unsigned count, int lds, hipSt
 	if (kind == PSVR_DP_KIND_TINY) {        // `lds` is the size bin: 512 bytes per anti-diagonal
 		const int max_rows = lds / 512;
 		hipLaunchKernelGGL(extd2_tiny_kernel, dim3((count + 63) / 64), dim3(64), (size_t)8192 + (size_t)max_rows * 1024, stream, B, P, max_rows);
+		return;
+	}
+	if (kind == PSVR_DP_KIND_RING1_3 || kind == PSVR_DP_KIND_RING1_4) {   // a workgroup per alignment
+		if (kind == PSVR_DP_KIND_RING1_3) hipLaunchKernelGGL(extd2_ring1_kernel<3>, dim3(count), dim3(64), lds, stream, B, P);
+		else hipLaunchKernelGGL(extd2_ring1_kernel<4>, dim3(count), dim3(64), lds, stream, B, P);
+		return;
+	}
+	if (kind == PSVR_DP_KIND_HBM) {
+		if (variant == 0) hipLaunchKernelGGL(extd2_hbm_kernel<0>, dim3(count), dim3(64 * kDpHbmWaves), 0, stream, B, P);
+		else hipLaunchKernelGGL(extd2_hbm_kernel<1>, dim3(count), dim3(64 * kDpHbmWaves), 0, stream, B, P);
 		return;
 	}
 	const bool reg = kind >= 1;
@@ -94,6 +107,7 @@ inline hipError_t dp_allow_big_lds()
 	PSVR_ATTR((extd2_reg_kernel<1, false>)); PSVR_ATTR((extd2_reg_kernel<2, false>)); PSVR_ATTR((extd2_reg_kernel<3, false>));
 	PSVR_ATTR((extd2_reg_kernel<4, false>)); PSVR_ATTR((extd2_reg_kernel<5, false>));
 	PSVR_ATTR(extd2_lds_kernel<0>); PSVR_ATTR(extd2_lds_kernel<1>); PSVR_ATTR(extd2_ring_kernel<3>); PSVR_ATTR(extd2_ring_kernel<4>);
+	PSVR_ATTR(extd2_ring1_kernel<3>); PSVR_ATTR(extd2_ring1_kernel<4>);
 #undef PSVR_ATTR
 	return e;
 }
