@@ -11,13 +11,18 @@ that the reference draws from one rand()/random_r sequence in input order: after
 integers (draws its block consumed) over RCCL and rebases to start where the previous rank ended (pansvr_amd/dist.py), so N
 GPUs produce exactly the records of one `-t 1` pass over the whole input.  Time is max over ranks between barriers.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints ONE JSON line (rank 0): the contract fields and
+the workload's "config".  Everything else takes runs or passes of its own and comes only with --full, which adds to the line
+  "engine", "kernels_ms_per_step": work counters and per-kernel HIP-event durations of one extra pass each
+  "multi_gpu":    (N > 1) the phases of the timed step and a check of the records rank 0 gathered
   "roofline":     HBM roofline of the dominant kernel, timed live with HIP events on its launch stream
   "cpu_baseline": the reference's own objects (oracle/_ref/ref_aln, kind "reference") or the oracle restatement
                   (kind "port") timed on this box's host cores on a bounded sample: -t 1 and -t <all cores>
   "parity_check": every rank's block (first pairs of it) against the reference objects started at that block's position
   "e2e":          wall of the drop-in command `panSVR aln` on the same workload (FASTQ in -> SAM / BAM out), phase split
   "pcie_inclusive": upload + run + compact download of one batch through the C ABI
+  "cfg5":         configs[4] (250 bp reads, edge-2000 anchors) timed beside it
+A --full run whose parity or gather check finds a difference says so in "error" and exits 3.
 """
 import argparse
 import json
@@ -245,24 +250,29 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--pairs", type=int, default=1000000, help="read pairs per GPU (configs[1]: 1 M)")
     ap.add_argument("--anchors", type=int, default=10000)
-    ap.add_argument("--cpu-pairs", type=int, default=300000, help="pairs of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--check-pairs", type=int, default=50000, help="pairs per rank whose engine records are compared with the reference objects")
-    ap.add_argument("--no-ref-cpu", action="store_true", help="time only the oracle port even if oracle/_ref/ref_aln is present")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end `panSVR aln` leg")
-    ap.add_argument("--no-pipeline", action="store_true", help="skip the overlapped-ABI leg (pcie_inclusive.pipelined)")
-    ap.add_argument("--no-cfg5", action="store_true", help="skip the configs[4] (250 bp / edge-2000) leg")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also everything beside the headline figure: work counters, per-kernel timing and "
+                                                        "roofline, parity check, CPU baseline, PCIe legs, e2e, cfg5 (the options below shape them)")
+    ap.add_argument("--cpu-pairs", type=int, default=300000, help="--full: pairs of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--check-pairs", type=int, default=50000, help="--full: pairs per rank whose engine records are compared with the reference objects")
+    ap.add_argument("--no-ref-cpu", action="store_true", help="--full: time only the oracle port even if oracle/_ref/ref_aln is present")
+    ap.add_argument("--no-e2e", action="store_true", help="--full: skip the end-to-end `panSVR aln` leg")
+    ap.add_argument("--no-pipeline", action="store_true", help="--full: skip the overlapped-ABI leg (pcie_inclusive.pipelined)")
+    ap.add_argument("--no-cfg5", action="store_true", help="--full: skip the configs[4] (250 bp / edge-2000) leg")
     ap.add_argument("--engines", type=int, default=int(os.environ.get("PSVR_BENCH_ENGINES", "1")),
                     help="engines per GPU: the rank's block is cut into that many contiguous sub-blocks, each run by its own engine on its own HIP queue.  Measured on "
                          "configs[1]: 1 engine 12.5 ms/step, 2 engines 16.5, 4 engines 27.6 -- the stages fill the chip by themselves, a second queue only adds the rebase rounds")
-    ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the multi-threaded CPU-baseline leg (0 = all cores, capped at the reference's 48)")
-    ap.add_argument("--one-pass", action="store_true", help="profiling runs (rocprofv3 --pmc): the warm-up and timed steps only, none of the extra engine passes (per-kernel timing, "
-                                                            "work counters, PCIe legs, e2e, cfg5): every kernel's counters then belong to exactly warmup + steps passes")
+    ap.add_argument("--cpu-threads", type=int, default=0, help="--full: threads of the multi-threaded CPU-baseline leg (0 = all cores, capped at the reference's 48)")
+    ap.add_argument("--one-pass", action="store_true", help="profiling runs (rocprofv3 --pmc): a plain run (the warm-up and timed steps are the only engine passes, so every "
+                                                            "kernel's counters belong to exactly warmup + steps passes) whose line records that; not with --full")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, rank -> device selection and one barrier only (no GPU is touched): the launch contract, testable on CPU")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the records the last one computed, for a fixed seeded sample of pairs, "
                                                           "as DIR/<name>.npy (float64, at most 64 MB in all; one process only)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.one_pass and args.full:
+        ap.error("--one-pass is a plain run: not with --full")
+    full = args.full
 
     import numpy as np
     import torch
@@ -291,12 +301,13 @@ def main():
         raise SystemExit("--dump-outputs: one process only (--gpus 1)")
     if torch.cuda.device_count() == 0:
         raise SystemExit("bench.py needs a GPU: the engine has no CPU path")
-    # the engine library, the CLI (its `index` sub-command builds the bench index) and the checkers: built here if the tree is a
-    # fresh checkout (no-ops otherwise); one rank builds, the others wait
+    # the engine library, the CLI (its `index` sub-command builds the bench index) and, for --full, the checkers: built here if the
+    # tree is a fresh checkout (no-ops otherwise); one rank builds, the others wait
     if rank == 0:
         from pansvr_amd import build as _build
         _build.build(force=False, verbose=False)
-        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")], stdout=subprocess.DEVNULL)
+        if full:
+            subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")], stdout=subprocess.DEVNULL)
     if world > 1:
         torch.cuda.set_device(local_rank)
         dist.barrier()
@@ -312,23 +323,25 @@ def main():
     ix_arrays = bench_data.build_index_cli(anc, dense=True)      # `panSVR index`: byte-identical to the reference builder's files
     bases, base_off, ori, isize = bench_data.make_reads(anc, args.pairs, seed=13 + rank)     # block `rank` of the input
     ref_exe = os.path.join(ROOT, "oracle", "_ref", "ref_aln")    # the reference's own aligner objects (oracle/Makefile)
-    have_ref = os.path.exists(ref_exe) and not args.no_ref_cpu and shm_ok     # its loader reads the dense 2 GiB table: RAM-backed tmp only
-    n_cpu = min(args.cpu_pairs, args.pairs) if rank == 0 else 0
-    n_chk = min(args.check_pairs, args.pairs)
-    n_e2e = args.pairs if (rank == 0 and world == 1 and not args.no_e2e) else 0
+    have_ref = full and os.path.exists(ref_exe) and not args.no_ref_cpu and shm_ok     # its loader reads the dense 2 GiB table: RAM-backed tmp only
+    # the checkers' inputs (FASTQ, header, index directory) only for --full: a plain run never starts them
+    n_cpu = min(args.cpu_pairs, args.pairs) if full and rank == 0 else 0
+    n_chk = min(args.check_pairs, args.pairs) if full else 0
+    n_e2e = args.pairs if (full and rank == 0 and world == 1 and not args.no_e2e) else 0
     n_fq = max(n_cpu, n_chk, n_e2e)
     fq = os.path.join(tmp, "block.fq")
     ncore = os.cpu_count() or 1
     if n_fq:
         # (forked formatting workers only in the single-process case, where nothing has touched the GPU yet)
         bench_data.write_fastq(fq, bases, base_off, ori, isize, n_pairs=n_fq, procs=min(16, ncore) if world == 1 else 1)
-    with open(os.path.join(tmp, "header.sam"), "w") as f:
-        f.write(HEADER)
-    ix_small = {k: v for k, v in ix_arrays.items() if k != "hash"}
     # one index directory per node in RAM-backed storage: the sparse form for `panSVR aln` / aln_oracle, the dense table for ref_aln
     idx_dir = os.path.join("/dev/shm" if shm_ok else tempfile.gettempdir(), "psvr_bench_idx_%d" % os.getppid()) if world > 1 else os.path.join(tmp, "idx")
-    if local_rank == 0 or world == 1:
-        bench_data.write_index_dir(ix_small, idx_dir, dense_hash=ix_arrays["hash"] if have_ref else None)
+    if full:
+        with open(os.path.join(tmp, "header.sam"), "w") as f:
+            f.write(HEADER)
+        ix_small = {k: v for k, v in ix_arrays.items() if k != "hash"}
+        if local_rank == 0 or world == 1:
+            bench_data.write_index_dir(ix_small, idx_dir, dense_hash=ix_arrays["hash"] if have_ref else None)
     t_host = time.time() - t_setup
 
     torch.cuda.set_device(local_rank)
@@ -465,12 +478,26 @@ def main():
     reads_per_step = 2 * args.pairs * world
     value = reads_per_step * args.steps / dt
     dumped = dump_outputs(args.dump_outputs, engs, cuts) if args.dump_outputs else None
+    # the contract fields and the workload
+    line = {"metric": "signal reads realigned/sec (150 bp PE); bit-exact CIGAR vs CPU ref", "value": round(value, 1), "unit": "reads/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32 (2-bit k-mers, 8-bit DP deltas, 32-bit scores)",
+            "data": "synthetic", "config": {"workload": "configs[1]: %d synthetic 150 bp PE signal read pairs per GPU vs %d-anchor SV reference (%.1f Mbp), `panSVR aln` hot path"
+                                             % (args.pairs, args.anchors, len(anc["codes"]) / 1e6),
+                                             "pairs_per_gpu": args.pairs, "reads_per_step": reads_per_step,
+                                             "parallelism": "shard%d x %d engine(s) per GPU (index replicated, one input cut into contiguous blocks, draw-order exchange: %s)" % (world, K, "none" if world == 1 else "all-gather of 6 int64 per rank over %s, %d per step" % ("RCCL" if xdev else "gloo", max(exchange_iters) if exchange_iters else 0)),
+                                             "engines_per_gpu": K, "in_process_rebases": group.rebases,
+                                             "index_hbm_bytes": index_device_bytes, "index_upload_s": round(t_index_upload, 2), "index_broadcast_ms": index_bcast, "index_distribution": index_how,
+                                             "host_setup_s": round(t_host, 1), "setup_s": round(t_setup, 1)}}
 
-    if args.one_pass:
+    if not full:
         if rank == 0:
-            print(json.dumps({"one_pass": True, "value": round(value, 1), "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                              "engine_passes": args.steps + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                              **({"dump_outputs": dumped} if dumped else {})}), flush=True)
+            if args.one_pass:
+                line = {"one_pass": True, "value": round(value, 1), "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                        "engine_passes": args.steps + args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3)}
+            if dumped:
+                line["dump_outputs"] = dumped
+            print(json.dumps(line), flush=True)
         for e in engs:
             e.close()
         index.close()
@@ -524,7 +551,6 @@ def main():
 
     # two extra passes (not timed above) on ONE engine over the whole block: per-kernel HIP-event durations on the launch stream, then
     # the work counters (their atomics would distort the timings)
-    group_rebases = group.rebases
     if K > 1:
         for e in engs:
             e.close()
@@ -774,19 +800,9 @@ def main():
                  "gather": "every rank's compact records (psvr_engine_download_compact into device memory) -> rank 0, point to point, in block order = input order; inside the timed step" if K == 1 else "not timed with --engines > 1"}
     failed = bool(parity and parity["pairs_differing"]) or bool(gather_check and gather_check["blocks_differing"])
     if rank == 0:
-        line = {"metric": "signal reads realigned/sec (150 bp PE); bit-exact CIGAR vs CPU ref", "value": round(value, 1), "unit": "reads/s",
-                "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
-                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32 (2-bit k-mers, 8-bit DP deltas, 32-bit scores)",
-                "data": "synthetic", "config": {"workload": "configs[1]: %d synthetic 150 bp PE signal read pairs per GPU vs %d-anchor SV reference (%.1f Mbp), `panSVR aln` hot path"
-                                                 % (args.pairs, args.anchors, len(anc["codes"]) / 1e6),
-                                                 "pairs_per_gpu": args.pairs, "reads_per_step": reads_per_step,
-                                                 "parallelism": "shard%d x %d engine(s) per GPU (index replicated, one input cut into contiguous blocks, draw-order exchange: %s)" % (world, K, "none" if world == 1 else "all-gather of 6 int64 per rank over %s, %d per step" % ("RCCL" if xdev else "gloo", max(exchange_iters) if exchange_iters else 0)),
-                                                 "engines_per_gpu": K, "in_process_rebases": group_rebases,
-                                                 "index_hbm_bytes": index_device_bytes, "index_upload_s": round(t_index_upload, 2), "index_broadcast_ms": index_bcast, "index_distribution": index_how,
-                                                 "host_setup_s": round(t_host, 1), "setup_s": round(t_setup, 1)},
-                "roofline": roofline, "cpu_baseline": cpu, "parity_check": parity, "multi_gpu": multi, "e2e": e2e, "pcie_inclusive": pcie, "cfg5": cfg5,
-                "engine": {k: st[k] for k in ("rounds", "pair_runs", "pair_only_runs", "shadow_runs", "sensitive_pairs", "window_misses", "adopted_pairs", "dp_problems", "dp_seq_bytes", "stale_open", "candidates", "walk_pairs", "walk_us", "n_special", "special_const", "special_nomove", "probes", "hits", "seeds", "dp_cells", "hbm_used_bytes") if k in st},
-                "kernels_ms_per_step": {k: round(v["ms"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms"])}}
+        line.update({"roofline": roofline, "cpu_baseline": cpu, "parity_check": parity, "multi_gpu": multi, "e2e": e2e, "pcie_inclusive": pcie, "cfg5": cfg5,
+                     "engine": {k: st[k] for k in ("rounds", "pair_runs", "pair_only_runs", "shadow_runs", "sensitive_pairs", "window_misses", "adopted_pairs", "dp_problems", "dp_seq_bytes", "stale_open", "candidates", "walk_pairs", "walk_us", "n_special", "special_const", "special_nomove", "probes", "hits", "seeds", "dp_cells", "hbm_used_bytes") if k in st},
+                     "kernels_ms_per_step": {k: round(v["ms"], 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms"])}})
         if dumped:
             line["dump_outputs"] = dumped
         if failed:

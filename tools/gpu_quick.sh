@@ -9,7 +9,7 @@ timeout -k 10 600 python -m pytest tests/test_aln_gpu.py tests/test_abi_gpu.py -
 tail -n 2 $O/gpu_tests.log
 [ $rc -eq 0 ] || exit 1
 for k in 1 2; do
-timeout -k 10 300 python bench.py --steps 30 --warmup 5 --cpu-pairs 0 --no-e2e --no-cfg5 > $O/bench$k.json 2> $O/bench$k.err; rc=$?; echo "bench rc $rc"
+timeout -k 10 300 python bench.py --steps 30 --warmup 5 --full --cpu-pairs 0 --no-e2e --no-cfg5 > $O/bench$k.json 2> $O/bench$k.err; rc=$?; echo "bench rc $rc"
 python - $O/bench$k.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
