@@ -44,6 +44,7 @@ struct DevBuf {
 		if (n == 0) n = 16;
 		hipError_t e = hipMalloc(&p, n);
 		if (e == hipSuccess) bytes = n;
+		else p = nullptr;
 		return e;
 	}
 	hipError_t ensure(size_t n) { return n <= bytes ? hipSuccess : alloc(n + n / 4); }

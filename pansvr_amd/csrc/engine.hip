@@ -1162,6 +1162,7 @@ static StreamPool &stream_pool() { static StreamPool *p = new StreamPool; return
 
 struct GpuBE {
 	static constexpr unsigned int kArenaShards = kArenaMaxShards;   // storage arenas: one counter (cache line) per workgroup residue
+	typedef DevBuf Buf;                                        // EngineCore's buffers (GpuBE is its Mem as well)
 	hipStream_t stream = nullptr;
 	hipError_t last = hipSuccess;
 	std::vector<std::pair<std::string, long long>> launches;   // for psvr_engine_stats
@@ -1224,9 +1225,7 @@ struct GpuBE {
 		evs.clear();
 	}
 
-	void note(hipError_t e) { if (e != hipSuccess && last == hipSuccess) last = e; }
-	void *dalloc(size_t n) { void *p = nullptr; hipError_t e = hipMalloc(&p, n ? n : 16); note(e); return e == hipSuccess ? p : nullptr; }
-	void dfree(void *p) { if (p) (void)hipFree(p); }
+	bool note(hipError_t e) { if (e != hipSuccess && last == hipSuccess) last = e; return e == hipSuccess; }
 	void dzero(void *p, size_t n) { note(hipMemsetAsync(p, 0, n, stream)); }
 	void scatter_u8_dev(uint8_t *a, const int32_t *d_idx, long long n, uint8_t v)
 	{
@@ -1236,7 +1235,7 @@ struct GpuBE {
 	// small transfers (counters, lists of a few thousand pairs) go through a pinned staging buffer: a copy to or from pageable
 	// memory costs several times the latency
 	void *pin = nullptr;
-	// layout of the 4 MB buffer: [0, 1.5 MB) staging of the small readbacks; [1.5 MB, 4 MB - 4 KB) the long readback of d2h_early_late, which stays
+	// layout of the 4 MB buffer: [0, 1.5 MB) staging of the readbacks; [1.5 MB, 4 MB - 4 KB) the long readback of d2h_early_late, which stays
 	// valid (the host reads the variant table in place) until the next one; the last 4 KB st_dp's slot for an upload nobody waits for
 	static constexpr size_t kPin = (size_t)4 << 20, kLateAt = (size_t)3 << 19, kPinUse = kLateAt;
 	void *pinned() { if (!pin && hipHostMalloc(&pin, kPin, hipHostMallocDefault) != hipSuccess) pin = nullptr; return pin; }
@@ -1285,63 +1284,60 @@ struct GpuBE {
 		if (h[0]) d2h(out.data(), list, (size_t)h[0] * 8);
 		return last == hipSuccess;
 	}
-	void d2h(void *h, const void *d, size_t n)
+	// Readbacks: the copies go out on the stream, then ONE synchronisation.  When they fit kPinUse together they are staged through the
+	// pinned buffer, device ranges that follow each other as one copy; otherwise they go straight to the host arrays.
+	bool d2h(Readbacks rb)
 	{
-		if (n && n <= kPinUse && pinned()) { note(hipMemcpyAsync(pin, d, n, hipMemcpyDeviceToHost, stream)); note(hipStreamSynchronize(stream)); synced(); memcpy(h, pin, n); return; }
-		note(hipMemcpyAsync(h, d, n, hipMemcpyDeviceToHost, stream)); note(hipStreamSynchronize(stream)); synced();
+		bool ok = true;
+		const bool staged = queue_d2h(rb, kPinUse, ok);
+		ok &= note(hipStreamSynchronize(stream));
+		synced();
+		if (staged) unstage(rb);
+		return ok;
 	}
-	// two small readbacks with one synchronisation
-	void d2h2(void *h1, const void *d1, size_t n1, void *h2, const void *d2, size_t n2)
+	bool d2h(void *h, const void *d, size_t n) { return d2h({{h, d, n}}); }
+	// queues the copies; true: into the pinned buffer (unstage() hands them over once they are there)
+	bool queue_d2h(Readbacks rb, size_t room, bool &ok)
 	{
-		if (n1 + n2 <= kPinUse && pinned()) {
-			note(hipMemcpyAsync(pin, d1, n1, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync((char *)pin + n1, d2, n2, hipMemcpyDeviceToHost, stream));
-			note(hipStreamSynchronize(stream)); synced();
-			memcpy(h1, pin, n1), memcpy(h2, (char *)pin + n1, n2);
-			return;
+		size_t tot = 0;
+		for (const Readback &x : rb) tot += x.n;
+		const bool staged = tot <= room && pinned();
+		const char *run = nullptr;
+		size_t from = 0, at = 0;                                 // the pending copy: device `run` -> pin + [from, at)
+		for (const Readback &x : rb) {
+			if (!x.n) continue;
+			if (!staged) { ok &= note(hipMemcpyAsync(x.h, x.d, x.n, hipMemcpyDeviceToHost, stream)); continue; }
+			if (run && (const char *)x.d == run + (at - from)) { at += x.n; continue; }
+			if (run) ok &= note(hipMemcpyAsync((char *)pin + from, run, at - from, hipMemcpyDeviceToHost, stream));
+			run = (const char *)x.d, from = at, at += x.n;
 		}
-		d2h(h1, d1, n1), d2h(h2, d2, n2);
+		if (run) ok &= note(hipMemcpyAsync((char *)pin + from, run, at - from, hipMemcpyDeviceToHost, stream));
+		return staged;
 	}
-	// Two small readbacks the host waits for (an event behind them), and a long one queued behind the event that it does NOT wait for: the
+	void unstage(Readbacks rb)
+	{
+		size_t at = 0;
+		for (const Readback &x : rb) if (x.n) memcpy(x.h, (char *)pin + at, x.n), at += x.n;
+	}
+	// Small readbacks the host waits for (an event behind them), and a long one queued behind the event that it does NOT wait for: the
 	// caller goes on with what the small ones brought, and the long copy is there after the stream's next synchronisation (d2h_late_done
 	// makes sure).  Returns where the long one lands -- a region of the page-locked buffer that nothing else uses, valid until the next call
 	// -- or nullptr when it does not fit (nothing was queued for it then: the caller fetches it some other way).
 	hipEvent_t ev_early = nullptr;
 	bool late_pending = false;
-	int32_t *d2h_early_late(void *h1, const void *d1, size_t n1, void *h2, const void *d2, size_t n2, const void *dl, size_t nl)
+	int32_t *d2h_early_late(Readbacks early, const void *dl, size_t nl)
 	{
-		if (!h2) n2 = 0;
-		if (!pinned() || n1 + n2 > kLateAt || (!ev_early && hipEventCreateWithFlags(&ev_early, hipEventDisableTiming) != hipSuccess)) {
-			if (n2) d2h2(h1, d1, n1, h2, d2, n2); else d2h(h1, d1, n1);
-			return nullptr;
-		}
-		char *p = (char *)pin;
-		note(hipMemcpyAsync(p, d1, n1, hipMemcpyDeviceToHost, stream));
-		if (n2) note(hipMemcpyAsync(p + n1, d2, n2, hipMemcpyDeviceToHost, stream));
+		if (!ev_early && hipEventCreateWithFlags(&ev_early, hipEventDisableTiming) != hipSuccess) { d2h(early); return nullptr; }
+		bool ok = true;
+		const bool staged = queue_d2h(early, kLateAt, ok);
 		note(hipEventRecord(ev_early, stream));
-		const bool fits = nl <= kPin - 4096 - kLateAt;
-		if (fits) { note(hipMemcpyAsync(p + kLateAt, dl, nl, hipMemcpyDeviceToHost, stream)); late_pending = true; }
+		const bool fits = staged && nl <= kPin - 4096 - kLateAt;
+		if (fits) { note(hipMemcpyAsync((char *)pin + kLateAt, dl, nl, hipMemcpyDeviceToHost, stream)); late_pending = true; }
 		note(hipEventSynchronize(ev_early));
-		memcpy(h1, p, n1);
-		if (n2) memcpy(h2, p + n1, n2);
-		return fits ? (int32_t *)(p + kLateAt) : nullptr;
+		if (staged) unstage(early);
+		return fits ? (int32_t *)((char *)pin + kLateAt) : nullptr;
 	}
 	void d2h_late_done() { if (late_pending) { note(hipStreamSynchronize(stream)); synced(); late_pending = false; } }
-	// four small readbacks with one synchronisation
-	void d2h4(void *h1, const void *d1, size_t n1, void *h2, const void *d2, size_t n2, void *h3, const void *d3, size_t n3, void *h4, const void *d4, size_t n4)
-	{
-		if (n1 + n2 + n3 + n4 <= kPinUse && pinned()) {
-			char *p = (char *)pin;
-			note(hipMemcpyAsync(p, d1, n1, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync(p + n1, d2, n2, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync(p + n1 + n2, d3, n3, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync(p + n1 + n2 + n3, d4, n4, hipMemcpyDeviceToHost, stream));
-			note(hipStreamSynchronize(stream)); synced();
-			memcpy(h1, p, n1), memcpy(h2, p + n1, n2), memcpy(h3, p + n1 + n2, n3), memcpy(h4, p + n1 + n2 + n3, n4);
-			return;
-		}
-		d2h2(h1, d1, n1, h2, d2, n2), d2h2(h3, d3, n3, h4, d4, n4);
-	}
 	~GpuBE()
 	{
 		if (pin) (void)hipHostFree(pin);
@@ -1484,38 +1480,15 @@ struct GpuBE {
 	void append_iota(int32_t *w, long long at, long long start, long long n) { if (n) hipLaunchKernelGGL(k_iota, dim3(grid_for(n)), dim3(kBlock), 0, stream, w, at, start, n); }
 	void append_list(int32_t *w, long long at, const int32_t *src, long long n) { if (n) hipLaunchKernelGGL(k_copy_i32, dim3(grid_for(n)), dim3(kBlock), 0, stream, w, at, src, n); }
 	// one index upload, one kernel, one synchronisation; the indices stay on the device for scatter_listed_i32
-	// oa / ob / oc = a / b / cc at the listed indices; x1..x3: up to three more small readbacks (or null) that ride on the same synchronisation
-	void gather_listed(const long long *a, const long long *b, const int32_t *cc, const int32_t *idx, long long n, long long *oa, long long *ob, int32_t *oc,
-	                   void *x1h, const void *x1d, size_t x1n, void *x2h, const void *x2d, size_t x2n, void *x3h, const void *x3d, size_t x3n)
+	// oa / ob / oc = a / b / cc at the listed indices (the kernel writes them back to back: staged, they come over as one copy)
+	void gather_listed(const long long *a, const long long *b, const int32_t *cc, const int32_t *idx, long long n, long long *oa, long long *ob, int32_t *oc)
 	{
-		void *xh[3] = {x1h, x2h, x3h};
-		const void *xd[3] = {x1d, x2d, x3d};
-		size_t xn[3] = {x1h ? x1n : 0, x2h ? x2n : 0, x3h ? x3n : 0};
-		const size_t xtot = xn[0] + xn[1] + xn[2];
-		if (n) {
-			note(tmp_idx.ensure(n * 4)), note(tmp_out.ensure(n * 20 + 16));
-			h2d(tmp_idx.p, idx, n * 4);
-			hipLaunchKernelGGL(k_gather_listed, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, b, cc, (const int32_t *)tmp_idx.p, n, (long long *)tmp_out.p);
-		}
-		if (!n && !xtot) return;
-		if ((size_t)n * 20 + xtot <= kPinUse && pinned()) {
-			char *p = (char *)pin;
-			if (n) note(hipMemcpyAsync(p, tmp_out.p, n * 20, hipMemcpyDeviceToHost, stream));
-			size_t at = (size_t)n * 20;
-			for (int k = 0; k < 3; ++k) if (xn[k]) { note(hipMemcpyAsync(p + at, xd[k], xn[k], hipMemcpyDeviceToHost, stream)); at += xn[k]; }
-			note(hipStreamSynchronize(stream)); synced();
-			if (n) memcpy(oa, p, n * 8), memcpy(ob, p + n * 8, n * 8), memcpy(oc, p + n * 16, n * 4);
-			at = (size_t)n * 20;
-			for (int k = 0; k < 3; ++k) if (xn[k]) { memcpy(xh[k], p + at, xn[k]); at += xn[k]; }
-			return;
-		}
-		if (n) {
-			note(hipMemcpyAsync(oa, tmp_out.p, n * 8, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync(ob, (char *)tmp_out.p + n * 8, n * 8, hipMemcpyDeviceToHost, stream));
-			note(hipMemcpyAsync(oc, (char *)tmp_out.p + n * 16, n * 4, hipMemcpyDeviceToHost, stream));
-		}
-		for (int k = 0; k < 3; ++k) if (xn[k]) note(hipMemcpyAsync(xh[k], xd[k], xn[k], hipMemcpyDeviceToHost, stream));
-		note(hipStreamSynchronize(stream)); synced();
+		if (!n) return;
+		note(tmp_idx.ensure(n * 4)), note(tmp_out.ensure(n * 20 + 16));
+		h2d(tmp_idx.p, idx, n * 4);
+		hipLaunchKernelGGL(k_gather_listed, dim3(grid_for(n)), dim3(kBlock), 0, stream, a, b, cc, (const int32_t *)tmp_idx.p, n, (long long *)tmp_out.p);
+		const char *o = (const char *)tmp_out.p;
+		d2h({{oa, o, (size_t)n * 8}, {ob, o + n * 8, (size_t)n * 8}, {oc, o + n * 16, (size_t)n * 4}});
 	}
 	void scatter_listed_i32(int32_t *a, const int32_t *val, long long n)
 	{
@@ -1644,19 +1617,8 @@ struct GpuBE {
 		PSVR_HIP(hipGetLastError());
 		unsigned long long hist[512], qmax[18];                // qmax[17]: query + target bytes of the round's problems
 		long long tot[3];
-		{
-			// one synchronisation for all five readbacks, through the pinned staging buffer when it exists
-			char stackbuf[512 * 8 + 18 * 8 + 24];
-			char *hb = pinned() ? (char *)pin : stackbuf;
-			PSVR_HIP(hipMemcpyAsync(hb, plan_hist.p, 512 * 8, hipMemcpyDeviceToHost, stream));
-			PSVR_HIP(hipMemcpyAsync(hb + 4096, (char *)plan_hist.p + 1024 * 8, 18 * 8, hipMemcpyDeviceToHost, stream));
-			PSVR_HIP(hipMemcpyAsync(hb + 4240, d.q_off + n, 8, hipMemcpyDeviceToHost, stream));
-			PSVR_HIP(hipMemcpyAsync(hb + 4248, d.t_off + n, 8, hipMemcpyDeviceToHost, stream));
-			PSVR_HIP(hipMemcpyAsync(hb + 4256, pd.p_off + n, 8, hipMemcpyDeviceToHost, stream));
-			PSVR_HIP(hipStreamSynchronize(stream));
-			synced();
-			memcpy(hist, hb, 4096), memcpy(qmax, hb + 4096, 144), memcpy(tot, hb + 4240, 24);
-		}
+		if (!d2h({{hist, plan_hist.p, sizeof hist}, {qmax, plan_hist.as<char>() + 1024 * 8, sizeof qmax}, {&tot[0], d.q_off + n, 8}, {&tot[1], d.t_off + n, 8}, {&tot[2], pd.p_off + n, 8}}))
+			return set_error(PSVR_ERR_DEVICE, "DP plan readback: %s", hipGetErrorString(last));
 		// NB: the scans ran over n+1 entries, element n of qlen/tlen/plen is scratch: its value only lands in slot n+1 (never read)
 		core.stats.dp_seq_bytes += (long long)qmax[17];              // query + target bytes the DP launches of this round read (k_dp_lens sums them)
 		if (!core.ensure_dp(n, tot[0], tot[1], tot[0] + tot[1] + 2 * n)) return set_error(PSVR_ERR_NOMEM, "DP sequence buffers");
@@ -2168,7 +2130,7 @@ extern "C" int psvr_device_warmup(int device, int n_streams)
 struct psvr_engine {
 	const psvr_index *ix;
 	GpuBE be;
-	EngineCore<GpuBE> core;
+	EngineCore<GpuBE, GpuBE> core;
 	bool committed = true;
 	// hand-over buffers: the materialised ABI records, or the compact form (valid until the next upload / run / rebase)
 	DevBuf full_out, cmp_cnt_c, cmp_cnt_w, cmp_off_c, cmp_off_w, cmp_hdr, cmp_cand, cmp_cig;
@@ -2198,10 +2160,9 @@ extern "C" void psvr_engine_destroy(psvr_engine_t *e)
 {
 	if (!e) return;
 	(void)hipSetDevice(e->ix->device);
-	e->core.free_all();
 	const int dev = e->ix->device;
 	hipStream_t own = e->own;
-	delete e;                                                // (its backend gives the side streams back)
+	delete e;                                                // (its core frees its buffers, then its backend gives the side streams back)
 	stream_pool().put(dev, own);
 }
 
@@ -2313,9 +2274,7 @@ extern "C" int psvr_engine_download_compact(psvr_engine_t *e, psvr_read_hdr_t *h
 		e->be.st_scan(e->cmp_cnt_w.as<int32_t>(), R + 1, 1, 0, 0ll, e->cmp_off_w.as<long long>());
 		PSVR_HIP(hipGetLastError());
 		long long tot[2] = {0, 0};
-		PSVR_HIP(hipMemcpyAsync(&tot[0], e->cmp_off_c.as<long long>() + R, 8, hipMemcpyDeviceToHost, e->own));
-		PSVR_HIP(hipMemcpyAsync(&tot[1], e->cmp_off_w.as<long long>() + R, 8, hipMemcpyDeviceToHost, e->own));
-		PSVR_HIP(hipStreamSynchronize(e->own));
+		if (!e->be.d2h({{&tot[0], e->cmp_off_c.as<long long>() + R, 8}, {&tot[1], e->cmp_off_w.as<long long>() + R, 8}})) return engine_status(e, PSVR_ERR_DEVICE);
 		PSVR_HIP(e->cmp_hdr.ensure((size_t)R * sizeof(psvr_read_hdr_t)));
 		PSVR_HIP(e->cmp_cand.ensure((size_t)(tot[0] + 1) * sizeof(psvr_cand_t)));
 		PSVR_HIP(e->cmp_cig.ensure((size_t)(tot[1] + 1) * 4));

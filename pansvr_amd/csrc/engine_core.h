@@ -27,10 +27,12 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <chrono>
+#include <type_traits>
 #include <vector>
 #include "aln_device.h"
 
@@ -120,14 +122,72 @@ struct DpIO {                 // what the DP stage needs beyond Ctx
 	long long qbytes, tbytes, cig_words;
 };
 
+// one device -> host copy: the backends' d2h takes a list of them and synchronises once
+struct Readback { void *h; const void *d; size_t n; };
+typedef std::initializer_list<Readback> Readbacks;
+
+// The memory side of a backend whose "device" is host memory (tests/emu): zero-filled buffers, readbacks that are plain copies.
+// EngineCore's default: such a backend only runs the stages.  (GpuBE is its own memory: DevBuf buffers, readbacks staged through
+// page-locked memory.)
+struct HostMem {
+	struct Buf {                                 // the host twin of DevBuf
+		void *p = nullptr;
+		size_t bytes = 0;
+		Buf() = default;
+		Buf(const Buf &) = delete;
+		Buf &operator=(const Buf &) = delete;
+		~Buf() { release(); }
+		void release() { free(p); p = nullptr; bytes = 0; }
+		bool alloc(size_t n)
+		{
+			release();
+			p = calloc(n ? n : 1, 1);
+			bytes = p ? n : 0;
+			return p != nullptr;
+		}
+	};
+	bool note(bool ok) { return ok; }
+	void d2h(Readbacks rb) { for (const Readback &x : rb) if (x.n) memcpy(x.h, x.d, x.n); }
+	void d2h(void *h, const void *d, size_t n) { d2h({{h, d, n}}); }
+	// (GPU: the small readbacks now, the long one queued behind them; here everything is there at once)
+	std::vector<int32_t> late_buf;
+	int32_t *d2h_early_late(Readbacks early, const void *dl, size_t nl)
+	{
+		d2h(early);
+		late_buf.resize(nl / 4 + 1);
+		memcpy(late_buf.data(), dl, nl);
+		return late_buf.data();
+	}
+	void d2h_late_done() {}
+	std::vector<int32_t> listed_idx;
+	void gather_listed(const long long *a, const long long *b, const int32_t *cc, const int32_t *idx, long long n, long long *oa, long long *ob, int32_t *oc)
+	{
+		if (!n) return;                          // (the indices of the gather before stay: scatter_listed_i32 is not called then)
+		listed_idx.assign(idx, idx + n);
+		for (long long i = 0; i < n; ++i) oa[i] = a[idx[i]], ob[i] = b[idx[i]], oc[i] = cc[idx[i]];
+	}
+	void scatter_listed_i32(int32_t *a, const int32_t *val, long long n) { for (long long i = 0; i < n; ++i) a[listed_idx[i]] = val[i]; }
+};
+
 struct RunStats {
 	long long rounds = 0, pairs_run = 0, pair_only = 0, shadow_runs = 0, sensitive = 0, window_miss = 0, dp_problems = 0, cands = 0, adopted = 0, stale_open = 0, dp_seq_bytes = 0, from_walk = 0;
 	long long walk_pairs = 0, walk_us = 0, n_special = 0, special_const = 0, special_nomove = 0;     // the host walk over the N / tie-sensitive pairs: entries, microseconds (all rounds of the batch)
 	unsigned long long counters[16] = {0};
 };
 
-template <class BE> struct EngineCore {
+// BE runs the stages; Mem owns the buffers and reads results back (d2h, d2h_early_late / d2h_late_done, gather_listed /
+// scatter_listed_i32): GpuBE is both, a host backend keeps the default
+template <class BE, class Mem = HostMem> struct EngineCore {
 	BE &be;
+	HostMem host;                                   // (Mem = HostMem)
+	Mem &mem;
+	// Device memory: every buffer is a member of Mem's owning type (GpuBE: DevBuf), freed when the core goes; Ctx and DpIO, the stages'
+	// arguments, hold plain pointers into them.  get() (re)allocates one; a failure is noted by Mem (an ABI caller gets PSVR_ERR_DEVICE)
+	// and clears alloc_ok.
+	typedef typename Mem::Buf Buf;
+	template <class T> struct Dev : Buf { operator T *() const { return (T *)this->p; } };
+	bool alloc_ok = true;
+	template <class T> T *get(Dev<T> &b, unsigned long long n) { alloc_ok &= mem.note(b.alloc((n ? n : 1) * sizeof(T))); return b; }
 	Ctx c;
 	long long P = 0, R = 0;                 // pairs / reads of the uploaded batch
 	long long total_bases = 0;
@@ -138,70 +198,74 @@ template <class BE> struct EngineCore {
 	// the device tables hold a WINDOW of the host streams: entries [base, base + n).  A run, a rebase or a new batch whose needs lie inside the
 	// window keeps it (a shard that moves behind its predecessors' draws, the next batch of a pipeline: no 28 MB upload, no hipFree)
 	long long grand_dev_base = 0, hrand_dev_base[2] = {0, 0}, grand_dev_cap = 0, hrand_dev_cap = 0;
-	int32_t *d_grand = nullptr, *d_hrand[2] = {nullptr, nullptr};
-	// device buffers owned here
-	std::vector<void *> owned;
-	long long *d_noff = nullptr, *d_nhoff = nullptr;
-	int32_t *d_work = nullptr, *d_workp = nullptr;   // full re-run list (real pairs then shadow slots) and the pairing-only list
-	int32_t *d_ctot = nullptr, *d_src = nullptr;     // per slot: total draws of the last evaluation; slot -> input pair
-	int32_t *d_hprev = nullptr;                      // per slot x mate: random_r draws of the last evaluation (to see whether a round changed anything)
-	uint8_t *d_sens = nullptr;                       // per pair: known count-sensitive
-	int32_t *d_slist = nullptr;                      // newly detected sensitive pairs
-	char *d_bases = nullptr; long long *d_off = nullptr; psvr_ori_t *d_ori = nullptr;   // the uploaded batch
-	long long cap_S = 0, cap_P = 0; int cap_lm = 0;                        // what the per-batch buffers were sized for
-	uint8_t *d_force = nullptr, *d_mask = nullptr;   // forced draws per read; per pair: resolved on the host (special or sensitive)
+	Dev<int32_t> d_grand, d_hrand[2];
+	// the per-batch buffers behind Ctx's arrays of the same names, and the scratch arenas
+	struct {
+		Dev<long long> poff, hoff;
+		Dev<int32_t> rcnt, hcnt, str_list, read_l, n_ccand;
+		Dev<unsigned int> str_cnt;
+		Dev<uint8_t> active, unmapped, is_str, has_n4, has_mem, bin, seed_list;
+		Dev<uint64_t> rb;
+		Dev<Strand> strand;
+		Dev<ChainCand> ccand;
+		Dev<psvr_read_hdr_t> rh;
+		Dev<psvr_pair_result_t> pres;
+		Dev<unsigned long long> stats;
+		Dev<VMem> mem;
+		Dev<USeed> us;
+		Dev<PathN> path;
+		Dev<Seg> seg;
+		Dev<DpDesc> dp;
+		Dev<CandWork> cw;
+		Dev<uint32_t> cig;
+		Dev<psvr_cand_t> cand;
+	} cb;
+	// the core's own per-batch buffers
+	Dev<long long> d_noff, d_nhoff;
+	Dev<int32_t> d_work, d_workp;                    // full re-run list (real pairs then shadow slots) and the pairing-only list
+	Dev<int32_t> d_ctot, d_src;                      // per slot: total draws of the last evaluation; slot -> input pair
+	Dev<int32_t> d_hprev;                            // per slot x mate: random_r draws of the last evaluation (to see whether a round changed anything)
+	Dev<uint8_t> d_sens;                             // per pair: known count-sensitive
+	Dev<int32_t> d_slist;                            // newly detected sensitive pairs
+	long long cap_S = 0, cap_P = 0; int cap_lm = 0;  // what the per-batch buffers were sized for (cap_S = 0: they are not usable)
+	Dev<uint8_t> d_force, d_mask;                    // forced draws per read; per pair: resolved on the host (special or sensitive)
 	// the special pairs on the device: the list, which of them draw the same number under every residue assignment (resolved there, not in the
 	// host walk), the variant slot each of those carries and the offset it was adopted at
-	SpecialPair *d_special = nullptr;
-	int32_t *d_vsrc = nullptr, *d_spidx = nullptr;   // variant slot -> pair, the special pairs' numbers: constant for the batch, copied / scattered device to device at every run
-	uint8_t *d_sp_class = nullptr;
-	int32_t *d_sp_adopted = nullptr;
-	long long *d_sp_adopted_at = nullptr;
+	Dev<SpecialPair> d_special;
+	Dev<int32_t> d_vsrc, d_spidx;                    // variant slot -> pair, the special pairs' numbers: constant for the batch, copied / scattered device to device at every run
+	Dev<uint8_t> d_sp_class;
+	Dev<int32_t> d_sp_adopted;
+	Dev<long long> d_sp_adopted_at;
 	std::vector<uint8_t> h_sp_class;
-	uint8_t *d_hasn = nullptr;                       // per pair: a read of it draws for N bases (its draws are not just chain-selection ties)
-	int32_t *d_resel = nullptr, *d_resel4 = nullptr;   // pairs whose chain selection runs again on its own (reselect_pair); of those, the ones that go on from the walk
+	Dev<uint8_t> d_hasn;                             // per pair: a read of it draws for N bases (its draws are not just chain-selection ties)
+	Dev<int32_t> d_resel, d_resel4;                  // pairs whose chain selection runs again on its own (reselect_pair); of those, the ones that go on from the walk
 	std::vector<int32_t> h_n_idx;                    // pairs with N draws (built by upload())
 	static const long long kReselCap = 1 << 16;      // tie-only pairs a round can resolve on the spot; beyond that they run in full
-	int32_t *d_cmask = nullptr;                      // totals with the host-resolved pairs masked out
+	Dev<int32_t> d_cmask;                            // totals with the host-resolved pairs masked out
 	typedef SpecialPair Special;                     // (aln_device.h: the device looks at them too)
 	std::vector<Special> special;                    // pairs with 1..3 N draws, ascending
 	long long V = 0;                                 // variant slots [P, P+V)
 	long long S = 0;                                 // slots = P real pairs + V variants + window-shadow capacity
 	static const int kWin = 32;                      // offsets evaluated per sensitive pair and round
-	unsigned long long *d_tops = nullptr;     // [16] dirty counts, totals counters
+	Dev<unsigned long long> d_tops;           // [16] dirty counts, totals counters
 	// the six arena tops, each in a cache line of its own (kTopStride words apart): a wavefront's atomic on a line costs ~12 ns however many
 	// lanes take part, and atomics on one line are served one after the other (tools/atomic_rate_bench.hip) -- three counters that the
 	// walk bumps per read shared one line
 	static constexpr int kTopStride = kArenaTopStride * kArenaMaxShards;   // words between two arenas' first counters
-	unsigned long long *d_atops = nullptr;
-	int32_t *d_flags = nullptr;               // [8] six overflow flags, the error word, [7] stale_open (aln_device.h stale_compare)
+	Dev<unsigned long long> d_atops;
+	Dev<int32_t> d_flags;                     // [8] six overflow flags, the error word, [7] stale_open (aln_device.h stale_compare)
 	unsigned long long cap_mem = 0, cap_us = 0, cap_seg = 0, cap_dp = 0, cap_cw = 0, cap_cig = 0;
 	DpIO dp;
+	struct { Dev<int32_t> qlen, tlen; Dev<long long> q_off, t_off; Dev<uint8_t> qbuf, tbuf; Dev<psvr_extz_t> ez; Dev<uint32_t> cig; } dpb;   // behind dp
 	long long dp_cap_q = 0, dp_cap_t = 0, dp_cap_c = 0, dp_cap_n = 0;
 	RunStats stats;
 	std::string err;
 
-	explicit EngineCore(BE &b) : be(b) { memset(&c, 0, sizeof c); memset(&dp, 0, sizeof dp); }
-
-	template <class T> T *alloc(unsigned long long n)
+	explicit EngineCore(BE &b) : be(b), mem(memory(b)) { memset(&c, 0, sizeof c); memset(&dp, 0, sizeof dp); }
+	Mem &memory(BE &b)
 	{
-		void *p = be.dalloc((n ? n : 1) * sizeof(T));
-		if (p) owned.push_back(p);
-		return (T *)p;
-	}
-	void free_all()
-	{
-		for (void *p : owned) be.dfree(p);
-		owned.clear();
-		free_inputs();
-		free_arenas();
-		for (void *p : {(void *)d_grand, (void *)d_hrand[0], (void *)d_hrand[1], (void *)dp.qlen, (void *)dp.tlen, (void *)dp.q_off,
-		                (void *)dp.t_off, (void *)dp.qbuf, (void *)dp.tbuf, (void *)dp.ez, (void *)dp.cig})
-			if (p) be.dfree(p);
-		d_grand = d_hrand[0] = d_hrand[1] = nullptr;
-		memset(&dp, 0, sizeof dp);
-		dp_cap_q = dp_cap_t = dp_cap_c = dp_cap_n = 0;
-		grand_dev_n = hrand_dev_n = 0, grand_dev_cap = hrand_dev_cap = 0;
+		if constexpr (std::is_same<Mem, BE>::value) return b;
+		else return host;
 	}
 
 	void init(const DevIndex &ix, const psvr_aln_params_t &par)
@@ -227,9 +291,7 @@ template <class BE> struct EngineCore {
 			const long long n = need_g + need_g / 2 + 4096 + margin;
 			grand.ensure(grand_pos + n);
 			if (n > grand_dev_cap || !d_grand) {
-				if (d_grand) be.dfree(d_grand);
-				d_grand = (int32_t *)be.dalloc(n * 4);
-				if (!d_grand) return false;
+				if (!get(d_grand, n)) return false;
 				grand_dev_cap = n;
 			}
 			grand.pieces(grand_pos, n, [&](long long o, const int32_t *src, long long m) { be.h2d(d_grand + o, src, (size_t)m * 4); });
@@ -241,11 +303,7 @@ template <class BE> struct EngineCore {
 			const long long n = need_h + need_h / 2 + 4096 + margin_h;
 			for (int k = 0; k < 2; ++k) {
 				hrand[k].ensure(hrand_pos[k] + n);
-				if (n > hrand_dev_cap || !d_hrand[k]) {
-					if (d_hrand[k]) be.dfree(d_hrand[k]);
-					d_hrand[k] = (int32_t *)be.dalloc(n * 4);
-					if (!d_hrand[k]) return false;
-				}
+				if ((n > hrand_dev_cap || !d_hrand[k]) && !get(d_hrand[k], n)) return false;
 				be.h2d(d_hrand[k], hrand[k].host.data() + hrand_pos[k], n * 4);
 				hrand_dev_base[k] = hrand_pos[k];
 			}
@@ -262,13 +320,18 @@ template <class BE> struct EngineCore {
 	// the batch's three arrays on the device, in buffers of their own (kept while the next batch fits), and the list the device's pass
 	// over the batch leaves: (pair, n0 | n1 << 8) for every pair a read of which will draw for N bases
 	long long in_cap_bases = 0, in_cap_R = 0;
-	int32_t *d_nlist = nullptr;
-	void free_inputs()
-	{
-		for (void *p : {(void *)d_bases, (void *)d_off, (void *)d_ori, (void *)d_nlist}) if (p) be.dfree(p);
-		d_bases = nullptr, d_off = nullptr, d_ori = nullptr, d_nlist = nullptr, in_cap_bases = in_cap_R = 0;
-	}
+	Dev<char> d_bases;
+	Dev<long long> d_off;
+	Dev<psvr_ori_t> d_ori;
+	Dev<int32_t> d_nlist;
 	int upload(long long n_pairs, const char *bases, const int64_t *base_off, const psvr_ori_t *ori)
+	{
+		const int rc = place_batch(n_pairs, bases, base_off, ori);
+		// a failure, too, returns only when the batch's copies are through: the caller's arrays are free once upload returns (psvr_engine.h)
+		if (rc) be.h2d_wait();
+		return rc;
+	}
+	int place_batch(long long n_pairs, const char *bases, const int64_t *base_off, const psvr_ori_t *ori)
 	{
 		P = n_pairs, R = 2 * n_pairs;
 		// a block of a larger batch may be handed over as a window of the batch's arrays: offsets then start at base_off[0] > 0
@@ -279,13 +342,11 @@ template <class BE> struct EngineCore {
 		// base before the transfer started -- 5 of an upload's 12 ms for 1 M pairs on eight threads, which a pipeline's three job slots
 		// took from the thread that drives the runs: the overlapped rate through the ABI was bound by it.
 		if (!d_bases || total_bases > in_cap_bases || R > in_cap_R) {
-			free_inputs();
 			in_cap_bases = total_bases + total_bases / 8 + 64, in_cap_R = R + R / 8 + 2;
-			d_bases = (char *)be.dalloc((size_t)in_cap_bases + 64);     // slack: the prep kernel loads whole 32-base groups
-			d_off = (long long *)be.dalloc((size_t)(in_cap_R + 1) * 8);
-			d_ori = (psvr_ori_t *)be.dalloc((size_t)in_cap_R * sizeof(psvr_ori_t));
-			d_nlist = (int32_t *)be.dalloc((size_t)(in_cap_R / 2 + 2) * 8);
-			if (!d_bases || !d_off || !d_ori || !d_nlist) { free_inputs(); err = "device allocation failed (batch)"; return PSVR_ERR_NOMEM; }
+			alloc_ok = true;
+			get(d_bases, in_cap_bases + 64);     // slack: the prep kernel loads whole 32-base groups
+			get(d_off, in_cap_R + 1), get(d_ori, in_cap_R), get(d_nlist, 2 * (in_cap_R / 2 + 2));
+			if (!alloc_ok) { d_bases.release(); err = "device allocation failed (batch)"; return PSVR_ERR_NOMEM; }
 		}
 		special.clear(), h_n_idx.clear();
 		V = 0;
@@ -314,41 +375,40 @@ template <class BE> struct EngineCore {
 		S = P + V + shadow_cap;
 		c.n_slots = S;
 		// keep every per-batch buffer (and the arenas) while the new batch fits
-		const bool fits = !owned.empty() && S <= cap_S && lm <= cap_lm && P <= cap_P;
+		const bool fits = S <= cap_S && lm <= cap_lm && P <= cap_P;
 		c.bases = d_bases - b0, c.base_off = d_off, c.ori = d_ori;
 		if (fits) {
 			upload_variants();
 			return PSVR_OK;
 		}
-		for (void *p : owned) be.dfree(p);
-		owned.clear();
 		cap_S = S, cap_lm = lm, cap_P = P;
 		c.lmax = lm;
 		c.wmax = c.lmax / 32 + 2;
 		const long long RS = 2 * S;                                 // reads incl. shadow slots
-		c.poff = alloc<long long>(S), c.rcnt = alloc<int32_t>(3 * S), d_noff = alloc<long long>(S);
-		c.hoff = alloc<long long>(RS), c.hcnt = alloc<int32_t>(RS), d_nhoff = alloc<long long>(RS);
-		c.active = alloc<uint8_t>(RS), c.unmapped = alloc<uint8_t>(RS), c.is_str = alloc<uint8_t>(RS), c.has_n4 = alloc<uint8_t>(RS);
-		c.has_mem = alloc<uint8_t>(RS);
-		c.str_list = alloc<int32_t>(RS), c.str_cnt = alloc<unsigned int>(4);
-		c.read_l = alloc<int32_t>(RS);
-		c.bin = alloc<uint8_t>((unsigned long long)RS * 2 * c.lmax);
-		c.rb = alloc<uint64_t>((unsigned long long)RS * 2 * c.wmax);
-		c.seed_list = alloc<uint8_t>((unsigned long long)RS * c.lmax);
-		c.strand = alloc<Strand>(2 * RS);
-		c.ccand = alloc<ChainCand>(12 * RS), c.n_ccand = alloc<int32_t>(RS);
-		c.rh = alloc<psvr_read_hdr_t>(RS), c.pres = alloc<psvr_pair_result_t>(S);
-		d_work = alloc<int32_t>(S), d_workp = alloc<int32_t>(P);
-		d_ctot = alloc<int32_t>(S), d_src = alloc<int32_t>(S), d_sens = alloc<uint8_t>(P), d_slist = alloc<int32_t>(P);
-		d_hprev = alloc<int32_t>(2 * S);
-		d_force = alloc<uint8_t>(8 * S), d_mask = alloc<uint8_t>(P), d_cmask = alloc<int32_t>(P);
-		d_hasn = alloc<uint8_t>(P), d_resel = alloc<int32_t>(P), d_resel4 = alloc<int32_t>(P < kReselCap ? P : kReselCap);
+		alloc_ok = true;
+		c.poff = get(cb.poff, S), c.rcnt = get(cb.rcnt, 3 * S), get(d_noff, S);
+		c.hoff = get(cb.hoff, RS), c.hcnt = get(cb.hcnt, RS), get(d_nhoff, RS);
+		c.active = get(cb.active, RS), c.unmapped = get(cb.unmapped, RS), c.is_str = get(cb.is_str, RS), c.has_n4 = get(cb.has_n4, RS);
+		c.has_mem = get(cb.has_mem, RS);
+		c.str_list = get(cb.str_list, RS), c.str_cnt = get(cb.str_cnt, 4);
+		c.read_l = get(cb.read_l, RS);
+		c.bin = get(cb.bin, (unsigned long long)RS * 2 * c.lmax);
+		c.rb = get(cb.rb, (unsigned long long)RS * 2 * c.wmax);
+		c.seed_list = get(cb.seed_list, (unsigned long long)RS * c.lmax);
+		c.strand = get(cb.strand, 2 * RS);
+		c.ccand = get(cb.ccand, 12 * RS), c.n_ccand = get(cb.n_ccand, RS);
+		c.rh = get(cb.rh, RS), c.pres = get(cb.pres, S);
+		get(d_work, S), get(d_workp, P);
+		get(d_ctot, S), get(d_src, S), get(d_sens, P), get(d_slist, P);
+		get(d_hprev, 2 * S);
+		get(d_force, 8 * S), get(d_mask, P), get(d_cmask, P);
+		get(d_hasn, P), get(d_resel, P), get(d_resel4, P < kReselCap ? P : kReselCap);
 		{
 			const long long nsp = S / 4 + 1;                 // (a special pair has >= 4 variant slots: whatever batch fits these buffers later has no more)
-			d_vsrc = alloc<int32_t>(S), d_spidx = alloc<int32_t>(nsp);
-			d_special = alloc<Special>(nsp), d_sp_class = alloc<uint8_t>(nsp), d_sp_adopted = alloc<int32_t>(nsp), d_sp_adopted_at = alloc<long long>(nsp);
+			get(d_vsrc, S), get(d_spidx, nsp);
+			get(d_special, nsp), get(d_sp_class, nsp), get(d_sp_adopted, nsp), get(d_sp_adopted_at, nsp);
 		}
-		d_tops = alloc<unsigned long long>(64), d_atops = alloc<unsigned long long>(6 * kTopStride), d_flags = alloc<int32_t>(16);
+		get(d_tops, 64), get(d_atops, 6 * kTopStride), get(d_flags, 16);
 		const long long R2 = RS;
 		cap_mem = (unsigned long long)2 * R2 * kMemSlot + (unsigned long long)R2 * 16 + 4096;
 		cap_us = (unsigned long long)R2 * 48 + 65536;
@@ -366,10 +426,8 @@ template <class BE> struct EngineCore {
 				cap_mem = slots + (cap_mem - slots) / n + 64;
 			}
 		}
-		c.stats = alloc<unsigned long long>(16);
-		for (void *p : owned) if (!p) { err = "device allocation failed"; return PSVR_ERR_NOMEM; }
-		free_arenas();
-		if (!alloc_arenas()) { err = "device allocation failed (arenas)"; return PSVR_ERR_NOMEM; }
+		c.stats = get(cb.stats, 16);
+		if (!alloc_ok || !alloc_arenas()) { cap_S = 0; err = "device allocation failed"; return PSVR_ERR_NOMEM; }
 		c.err = d_flags + 6, c.stale_open = d_flags + 7, c.any_h = d_flags + 8;
 		upload_variants();
 		return PSVR_OK;
@@ -409,24 +467,18 @@ template <class BE> struct EngineCore {
 		}
 	}
 
-	void free_arenas()
-	{
-		for (void *p : {(void *)c.mem.base, (void *)c.us.base, (void *)c.path, (void *)c.seg.base, (void *)c.dp.base, (void *)c.cw.base, (void *)c.cig.base, (void *)c.cand})
-			if (p) be.dfree(p);
-		c.mem.base = nullptr, c.us.base = nullptr, c.path = nullptr, c.seg.base = nullptr, c.dp.base = nullptr, c.cw.base = nullptr, c.cig.base = nullptr, c.cand = nullptr;
-	}
 	bool alloc_arenas()
 	{
-		c.mem.base = (VMem *)be.dalloc(cap_mem * sizeof(VMem)), c.us.base = (USeed *)be.dalloc(cap_us * sizeof(USeed)), c.path = (PathN *)be.dalloc(cap_us * sizeof(PathN));
-		c.seg.base = (Seg *)be.dalloc(cap_seg * sizeof(Seg)), c.dp.base = (DpDesc *)be.dalloc(cap_dp * sizeof(DpDesc));
-		c.cw.base = (CandWork *)be.dalloc(cap_cw * sizeof(CandWork)), c.cig.base = (uint32_t *)be.dalloc(cap_cig * 4);
-		c.cand = (psvr_cand_t *)be.dalloc(cap_cw * sizeof(psvr_cand_t));       // candidate records share the CandWork arena's indices
+		alloc_ok = true;
+		c.mem.base = get(cb.mem, cap_mem), c.us.base = get(cb.us, cap_us), c.path = get(cb.path, cap_us);
+		c.seg.base = get(cb.seg, cap_seg), c.dp.base = get(cb.dp, cap_dp), c.cw.base = get(cb.cw, cap_cw), c.cig.base = get(cb.cig, cap_cig);
+		c.cand = get(cb.cand, cap_cw);       // candidate records share the CandWork arena's indices
 		c.mem.top = d_atops + 0 * kTopStride, c.us.top = d_atops + 1 * kTopStride, c.seg.top = d_atops + 2 * kTopStride, c.dp.top = d_atops + 3 * kTopStride, c.cw.top = d_atops + 4 * kTopStride, c.cig.top = d_atops + 5 * kTopStride;
 		c.mem.cap = cap_mem, c.us.cap = cap_us, c.seg.cap = cap_seg, c.dp.cap = cap_dp, c.cw.cap = cap_cw, c.cig.cap = cap_cig;
 		c.mem.nshard = c.dp.nshard = c.cw.nshard = c.cig.nshard = 1;          // mem: fixed slots in front; dp, cw: their ids are ranges the host plans on; cig: downloaded as one piece
 		c.us.nshard = c.seg.nshard = BE::kArenaShards;
 		c.mem.overflow = d_flags + 0, c.us.overflow = d_flags + 1, c.seg.overflow = d_flags + 2, c.dp.overflow = d_flags + 3, c.cw.overflow = d_flags + 4, c.cig.overflow = d_flags + 5;
-		return c.mem.base && c.us.base && c.path && c.seg.base && c.dp.base && c.cw.base && c.cig.base && c.cand;
+		return alloc_ok;
 	}
 	// a scratch arena overflowed (repeat-rich reads expand to many seeds): grow it 4x and run the batch again
 	int grow_and_rerun(const int32_t *flags, int trace, bool want_stats, int depth)
@@ -437,32 +489,25 @@ template <class BE> struct EngineCore {
 		if (flags[0]) cap_mem += (unsigned long long)4 * S * kMemSlot;
 		fprintf(stderr, "[psvr] scratch arena overflow (mem %d us %d seg %d dp %d cand %d cigar %d): growing 4x and re-running the batch\n", flags[0], flags[1], flags[2], flags[3],
 		        flags[4], flags[5]);
-		free_arenas();
-		if (!alloc_arenas()) { err = "device allocation failed while growing arenas"; return PSVR_ERR_NOMEM; }
+		if (!alloc_arenas()) { cap_S = 0; err = "device allocation failed while growing arenas"; return PSVR_ERR_NOMEM; }
 		return run(trace, want_stats, depth + 1);
 	}
 
+	// the DP stage's buffers for n problems and qb / tb / cw bytes and CIGAR words: grown to need + need / 4 + 1024 when a round needs more
 	bool ensure_dp(long long n, long long qb, long long tb, long long cw)
 	{
-		auto grow = [&](void **p, long long &cap, long long need, size_t el) {
-			if (need <= cap && *p) return true;
-			if (*p) be.dfree(*p);
-			cap = need + need / 4 + 1024;
-			*p = be.dalloc(cap * el);
-			return *p != nullptr;
-		};
-		bool ok = true;
-		if (n + 2 > dp_cap_n || !dp.qlen) {
-			long long cap = 0;
-			void **arr[5] = {(void **)&dp.qlen, (void **)&dp.tlen, (void **)&dp.q_off, (void **)&dp.t_off, (void **)&dp.ez};
-			const size_t el[5] = {4, 4, 8, 8, sizeof(psvr_extz_t)};
-			for (int k = 0; k < 5; ++k) { cap = 0; if (*arr[k]) be.dfree(*arr[k]); *arr[k] = nullptr; ok &= grow(arr[k], cap, n + 2, el[k]); }
-			dp_cap_n = cap;
+		auto room = [](long long need) { return need + need / 4 + 1024; };
+		alloc_ok = true;
+		if (n + 2 > dp_cap_n) {
+			dp_cap_n = room(n + 2);
+			dp.qlen = get(dpb.qlen, dp_cap_n), dp.tlen = get(dpb.tlen, dp_cap_n), dp.q_off = get(dpb.q_off, dp_cap_n), dp.t_off = get(dpb.t_off, dp_cap_n);
+			dp.ez = get(dpb.ez, dp_cap_n);
 		}
-		ok &= grow((void **)&dp.qbuf, dp_cap_q, qb + 64, 1);
-		ok &= grow((void **)&dp.tbuf, dp_cap_t, tb + 64, 1);
-		ok &= grow((void **)&dp.cig, dp_cap_c, cw + 64, 4);
-		return ok;
+		if (qb + 64 > dp_cap_q) dp.qbuf = get(dpb.qbuf, dp_cap_q = room(qb + 64));
+		if (tb + 64 > dp_cap_t) dp.tbuf = get(dpb.tbuf, dp_cap_t = room(tb + 64));
+		if (cw + 64 > dp_cap_c) dp.cig = get(dpb.cig, dp_cap_c = room(cw + 64));
+		if (!alloc_ok) dp_cap_n = dp_cap_q = dp_cap_t = dp_cap_c = 0;     // (every one of them again next time)
+		return alloc_ok;
 	}
 
 	// the stages of one round over a list of slots: mate 0, then mate 1 (continues mate 0's draws), then the
@@ -480,7 +525,7 @@ template <class BE> struct EngineCore {
 		be.st_walk(c, work, nwork + nwalk);
 		unsigned long long tops[kTopStride + 1];                             // from the dp counter to the cw counter
 		int32_t fl[16];
-		be.d2h2(tops, d_atops + 3 * kTopStride, sizeof tops, fl, d_flags, 64);
+		mem.d2h({{tops, d_atops + 3 * kTopStride, sizeof tops}, {fl, d_flags, 64}});
 		if (fl[8]) any_h = true;
 		long long dp_end = (long long)tops[0], cw_end = (long long)tops[kTopStride];
 		if (fl[7]) stats.stale_open = 1;
@@ -694,28 +739,27 @@ template <class BE> struct EngineCore {
 				const bool classify = want_vcnt && !special.empty();
 				if (classify) be.st_special_class(c, d_special, (long long)special.size(), d_mask, d_sp_class);
 				enqueue_offset_scans();
-				int32_t *late = want_vcnt ? be.d2h_early_late(nnew_chg, d_tops + 8, 16, classify ? h_sp_class.data() : nullptr, d_sp_class, classify ? special.size() : 0,
-				                                              c.rcnt + 3 * P, (size_t)3 * V * 4)
-				                          : (be.d2h(nnew_chg, d_tops + 8, 16), (int32_t *)nullptr);
+				int32_t *late = want_vcnt ? mem.d2h_early_late({{nnew_chg, d_tops + 8, 16}, {h_sp_class.data(), d_sp_class, classify ? special.size() : 0}}, c.rcnt + 3 * P, (size_t)3 * V * 4)
+				                          : (mem.d2h(nnew_chg, d_tops + 8, 16), (int32_t *)nullptr);
 				if (classify) for (size_t i = 0; i < special.size(); ++i) if (h_sp_class[i] && is_special[i] == 1) is_special[i] = 2;
 				build_listed();
-				be.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data(), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0);
+				mem.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data());
 				if (want_vcnt) {
-					be.d2h_late_done();                      // (the gather's synchronisation has brought the late copy in as well; no list, no gather: waits here)
+					mem.d2h_late_done();                      // (the gather's synchronisation has brought the late copy in as well; no list, no gather: waits here)
 					// the table is read at random by the walk below: out of the page-locked region the DMA engine has just written every
 					// row is a miss to memory (~170 ns per pair measured: 0.45 ms for 2.9 k pairs); one streaming copy (1 MB, ~35 us) puts it in
 					// the CPU's caches
 					if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
 					else if (late) memcpy(vcnt.data(), late, (size_t)3 * V * 4);
-					else be.d2h(vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4);
+					else mem.d2h(vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4);
 					build_rows();
 				}
 				gathered = true;
 			} else if (want_vcnt) {
 				if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
-				be.d2h2(nnew_chg, d_tops + 8, 16, vcnt.data(), c.rcnt + 3 * P, 3 * V * 4);
+				mem.d2h({{nnew_chg, d_tops + 8, 16}, {vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4}});
 			}
-			else be.d2h(nnew_chg, d_tops + 8, 16);
+			else mem.d2h(nnew_chg, d_tops + 8, 16);
 			const unsigned long long nnew = nnew_chg[0];
 			// A re-run round in which every slot drew exactly as often as at its previous evaluation leaves every offset where it is: the
 			// streams are consistent, the bookkeeping below would find nothing dirty.
@@ -723,7 +767,7 @@ template <class BE> struct EngineCore {
 			// window tables of the pairs evaluated with offset shadows this round
 			if (nshadow > 0) {
 				std::vector<int32_t> tot(nshadow);
-				be.d2h(tot.data(), d_ctot + (P + V), nshadow * 4);
+				mem.d2h(tot.data(), d_ctot + (P + V), nshadow * 4);
 				size_t sh = 0;
 				for (Win &w : wins) {
 					w.off.clear(), w.tot.clear();
@@ -732,7 +776,7 @@ template <class BE> struct EngineCore {
 			}
 			if (nnew) {
 				std::vector<int32_t> add(nnew);
-				be.d2h(add.data(), d_slist, nnew * 4);
+				mem.d2h(add.data(), d_slist, nnew * 4);
 				for (int32_t s : add) {
 					for (size_t i = 0; i < special.size(); ++i) if (special[i].pair == s) is_special[i] = 0;
 					Win w; w.pair = s, w.eval_off = -1, w.eval_tot = 0;
@@ -748,7 +792,7 @@ template <class BE> struct EngineCore {
 			if (!gathered) {
 				enqueue_offset_scans();
 				build_listed();
-				be.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data(), nullptr, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 0);
+				mem.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data());
 			}
 			// walk O_{s+1} = O_s + D_s through the tables
 			{
@@ -822,7 +866,7 @@ template <class BE> struct EngineCore {
 				stats.walk_pairs += (long long)listed.size();
 				stats.walk_us += (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - walk_t0).count();
 			}
-			if (!listed.empty()) be.scatter_listed_i32(d_ctot, res.data(), (long long)listed.size());   // same indices as gather_listed
+			if (!listed.empty()) mem.scatter_listed_i32(d_ctot, res.data(), (long long)listed.size());   // same indices as gather_listed
 			// new offsets from the totals; which pairs drew from a stale offset?
 			be.st_scan(d_ctot, P, 1, 0, grand_pos, d_noff);
 			// (the two list counters in cache lines of their own: d_tops[32], d_tops[48])
@@ -845,7 +889,7 @@ template <class BE> struct EngineCore {
 			unsigned long long tops[53];                    // d_tops[8..60]: [0] newly count-sensitive, [1] any count changed, from [24] on the lists' counters, [52] adoptions made on the device
 			const unsigned long long *nd17 = tops + 24;     // [0] full re-runs, [16] pairing only, [24] tie-only pairs seen, [25] of those: on from the walk
 			int32_t flags[16];
-			be.d2h2(tops, d_tops + 8, sizeof tops, flags, d_flags, 64);
+			mem.d2h({{tops, d_tops + 8, sizeof tops}, {flags, d_flags, 64}});
 			if (flags[8]) any_h = true;
 			stats.adopted += (long long)tops[52];
 			const unsigned long long nd[2] = {nd17[0], nd17[16]};
@@ -894,7 +938,7 @@ template <class BE> struct EngineCore {
 			if (nwalk) be.append_list(d_work, nfull + nshadow, d_resel4, nwalk);   // ... then the pairs that go on from the walk
 		}
 		c.stats = stats_ptr;
-		if (rc == PSVR_OK && want_stats) be.d2h(stats.counters, stats_ptr, 16 * 8);
+		if (rc == PSVR_OK && want_stats) mem.d2h(stats.counters, stats_ptr, 16 * 8);
 		return rc;
 	}
 
@@ -906,7 +950,7 @@ template <class BE> struct EngineCore {
 		// the last pair's offset + draw count of each stream (one readback: poff[P-1], then hoff / hcnt of the pair are neighbours)
 		long long lo, ho[2];
 		int32_t lc, hc[2];
-		be.d2h4(&lo, c.poff + (P - 1), 8, &lc, d_ctot + (P - 1), 4, ho, c.hoff + 2 * (P - 1), 16, hc, c.hcnt + 2 * (P - 1), 8);
+		mem.d2h({{&lo, c.poff + (P - 1), 8}, {&lc, d_ctot + (P - 1), 4}, {ho, c.hoff + 2 * (P - 1), 16}, {hc, c.hcnt + 2 * (P - 1), 8}});
 		out[0] = lo + lc, out[1] = ho[0] + hc[0], out[2] = ho[1] + hc[1];
 	}
 
