@@ -312,6 +312,15 @@ int psvr_engine_stats(const psvr_engine_t *eng, char *buf, size_t buflen);
 int64_t psvr_bgzf_bound(int64_t n_bytes);
 int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, void *out, int64_t out_cap, int64_t *out_bytes);
 
+/* ---- Stable order of 64-bit keys on the device (the coordinate sort of the BAM output) -------------------------------------------------
+ * Replaces, for `panSVR aln --sort` and `panSVR sort`, the ordering step of `samtools sort` that panSVR_run.sh:53 runs between `aln` and
+ * `fc_sv` (samtools bam_sort.c: the key (uint64)tid << 32 | (uint32)(pos + 1) << 1 | reverse, ties in input order).
+ * order[i] = index of the i-th smallest key; equal keys keep ascending index (stable).
+ * Host pointers; 0 <= n < 2^32 (else PSVR_ERR_UNSUPPORTED); runs on HIP device `device`.  An LSD radix sort with 8-bit digits in tiles of
+ * 2048 keys; passes whose digit is the same for every key are skipped.  Device memory: about 24 bytes per key, allocated per call
+ * (PSVR_ERR_NOMEM with the byte count in psvr_last_error() when it does not fit). */
+int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *order);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@
 #include "index_build.h"
 #include "signal_step.h"
 #include "bam_sort.h"
+#include "sorted_bam.h"
 
 using namespace psvr;
 
@@ -54,6 +55,7 @@ struct Opt {
 	bool sig_all = false, sig_discard = false;   // BAM input: fc_signal's -D / -U
 	int bam_level = -1;                          // zlib level of the BGZF blocks (-1 = zlib's default, what htslib's "wb" uses)
 	bool bgzf_device = false;                    // the main file's BGZF blocks compressed on the first device (psvr_bgzf_compress)
+	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 };
 
 static int usage()
@@ -91,6 +93,9 @@ static int usage()
 	        "        --bgzf-fast              BGZF blocks from the built-in encoder on the -t threads (1.6x the speed of level 1, blocks ~10%% larger)\n"
 	        "        --bgzf-device            compress the BAM output's BGZF blocks on the GPU (a lane per block; ~10 %% larger than zlib level 1,\n"
 	        "                                 the host's deflate is what bounds the BAM route otherwise)\n"
+	        "        --sort                   write the main output (-o) coordinate-sorted with its index <out>.bai, as `panSVR sort`\n"
+	        "                                 would from the unsorted file (ordered on the first device of --devices; not with -S,\n"
+	        "                                 --compress-level, --bgzf-fast or --bgzf-device)\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -178,17 +183,19 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
 	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv);
 	if (argc < 2 || (strcmp(argv[1], "aln") && strcmp(argv[1], "fc_aln"))) {
-		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n");
+		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n"
+		                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 		return 1;
 	}
 	Opt o;
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	bool sig_by_name = false;
+	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
 	optind = 2;
 	while ((c = getopt_long(argc, argv, "t:O:P:E:F:M:m:z:w:o:p:QSR:DUN", lo, NULL)) >= 0) {
 		switch (c) {
@@ -204,7 +211,7 @@ int main(int argc, char **argv)
 		case 'o': o.out = optarg; break;
 		case 'p': o.out_ori = optarg; break;
 		case 'Q': o.not_ori = true; break;
-		case 'S': o.sam = true; break;
+		case 'S': o.sam = true; if (!sort_conflict) sort_conflict = "-S"; break;
 		case 'R': o.max_use_read = atoll(optarg); break;
 		case 1000: o.devices = {atoi(optarg)}; break;
 		case 1001: o.records = optarg; break;
@@ -213,14 +220,19 @@ int main(int argc, char **argv)
 		case 1004: if (!parse_devices(optarg, &o.devices)) { fprintf(stderr, "bad --devices list '%s'\n", optarg); return 1; } break;
 		case 1005: o.batch_bases = atoll(optarg); break;
 		case 1007: o.sub_pairs = atoll(optarg); break;
-		case 1008: o.bgzf_device = true; break;
-		case 1009: o.bam_level = psvr::BgzfWriter::kLevelFast; break;
-		case 1006: o.bam_level = atoi(optarg); if (o.bam_level < -1 || o.bam_level > 9) { fprintf(stderr, "--compress-level wants -1 .. 9\n"); return 1; } break;
+		case 1008: o.bgzf_device = true; if (!sort_conflict) sort_conflict = "--bgzf-device"; break;
+		case 1009: o.bam_level = psvr::BgzfWriter::kLevelFast; if (!sort_conflict) sort_conflict = "--bgzf-fast"; break;
+		case 1006: o.bam_level = atoi(optarg); if (o.bam_level < -1 || o.bam_level > 9) { fprintf(stderr, "--compress-level wants -1 .. 9\n"); return 1; } if (!sort_conflict) sort_conflict = "--compress-level"; break;
+		case 1010: o.sort = true; break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
 		case 'N': sig_by_name = true; break;
 		default: return usage();
 		}
+	}
+	if (o.sort && sort_conflict) {
+		fprintf(stderr, "--sort cannot be combined with %s: the sorted file is BAM compressed as `panSVR sort` compresses it\n", sort_conflict);
+		return 1;
 	}
 	if (argc - optind < 3) return usage();
 	if (!(o.thread_n >= 1 && o.thread_n <= 48)) { fprintf(stderr, "Input error: thread_n cannot be less than 1 or more than 48\n"); abort(); }   // xassert, rr.hpp:121
@@ -285,7 +297,9 @@ int main(int argc, char **argv)
 	if (from_bam) fq.open_feed(&feed);
 	else if (!fq.open(fq_path.c_str())) { fprintf(stderr, "%s\n", fq.error().c_str()); abort(); }
 	OutFile fo, fo_ori;
-	if (!fo.open(o.out, !o.sam, H, o.thread_n, o.bam_level) || !fo_ori.open(o.out_ori, !o.sam, H, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
+	if ((!o.sort && !fo.open(o.out, !o.sam, H, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
+	SortRecords sorted;                                  // --sort: the main file's records, kept until the input ends
+	static const char *kSortNoMem = "[panSVR-amd] --sort: out of host memory for the main file's records; run `panSVR aln` without --sort, then `panSVR sort` on its output\n";
 	if (o.bgzf_device && !o.sam) fo.bam.set_device(o.devices[0]), fo_ori.bam.set_device(o.devices[0]);
 	FILE *frec = o.records.empty() ? nullptr : fopen(o.records.c_str(), "w");
 	fprintf(stderr, "Processing file: [%s].\n", o.reads.c_str());
@@ -417,7 +431,14 @@ int main(int argc, char **argv)
 			wait_state(J, 3);
 			if (J.last) return;
 			const double tw = walltime();
-			for (size_t ci = 0; ci < J.mb.size(); ++ci) fo.write_raw(J.mb[ci]), fo_ori.write_raw(J.ob[ci]);
+			if (o.sort) {
+				try {
+					for (size_t ci = 0; ci < J.mb.size(); ++ci)
+						if (!sorted.add_stream(J.mb[ci].data(), J.mb[ci].size())) { fprintf(stderr, "[panSVR-amd] --sort: malformed record from the formatter\n"); abort(); }
+				} catch (const std::bad_alloc &) { fputs(kSortNoMem, stderr); _exit(2); }
+				for (size_t ci = 0; ci < J.ob.size(); ++ci) fo_ori.write_raw(J.ob[ci]);
+			} else
+				for (size_t ci = 0; ci < J.mb.size(); ++ci) fo.write_raw(J.mb[ci]), fo_ori.write_raw(J.ob[ci]);
 			t_write += walltime() - tw;
 			mark(3, n_wr_pieces++, tw, walltime());
 			set_state(J, 0);
@@ -527,7 +548,24 @@ int main(int argc, char **argv)
 		sig_thread.join();
 		if (sig_rc) { fprintf(stderr, "[panSVR-amd] the signal step failed\n"); abort(); }
 	}
-	if (!fo.close() || !fo_ori.close()) { fprintf(stderr, "fail to write output file\n"); abort(); }
+	if ((!o.sort && !fo.close()) || !fo_ori.close()) { fprintf(stderr, "fail to write output file\n"); abort(); }
+	double t_sort = 0, t_sort_order = 0;
+	if (o.sort) {                                        // the main file: the records ordered on the first device, written with the index
+		const double ts = walltime();
+		try {
+			std::vector<uint32_t> ord;
+			bool on_device = false;
+			std::string err;
+			if (!coordinate_order(sorted, o.devices[0], ord, &on_device, &err)) { fprintf(stderr, "[panSVR-amd] --sort: device order: %s\n", err.c_str()); return 2; }
+			t_sort_order = walltime() - ts;
+			fprintf(stderr, "[panSVR-amd] --sort: %zu records (%.1f MB) ordered %s in %.1f ms\n", sorted.size(), sorted.bytes / 1e6, on_device ? "on the device" : "on the host",
+			        t_sort_order * 1e3);
+			std::vector<std::pair<std::string, int32_t>> refs;
+			for (size_t i = 0; i < H.names.size(); ++i) refs.push_back({H.names[i], (int32_t)H.lens[i]});
+			if (!write_sorted_bam(o.out, H.text, refs, sorted, ord, false, o.thread_n, &err)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
+		} catch (const std::bad_alloc &) { fputs(kSortNoMem, stderr); return 2; }
+		t_sort = walltime() - ts;
+	}
 	if (frec) fclose(frec);
 	const double wall = walltime() - wall0;              // first FASTQ byte to the files closed; giving the HBM back is reported beside it, like the index load
 	for (int d = 0; d < D; ++d) if (eng[(size_t)d]) psvr_engine_destroy(eng[(size_t)d]);
@@ -551,8 +589,8 @@ int main(int argc, char **argv)
 	fprintf(stderr, "[panSVR-amd] wall: read+parse %.3f s, engine (upload+run+download) %.3f s, format %.3f s, write%s %.3f s\n", t_read, t_engine, t_format, o.sam ? "" : "+compress", t_write);
 	fprintf(stderr,
 	        "[panSVR-amd] e2e_json {\"pairs\":%lld,\"batches\":%lld,\"pieces\":%lld,\"devices\":%d,\"threads\":%d,\"wall_s\":%.4f,\"index_s\":%.4f,\"index_first_s\":%.4f,\"index_clone_s\":%.4f,\"read_parse_s\":%.4f,"
-	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f}\n",
-	        total_pairs, n_ref_batches, n_batches, D, o.thread_n, wall, t_index, t_idx_first, t_idx_clone, t_read, t_engine, t_exchange, rebase_iters, t_format, t_write, d2h_bytes, hbm_first, hbm_last,
+	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f}\n",
+	        total_pairs, n_ref_batches, n_batches, D, o.thread_n, wall, t_index, t_idx_first, t_idx_clone, t_read, t_engine, t_exchange, rebase_iters, t_format, t_write, t_sort, t_sort_order, d2h_bytes, hbm_first, hbm_last,
 	        (long long)emit_stats.dropped, t_teardown);
 	return 0;
 }

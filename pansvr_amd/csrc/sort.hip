@@ -1,0 +1,180 @@
+// sort.hip -- psvr_sort_order_u64 (include/psvr_engine.h): the stable order of n 64-bit keys, as an LSD radix sort with 8-bit digits.
+// `panSVR aln --sort` and `panSVR sort` order their records by samtools' coordinate key with it (sorted_bam.h).
+//   histogram: one read of the keys builds all eight digit histograms (a slab per workgroup, summed by a second launch); the host
+//              reads them back and skips every pass whose digit is the same for every key
+//   per pass:  k_sort_count (digit counts per tile of kSortTile keys, stored in (digit, tile) order) -> the exclusive scan of scan.h
+//              -> k_sort_scatter (a stable rank inside the tile from per-wavefront ballots, the wavefronts' offsets through LDS)
+// Every phase hands over to the next at a kernel boundary: no workgroup waits for another inside a launch.
+#include <hip/hip_runtime.h>
+#include <mutex>
+#include <vector>
+#include "../../include/psvr_engine.h"
+#include "common.h"
+#include "scan.h"
+
+namespace psvr {
+
+static const int kSortThreads = 256, kSortItems = 8, kSortTile = kSortThreads * kSortItems;   // 2048 keys per tile, 512 per wavefront
+static const int kSortWaves = kSortThreads / 64;
+static const int kHistBlocks = 1024;
+
+// the eight digit histograms of this workgroup's share of the keys (grid-stride), counted in LDS, stored as its slab of 8 x 256
+__global__ __launch_bounds__(256) void k_sort_hist(const uint64_t *keys, long long n, uint32_t *slab)
+{
+	__shared__ uint32_t h[8 * 256];
+	for (int i = threadIdx.x; i < 8 * 256; i += 256) h[i] = 0;
+	__syncthreads();
+	for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+		const uint64_t k = keys[i];
+#pragma unroll
+		for (int d = 0; d < 8; ++d) atomicAdd(&h[d * 256 + (int)((k >> (8 * d)) & 255)], 1u);
+	}
+	__syncthreads();
+	for (int i = threadIdx.x; i < 8 * 256; i += 256) slab[(size_t)blockIdx.x * 2048 + i] = h[i];
+}
+// the slabs summed: hist[d * 256 + v] = keys whose digit d is v
+__global__ __launch_bounds__(256) void k_sort_hist_sum(const uint32_t *slab, int n_slab, uint32_t *hist)
+{
+	const int j = blockIdx.x * 256 + threadIdx.x;
+	uint32_t s = 0;
+	for (int b = 0; b < n_slab; ++b) s += slab[(size_t)b * 2048 + j];
+	hist[j] = s;
+}
+// digit counts of tile t, stored at cnt[digit * ntile + t]: the scan over that order gives every (digit, tile) its first output slot
+__global__ __launch_bounds__(kSortThreads) void k_sort_count(const uint64_t *keys, long long n, int shift, long long ntile, int32_t *cnt)
+{
+	__shared__ int32_t h[256];
+	h[threadIdx.x] = 0;
+	__syncthreads();
+	const long long t = blockIdx.x, base = t * kSortTile;
+#pragma unroll
+	for (int r = 0; r < kSortItems; ++r) {
+		const long long i = base + r * kSortThreads + threadIdx.x;
+		if (i < n) atomicAdd(&h[(int)((keys[i] >> shift) & 255)], 1);
+	}
+	__syncthreads();
+	cnt[threadIdx.x * ntile + t] = h[threadIdx.x];
+}
+// the stable scatter of tile t.  Wavefront w holds keys [base + 512 w, base + 512 (w + 1)) in 8 rounds of 64 (lane order = input order).
+// A round's lanes with equal digits find each other by 8 ballots; a key's rank is the number of earlier keys of its digit in the
+// wavefront: the wavefront's running count (LDS) plus the matching lanes below it (mbcnt).  The group's lowest lane moves the count on.
+// Then per digit the wavefronts' counts become offsets in wavefront order, on top of the scanned (digit, tile) offset.
+// iin == nullptr: the first pass, the index is the position.
+__global__ __launch_bounds__(kSortThreads) void k_sort_scatter(const uint64_t *kin, const uint32_t *iin, long long n, int shift, long long ntile, const long long *off,
+                                                               uint64_t *kout, uint32_t *iout)
+{
+	__shared__ uint32_t wcnt[kSortWaves][256];
+	for (int i = threadIdx.x; i < kSortWaves * 256; i += kSortThreads) (&wcnt[0][0])[i] = 0;
+	__syncthreads();
+	const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+	const long long t = blockIdx.x, base = t * kSortTile + (long long)w * 64 * kSortItems;
+	uint64_t key[kSortItems];
+	uint32_t idx[kSortItems], rank[kSortItems];
+	int dig[kSortItems];
+#pragma unroll
+	for (int r = 0; r < kSortItems; ++r) {
+		const long long i = base + r * 64 + lane;
+		const bool ok = i < n;
+		key[r] = ok ? kin[i] : 0;
+		idx[r] = ok ? (iin ? iin[i] : (uint32_t)i) : 0;
+	}
+	const unsigned long long below = (1ull << lane) - 1;
+#pragma unroll
+	for (int r = 0; r < kSortItems; ++r) {
+		const bool ok = base + r * 64 + lane < n;
+		const int d = (int)((key[r] >> shift) & 255);
+		unsigned long long m = __ballot(ok);
+#pragma unroll
+		for (int b = 0; b < 8; ++b) {
+			const unsigned long long v = __ballot((d >> b) & 1);
+			m &= ((d >> b) & 1) ? v : ~v;
+		}
+		const uint32_t before = wcnt[w][d];
+		rank[r] = before + (uint32_t)__popcll(m & below);
+		dig[r] = d;
+		__builtin_amdgcn_wave_barrier();                           // every lane has read the count before the group's lowest lane moves it
+		if (ok && (m & below) == 0) wcnt[w][d] = before + (uint32_t)__popcll(m);
+		__builtin_amdgcn_wave_barrier();
+	}
+	__syncthreads();
+	{
+		const int d = threadIdx.x;                                 // kSortThreads == 256 digits
+		uint32_t s = (uint32_t)off[(long long)d * ntile + t];      // < n < 2^32
+		for (int q = 0; q < kSortWaves; ++q) { const uint32_t c = wcnt[q][d]; wcnt[q][d] = s; s += c; }
+	}
+	__syncthreads();
+#pragma unroll
+	for (int r = 0; r < kSortItems; ++r) {
+		if (base + r * 64 + lane >= n) continue;
+		const uint32_t p = wcnt[w][dig[r]] + rank[r];
+		if (p < n) kout[p] = key[r], iout[p] = idx[r];             // (always: the counts and the ranks see the same keys)
+	}
+}
+
+struct SortCtx {
+	std::mutex mu;
+	int device = -1;
+	hipStream_t stream = nullptr;
+};
+static SortCtx &sort_ctx() { static SortCtx c; return c; }
+
+} // namespace psvr
+
+using namespace psvr;
+
+extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *order)
+{
+	if (n < 0 || (n > 0 && (!keys || !order))) return set_error(PSVR_ERR_ARG, "psvr_sort_order_u64: bad argument");
+	if (n >= ((int64_t)1 << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_sort_order_u64: %lld keys, the order is 32-bit (at most 2^32 - 1 keys)", (long long)n);
+	if (n == 0) return PSVR_OK;
+	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
+	SortCtx &c = sort_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	PSVR_HIP(hipSetDevice(device));
+	if (c.device != device) {
+		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
+		PSVR_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+		c.device = device;
+	}
+	hipStream_t st = c.stream;
+	const long long ntile = (n + kSortTile - 1) / kSortTile, ncnt = 256 * ntile;
+	const int nhb = (int)(ntile < kHistBlocks ? ntile : kHistBlocks);
+	// two key arrays and two index arrays (ping-pong), the (digit, tile) counts and offsets, the scan's and the histogram's scratch
+	const size_t need = (size_t)n * 24 + (size_t)ncnt * 12 + scan_tmp_bytes(1, ncnt) + (size_t)(nhb + 1) * 8192;
+	size_t free_b = 0, total_b = 0;
+	PSVR_HIP(hipMemGetInfo(&free_b, &total_b));
+	if (need > free_b) return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_u64: %zu bytes of device memory needed for %lld keys, %zu free", need, (long long)n, free_b);
+	DevBuf k0, k1, i0, i1, cnt, off, tmp, slab, hist;
+	if (k0.alloc((size_t)n * 8) || k1.alloc((size_t)n * 8) || i0.alloc((size_t)n * 4) || i1.alloc((size_t)n * 4) || cnt.alloc((size_t)ncnt * 4) ||
+	    off.alloc((size_t)ncnt * 8) || tmp.alloc(scan_tmp_bytes(1, ncnt)) || slab.alloc((size_t)nhb * 8192) || hist.alloc(8192)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_u64: %zu bytes of device memory needed for %lld keys", need, (long long)n);
+	}
+	PSVR_HIP(hipMemcpyAsync(k0.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, st));
+	hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nhb), dim3(256), 0, st, k0.as<uint64_t>(), (long long)n, slab.as<uint32_t>());
+	hipLaunchKernelGGL(k_sort_hist_sum, dim3(8), dim3(256), 0, st, (const uint32_t *)slab.p, nhb, hist.as<uint32_t>());
+	PSVR_HIP(hipGetLastError());
+	std::vector<uint32_t> h(2048);
+	PSVR_HIP(hipMemcpyAsync(h.data(), hist.p, 8192, hipMemcpyDeviceToHost, st));
+	PSVR_HIP(hipStreamSynchronize(st));
+	uint64_t *kin = k0.as<uint64_t>(), *kout = k1.as<uint64_t>();
+	uint32_t *iin = nullptr, *iout = i0.as<uint32_t>();
+	for (int d = 0; d < 8; ++d) {
+		bool constant = false;
+		for (int v = 0; v < 256; ++v) if (h[(size_t)d * 256 + v] == (uint32_t)n) constant = true;
+		if (constant) continue;                                    // this digit orders nothing
+		hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (long long)n, 8 * d, ntile, cnt.as<int32_t>());
+		ScanSet S = {};
+		S.cnt[0] = cnt.as<int32_t>(), S.out[0] = off.as<long long>(), S.stride[0] = 1;
+		scan_launch(S, 1, ncnt, tmp.as<long long>(), st);
+		hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (const uint32_t *)iin, (long long)n, 8 * d, ntile,
+		                   (const long long *)off.p, kout, iout);
+		PSVR_HIP(hipGetLastError());
+		std::swap(kin, kout);
+		iin = iout, iout = (iout == i0.as<uint32_t>()) ? i1.as<uint32_t>() : i0.as<uint32_t>();
+	}
+	if (iin) PSVR_HIP(hipMemcpyAsync(order, iin, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+	PSVR_HIP(hipStreamSynchronize(st));
+	if (!iin) for (int64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;   // every digit constant: all keys equal, the input order stands
+	return PSVR_OK;
+}

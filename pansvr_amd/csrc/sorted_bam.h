@@ -1,0 +1,247 @@
+// sorted_bam.h -- the sorted BAM writer shared by `panSVR sort` (bam_sort.h) and `panSVR aln --sort` (cli_main.cpp): what
+// `samtools sort` + `samtools index` produce between the `aln` and `fc_sv` steps of panSVR_run.sh (lines 53-54).  Host C++ above the C ABI.
+//   SortRecords          the encoded records (block_size + body, the fixed part re-encoded with the bin taken from the CIGAR's span)
+//                        and samtools' coordinate key of each
+//   coordinate_order     samtools' order (bam_sort.c bam1_lt): reference id as unsigned (unplaced records last), position, forward strand
+//                        before reverse, ties in input order.  On the device (psvr_sort_order_u64) when one is visible and every
+//                        position lies in SAMv1's range; otherwise std::stable_sort on the host.
+//   write_sorted_bam     the header with SO rewritten, the records in the given order in BGZF blocks of 0xff00 bytes compressed on
+//                        `threads` threads, and (coordinate order) the .bai of SAMv1 section 5.2: bins with their chunk lists (virtual
+//                        file offsets), the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.
+// The sorted stream is gathered a window of blocks at a time: it never exists in memory as a whole, only the records do.
+#pragma once
+#include <stdint.h>
+#include <stdio.h>
+#include <string.h>
+#include <algorithm>
+#include <atomic>
+#include <map>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+#include "../../include/psvr_engine.h"
+#include "bam_writer.h"
+
+namespace psvr {
+
+struct SortRecords {
+	// every record (block_size + body) in chunks of kChunk bytes that are allocated once and never grow: the records take their own
+	// size in memory, not the up to 3x of one vector that doubles as it fills
+	static const size_t kChunk = (size_t)64 << 20;
+	std::vector<std::vector<uint8_t>> chunk;
+	std::vector<uint64_t> off;              // record i: chunk index << 32 | offset in the chunk
+	std::vector<uint64_t> key;              // (uint64)tid << 32 | (uint32)(pos + 1) << 1 | reverse
+	bool key_exact = true;                  // every pos in [-1, 2^31 - 2]: the key orders exactly as the comparator
+	uint64_t bytes = 0;                     // the records' total size
+	size_t size() const { return off.size(); }
+	const uint8_t *rec(size_t i) const { return chunk[(size_t)(off[i] >> 32)].data() + (off[i] & 0xffffffffu); }
+	static uint32_t u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+	static int64_t ref_span(const uint8_t *r)       // reference bases the CIGAR covers (M, D, N, =, X)
+	{
+		const uint32_t l_qname = r[12], n_cig = r[16] | (uint32_t)r[17] << 8;
+		int64_t rlen = 0;
+		for (uint32_t k = 0; k < n_cig; ++k) { const uint32_t c = u32(r + 36 + l_qname + 4 * k); const int op = (int)(c & 0xf); if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4; }
+		return rlen;
+	}
+	// one record: `fixed` = the 32 bytes after block_size (bam1_core_t as in the file), `data` = qname | cigar | seq | qual | aux.
+	// The bin is recomputed from pos and the CIGAR's span (1 base without one); every other byte is kept.
+	void add(const uint8_t fixed[32], const uint8_t *data, size_t n_data)
+	{
+		const size_t len = 36 + n_data;
+		if (chunk.empty() || chunk.back().capacity() - chunk.back().size() < len) {
+			chunk.emplace_back();
+			chunk.back().reserve(len > kChunk ? len : kChunk);
+		}
+		std::vector<uint8_t> &c = chunk.back();
+		const uint64_t o = c.size();
+		c.resize(o + len);                       // (within the capacity: the records already in the chunk stay where they are)
+		uint8_t *r = c.data() + o;
+		const uint32_t bs = (uint32_t)(32 + n_data);
+		for (int k = 0; k < 4; ++k) r[k] = (uint8_t)(bs >> (8 * k));
+		memcpy(r + 4, fixed, 32);
+		if (n_data) memcpy(r + 36, data, n_data);
+		const int32_t tid = (int32_t)u32(r + 4), pos = (int32_t)u32(r + 8);
+		const int64_t rlen = ref_span(r), beg = pos < 0 ? 0 : pos, end = beg + (rlen > 0 ? rlen : 1), e = end - 1;
+		int bin;
+		if (beg >> 14 == e >> 14) bin = (int)(((1 << 15) - 1) / 7 + (beg >> 14));
+		else if (beg >> 17 == e >> 17) bin = (int)(((1 << 12) - 1) / 7 + (beg >> 17));
+		else if (beg >> 20 == e >> 20) bin = (int)(((1 << 9) - 1) / 7 + (beg >> 20));
+		else if (beg >> 23 == e >> 23) bin = (int)(((1 << 6) - 1) / 7 + (beg >> 23));
+		else if (beg >> 26 == e >> 26) bin = (int)(((1 << 3) - 1) / 7 + (beg >> 26));
+		else bin = 0;
+		r[14] = (uint8_t)bin, r[15] = (uint8_t)(bin >> 8);
+		const uint16_t flag = (uint16_t)(r[18] | r[19] << 8);
+		if (pos < -1 || pos > 0x7ffffffe) key_exact = false;
+		off.push_back((uint64_t)(chunk.size() - 1) << 32 | o);
+		bytes += len;
+		key.push_back((uint64_t)(uint32_t)tid << 32 | (uint64_t)(((uint32_t)pos + 1u) << 1) | ((flag >> 4) & 1));
+	}
+	// records back to back as in a BAM stream (what the formatter produces for the main file); false on a malformed one
+	bool add_stream(const uint8_t *p, size_t n)
+	{
+		size_t i = 0;
+		while (i < n) {
+			if (n - i < 36) return false;
+			const uint32_t bs = u32(p + i);
+			if (bs < 32 || bs > n - i - 4) return false;
+			const uint8_t *f = p + i + 4;
+			if ((size_t)f[8] + 4 * (size_t)(f[12] | f[13] << 8) > bs - 32) return false;   // the CIGAR lies inside the record
+			add(f, f + 32, bs - 32);
+			i += 4 + bs;
+		}
+		return true;
+	}
+};
+
+// the order in which write_sorted_bam takes the records.  Returns false (and the reason) only when the device sort fails.
+inline bool coordinate_order(const SortRecords &R, int device, std::vector<uint32_t> &ord, bool *on_device, std::string *err)
+{
+	const size_t n = R.size();
+	ord.resize(n);
+	*on_device = false;
+	if (n > 0 && R.key_exact && n < ((size_t)1 << 32) && psvr_device_count() > 0) {
+		if (psvr_sort_order_u64(device, (int64_t)n, R.key.data(), ord.data())) { *err = psvr_last_error(); return false; }
+		*on_device = true;
+		return true;
+	}
+	for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
+	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+		const uint8_t *x = R.rec(a), *y = R.rec(b);
+		const uint32_t xt = SortRecords::u32(x + 4), yt = SortRecords::u32(y + 4);
+		if (xt != yt) return xt < yt;
+		const int32_t xp = (int32_t)SortRecords::u32(x + 8), yp = (int32_t)SortRecords::u32(y + 8);
+		if (xp != yp) return xp < yp;
+		return (x[18] & 0x10) < (y[18] & 0x10);
+	});
+	return true;
+}
+
+// name order (`panSVR sort -n`): the names with strcmp, first read before second, ties in input order
+inline void name_order(const SortRecords &R, std::vector<uint32_t> &ord)
+{
+	ord.resize(R.size());
+	for (size_t i = 0; i < ord.size(); ++i) ord[i] = (uint32_t)i;
+	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
+		const uint8_t *x = R.rec(a), *y = R.rec(b);
+		const int c = strcmp((const char *)x + 36, (const char *)y + 36);
+		if (c) return c < 0;
+		return (x[18] & 0xc0) < (y[18] & 0xc0);
+	});
+}
+
+// writes out_fn (and out_fn + ".bai" unless by_name); false with the reason in *err
+inline bool write_sorted_bam(const std::string &out_fn, const std::string &header_text, const std::vector<std::pair<std::string, int32_t>> &refs,
+                             const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err)
+{
+	if (threads < 1) threads = 1;
+	// header with the sort order stated, as samtools rewrites it
+	std::string text = header_text;
+	while (!text.empty() && text.back() == '\0') text.pop_back();
+	{
+		const std::string so = by_name ? "queryname" : "coordinate";
+		if (text.compare(0, 3, "@HD") == 0) {
+			const size_t eol = text.find('\n');
+			std::string hd = text.substr(0, eol);
+			const size_t p = hd.find("\tSO:");
+			if (p != std::string::npos) { size_t e = hd.find('\t', p + 1); hd.erase(p, (e == std::string::npos ? hd.size() : e) - p); }
+			hd += "\tSO:" + so;
+			text = hd + text.substr(eol == std::string::npos ? text.size() : eol);
+		} else text = "@HD\tVN:1.6\tSO:" + so + "\n" + text;
+	}
+	std::vector<uint8_t> win = {'B', 'A', 'M', 1};
+	auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) win.push_back((uint8_t)(v >> (8 * k))); };
+	put32((uint32_t)text.size());
+	win.insert(win.end(), text.begin(), text.end());
+	put32((uint32_t)refs.size());
+	for (auto &rf : refs) { put32((uint32_t)rf.first.size() + 1); win.insert(win.end(), rf.first.begin(), rf.first.end()); win.push_back(0); put32((uint32_t)rf.second); }
+	const uint64_t header_bytes = win.size();
+	FILE *fo = fopen(out_fn.c_str(), "wb");
+	if (!fo) { *err = "fail to open file '" + out_fn + "'"; return false; }
+	// BGZF blocks of 0xff00 uncompressed bytes of the whole stream, the header included; their file offsets give the virtual offsets
+	const size_t kBlock = 0xff00, kWindow = (size_t)(threads < 4 ? 4 : threads) * 16 * kBlock;
+	std::vector<uint64_t> cstart(1, 0);
+	std::vector<std::vector<uint8_t>> comp;
+	bool ok = true;
+	auto flush = [&](size_t nb) {                     // compresses and writes the first nb blocks of win (the last one may be short)
+		comp.resize(nb);
+		std::atomic<size_t> next(0);
+		auto work = [&]() {
+			std::vector<uint8_t> tmp(0x10000 + 64);
+			for (size_t b = next++; b < nb; b = next++) {
+				const size_t o = b * kBlock, m = win.size() - o < kBlock ? win.size() - o : kBlock;
+				const size_t c = BgzfWriter::compress_block_public(win.data() + o, m, tmp.data());
+				comp[b].assign(tmp.begin(), tmp.begin() + (long)c);
+			}
+		};
+		std::vector<std::thread> th;
+		for (int t = 1; t < threads && (size_t)t < nb; ++t) th.emplace_back(work);
+		work();
+		for (auto &t : th) t.join();
+		for (size_t b = 0; b < nb; ++b) {
+			if (comp[b].empty()) { *err = "compression failed"; ok = false; return; }
+			if (fwrite(comp[b].data(), 1, comp[b].size(), fo) != comp[b].size()) { *err = "fail to write file '" + out_fn + "'"; ok = false; return; }
+			cstart.push_back(cstart.back() + comp[b].size());
+		}
+		const size_t used = nb * kBlock < win.size() ? nb * kBlock : win.size();
+		win.erase(win.begin(), win.begin() + (long)used);
+	};
+	for (size_t i = 0; i < ord.size() && ok; ++i) {
+		const uint8_t *r = R.rec(ord[i]);
+		win.insert(win.end(), r, r + 4 + SortRecords::u32(r));
+		if (win.size() >= kWindow) flush(win.size() / kBlock);
+	}
+	if (ok && !win.empty()) flush((win.size() + kBlock - 1) / kBlock);
+	static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	if (ok && fwrite(eof, 1, 28, fo) != 28) *err = "fail to write file '" + out_fn + "'", ok = false;
+	if (fclose(fo) != 0 && ok) *err = "fail to write file '" + out_fn + "'", ok = false;
+	if (!ok || by_name) return ok;
+	// ---- .bai
+	const size_t nb = cstart.size() - 1;
+	auto voff = [&](uint64_t u) { const size_t b = (size_t)(u / kBlock); return b < nb ? (cstart[b] << 16) | (u % kBlock) : (cstart[nb] << 16); };   // (the end of the data = the EOF block)
+	struct RefIdx { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; std::vector<uint64_t> lin; uint64_t beg = ~0ull, end = 0, n_mapped = 0, n_unmapped = 0; };
+	std::vector<RefIdx> ri(refs.size());
+	uint64_t n_no_coor = 0, u = header_bytes;
+	for (size_t i = 0; i < ord.size(); ++i) {
+		const uint8_t *h = R.rec(ord[i]);
+		const uint64_t us = u;
+		u += 4 + SortRecords::u32(h);
+		const uint32_t tid = SortRecords::u32(h + 4);
+		if ((int32_t)tid < 0 || tid >= ri.size()) { ++n_no_coor; continue; }
+		const int32_t pos = (int32_t)SortRecords::u32(h + 8);
+		const uint32_t bin = h[14] | (uint32_t)h[15] << 8;
+		const uint64_t vb = voff(us), ve = voff(u);
+		RefIdx &X = ri[tid];
+		auto &ch = X.bins[bin];
+		if (!ch.empty() && ch.back().second == vb) ch.back().second = ve;       // adjacent records of a bin share a chunk
+		else ch.push_back({vb, ve});
+		// reference span from the CIGAR (1 base without one), for the linear index
+		const int64_t rlen = SortRecords::ref_span(h), beg = pos < 0 ? 0 : pos, end = beg + (rlen > 0 ? rlen : 1);
+		for (int64_t w = beg >> 14; w <= (end - 1) >> 14; ++w) {
+			if ((size_t)w >= X.lin.size()) X.lin.resize((size_t)w + 1, 0);
+			if (X.lin[(size_t)w] == 0) X.lin[(size_t)w] = vb;
+		}
+		if (vb < X.beg) X.beg = vb;
+		if (ve > X.end) X.end = ve;
+		if ((h[18] | h[19] << 8) & 0x4) ++X.n_unmapped; else ++X.n_mapped;
+	}
+	std::vector<uint8_t> bai = {'B', 'A', 'I', 1};
+	auto b32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) bai.push_back((uint8_t)(v >> (8 * k))); };
+	auto b64 = [&](uint64_t v) { for (int k = 0; k < 8; ++k) bai.push_back((uint8_t)(v >> (8 * k))); };
+	b32((uint32_t)ri.size());
+	for (RefIdx &X : ri) {
+		const bool any = !X.bins.empty();
+		b32((uint32_t)X.bins.size() + (any ? 1 : 0));
+		for (auto &kv : X.bins) { b32(kv.first); b32((uint32_t)kv.second.size()); for (auto &c : kv.second) b64(c.first), b64(c.second); }
+		if (any) { b32(37450), b32(2), b64(X.beg), b64(X.end), b64(X.n_mapped), b64(X.n_unmapped); }
+		for (size_t w = 1; w < X.lin.size(); ++w) if (X.lin[w] == 0) X.lin[w] = X.lin[w - 1];          // empty windows point at the previous one, as samtools fills them
+		b32((uint32_t)X.lin.size());
+		for (uint64_t v : X.lin) b64(v);
+	}
+	b64(n_no_coor);
+	FILE *fi = fopen((out_fn + ".bai").c_str(), "wb");
+	if (!fi || fwrite(bai.data(), 1, bai.size(), fi) != bai.size() || fclose(fi) != 0) { *err = "fail to write file '" + out_fn + ".bai'"; return false; }
+	return true;
+}
+
+} // namespace psvr
