@@ -312,6 +312,24 @@ int psvr_engine_stats(const psvr_engine_t *eng, char *buf, size_t buflen);
 int64_t psvr_bgzf_bound(int64_t n_bytes);
 int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, void *out, int64_t out_cap, int64_t *out_bytes);
 
+/* ---- BGZF members inflated on the device (the BAM input's decompression) --------------------------------------------------------------
+ * Replaces, for the commands that read a BAM (`panSVR signal`, `panSVR sort`, `panSVR aln` with a *.bam read file), htslib's
+ * bgzf_read_block -> inflate_block (htslib bgzf.c: zlib inflate of one member at a time on the calling thread).
+ * `in` (host memory) holds BGZF members back to back.  Whole members are consumed: *in_used is the size of the longest prefix of n_bytes
+ * made of whole members (a cut-off member at the end is the caller's to complete), *out_bytes the sum of their ISIZE fields.
+ * out == NULL: only the sizes are computed (no device needed for that).  Otherwise the members are inflated on HIP device `device`, one
+ * wavefront per member, into out[0, *out_bytes), in order (out_cap too small: PSVR_ERR_OVERFLOW, the sizes still returned).
+ * member_off, if not NULL, has room for member_cap + 1 entries: member_off[i] = where member i starts in `out`, member_off[*n_members] =
+ * *out_bytes (more members than member_cap: PSVR_ERR_OVERFLOW); n_members and bad_member may be NULL.
+ * Every member's CRC32 and ISIZE are checked on the device.  A member zlib would refuse (its header is judged by the rules of the
+ * command's serial reader: magic, CM, FEXTRA, a BC subfield of length 2 anywhere in the extra field, BSIZE large enough for header and
+ * trailer) -> PSVR_ERR_IO; *bad_member is its index and psvr_last_error() names index and byte offset; the bytes of the members in front
+ * of it are valid, nothing is promised from its start on.  A member with a bad header ends the chain: *in_used and *out_bytes cover the
+ * members in front of it.  Device buffers and the call's stream are kept across calls; calls are serialised. */
+int psvr_bgzf_decompress(int device, const void *in, int64_t n_bytes, int64_t *in_used,
+                         void *out, int64_t out_cap, int64_t *out_bytes,
+                         int64_t *member_off, int64_t member_cap, int64_t *n_members, int64_t *bad_member);
+
 /* ---- Stable order of 64-bit keys on the device (the coordinate sort of the BAM output) -------------------------------------------------
  * Replaces, for `panSVR aln --sort` and `panSVR sort`, the ordering step of `samtools sort` that panSVR_run.sh:53 runs between `aln` and
  * `fc_sv` (samtools bam_sort.c: the key (uint64)tid << 32 | (uint32)(pos + 1) << 1 | reverse, ties in input order).

@@ -1,0 +1,47 @@
+"""BGZF members inflated on the device through the C ABI (psvr_bgzf_decompress)."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import EngineError, check, lib
+
+
+class BgzfError(EngineError):
+    """A member zlib would refuse; bad_member is its index, valid_bytes what the members in front of it inflate to."""
+
+    def __init__(self, msg, bad_member, valid_bytes):
+        EngineError.__init__(self, msg)
+        self.bad_member, self.valid_bytes = bad_member, valid_bytes
+
+
+def _call(device, buf, out, out_cap, offs, off_cap):
+    used, total, nm, bad = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(-1)
+    rc = lib().psvr_bgzf_decompress(C.c_int(device), buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.byref(used), out, C.c_int64(out_cap), C.byref(total),
+                                    offs, C.c_int64(off_cap), C.byref(nm), C.byref(bad))
+    return rc, used.value, total.value, nm.value, bad.value
+
+
+def bgzf_sizes(data):
+    """(bytes of the longest prefix of whole members, bytes they inflate to, their number); needs no device."""
+    buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+    rc, used, total, nm, bad = _call(0, buf, None, 0, None, 0)
+    if rc == 5:
+        raise BgzfError(lib().psvr_last_error().decode(), bad, total)
+    check(rc)
+    return used, total, nm
+
+
+def bgzf_decompress(data, device=0):
+    """The whole members at the start of `data` inflated on HIP device `device`: (uint8 array, member offsets [n + 1], bytes of data used)."""
+    buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+    rc, used, total, nm, bad = _call(device, buf, None, 0, None, 0)
+    header_bad = rc == 5
+    if not header_bad:
+        check(rc)
+    out = np.empty(max(total, 1), dtype=np.uint8)
+    offs = np.zeros(nm + 1, dtype=np.int64)
+    rc, used, total, nm, bad = _call(device, buf, out.ctypes.data_as(C.c_void_p), total, offs.ctypes.data_as(C.c_void_p), nm)
+    if rc == 5:
+        raise BgzfError(lib().psvr_last_error().decode(), bad, bytes(out[:offs[bad] if bad < nm else total]))
+    check(rc)
+    return out[:total], offs, used

@@ -1,6 +1,6 @@
 // bam_sort.h -- `panSVR sort`: what panSVR_run.sh does after the `aln` step with `samtools sort` + `samtools index`
 // (panSVR_run.sh:53-54), so the drop-in does not depend on an external binary.  Host C++ only.
-//   panSVR sort [-n] [-t threads] [-o out.bam] in.bam      coordinate order (default) + out.bam.bai, or name order (-n)
+//   panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] in.bam      coordinate order (default) + out.bam.bai, or name order (-n)
 // Coordinate order is samtools' (bam_sort.c bam1_lt): reference id as unsigned (unplaced records last), position, forward strand
 // before reverse, ties in input order; name order compares the names with strcmp, first read before second.  The whole file is held
 // in memory (the aln step's output is the signal subset of a run, not the full BAM).  The order and the writing are sorted_bam.h's, which
@@ -19,18 +19,29 @@ namespace psvr {
 inline int bam_sort_main(int argc, char **argv)
 {
 	bool by_name = false;
-	int threads = 4;
+	int threads = 4, inflate_device = -1, inflate_threads = 0;
+	bool bad_arg = false;
 	std::string out_fn, in_fn;
 	for (int i = 2; i < argc; ++i) {
 		if (!strcmp(argv[i], "-n")) by_name = true;
 		else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "-@")) && i + 1 < argc) threads = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "-o") && i + 1 < argc) out_fn = argv[++i];
+		else if (!strcmp(argv[i], "--inflate-device")) inflate_device = 0;
+		else if (!strcmp(argv[i], "--inflate-threads") && i + 1 < argc) { inflate_threads = atoi(argv[++i]); bad_arg |= inflate_threads < 1; }
 		else in_fn = argv[i];
 	}
-	if (in_fn.empty()) { fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] in.bam\n"); return 1; }
+	if (bad_arg) fprintf(stderr, "--inflate-threads wants a positive number\n");
+	if (in_fn.empty() || bad_arg) {
+		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] in.bam\n"
+		                "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
+		                "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
+		                "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n");
+		return 1;
+	}
 	if (out_fn.empty()) out_fn = in_fn + (by_name ? ".nsorted.bam" : ".sorted.bam");
 	if (threads < 1) threads = 1;
 	BamReader rd;
+	if (inflate_device >= 0 || inflate_threads > 0) rd.set_batched(inflate_device, inflate_threads);
 	if (!rd.open(in_fn.c_str())) { fprintf(stderr, "[panSVR-amd] sort: %s\n", rd.error().c_str()); return 2; }
 	// every record as it stands in the file (block_size + body, the fixed part re-encoded), one buffer
 	SortRecords R;

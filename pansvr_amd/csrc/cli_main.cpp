@@ -55,6 +55,8 @@ struct Opt {
 	bool sig_all = false, sig_discard = false;   // BAM input: fc_signal's -D / -U
 	int bam_level = -1;                          // zlib level of the BGZF blocks (-1 = zlib's default, what htslib's "wb" uses)
 	bool bgzf_device = false;                    // the main file's BGZF blocks compressed on the first device (psvr_bgzf_compress)
+	bool inflate_device = false;                 // BAM input: its BGZF members inflated on the first device (psvr_bgzf_decompress) ...
+	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 };
 
@@ -96,6 +98,11 @@ static int usage()
 	        "        --sort                   write the main output (-o) coordinate-sorted with its index <out>.bai, as `panSVR sort`\n"
 	        "                                 would from the unsorted file (ordered on the first device of --devices; not with -S,\n"
 	        "                                 --compress-level, --bgzf-fast or --bgzf-device)\n"
+	        "        --inflate-device         a *.bam read file: inflate its BGZF members on the GPU (the first device; a wavefront per member,\n"
+	        "                                 a chunk of the file at a time, on a stream of its own; faster than the default reader, but it\n"
+	        "                                 does not win against --inflate-threads 16.  Whether the engine's launches queue behind the inflate\n"
+	        "                                 calls on the shared GPU has not been measured)\n"
+	        "        --inflate-threads   INT  ... or with zlib on INT host threads (also what takes over when the device route fails)\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -183,7 +190,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
 	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv);
 	if (argc < 2 || (strcmp(argv[1], "aln") && strcmp(argv[1], "fc_aln"))) {
-		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n"
+		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n"
 		                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 		return 1;
 	}
@@ -191,7 +198,7 @@ int main(int argc, char **argv)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	bool sig_by_name = false;
@@ -224,6 +231,8 @@ int main(int argc, char **argv)
 		case 1009: o.bam_level = psvr::BgzfWriter::kLevelFast; if (!sort_conflict) sort_conflict = "--bgzf-fast"; break;
 		case 1006: o.bam_level = atoi(optarg); if (o.bam_level < -1 || o.bam_level > 9) { fprintf(stderr, "--compress-level wants -1 .. 9\n"); return 1; } if (!sort_conflict) sort_conflict = "--compress-level"; break;
 		case 1010: o.sort = true; break;
+		case 1011: o.inflate_device = true; break;
+		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
 		case 'N': sig_by_name = true; break;
@@ -242,6 +251,7 @@ int main(int argc, char **argv)
 	// <reads> may be a BAM (*.bam): the signal step then runs in this process (options of fc_signal: -N for name-sorted input,
 	// position-sorted otherwise) and hands its FASTQ text through a pipe to the reader below; <header.sam> is WRITTEN from the BAM's header
 	const bool from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
+	if (!from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
 	if (from_bam) {
 		psvr::BamReader rd;
 		if (!rd.open(o.reads.c_str())) { fprintf(stderr, "[panSVR-amd] %s\n", rd.error().c_str()); abort(); }
@@ -289,6 +299,7 @@ int main(int argc, char **argv)
 		// f2 fused: the signal step's thread hands its pairs straight to the batch being built (PairFeed, fastq_batch.h) -- no FASTQ text, no pipe
 		sig.o.sort_by_name = sig_by_name, sig.o.input = o.reads, sig.o.header_fn = o.header, sig.o.status_fn = o.header + ".status";
 		sig.o.not_use_filter = o.sig_all, sig.o.discard_full_match = o.sig_discard;
+		sig.o.inflate_device = o.inflate_device ? o.devices[0] : -1, sig.o.inflate_threads = o.inflate_threads;
 		sig.o.match = o.match, sig.o.mismatch = o.mismatch, sig.o.gap_open = o.gap_open, sig.o.gap_ex = o.gap_ex, sig.o.gap_open2 = o.gap_open2, sig.o.gap_ex2 = o.gap_ex2;
 		sig.feed = &feed;
 		sig_thread = std::thread([&sig, &sig_rc, &feed]() { sig_rc = sig.run(); feed.close(); });

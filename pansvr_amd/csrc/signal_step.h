@@ -35,6 +35,7 @@ struct SignalOpt {
 	double sample_rate = 1;
 	std::string header_fn = "./header.sam", status_fn = "./status.sam", input;
 	int isize_override[3] = {-1, -1, -1};                                                   // --isize MIN,MID,MAX
+	int inflate_device = -1, inflate_threads = 0;                                           // --inflate-device / --inflate-threads N: the batched BGZF reader (bam_reader.h)
 };
 
 struct BamStat {                                            // BAM_STAT, getSignalRead.hpp:33-190
@@ -408,6 +409,7 @@ struct SignalStep {
 			fprintf(stderr, "Sample_rate: [%f] sample_max_number_int: [%d]\n", o.sample_rate, sample_max);
 		}
 		BamReader rd;
+		if (o.inflate_device >= 0 || o.inflate_threads > 0) rd.set_batched(o.inflate_device, o.inflate_threads);   // (sample_stats reads 100 000 records: serial)
 		if (!rd.open(o.input.c_str())) { fprintf(stderr, "[panSVR-amd] signal: %s\n", rd.error().c_str()); return 1; }
 		if (!o.header_fn.empty()) {                         // sam_hdr_write in SAM text mode: the header text as stored
 			FILE *h = fopen(o.header_fn.c_str(), "w");
@@ -452,7 +454,11 @@ inline int signal_main(int argc, char **argv)
 	static struct option lo[] = {{"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'}, {"match-score", 1, 0, 'M'},
 	                             {"mis-score", 1, 0, 'm'}, {"max-tid-filter", 1, 0, 'I'}, {"sort-by-name", 0, 0, 'N'}, {"not-ignore-low-q", 0, 0, 'L'}, {"reference", 1, 0, 'r'},
 	                             {"header-file", 1, 0, 'H'}, {"status-file", 1, 0, 'S'}, {"tmp_file_pairing", 1, 0, 't'}, {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'},
-	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {0, 0, 0, 0}};
+	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {"inflate-device", 0, 0, 1001}, {"inflate-threads", 1, 0, 1002}, {0, 0, 0, 0}};
+	static const char *usage = "usage: panSVR signal|fc_signal [-N] [options] <in.bam>  > reads.fq\n"
+	                           "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
+	                           "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
+	                           "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n";
 	int c;
 	optind = 2;
 	while ((c = getopt_long(argc, argv, "O:P:E:F:M:m:I:NLr:H:S:t:DUR:", lo, NULL)) >= 0) {
@@ -472,10 +478,12 @@ inline int signal_main(int argc, char **argv)
 		case 'U': S.o.discard_full_match = true; break;
 		case 'R': S.o.sample_rate = atof(optarg); break;
 		case 1000: if (sscanf(optarg, "%d,%d,%d", &S.o.isize_override[0], &S.o.isize_override[1], &S.o.isize_override[2]) != 3) { fprintf(stderr, "--isize wants MIN,MID,MAX\n"); return 1; } break;
-		default: fprintf(stderr, "usage: panSVR signal|fc_signal [-N] [options] <in.bam>  > reads.fq\n"); return 1;
+		case 1001: S.o.inflate_device = 0; break;
+		case 1002: S.o.inflate_threads = atoi(optarg); if (S.o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
+		default: fputs(usage, stderr); return 1;
 		}
 	}
-	if (argc - optind < 1) { fprintf(stderr, "usage: panSVR signal|fc_signal [-N] [options] <in.bam>  > reads.fq\n"); return 1; }
+	if (argc - optind < 1) { fputs(usage, stderr); return 1; }
 	S.o.input = argv[optind];
 	return S.run();
 }
