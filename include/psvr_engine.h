@@ -312,6 +312,24 @@ int psvr_engine_stats(const psvr_engine_t *eng, char *buf, size_t buflen);
 int64_t psvr_bgzf_bound(int64_t n_bytes);
 int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, void *out, int64_t out_cap, int64_t *out_bytes);
 
+/* ---- BGZF members on the device, a wavefront per member (the BAM output's compression, sorted or not) ---------------------------------
+ * The same service as psvr_bgzf_compress with the member's bytes shared by the 64 lanes of a wavefront instead of given to one lane, and
+ * with the member offsets returned (a sorted BAM's index needs them for its virtual offsets).  `in` (host memory, n_bytes) is cut into
+ * members of member_bytes input bytes (256..0xff00; 0 = 0xff00, htslib's size); member i becomes one BGZF member (gzip header with the BC
+ * field, one DEFLATE block -- dynamic Huffman, fixed Huffman or stored, whichever is smallest --, CRC32, ISIZE).  The members are written
+ * next to each other into out[0, *out_bytes) (host memory; psvr_bgzf_members_bound(n_bytes, member_bytes) always suffices, and every
+ * member is at most 31 bytes larger than its input, so it fits BGZF's 64 KB).  member_off, if not NULL, has room for member_cap + 1
+ * entries: member_off[i] = where member i starts in `out`, member_off[*n_members] = *out_bytes.  The EOF marker block is the caller's.
+ * A member's bytes depend on its input bytes alone: the same input gives the same member in every call, at every offset, on the device
+ * and in the encoder's host build (tests/tools/deflate_wave_check.cpp).  Any BGZF / gzip reader decodes them; they differ from zlib's.
+ * n_bytes == 0: no members, PSVR_OK.  out_cap or member_cap too small: PSVR_ERR_OVERFLOW (*out_bytes and *n_members are still set when the
+ * device ran).  Bytes of `out` behind *out_bytes are unspecified.  Device buffers and the call's stream (of the lowest priority) are kept
+ * across calls; calls are serialised. */
+int64_t psvr_bgzf_members_bound(int64_t n_bytes, int32_t member_bytes);
+int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int32_t member_bytes,
+                               void *out, int64_t out_cap, int64_t *out_bytes,
+                               int64_t *member_off, int64_t member_cap, int64_t *n_members);
+
 /* ---- BGZF members inflated on the device (the BAM input's decompression) --------------------------------------------------------------
  * Replaces, for the commands that read a BAM (`panSVR signal`, `panSVR sort`, `panSVR aln` with a *.bam read file), htslib's
  * bgzf_read_block -> inflate_block (htslib bgzf.c: zlib inflate of one member at a time on the calling thread).

@@ -1,4 +1,4 @@
-"""BGZF members inflated on the device through the C ABI (psvr_bgzf_decompress)."""
+"""BGZF members inflated and compressed on the device through the C ABI (psvr_bgzf_decompress, psvr_bgzf_compress_members)."""
 import ctypes as C
 
 import numpy as np
@@ -45,3 +45,20 @@ def bgzf_decompress(data, device=0):
         raise BgzfError(lib().psvr_last_error().decode(), bad, bytes(out[:offs[bad] if bad < nm else total]))
     check(rc)
     return out[:total], offs, used
+
+
+def bgzf_compress(data, member_bytes=0xff00, device=0):
+    """`data` cut into members of member_bytes input bytes, each compressed by a wavefront of HIP device `device`:
+    (uint8 array of the members side by side, member offsets [n + 1])."""
+    buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+    L = lib()
+    L.psvr_bgzf_members_bound.restype = C.c_int64
+    cap = L.psvr_bgzf_members_bound(C.c_int64(len(buf)), C.c_int32(member_bytes))
+    mb = member_bytes or 0xff00
+    nm_cap = (len(buf) + mb - 1) // mb if mb > 0 else 0
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    offs = np.zeros(nm_cap + 1, dtype=np.int64)
+    total, nm = C.c_int64(0), C.c_int64(0)
+    check(L.psvr_bgzf_compress_members(C.c_int(device), buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.c_int32(member_bytes), out.ctypes.data_as(C.c_void_p),
+                                       C.c_int64(cap), C.byref(total), offs.ctypes.data_as(C.c_void_p), C.c_int64(nm_cap), C.byref(nm)))
+    return out[:total.value], offs[:nm.value + 1]

@@ -32,6 +32,12 @@ namespace psvr {
 
 // A byte buffer whose resize() does not zero what it adds: the record formatters reserve a bound, write through a raw pointer and
 // shrink to what they wrote (value-initialising the slack was a second pass over every output byte).
+// The shape of psvr_bgzf_compress_members (include/psvr_engine.h): `in` cut into members of member_bytes, written side by side into `out`,
+// their offsets into member_off[0..n] when that is not NULL.  The writers take the compressor as a pointer of this type and do not name
+// the engine's symbol themselves (cli_main.cpp hands &psvr_bgzf_compress_members in; the tests hand in stand-ins).
+typedef int (*BgzfMembersFn)(int device, const void *in, int64_t n_bytes, int32_t member_bytes, void *out, int64_t out_cap, int64_t *out_bytes,
+                             int64_t *member_off, int64_t member_cap, int64_t *n_members);
+
 template <class T> struct NoInitAlloc : std::allocator<T> {
 	template <class U> struct rebind { typedef NoInitAlloc<U> other; };
 	NoInitAlloc() = default;
@@ -50,7 +56,8 @@ class BgzfWriter {
 	bool ok_ = true;
 	int threads_ = 1;
 	int level_ = Z_DEFAULT_COMPRESSION;           // htslib's "wb" is zlib's default level too
-	int device_ = -1;                             // >= 0: BGZF members come from psvr_bgzf_compress on that device
+	int device_ = -1;                             // >= 0: BGZF members come from psvr_bgzf_compress on that device ...
+	BgzfMembersFn members_ = nullptr;             // ... or, when set, from this compressor: a wavefront per member of kBlock bytes
 	uint8_t *pin_in_ = nullptr, *pin_out_ = nullptr;   // page-locked: the records of a batch, its members
 	size_t pin_n_ = 0, pin_out_cap_ = 0;
 	size_t gather_blocks_;                        // blocks of records gathered in page-locked memory per device call
@@ -106,10 +113,11 @@ private:
 #ifdef PSVR_BGZF_ON_DEVICE
 		static const size_t dev_min = getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS") ? (size_t)atoll(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS")) : 64;   // (tests: small files through the device too)
 		if (device_ >= 0 && nb >= dev_min) {
-			const size_t need = (size_t)psvr_bgzf_bound((int64_t)n);
+			const size_t need = members_ ? n + nb * 32 : (size_t)psvr_bgzf_bound((int64_t)n);   // (a member of the wavefront encoder: its input + 31 bytes at most)
 			if (need > pin_out_cap_) { if (pin_out_) psvr_host_free(pin_out_); pin_out_ = (uint8_t *)psvr_host_alloc(need), pin_out_cap_ = pin_out_ ? need : 0; }
 			int64_t got = 0;
-			if (pin_out_ && psvr_bgzf_compress(device_, p, (int64_t)n, pin_out_, (int64_t)pin_out_cap_, &got) == 0) {
+			if (pin_out_ && (members_ ? members_(device_, p, (int64_t)n, (int32_t)kBlock, pin_out_, (int64_t)pin_out_cap_, &got, nullptr, 0, nullptr)
+			                          : psvr_bgzf_compress(device_, p, (int64_t)n, pin_out_, (int64_t)pin_out_cap_, &got)) == 0) {
 				if (fwrite(pin_out_, 1, (size_t)got, f_) != (size_t)got) ok_ = false;
 				return;
 			}
@@ -138,6 +146,9 @@ public:
 	bool open(const char *fn, int threads = 1, int level = Z_DEFAULT_COMPRESSION) { f_ = fopen(fn, "wb"); threads_ = threads; level_ = level; return f_ != nullptr; }
 	// compress on HIP device `d` (psvr_bgzf_compress: a lane per block; the members decode like any other, their bytes are not zlib's)
 	void set_device(int d) { device_ = d; }
+	// compress on HIP device `d` through `fn` (psvr_bgzf_compress_members: a wavefront per member of 0xff00 bytes), gather_blocks members per
+	// call (0: as constructed); before the first write() after open()'s header.  A failed call is handled as on the other device route.
+	void set_device_members(int d, BgzfMembersFn fn, size_t gather_blocks = 0) { device_ = d, members_ = fn; if (gather_blocks && !pin_in_) gather_blocks_ = gather_blocks; }
 	void write(const void *p, size_t n)
 	{
 		const uint8_t *b = (const uint8_t *)p;
@@ -364,6 +375,7 @@ public:
 	}
 	void write_raw(const void *p, size_t n) { z_.write(p, n); }
 	void set_device(int d) { z_.set_device(d); }
+	void set_device_members(int d, BgzfMembersFn fn, size_t gather_blocks = 0) { z_.set_device_members(d, fn, gather_blocks); }
 	bool close() { return z_.close(); }
 };
 

@@ -91,23 +91,11 @@ PSVR_DF void df_dist_code(uint32_t dist, uint32_t &sym, uint32_t &ebits, uint32_
 	ebits = e, eval = d & ((1u << e) - 1u);
 }
 
-// code lengths (at most `maxbits`) for the n symbols with the frequencies f[0..n); len[] gets 0 for unused symbols.  At least two
-// symbols get a code (zlib does the same: a lone code confuses some decoders).
-PSVR_DF void df_code_lengths(const uint16_t *f, int n, int maxbits, uint8_t *len, uint16_t *A, uint16_t *S)
+// code lengths (at most `maxbits`) for the m >= 2 symbols S[0..m) whose frequencies A[0..m) are in ascending order; len[S[i]] is set (the
+// other entries of len[] are the caller's).  Shared with deflate_wave_device.h, which ranks the symbols with the lanes of a wavefront.
+// cnt: 33 words of the caller's (registers or scratch for a lane that has a block of its own, LDS for a wavefront's).
+PSVR_DF void df_lengths_sorted(int m, int maxbits, uint8_t *len, uint16_t *A, const uint16_t *S, int *cnt)
 {
-	int m = 0;
-	for (int i = 0; i < n; ++i) { len[i] = 0; if (f[i]) S[m++] = (uint16_t)i; }
-	// force two symbols
-	for (int i = 0; m < 2 && i < n; ++i) { bool have = false; for (int k = 0; k < m; ++k) have |= S[k] == i; if (!have) S[m++] = (uint16_t)i; }
-	// sort by (frequency, symbol): insertion sort, n <= 286
-	for (int i = 1; i < m; ++i) {
-		const uint16_t s = S[i];
-		const uint32_t fs = f[s] ? f[s] : 1u;
-		int j = i;
-		while (j > 0) { const uint32_t fp = f[S[j - 1]] ? f[S[j - 1]] : 1u; if (fp < fs || (fp == fs && S[j - 1] < s)) break; S[j] = S[j - 1]; --j; }
-		S[j] = s;
-	}
-	for (int i = 0; i < m; ++i) A[i] = f[S[i]] ? f[S[i]] : (uint16_t)1;      // (a block's symbols number at most 65281: the sums fit)
 	if (m == 2) { len[S[0]] = len[S[1]] = 1; return; }
 	// Moffat & Katajainen, in-place calculation of minimum-redundancy codes: A[i] becomes the code length of the i-th smallest frequency
 	{
@@ -128,7 +116,6 @@ PSVR_DF void df_code_lengths(const uint16_t *f, int n, int maxbits, uint8_t *len
 	}
 	// limit to maxbits (miniz: tdefl_huffman_enforce_max_code_size): count per length, fold the long ones, repair the Kraft sum
 	{
-		int cnt[33];
 		for (int i = 0; i <= 32; ++i) cnt[i] = 0;
 		for (int i = 0; i < m; ++i) cnt[A[i] > 32 ? 32 : A[i]]++;
 		for (int i = maxbits + 1; i <= 32; ++i) cnt[maxbits] += cnt[i];
@@ -144,10 +131,30 @@ PSVR_DF void df_code_lengths(const uint16_t *f, int n, int maxbits, uint8_t *len
 		for (int l = maxbits; l > 0; --l) for (int c = 0; c < cnt[l]; ++c) len[S[k++]] = (uint8_t)l;
 	}
 }
-// canonical codes, bit-reversed for the LSB-first stream, as code | length << 16
-PSVR_DF void df_codes(const uint8_t *len, int n, uint32_t *code)
+// code lengths (at most `maxbits`) for the n symbols with the frequencies f[0..n); len[] gets 0 for unused symbols.  At least two
+// symbols get a code (zlib does the same: a lone code confuses some decoders).
+PSVR_DF void df_code_lengths(const uint16_t *f, int n, int maxbits, uint8_t *len, uint16_t *A, uint16_t *S)
 {
-	uint32_t cnt[16], next[16];
+	int m = 0;
+	for (int i = 0; i < n; ++i) { len[i] = 0; if (f[i]) S[m++] = (uint16_t)i; }
+	// force two symbols
+	for (int i = 0; m < 2 && i < n; ++i) { bool have = false; for (int k = 0; k < m; ++k) have |= S[k] == i; if (!have) S[m++] = (uint16_t)i; }
+	// sort by (frequency, symbol): insertion sort, n <= 286
+	for (int i = 1; i < m; ++i) {
+		const uint16_t s = S[i];
+		const uint32_t fs = f[s] ? f[s] : 1u;
+		int j = i;
+		while (j > 0) { const uint32_t fp = f[S[j - 1]] ? f[S[j - 1]] : 1u; if (fp < fs || (fp == fs && S[j - 1] < s)) break; S[j] = S[j - 1]; --j; }
+		S[j] = s;
+	}
+	for (int i = 0; i < m; ++i) A[i] = f[S[i]] ? f[S[i]] : (uint16_t)1;      // (a block's symbols number at most 65281: the sums fit)
+	int cnt[33];
+	df_lengths_sorted(m, maxbits, len, A, S, cnt);
+}
+// canonical codes, bit-reversed for the LSB-first stream, as code | length << 16
+// (cnt, next: 16 words each of the caller's, as for df_lengths_sorted)
+PSVR_DF void df_codes(const uint8_t *len, int n, uint32_t *code, uint32_t *cnt, uint32_t *next)
+{
 	for (int i = 0; i < 16; ++i) cnt[i] = 0;
 	for (int i = 0; i < n; ++i) cnt[len[i]]++;
 	cnt[0] = 0;
@@ -161,6 +168,12 @@ PSVR_DF void df_codes(const uint8_t *len, int n, uint32_t *code)
 		for (uint32_t b = 0; b < l; ++b) r = (r << 1) | ((v >> b) & 1u);
 		code[i] = r | (l << 16);
 	}
+}
+
+PSVR_DF void df_codes(const uint8_t *len, int n, uint32_t *code)
+{
+	uint32_t cnt[16], next[16];
+	df_codes(len, n, code, cnt, next);
 }
 
 // The raw DEFLATE stream of in[0..n) (n <= kDfMaxIn) into out[0..cap); returns its size, 0 if even a stored block does not fit.

@@ -1,0 +1,130 @@
+// deflate_wave.hip -- BGZF members compressed on the device, ONE WAVEFRONT PER MEMBER: psvr_bgzf_compress_members (include/psvr_engine.h).
+// The reference writes its BAM through htslib, whose bgzf_compress deflates 0xff00-byte blocks with zlib on a host thread (htslib bgzf.c:
+// bgzf_write -> bgzf_flush -> bgzf_compress).  bgzf.hip's k_bgzf_deflate gives a block to one lane, and a call lasts as long as one lane
+// needs; here a member's 64 KB are shared by the 64 lanes (deflate_wave_device.h), the member sizes become offsets on the device (scan.h)
+// and a pack launch lays the members side by side, so that nothing returns to the host between compressing and packing.
+#include <hip/hip_runtime.h>
+#include <mutex>
+#include <vector>
+#include "../../include/psvr_engine.h"
+#include "common.h"
+#include "deflate_wave_device.h"
+#include "scan.h"
+
+namespace psvr {
+
+__global__ __launch_bounds__(64) void k_bgzf_deflate_wave(const uint8_t *__restrict__ in, long long n_bytes, uint32_t mb, uint8_t *slots, uint32_t slot, uint32_t *tok,
+                                                          uint32_t tok_stride, int32_t *len)
+{
+	__shared__ DfwLds lds;
+	const long long b = blockIdx.x, at = b * (long long)mb;
+	const uint32_t n = (uint32_t)(n_bytes - at < (long long)mb ? n_bytes - at : (long long)mb);
+	const uint32_t size = dfw_member<64>(in + at, n, slots + b * (long long)slot, tok + b * (long long)tok_stride, &lds, (int)threadIdx.x);
+	if (threadIdx.x == 0) len[b] = (int32_t)size;
+}
+// the members side by side: a workgroup per member, whole dwords once the destination is aligned
+__global__ __launch_bounds__(256) void k_bgzf_pack_members(const uint8_t *__restrict__ slots, uint32_t slot, const int32_t *__restrict__ len, const long long *__restrict__ off,
+                                                           uint8_t *__restrict__ packed)
+{
+	const long long b = blockIdx.x;
+	const uint8_t *s = slots + b * (long long)slot;
+	uint8_t *d = packed + off[b];
+	const uint32_t n = (uint32_t)len[b];
+	uint32_t lead = (uint32_t)(-(intptr_t)d) & 3u;
+	if (lead > n) lead = n;
+	const uint32_t nw = (n - lead) / 4u, done = lead + 4u * nw;
+	if (threadIdx.x < lead) d[threadIdx.x] = s[threadIdx.x];
+	for (uint32_t w = threadIdx.x; w < nw; w += 256) {
+		uint32_t v;
+		__builtin_memcpy(&v, s + lead + 4u * w, 4);
+		*(uint32_t *)(d + lead + 4u * w) = v;
+	}
+	if (threadIdx.x < n - done) d[done + threadIdx.x] = s[done + threadIdx.x];
+}
+
+struct DfwCtx {
+	std::mutex mu;
+	int device = -1;
+	DevBuf in, slots, tok, len, off, tmp, packed;
+	std::vector<long long> h_off;            // what an asynchronous copy writes on the host lives as long as the stream
+	hipStream_t stream = nullptr;
+};
+static DfwCtx &dfw_ctx() { static DfwCtx c; return c; }
+
+static inline bool member_bytes_ok(int32_t mb) { return mb == 0 || (mb >= 256 && mb <= (int32_t)kDfMaxIn); }
+
+} // namespace psvr
+
+using namespace psvr;
+
+extern "C" int64_t psvr_bgzf_members_bound(int64_t n_bytes, int32_t member_bytes)
+{
+	if (n_bytes <= 0 || !member_bytes_ok(member_bytes)) return 0;
+	const int64_t mb = member_bytes ? member_bytes : (int64_t)kDfMaxIn, nm = (n_bytes + mb - 1) / mb;
+	return n_bytes + nm * 31;                                                                  // (a member is at most its input in a stored block: 18 + 5 + 8 bytes around it)
+}
+
+extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int32_t member_bytes, void *out, int64_t out_cap, int64_t *out_bytes,
+                                          int64_t *member_off, int64_t member_cap, int64_t *n_members)
+{
+	if (n_bytes < 0 || (n_bytes > 0 && (!in || !out)) || !out_bytes || out_cap < 0 || !member_bytes_ok(member_bytes) || (member_off && member_cap < 0))
+		return set_error(PSVR_ERR_ARG, "psvr_bgzf_compress_members: bad argument");
+	*out_bytes = 0;
+	if (n_members) *n_members = 0;
+	if (member_off) member_off[0] = 0;
+	if (n_bytes == 0) return PSVR_OK;
+	const uint32_t mb = member_bytes ? (uint32_t)member_bytes : kDfMaxIn;
+	const long long nm = (n_bytes + mb - 1) / mb;
+	if (member_off && nm > member_cap) return set_error(PSVR_ERR_OVERFLOW, "psvr_bgzf_compress_members: %lld members, room for %lld offsets", nm, (long long)member_cap);
+	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	PSVR_HIP(hipSetDevice(device));
+	if (c.device != device) {                                                              // (recorded once everything of the device is set up)
+		c.device = -1;
+		c.in.release(), c.slots.release(), c.tok.release(), c.len.release(), c.off.release(), c.tmp.release(), c.packed.release();
+		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
+		// the lowest priority there is: an engine launch that becomes ready while a call runs is not kept waiting behind it
+		int least = 0, greatest = 0;
+		PSVR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+		PSVR_HIP(hipStreamCreateWithPriority(&c.stream, hipStreamNonBlocking, least));
+		c.device = device;
+	}
+	const uint32_t slot = dfw_slot_bytes(mb), tok_stride = (mb + 1u + 63u) & ~63u;         // (words: a token per input byte at most, and the end of block)
+	const long long bound = psvr_bgzf_members_bound(n_bytes, (int32_t)mb);
+	PSVR_HIP(c.in.ensure((size_t)n_bytes));
+	PSVR_HIP(c.slots.ensure((size_t)nm * slot));
+	PSVR_HIP(c.tok.ensure((size_t)nm * tok_stride * 4));
+	PSVR_HIP(c.len.ensure((size_t)(nm + 1) * 4));
+	PSVR_HIP(c.off.ensure((size_t)(nm + 1) * 8));
+	PSVR_HIP(c.tmp.ensure(scan_tmp_bytes(1, nm + 1)));
+	PSVR_HIP(c.packed.ensure((size_t)bound));
+	c.h_off.assign((size_t)nm + 1, 0);
+	// (an error return in between leaves nothing in flight that reads the caller's `in` or writes its `out`)
+	struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{c.stream};
+	PSVR_HIP(hipMemcpyAsync(c.in.p, in, (size_t)n_bytes, hipMemcpyHostToDevice, c.stream));
+	PSVR_HIP(hipMemsetAsync(c.len.as<int32_t>() + nm, 0, 4, c.stream));                     // (the scan runs over nm + 1 sizes: its last offset is the total)
+	hipLaunchKernelGGL(k_bgzf_deflate_wave, dim3((unsigned)nm), dim3(64), 0, c.stream, c.in.as<uint8_t>(), (long long)n_bytes, mb, c.slots.as<uint8_t>(), slot, c.tok.as<uint32_t>(),
+	                   tok_stride, c.len.as<int32_t>());
+	PSVR_HIP(hipGetLastError());
+	ScanSet S = {};
+	S.cnt[0] = c.len.as<int32_t>(), S.out[0] = c.off.as<long long>(), S.stride[0] = 1, S.off[0] = 0, S.base[0] = 0;
+	scan_launch(S, 1, nm + 1, c.tmp.as<long long>(), c.stream);
+	PSVR_HIP(hipGetLastError());
+	hipLaunchKernelGGL(k_bgzf_pack_members, dim3((unsigned)nm), dim3(256), 0, c.stream, c.slots.as<uint8_t>(), slot, c.len.as<int32_t>(), c.off.as<long long>(), c.packed.as<uint8_t>());
+	PSVR_HIP(hipGetLastError());
+	// One download, one wait: the total is known only on the device, so whatever of the bound fits `out` comes back with the offsets, and what
+	// lies behind the total is not part of the result.  (The alternative, a wait for the offsets and a second one for exactly the bytes,
+	// moves fewer bytes and costs a second wake-up; tools/deflate_bench.py measures the call as it is.)
+	const long long take = bound < (long long)out_cap ? bound : (long long)out_cap;
+	PSVR_HIP(hipMemcpyAsync(c.h_off.data(), c.off.p, (size_t)(nm + 1) * 8, hipMemcpyDeviceToHost, c.stream));
+	if (take) PSVR_HIP(hipMemcpyAsync(out, c.packed.p, (size_t)take, hipMemcpyDeviceToHost, c.stream));
+	drain.armed = false;
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	const long long total = c.h_off[(size_t)nm];
+	if (n_members) *n_members = nm;
+	*out_bytes = total;
+	if (member_off) for (long long i = 0; i <= nm; ++i) member_off[i] = c.h_off[(size_t)i];
+	if (total > (long long)out_cap) return set_error(PSVR_ERR_OVERFLOW, "psvr_bgzf_compress_members: need %lld bytes, have %lld", total, (long long)out_cap);
+	return PSVR_OK;
+}

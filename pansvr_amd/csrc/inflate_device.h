@@ -120,6 +120,36 @@ PSVR_IF uint32_t inf_xpow8(uint32_t n)
 	return p;
 }
 
+// the byte table of the reflected CRC32 (a sync of the caller's comes before its first reader)
+template <int NL>
+PSVR_IF void inf_crc_table(uint32_t *crc_tab, int lane)
+{
+	for (int i = lane; i < 256; i += NL) {
+		uint32_t c = (uint32_t)i;
+		for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
+		crc_tab[i] = c;
+	}
+}
+// CRC32 of p[0, n) by the wavefront (shared with deflate_wave_device.h): lane k takes p[k * slice, (k + 1) * slice), the slices' CRCs are
+// moved to the end and added.  crc_tab: inf_crc_table's; red: 64 words.  Every lane returns the same value.
+template <int NL>
+PSVR_IF uint32_t inf_crc32(const uint8_t *p, uint32_t n, const uint32_t *crc_tab, uint32_t *red, int lane)
+{
+	inf_sync();
+	const uint32_t slice = (n + 63u) / 64u;
+	for (int k = lane; k < 64; k += NL) {                                                       // (64 slices on the host too: the same arithmetic)
+		const uint32_t lo = (uint32_t)k * slice < n ? (uint32_t)k * slice : n;
+		const uint32_t hi = lo + slice < n ? lo + slice : n;
+		uint32_t c = 0xffffffffu;
+		for (uint32_t i = lo; i < hi; ++i) c = crc_tab[(c ^ p[i]) & 0xffu] ^ (c >> 8);
+		red[k] = hi > lo ? inf_mulmod(inf_xpow8(n - hi), ~c) : 0u;
+	}
+	inf_sync();
+	uint32_t crc = 0;
+	for (int i = 0; i < 64; ++i) crc ^= red[i];
+	return INF_UNI(crc);
+}
+
 // ---- canonical codes ---------------------------------------------------------------------------------------------------------------------
 // the symbol whose code starts the bit string v (first bit = bit 0), among the codes of at most `maxlen` bits (puff.c's decode())
 PSVR_IF bool inf_canon(const uint16_t *cnt, const uint16_t *sym, uint32_t v, int maxlen, uint32_t &s, uint32_t &l)
@@ -253,11 +283,7 @@ PSVR_IF int inf_member(const uint8_t *member, uint32_t bsize, uint32_t hdr, uint
 	const uint8_t *tr = member + bsize - 8;
 	const uint32_t want_crc = tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24;
 	const uint32_t want_n = tr[4] | (uint32_t)tr[5] << 8 | (uint32_t)tr[6] << 16 | (uint32_t)tr[7] << 24;
-	for (int i = lane; i < 256; i += NL) {
-		uint32_t c = (uint32_t)i;
-		for (int k = 0; k < 8; ++k) c = (c & 1u) ? 0xEDB88320u ^ (c >> 1) : c >> 1;
-		t->crc_tab[i] = c;
-	}
+	inf_crc_table<NL>(t->crc_tab, lane);
 	InfBits b;
 	b.base = member, b.pos = hdr, b.end = bsize - 8, b.acc = 0, b.n = 0;
 	InfOut<NL> w;
@@ -375,21 +401,8 @@ PSVR_IF int inf_member(const uint8_t *member, uint32_t bsize, uint32_t hdr, uint
 	w.flush();
 	if (w.o != isize) return kInfTooShort;
 	if (want_n != isize) return kInfTooShort;
-	// CRC32: lane k takes out[k * slice, (k + 1) * slice), the slices' CRCs are moved to the end and added
 	inf_fence();
-	inf_sync();
-	const uint32_t slice = (isize + 63u) / 64u;
-	for (int k = lane; k < 64; k += NL) {                                                       // (64 slices on the host too: the same arithmetic)
-		const uint32_t lo = (uint32_t)k * slice < isize ? (uint32_t)k * slice : isize;
-		const uint32_t hi = lo + slice < isize ? lo + slice : isize;
-		uint32_t c = 0xffffffffu;
-		for (uint32_t i = lo; i < hi; ++i) c = t->crc_tab[(c ^ out[i]) & 0xffu] ^ (c >> 8);
-		t->red[k] = hi > lo ? inf_mulmod(inf_xpow8(isize - hi), ~c) : 0u;
-	}
-	inf_sync();
-	uint32_t crc = 0;
-	for (int i = 0; i < 64; ++i) crc ^= t->red[i];
-	crc = INF_UNI(crc);
+	const uint32_t crc = inf_crc32<NL>(out, isize, t->crc_tab, t->red, lane);
 	return crc == want_crc ? kInfOk : kInfCrc;
 }
 

@@ -7,7 +7,9 @@
 //                        position lies in SAMv1's range; otherwise std::stable_sort on the host.
 //   write_sorted_bam     the header with SO rewritten, the records in the given order in BGZF blocks of 0xff00 bytes compressed on
 //                        `threads` threads, and (coordinate order) the .bai of SAMv1 section 5.2: bins with their chunk lists (virtual
-//                        file offsets), the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.
+//                        file offsets), the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.  With a device
+//                        compressor (BgzfMembersFn, bam_writer.h) a window's blocks go to the device in one call and the block offsets
+//                        are the returned member offsets; a failed call hands that window and all later ones to the host threads.
 // The sorted stream is gathered a window of blocks at a time: it never exists in memory as a whole, only the records do.
 #pragma once
 #include <stdint.h>
@@ -94,6 +96,9 @@ struct SortRecords {
 	}
 };
 
+// members of 0xff00 bytes per call of the device compressor (--deflate-device: BgzfWriter's gather buffer and write_sorted_bam's window)
+static const size_t kDeflateDeviceBlocks = 1024;
+
 // the order in which write_sorted_bam takes the records.  Returns false (and the reason) only when the device sort fails.
 inline bool coordinate_order(const SortRecords &R, int device, std::vector<uint32_t> &ord, bool *on_device, std::string *err)
 {
@@ -132,9 +137,11 @@ inline void name_order(const SortRecords &R, std::vector<uint32_t> &ord)
 
 // writes out_fn (and out_fn + ".bai" unless by_name); false with the reason in *err
 inline bool write_sorted_bam(const std::string &out_fn, const std::string &header_text, const std::vector<std::pair<std::string, int32_t>> &refs,
-                             const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err)
+                             const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err,
+                             BgzfMembersFn dev_fn = nullptr, int device = 0, size_t dev_window_blocks = kDeflateDeviceBlocks)
 {
 	if (threads < 1) threads = 1;
+	if (dev_window_blocks < 1) dev_window_blocks = 1;
 	// header with the sort order stated, as samtools rewrites it
 	std::string text = header_text;
 	while (!text.empty() && text.back() == '\0') text.pop_back();
@@ -159,11 +166,27 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 	FILE *fo = fopen(out_fn.c_str(), "wb");
 	if (!fo) { *err = "fail to open file '" + out_fn + "'"; return false; }
 	// BGZF blocks of 0xff00 uncompressed bytes of the whole stream, the header included; their file offsets give the virtual offsets
-	const size_t kBlock = 0xff00, kWindow = (size_t)(threads < 4 ? 4 : threads) * 16 * kBlock;
+	const size_t kBlock = 0xff00, kHostWindow = (size_t)(threads < 4 ? 4 : threads) * 16 * kBlock;
 	std::vector<uint64_t> cstart(1, 0);
 	std::vector<std::vector<uint8_t>> comp;
+	std::vector<uint8_t> dev_out;
+	std::vector<int64_t> dev_off;
 	bool ok = true;
 	auto flush = [&](size_t nb) {                     // compresses and writes the first nb blocks of win (the last one may be short)
+		const size_t used = nb * kBlock < win.size() ? nb * kBlock : win.size();
+		if (dev_fn) {
+			dev_out.resize(used + nb * 32), dev_off.assign(nb + 1, 0);          // (a member: its input + 31 bytes at most)
+			int64_t got = 0, nm = 0;
+			if (dev_fn(device, win.data(), (int64_t)used, (int32_t)kBlock, dev_out.data(), (int64_t)dev_out.size(), &got, dev_off.data(), (int64_t)nb, &nm) == 0 && (size_t)nm == nb) {
+				if (fwrite(dev_out.data(), 1, (size_t)got, fo) != (size_t)got) { *err = "fail to write file '" + out_fn + "'"; ok = false; return; }
+				const uint64_t base = cstart.back();
+				for (size_t b = 1; b <= nb; ++b) cstart.push_back(base + (uint64_t)dev_off[b]);
+				win.erase(win.begin(), win.begin() + (long)used);
+				return;
+			}
+			fprintf(stderr, "[panSVR-amd] BGZF on the device failed (%s): compressing on the host\n", psvr_last_error());
+			dev_fn = nullptr;
+		}
 		comp.resize(nb);
 		std::atomic<size_t> next(0);
 		auto work = [&]() {
@@ -183,13 +206,12 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 			if (fwrite(comp[b].data(), 1, comp[b].size(), fo) != comp[b].size()) { *err = "fail to write file '" + out_fn + "'"; ok = false; return; }
 			cstart.push_back(cstart.back() + comp[b].size());
 		}
-		const size_t used = nb * kBlock < win.size() ? nb * kBlock : win.size();
 		win.erase(win.begin(), win.begin() + (long)used);
 	};
 	for (size_t i = 0; i < ord.size() && ok; ++i) {
 		const uint8_t *r = R.rec(ord[i]);
 		win.insert(win.end(), r, r + 4 + SortRecords::u32(r));
-		if (win.size() >= kWindow) flush(win.size() / kBlock);
+		if (win.size() >= (dev_fn ? dev_window_blocks * kBlock : kHostWindow)) flush(win.size() / kBlock);
 	}
 	if (ok && !win.empty()) flush((win.size() + kBlock - 1) / kBlock);
 	static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};

@@ -37,6 +37,7 @@ def main():
     ap.add_argument("--pairs", type=int, default=1000000)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--deflate-device", action="store_true")
     a = ap.parse_args()
     import bench_data
     tmp = tempfile.mkdtemp(prefix="psvr_alnsort_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -67,6 +68,21 @@ def main():
                                     "max_rss_mb": round(m3), "out_bytes": os.path.getsize(o2)})
             same = all(open(x, "rb").read() == open(y, "rb").read() for x, y in ((s, o2), (s + ".bai", o2 + ".bai"), (p, p2)))
             res.setdefault("identical", []).append(same)
+            if a.deflate_device:
+                import gzip
+                o3, p3, s3 = (os.path.join(tmp, x) for x in ("o3.bam", "p3.bam", "s3.bam"))
+                w4, m4, j4 = run([CLI, "aln", "--sort", "--deflate-device", "-t", t, "-o", o3, "-p", p3] + pos)
+                res.setdefault("aln_sort_deflate_device", []).append({"wall_s": round(w4, 3), "e2e_wall_s": j4["wall_s"], "index_s": j4["index_s"], "sort_s": j4["sort_s"],
+                                                                      "write_s": j4["write_s"], "max_rss_mb": round(m4), "out_bytes": os.path.getsize(o3)})
+                w5, m5, _ = run([CLI, "sort", "--deflate-device", "-t", t, "-o", s3, o])
+                res.setdefault("sort_deflate_device", []).append({"sort_wall_s": round(w5, 3), "sort_max_rss_mb": round(m5), "out_bytes": os.path.getsize(s3)})
+                # the unsorted route: the same option, and the fastest host route, beside two_step's default `aln`
+                for key, flags in (("aln_deflate_device", ["--deflate-device"]), ("aln_bgzf_fast", ["--bgzf-fast"])):
+                    o4, p4 = os.path.join(tmp, "o4.bam"), os.path.join(tmp, "p4.bam")
+                    w6, m6, j6 = run([CLI, "aln"] + flags + ["-t", t, "-o", o4, "-p", p4] + pos)
+                    res.setdefault(key, []).append({"wall_s": round(w6, 3), "e2e_wall_s": j6["wall_s"], "write_s": j6["write_s"], "max_rss_mb": round(m6), "out_bytes": os.path.getsize(o4)})
+                ref = gzip.open(s, "rb").read()
+                res.setdefault("deflate_device_same_payload", []).append(all(gzip.open(x, "rb").read() == ref for x in (o3, s3)))
         print(json.dumps(res), flush=True)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
