@@ -8,6 +8,10 @@
 //   * bin = reg2bin(pos, pos + reference length of the CIGAR), or reg2bin(pos, pos + 1) without a CIGAR or with FLAG 0x4
 //     (sam_parse1 takes a span of 1 for an unmapped record whatever its CIGAR, htslib sam.c:1270-1278),
 //   * sequence as 4-bit codes of "=ACMGRSVTWYHKDBN", qualities as phred (text - 33), '*' -> 0xff.
+// BgzfWriter is the one BGZF block writer: the stream cut every 0xff00 bytes, each block one member (bgzf_format.h has the framing), made
+// by zlib or the built-in encoder on the worker pool or, a batch gathered in page-locked memory at a time, by a device compressor of the
+// shape of BgzfMembersFn; a failed device call hands its batch and everything after it to the host, in order.  It can log where every
+// block starts in the file, which is what the sorted writer's .bai is built from (sorted_bam.h).
 // Byte-identity with htslib's BGZF blocks is not claimed (block boundaries and deflate output depend on the
 // zlib build); the decompressed stream is pinned byte for byte against the reference's own htslib output
 // (tests/golden/<set>/<reads>.bam, written by bam_hdr_write / bam_write1: tests/test_bam_golden.py, tests/test_aln_gpu.py).
@@ -20,7 +24,6 @@
 #include <atomic>
 #include <memory>
 #include <string>
-#include <thread>
 #include <vector>
 #include "worker_pool.h"
 #include "deflate_device.h"
@@ -51,17 +54,25 @@ class BgzfWriter {
 	FILE *f_ = nullptr;
 	std::vector<uint8_t> buf_;
 	std::vector<uint8_t> out_;                    // compressed blocks of a flush
-	static const size_t kBlock = 0xff00;      // uncompressed bytes per BGZF block (htslib's BGZF_BLOCK_SIZE)
+	static const size_t kBlock = kBgzfBlock;      // every block but the last holds this much of the stream, on every route
 	static const size_t kOut = 0x10000 + 64;
-	bool ok_ = true;
+	bool ok_ = true, compress_failed_ = false;
 	int threads_ = 1;
 	int level_ = Z_DEFAULT_COMPRESSION;           // htslib's "wb" is zlib's default level too
-	int device_ = -1;                             // >= 0: BGZF members come from psvr_bgzf_compress on that device ...
-	BgzfMembersFn members_ = nullptr;             // ... or, when set, from this compressor: a wavefront per member of kBlock bytes
+	int device_ = -1;                             // >= 0: a flush of dev_min_ blocks or more goes to members_ on that device
+	BgzfMembersFn members_ = nullptr;
+	bool members_are_blocks_ = false;             // the compressor makes one member of every kBlock bytes (set_device_members; not set_device)
+	size_t dev_min_;
 	uint8_t *pin_in_ = nullptr, *pin_out_ = nullptr;   // page-locked: the records of a batch, its members
 	size_t pin_n_ = 0, pin_out_cap_ = 0;
 	size_t gather_blocks_;                        // blocks of records gathered in page-locked memory per device call
-	// one member: gzip header with the BC extra field, raw deflate, CRC32, ISIZE (SAMv1 4.1); returns the member size
+	bool log_ = false;
+	std::vector<uint64_t> starts_;                // log_block_starts()
+	std::vector<int64_t> dev_off_;
+	uint64_t fpos_ = 0;                           // bytes handed to fwrite
+	void put(const uint8_t *p, size_t n) { if (fwrite(p, 1, n, f_) != n) ok_ = false; fpos_ += n; }
+	static uint32_t crc_of(const uint8_t *p, size_t n) { return (uint32_t)crc32(crc32(0L, Z_NULL, 0), p, (uInt)n); }
+	// one member: raw deflate inside bgzf_wrap (bgzf_format.h); returns the member size
 	static size_t compress_block(const uint8_t *p, size_t n, uint8_t *out, int level = Z_DEFAULT_COMPRESSION)
 	{
 		z_stream zs;
@@ -72,14 +83,7 @@ class BgzfWriter {
 		int rc = deflate(&zs, Z_FINISH);
 		deflateEnd(&zs);
 		if (rc != Z_STREAM_END) return 0;
-		const size_t clen = zs.total_out, bsize = clen + 18 + 8 - 1;
-		static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-		memcpy(out, hdr, 16);
-		out[16] = (uint8_t)(bsize & 0xff), out[17] = (uint8_t)(bsize >> 8);
-		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), p, (uInt)n);
-		uint8_t *t = out + 18 + clen;
-		for (int i = 0; i < 4; ++i) t[i] = (uint8_t)(crc >> (8 * i)), t[4 + i] = (uint8_t)((uint32_t)n >> (8 * i));
-		return clen + 26;
+		return bgzf_wrap(out, (uint32_t)zs.total_out, crc_of(p, n), (uint32_t)n);
 	}
 	// the same member from this repository's own encoder (deflate_device.h, the one the device route runs a lane per member, here a host
 	// thread per member): greedy LZ77 + one dynamic-Huffman block.  1.6 x zlib level 1's speed per thread for members 8 - 10 % larger.
@@ -93,32 +97,31 @@ class BgzfWriter {
 		uint32_t *tk = (uint32_t *)(((uintptr_t)tok.data() + 15) & ~(uintptr_t)15);
 		const size_t clen = deflate_block(p, (uint32_t)n, out + 18, (uint32_t)(0x10000 - 26), fast.data(), hbits, tk);
 		if (!clen) return 0;
-		const size_t bsize = clen + 18 + 8 - 1;
-		static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-		memcpy(out, hdr, 16);
-		out[16] = (uint8_t)(bsize & 0xff), out[17] = (uint8_t)(bsize >> 8);
-		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), p, (uInt)n);
-		uint8_t *t = out + 18 + clen;
-		for (int i = 0; i < 4; ++i) t[i] = (uint8_t)(crc >> (8 * i)), t[4 + i] = (uint8_t)((uint32_t)n >> (8 * i));
-		return clen + 26;
+		return bgzf_wrap(out, (uint32_t)clen, crc_of(p, n), (uint32_t)n);
 	}
+#ifdef PSVR_BGZF_ON_DEVICE
+	// psvr_bgzf_compress (a lane per block of its own size) in the shape of BgzfMembersFn: the members decode like any other, but they are
+	// not members of member_bytes, so it has no offsets to give
+	static int lane_per_block(int device, const void *in, int64_t n, int32_t, void *out, int64_t cap, int64_t *got, int64_t *, int64_t, int64_t *) { return psvr_bgzf_compress(device, in, n, out, cap, got); }
+#endif
 public:
 	static const int kLevelFast = -2;             // `level`: zlib's levels, Z_DEFAULT_COMPRESSION (-1), or this: compress_block_fast
 	static size_t compress_block_public(const uint8_t *p, size_t n, uint8_t *out) { return compress_block(p, n, out); }   // out: 0x10000 + 64 bytes
 private:
-	// blocks are independent: compress them on `threads_` threads, write in order
+	// blocks are independent: from the device in one call, or compressed on `threads_` threads; written in order
 	void flush_blocks(const uint8_t *p, size_t n)
 	{
 		const size_t nb = (n + kBlock - 1) / kBlock;
 #ifdef PSVR_BGZF_ON_DEVICE
-		static const size_t dev_min = getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS") ? (size_t)atoll(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS")) : 64;   // (tests: small files through the device too)
-		if (device_ >= 0 && nb >= dev_min) {
-			const size_t need = members_ ? n + nb * 32 : (size_t)psvr_bgzf_bound((int64_t)n);   // (a member of the wavefront encoder: its input + 31 bytes at most)
+		if (device_ >= 0 && nb >= dev_min_) {
+			const size_t need = members_are_blocks_ ? (size_t)bgzf_members_max((int64_t)n, kBlock) : (size_t)psvr_bgzf_bound((int64_t)n);
 			if (need > pin_out_cap_) { if (pin_out_) psvr_host_free(pin_out_); pin_out_ = (uint8_t *)psvr_host_alloc(need), pin_out_cap_ = pin_out_ ? need : 0; }
-			int64_t got = 0;
-			if (pin_out_ && (members_ ? members_(device_, p, (int64_t)n, (int32_t)kBlock, pin_out_, (int64_t)pin_out_cap_, &got, nullptr, 0, nullptr)
-			                          : psvr_bgzf_compress(device_, p, (int64_t)n, pin_out_, (int64_t)pin_out_cap_, &got)) == 0) {
-				if (fwrite(pin_out_, 1, (size_t)got, f_) != (size_t)got) ok_ = false;
+			int64_t got = 0, nm = 0;
+			if (log_) dev_off_.assign(nb + 1, 0);
+			if (pin_out_ && members_(device_, p, (int64_t)n, (int32_t)kBlock, pin_out_, (int64_t)pin_out_cap_, &got, log_ ? dev_off_.data() : nullptr, log_ ? (int64_t)nb : 0, log_ ? &nm : nullptr) == 0 &&
+			    (!log_ || (size_t)nm == nb)) {
+				if (log_) for (size_t b = 0; b < nb; ++b) starts_.push_back(fpos_ + (uint64_t)dev_off_[b]);
+				put(pin_out_, (size_t)got);
 				return;
 			}
 			fprintf(stderr, "[panSVR-amd] BGZF on the device failed (%s): compressing on the host\n", psvr_last_error());
@@ -138,24 +141,39 @@ private:
 		const int nt = threads_ < 1 ? 1 : (size_t)threads_ > nb ? (int)nb : threads_;
 		thread_pool().run(nt, [&](int) { work(); });
 		for (size_t b = 0; b < nb; ++b) {
-			if (!len[b] || fwrite(out.data() + b * kOut, 1, len[b], f_) != len[b]) ok_ = false;
+			if (!len[b]) { ok_ = false, compress_failed_ = true; continue; }
+			if (log_) starts_.push_back(fpos_);
+			put(out.data() + b * kOut, len[b]);
 		}
 	}
 public:
-	explicit BgzfWriter(size_t gather_blocks = 3072) : gather_blocks_(gather_blocks < 1 ? 1 : gather_blocks) {}
+	// dev_min: PSVR_BGZF_DEVICE_MIN_BLOCKS (tests: small files through the device too)
+	explicit BgzfWriter(size_t gather_blocks = 3072) : dev_min_(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS") ? (size_t)atoll(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS")) : 64), gather_blocks_(gather_blocks < 1 ? 1 : gather_blocks) {}
 	bool open(const char *fn, int threads = 1, int level = Z_DEFAULT_COMPRESSION) { f_ = fopen(fn, "wb"); threads_ = threads; level_ = level; return f_ != nullptr; }
-	// compress on HIP device `d` (psvr_bgzf_compress: a lane per block; the members decode like any other, their bytes are not zlib's)
-	void set_device(int d) { device_ = d; }
+	bool ok() const { return ok_; }                             // nothing has failed so far; when something has: in compressing, or in writing
+	bool compress_failed() const { return compress_failed_; }
+#ifdef PSVR_BGZF_ON_DEVICE
+	// compress on HIP device `d` (psvr_bgzf_compress: a lane per block; the members decode like any other, their bytes are not zlib's);
+	// refused (false) when the block starts are logged
+	bool set_device(int d) { if (log_) return false; device_ = d, members_ = &lane_per_block, members_are_blocks_ = false; return true; }
 	// compress on HIP device `d` through `fn` (psvr_bgzf_compress_members: a wavefront per member of 0xff00 bytes), gather_blocks members per
 	// call (0: as constructed); before the first write() after open()'s header.  A failed call is handled as on the other device route.
-	void set_device_members(int d, BgzfMembersFn fn, size_t gather_blocks = 0) { device_ = d, members_ = fn; if (gather_blocks && !pin_in_) gather_blocks_ = gather_blocks; }
+	void set_device_members(int d, BgzfMembersFn fn, size_t gather_blocks = 0) { device_ = d, members_ = fn, members_are_blocks_ = true; if (gather_blocks && !pin_in_) gather_blocks_ = gather_blocks; }
+	// a flush of fewer blocks than this (the stream's tail, as a rule) goes to the host though a device is set
+	void set_device_min_blocks(size_t n) { dev_min_ = n; }
+#endif
+	// Keeps the file offset at which every block starts, the EOF block's last: what virtual file offsets (the .bai) are made of.  Block b
+	// holds bytes [b * 0xff00, (b + 1) * 0xff00) of the stream on the host route and the members route; set_device's route cuts its own
+	// blocks, and the two refuse each other (false).  Before the first write().
+	bool log_block_starts() { if (device_ >= 0 && !members_are_blocks_) return false; log_ = true; return true; }
+	const std::vector<uint64_t> &block_starts() const { return starts_; }
 	void write(const void *p, size_t n)
 	{
 		const uint8_t *b = (const uint8_t *)p;
 #ifdef PSVR_BGZF_ON_DEVICE
 		if (device_ >= 0) {
 			// the records gather in page-locked memory (the transfer starts from where they lie: out of pageable memory the runtime copies
-			// them once more), whole batches go to the device, what is left at close() to the host's zlib
+			// them once more), whole batches go to the device, what is left at close() to the device or, below dev_min_ blocks, the host's zlib
 			const size_t cap = kBlock * gather_blocks_;
 			if (!pin_in_ && !(pin_in_ = (uint8_t *)psvr_host_alloc(cap))) { device_ = -1; }
 			else {
@@ -189,8 +207,8 @@ public:
 		if (pin_out_) psvr_host_free(pin_out_), pin_out_ = nullptr, pin_out_cap_ = 0;
 #endif
 		if (!buf_.empty()) flush_blocks(buf_.data(), buf_.size());
-		static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-		if (fwrite(eof, 1, 28, f_) != 28) ok_ = false;
+		if (log_) starts_.push_back(fpos_);
+		put(kBgzfEof, sizeof kBgzfEof);
 		if (fclose(f_) != 0) ok_ = false;
 		f_ = nullptr;
 		return ok_;
@@ -224,6 +242,18 @@ inline int bam_reg2bin(int64_t beg, int64_t end)             // SAMv1 section 5.
 	return 0;
 }
 
+// what a BAM stream starts with (SAMv1 4.2): magic, header text, reference names and lengths
+inline std::vector<uint8_t> bam_header_block(const std::string &text, const std::vector<BamRef> &refs)
+{
+	std::vector<uint8_t> h = {'B', 'A', 'M', 1};
+	auto put32 = [&](uint32_t x) { for (int i = 0; i < 4; ++i) h.push_back((uint8_t)(x >> (8 * i))); };
+	put32((uint32_t)text.size());
+	h.insert(h.end(), text.begin(), text.end());
+	put32((uint32_t)refs.size());
+	for (const BamRef &r : refs) { put32((uint32_t)r.name.size() + 1); h.insert(h.end(), r.name.begin(), r.name.end()); h.push_back(0); put32(r.len); }
+	return h;
+}
+
 // one alignment record in SAM terms (what the CLI's emit_record prints)
 struct SamFields {
 	std::string qname, cigar, seq, qual, tags;   // tags: "\tXX:t:value..." as in the SAM line; cigar/seq/qual may be "*"
@@ -238,16 +268,6 @@ public:
 private:
 	template <class V> static void put32(V &v, uint32_t x) { for (int i = 0; i < 4; ++i) v.push_back((uint8_t)(x >> (8 * i))); }
 	template <class V> static void put16(V &v, uint16_t x) { v.push_back((uint8_t)x), v.push_back((uint8_t)(x >> 8)); }
-	static int reg2bin(int64_t beg, int64_t end)             // SAMv1 section 5.3
-	{
-		--end;
-		if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-		if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-		if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-		if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-		if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-		return 0;
-	}
 	template <class V> static void put_int_tag(V &v, long long x)   // smallest type, as sam_parse1 chooses
 	{
 		if (x < 0) {
@@ -300,16 +320,7 @@ public:
 	bool open(const char *fn, const std::string &header_text, const std::vector<BamRef> &refs, int threads = 1, int level = Z_DEFAULT_COMPRESSION)
 	{
 		if (!z_.open(fn, threads, level)) return false;
-		std::vector<uint8_t> h = {'B', 'A', 'M', 1};
-		put32(h, (uint32_t)header_text.size());
-		h.insert(h.end(), header_text.begin(), header_text.end());
-		put32(h, (uint32_t)refs.size());
-		for (const BamRef &r : refs) {
-			put32(h, (uint32_t)r.name.size() + 1);
-			h.insert(h.end(), r.name.begin(), r.name.end());
-			h.push_back(0);
-			put32(h, r.len);
-		}
+		const std::vector<uint8_t> h = bam_header_block(header_text, refs);
 		z_.write(h.data(), h.size());
 		return true;
 	}
@@ -342,7 +353,7 @@ public:
 		put32(rec_, (uint32_t)s.tid), put32(rec_, (uint32_t)(int32_t)pos0);
 		rec_.push_back((uint8_t)(s.qname.size() + 1)), rec_.push_back((uint8_t)s.mapq);
 		const bool has_cigar = !s.cigar.empty() && s.cigar != "*";
-		put16(rec_, (uint16_t)reg2bin(pos0 < 0 ? 0 : pos0, (pos0 < 0 ? 0 : pos0) + (has_cigar && !(s.flag & 0x4) ? rlen : 1)));
+		put16(rec_, (uint16_t)bam_reg2bin(pos0 < 0 ? 0 : pos0, (pos0 < 0 ? 0 : pos0) + (has_cigar && !(s.flag & 0x4) ? rlen : 1)));
 		if (cig.size() > 0xffff) { rec_.resize(base); return false; }     // n_cigar_op is 16 bits (no CG:B long-CIGAR tag is written)
 		put16(rec_, (uint16_t)cig.size()), put16(rec_, (uint16_t)s.flag);
 		put32(rec_, l_seq);
@@ -374,8 +385,7 @@ public:
 		return true;
 	}
 	void write_raw(const void *p, size_t n) { z_.write(p, n); }
-	void set_device(int d) { z_.set_device(d); }
-	void set_device_members(int d, BgzfMembersFn fn, size_t gather_blocks = 0) { z_.set_device_members(d, fn, gather_blocks); }
+	BgzfWriter &bgzf() { return z_; }                          // (set_device, set_device_members)
 	bool close() { return z_.close(); }
 };
 

@@ -5,7 +5,6 @@
 // block, CRC32 from an LDS table), and a second launch packs the members next to each other for one transfer back.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
-#include <mutex>
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "common.h"
@@ -34,11 +33,8 @@ __global__ __launch_bounds__(64) void k_bgzf_deflate(const uint8_t *in, long lon
 	const uint32_t n = (uint32_t)(n_bytes - b * (long long)blk < (long long)blk ? n_bytes - b * (long long)blk : (long long)blk);
 	uint8_t *out = slots + b * (long long)slot;
 	const uint32_t c = deflate_block(src, n, out + 18, slot - 26, fast, kBgzfHashBits, (uint32_t *)(work + (size_t)b * work_stride));
-	// the member around it: gzip header with the BC extra field (BSIZE = member size - 1), CRC32 and ISIZE of the uncompressed bytes (SAMv1 4.1)
-	const uint32_t bsize = c + 18 + 8 - 1;
-	const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-	for (int i = 0; i < 16; ++i) out[i] = hdr[i];
-	out[16] = (uint8_t)bsize, out[17] = (uint8_t)(bsize >> 8);
+	// the member around it (SAMv1 4.1, bgzf_format.h): the header, the CRC32 of the uncompressed bytes, the trailer
+	bgzf_wrap_head(out, c);
 	uint32_t crc = 0xffffffffu;
 	{
 		uint32_t i = 0;
@@ -51,8 +47,7 @@ __global__ __launch_bounds__(64) void k_bgzf_deflate(const uint8_t *in, long lon
 		for (; i < n; ++i) crc = crc_tab[(crc ^ src[i]) & 0xffu] ^ (crc >> 8);
 	}
 	crc = ~crc;
-	uint8_t *t = out + 18 + c;
-	for (int i = 0; i < 4; ++i) t[i] = (uint8_t)(crc >> (8 * i)), t[4 + i] = (uint8_t)(n >> (8 * i));
+	bgzf_wrap_tail(out, c, crc, n);
 	len[b] = c ? (int32_t)(c + 26) : 0;
 }
 // the members side by side: a workgroup per block
@@ -65,11 +60,10 @@ __global__ __launch_bounds__(256) void k_bgzf_pack(const uint8_t *slots, uint32_
 	for (int i = threadIdx.x; i < n; i += 256) d[i] = s[i];
 }
 
-struct BgzfCtx {
-	std::mutex mu;
-	int device = -1;
+struct BgzfCtx : DeviceService {
 	DevBuf in, slots, work, len, off, packed;
-	hipStream_t stream = nullptr;
+	std::vector<int32_t> h_len;              // what asynchronous copies read and write on the host lives as long as the stream
+	std::vector<long long> h_off;
 };
 static BgzfCtx &bgzf_ctx() { static BgzfCtx c; return c; }
 
@@ -94,14 +88,8 @@ extern "C" int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, v
 	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
 	BgzfCtx &c = bgzf_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
-	PSVR_HIP(hipSetDevice(device));
-	if (c.device != device) {
-		c.in.release(), c.slots.release(), c.work.release(), c.len.release(), c.off.release(), c.packed.release();
-		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
-		c.device = device;
-		PSVR_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-		PSVR_HIP(hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 + 64 * (int)kBgzfLaneLds));
-	}
+	if (int rc = c.bind(device, false, [&] { c.in.release(), c.slots.release(), c.work.release(), c.len.release(), c.off.release(), c.packed.release(); },
+	                    [] { return hipFuncSetAttribute((const void *)k_bgzf_deflate, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 + 64 * (int)kBgzfLaneLds); })) return rc;
 	const uint32_t blk = bgzf_block_bytes(), slot = blk + 64;             // (a member never exceeds its input by more than the stored block's 5 + 26 bytes)
 	const long long nb = (n_bytes + blk - 1) / blk;
 	const uint32_t wstride = (blk * 4u + 16u + 255u) & ~255u;             // the tokens: a word per input byte at most (+ a group of four)
@@ -111,14 +99,16 @@ extern "C" int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, v
 	PSVR_HIP(c.len.ensure((size_t)nb * 4));
 	PSVR_HIP(c.off.ensure((size_t)nb * 8));
 	PSVR_HIP(c.packed.ensure((size_t)psvr_bgzf_bound(n_bytes)));
+	std::vector<int32_t> &len = c.h_len;
+	std::vector<long long> &off = c.h_off;
+	len.assign((size_t)nb, 0), off.assign((size_t)nb, 0);
+	StreamDrain drain{c.stream};
 	PSVR_HIP(hipMemcpyAsync(c.in.p, in, (size_t)n_bytes, hipMemcpyHostToDevice, c.stream));
 	hipLaunchKernelGGL(k_bgzf_deflate, dim3((unsigned)((nb + 63) / 64)), dim3(64), (size_t)1024 + (size_t)64 * kBgzfLaneLds, c.stream, c.in.as<uint8_t>(), (long long)n_bytes, nb, blk, slot,
 	                   c.slots.as<uint8_t>(), c.work.as<uint8_t>(), wstride, c.len.as<int32_t>());
 	PSVR_HIP(hipGetLastError());
-	std::vector<int32_t> len((size_t)nb);
 	PSVR_HIP(hipMemcpyAsync(len.data(), c.len.p, (size_t)nb * 4, hipMemcpyDeviceToHost, c.stream));
 	PSVR_HIP(hipStreamSynchronize(c.stream));
-	std::vector<long long> off((size_t)nb);
 	long long total = 0;
 	for (long long b = 0; b < nb; ++b) { if (len[(size_t)b] <= 0) return set_error(PSVR_ERR_DEVICE, "psvr_bgzf_compress: block %lld did not fit its member", b); off[(size_t)b] = total, total += len[(size_t)b]; }
 	if (total > out_cap) return set_error(PSVR_ERR_OVERFLOW, "psvr_bgzf_compress: need %lld bytes, have %lld", total, (long long)out_cap);
@@ -126,6 +116,7 @@ extern "C" int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, v
 	hipLaunchKernelGGL(k_bgzf_pack, dim3((unsigned)nb), dim3(256), 0, c.stream, c.slots.as<uint8_t>(), slot, c.len.as<int32_t>(), c.off.as<long long>(), c.packed.as<uint8_t>());
 	PSVR_HIP(hipGetLastError());
 	PSVR_HIP(hipMemcpyAsync(out, c.packed.p, (size_t)total, hipMemcpyDeviceToHost, c.stream));
+	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(c.stream));
 	*out_bytes = total;
 	return PSVR_OK;

@@ -326,8 +326,8 @@ int main(int argc, char **argv)
 	if ((!o.sort && !fo.open(o.out, !o.sam, H, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	SortRecords sorted;                                  // --sort: the main file's records, kept until the input ends
 	static const char *kSortNoMem = "[panSVR-amd] --sort: out of host memory for the main file's records; run `panSVR aln` without --sort, then `panSVR sort` on its output\n";
-	if (o.bgzf_device && !o.sam) fo.bam.set_device(o.devices[0]), fo_ori.bam.set_device(o.devices[0]);
-	if (o.deflate_device) fo.bam.set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks), fo_ori.bam.set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
+	if (o.bgzf_device && !o.sam) fo.bam.bgzf().set_device(o.devices[0]), fo_ori.bam.bgzf().set_device(o.devices[0]);
+	if (o.deflate_device) fo.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks), fo_ori.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
 	FILE *frec = o.records.empty() ? nullptr : fopen(o.records.c_str(), "w");
 	fprintf(stderr, "Processing file: [%s].\n", o.reads.c_str());
 

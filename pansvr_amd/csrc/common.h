@@ -1,8 +1,10 @@
-// common.h -- error plumbing shared by the host-side translation units of libpsvr_engine.so
+// common.h -- what the host-side translation units of libpsvr_engine.so share: error plumbing, the device buffer, and the scaffold of a
+// "service call" (a C ABI function that owns a process-wide stream and device buffers: bgzf.hip, deflate_wave.hip, inflate.hip, sort.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
+#include <mutex>
 #include <string>
 #include "../../include/psvr_engine.h"
 
@@ -49,6 +51,40 @@ struct DevBuf {
 	}
 	hipError_t ensure(size_t n) { return n <= bytes ? hipSuccess : alloc(n + n / 4); }
 	template <class T> T *as() const { return (T *)p; }
+};
+
+// The process-wide state of a service call: one caller at a time (mu), on the stream of the device it was last bound to.  The owner
+// derives its context from it and keeps there what an asynchronous copy touches on the host, so that it lives as long as the stream.
+struct DeviceService {
+	std::mutex mu;
+	int device = -1;
+	hipStream_t stream = nullptr;
+	// Makes `dev` current; when it is not the bound one: release() frees the owner's DevBufs, the stream is made anew (lowest_priority: an
+	// engine launch that becomes ready while a call runs is not kept waiting behind it), setup() does what the owner needs once per device
+	// (a hipError_t).  The device is recorded only once all of that has succeeded: after a failure the next call starts over.
+	template <class Release, class Setup> int bind(int dev, bool lowest_priority, Release release, Setup setup)
+	{
+		PSVR_HIP(hipSetDevice(dev));
+		if (device == dev) return PSVR_OK;
+		device = -1;
+		release();
+		if (stream) (void)hipStreamDestroy(stream), stream = nullptr;
+		int least = 0, greatest = 0;                                     // (0: the default priority)
+		if (lowest_priority) PSVR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+		PSVR_HIP(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, least));
+		PSVR_HIP(setup());
+		device = dev;
+		return PSVR_OK;
+	}
+	template <class Release> int bind(int dev, bool lowest_priority, Release release) { return bind(dev, lowest_priority, release, [] { return hipSuccess; }); }
+};
+
+// Between a call's first asynchronous operation and its last wait: an error return in between leaves nothing in flight that reads the
+// caller's input or writes its output.  Declared after the buffers the stream touches; disarmed before the wait that ends the call.
+struct StreamDrain {
+	hipStream_t s;
+	bool armed = true;
+	~StreamDrain() { if (armed) (void)hipStreamSynchronize(s); }
 };
 
 } // namespace psvr

@@ -9,9 +9,10 @@
 //     frequencies, limited to 15 bits the way miniz does it, canonical codes; the code-length alphabet is sent with fixed 4-bit codes
 //     for the lengths 0..15 (no run-length symbols: ~160 header bytes per 64 KB block);
 //   * a stored block when that does not pay (the member must fit BGZF's 64 KB).
-// The gzip wrapper, CRC32 and ISIZE of a BGZF member are the host's (bam_writer.h).
+// The gzip wrapper, CRC32 and ISIZE of a BGZF member are the caller's (bgzf_wrap, bgzf_format.h).
 #pragma once
 #include <stdint.h>
+#include "bgzf_format.h"
 
 #if defined(__HIPCC__)
 #define PSVR_DF __host__ __device__ inline
@@ -21,7 +22,7 @@
 
 namespace psvr {
 
-static const uint32_t kDfMaxIn = 0xff00;           // bytes per BGZF block (htslib's BGZF_BLOCK_SIZE)
+static const uint32_t kDfMaxIn = kBgzfBlock;       // the most a block takes in
 static const int kDfLit = 286, kDfDist = 30;
 
 struct DfBits {                                     // LSB-first bit writer into [p, end): four bytes at a time, one test per put

@@ -4,7 +4,6 @@
 // needs; here a member's 64 KB are shared by the 64 lanes (deflate_wave_device.h), the member sizes become offsets on the device (scan.h)
 // and a pack launch lays the members side by side, so that nothing returns to the host between compressing and packing.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "common.h"
@@ -42,12 +41,9 @@ __global__ __launch_bounds__(256) void k_bgzf_pack_members(const uint8_t *__rest
 	if (threadIdx.x < n - done) d[done + threadIdx.x] = s[done + threadIdx.x];
 }
 
-struct DfwCtx {
-	std::mutex mu;
-	int device = -1;
+struct DfwCtx : DeviceService {
 	DevBuf in, slots, tok, len, off, tmp, packed;
 	std::vector<long long> h_off;            // what an asynchronous copy writes on the host lives as long as the stream
-	hipStream_t stream = nullptr;
 };
 static DfwCtx &dfw_ctx() { static DfwCtx c; return c; }
 
@@ -60,8 +56,8 @@ using namespace psvr;
 extern "C" int64_t psvr_bgzf_members_bound(int64_t n_bytes, int32_t member_bytes)
 {
 	if (n_bytes <= 0 || !member_bytes_ok(member_bytes)) return 0;
-	const int64_t mb = member_bytes ? member_bytes : (int64_t)kDfMaxIn, nm = (n_bytes + mb - 1) / mb;
-	return n_bytes + nm * 31;                                                                  // (a member is at most its input in a stored block: 18 + 5 + 8 bytes around it)
+	const int64_t mb = member_bytes ? member_bytes : (int64_t)kDfMaxIn;
+	return bgzf_members_max(n_bytes, mb);
 }
 
 extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int32_t member_bytes, void *out, int64_t out_cap, int64_t *out_bytes,
@@ -79,17 +75,7 @@ extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_
 	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
 	DfwCtx &c = dfw_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
-	PSVR_HIP(hipSetDevice(device));
-	if (c.device != device) {                                                              // (recorded once everything of the device is set up)
-		c.device = -1;
-		c.in.release(), c.slots.release(), c.tok.release(), c.len.release(), c.off.release(), c.tmp.release(), c.packed.release();
-		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
-		// the lowest priority there is: an engine launch that becomes ready while a call runs is not kept waiting behind it
-		int least = 0, greatest = 0;
-		PSVR_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-		PSVR_HIP(hipStreamCreateWithPriority(&c.stream, hipStreamNonBlocking, least));
-		c.device = device;
-	}
+	if (int rc = c.bind(device, true, [&] { c.in.release(), c.slots.release(), c.tok.release(), c.len.release(), c.off.release(), c.tmp.release(), c.packed.release(); })) return rc;
 	const uint32_t slot = dfw_slot_bytes(mb), tok_stride = (mb + 1u + 63u) & ~63u;         // (words: a token per input byte at most, and the end of block)
 	const long long bound = psvr_bgzf_members_bound(n_bytes, (int32_t)mb);
 	PSVR_HIP(c.in.ensure((size_t)n_bytes));
@@ -100,8 +86,7 @@ extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_
 	PSVR_HIP(c.tmp.ensure(scan_tmp_bytes(1, nm + 1)));
 	PSVR_HIP(c.packed.ensure((size_t)bound));
 	c.h_off.assign((size_t)nm + 1, 0);
-	// (an error return in between leaves nothing in flight that reads the caller's `in` or writes its `out`)
-	struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{c.stream};
+	StreamDrain drain{c.stream};
 	PSVR_HIP(hipMemcpyAsync(c.in.p, in, (size_t)n_bytes, hipMemcpyHostToDevice, c.stream));
 	PSVR_HIP(hipMemsetAsync(c.len.as<int32_t>() + nm, 0, 4, c.stream));                     // (the scan runs over nm + 1 sizes: its last offset is the total)
 	hipLaunchKernelGGL(k_bgzf_deflate_wave, dim3((unsigned)nm), dim3(64), 0, c.stream, c.in.as<uint8_t>(), (long long)n_bytes, mb, c.slots.as<uint8_t>(), slot, c.tok.as<uint32_t>(),

@@ -3,7 +3,6 @@
 // (htslib bgzf.c); members are independent and carry their compressed and inflated sizes in the clear, so the host lays a batch out from
 // the BSIZE / ISIZE fields alone and ONE WAVEFRONT PER MEMBER decodes it (inflate_device.h), CRC32 and ISIZE checked on the device.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "common.h"
@@ -24,13 +23,10 @@ __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *__restrict__
 	if (threadIdx.x == 0) status[blockIdx.x] = rc;
 }
 
-struct InflateCtx {
-	std::mutex mu;
-	int device = -1;
+struct InflateCtx : DeviceService {
 	DevBuf in, out, mem, status;
 	std::vector<InfMember> h_mem;        // what asynchronous copies read and write on the host lives as long as the stream
 	std::vector<int32_t> h_status;
-	hipStream_t stream = nullptr;
 };
 static InflateCtx &inflate_ctx() { static InflateCtx c; return c; }
 
@@ -78,21 +74,13 @@ extern "C" int psvr_bgzf_decompress(int device, const void *in_, int64_t n_bytes
 	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
 	InflateCtx &c = inflate_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
-	PSVR_HIP(hipSetDevice(device));
-	if (c.device != device) {                                                              // (recorded once everything of the device is set up)
-		c.device = -1;
-		c.in.release(), c.out.release(), c.mem.release(), c.status.release();
-		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
-		PSVR_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-		c.device = device;
-	}
+	if (int rc = c.bind(device, false, [&] { c.in.release(), c.out.release(), c.mem.release(), c.status.release(); })) return rc;
 	c.h_mem = mem, c.h_status.assign((size_t)nm, -1);
 	PSVR_HIP(c.in.ensure((size_t)at));
 	PSVR_HIP(c.out.ensure((size_t)total));
 	PSVR_HIP(c.mem.ensure((size_t)nm * sizeof(InfMember)));
 	PSVR_HIP(c.status.ensure((size_t)nm * 4));
-	// (an error return in between leaves nothing in flight that reads the caller's `in` or writes its `out`)
-	struct Drain { hipStream_t s; bool armed = true; ~Drain() { if (armed) (void)hipStreamSynchronize(s); } } drain{c.stream};
+	StreamDrain drain{c.stream};
 	PSVR_HIP(hipMemcpyAsync(c.in.p, in, (size_t)at, hipMemcpyHostToDevice, c.stream));
 	PSVR_HIP(hipMemcpyAsync(c.mem.p, c.h_mem.data(), (size_t)nm * sizeof(InfMember), hipMemcpyHostToDevice, c.stream));
 	hipLaunchKernelGGL(k_bgzf_inflate, dim3((unsigned)nm), dim3(64), 0, c.stream, c.in.as<uint8_t>(), c.mem.as<InfMember>(), c.out.as<uint8_t>(), c.status.as<int32_t>());

@@ -6,7 +6,6 @@
 //              -> k_sort_scatter (a stable rank inside the tile from per-wavefront ballots, the wavefronts' offsets through LDS)
 // Every phase hands over to the next at a kernel boundary: no workgroup waits for another inside a launch.
 #include <hip/hip_runtime.h>
-#include <mutex>
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "common.h"
@@ -111,10 +110,8 @@ __global__ __launch_bounds__(kSortThreads) void k_sort_scatter(const uint64_t *k
 	}
 }
 
-struct SortCtx {
-	std::mutex mu;
-	int device = -1;
-	hipStream_t stream = nullptr;
+struct SortCtx : DeviceService {
+	std::vector<uint32_t> h_hist;            // what an asynchronous copy writes on the host lives as long as the stream
 };
 static SortCtx &sort_ctx() { static SortCtx c; return c; }
 
@@ -130,12 +127,7 @@ extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, 
 	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
 	SortCtx &c = sort_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
-	PSVR_HIP(hipSetDevice(device));
-	if (c.device != device) {
-		if (c.stream) (void)hipStreamDestroy(c.stream), c.stream = nullptr;
-		PSVR_HIP(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-		c.device = device;
-	}
+	if (int rc = c.bind(device, false, [] {})) return rc;                                  // (the buffers are the call's own)
 	hipStream_t st = c.stream;
 	const long long ntile = (n + kSortTile - 1) / kSortTile, ncnt = 256 * ntile;
 	const int nhb = (int)(ntile < kHistBlocks ? ntile : kHistBlocks);
@@ -150,11 +142,13 @@ extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, 
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_u64: %zu bytes of device memory needed for %lld keys", need, (long long)n);
 	}
+	std::vector<uint32_t> &h = c.h_hist;
+	h.assign(2048, 0);
+	StreamDrain drain{st};                                         // (after the buffers: nothing is in flight when they are freed)
 	PSVR_HIP(hipMemcpyAsync(k0.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, st));
 	hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nhb), dim3(256), 0, st, k0.as<uint64_t>(), (long long)n, slab.as<uint32_t>());
 	hipLaunchKernelGGL(k_sort_hist_sum, dim3(8), dim3(256), 0, st, (const uint32_t *)slab.p, nhb, hist.as<uint32_t>());
 	PSVR_HIP(hipGetLastError());
-	std::vector<uint32_t> h(2048);
 	PSVR_HIP(hipMemcpyAsync(h.data(), hist.p, 8192, hipMemcpyDeviceToHost, st));
 	PSVR_HIP(hipStreamSynchronize(st));
 	uint64_t *kin = k0.as<uint64_t>(), *kout = k1.as<uint64_t>();
@@ -174,6 +168,7 @@ extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, 
 		iin = iout, iout = (iout == i0.as<uint32_t>()) ? i1.as<uint32_t>() : i0.as<uint32_t>();
 	}
 	if (iin) PSVR_HIP(hipMemcpyAsync(order, iin, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(st));
 	if (!iin) for (int64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;   // every digit constant: all keys equal, the input order stands
 	return PSVR_OK;

@@ -5,21 +5,19 @@
 //   coordinate_order     samtools' order (bam_sort.c bam1_lt): reference id as unsigned (unplaced records last), position, forward strand
 //                        before reverse, ties in input order.  On the device (psvr_sort_order_u64) when one is visible and every
 //                        position lies in SAMv1's range; otherwise std::stable_sort on the host.
-//   write_sorted_bam     the header with SO rewritten, the records in the given order in BGZF blocks of 0xff00 bytes compressed on
-//                        `threads` threads, and (coordinate order) the .bai of SAMv1 section 5.2: bins with their chunk lists (virtual
-//                        file offsets), the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.  With a device
-//                        compressor (BgzfMembersFn, bam_writer.h) a window's blocks go to the device in one call and the block offsets
-//                        are the returned member offsets; a failed call hands that window and all later ones to the host threads.
-// The sorted stream is gathered a window of blocks at a time: it never exists in memory as a whole, only the records do.
+//   write_sorted_bam     the header with SO rewritten and the records in the given order through BgzfWriter (bam_writer.h: blocks of
+//                        0xff00 bytes from `threads` pool threads or, with a device compressor, a window of blocks per call, the stream's
+//                        tail included; a failed call hands that window and all later ones to the host), and (coordinate order) the .bai
+//                        of SAMv1 section 5.2 from the writer's log of block starts: bins with their chunk lists (virtual file offsets),
+//                        the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.
+// The sorted stream never exists in memory as a whole, only the records do.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
-#include <atomic>
 #include <map>
 #include <string>
-#include <thread>
 #include <utility>
 #include <vector>
 #include "../../include/psvr_engine.h"
@@ -64,14 +62,8 @@ struct SortRecords {
 		memcpy(r + 4, fixed, 32);
 		if (n_data) memcpy(r + 36, data, n_data);
 		const int32_t tid = (int32_t)u32(r + 4), pos = (int32_t)u32(r + 8);
-		const int64_t rlen = ref_span(r), beg = pos < 0 ? 0 : pos, end = beg + (rlen > 0 ? rlen : 1), e = end - 1;
-		int bin;
-		if (beg >> 14 == e >> 14) bin = (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-		else if (beg >> 17 == e >> 17) bin = (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-		else if (beg >> 20 == e >> 20) bin = (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-		else if (beg >> 23 == e >> 23) bin = (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-		else if (beg >> 26 == e >> 26) bin = (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-		else bin = 0;
+		const int64_t rlen = ref_span(r), beg = pos < 0 ? 0 : pos;
+		const int bin = bam_reg2bin(beg, beg + (rlen > 0 ? rlen : 1));
 		r[14] = (uint8_t)bin, r[15] = (uint8_t)(bin >> 8);
 		const uint16_t flag = (uint16_t)(r[18] | r[19] << 8);
 		if (pos < -1 || pos > 0x7ffffffe) key_exact = false;
@@ -140,8 +132,6 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
                              const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err,
                              BgzfMembersFn dev_fn = nullptr, int device = 0, size_t dev_window_blocks = kDeflateDeviceBlocks)
 {
-	if (threads < 1) threads = 1;
-	if (dev_window_blocks < 1) dev_window_blocks = 1;
 	// header with the sort order stated, as samtools rewrites it
 	std::string text = header_text;
 	while (!text.empty() && text.back() == '\0') text.pop_back();
@@ -156,70 +146,25 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 			text = hd + text.substr(eol == std::string::npos ? text.size() : eol);
 		} else text = "@HD\tVN:1.6\tSO:" + so + "\n" + text;
 	}
-	std::vector<uint8_t> win = {'B', 'A', 'M', 1};
-	auto put32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) win.push_back((uint8_t)(v >> (8 * k))); };
-	put32((uint32_t)text.size());
-	win.insert(win.end(), text.begin(), text.end());
-	put32((uint32_t)refs.size());
-	for (auto &rf : refs) { put32((uint32_t)rf.first.size() + 1); win.insert(win.end(), rf.first.begin(), rf.first.end()); win.push_back(0); put32((uint32_t)rf.second); }
-	const uint64_t header_bytes = win.size();
-	FILE *fo = fopen(out_fn.c_str(), "wb");
-	if (!fo) { *err = "fail to open file '" + out_fn + "'"; return false; }
-	// BGZF blocks of 0xff00 uncompressed bytes of the whole stream, the header included; their file offsets give the virtual offsets
-	const size_t kBlock = 0xff00, kHostWindow = (size_t)(threads < 4 ? 4 : threads) * 16 * kBlock;
-	std::vector<uint64_t> cstart(1, 0);
-	std::vector<std::vector<uint8_t>> comp;
-	std::vector<uint8_t> dev_out;
-	std::vector<int64_t> dev_off;
-	bool ok = true;
-	auto flush = [&](size_t nb) {                     // compresses and writes the first nb blocks of win (the last one may be short)
-		const size_t used = nb * kBlock < win.size() ? nb * kBlock : win.size();
-		if (dev_fn) {
-			dev_out.resize(used + nb * 32), dev_off.assign(nb + 1, 0);          // (a member: its input + 31 bytes at most)
-			int64_t got = 0, nm = 0;
-			if (dev_fn(device, win.data(), (int64_t)used, (int32_t)kBlock, dev_out.data(), (int64_t)dev_out.size(), &got, dev_off.data(), (int64_t)nb, &nm) == 0 && (size_t)nm == nb) {
-				if (fwrite(dev_out.data(), 1, (size_t)got, fo) != (size_t)got) { *err = "fail to write file '" + out_fn + "'"; ok = false; return; }
-				const uint64_t base = cstart.back();
-				for (size_t b = 1; b <= nb; ++b) cstart.push_back(base + (uint64_t)dev_off[b]);
-				win.erase(win.begin(), win.begin() + (long)used);
-				return;
-			}
-			fprintf(stderr, "[panSVR-amd] BGZF on the device failed (%s): compressing on the host\n", psvr_last_error());
-			dev_fn = nullptr;
-		}
-		comp.resize(nb);
-		std::atomic<size_t> next(0);
-		auto work = [&]() {
-			std::vector<uint8_t> tmp(0x10000 + 64);
-			for (size_t b = next++; b < nb; b = next++) {
-				const size_t o = b * kBlock, m = win.size() - o < kBlock ? win.size() - o : kBlock;
-				const size_t c = BgzfWriter::compress_block_public(win.data() + o, m, tmp.data());
-				comp[b].assign(tmp.begin(), tmp.begin() + (long)c);
-			}
-		};
-		std::vector<std::thread> th;
-		for (int t = 1; t < threads && (size_t)t < nb; ++t) th.emplace_back(work);
-		work();
-		for (auto &t : th) t.join();
-		for (size_t b = 0; b < nb; ++b) {
-			if (comp[b].empty()) { *err = "compression failed"; ok = false; return; }
-			if (fwrite(comp[b].data(), 1, comp[b].size(), fo) != comp[b].size()) { *err = "fail to write file '" + out_fn + "'"; ok = false; return; }
-			cstart.push_back(cstart.back() + comp[b].size());
-		}
-		win.erase(win.begin(), win.begin() + (long)used);
-	};
-	for (size_t i = 0; i < ord.size() && ok; ++i) {
+	std::vector<BamRef> brefs;
+	for (auto &rf : refs) brefs.push_back({rf.first, (uint32_t)rf.second});
+	const std::vector<uint8_t> head = bam_header_block(text, brefs);
+	const uint64_t header_bytes = head.size();
+	BgzfWriter w(dev_window_blocks);
+	if (!w.open(out_fn.c_str(), threads)) { *err = "fail to open file '" + out_fn + "'"; return false; }
+	w.log_block_starts();
+	if (dev_fn) w.set_device_members(device, dev_fn), w.set_device_min_blocks(1);       // (the tail of the stream goes to the device too)
+	w.write(head.data(), head.size());
+	for (size_t i = 0; i < ord.size() && w.ok(); ++i) {
 		const uint8_t *r = R.rec(ord[i]);
-		win.insert(win.end(), r, r + 4 + SortRecords::u32(r));
-		if (win.size() >= (dev_fn ? dev_window_blocks * kBlock : kHostWindow)) flush(win.size() / kBlock);
+		w.write(r, 4 + SortRecords::u32(r));
 	}
-	if (ok && !win.empty()) flush((win.size() + kBlock - 1) / kBlock);
-	static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-	if (ok && fwrite(eof, 1, 28, fo) != 28) *err = "fail to write file '" + out_fn + "'", ok = false;
-	if (fclose(fo) != 0 && ok) *err = "fail to write file '" + out_fn + "'", ok = false;
-	if (!ok || by_name) return ok;
+	if (!w.close()) { *err = w.compress_failed() ? "compression failed" : "fail to write file '" + out_fn + "'"; return false; }
+	if (by_name) return true;
 	// ---- .bai
-	const size_t nb = cstart.size() - 1;
+	// the stream's blocks of 0xff00 bytes, the header included: their file offsets give the virtual offsets
+	const std::vector<uint64_t> &cstart = w.block_starts();
+	const size_t nb = cstart.size() - 1, kBlock = kBgzfBlock;
 	auto voff = [&](uint64_t u) { const size_t b = (size_t)(u / kBlock); return b < nb ? (cstart[b] << 16) | (u % kBlock) : (cstart[nb] << 16); };   // (the end of the data = the EOF block)
 	struct RefIdx { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; std::vector<uint64_t> lin; uint64_t beg = ~0ull, end = 0, n_mapped = 0, n_unmapped = 0; };
 	std::vector<RefIdx> ri(refs.size());

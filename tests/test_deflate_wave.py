@@ -152,6 +152,10 @@ extern "C" {
 const char *psvr_last_error(void) { return "stand-in failure"; }
 int psvr_device_count(void) { return 0; }
 int psvr_sort_order_u64(int, int64_t, const uint64_t *, uint32_t *) { abort(); }
+void *psvr_host_alloc(size_t n) { return malloc(n); }
+void psvr_host_free(void *p) { free(p); }
+int64_t psvr_bgzf_bound(int64_t n) { return n; }
+int psvr_bgzf_compress(int, const void *, int64_t, void *, int64_t, int64_t *) { abort(); }   // (the other device route: not this test's)
 }
 ''' + STANDIN + r'''
 int main(int argc, char **argv)
@@ -189,7 +193,7 @@ int main(int argc, char **argv)
 def test_write_sorted_bam_members_failure_equals_the_host_route():
     d = tempfile.mkdtemp(prefix="psvr_dfws_")
     open(os.path.join(d, "t.cpp"), "w").write(SORTED)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + CSRC, "-o", os.path.join(d, "t"), os.path.join(d, "t.cpp"), "-lz", "-lpthread"])
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-DPSVR_BGZF_ON_DEVICE", "-I" + CSRC, "-o", os.path.join(d, "t"), os.path.join(d, "t.cpp"), "-lz", "-lpthread"])
     host, dev = os.path.join(d, "host.bam"), os.path.join(d, "dev.bam")
     r = subprocess.run([os.path.join(d, "t"), host, dev], stdout=subprocess.PIPE, stderr=subprocess.PIPE)
     assert r.returncode == 0, r.stderr.decode()

@@ -57,13 +57,8 @@ static int members(uint32_t blk, const char *in_fn, const char *out_fn)
 		const uint32_t n = (uint32_t)(v.size() - at < blk ? v.size() - at : blk);
 		const uint32_t c = deflate_block(v.data() + at, n, out.data() + 18, slot - 26, fast.data(), hbits, tok.data());
 		if (!c) return 3;
-		const uint32_t bsize = c + 18 + 8 - 1;
-		static const uint8_t hdr[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-		memcpy(out.data(), hdr, 16);
-		out[16] = (uint8_t)bsize, out[17] = (uint8_t)(bsize >> 8);
-		const uint32_t crc = (uint32_t)crc32(crc32(0L, Z_NULL, 0), v.data() + at, n);
-		for (int i = 0; i < 4; ++i) out[18 + c + i] = (uint8_t)(crc >> (8 * i)), out[18 + c + 4 + i] = (uint8_t)(n >> (8 * i));
-		if (fwrite(out.data(), 1, c + 26, o) != c + 26) return 2;
+		const uint32_t size = bgzf_wrap(out.data(), c, (uint32_t)crc32(crc32(0L, Z_NULL, 0), v.data() + at, n), n);
+		if (fwrite(out.data(), 1, size, o) != size) return 2;
 	}
 	return fclose(o) == 0 ? 0 : 2;
 }
