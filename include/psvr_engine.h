@@ -131,6 +131,20 @@ int psvr_dp_plan_launch(psvr_dp_plan_t *plan,
 int psvr_dp_plan_describe(const psvr_dp_plan_t *plan, char *buf, size_t buflen);
 void psvr_dp_plan_destroy(psvr_dp_plan_t *plan);
 
+/*
+ * What the planners derive from a parameter set before they look at a shape (no device is touched): the predicates that decide
+ * which kernel families a problem may go to.  The tests hold them against the reference library's behaviour.
+ */
+typedef struct psvr_dp_regime {
+	int32_t skip;           /* the reference returns right after ksw_reset_extz for these parameters */
+	int32_t swapped;        /* extd2: the gap pairs arrived with q+e > q2+e2 and were exchanged */
+	int32_t nowrap_ok;      /* in-band values provably fit int8 (the bound holds and the boundary costs are the recurrences'): the team / tiny kernels may run */
+	int32_t zdrop_inert;    /* extd2: the z-drop rule cannot fire whatever the sequences: the engine's lean team variant may run */
+	int32_t long_thres;
+	int32_t qe_shift;       /* pre-swap q+e minus post-swap q+e (0 for pairs in plain order) */
+} psvr_dp_regime_t;
+int psvr_dp_regime(const psvr_ksw_params_t *par, int variant /*0 extd2, 1 extz2*/, psvr_dp_regime_t *out);
+
 
 /* ------------------------------------------------------------------------------------------
  * The deBGA unipath k-mer index, resident in HBM.

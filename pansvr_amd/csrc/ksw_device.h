@@ -75,9 +75,16 @@ struct TeamPlan {
 template <int LANES, int CPL, int LEAN> __global__ void extd2_team_kernel(DpBatch B, DpParams P, TeamPlan T);          // ksw_kernels.hip: the sweep, a row per lane and step
 template <int LANES, int CPL, int LEAN> __global__ void extd2_team_finish_kernel(DpBatch B, DpParams P, TeamPlan T);   // z-drop / end rules and traceback, a thread per alignment
 // the z-drop rule cannot trigger whatever the sequences are: a gap of any length costs at most q2 (e2 == 0), so an anti-diagonal's maximum
-// is never more than 2 q2 below the running maximum (one insertion + one deletion from the cell that holds it); the team kernel's LEAN
-// variant (no per-diagonal maximum) is exact then, for a caller that reads neither ez.max nor max_q / max_t
-inline bool dp_zdrop_inert(const DpParams &P) { return P.e2 == 0 && (P.zdrop < 0 || P.zdrop >= 2 * P.q2) && !(P.flag & PSVR_EZ_EXTZ_ONLY); }
+// is never more than 2 q2 below the running maximum (one insertion + one deletion from the cell that holds it) -- in a matrix whose first
+// row and column are charged with the same (post-swap) pairs as its interior.  The reference charges H[0] at r == 0 with q + e taken
+// BEFORE the swap (qe_pre, ksw2_extd2_sse.c:60,351): when the caller's pairs arrive in the other order, every H is lower by
+// qe_pre - (q + e) than that argument assumes while the running maximum starts at 0, so the threshold rises by that shift (0 for
+// pairs in plain order).  The team kernel's LEAN variant (no per-diagonal maximum) is exact then, for a caller that reads neither
+// ez.max nor max_q / max_t
+inline bool dp_zdrop_inert(const DpParams &P)
+{
+	return P.e2 == 0 && (P.zdrop < 0 || P.zdrop >= 2 * P.q2 + (P.qe_pre - (P.q + P.e))) && !(P.flag & PSVR_EZ_EXTZ_ONLY);
+}
 // the tiny / team kernels need the lean regime (values fit int8, band never clips) and only the flags they implement
 __host__ __device__ inline bool dp_tiny_ok(const DpParams &P, bool fast_ok) { return fast_ok && P.nowrap_ok && !P.skip && (P.w < 0 || P.w >= PSVR_DP_TINY_MAX); }
 // lanes per alignment of the team kernel for the class of problems with n_strips16 16-column strips

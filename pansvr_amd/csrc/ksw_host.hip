@@ -95,7 +95,15 @@ int make_dp_params(const psvr_ksw_params_t *par, int variant, DpParams *P)
 		int max_sc = par->mat[0];
 		for (int t = 1; t < m * m; ++t) max_sc = std::max<int>(max_sc, par->mat[t]);
 		int g = std::max(q + e, q2 + e2);
-		P->nowrap_ok = (max_sc + 3 * g + std::max(-min_sc, 0) <= 127) && q >= 0 && e >= 0 && q2 >= 0 && e2 >= 0;
+		// That bound is an argument about a DP whose first row and column are charged what the recurrences charge inside.  The reference
+		// charges them q+e, then e per base up to long_thres and e2 per base after it (:151,155): the cheaper of the two pairs at every
+		// length exactly when the second pair is the long-gap pair (e > e2) or the pairs are the same; z <= sc_mch holds in every cell
+		// then and z = min(z, sc_mch) (:193) never binds.  Otherwise the boundary overcharges and the clamp binds beside it.  With
+		// e < e2 what it cuts off accumulates in x / y along a row until the reference's int8 lanes wrap (17+0k | 16+1k at 200 x 201:
+		// score -66, without the wrap -65), which only the wavefront kernels reproduce.  With e == e2 and q2 > q the excess is
+		// bounded by q2 - q and no wrap was seen, but the bound above is not proven there either: not the team / tiny kernels' regime
+		const bool boundary_is_the_recurrences = e > e2 || (e == e2 && q == q2);
+		P->nowrap_ok = (max_sc + 3 * g + std::max(-min_sc, 0) <= 127) && q >= 0 && e >= 0 && q2 >= 0 && e2 >= 0 && boundary_is_the_recurrences;
 	}
 	if (variant == 0) {
 		int lt = e != e2 ? (q2 - q) / (e - e2) - 1 : 0;                             // :95-98
@@ -230,6 +238,19 @@ extern "C" int psvr_dp_plan_describe(const psvr_dp_plan_t *pl, char *buf, size_t
 }
 
 extern "C" void psvr_dp_plan_destroy(psvr_dp_plan_t *pl) { delete pl; }
+
+extern "C" int psvr_dp_regime(const psvr_ksw_params_t *par, int variant, psvr_dp_regime_t *out)
+{
+	if (!par || !out || (variant != 0 && variant != 1)) return set_error(PSVR_ERR_ARG, "psvr_dp_regime: bad argument");
+	DpParams P;
+	int rc = make_dp_params(par, variant, &P);
+	if (rc) return rc;
+	out->skip = P.skip, out->nowrap_ok = P.nowrap_ok, out->long_thres = P.long_thres;
+	out->swapped = variant == 0 && !P.skip && par->q2 + par->e2 < par->q + par->e;
+	out->qe_shift = P.skip ? 0 : P.qe_pre - (P.q + P.e);
+	out->zdrop_inert = variant == 0 && !P.skip && dp_zdrop_inert(P);
+	return PSVR_OK;
+}
 
 extern "C" int psvr_dp_plan_launch(psvr_dp_plan_t *pl, const uint8_t *d_qseq, const int64_t *d_q_off,
                                    const uint8_t *d_tseq, const int64_t *d_t_off,

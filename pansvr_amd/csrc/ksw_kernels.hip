@@ -661,8 +661,11 @@ __global__ __launch_bounds__(64) void extd2_tiny_kernel(DpBatch B, DpParams P, i
 static constexpr int kTeamWaves = 3;
 // LEAN = 1: no per-anti-diagonal maximum (M[], K[], G[], the D[r] records).  That maximum feeds ksw_apply_zdrop and ez.max / max_q / max_t
 // only.  With e2 == 0 a gap of ANY length costs at most q2, so every anti-diagonal behind the cell that holds the running maximum has a cell
-// reachable from it by one insertion and one deletion: its maximum is at least max - 2 q2, and with zdrop >= 2 q2 (the reference's defaults:
-// 32 / 0, zdrop 400) the rule `max - H > zdrop + l * e2` can never hold -- dp_zdrop_inert().  The engine's own launches (seam B1 reads
+// reachable from it by one insertion and one deletion: its maximum is at least max - 2 q2 -- less the pre-swap q + e term: the reference
+// charges H[0] of the first anti-diagonal with q + e taken BEFORE the q+e <= q2+e2 swap (DpParams::qe_pre), which lowers every H by
+// qe_pre - (q + e) for pairs that arrived in the other order while the running maximum starts at 0.  So with
+// zdrop >= 2 q2 + (qe_pre - (q + e)) (the reference's defaults: 16+1 | 32+0 in plain order, term 0, zdrop 400) the rule
+// `max - H > zdrop + l * e2` can never hold -- dp_zdrop_inert().  The engine's own launches (seam B1 reads
 // score, mqe and the CIGAR of its pieces) then run this variant; psvr_extd2_batch, whose ksw_extz_t carries max / max_q / max_t, never does.
 template <int LANES, int CPL, int LEAN>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 8))) void extd2_team_kernel(DpBatch B, DpParams P, TeamPlan T)

@@ -46,6 +46,18 @@ DATASETS = {
 }
 
 
+# `aln` option sets other than the defaults (-M -m -O -E -P -F -z, in that order), run on fx2/reads150 through the reference's own option
+# parser and aligner objects (tests/golden/gen_aln_golden.py writes tests/golden/fx2/reads150.score_*.jsonl.gz, the oracle, emulated-engine
+# and GPU CLI tests read them): three general ones, then one per regime of the DP's routing predicates (make_dp_params,
+# dp_zdrop_inert) -- the gap pairs in the other order with a z-drop inside 2 q2 .. 2 q2 + (pre-swap q+e - post-swap q+e), where the
+# z-drop rule still fires; e2 = 0 with the z-drop one below 2 q2; the int8 bound max_sc + 3 max(q+e, q2+e2) + |min_sc| at exactly 127
+# and at 128; e == e2; and the skip rule -min_sc > 2(q+e), where the reference's DP returns right after ksw_reset_extz
+REGIME_SCORE_SETS = {"swapped_pairs_zdrop_in_the_old_inert_zone": (2, 12, 32, 0, 16, 1, 64), "e2_zero_zdrop_just_active": (2, 12, 16, 1, 32, 0, 63),
+                     "int8_bound_127": (2, 23, 30, 4, 33, 1, 400), "int8_bound_128": (2, 24, 30, 4, 33, 1, 400), "e_equals_e2": (2, 12, 16, 1, 32, 1, 400),
+                     "skip": (2, 40, 16, 1, 32, 0, 400)}
+SCORE_SETS = [(3, 9, 12, 2, 24, 1, 200), (1, 4, 6, 1, 20, 0, 50), (2, 30, 40, 3, 60, 2, 400)] + list(REGIME_SCORE_SETS.values())
+
+
 def anchors_of(name):
     return synth.make_anchors(**DATASETS[name]["anchors"])
 

@@ -198,6 +198,8 @@ int main(int argc, char **argv)
 	bool bam_text = false;
 	int format_reps = 0;
 	long long pos[3] = {-1, -1, -1}, from[3] = {-1, -1, -1};
+	int score[7] = {0};
+	bool have_score = false;
 	for (int i = 4; i < argc; ++i) {
 		if (!strcmp(argv[i], "--trace")) trace = true;
 		else if (!strcmp(argv[i], "--no-records")) quiet = true;
@@ -216,6 +218,10 @@ int main(int argc, char **argv)
 		else if (!strcmp(argv[i], "--bam-via-text")) bam_text = true;                          // ... through the SAM-line strings and BamWriter::encode instead
 		else if (!strcmp(argv[i], "--stream-pos") && i + 1 < argc) sscanf(argv[++i], "%lld,%lld,%lld", &pos[0], &pos[1], &pos[2]);       // start of this shard in the three draw streams
 		else if (!strcmp(argv[i], "--rebase-from") && i + 1 < argc) sscanf(argv[++i], "%lld,%lld,%lld", &from[0], &from[1], &from[2]);  // run there first, then rebase to --stream-pos
+		else if (!strcmp(argv[i], "--score") && i + 1 < argc) {                                // -M -m -O -E -P -F -z of the CLI, in that order
+			if (sscanf(argv[++i], "%d,%d,%d,%d,%d,%d,%d", &score[0], &score[1], &score[2], &score[3], &score[4], &score[5], &score[6]) != 7) { fprintf(stderr, "--score wants M,m,O,E,P,F,z\n"); return 1; }
+			have_score = true;
+		}
 	}
 	const size_t rl = strlen(argv[2]);
 	const bool from_bam = rl > 4 && !strcmp(argv[2] + rl - 4, ".bam");
@@ -234,6 +240,7 @@ int main(int argc, char **argv)
 	DevIndex ix = hi.view();       // host pointers: the CPU backend's "device" is host memory
 	psvr_aln_params_t par;
 	aln_params_default(&par);
+	if (have_score) par.match = score[0], par.mismatch = score[1], par.gap_open = score[2], par.gap_ex = score[3], par.gap_open2 = score[4], par.gap_ex2 = score[5], par.zdrop = score[6];
 	CpuBE be;
 	EngineCore<CpuBE> core(be);
 	FastqReader rd;

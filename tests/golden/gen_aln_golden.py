@@ -12,7 +12,8 @@ with the reference deBGA (-k 22), run ref_aln --trace, and commit
     tests/golden/<name>/<reads>.bam, <reads>.ori.bam         the same two files as `fc_aln -t 1` writes them by default: BAM, through
                                            htslib's bam_hdr_write / bam_write1 / BGZF (ref_aln --bam), committed as written
 and for the `-Q` sets <reads>.notori.{sam.gz,ori.sam.gz,bam,ori.bam}.  The BGZF blocks depend on the zlib that wrote them; tests compare
-the decompressed streams.  --only-bam writes the .bam files alone (the other fixtures stay as committed).
+the decompressed streams.  --only-bam writes the .bam files alone, --only-scores the SCORE_SETS records alone (the other fixtures
+stay as committed).
 """
 import gzip
 import os
@@ -29,7 +30,7 @@ import datasets  # noqa: E402
 
 REF = os.path.join(ROOT, "oracle", "_ref")
 # non-default scoring options (-M -m -O -E -P -F -z) run through the reference objects as well: (data set, reads, options)
-SCORE_SETS = [("fx2", "reads150", s) for s in ((3, 9, 12, 2, 24, 1, 200), (1, 4, 6, 1, 20, 0, 50), (2, 30, 40, 3, 60, 2, 400))]
+SCORE_SETS = [("fx2", "reads150", s) for s in datasets.SCORE_SETS]
 
 
 # `-Q` / --not-ori (read_realignment.cpp:485: an ORIGINAL primary is not written to the main file): (data set, reads).  fx2 holds
@@ -47,7 +48,7 @@ def ref_bam(idx, work, rname, out_main, out_ori, extra=()):
                     os.path.join(work, "header.sam")], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
 
 
-def main(names, only_not_ori=False, only_bam=False):
+def main(names, only_not_ori=False, only_bam=False, only_scores=False):
     for name in names:
         ds = datasets.DATASETS[name]
         work = os.environ.get("PSVR_GOLDEN_WORK", tempfile.mkdtemp(prefix="psvr_" + name))
@@ -60,7 +61,7 @@ def main(names, only_not_ori=False, only_bam=False):
                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
         out = os.path.join(HERE, name)
         os.makedirs(out, exist_ok=True)
-        if only_not_ori or only_bam:
+        if only_not_ori or only_bam or only_scores:
             pass
         elif ds.get("index") == "sha256":
             # too large to commit: the compact form's SHA-256 per file; tests rebuild the index with `panSVR index` and compare
@@ -72,7 +73,7 @@ def main(names, only_not_ori=False, only_bam=False):
                     f.write("%s  %s\n" % (hashlib.sha256(open(os.path.join(cdir, fn), "rb").read()).hexdigest(), fn))
         else:
             index_fixture.compact(idx, os.path.join(out, "idx"))
-        for rname in ([] if only_not_ori else ds["reads"]):
+        for rname in ([] if only_not_ori or only_scores else ds["reads"]):
             ref_bam(idx, work, rname, os.path.join(out, rname + ".bam"), os.path.join(out, rname + ".ori.bam"))
             if only_bam:
                 continue
@@ -89,7 +90,7 @@ def main(names, only_not_ori=False, only_bam=False):
             put(os.path.join(out, rname + ".ori.sam.gz"), open(ori, "rb").read())
             print(name, rname, len(lines), "pairs", os.path.getsize(sam), "B sam", os.path.getsize(ori), "B ori sam")
         for sname, rname in NOT_ORI_SETS:
-            if sname != name:
+            if sname != name or only_scores:
                 continue
             ref_bam(idx, work, rname, os.path.join(out, rname + ".notori.bam"), os.path.join(out, rname + ".notori.ori.bam"), ["-Q"])
             if only_bam:
@@ -116,5 +117,5 @@ def main(names, only_not_ori=False, only_bam=False):
 
 
 if __name__ == "__main__":
-    argv = [a for a in sys.argv[1:] if a not in ("--only-not-ori", "--only-bam")]      # --only-not-ori: just the -Q files (the other fixtures stay as committed)
-    main(argv or list(datasets.DATASETS), only_not_ori="--only-not-ori" in sys.argv[1:], only_bam="--only-bam" in sys.argv[1:])
+    argv = [a for a in sys.argv[1:] if a not in ("--only-not-ori", "--only-bam", "--only-scores")]      # --only-not-ori: just the -Q files (the other fixtures stay as committed)
+    main(argv or list(datasets.DATASETS), only_not_ori="--only-not-ori" in sys.argv[1:], only_bam="--only-bam" in sys.argv[1:], only_scores="--only-scores" in sys.argv[1:])

@@ -3,7 +3,9 @@
 outputs of the REFERENCE kswlib itself (oracle/_ref/libref_ksw.so, compiled from
 /root/reference/src/kswlib by oracle/Makefile), and tests/golden/ksw_random_kat.json.gz: the same
 library's outputs for the seeded tests/ksw_cases.random_cases() of tests/test_oracle_ksw.py (inputs
-are regenerated from the seed).  Run in the build container only."""
+are regenerated from the seed), and tests/golden/ksw_regime_kat.json.gz: its outputs for a seeded subset of the regime-directed
+sweep of tests/ksw_regimes.py -- the first REGIME_KAT_PER_BATCH problems of every (parameter set, flag, variant) batch and the
+problems of their own (inputs regenerated from the seed as well).  Run in the build container only."""
 import gzip
 import json
 import os
@@ -13,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 from ksw_cases import fixed_cases, random_cases  # noqa: E402
 from ksw_ref import ref_available, run_ref  # noqa: E402
+import ksw_regimes as kr  # noqa: E402
 
 assert ref_available(), "build oracle/_ref first: make -C oracle"
 out = []
@@ -34,3 +37,10 @@ rnd = {"seed": seed, "n": n, "maxlen": maxlen, "extd2": [run_ref(c, "extd2") for
 with gzip.GzipFile(os.path.join(HERE, "ksw_random_kat.json.gz"), "wb", mtime=0) as f:
     f.write(json.dumps(rnd, separators=(",", ":")).encode())
 print("wrote", n, "random cases")
+
+reg = {"seed": kr.SEED, "per_batch": kr.REGIME_KAT_PER_BATCH,
+       "batches": [[run_ref(c, b[3]) for c in kr.batch_cases(b, kr.REGIME_KAT_PER_BATCH)] for b in kr.batches()],
+       "special": [run_ref(c, variant) for _, variant, c in kr.special_cases()]}
+with gzip.GzipFile(os.path.join(HERE, "ksw_regime_kat.json.gz"), "wb", mtime=0) as f:
+    f.write(json.dumps(reg, separators=(",", ":")).encode())
+print("wrote", sum(len(b) for b in reg["batches"]) + len(reg["special"]), "regime cases")

@@ -11,6 +11,7 @@ import pytest
 import aln_common as ac
 import datasets
 from test_emu_aln import CASES, normalise
+from test_oracle_aln import SCORE_SETS
 
 pytestmark = pytest.mark.gpu
 CLI = os.path.join(ac.ROOT, "pansvr_amd", "bin", "panSVR")
@@ -135,11 +136,12 @@ def test_gpu_cli_bam_encoder_routes_match_the_reference(route, extra, env):
     _check_against_bam_goldens(_cli_bam(name, rname, extra, env), name, rname + (".notori" if route == "notori" else ""))
 
 
-@pytest.mark.parametrize("score", [(3, 9, 12, 2, 24, 1, 200), (1, 4, 6, 1, 20, 0, 50), (2, 30, 40, 3, 60, 2, 400)])
+@pytest.mark.parametrize("score", SCORE_SETS)
 def test_gpu_cli_scoring_options_match_reference(score):
     """-M -m -O -E -P -F -z: the engine against what the REFERENCE's objects decided with the same options
     (tests/golden/fx2/reads150.score_*.jsonl.gz, through the reference's own option parser).  The third set leaves the int8-safe
-    regime, so its DP goes through the wavefront kernels instead of the team kernel."""
+    regime, so its DP goes through the wavefront kernels instead of the team kernel; the sets after it sit on the boundaries of the DP's
+    routing predicates (datasets.REGIME_SCORE_SETS)."""
     name, rname = "fx2", "reads150"
     w = ac.workdir(name)
     tmp = tempfile.mkdtemp(prefix="psvr_score_")

@@ -45,6 +45,25 @@ def test_emulated_engine_matches_reference_records(emu, name, rname):
     assert not bad, "%d/%d pairs differ; first %d:\nref: %s\nemu: %s" % (len(bad), len(want), bad[0], want[bad[0]], got[bad[0]])
 
 
+def _score_sets():
+    from test_oracle_aln import SCORE_SETS
+    return SCORE_SETS
+
+
+@pytest.mark.parametrize("score", _score_sets())
+def test_emulated_engine_matches_reference_records_with_scoring_options(emu, score):
+    """-M -m -O -E -P -F -z through the engine's stage functions and orchestration (emu_aln --score): the reference's records for the
+    same options (tests/golden/fx2/reads150.score_*.jsonl.gz)."""
+    w = ac.workdir("fx2")
+    out = subprocess.run([emu, ac.index_dir("fx2"), os.path.join(w, "reads150.fq"), os.path.join(w, "header.sam"), "--trace", "--score", ",".join(str(x) for x in score)],
+                         stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True).stdout.decode()
+    got = [normalise(l) for l in out.split("\n") if l.strip()]
+    want = [normalise(l) for l in ac.golden_lines("fx2", "reads150.score_" + "_".join(str(x) for x in score))]
+    assert len(got) == len(want)
+    bad = [i for i, (a, b) in enumerate(zip(want, got)) if a != b]
+    assert not bad, "%d/%d pairs differ; first %d:\nref: %s\nemu: %s" % (len(bad), len(want), bad[0], want[bad[0]], got[bad[0]])
+
+
 @pytest.mark.parametrize("shrink", [4, 16])
 def test_scratch_arena_growth_reruns_the_batch(emu, shrink):
     """PSVR_ARENA_SHRINK starts the engine with a fraction of its scratch arenas: every arena (MEMs, seeds, pieces, DP descriptors,

@@ -23,7 +23,8 @@ def test_oracle_matches_reference_records(name, rname):
     assert not bad, "%d/%d pairs differ; first %d:\nref: %s\norc: %s" % (len(bad), len(want), bad[0], want[bad[0]], got[bad[0]])
 
 
-SCORE_SETS = [(3, 9, 12, 2, 24, 1, 200), (1, 4, 6, 1, 20, 0, 50), (2, 30, 40, 3, 60, 2, 400)]
+SCORE_SETS, REGIME_SETS = datasets.SCORE_SETS, datasets.REGIME_SCORE_SETS
+ZDROP_SETS = [REGIME_SETS["swapped_pairs_zdrop_in_the_old_inert_zone"], REGIME_SETS["e2_zero_zdrop_just_active"]]
 
 
 def score_tag(score):
@@ -37,6 +38,14 @@ def test_oracle_matches_reference_records_with_scoring_options(score):
     got = ac.run_oracle("fx2", "reads150", trace=True, score=score)
     assert len(got) == len(want) and got == want
     assert want != ac.golden_lines("fx2", "reads150")          # the options really changed the results
+
+
+@pytest.mark.parametrize("score", ZDROP_SETS)
+def test_zdrop_sets_differ_from_the_same_pairs_at_zdrop_400(score):
+    """The two sets that sit at the z-drop rule's edge exercise it only if the rule fires on these reads: the reference's records
+    must differ from the run of the same gap pairs with -z 400 (the oracle's, which the test above holds to the reference)."""
+    want = ac.golden_lines("fx2", "reads150." + score_tag(score))
+    assert want != ac.run_oracle("fx2", "reads150", trace=True, score=score[:6] + (400,))
 
 
 def test_private_rand_matches_libc():
