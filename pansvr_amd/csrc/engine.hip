@@ -1629,7 +1629,7 @@ struct GpuBE {
 			}
 			B.idx = plan_idx.as<int32_t>() + L.first;
 			t0(dp_kind_name(L.kind, 0));
-			dp_launch_kind(L.kind, 0, (unsigned)L.count, L.lds, s2, B, dpP);
+			PSVR_HIP(dp_launch_kind(L.kind, 0, (unsigned)L.count, L.lds, s2, B, dpP));
 			t1();
 			PSVR_HIP(hipGetLastError());
 		}

@@ -11,7 +11,7 @@
 //   * extd2_tiny_kernel     -- same regime, qlen, tlen <= 16: one thread per alignment, state in LDS.
 //   * extd2_reg_kernel<K,PG> -- one 64-lane wavefront per alignment, lane L of chunk c owns target column t = 64c + L, the
 //     per-column state (u,v,x,y,x2,y2,s,H) in VGPRs, (r-1,t-1) neighbours by DPP wave_shr:1 with the inter-chunk carry
-//     through v_readlane, direction bytes in LDS or an HBM slab, exact max / arg-max by DPP reductions.  Its dp_main_loop
+//     through v_readlane, direction bytes in LDS or an HBM slab, exact max / arg-max by DPP reductions.  Its dp_wave_loop
 //     keeps the reference's 16-lane block rounding of [st,en] bit for bit (lanes outside the band but inside the rounded
 //     block are computed and read back exactly as the SSE code does, 8-bit wrap included): needed when the band clips.
 //   * extd2_lds_kernel<VAR>  -- any shape and flag, and the single-affine extz2 variant: state in LDS in the reference's layout.
@@ -115,9 +115,12 @@ __host__ __device__ inline int dp_lds_class_bytes(int cls)
 	const int t[PSVR_DP_NUM_LDS_CLASSES] = {2048, 4096, 6144, 8192, 12288, 16384, 24576, 32768, 49152, 65536, 98304, 131072, PSVR_DP_MAX_LDS};
 	return t[cls];
 }
+// the band width in effect: w < 0 means unbanded (ksw2_extd2_sse.c:83)
+__host__ __device__ inline int dp_band_w(int qlen, int tlen, int w) { return w < 0 ? (qlen > tlen ? qlen : tlen) : w; }
+// 16-byte blocks of one row of direction bytes (:86-87); the row pitch is 16 times this
 __host__ __device__ inline int dp_n_col(int qlen, int tlen, int w_in)
 {
-	int w = w_in < 0 ? (qlen > tlen ? qlen : tlen) : w_in;
+	int w = dp_band_w(qlen, tlen, w_in);
 	int n_col = qlen < tlen ? qlen : tlen;
 	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
 	return n_col;
@@ -161,7 +164,7 @@ __host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_
 	// The size class is the number of strips (1..13), expressed through `need` as that class's byte threshold.
 	// (team_ok = false: a batch too small to fill the chip with 16 alignments per wavefront goes to the wavefront-per-alignment kernels,
 	// whose sweep is qlen + tlen steps instead of strips x (qlen + 15))
-	if (tiny_ok && team_ok && dp_band_never_binds(qlen, tlen, w < 0 ? (qlen > tlen ? qlen : tlen) : w) && tlen <= PSVR_DP_STRIP * PSVR_DP_NUM_LDS_CLASSES) {
+	if (tiny_ok && team_ok && dp_band_never_binds(qlen, tlen, dp_band_w(qlen, tlen, w)) && tlen <= PSVR_DP_STRIP * PSVR_DP_NUM_LDS_CLASSES) {
 		*need = dp_lds_class_bytes((tlen + PSVR_DP_STRIP - 1) / PSVR_DP_STRIP - 1);
 		return PSVR_DP_KIND_STRIP;
 	}
@@ -176,7 +179,7 @@ __host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_
 		// wider than the register-resident kernels' 320 columns: the ring kernels, when the columns an anti-diagonal can touch -- the band,
 		// w + 1 wide at most (and never wider than the shorter sequence), plus the 16-lane rounding at both ends, the stale-score block and
 		// the left neighbour of its first column -- fit their ring.  LDS: the query image and the target.
-		const int wf = w < 0 ? (qlen > tlen ? qlen : tlen) : w, sh = qlen < tlen ? qlen : tlen;
+		const int wf = dp_band_w(qlen, tlen, w), sh = qlen < tlen ? qlen : tlen;
 		const int span = (wf < sh - 1 ? wf : sh - 1) + 33;
 		if (span <= 256) {
 			*need = ((qlen + 16 + 15) & ~15) + ((tlen + 15) & ~15) + 16;
@@ -201,6 +204,24 @@ __host__ __device__ inline long long dp_hbm_img_bytes(int qlen, int tlen, int va
 }
 
 __device__ __forceinline__ int s8(int v) { return (int)(int8_t)v; }
+
+// u / v of the first cell of row / column r: the gap that reaches it along the matrix edge (ksw2_extd2_sse.c:142-156)
+__device__ __forceinline__ int dp_edge_gap(const DpParams &P, int r)
+{
+	return r == 0 ? s8(-P.q - P.e) : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
+}
+// last column that gets a fresh score on a diagonal: score groups of 16 from st0 (:159)
+__device__ __forceinline__ int dp_fresh_end(int st0, int en0) { return st0 + ((en0 - st0) / 16 + 1) * 16 - 1; }
+// The reference's order among cells of one anti-diagonal that tie for the maximum (:322-349): en0 first, then the 4-lane SSE groups
+// [st0, en1) lane by lane, then the scalar tail.  Smaller rank = earlier; t - st0 < 1 << RS.  dp_rank_col is the way back.
+__device__ __forceinline__ int dp_diag_en1(int st0, int en0) { return st0 + (en0 - st0) / 4 * 4; }
+template <int RS>
+__device__ __forceinline__ unsigned dp_diag_rank(int t, int st0, int en0, int en1)
+{
+	return t == en0 ? 0u : t < en1 ? 1u + ((unsigned)((t - st0) & 3) << RS) + (unsigned)(t - st0) : 1u + (4u << RS) + (unsigned)(t - st0);
+}
+template <int RS>
+__device__ __forceinline__ int dp_rank_col(unsigned rk, int st0, int en0) { return rk == 0 ? en0 : st0 + (int)((rk - 1u) & ((1u << RS) - 1u)); }
 
 // mark a value the code knows to be identical in all lanes of the wavefront as uniform (-> SGPR, scalar control flow)
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -279,7 +300,27 @@ struct EzAcc { // running ksw_extz_t (uniform per wave)
 		}
 		return false;
 	}
+	// what the reference does with H at the end of anti-diagonal r (ksw2_extd2_sse.c:352-359): the end scores, the z-drop rule
+	// (true = stop), the global score.  H_st0 / H_en0: H at the band's ends; `e` the extension cost the rule charges (e2; extz2: e)
+	__device__ __forceinline__ bool end_diagonal(int r, int qlen, int tlen, int st0, int en0, int H_st0, int H_en0, int max_H, int max_t, int zdrop, int e)
+	{
+		if (en0 == tlen - 1 && H_en0 > mte) mte = H_en0, mte_q = r - (((en0 + 16) & ~15) - 1);   // r - en
+		if (r - st0 == qlen - 1 && H_st0 > mqe) mqe = H_st0, mqe_t = st0;
+		if (apply_zdrop(max_H, r, max_t, zdrop, e)) return true;
+		if (r == qlen + tlen - 2 && en0 == tlen - 1) score = H_en0;
+		return false;
+	}
 };
+
+// Where the traceback starts (ksw2_extd2_sse.c:382-391); false = no CIGAR.  Sets ez.reach_end, so it is part of the result.
+__device__ __forceinline__ bool trace_start(EzAcc &ez, const DpParams &P, int qlen, int tlen, int &i0, int &j0)
+{
+	i0 = j0 = -1;
+	if (!ez.zdropped && !(P.flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
+	else if (!ez.zdropped && (P.flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
+	else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
+	return i0 >= 0 && j0 >= 0;
+}
 
 // Traceback over direction bytes (ksw_backtrack_D with is_rot=1, min_intron_len=0; ksw2.h:119-151).
 // `P` reads one byte of row r at column offset k; ops are staged through `emit(k, word)`.

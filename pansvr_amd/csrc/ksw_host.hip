@@ -273,7 +273,7 @@ extern "C" int psvr_dp_plan_launch(psvr_dp_plan_t *pl, const uint8_t *d_qseq, co
 	for (const Launch &L : pl->launches) {
 		if (L.kind == PSVR_DP_KIND_STRIP) { team.add(dp_class_of(L.lds_bytes) + 1, L.first, L.count, L.qmax); continue; }
 		B.idx = pl->d_idx.as<int32_t>() + L.first;
-		dp_launch_kind(L.kind, pl->variant, (unsigned)L.count, L.lds_bytes, stream, B, pl->P);
+		PSVR_HIP(dp_launch_kind(L.kind, pl->variant, (unsigned)L.count, L.lds_bytes, stream, B, pl->P));
 		PSVR_HIP(hipGetLastError());
 	}
 	B.idx = pl->d_idx.as<int32_t>();

@@ -1,10 +1,15 @@
 // ksw_kernels.hip -- K4 `extd2_dp`: the banded dual-affine anti-diagonal DP on gfx950.
-// See ksw_device.h for the design.  Two kernels:
-//   extd2_reg_kernel<K>  : fast path. tlen rounded to 16 fits 64*K columns (K<=5, i.e. tlen<=320),
-//                          DP state in VGPRs, direction bytes in LDS, traceback from LDS.
-//   extd2_lds_kernel     : general path (any shape the C ABI accepts, all KSW_EZ flags, and the
-//                          single-affine extz2 variant): DP state in LDS, direction bytes in a
-//                          global scratch slab.
+// See ksw_device.h for the design and for what the kernel families share (edge values, tie rank, end-of-diagonal rules, where the
+// traceback starts, the traceback itself).  In this file, in order:
+//   extd2_reg_kernel<K,PG>, extd2_ring_kernel<K>, extd2_ring1_kernel<K>
+//                          : a wavefront per alignment, DP state in VGPRs (dp_wave_loop, dp_lean_loop), direction bytes in LDS or
+//                            the HBM slab.  reg: tlen rounded to 16 fits 64 K columns (K <= 5); ring: the band does.
+//   extd2_tiny_kernel      : qlen, tlen <= 16, a thread per alignment.
+//   extd2_team_kernel, extd2_team_finish_kernel
+//                          : the lean regime at any size, a team of lanes per alignment; rules and traceback in a second launch.
+//   extd2_lds_kernel<VAR>, extd2_hbm_kernel<VAR>
+//                          : general path (any shape the C ABI accepts, all KSW_EZ flags, and the single-affine extz2 variant): the
+//                            reference's flat image in LDS or HBM, one recurrence (gen_*) for both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ksw_device.h"
@@ -23,151 +28,50 @@ __device__ __forceinline__ void write_ez(psvr_extz_t *o, const EzAcc &a, int n_c
 // ------------------------------------------------------------------------------------------
 // fast path
 // ------------------------------------------------------------------------------------------
-// the anti-diagonal sweep.  WRAP = emulate the 8-bit wrap-around of every SSE add/sub (needed whenever an in-band cell can
-// read a lane outside the band); without it the arithmetic stays in 32 bits, which is value-identical when wrap cannot be
-// observed (see extd2_reg_kernel).
-template <int K, bool WRAP>
-__device__ __forceinline__ void dp_main_loop(const DpParams &P, const uint8_t *target, int lane, int qlen, int tlen, int w, int rowb, int n_rows,
-                                             const uint8_t *QR, uint8_t *Pm, EzAcc &ez)
-{
-#define W8(e) (WRAP ? s8(e) : (int)(e))
-	const int neg_qe = s8(-P.q - P.e), neg_qe2 = s8(-P.q2 - P.e2);
-	const int qe8 = s8(P.q + P.e), qe28 = s8(P.q2 + P.e2);
-	int u[K], v[K], x[K], y[K], x2[K], y2[K], s[K], H[K], tb[K];
-#pragma unroll
-	for (int c = 0; c < K; ++c) {
-		int t = c * 64 + lane;
-		u[c] = v[c] = x[c] = y[c] = neg_qe;
-		x2[c] = y2[c] = neg_qe2;
-		s[c] = 0;
-		H[c] = PSVR_KSW_NEG_INF;
-		tb[c] = t < tlen ? target[t] : 0;
-	}
-	__builtin_amdgcn_wave_barrier();      // the query image was written by this wave's own lanes (LDS is in-order per wave)
-
-	int last_st = -1;
-	const int with_cigar = !(P.flag & PSVR_EZ_SCORE_ONLY);
-	for (int r = 0; r < n_rows; ++r) {
-		int st0, en0, st, en;
-		if (!band_limits(r, qlen, tlen, w, st0, en0, st, en)) { ez.zdropped = 1; break; }
-		const bool adv = st > 0 && st > last_st;   // (r-1,st-1) was computed last round (:143)
-		const int ur = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-		const int fresh_end = st0 + ((en0 - st0) / 16 + 1) * 16 - 1;  // score groups of 16 from st0 (:159)
-		const int qbase = qlen - 1 - r;
-		const int c_first = st >> 6, c_last = en >> 6;
-		const int en1 = st0 + (en0 - st0) / 4 * 4;
-		int h_prev = 0;                                  // H[en0-1] of the previous diagonal (:322)
-		if (en0 > 0) {
-#pragma unroll
-			for (int c = 0; c < K; ++c)
-				if (((en0 - 1) >> 6) == c) h_prev = __builtin_amdgcn_readlane(H[c], (en0 - 1) & 63);
-		}
-		int bh = (int)0x80000000; unsigned bk = 0xffffffffu;
-		uint8_t *prow = Pm + r * rowb - st;
-#pragma unroll
-		for (int c = K - 1; c >= 0; --c) {
-			if (c < c_first || c > c_last) continue;
-			const int t = c * 64 + lane;
-			// branch-free: every lane computes, the state of lanes outside [st,en] is kept by selects (v_cndmask)
-			const bool act = (t >= st) & (t <= en);
-			const bool ovr = (en >= r) & (t == r);                                  // (:153-156); lane r is always inside [st,en]
-			const int yy = ovr ? neg_qe : y[c], yy2 = ovr ? neg_qe2 : y2[c], ut = ovr ? ur : u[c];
-			int cx = 0, cv = 0, cx2 = 0;
-			if (c > 0) {
-				cx = __builtin_amdgcn_readlane(x[c - 1], 63);
-				cv = __builtin_amdgcn_readlane(v[c - 1], 63);
-				cx2 = __builtin_amdgcn_readlane(x2[c - 1], 63);
-			}
-			int xt1 = dpp_wave_shr1(x[c], cx), vt1 = dpp_wave_shr1(v[c], cv), x2t1 = dpp_wave_shr1(x2[c], cx2);
-			const bool bnd = (t == st) & !adv;                                       // (:142-152)
-			xt1 = bnd ? neg_qe : xt1, x2t1 = bnd ? neg_qe2 : x2t1, vt1 = bnd ? (st > 0 ? neg_qe : ur) : vt1;
-			const bool fresh = (t >= st0) & (t <= fresh_end);                          // fresh score (:158-173)
-			const int qb = QR[fresh ? qbase + t : 0];
-			int sc = tb[c] == qb ? P.sc_mch : P.sc_mis;
-			sc = ((tb[c] == P.m1) | (qb == P.m1)) ? P.sc_N : sc;
-			const int sv = fresh ? sc : s[c];
-			s[c] = sv;
-			int z = sv;
-			int a = W8(xt1 + vt1), b = W8(yy + ut), a2 = W8(x2t1 + vt1), b2 = W8(yy2 + ut);
-			int d = a > z ? 1 : 0;   z = max(z, a);
-			d = b > z ? 2 : d;       z = max(z, b);
-			d = a2 > z ? 3 : d;      z = max(z, a2);
-			d = b2 > z ? 4 : d;      z = max(z, b2);
-			z = min(z, P.sc_mch);
-			const int un = W8(z - vt1), vn = W8(z - ut);
-			int tmp = W8(z - P.q);
-			a = W8(a - tmp), b = W8(b - tmp);
-			tmp = W8(z - P.q2);
-			a2 = W8(a2 - tmp), b2 = W8(b2 - tmp);
-			d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > 0 ? 0x20 : 0) | (b2 > 0 ? 0x40 : 0);
-			u[c] = act ? un : u[c], v[c] = act ? vn : v[c];
-			x[c] = act ? W8(max(a, 0) - qe8) : x[c];
-			y[c] = act ? W8(max(b, 0) - qe8) : y[c];
-			x2[c] = act ? W8(max(a2, 0) - qe28) : x2[c];
-			y2[c] = act ? W8(max(b2, 0) - qe28) : y2[c];
-			if (act & (with_cigar != 0)) prow[t] = (uint8_t)d;
-			// exact H tracking (:316-351)
-			const int hold = H[c];
-			int hn = (t == en0) ? (en0 > 0 ? h_prev + un : hold + vn) : (((t >= st0) & (t < en0)) ? hold + vn : hold);
-			hn = r == 0 ? (t == 0 ? vn - P.qe_pre : hold) : hn;
-			hn = act ? hn : hold;
-			H[c] = hn;
-			const bool valid = (t >= st0) & (t <= en0);
-			const unsigned rank = t == en0 ? 0u : (t < en1 ? 1u + (unsigned)((t - st0) & 3) * 4096u + (unsigned)(t - st0)
-			                                                : 1u + 4u * 4096u + (unsigned)(t - st0));
-			const bool better = valid & ((hn > bh) | ((hn == bh) & (rank < bk)));
-			bh = better ? hn : bh, bk = better ? rank : bk;
-		}
-		const int max_H = wave_max_i32(bh);
-		// arg-max with the reference's tie order: usually one lane holds the maximum, then its rank is a single v_readlane
-		const unsigned long long top = __ballot(bh == max_H);
-		unsigned rk;
-		if (__popcll(top) == 1) rk = (unsigned)__builtin_amdgcn_readlane((int)bk, __ffsll((unsigned long long)top) - 1);
-		else rk = wave_min_u32(bh == max_H ? bk : 0xffffffffu);
-		const int max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & 4095u);
-		int H_en0 = 0, H_st0 = 0;
-#pragma unroll
-		for (int c = 0; c < K; ++c) {
-			if ((en0 >> 6) == c) H_en0 = __builtin_amdgcn_readlane(H[c], en0 & 63);
-			if ((st0 >> 6) == c) H_st0 = __builtin_amdgcn_readlane(H[c], st0 & 63);
-		}
-		if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - en;
-		if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
-		if (ez.apply_zdrop(max_H, r, max_t, P.zdrop, P.e2)) break;
-		if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H_en0;
-		last_st = st;
-	}
-#undef W8
-}
-
-// The same sweep for matrices wider than 64 K columns whose BAND fits 64 K columns (`fc_sv`'s contig re-alignment: q/t up to 3100 at
+// The anti-diagonal sweep, the 8-bit wrap-around of every SSE add/sub emulated (an in-band cell can read a lane outside the band; where
+// it cannot, dp_lean_loop takes over).  Lane L of chunk c holds one target column's state; (r-1,t-1) is the lane to the left, lane 0 of
+// chunk c receiving lane 63 of chunk c-1.
+//
+// RING: the same sweep for matrices wider than 64 K columns whose BAND fits 64 K columns (`fc_sv`'s contig re-alignment: q/t up to 3100 at
 // w = 132, SignalAssembly.hpp:418-420,463; reads beyond 320 bases on the `aln` path at its fixed w = 200): the lanes hold a RING of
 // R = 64 K columns -- column t lives in slot t mod R (chunk (t mod R) / 64, lane t mod 64) -- that slides along the matrix with the band.
 // The reference's per-column arrays (u, v, x, y, x2, y2, s, H) are only ever touched inside [st, max(en, fresh_end)] of the current
 // anti-diagonal (ksw2_extd2_sse.c:125-140,158-173), that interval moves right monotonically and is at most w + 32 columns wide, so a
 // column that has fallen out of it on the left is dead and its slot is given to column t + R -- with the arrays' initial values
-// (:100-121) -- when that one comes into reach on the right.  The neighbour (r-1, t-1) is the lane to the left as before, lane 0 of
-// chunk c receiving lane 63 of chunk c-1 and chunk 0 that of chunk K-1 (read before any chunk is updated).  Everything else -- the
-// 16-lane block rounding, the stale-score lanes, the 8-bit wrap of every add/sub -- is dp_main_loop's, cell for cell.
-template <int K>
-__device__ __forceinline__ void dp_ring_loop(const DpParams &P, const uint8_t *target, int lane, int qlen, int tlen, int w, int rowb, int n_rows,
+// (:100-121) -- when that one comes into reach on the right.  Chunk 0's left neighbour is then lane 63 of chunk K-1.  Everything else --
+// the 16-lane block rounding, the stale-score lanes, the 8-bit wrap -- is the same code, cell for cell.
+// a slot takes column t: the arrays' initial values (:100-121) and the column's target base
+// (a plain function over the slot's registers: a lambda that captures the arrays costs the sweep ~15 scalar instructions per chunk)
+__device__ __forceinline__ void wave_slot_take(int t, int tlen, const uint8_t *target, int neg_qe, int neg_qe2,
+                                               int &u, int &v, int &x, int &y, int &x2, int &y2, int &s, int &H, int &tb)
+{
+	u = v = x = y = neg_qe, x2 = y2 = neg_qe2, s = 0, H = PSVR_KSW_NEG_INF;
+	tb = t < tlen ? target[t] : 0;
+}
+template <int K, bool RING>
+__device__ __forceinline__ void dp_wave_loop(const DpParams &P, const uint8_t *target, int lane, int qlen, int tlen, int w, int rowb, int n_rows,
                                              const uint8_t *QR, uint8_t *Pm, EzAcc &ez)
 {
 	constexpr int R = 64 * K;
+	constexpr int RS = 12;                          // rank shift: a diagonal of these kernels spans fewer than 4096 columns
 	const int neg_qe = s8(-P.q - P.e), neg_qe2 = s8(-P.q2 - P.e2);
 	const int qe8 = s8(P.q + P.e), qe28 = s8(P.q2 + P.e2);
-	int u[K], v[K], x[K], y[K], x2[K], y2[K], s[K], H[K], tb[K], tc[K];
+	int u[K], v[K], x[K], y[K], x2[K], y2[K], s[K], H[K], tb[K], tc[K];   // tc: the slot's column (fixed unless RING)
+	auto slot_of = [](int t) { return RING ? t % R : t; };
+	auto H_at = [&](int t) {                        // H of column t, wave-uniform
+		const int j = slot_of(t);
+		int h = 0;
+#pragma unroll
+		for (int c = 0; c < K; ++c)
+			if ((j >> 6) == c) h = __builtin_amdgcn_readlane(H[c], j & 63);
+		return h;
+	};
 #pragma unroll
 	for (int c = 0; c < K; ++c) {
-		const int t = c * 64 + lane;
-		tc[c] = t;
-		u[c] = v[c] = x[c] = y[c] = neg_qe;
-		x2[c] = y2[c] = neg_qe2;
-		s[c] = 0;
-		H[c] = PSVR_KSW_NEG_INF;
-		tb[c] = t < tlen ? target[t] : 0;
+		tc[c] = c * 64 + lane;
+		wave_slot_take(tc[c], tlen, target, neg_qe, neg_qe2, u[c], v[c], x[c], y[c], x2[c], y2[c], s[c], H[c], tb[c]);
 	}
-	__builtin_amdgcn_wave_barrier();      // the query / target images were written by this wave's own lanes (LDS is in-order per wave)
+	__builtin_amdgcn_wave_barrier();      // the query (RING: and target) image was written by this wave's own lanes (LDS is in-order per wave)
 
 	int last_st = -1;
 	const int with_cigar = !(P.flag & PSVR_EZ_SCORE_ONLY);
@@ -175,50 +79,47 @@ __device__ __forceinline__ void dp_ring_loop(const DpParams &P, const uint8_t *t
 		int st0, en0, st, en;
 		if (!band_limits(r, qlen, tlen, w, st0, en0, st, en)) { ez.zdropped = 1; break; }
 		const bool adv = st > 0 && st > last_st;   // (r-1,st-1) was computed last round (:143)
-		const int ur = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-		const int fresh_end = st0 + ((en0 - st0) / 16 + 1) * 16 - 1;  // score groups of 16 from st0 (:159)
+		const int ur = dp_edge_gap(P, r);
+		const int fresh_end = dp_fresh_end(st0, en0);
 		const int qbase = qlen - 1 - r;
-		const int en1 = st0 + (en0 - st0) / 4 * 4;
-		const int reach = en > fresh_end ? en : fresh_end;
-		// a slot whose next column has come into reach starts over with the arrays' initial values (:100-121) -- before its neighbour to the
-		// right, which may enter the band on this very diagonal (en moves 16 columns at a time), looks at it.  Its old column lies left of
-		// st - 1 (the interval [st - 1, reach] is at most w + 33 <= R columns wide), so nobody reads that one again.
-#pragma unroll
-		for (int c = 0; c < K; ++c) {
-			if (tc[c] + R <= reach) {
-				tc[c] += R;
-				u[c] = v[c] = x[c] = y[c] = neg_qe;
-				x2[c] = y2[c] = neg_qe2;
-				s[c] = 0;
-				H[c] = PSVR_KSW_NEG_INF;
-				tb[c] = tc[c] < tlen ? target[tc[c]] : 0;
-			}
-		}
-		// the neighbours' values of the previous diagonal that cross a chunk boundary, and H[en0-1] (:322), before anything is updated
-		int cx[K], cv[K], cx2[K];
-#pragma unroll
-		for (int c = 0; c < K; ++c) {
-			const int src = (c + K - 1) % K;
-			cx[c] = __builtin_amdgcn_readlane(x[src], 63);
-			cv[c] = __builtin_amdgcn_readlane(v[src], 63);
-			cx2[c] = __builtin_amdgcn_readlane(x2[src], 63);
-		}
-		int h_prev = 0;
-		if (en0 > 0) {
-			const int j = (en0 - 1) % R;
+		const int c_first = st >> 6, c_last = en >> 6;
+		const int en1 = dp_diag_en1(st0, en0);
+		int wx = 0, wv = 0, wx2 = 0;
+		if constexpr (RING) {
+			// a slot whose next column has come into reach starts over with that column -- before its neighbour to the
+			// right, which may enter the band on this very diagonal (en moves 16 columns at a time), looks at it.  Its old column lies left of
+			// st - 1 (the interval [st - 1, reach] is at most w + 33 <= R columns wide), so nobody reads that one again.
+			const int reach = en > fresh_end ? en : fresh_end;
 #pragma unroll
 			for (int c = 0; c < K; ++c)
-				if ((j >> 6) == c) h_prev = __builtin_amdgcn_readlane(H[c], j & 63);
+				if (tc[c] + R <= reach) {
+					tc[c] += R;
+					wave_slot_take(tc[c], tlen, target, neg_qe, neg_qe2, u[c], v[c], x[c], y[c], x2[c], y2[c], s[c], H[c], tb[c]);
+				}
+			// what wraps round the ring: chunk K-1's lane 63 of the previous diagonal, read before that chunk is updated
+			wx = __builtin_amdgcn_readlane(x[K - 1], 63);
+			wv = __builtin_amdgcn_readlane(v[K - 1], 63);
+			wx2 = __builtin_amdgcn_readlane(x2[K - 1], 63);
 		}
+		const int h_prev = en0 > 0 ? H_at(en0 - 1) : 0;   // H[en0-1] of the previous diagonal (:322)
 		int bh = (int)0x80000000; unsigned bk = 0xffffffffu;
-		uint8_t *prow = Pm + (size_t)r * rowb - st;
+		uint8_t *prow = Pm + r * rowb - st;
+		// chunks from high to low: chunk c - 1's lane 63 is read just before chunk c is updated, chunk c - 1 itself after that
 #pragma unroll
-		for (int c = 0; c < K; ++c) {
+		for (int c = K - 1; c >= 0; --c) {
+			if (!RING && (c < c_first || c > c_last)) continue;   // (a ring's slots are in no order)
 			const int t = tc[c];
+			// branch-free: every lane computes, the state of lanes outside [st,en] is kept by selects (v_cndmask)
 			const bool act = (t >= st) & (t <= en);
 			const bool ovr = (en >= r) & (t == r);                                  // (:153-156); lane r is always inside [st,en]
 			const int yy = ovr ? neg_qe : y[c], yy2 = ovr ? neg_qe2 : y2[c], ut = ovr ? ur : u[c];
-			int xt1 = dpp_wave_shr1(x[c], cx[c]), vt1 = dpp_wave_shr1(v[c], cv[c]), x2t1 = dpp_wave_shr1(x2[c], cx2[c]);   // (r-1,t-1)
+			int cx = wx, cv = wv, cx2 = wx2;
+			if (c > 0) {
+				cx = __builtin_amdgcn_readlane(x[c - 1], 63);
+				cv = __builtin_amdgcn_readlane(v[c - 1], 63);
+				cx2 = __builtin_amdgcn_readlane(x2[c - 1], 63);
+			}
+			int xt1 = dpp_wave_shr1(x[c], cx), vt1 = dpp_wave_shr1(v[c], cv), x2t1 = dpp_wave_shr1(x2[c], cx2);   // (r-1,t-1)
 			const bool bnd = (t == st) & !adv;                                       // (:142-152)
 			xt1 = bnd ? neg_qe : xt1, x2t1 = bnd ? neg_qe2 : x2t1, vt1 = bnd ? (st > 0 ? neg_qe : ur) : vt1;
 			const bool fresh = (t >= st0) & (t <= fresh_end);                          // fresh score (:158-173)
@@ -253,36 +154,24 @@ __device__ __forceinline__ void dp_ring_loop(const DpParams &P, const uint8_t *t
 			hn = act ? hn : hold;
 			H[c] = hn;
 			const bool valid = (t >= st0) & (t <= en0);
-			const unsigned rank = t == en0 ? 0u : (t < en1 ? 1u + (unsigned)((t - st0) & 3) * 4096u + (unsigned)(t - st0)
-			                                                : 1u + 4u * 4096u + (unsigned)(t - st0));
+			const unsigned rank = dp_diag_rank<RS>(t, st0, en0, en1);
 			const bool better = valid & ((hn > bh) | ((hn == bh) & (rank < bk)));
 			bh = better ? hn : bh, bk = better ? rank : bk;
 		}
 		const int max_H = wave_max_i32(bh);
+		// arg-max with the reference's tie order: usually one lane holds the maximum, then its rank is a single v_readlane
 		const unsigned long long top = __ballot(bh == max_H);
 		unsigned rk;
 		if (__popcll(top) == 1) rk = (unsigned)__builtin_amdgcn_readlane((int)bk, __ffsll((unsigned long long)top) - 1);
 		else rk = wave_min_u32(bh == max_H ? bk : 0xffffffffu);
-		const int max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & 4095u);
-		int H_en0 = 0, H_st0 = 0;
-		{
-			const int je = en0 % R, js = st0 % R;
-#pragma unroll
-			for (int c = 0; c < K; ++c) {
-				if ((je >> 6) == c) H_en0 = __builtin_amdgcn_readlane(H[c], je & 63);
-				if ((js >> 6) == c) H_st0 = __builtin_amdgcn_readlane(H[c], js & 63);
-			}
-		}
-		if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - en;
-		if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
-		if (ez.apply_zdrop(max_H, r, max_t, P.zdrop, P.e2)) break;
-		if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H_en0;
+		const int max_t = dp_rank_col<RS>(rk, st0, en0);
+		if (ez.end_diagonal(r, qlen, tlen, st0, en0, H_at(st0), H_at(en0), max_H, max_t, P.zdrop, P.e2)) break;
 		last_st = st;
 	}
 }
 
 // The sweep for problems whose band never clips the matrix and whose in-band values fit int8 (P.nowrap_ok &&
-// dp_band_never_binds): the common case on the `aln` path (qlen <= 200, tlen <= 201).  Same results as dp_main_loop, far
+// dp_band_never_binds): the common case on the `aln` path (qlen <= 200, tlen <= 201).  Same results as dp_wave_loop, far
 // fewer instructions per anti-diagonal:
 //   * an in-band cell only ever reads in-band cells of the previous diagonal or one of the explicit boundary values
 //     (:142-156): the 16-lane block rounding, the stale-score lanes and the 8-bit wrap are not modelled at all, and lanes
@@ -305,7 +194,7 @@ __device__ __forceinline__ void dp_lean_loop(const DpParams &P, const uint8_t *t
 		v[c] = x[c] = y[c] = neg_qe;
 		x2[c] = y2[c] = neg_qe2;
 		// lanes keep these values until their column enters the band at r == t: u/y/y2 of the first cell of column t (:153-156)
-		u[c] = t == 0 ? neg_qe : t < P.long_thres ? s8(-P.e) : t == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
+		u[c] = dp_edge_gap(P, t);
 		H[c] = -P.qe_pre;                 // H[0] = v - qe on the first diagonal (:351); every other lane is set before it is read
 		const int tc = t < tlen ? target[t] : 0;
 		tb[c] = tc == P.m1 ? 0x100 : tc;  // an N never equals a query code
@@ -316,8 +205,7 @@ __device__ __forceinline__ void dp_lean_loop(const DpParams &P, const uint8_t *t
 	int e_score = PSVR_KSW_NEG_INF, e_zd = 0, last_H = PSVR_KSW_NEG_INF;
 	for (int r = 0; r < n_rows; ++r) {
 		const int st0 = max(0, r - qlen + 1), en0 = min(tlen - 1, r);
-		int ur = s8(-P.e2);                // v of column -1 (:142-152); only the first long_thres + 1 diagonals differ
-		if (r <= P.long_thres) ur = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : s8(P.long_diff);
+		const int ur = dp_edge_gap(P, r);  // v of column -1 (:142-152)
 		const int c_first = st0 >> 6, c_last = en0 >> 6;
 		const int qbase = qlen - 1 - r;
 		const unsigned prow = (unsigned)(r * rowb - (st0 & ~15));
@@ -385,17 +273,12 @@ __device__ __forceinline__ void dp_lean_loop(const DpParams &P, const uint8_t *t
 			if (top[c]) max_t = c * 64 + __ffsll((unsigned long long)top[c]) - 1;
 		}
 		if (n_top != 1) {                                  // the reference's order among equal lanes (:322-349)
-			const int en1 = st0 + (en0 - st0) / 4 * 4;
+			const int en1 = dp_diag_en1(st0, en0);
 			unsigned bk = 0xffffffffu;
 #pragma unroll
-			for (int c = 0; c < K; ++c) {
-				const int t = c * 64 + lane;
-				const unsigned rank = t == en0 ? 0u : (t < en1 ? 1u + (unsigned)((t - st0) & 3) * 4096u + (unsigned)(t - st0)
-				                                                : 1u + 4u * 4096u + (unsigned)(t - st0));
-				if ((top[c] >> lane) & 1) bk = min(bk, rank);
-			}
-			const unsigned rk = wave_min_u32(bk);
-			max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & 4095u);
+			for (int c = 0; c < K; ++c)
+				if ((top[c] >> lane) & 1) bk = min(bk, dp_diag_rank<12>(c * 64 + lane, st0, en0, en1));
+			max_t = dp_rank_col<12>(wave_min_u32(bk), st0, en0);
 		}
 		if (en0 == tlen - 1) {
 			int H_en0 = 0;
@@ -429,7 +312,7 @@ __device__ __forceinline__ void dp_lean_loop(const DpParams &P, const uint8_t *t
 
 // kDpWaves independent alignments per workgroup (one per wavefront, no inter-wave communication): single-wave workgroups
 // run into the workgroups-per-CU limit long before the wave slots are full
-// RING: the matrix is wider than 64 K columns but its band is not (dp_ring_loop); the target is staged in LDS behind the query image
+// RING: the matrix is wider than 64 K columns but its band is not (dp_wave_loop<K, true>); the target is staged in LDS behind the query image
 // (a slot that is handed on fetches its new column's base from there), the direction bytes are in the HBM slab (PG)
 // NW: wavefronts per workgroup (extd2_ring1_kernel: 1, so that a long problem's query + target image may take all 160 KiB)
 template <int K, bool PG, bool RING, int NW = kDpWaves>
@@ -453,10 +336,8 @@ __device__ __forceinline__ void extd2_wave_body(const DpBatch &B, const DpParams
 		return;
 	}
 	const uint8_t *query = B.qseq + uni64(B.q_off[pid]), *target = B.tseq + uni64(B.t_off[pid]);
-	const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
-	int n_col = qlen < tlen ? qlen : tlen;
-	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
-	const int rowb = n_col * 16;
+	const int w = dp_band_w(qlen, tlen, P.w);
+	const int rowb = uni(dp_n_col(qlen, tlen, P.w) * 16);   // (said to be uniform: what is derived from it, the staging pointer below, stays in scalar registers)
 	const int n_rows = qlen + tlen - 1;
 	const int qimg = (qlen + 16 + 15) & ~15;
 	uint8_t *QR = lds;                 // reversed query + >=16 zero bytes (the calloc'ed tail of `qr`, :100,121)
@@ -467,23 +348,20 @@ __device__ __forceinline__ void extd2_wave_body(const DpBatch &B, const DpParams
 	if (RING) {
 		uint8_t *TG = lds + qimg;
 		for (int i = lane; i < tlen; i += 64) TG[i] = target[i];
-		dp_ring_loop<K>(P, TG, lane, qlen, tlen, w, rowb, n_rows, QR, Pm, ez);
+		dp_wave_loop<K, true>(P, TG, lane, qlen, tlen, w, rowb, n_rows, QR, Pm, ez);
 	}
 	// 8-bit wrap-around only has to be emulated when it can be observed: if the band never clips the matrix, in-band cells
 	// never read a lane outside the band (dp_band_never_binds) and all in-band values fit int8 for these scoring parameters
 	// (P.nowrap_ok, make_dp_params), so the sign-extension after every add/sub is dropped
 	else if (P.nowrap_ok && dp_band_never_binds(qlen, tlen, w)) dp_lean_loop<K>(P, target, lane, qlen, tlen, rowb, n_rows, QR, Pm, ez);
-	else dp_main_loop<K, true>(P, target, lane, qlen, tlen, w, rowb, n_rows, QR, Pm, ez);
+	else dp_wave_loop<K, false>(P, target, lane, qlen, tlen, w, rowb, n_rows, QR, Pm, ez);
 	const int with_cigar = !(P.flag & PSVR_EZ_SCORE_ONLY);
 	int n_cigar = 0;
 	if (with_cigar) {
 		if (PG) __threadfence_block();
 		__builtin_amdgcn_wave_barrier();
-		int i0 = -1, j0 = -1;
-		if (!ez.zdropped && !(P.flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
-		else if (!ez.zdropped && (P.flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
-		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
-		if (i0 >= 0 && j0 >= 0) {
+		int i0, j0;
+		if (trace_start(ez, P, qlen, tlen, i0, j0)) {
 			// ops are staged in the already-consumed tail of the direction-byte area (rows > r are dead)
 			uint32_t *stage_end = (uint32_t*)(Pm + p_end);
 			n_cigar = traceback(i0, j0, qlen, tlen, w,
@@ -514,9 +392,6 @@ template __global__ void extd2_ring1_kernel<4>(DpBatch, DpParams);
 
 template __global__ void extd2_reg_kernel<1, false>(DpBatch, DpParams);
 template __global__ void extd2_reg_kernel<2, false>(DpBatch, DpParams);
-template __global__ void extd2_reg_kernel<3, false>(DpBatch, DpParams);
-template __global__ void extd2_reg_kernel<4, false>(DpBatch, DpParams);
-template __global__ void extd2_reg_kernel<5, false>(DpBatch, DpParams);
 template __global__ void extd2_reg_kernel<1, true>(DpBatch, DpParams);
 template __global__ void extd2_reg_kernel<2, true>(DpBatch, DpParams);
 template __global__ void extd2_reg_kernel<3, true>(DpBatch, DpParams);
@@ -556,17 +431,16 @@ __global__ __launch_bounds__(64) void extd2_tiny_kernel(DpBatch B, DpParams P, i
 	const int with_cigar = !(P.flag & PSVR_EZ_SCORE_ONLY);
 	auto pack0 = [](int u, int v, int x, int y) { return (uint32_t)(u & 0xff) | (uint32_t)(v & 0xff) << 8 | (uint32_t)(x & 0xff) << 16 | (uint32_t)(y & 0xff) << 24; };
 	auto pack1 = [](int x2, int y2, int h) { return (uint32_t)(x2 & 0xff) | (uint32_t)(y2 & 0xff) << 8 | (uint32_t)(h & 0xffff) << 16; };
-	auto ur_of = [&](int r) { return r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2); };
 	for (int t = 0; t < tlen; ++t) {
-		W0[t * 64] = pack0(ur_of(t), neg_qe, neg_qe, neg_qe);                // u/y/y2 of the first cell of column t (:153-156)
+		W0[t * 64] = pack0(dp_edge_gap(P, t), neg_qe, neg_qe, neg_qe);                // u/y/y2 of the first cell of column t (:153-156)
 		W1[t * 64] = pack1(neg_qe2, neg_qe2, -P.qe_pre);
 	}
 	const int n_rows = qlen + tlen - 1;
 	for (int r = 0; r < n_rows; ++r) {
 		const int st0 = max(0, r - qlen + 1), en0 = min(tlen - 1, r);
-		const int en1 = st0 + (en0 - st0) / 4 * 4;
+		const int en1 = dp_diag_en1(st0, en0);
 		// (r-1, st0-1): the boundary column -1 (:142-152) or the old state of the slot left of the band
-		int x1 = neg_qe, v1 = ur_of(r), x21 = neg_qe2, h1 = 0;
+		int x1 = neg_qe, v1 = dp_edge_gap(P, r), x21 = neg_qe2, h1 = 0;
 		if (st0 > 0) {
 			const uint32_t a = W0[(st0 - 1) * 64], b = W1[(st0 - 1) * 64];
 			v1 = s8(a >> 8), x1 = s8(a >> 16), x21 = s8(b), h1 = (int)(int16_t)(b >> 16);
@@ -600,24 +474,17 @@ __global__ __launch_bounds__(64) void extd2_tiny_kernel(DpBatch B, DpParams P, i
 			if (with_cigar) PD[(r * 16 + t) * 64] = (uint8_t)d;
 			if (t == en0) H_en0 = hn;
 			if (t == st0) H_st0 = hn;
-			const unsigned rank = t == en0 ? 0u : (t < en1 ? 1u + (unsigned)((t - st0) & 3) * 4096u + (unsigned)(t - st0)
-			                                                : 1u + 4u * 4096u + (unsigned)(t - st0));
+			const unsigned rank = dp_diag_rank<12>(t, st0, en0, en1);
 			if (hn > bh || (hn == bh && rank < bk)) bh = hn, bk = rank;          // the reference's order among equal cells (:322-349)
 		}
-		const int max_t = bk == 0 ? en0 : st0 + (int)((bk - 1u) & 4095u);
-		if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - (((en0 + 16) & ~15) - 1);
-		if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
-		if (ez.apply_zdrop(bh, r, max_t, P.zdrop, P.e2)) break;
-		if (r == n_rows - 1 && en0 == tlen - 1) ez.score = H_en0;
+		const int max_t = dp_rank_col<12>(bk, st0, en0);
+		if (ez.end_diagonal(r, qlen, tlen, st0, en0, H_st0, H_en0, bh, max_t, P.zdrop, P.e2)) break;
 	}
 	int n_cigar = 0;
 	if (with_cigar) {
-		int i0 = -1, j0 = -1;
-		if (!ez.zdropped && !(P.flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
-		else if (!ez.zdropped && (P.flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
-		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
-		if (i0 >= 0 && j0 >= 0) {
-			const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
+		int i0, j0;
+		if (trace_start(ez, P, qlen, tlen, i0, j0)) {
+			const int w = dp_band_w(qlen, tlen, P.w);
 			// at most qlen + tlen <= 32 ops: staged in the 32 state words, which are dead now
 			n_cigar = traceback(i0, j0, qlen, tlen, w,
 				[&](int r, int k) { return (int)PD[(r * 16 + k) * 64]; },
@@ -889,12 +756,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, kFinishWa
 	}
 	int n_cigar = 0;
 	if (with_cigar) {
-		int i0 = -1, j0 = -1;
-		if (!ez.zdropped && !(P.flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
-		else if (!ez.zdropped && (P.flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
-		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
-		if (i0 >= 0 && j0 >= 0) {
-			const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
+		int i0, j0;
+		if (trace_start(ez, P, qlen, tlen, i0, j0)) {
+			const int w = dp_band_w(qlen, tlen, P.w);
 			const uint8_t *pb = w0 + team * SW;                      // the team's SW direction bytes of a step are contiguous
 			uint32_t *stage = (uint32_t *)(w0 + offE) + team;         // <= qlen + tlen ops; the strip-boundary arrays are dead now
 			// A byte per CIGAR step, each address known only when the byte before it has arrived, is a chain of memory round trips.  The
@@ -937,17 +801,256 @@ template __global__ void extd2_team_kernel<kDpTeamLanes, kDpTeamCpl, 1>(DpBatch,
 template __global__ void extd2_team_finish_kernel<kDpTeamLanes, kDpTeamCpl, 1>(DpBatch, DpParams, TeamPlan);
 
 // ------------------------------------------------------------------------------------------
-// general path: DP state in LDS laid out exactly like the reference's flat image
+// general path: DP state laid out exactly like the reference's flat image
 //   extd2: u|v|x|y|x2|y2|s|sf|qr   (ksw2_extd2_sse.c:100-103)
 //   extz2: u|v|x|y|s|sf|qr         (ksw2_extz2_sse.c:85-87)
 // so that the unaligned 16-byte score loads/stores that run past an array behave identically.
 // Direction bytes go to a global slab (they can exceed LDS for long sequences).
 // VAR = 0: dual affine (extd2);  VAR = 1: single affine (extz2, SSE2 code path).
+// Two kernels run it, extd2_lds_kernel (image in LDS, one wavefront) and extd2_hbm_kernel (image in HBM, kDpHbmWaves wavefronts);
+// the steps of an anti-diagonal are the gen_* functions below, the barriers between them are each kernel's own.
 // ------------------------------------------------------------------------------------------
+struct GenK { // constants of one launch
+	int neg_qe, neg_qe2, qe8, qe28;    // extd2, after the swap
+	int qe;                            // extz2: no swap, qe used throughout
+	uint8_t qe2b, max_scb, qb8;        // extz2 keeps its bytes unsigned, biased by qe
+	int with_cigar, approx_max, right;
+};
+__device__ __forceinline__ GenK gen_consts(const DpParams &P)
+{
+	GenK k;
+	k.neg_qe = s8(-P.q - P.e), k.neg_qe2 = s8(-P.q2 - P.e2), k.qe8 = s8(P.q + P.e), k.qe28 = s8(P.q2 + P.e2);
+	k.qe = P.q + P.e;
+	k.qe2b = (uint8_t)((P.q + P.e) * 2), k.max_scb = (uint8_t)(P.mat[0] + (P.q + P.e) * 2), k.qb8 = (uint8_t)P.q;
+	k.with_cigar = !(P.flag & PSVR_EZ_SCORE_ONLY), k.approx_max = !!(P.flag & PSVR_EZ_APPROX_MAX);
+	k.right = k.with_cigar && (P.flag & PSVR_EZ_RIGHT);
+	return k;
+}
+
+// the flat image with H (int32 per column) behind it.  IDX: int where it lies in LDS (32-bit addressing), long long in the HBM slab
+template <int VAR, class IDX>
+struct GenImage {
+	static constexpr int NARR = VAR == 0 ? 7 : 5;
+	uint8_t *base;
+	IDX T, img;                        // columns rounded to 16; bytes of the byte image (+16 calloc tail)
+	int8_t *u8, *v8, *x8, *y8, *x28, *y28, *sa;
+	uint8_t *sf, *qr;
+	int32_t *H;
+	__device__ __forceinline__ void place(uint8_t *at, int qlen, int tlen)
+	{
+		base = at;
+		T = ((IDX)tlen + 15) / 16 * 16;
+		const IDX QL = ((IDX)qlen + 15) / 16 * 16;
+		u8 = (int8_t*)at, v8 = u8 + T, x8 = v8 + T, y8 = x8 + T;
+		x28 = VAR == 0 ? y8 + T : nullptr, y28 = VAR == 0 ? x28 + T : nullptr;
+		sa = VAR == 0 ? y28 + T : y8 + T;
+		sf = (uint8_t*)(sa + T), qr = sf + T;
+		img = NARR * T + T + QL + 16;
+		H = (int32_t*)(at + ((img + 15) & ~(IDX)15));
+	}
+	__device__ __forceinline__ void init(int tid, int nthreads, const uint8_t *query, const uint8_t *target, int qlen, int tlen, const GenK &k) const
+	{
+		for (IDX i = tid; i < img; i += nthreads) {
+			const IDX a = i / T;                         // which array
+			uint8_t val = 0;
+			if (VAR == 0) { if (a < 4) val = (uint8_t)k.neg_qe; else if (a < 6) val = (uint8_t)k.neg_qe2; }
+			if (a == NARR) { const IDX t = i - NARR * T; val = t < tlen ? target[t] : 0; }
+			if (a > NARR)  { const IDX j = i - (NARR + 1) * T; val = j < qlen ? query[qlen - 1 - j] : 0; }
+			base[i] = val;
+		}
+		for (IDX i = tid; i < T; i += nthreads) H[i] = PSVR_KSW_NEG_INF;
+	}
+	// u / v as differences of H: extz2's bytes are unsigned and biased by qe
+	__device__ __forceinline__ int du(const GenK &k, int t) const { return VAR == 0 ? (int)u8[t] : (int)(uint8_t)u8[t] - k.qe; }
+	__device__ __forceinline__ int dv(const GenK &k, int t) const { return VAR == 0 ? (int)v8[t] : (int)(uint8_t)v8[t] - k.qe; }
+	// H[0] of the first diagonal (ksw2_extd2_sse.c:351, with q + e taken before the swap; ksw2_extz2_sse.c: v8[0] - qe - qe)
+	__device__ __forceinline__ int h_first(const GenK &k, const DpParams &P) const { return dv(k, 0) - (VAR == 0 ? P.qe_pre : k.qe); }
+};
+
+// (r-1, st-1) for the first cell of the diagonal: what the previous diagonal left in column st - 1 if it reached it, else the boundary
+// values (:142-152; int8_t in extz2, ksw2_extz2_sse.c:104,121)
+template <int VAR, class IMG>
+__device__ __forceinline__ void gen_left_boundary(const IMG &I, const GenK &k, const DpParams &P, int r, int st, int last_st, int last_en, int &x1, int &x21, int &v1)
+{
+	x21 = 0;
+	if (VAR == 0) {
+		if (st > 0) {
+			if (st - 1 >= last_st && st - 1 <= last_en) x1 = I.x8[st - 1], x21 = I.x28[st - 1], v1 = I.v8[st - 1];
+			else x1 = k.neg_qe, x21 = k.neg_qe2, v1 = k.neg_qe;
+		} else x1 = k.neg_qe, x21 = k.neg_qe2, v1 = dp_edge_gap(P, r);
+	} else {
+		if (st > 0) {
+			if (st - 1 >= last_st && st - 1 <= last_en) x1 = I.x8[st - 1], v1 = I.v8[st - 1];
+			else x1 = v1 = 0;
+		} else x1 = 0, v1 = r ? s8(P.q) : 0;
+	}
+}
+
+// u / y (y2) of the cell in the matrix's first row, column r (:153-156); one thread's job on diagonals with en >= r
+template <int VAR, class IMG>
+__device__ __forceinline__ void gen_row_override(const IMG &I, const GenK &k, const DpParams &P, int r)
+{
+	if (VAR == 0) I.y8[r] = k.neg_qe, I.y28[r] = k.neg_qe2, I.u8[r] = dp_edge_gap(P, r);
+	else I.y8[r] = 0, I.u8[r] = r ? (int8_t)k.qb8 : 0;
+}
+
+// The scores of diagonal r, into s.  The reference writes them in groups of 16 from st0 (:158-173), so the last group may run past s
+// into sf[0..14]: a store at t >= T.  DEFER: such a store (at most one per thread, for nthreads >= 15) is handed back, not done -- other
+// wavefronts may still be reading those target bases.
+struct GenLate { int t, sc; };
+template <bool DEFER, class IMG>
+__device__ __forceinline__ GenLate gen_scores(const IMG &I, const DpParams &P, int qlen, int r, int st0, int en0, int tid, int nthreads)
+{
+	const uint8_t *qrr = I.qr + (qlen - 1 - r);
+	GenLate late = {-1, 0};
+	if (!(P.flag & PSVR_EZ_GENERIC_SC)) {
+		const int fresh_end = dp_fresh_end(st0, en0);
+		for (int t = st0 + tid; t <= fresh_end; t += nthreads) {
+			const uint8_t sq = I.sf[t], sq2 = qrr[t];
+			int sc = sq == sq2 ? P.sc_mch : P.sc_mis;
+			if (sq == (uint8_t)P.m1 || sq2 == (uint8_t)P.m1) sc = P.sc_N;
+			if (!DEFER || t < I.T) I.sa[t] = (int8_t)sc;
+			else late.t = t, late.sc = sc;
+		}
+	} else {
+		for (int t = st0 + tid; t <= en0; t += nthreads) I.sa[t] = P.mat[I.sf[t] * P.m + qrr[t]];
+	}
+	return late;
+}
+
+// One cell (r, t): reads the image, returns the column's new state and the direction byte; the caller stores them.
+struct GenCell { int u, v, x, y, x2, y2, d; };
+template <int VAR, class IMG>
+__device__ __forceinline__ GenCell gen_cell(const IMG &I, const GenK &k, const DpParams &P, int t, int st, int x1, int x21, int v1)
+{
+	GenCell c = {0, 0, 0, 0, 0, 0, 0};
+	int d = 0;
+	if (VAR == 0) {
+		int xt1 = t == st ? x1 : (int)I.x8[t - 1], vt1 = t == st ? v1 : (int)I.v8[t - 1], x2t1 = t == st ? x21 : (int)I.x28[t - 1];
+		int z = I.sa[t], ut = I.u8[t];
+		int a = s8(xt1 + vt1), b = s8(I.y8[t] + ut), a2 = s8(x2t1 + vt1), b2 = s8(I.y28[t] + ut);
+		if (!k.right) {
+			if (a > z)  d = 1, z = a;
+			if (b > z)  d = 2, z = b;
+			if (a2 > z) d = 3, z = a2;
+			if (b2 > z) d = 4, z = b2;
+		} else {
+			d = z > a ? 0 : 1;  z = z > a ? z : a;
+			d = z > b ? d : 2;  z = z > b ? z : b;
+			d = z > a2 ? d : 3; z = z > a2 ? z : a2;
+			d = z > b2 ? d : 4; z = z > b2 ? z : b2;
+		}
+		z = min(z, P.sc_mch);
+		c.u = z - vt1, c.v = z - ut;
+		int tmp = s8(z - P.q);
+		a = s8(a - tmp), b = s8(b - tmp);
+		tmp = s8(z - P.q2);
+		a2 = s8(a2 - tmp), b2 = s8(b2 - tmp);
+		c.x = max(a, 0) - k.qe8, c.y = max(b, 0) - k.qe8, c.x2 = max(a2, 0) - k.qe28, c.y2 = max(b2, 0) - k.qe28;
+		if (!k.right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > 0 ? 0x20 : 0) | (b2 > 0 ? 0x40 : 0);
+		else d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= 0 ? 0x20 : 0) | (b2 >= 0 ? 0x40 : 0);
+	} else {
+		const int j = t - st;
+		unsigned x1w = (unsigned)x1, v1w = (unsigned)v1;   // sign-extended into lanes 1..3 (:147-148)
+		uint8_t xt1 = j == 0 ? 0 : (uint8_t)I.x8[t - 1], vt1 = j == 0 ? 0 : (uint8_t)I.v8[t - 1];
+		if (j < 4) xt1 |= (uint8_t)(x1w >> (8 * j)), vt1 |= (uint8_t)(v1w >> (8 * j));
+		uint8_t z = (uint8_t)((uint8_t)I.sa[t] + k.qe2b), a = (uint8_t)(xt1 + vt1), ut = (uint8_t)I.u8[t], b = (uint8_t)((uint8_t)I.y8[t] + ut);
+		if (!k.with_cigar) {
+			z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+		} else if (!k.right) {
+			d = (int8_t)a > (int8_t)z ? 1 : 0;
+			z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+			if ((int8_t)b > (int8_t)z) d = 2;
+		} else {
+			d = (int8_t)z > (int8_t)a ? 0 : 1;
+			z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
+			if (!((int8_t)z > (int8_t)b)) d = 2;
+		}
+		z = z > b ? z : b;
+		z = z < k.max_scb ? z : k.max_scb;
+		c.u = (uint8_t)(z - vt1), c.v = (uint8_t)(z - ut);
+		z = (uint8_t)(z - k.qb8);
+		a = (uint8_t)(a - z), b = (uint8_t)(b - z);
+		if (!k.right) {
+			c.x = (int8_t)a > 0 ? (int8_t)a : 0; d |= (int8_t)a > 0 ? 0x08 : 0;
+			c.y = (int8_t)b > 0 ? (int8_t)b : 0; d |= (int8_t)b > 0 ? 0x10 : 0;
+		} else {
+			c.x = (int8_t)a < 0 ? 0 : (int8_t)a; d |= (int8_t)a < 0 ? 0 : 0x08;
+			c.y = (int8_t)b < 0 ? 0 : (int8_t)b; d |= (int8_t)b < 0 ? 0 : 0x10;
+		}
+	}
+	c.d = d;
+	return c;
+}
+template <int VAR, class IMG>
+__device__ __forceinline__ void gen_store_cell(const IMG &I, int t, const GenCell &c)
+{
+	I.u8[t] = (int8_t)c.u, I.v8[t] = (int8_t)c.v, I.x8[t] = (int8_t)c.x, I.y8[t] = (int8_t)c.y;
+	if (VAR == 0) I.x28[t] = (int8_t)c.x2, I.y28[t] = (int8_t)c.y2;
+}
+
+// exact H (:316-351).  On a diagonal r > 0 the last in-band column continues from its left neighbour (:322), read before anybody
+// updates H; then every thread adds v to its share of H[st0..en0) and keeps the best (h, rank) it has seen.  The reduction over
+// threads is the caller's.
+template <class IMG>
+__device__ __forceinline__ int gen_h_en0(const IMG &I, const GenK &k, int en0)
+{
+	const int uen = I.du(k, en0), ven = I.dv(k, en0);
+	return en0 > 0 ? I.H[en0 - 1] + uen : I.H[en0] + ven;
+}
+template <int RS, class IMG>
+__device__ __forceinline__ void gen_exact_h_partial(const IMG &I, const GenK &k, int st0, int en0, int h_en0, int tid, int nthreads, int &bh, unsigned &bk)
+{
+	const int en1 = dp_diag_en1(st0, en0);
+	bh = (int)0x80000000, bk = 0xffffffffu;
+	for (int t = st0 + tid; t <= en0; t += nthreads) {
+		const int h = t == en0 ? h_en0 : I.H[t] + I.dv(k, t);
+		I.H[t] = h;
+		const unsigned rank = dp_diag_rank<RS>(t, st0, en0, en1);
+		if (h > bh || (h == bh && rank < bk)) bh = h, bk = rank;
+	}
+}
+
+// KSW_EZ_APPROX_MAX: H followed along one path only (:360-376; ksw2_extz2_sse.c:270-286).  Uniform, every thread does it.  true = z-drop
+template <int VAR, class IMG>
+__device__ __forceinline__ bool gen_approx_step(const IMG &I, const GenK &k, const DpParams &P, EzAcc &ez, int r, int qlen, int tlen, int st0, int en0, int &H0, int &last_H0_t)
+{
+	const int e_drop = VAR == 0 ? P.e2 : P.e;
+	const bool drop = (P.flag & PSVR_EZ_APPROX_DROP) != 0;
+	if (r > 0) {
+		if (last_H0_t >= st0 && last_H0_t <= en0 && last_H0_t + 1 >= st0 && last_H0_t + 1 <= en0) {
+			const int d0 = I.dv(k, last_H0_t), d1 = I.du(k, last_H0_t + 1);
+			if (d0 > d1) H0 += d0;
+			else H0 += d1, ++last_H0_t;
+		} else if (last_H0_t >= st0 && last_H0_t <= en0) {
+			H0 += I.dv(k, last_H0_t);
+		} else {
+			++last_H0_t, H0 += I.du(k, last_H0_t);
+		}
+		if (VAR == 1 && drop && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) return true;
+	} else H0 = I.h_first(k, P), last_H0_t = 0;
+	// extd2 tests the approximate drop on every diagonal including r==0 (ksw2_extd2_sse.c:373);
+	// extz2 only for r>0 (ksw2_extz2_sse.c:283)
+	if (VAR == 0 && drop && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) return true;
+	if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H0;
+	return false;
+}
+
+// The walk emitted the ops last first, straight into the output; the order the caller wants unless PSVR_EZ_REV_CIGAR is the other one:
+// turned round in place by one wavefront, after the caller's fence and barrier
+__device__ __forceinline__ void cigar_reverse_in_place(uint32_t *dst, int n_cigar, int lane)
+{
+	for (int m = lane; m < (n_cigar >> 1); m += 64) {
+		uint32_t a = __builtin_nontemporal_load(dst + m), b = __builtin_nontemporal_load(dst + n_cigar - 1 - m);
+		dst[m] = b, dst[n_cigar - 1 - m] = a;
+	}
+}
+
 template <int VAR>
 __global__ __launch_bounds__(64) void extd2_lds_kernel(DpBatch B, DpParams P)
 {
 	extern __shared__ __align__(16) uint8_t lds[];
+	constexpr int RS = 14;                          // rank shift: the image of at most 16384 columns is all LDS holds
 	const int pid = B.idx[blockIdx.x];
 	const int lane = threadIdx.x;
 	const int qlen = B.qlen[pid], tlen = B.tlen[pid];
@@ -959,234 +1062,72 @@ __global__ __launch_bounds__(64) void extd2_lds_kernel(DpBatch B, DpParams P)
 		return;
 	}
 	const uint8_t *query = B.qseq + B.q_off[pid], *target = B.tseq + B.t_off[pid];
-	const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
-	int n_col = qlen < tlen ? qlen : tlen;
-	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
-	const int rowb = n_col * 16;
+	const int w = dp_band_w(qlen, tlen, P.w);
+	const int rowb = dp_n_col(qlen, tlen, P.w) * 16;
 	const int n_rows = qlen + tlen - 1;
-	const int T = ((tlen + 15) / 16) * 16, QL = ((qlen + 15) / 16) * 16;
-	constexpr int NARR = VAR == 0 ? 7 : 5;
-	int8_t *u8 = (int8_t*)lds, *v8 = u8 + T, *x8 = v8 + T, *y8 = x8 + T;
-	int8_t *x28 = VAR == 0 ? y8 + T : nullptr, *y28 = VAR == 0 ? x28 + T : nullptr;
-	int8_t *sa = VAR == 0 ? y28 + T : y8 + T;
-	uint8_t *sf = (uint8_t*)(sa + T), *qr = sf + T;
-	const int img = NARR * T + T + QL + 16;            // bytes of the byte image (+16 calloc tail)
-	int32_t *H = (int32_t*)(lds + ((img + 15) & ~15));
+	const GenK k = gen_consts(P);
+	GenImage<VAR, int> I;
+	I.place(lds, qlen, tlen);
 	uint8_t *Pm = B.pslab + (B.p_off[pid] << B.p_unit_shift);
-	const int flag = P.flag;
-	const int with_cigar = !(flag & PSVR_EZ_SCORE_ONLY), approx_max = !!(flag & PSVR_EZ_APPROX_MAX);
-	const int right = with_cigar && (flag & PSVR_EZ_RIGHT);
-
-	const int neg_qe = s8(-P.q - P.e), neg_qe2 = s8(-P.q2 - P.e2);
-	const int qe8 = s8(P.q + P.e), qe28 = s8(P.q2 + P.e2);
-	const int qe = P.q + P.e;                       // extz2: no swap, qe used throughout
-	for (int i = lane; i < img; i += 64) {
-		int a = i / T;                               // which array
-		uint8_t val = 0;
-		if (VAR == 0) { if (a < 4) val = (uint8_t)neg_qe; else if (a < 6) val = (uint8_t)neg_qe2; }
-		if (a == NARR) { int t = i - NARR * T; val = t < tlen ? target[t] : 0; }
-		if (a > NARR)  { int k = i - (NARR + 1) * T; val = k < qlen ? query[qlen - 1 - k] : 0; }
-		lds[i] = val;
-	}
-	for (int i = lane; i < T; i += 64) H[i] = PSVR_KSW_NEG_INF;
+	I.init(lane, 64, query, target, qlen, tlen, k);
 	__syncthreads();
 
 	int last_st = -1, last_en = -1, H0 = 0, last_H0_t = 0;
-	const uint8_t qe2b = (uint8_t)((P.q + P.e) * 2), max_scb = (uint8_t)(P.mat[0] + (P.q + P.e) * 2), qb8 = (uint8_t)P.q;
 	for (int r = 0; r < n_rows; ++r) {
 		int st0, en0, st, en;
 		if (!band_limits(r, qlen, tlen, w, st0, en0, st, en)) { ez.zdropped = 1; break; }
-		int x1, x21 = 0, v1;
-		if (VAR == 0) {
-			if (st > 0) {
-				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], x21 = x28[st - 1], v1 = v8[st - 1];
-				else x1 = neg_qe, x21 = neg_qe2, v1 = neg_qe;
-			} else {
-				x1 = neg_qe, x21 = neg_qe2;
-				v1 = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-			}
-		} else {
-			if (st > 0) {
-				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], v1 = v8[st - 1];   // int8_t in the reference (:104,121)
-				else x1 = v1 = 0;
-			} else x1 = 0, v1 = r ? s8(P.q) : 0;
-		}
+		int x1, x21, v1;
+		gen_left_boundary<VAR>(I, k, P, r, st, last_st, last_en, x1, x21, v1);
 		__syncthreads();
-		if (en >= r && lane == 0) {
-			if (VAR == 0) {
-				y8[r] = neg_qe, y28[r] = neg_qe2;
-				u8[r] = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-			} else y8[r] = 0, u8[r] = r ? (int8_t)qb8 : 0;
-		}
-		// scores
-		const uint8_t *qrr = qr + (qlen - 1 - r);
-		if (!(flag & PSVR_EZ_GENERIC_SC)) {
-			const int fresh_end = st0 + ((en0 - st0) / 16 + 1) * 16 - 1;
-			for (int t0 = st0; t0 <= fresh_end; t0 += 64) {
-				int t = t0 + lane;
-				if (t <= fresh_end) {
-					uint8_t sq = sf[t], sq2 = qrr[t];
-					int sc = sq == sq2 ? P.sc_mch : P.sc_mis;
-					if (sq == (uint8_t)P.m1 || sq2 == (uint8_t)P.m1) sc = P.sc_N;
-					sa[t] = (int8_t)sc;
-				}
-			}
-		} else {
-			for (int t = st0 + lane; t <= en0; t += 64) sa[t] = P.mat[sf[t] * P.m + qrr[t]];
-		}
+		if (en >= r && lane == 0) gen_row_override<VAR>(I, k, P, r);
+		gen_scores<false>(I, P, qlen, r, st0, en0, lane, 64);
 		__syncthreads();
-		// core: 64-lane groups from high t to low t
+		// core: 64-lane groups from high t to low t, updated in place (the lanes of a wavefront have all read before any of them writes)
 		const int ngrp = (en - st) / 64 + 1;
 		for (int g = ngrp - 1; g >= 0; --g) {
 			const int t = st + g * 64 + lane;
 			if (t <= en) {
-				int d = 0;
-				if (VAR == 0) {
-					int xt1 = t == st ? x1 : (int)x8[t - 1], vt1 = t == st ? v1 : (int)v8[t - 1], x2t1 = t == st ? x21 : (int)x28[t - 1];
-					int z = sa[t], ut = u8[t];
-					int a = s8(xt1 + vt1), b = s8(y8[t] + ut), a2 = s8(x2t1 + vt1), b2 = s8(y28[t] + ut);
-					if (!right) {
-						if (a > z)  d = 1, z = a;
-						if (b > z)  d = 2, z = b;
-						if (a2 > z) d = 3, z = a2;
-						if (b2 > z) d = 4, z = b2;
-					} else {
-						d = z > a ? 0 : 1;  z = z > a ? z : a;
-						d = z > b ? d : 2;  z = z > b ? z : b;
-						d = z > a2 ? d : 3; z = z > a2 ? z : a2;
-						d = z > b2 ? d : 4; z = z > b2 ? z : b2;
-					}
-					z = min(z, P.sc_mch);
-					u8[t] = (int8_t)(z - vt1), v8[t] = (int8_t)(z - ut);
-					int tmp = s8(z - P.q);
-					a = s8(a - tmp), b = s8(b - tmp);
-					tmp = s8(z - P.q2);
-					a2 = s8(a2 - tmp), b2 = s8(b2 - tmp);
-					if (!right) {
-						x8[t]  = (int8_t)(max(a, 0) - qe8);   d |= a  > 0 ? 0x08 : 0;
-						y8[t]  = (int8_t)(max(b, 0) - qe8);   d |= b  > 0 ? 0x10 : 0;
-						x28[t] = (int8_t)(max(a2, 0) - qe28); d |= a2 > 0 ? 0x20 : 0;
-						y28[t] = (int8_t)(max(b2, 0) - qe28); d |= b2 > 0 ? 0x40 : 0;
-					} else {
-						x8[t]  = (int8_t)(max(a, 0) - qe8);   d |= a  >= 0 ? 0x08 : 0;
-						y8[t]  = (int8_t)(max(b, 0) - qe8);   d |= b  >= 0 ? 0x10 : 0;
-						x28[t] = (int8_t)(max(a2, 0) - qe28); d |= a2 >= 0 ? 0x20 : 0;
-						y28[t] = (int8_t)(max(b2, 0) - qe28); d |= b2 >= 0 ? 0x40 : 0;
-					}
-				} else {
-					const int k = t - st;
-					unsigned x1w = (unsigned)x1, v1w = (unsigned)v1;   // sign-extended into lanes 1..3 (:147-148)
-					uint8_t xt1 = k == 0 ? 0 : (uint8_t)x8[t - 1], vt1 = k == 0 ? 0 : (uint8_t)v8[t - 1];
-					if (k < 4) xt1 |= (uint8_t)(x1w >> (8 * k)), vt1 |= (uint8_t)(v1w >> (8 * k));
-					uint8_t z = (uint8_t)((uint8_t)sa[t] + qe2b), a = (uint8_t)(xt1 + vt1), ut = (uint8_t)u8[t], b = (uint8_t)((uint8_t)y8[t] + ut);
-					if (!with_cigar) {
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-					} else if (!right) {
-						d = (int8_t)a > (int8_t)z ? 1 : 0;
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-						if ((int8_t)b > (int8_t)z) d = 2;
-					} else {
-						d = (int8_t)z > (int8_t)a ? 0 : 1;
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-						if (!((int8_t)z > (int8_t)b)) d = 2;
-					}
-					z = z > b ? z : b;
-					z = z < max_scb ? z : max_scb;
-					u8[t] = (int8_t)(uint8_t)(z - vt1), v8[t] = (int8_t)(uint8_t)(z - ut);
-					z = (uint8_t)(z - qb8);
-					a = (uint8_t)(a - z), b = (uint8_t)(b - z);
-					if (!right) {
-						x8[t] = (int8_t)a > 0 ? (int8_t)a : 0; d |= (int8_t)a > 0 ? 0x08 : 0;
-						y8[t] = (int8_t)b > 0 ? (int8_t)b : 0; d |= (int8_t)b > 0 ? 0x10 : 0;
-					} else {
-						x8[t] = (int8_t)a < 0 ? 0 : (int8_t)a; d |= (int8_t)a < 0 ? 0 : 0x08;
-						y8[t] = (int8_t)b < 0 ? 0 : (int8_t)b; d |= (int8_t)b < 0 ? 0 : 0x10;
-					}
-				}
-				if (with_cigar) Pm[(size_t)r * rowb + (t - st)] = (uint8_t)d;
+				const GenCell c = gen_cell<VAR>(I, k, P, t, st, x1, x21, v1);
+				gen_store_cell<VAR>(I, t, c);
+				if (k.with_cigar) Pm[(size_t)r * rowb + (t - st)] = (uint8_t)c.d;
 			}
 			__syncthreads();
 		}
-		const int e_drop = VAR == 0 ? P.e2 : P.e;
-		if (!approx_max) {
+		if (!k.approx_max) {
 			int max_H, max_t;
 			if (r > 0) {
-				const int en1 = st0 + (en0 - st0) / 4 * 4;
-				const int uen = VAR == 0 ? (int)u8[en0] : (int)(uint8_t)u8[en0] - qe;
-				const int ven = VAR == 0 ? (int)v8[en0] : (int)(uint8_t)v8[en0] - qe;
-				const int h_en0 = en0 > 0 ? H[en0 - 1] + uen : H[en0] + ven;
+				const int h_en0 = gen_h_en0(I, k, en0);
 				__syncthreads();
-				int bh = (int)0x80000000; unsigned bk = 0xffffffffu;
-				for (int t0 = st0; t0 <= en0; t0 += 64) {
-					int t = t0 + lane;
-					if (t <= en0) {
-						int h;
-						if (t == en0) h = h_en0;
-						else h = H[t] + (VAR == 0 ? (int)v8[t] : (int)(uint8_t)v8[t] - qe);
-						H[t] = h;
-						unsigned rank = t == en0 ? 0u : t < en1 ? 1u + (unsigned)((t - st0) & 3) * 16384u + (unsigned)(t - st0)
-						                                        : 1u + 4u * 16384u + (unsigned)(t - st0);
-						if (h > bh || (h == bh && rank < bk)) bh = h, bk = rank;
-					}
-				}
+				int bh; unsigned bk;
+				gen_exact_h_partial<RS>(I, k, st0, en0, h_en0, lane, 64, bh, bk);
 				max_H = wave_max_i32(bh);
-				unsigned rk = wave_min_u32(bh == max_H ? bk : 0xffffffffu);
-				max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & 16383u);
+				max_t = dp_rank_col<RS>(wave_min_u32(bh == max_H ? bk : 0xffffffffu), st0, en0);
 				__syncthreads();
 			} else {
-				int h0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe;
+				const int h0 = I.h_first(k, P);
 				__syncthreads();
-				if (lane == 0) H[0] = h0;
+				if (lane == 0) I.H[0] = h0;
 				max_H = h0, max_t = 0;
 				__syncthreads();
 			}
-			const int H_en0 = H[en0], H_st0 = H[st0];
-			if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - en;
-			if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
-			if (ez.apply_zdrop(max_H, r, max_t, P.zdrop, e_drop)) break;
-			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H[tlen - 1];
-		} else {
-			const int bias = VAR == 0 ? 0 : qe;
-			if (r > 0) {
-				if (last_H0_t >= st0 && last_H0_t <= en0 && last_H0_t + 1 >= st0 && last_H0_t + 1 <= en0) {
-					int d0 = (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
-					int d1 = (VAR == 0 ? (int)u8[last_H0_t + 1] : (int)(uint8_t)u8[last_H0_t + 1]) - bias;
-					if (d0 > d1) H0 += d0;
-					else H0 += d1, ++last_H0_t;
-				} else if (last_H0_t >= st0 && last_H0_t <= en0) {
-					H0 += (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
-				} else {
-					++last_H0_t, H0 += (VAR == 0 ? (int)u8[last_H0_t] : (int)(uint8_t)u8[last_H0_t]) - bias;
-				}
-				if (VAR == 1 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
-			} else H0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe, last_H0_t = 0;
-			// extd2 tests the approximate drop on every diagonal including r==0 (ksw2_extd2_sse.c:373);
-			// extz2 only for r>0 (ksw2_extz2_sse.c:283)
-			if (VAR == 0 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
-			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H0;
-		}
+			if (ez.end_diagonal(r, qlen, tlen, st0, en0, I.H[st0], I.H[en0], max_H, max_t, P.zdrop, VAR == 0 ? P.e2 : P.e)) break;
+		} else if (gen_approx_step<VAR>(I, k, P, ez, r, qlen, tlen, st0, en0, H0, last_H0_t)) break;
 		last_st = st, last_en = en;
 	}
 	int n_cigar = 0;
-	if (with_cigar) {
+	if (k.with_cigar) {
 		__threadfence_block();
 		__syncthreads();
-		int i0 = -1, j0 = -1;
-		if (!ez.zdropped && !(flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
-		else if (!ez.zdropped && (flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
-		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
-		if (i0 >= 0 && j0 >= 0) {
+		int i0, j0;
+		if (trace_start(ez, P, qlen, tlen, i0, j0)) {
 			uint32_t *dst = B.cigar + uni64(out->cigar_off);
 			n_cigar = traceback(i0, j0, qlen, tlen, w,
-				[&](int r, int k) { return (int)__builtin_nontemporal_load(Pm + (size_t)r * rowb + k); },
-				[&](int k, uint32_t word) { if (lane == 0) dst[k] = word; });
-			if (!(flag & PSVR_EZ_REV_CIGAR)) {
+				[&](int r, int j) { return (int)__builtin_nontemporal_load(Pm + (size_t)r * rowb + j); },
+				[&](int j, uint32_t word) { if (lane == 0) dst[j] = word; });
+			if (!(P.flag & PSVR_EZ_REV_CIGAR)) {
 				__threadfence_block();
 				__syncthreads();
-				for (int m = lane; m < (n_cigar >> 1); m += 64) {
-					uint32_t a = __builtin_nontemporal_load(dst + m), b = __builtin_nontemporal_load(dst + n_cigar - 1 - m);
-					dst[m] = b, dst[n_cigar - 1 - m] = a;
-				}
+				cigar_reverse_in_place(dst, n_cigar, lane);
 			}
 		}
 	}
@@ -1197,13 +1138,13 @@ template __global__ void extd2_lds_kernel<0>(DpBatch, DpParams);
 template __global__ void extd2_lds_kernel<1>(DpBatch, DpParams);
 
 // ------------------------------------------------------------------------------------------
-// general path for what LDS cannot hold: extd2_lds_kernel's recurrence, cell for cell, with its flat image (and so every
-// artefact of the reference's unaligned 16-byte score stores) and H in this problem's slice of the HBM slab
-// (dp_hbm_img_off), query and target read from global memory once into that image.  Anti-diagonal r touches the columns
-// [st, max(en, fresh_end)] only -- contiguous, coalesced byte accesses that stay in L2.  A workgroup of kDpHbmWaves
-// wavefronts per alignment: an unbanded anti-diagonal has up to min(qlen, tlen) cells.  The in-place update of the column
-// arrays reads column t - 1 of the previous diagonal, which another wavefront may own, so a chunk of 64 kDpHbmWaves cells
-// (chunks from high t to low t, as in extd2_lds_kernel) computes everything, waits at a barrier, then stores.
+// general path for what LDS cannot hold: the same recurrence with its flat image (and so every artefact of the reference's
+// unaligned 16-byte score stores) and H in this problem's slice of the HBM slab (dp_hbm_img_off), query and target read from
+// global memory once into that image.  Anti-diagonal r touches the columns [st, max(en, fresh_end)] only -- contiguous,
+// coalesced byte accesses that stay in L2.  A workgroup of kDpHbmWaves wavefronts per alignment: an unbanded anti-diagonal has
+// up to min(qlen, tlen) cells.  The in-place update of the column arrays reads column t - 1 of the previous diagonal, which
+// another wavefront may own, so a chunk of 64 kDpHbmWaves cells (chunks from high t to low t, as in extd2_lds_kernel) computes
+// everything, waits at a barrier, then stores.
 // ------------------------------------------------------------------------------------------
 template <int VAR>
 __global__ __launch_bounds__(64 * kDpHbmWaves) void extd2_hbm_kernel(DpBatch B, DpParams P)
@@ -1223,86 +1164,30 @@ __global__ __launch_bounds__(64 * kDpHbmWaves) void extd2_hbm_kernel(DpBatch B, 
 		return;
 	}
 	const uint8_t *query = B.qseq + B.q_off[pid], *target = B.tseq + B.t_off[pid];
-	const int w = P.w < 0 ? (tlen > qlen ? tlen : qlen) : P.w;
-	int n_col = qlen < tlen ? qlen : tlen;
-	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
-	const long long rowb = n_col * 16;
+	const int w = dp_band_w(qlen, tlen, P.w);
+	const long long rowb = dp_n_col(qlen, tlen, P.w) * 16;
 	const int n_rows = qlen + tlen - 1;
-	const long long T = ((tlen + 15LL) / 16) * 16, QL = ((qlen + 15LL) / 16) * 16;
-	constexpr int NARR = VAR == 0 ? 7 : 5;
-	const int flag = P.flag;
-	const int with_cigar = !(flag & PSVR_EZ_SCORE_ONLY), approx_max = !!(flag & PSVR_EZ_APPROX_MAX);
-	const int right = with_cigar && (flag & PSVR_EZ_RIGHT);
+	const GenK k = gen_consts(P);
 	uint8_t *Pm = B.pslab + (B.p_off[pid] << B.p_unit_shift);
-	uint8_t *img8 = Pm + dp_hbm_img_off(qlen, tlen, P.w, with_cigar != 0);
-	int8_t *u8 = (int8_t*)img8, *v8 = u8 + T, *x8 = v8 + T, *y8 = x8 + T;
-	int8_t *x28 = VAR == 0 ? y8 + T : nullptr, *y28 = VAR == 0 ? x28 + T : nullptr;
-	int8_t *sa = VAR == 0 ? y28 + T : y8 + T;
-	uint8_t *sf = (uint8_t*)(sa + T), *qr = sf + T;
-	const long long img = NARR * T + T + QL + 16;
-	int32_t *H = (int32_t*)(img8 + ((img + 15) & ~15LL));
-
-	const int neg_qe = s8(-P.q - P.e), neg_qe2 = s8(-P.q2 - P.e2);
-	const int qe8 = s8(P.q + P.e), qe28 = s8(P.q2 + P.e2);
-	const int qe = P.q + P.e;
-	for (long long i = tid; i < img; i += NT) {
-		const long long a = i / T;
-		uint8_t val = 0;
-		if (VAR == 0) { if (a < 4) val = (uint8_t)neg_qe; else if (a < 6) val = (uint8_t)neg_qe2; }
-		if (a == NARR) { long long t = i - NARR * T; val = t < tlen ? target[t] : 0; }
-		if (a > NARR)  { long long k = i - (NARR + 1) * T; val = k < qlen ? query[qlen - 1 - k] : 0; }
-		img8[i] = val;
-	}
-	for (long long i = tid; i < T; i += NT) H[i] = PSVR_KSW_NEG_INF;
+	GenImage<VAR, long long> I;
+	I.place(Pm + dp_hbm_img_off(qlen, tlen, P.w, k.with_cigar != 0), qlen, tlen);
+	I.init(tid, NT, query, target, qlen, tlen, k);
 	__syncthreads();
 
 	int last_st = -1, last_en = -1, H0 = 0, last_H0_t = 0;
-	const uint8_t qe2b = (uint8_t)((P.q + P.e) * 2), max_scb = (uint8_t)(P.mat[0] + (P.q + P.e) * 2), qb8 = (uint8_t)P.q;
 	for (int r = 0; r < n_rows; ++r) {
 		int st0, en0, st, en;
 		if (!band_limits(r, qlen, tlen, w, st0, en0, st, en)) { ez.zdropped = 1; break; }
-		int x1, x21 = 0, v1;
-		if (VAR == 0) {
-			if (st > 0) {
-				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], x21 = x28[st - 1], v1 = v8[st - 1];
-				else x1 = neg_qe, x21 = neg_qe2, v1 = neg_qe;
-			} else {
-				x1 = neg_qe, x21 = neg_qe2;
-				v1 = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-			}
-		} else {
-			if (st > 0) {
-				if (st - 1 >= last_st && st - 1 <= last_en) x1 = x8[st - 1], v1 = v8[st - 1];
-				else x1 = v1 = 0;
-			} else x1 = 0, v1 = r ? s8(P.q) : 0;
-		}
+		int x1, x21, v1;
+		gen_left_boundary<VAR>(I, k, P, r, st, last_st, last_en, x1, x21, v1);
 		__syncthreads();
-		if (en >= r && tid == 0) {
-			if (VAR == 0) {
-				y8[r] = neg_qe, y28[r] = neg_qe2;
-				u8[r] = r == 0 ? neg_qe : r < P.long_thres ? s8(-P.e) : r == P.long_thres ? s8(P.long_diff) : s8(-P.e2);
-			} else y8[r] = 0, u8[r] = r ? (int8_t)qb8 : 0;
-		}
-		// scores
-		const uint8_t *qrr = qr + (qlen - 1 - r);
-		if (!(flag & PSVR_EZ_GENERIC_SC)) {
-			const int fresh_end = st0 + ((en0 - st0) / 16 + 1) * 16 - 1;
-			// the last 16-block may run past s into sf[0..14] (the reference's unaligned store): those columns were read
-			// above by lanes of other wavefronts, so that store waits for a barrier (at most one such cell per thread)
-			int ovr_t = -1, ovr_sc = 0;
-			for (int t = st0 + tid; t <= fresh_end; t += NT) {
-				uint8_t sq = sf[t], sq2 = qrr[t];
-				int sc = sq == sq2 ? P.sc_mch : P.sc_mis;
-				if (sq == (uint8_t)P.m1 || sq2 == (uint8_t)P.m1) sc = P.sc_N;
-				if (t < T) sa[t] = (int8_t)sc;
-				else ovr_t = t, ovr_sc = sc;
-			}
-			if (fresh_end >= T) {
-				__syncthreads();
-				if (ovr_t >= 0) sa[ovr_t] = (int8_t)ovr_sc;
-			}
-		} else {
-			for (int t = st0 + tid; t <= en0; t += NT) sa[t] = P.mat[sf[t] * P.m + qrr[t]];
+		if (en >= r && tid == 0) gen_row_override<VAR>(I, k, P, r);
+		// a score that lands in sf[0..14] (the reference's unaligned store past s): those columns were read above by lanes of other
+		// wavefronts, so that store waits for a barrier
+		const GenLate late = gen_scores<true>(I, P, qlen, r, st0, en0, tid, NT);
+		if (!(P.flag & PSVR_EZ_GENERIC_SC) && dp_fresh_end(st0, en0) >= I.T) {
+			__syncthreads();
+			if (late.t >= 0) I.sa[late.t] = (int8_t)late.sc;
 		}
 		__syncthreads();
 		// core: chunks of NT cells from high t to low t; a chunk reads nothing a later (lower) chunk writes
@@ -1310,154 +1195,59 @@ __global__ __launch_bounds__(64 * kDpHbmWaves) void extd2_hbm_kernel(DpBatch B, 
 		for (int g = ngrp - 1; g >= 0; --g) {
 			const int t = st + g * NT + tid;
 			const bool act = t <= en;
-			int nu = 0, nv = 0, nx = 0, ny = 0, nx2 = 0, ny2 = 0, d = 0;
-			if (act) {
-				if (VAR == 0) {
-					int xt1 = t == st ? x1 : (int)x8[t - 1], vt1 = t == st ? v1 : (int)v8[t - 1], x2t1 = t == st ? x21 : (int)x28[t - 1];
-					int z = sa[t], ut = u8[t];
-					int a = s8(xt1 + vt1), b = s8(y8[t] + ut), a2 = s8(x2t1 + vt1), b2 = s8(y28[t] + ut);
-					if (!right) {
-						if (a > z)  d = 1, z = a;
-						if (b > z)  d = 2, z = b;
-						if (a2 > z) d = 3, z = a2;
-						if (b2 > z) d = 4, z = b2;
-					} else {
-						d = z > a ? 0 : 1;  z = z > a ? z : a;
-						d = z > b ? d : 2;  z = z > b ? z : b;
-						d = z > a2 ? d : 3; z = z > a2 ? z : a2;
-						d = z > b2 ? d : 4; z = z > b2 ? z : b2;
-					}
-					z = min(z, P.sc_mch);
-					nu = z - vt1, nv = z - ut;
-					int tmp = s8(z - P.q);
-					a = s8(a - tmp), b = s8(b - tmp);
-					tmp = s8(z - P.q2);
-					a2 = s8(a2 - tmp), b2 = s8(b2 - tmp);
-					nx = max(a, 0) - qe8, ny = max(b, 0) - qe8, nx2 = max(a2, 0) - qe28, ny2 = max(b2, 0) - qe28;
-					if (!right) d |= (a > 0 ? 0x08 : 0) | (b > 0 ? 0x10 : 0) | (a2 > 0 ? 0x20 : 0) | (b2 > 0 ? 0x40 : 0);
-					else d |= (a >= 0 ? 0x08 : 0) | (b >= 0 ? 0x10 : 0) | (a2 >= 0 ? 0x20 : 0) | (b2 >= 0 ? 0x40 : 0);
-				} else {
-					const int k = t - st;
-					unsigned x1w = (unsigned)x1, v1w = (unsigned)v1;   // sign-extended into lanes 1..3 (:147-148)
-					uint8_t xt1 = k == 0 ? 0 : (uint8_t)x8[t - 1], vt1 = k == 0 ? 0 : (uint8_t)v8[t - 1];
-					if (k < 4) xt1 |= (uint8_t)(x1w >> (8 * k)), vt1 |= (uint8_t)(v1w >> (8 * k));
-					uint8_t z = (uint8_t)((uint8_t)sa[t] + qe2b), a = (uint8_t)(xt1 + vt1), ut = (uint8_t)u8[t], b = (uint8_t)((uint8_t)y8[t] + ut);
-					if (!with_cigar) {
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-					} else if (!right) {
-						d = (int8_t)a > (int8_t)z ? 1 : 0;
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-						if ((int8_t)b > (int8_t)z) d = 2;
-					} else {
-						d = (int8_t)z > (int8_t)a ? 0 : 1;
-						z = (int8_t)z > 0 ? z : 0; z = z > a ? z : a;
-						if (!((int8_t)z > (int8_t)b)) d = 2;
-					}
-					z = z > b ? z : b;
-					z = z < max_scb ? z : max_scb;
-					nu = (uint8_t)(z - vt1), nv = (uint8_t)(z - ut);
-					z = (uint8_t)(z - qb8);
-					a = (uint8_t)(a - z), b = (uint8_t)(b - z);
-					if (!right) {
-						nx = (int8_t)a > 0 ? (int8_t)a : 0; d |= (int8_t)a > 0 ? 0x08 : 0;
-						ny = (int8_t)b > 0 ? (int8_t)b : 0; d |= (int8_t)b > 0 ? 0x10 : 0;
-					} else {
-						nx = (int8_t)a < 0 ? 0 : (int8_t)a; d |= (int8_t)a < 0 ? 0 : 0x08;
-						ny = (int8_t)b < 0 ? 0 : (int8_t)b; d |= (int8_t)b < 0 ? 0 : 0x10;
-					}
-				}
-			}
+			GenCell c;
+			if (act) c = gen_cell<VAR>(I, k, P, t, st, x1, x21, v1);
 			__syncthreads();          // every read of this chunk's columns (t - 1 may belong to another wavefront) precedes its writes
 			if (act) {
-				u8[t] = (int8_t)nu, v8[t] = (int8_t)nv, x8[t] = (int8_t)nx, y8[t] = (int8_t)ny;
-				if (VAR == 0) x28[t] = (int8_t)nx2, y28[t] = (int8_t)ny2;
-				if (with_cigar) Pm[r * rowb + (t - st)] = (uint8_t)d;
+				gen_store_cell<VAR>(I, t, c);
+				if (k.with_cigar) Pm[r * rowb + (t - st)] = (uint8_t)c.d;
 			}
 		}
 		__syncthreads();
-		const int e_drop = VAR == 0 ? P.e2 : P.e;
-		if (!approx_max) {
+		if (!k.approx_max) {
 			int max_H, max_t;
 			if (r > 0) {
-				const int en1 = st0 + (en0 - st0) / 4 * 4;
-				const int uen = VAR == 0 ? (int)u8[en0] : (int)(uint8_t)u8[en0] - qe;
-				const int ven = VAR == 0 ? (int)v8[en0] : (int)(uint8_t)v8[en0] - qe;
-				const int h_en0 = en0 > 0 ? H[en0 - 1] + uen : H[en0] + ven;
+				const int h_en0 = gen_h_en0(I, k, en0);
 				__syncthreads();
-				int bh = (int)0x80000000; unsigned bk = 0xffffffffu;
-				for (int t = st0 + tid; t <= en0; t += NT) {
-					int h;
-					if (t == en0) h = h_en0;
-					else h = H[t] + (VAR == 0 ? (int)v8[t] : (int)(uint8_t)v8[t] - qe);
-					H[t] = h;
-					unsigned rank = t == en0 ? 0u : t < en1 ? 1u + ((unsigned)((t - st0) & 3) << RS) + (unsigned)(t - st0)
-					                                        : 1u + (4u << RS) + (unsigned)(t - st0);
-					if (h > bh || (h == bh && rank < bk)) bh = h, bk = rank;
-				}
+				int bh; unsigned bk;
+				gen_exact_h_partial<RS>(I, k, st0, en0, h_en0, tid, NT, bh, bk);
 				const int wm = wave_max_i32(bh);
 				const unsigned wk = wave_min_u32(bh == wm ? bk : 0xffffffffu);
 				if (lane == 0) red_h[wave] = wm, red_k[wave] = wk;
 				__syncthreads();
 				max_H = red_h[0];
 				unsigned rk = red_k[0];
-				for (int k = 1; k < kDpHbmWaves; ++k) {
-					const int h = red_h[k];
-					if (h > max_H) max_H = h, rk = red_k[k];
-					else if (h == max_H) rk = min(rk, red_k[k]);
+				for (int j = 1; j < kDpHbmWaves; ++j) {
+					const int h = red_h[j];
+					if (h > max_H) max_H = h, rk = red_k[j];
+					else if (h == max_H) rk = min(rk, red_k[j]);
 				}
-				max_t = rk == 0 ? en0 : st0 + (int)((rk - 1u) & ((1u << RS) - 1u));
+				max_t = dp_rank_col<RS>(rk, st0, en0);
 			} else {
-				int h0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe;
-				if (tid == 0) H[0] = h0;
+				const int h0 = I.h_first(k, P);
+				if (tid == 0) I.H[0] = h0;
 				max_H = h0, max_t = 0;
 			}
 			__syncthreads();
-			const int H_en0 = H[en0], H_st0 = H[st0];
-			if (en0 == tlen - 1 && H_en0 > ez.mte) ez.mte = H_en0, ez.mte_q = r - en;
-			if (r - st0 == qlen - 1 && H_st0 > ez.mqe) ez.mqe = H_st0, ez.mqe_t = st0;
-			if (ez.apply_zdrop(max_H, r, max_t, P.zdrop, e_drop)) break;
-			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H_en0;
-		} else {
-			const int bias = VAR == 0 ? 0 : qe;
-			if (r > 0) {
-				if (last_H0_t >= st0 && last_H0_t <= en0 && last_H0_t + 1 >= st0 && last_H0_t + 1 <= en0) {
-					int d0 = (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
-					int d1 = (VAR == 0 ? (int)u8[last_H0_t + 1] : (int)(uint8_t)u8[last_H0_t + 1]) - bias;
-					if (d0 > d1) H0 += d0;
-					else H0 += d1, ++last_H0_t;
-				} else if (last_H0_t >= st0 && last_H0_t <= en0) {
-					H0 += (VAR == 0 ? (int)v8[last_H0_t] : (int)(uint8_t)v8[last_H0_t]) - bias;
-				} else {
-					++last_H0_t, H0 += (VAR == 0 ? (int)u8[last_H0_t] : (int)(uint8_t)u8[last_H0_t]) - bias;
-				}
-				if (VAR == 1 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
-			} else H0 = VAR == 0 ? (int)v8[0] - P.qe_pre : (int)(uint8_t)v8[0] - qe - qe, last_H0_t = 0;
-			if (VAR == 0 && (flag & PSVR_EZ_APPROX_DROP) && ez.apply_zdrop(H0, r, last_H0_t, P.zdrop, e_drop)) break;
-			if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = H0;
-		}
+			if (ez.end_diagonal(r, qlen, tlen, st0, en0, I.H[st0], I.H[en0], max_H, max_t, P.zdrop, VAR == 0 ? P.e2 : P.e)) break;
+		} else if (gen_approx_step<VAR>(I, k, P, ez, r, qlen, tlen, st0, en0, H0, last_H0_t)) break;
 		last_st = st, last_en = en;
 	}
 	// the traceback is one uniform walk: the first wavefront alone
 	if (wave != 0) return;
 	int n_cigar = 0;
-	if (with_cigar) {
+	if (k.with_cigar) {
 		__threadfence_block();
-		int i0 = -1, j0 = -1;
-		if (!ez.zdropped && !(flag & PSVR_EZ_EXTZ_ONLY)) i0 = tlen - 1, j0 = qlen - 1;
-		else if (!ez.zdropped && (flag & PSVR_EZ_EXTZ_ONLY) && ez.mqe + P.end_bonus > ez.max) ez.reach_end = 1, i0 = ez.mqe_t, j0 = qlen - 1;
-		else if (ez.max_t >= 0 && ez.max_q >= 0) i0 = ez.max_t, j0 = ez.max_q;
-		if (i0 >= 0 && j0 >= 0) {
+		int i0, j0;
+		if (trace_start(ez, P, qlen, tlen, i0, j0)) {
 			uint32_t *dst = B.cigar + uni64(out->cigar_off);
 			n_cigar = traceback(i0, j0, qlen, tlen, w,
-				[&](int r, int k) { return (int)__builtin_nontemporal_load(Pm + r * rowb + k); },
-				[&](int k, uint32_t word) { if (lane == 0) dst[k] = word; });
-			if (!(flag & PSVR_EZ_REV_CIGAR)) {
+				[&](int r, int j) { return (int)__builtin_nontemporal_load(Pm + r * rowb + j); },
+				[&](int j, uint32_t word) { if (lane == 0) dst[j] = word; });
+			if (!(P.flag & PSVR_EZ_REV_CIGAR)) {
 				__threadfence_block();
 				__builtin_amdgcn_wave_barrier();
-				for (int m = lane; m < (n_cigar >> 1); m += 64) {
-					uint32_t a = __builtin_nontemporal_load(dst + m), b = __builtin_nontemporal_load(dst + n_cigar - 1 - m);
-					dst[m] = b, dst[n_cigar - 1 - m] = a;
-				}
+				cigar_reverse_in_place(dst, n_cigar, lane);
 			}
 		}
 	}

@@ -17,24 +17,26 @@ inline const char *dp_kind_name(int kind, int variant)
 	return n[kind];
 }
 
-inline void dp_launch_kind(int kind, int variant, unsigned count, int lds, hipStream_t stream, const DpBatch &B0, const DpParams &P)
+// (kinds 3..5, extd2_reg_kernel<3..5,lds>, have no kernel: 129 target columns already need more direction bytes than PSVR_DP_PG_THRESHOLD,
+// so no planner produces them; one that did would be an internal error)
+inline hipError_t dp_launch_kind(int kind, int variant, unsigned count, int lds, hipStream_t stream, const DpBatch &B0, const DpParams &P)
 {
 	DpBatch B = B0;
 	B.n = count, B.lds_per_wave = lds;
 	if (kind == PSVR_DP_KIND_TINY) {        // `lds` is the size bin: 512 bytes per anti-diagonal
 		const int max_rows = lds / 512;
 		hipLaunchKernelGGL(extd2_tiny_kernel, dim3((count + 63) / 64), dim3(64), (size_t)8192 + (size_t)max_rows * 1024, stream, B, P, max_rows);
-		return;
+		return hipSuccess;
 	}
 	if (kind == PSVR_DP_KIND_RING1_3 || kind == PSVR_DP_KIND_RING1_4) {   // a workgroup per alignment
 		if (kind == PSVR_DP_KIND_RING1_3) hipLaunchKernelGGL(extd2_ring1_kernel<3>, dim3(count), dim3(64), lds, stream, B, P);
 		else hipLaunchKernelGGL(extd2_ring1_kernel<4>, dim3(count), dim3(64), lds, stream, B, P);
-		return;
+		return hipSuccess;
 	}
 	if (kind == PSVR_DP_KIND_HBM) {
 		if (variant == 0) hipLaunchKernelGGL(extd2_hbm_kernel<0>, dim3(count), dim3(64 * kDpHbmWaves), 0, stream, B, P);
 		else hipLaunchKernelGGL(extd2_hbm_kernel<1>, dim3(count), dim3(64 * kDpHbmWaves), 0, stream, B, P);
-		return;
+		return hipSuccess;
 	}
 	const bool reg = kind >= 1;
 	dim3 g(reg ? (count + kDpWaves - 1) / kDpWaves : count), b(reg ? 64 * kDpWaves : 64);
@@ -42,9 +44,7 @@ inline void dp_launch_kind(int kind, int variant, unsigned count, int lds, hipSt
 	switch (kind) {
 	case 1: hipLaunchKernelGGL((extd2_reg_kernel<1, false>), g, b, lds, stream, B, P); break;
 	case 2: hipLaunchKernelGGL((extd2_reg_kernel<2, false>), g, b, lds, stream, B, P); break;
-	case 3: hipLaunchKernelGGL((extd2_reg_kernel<3, false>), g, b, lds, stream, B, P); break;
-	case 4: hipLaunchKernelGGL((extd2_reg_kernel<4, false>), g, b, lds, stream, B, P); break;
-	case 5: hipLaunchKernelGGL((extd2_reg_kernel<5, false>), g, b, lds, stream, B, P); break;
+	case 3: case 4: case 5: return hipErrorInvalidDeviceFunction;
 	case 6: hipLaunchKernelGGL((extd2_reg_kernel<1, true>), g, b, lds, stream, B, P); break;
 	case 7: hipLaunchKernelGGL((extd2_reg_kernel<2, true>), g, b, lds, stream, B, P); break;
 	case 8: hipLaunchKernelGGL((extd2_reg_kernel<3, true>), g, b, lds, stream, B, P); break;
@@ -56,6 +56,7 @@ inline void dp_launch_kind(int kind, int variant, unsigned count, int lds, hipSt
 		if (variant == 0) hipLaunchKernelGGL(extd2_lds_kernel<0>, g, b, lds, stream, B, P);
 		else hipLaunchKernelGGL(extd2_lds_kernel<1>, g, b, lds, stream, B, P);
 	}
+	return hipSuccess;
 }
 
 // the team kernel: every class in one launch (largest classes first, their wavefronts run longest), then the launch that turns what
@@ -104,8 +105,7 @@ inline hipError_t dp_allow_big_lds()
 {
 	hipError_t e = hipSuccess;
 #define PSVR_ATTR(k) do { hipError_t x = hipFuncSetAttribute((const void *)(k), hipFuncAttributeMaxDynamicSharedMemorySize, PSVR_DP_MAX_LDS); if (x != hipSuccess) e = x; } while (0)
-	PSVR_ATTR((extd2_reg_kernel<1, false>)); PSVR_ATTR((extd2_reg_kernel<2, false>)); PSVR_ATTR((extd2_reg_kernel<3, false>));
-	PSVR_ATTR((extd2_reg_kernel<4, false>)); PSVR_ATTR((extd2_reg_kernel<5, false>));
+	PSVR_ATTR((extd2_reg_kernel<1, false>)); PSVR_ATTR((extd2_reg_kernel<2, false>));
 	PSVR_ATTR(extd2_lds_kernel<0>); PSVR_ATTR(extd2_lds_kernel<1>); PSVR_ATTR(extd2_ring_kernel<3>); PSVR_ATTR(extd2_ring_kernel<4>);
 	PSVR_ATTR(extd2_ring1_kernel<3>); PSVR_ATTR(extd2_ring1_kernel<4>);
 #undef PSVR_ATTR
