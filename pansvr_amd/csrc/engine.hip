@@ -925,77 +925,202 @@ __global__ void k_scatter_u8(uint8_t *a, const int32_t *idx, long long n, uint8_
 }
 
 // ---- DP planning on the device ---------------------------------------------------------------
+// A round's DP stage is planned behind k_walk without the host: k_dp_plan reads the number of queued problems from the queue's counter,
+// classifies them, counts the buckets (dp_plan_bucket, engine_core.h) and hands out the sequence / slab / CIGAR ranges; k_dp_plan_starts
+// (one workgroup) turns the counts into bucket starts and writes the round's plan record, the one thing the host reads before it
+// launches the DP kernels; k_dp_scatter and k_dp_fetch place the problem ids and the sequences while the host reads it.
+static_assert(kDpPlanClasses == PSVR_DP_NUM_LDS_CLASSES && kDpPlanKinds == PSVR_DP_NUM_KINDS && kDpPlanTeamKind == PSVR_DP_KIND_STRIP, "engine_core.h's launch order follows ksw_device.h");
+struct DpPlanRec {                 // the plan record: one contiguous readback
+	unsigned long long dp_top, cw_top;       // the queue counters the round ended with
+	unsigned long long n;                    // DP problems of this round (0 when an arena overflowed)
+	unsigned long long verdict;              // 0: placed; kDpGrow* bits: that buffer is too small, nothing was placed; kDpFull: an arena overflowed
+	unsigned long long tot_q, tot_t, tot_p, tot_c, ws_bytes, seq_bytes;   // bytes of the padded sequences, slab units of 256 B, CIGAR words, team scratch, query + target bases
+	unsigned long long pad[6];
+	int32_t flags[16];
+	unsigned long long team_cnt[16], qmax[16];                            // per team-kernel class: problems, longest query
+	unsigned long long cnt[kDpPlanTeam0];                                 // per (kind, class) of the wavefront / tiny kernels
+};
+enum { kDpGrowN = 1, kDpGrowQ = 2, kDpGrowT = 4, kDpGrowC = 8, kDpGrowSlab = 16, kDpGrowWs = 32, kDpFull = 64 };
+struct DpPlanWork {                // zeroed before every plan
+	unsigned int hist[kDpPlanBuckets];       // problems per bucket
+	unsigned int cursor[kDpPlanBuckets];     // bucket start + ids placed so far
+	unsigned long long qmax[16];             // longest query per team-kernel class
+	unsigned long long alloc[4];             // bump counters: query bytes, target bytes, slab units, CIGAR words
+	unsigned long long seq_bytes;
+	DpPlanRec rec;
+};
+struct DpCaps { long long n, q, t, c, slab, ws; };   // what the DP stage's buffers hold: problems, query / target bytes, CIGAR words, slab and scratch bytes
 struct DpPlanDev {
-	const DpDesc *desc; long long n;
-	int32_t *qlen, *tlen; long long *q_off, *t_off, *p_off;
-	int32_t *qpad, *tpad;          // the lengths rounded up to 16: every sequence starts on a 16-byte boundary of its buffer (k_dp_fetch stores 16 bases at a time)
-	int32_t *plen;                 // padded direction-byte bytes for general-kernel problems (0 otherwise), as int32 units of 256 B
+	DpPlanWork *wk;
+	int32_t *qlen, *tlen; long long *q_off, *t_off, *p_off;    // the sequences start on 16-byte boundaries of their buffers (k_dp_fetch stores 16 bases at a time)
 	int32_t *bucket;               // bucket id per problem
-	unsigned long long *hist;      // [512] counts, [512] cursors, then [16] the longest query per team-kernel class + [1] the scratch top
 	int32_t *idx;
 	psvr_extz_t *ez;
 };
-// bucket ids: kind * 13 + class for the wavefront / tiny kernels (< 256); the team kernel's problems are additionally binned by
-// query length inside their class (256 + class * 16 + (qlen - 1) / 16), so that the 16 alignments of a wavefront have similar
-// numbers of steps per strip
-__device__ __forceinline__ int dp_bucket_of(int kind, int cls, int qlen)
+// the problems of the round that began at dp_done; none when an arena has overflowed in the stages so far (the host ends the round then:
+// descriptors may be missing, and the counter may stand beyond the capacity)
+__device__ __forceinline__ long long dp_round_n(const Ctx &c, long long dp_done, bool &full)
 {
-	if (kind == PSVR_DP_KIND_STRIP) { int qb = (qlen - 1) >> 4; return 256 + cls * 16 + (qb > 15 ? 15 : qb); }
-	return (kind < 0 ? 0 : kind) * PSVR_DP_NUM_LDS_CLASSES + cls;
+	const unsigned long long top = *c.dp.top, cw = *c.cw.top;
+	const int *fl = c.mem.overflow;                              // the flag words: mem, us, seg, dp, cw
+	full = top > c.dp.cap || cw > c.cw.cap || fl[0] || fl[1] || fl[2] || fl[3] || fl[4];
+	return full || (long long)top <= dp_done ? 0 : (long long)top - dp_done;
 }
-__global__ __launch_bounds__(kBlock) void k_dp_lens(DpPlanDev d, int w, int tiny_ok, int team_ok)
+static const int kDpPlanGrid = 1024;       // workgroups of k_dp_plan and k_dp_scatter, whatever the round holds
+static const int kDpFetchGrid = 4096;      // ... of k_dp_fetch
+__global__ __launch_bounds__(kBlock) void k_dp_plan(Ctx c, long long dp_done, DpPlanDev d, DpCaps cap, int w, int tiny_ok, long long team_min)
 {
-	__shared__ unsigned int lh[512];
+	__shared__ unsigned int lh[kDpPlanBuckets];
 	__shared__ unsigned int lq[PSVR_DP_NUM_LDS_CLASSES];       // longest query per team-kernel class, aggregated per block
-	lh[threadIdx.x] = 0, lh[threadIdx.x + 256] = 0;
+	__shared__ unsigned int wsum[4][kBlock / 64];
+	__shared__ unsigned long long base[4];
+	__shared__ unsigned int lbytes;
+	bool full;
+	const long long n = dp_round_n(c, dp_done, full);
+	if (n + 2 > cap.n || blockIdx.x * (long long)kBlock >= n) return;     // (too many for the per-problem arrays: k_dp_plan_starts says so)
+	for (int t = threadIdx.x; t < kDpPlanBuckets; t += kBlock) lh[t] = 0;
 	if (threadIdx.x < PSVR_DP_NUM_LDS_CLASSES) lq[threadIdx.x] = 0;
+	if (threadIdx.x == 0) lbytes = 0;
 	__syncthreads();
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	unsigned int seq_bytes = 0;                                  // query + target bytes of this thread's problem (summed per block into hist[1041])
-	if (i == 0) d.qlen[d.n] = d.tlen[d.n] = d.plen[d.n] = d.qpad[d.n] = d.tpad[d.n] = 0;      // the scans run over n + 1 entries
-	if (i < d.n) {
-		const DpDesc &x = d.desc[i];
-		d.qlen[i] = x.qlen, d.tlen[i] = x.tlen;
-		d.qpad[i] = (x.qlen + 15) & ~15, d.tpad[i] = (x.tlen + 15) & ~15;
-		seq_bytes = (unsigned int)(x.qlen + x.tlen);
-		int need;
-		int kind = dp_classify(x.qlen, x.tlen, w, true, 0, false, &need, tiny_ok != 0, team_ok != 0);
-		int cls = 0;
-		while (cls < PSVR_DP_NUM_LDS_CLASSES - 1 && dp_lds_class_bytes(cls) < need) ++cls;
-		d.plen[i] = dp_kind_uses_slab(kind) ? (int32_t)((dp_p_bytes(x.qlen, x.tlen, w) + 255) >> 8) : 0;
-		const int b = dp_bucket_of(kind, cls, x.qlen);
-		d.bucket[i] = b;
-		if (kind == PSVR_DP_KIND_STRIP) atomicMax(&lq[cls], (unsigned int)x.qlen);
-		atomicAdd(&lh[b], 1u);
+	const DpDesc *desc = c.dp.base + dp_done;
+	const int team_ok = n >= team_min;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	unsigned int seq_bytes = 0;                                  // query + target bytes of this thread's problems
+	for (long long i0 = blockIdx.x * (long long)kBlock; i0 < n; i0 += (long long)gridDim.x * kBlock) {
+		const long long i = i0 + threadIdx.x;
+		unsigned int v[4] = {0, 0, 0, 0};                         // what the problem needs: padded query, padded target, slab units, CIGAR words
+		if (i < n) {
+			const DpDesc &x = desc[i];
+			d.qlen[i] = x.qlen, d.tlen[i] = x.tlen;
+			v[0] = (unsigned int)((x.qlen + 15) & ~15), v[1] = (unsigned int)((x.tlen + 15) & ~15);
+			seq_bytes += (unsigned int)(x.qlen + x.tlen);
+			int need;
+			const int kind = dp_classify(x.qlen, x.tlen, w, true, 0, false, &need, tiny_ok != 0, team_ok != 0);
+			int cls = 0;
+			while (cls < PSVR_DP_NUM_LDS_CLASSES - 1 && dp_lds_class_bytes(cls) < need) ++cls;
+			v[2] = dp_kind_uses_slab(kind) ? (unsigned int)((dp_p_bytes(x.qlen, x.tlen, w) + 255) >> 8) : 0;
+			v[3] = v[0] + v[1] + 2;
+			const int b = dp_plan_bucket(kind, cls, x.qlen);
+			d.bucket[i] = b;
+			if (kind == PSVR_DP_KIND_STRIP) atomicMax(&lq[cls], (unsigned int)x.qlen);
+			atomicAdd(&lh[b], 1u);
+		}
+		// ranges by any scheme that keeps them disjoint: a prefix inside the workgroup, one bump per workgroup and quantity
+		unsigned int inc[4];
+		for (int k = 0; k < 4; ++k) {
+			unsigned int s = v[k];
+			for (int o = 1; o < 64; o <<= 1) { const unsigned int t = __shfl_up(s, o); if (lane >= o) s += t; }
+			inc[k] = s;
+			if (lane == 63) wsum[k][wave] = s;
+		}
+		__syncthreads();
+		if (threadIdx.x < 4) {
+			unsigned long long tot = 0;
+			for (int q = 0; q < kBlock / 64; ++q) tot += wsum[threadIdx.x][q];
+			base[threadIdx.x] = tot ? atomicAdd(d.wk->alloc + threadIdx.x, tot) : 0;
+		}
+		__syncthreads();
+		if (i < n) {
+			unsigned long long o[4];
+			for (int k = 0; k < 4; ++k) {
+				o[k] = base[k] + inc[k] - v[k];
+				for (int q = 0; q < wave; ++q) o[k] += wsum[k][q];
+			}
+			d.q_off[i] = (long long)o[0], d.t_off[i] = (long long)o[1], d.p_off[i] = (long long)o[2];
+			d.ez[i].cigar_off = (long long)o[3];
+		}
+		__syncthreads();                                           // wsum and base are free again
 	}
-	__syncthreads();
-	for (int t = threadIdx.x; t < 512; t += 256) if (lh[t]) atomicAdd(d.hist + t, (unsigned long long)lh[t]);
-	if (threadIdx.x < PSVR_DP_NUM_LDS_CLASSES && lq[threadIdx.x]) atomicMax(d.hist + 1024 + threadIdx.x, (unsigned long long)lq[threadIdx.x]);
-	// (one atomic per workgroup, through LDS: 11 k wavefronts on one address were 0.1 ms of this kernel)
+	for (int t = threadIdx.x; t < kDpPlanBuckets; t += kBlock) if (lh[t]) atomicAdd(d.wk->hist + t, lh[t]);
+	if (threadIdx.x < PSVR_DP_NUM_LDS_CLASSES && lq[threadIdx.x]) atomicMax(d.wk->qmax + threadIdx.x, (unsigned long long)lq[threadIdx.x]);
+	// (one atomic per workgroup, through LDS: thousands of wavefronts on one address were 0.1 ms of the planning)
 	for (int o = 32; o; o >>= 1) seq_bytes += __shfl_xor(seq_bytes, o);
-	__syncthreads();                                              // lh is free again
-	if (threadIdx.x == 0) lh[0] = 0;
+	if (lane == 0 && seq_bytes) atomicAdd(&lbytes, seq_bytes);
 	__syncthreads();
-	if ((threadIdx.x & 63) == 0 && seq_bytes) atomicAdd(&lh[0], seq_bytes);
-	__syncthreads();
-	if (threadIdx.x == 0 && lh[0]) atomicAdd(d.hist + 1041, (unsigned long long)lh[0]);
+	if (threadIdx.x == 0 && lbytes) atomicAdd(&d.wk->seq_bytes, (unsigned long long)lbytes);
 }
-__global__ __launch_bounds__(kBlock) void k_dp_scatter(DpPlanDev d, const long long *bucket_start)
+// one workgroup: bucket counts -> bucket starts in launch order (dp_plan_slot_bucket), the totals, the verdict on the buffers' capacities
+__global__ __launch_bounds__(kBlock) void k_dp_plan_starts(Ctx c, long long dp_done, DpPlanDev d, DpCaps cap)
 {
-	__shared__ unsigned int lh[512];
-	__shared__ unsigned long long lb[512];
-	lh[threadIdx.x] = 0, lh[threadIdx.x + 256] = 0;
+	__shared__ unsigned int lh[kDpPlanBuckets];
+	__shared__ unsigned int part[kBlock];
+	__shared__ unsigned long long team_cnt[PSVR_DP_NUM_LDS_CLASSES];
+	DpPlanWork &wk = *d.wk;
+	bool full;
+	const long long n = dp_round_n(c, dp_done, full);
+	for (int t = threadIdx.x; t < kDpPlanBuckets; t += kBlock) lh[t] = wk.hist[t];
 	__syncthreads();
-	long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-	int b = 0;
-	unsigned int me = 0;
-	if (i < d.n) { b = d.bucket[i]; me = atomicAdd(&lh[b], 1u); }
+	constexpr int per = (kDpPlanSlots + kBlock - 1) / kBlock;
+	unsigned int v[per], s = 0;
+	for (int k = 0; k < per; ++k) {
+		const int slot = threadIdx.x * per + k;
+		v[k] = slot < kDpPlanSlots ? lh[dp_plan_slot_bucket(slot)] : 0;
+		s += v[k];
+	}
+	part[threadIdx.x] = s;
 	__syncthreads();
-	for (int t = threadIdx.x; t < 512; t += 256) if (lh[t]) lb[t] = atomicAdd(d.hist + 512 + t, (unsigned long long)lh[t]);
+	for (int o = 1; o < kBlock; o <<= 1) {
+		const unsigned int t = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0;
+		__syncthreads();
+		part[threadIdx.x] += t;
+		__syncthreads();
+	}
+	unsigned int run = part[threadIdx.x] - s;
+	for (int k = 0; k < per; ++k) {
+		const int slot = threadIdx.x * per + k;
+		if (slot < kDpPlanSlots) wk.cursor[dp_plan_slot_bucket(slot)] = run;
+		run += v[k];
+	}
+	for (int t = threadIdx.x; t < kDpPlanTeam0; t += kBlock) wk.rec.cnt[t] = lh[t];
+	if (threadIdx.x < PSVR_DP_NUM_LDS_CLASSES) {
+		unsigned long long tc = 0;
+		for (int q = 0; q < kDpPlanQBins; ++q) tc += lh[kDpPlanTeam0 + threadIdx.x * kDpPlanQBins + q];
+		team_cnt[threadIdx.x] = tc;
+		wk.rec.team_cnt[threadIdx.x] = tc, wk.rec.qmax[threadIdx.x] = wk.qmax[threadIdx.x];
+	}
+	if (threadIdx.x < 16) wk.rec.flags[threadIdx.x] = c.mem.overflow[threadIdx.x];
 	__syncthreads();
-	if (i < d.n) {
-		d.idx[bucket_start[b] + lb[b] + me] = (int32_t)i;
-		d.ez[i].cigar_off = d.q_off[i] + d.t_off[i] + 2 * i;
+	if (threadIdx.x == 0) {
+		// scratch of the team kernel: a wavefront's slice is sized by its class's longest query (TeamLaunch::add, the same clamp)
+		unsigned long long ws = 0;
+		for (int cls = 0; cls < PSVR_DP_NUM_LDS_CLASSES; ++cls)
+			if (team_cnt[cls]) {
+				const int lanes = dp_team_lanes(cls + 1), qm = (int)wk.qmax[cls];
+				ws += (team_cnt[cls] * lanes + 63) / 64 * dp_team_ws_bytes(qm > 0 ? qm : 1, cls + 1, lanes);
+			}
+		DpPlanRec &r = wk.rec;
+		r.dp_top = *c.dp.top, r.cw_top = *c.cw.top, r.n = (unsigned long long)n;
+		r.tot_q = wk.alloc[0], r.tot_t = wk.alloc[1], r.tot_p = wk.alloc[2], r.tot_c = wk.alloc[3], r.ws_bytes = ws, r.seq_bytes = wk.seq_bytes;
+		unsigned long long verdict = full ? kDpFull : 0;
+		if (n + 2 > cap.n) verdict |= kDpGrowN;
+		if ((long long)r.tot_q + 64 > cap.q) verdict |= kDpGrowQ;
+		if ((long long)r.tot_t + 64 > cap.t) verdict |= kDpGrowT;
+		if ((long long)r.tot_c + 64 > cap.c) verdict |= kDpGrowC;
+		if ((long long)(r.tot_p << 8) + 256 > cap.slab) verdict |= kDpGrowSlab;
+		if ((long long)ws + 256 > cap.ws) verdict |= kDpGrowWs;
+		r.verdict = verdict;
+	}
+}
+// the problem ids, bucket by bucket: a workgroup counts its share of the problems per bucket, reserves a range in every bucket it
+// holds with one atomic, and places its ids there
+__global__ __launch_bounds__(kBlock) void k_dp_scatter(DpPlanDev d)
+{
+	__shared__ unsigned int lh[kDpPlanBuckets], lb[kDpPlanBuckets];
+	const DpPlanRec &r = d.wk->rec;
+	if (r.verdict) return;
+	const long long n = (long long)r.n;
+	const long long share = ((n + gridDim.x - 1) / gridDim.x + kBlock - 1) / kBlock * kBlock;
+	const long long lo = blockIdx.x * share, hi = lo + share < n ? lo + share : n;
+	if (lo >= n) return;
+	for (int t = threadIdx.x; t < kDpPlanBuckets; t += kBlock) lh[t] = 0;
+	__syncthreads();
+	for (long long i = lo + threadIdx.x; i < hi; i += kBlock) atomicAdd(&lh[d.bucket[i]], 1u);
+	__syncthreads();
+	for (int t = threadIdx.x; t < kDpPlanBuckets; t += kBlock) if (lh[t]) { lb[t] = atomicAdd(d.wk->cursor + t, lh[t]); lh[t] = 0; }
+	__syncthreads();
+	for (long long i = lo + threadIdx.x; i < hi; i += kBlock) {
+		const int b = d.bucket[i];
+		d.idx[lb[b] + atomicAdd(&lh[b], 1u)] = (int32_t)i;
 	}
 }
 // K5 ref_fetch: unpack the 2-bit reference window / slice the read for every queued DP problem (get_refseq + the reversal of left
@@ -1015,10 +1140,8 @@ __device__ __forceinline__ uint32_t rev_bases16(uint32_t w)         // the 16 2-
 	const uint32_t t = __builtin_bitreverse32(w);
 	return ((t >> 1) & 0x55555555u) | ((t & 0x55555555u) << 1);
 }
-__global__ __launch_bounds__(256) void k_dp_fetch(Ctx c, long long begin, long long np, const long long *q_off, const long long *t_off, uint8_t *qbuf, uint8_t *tbuf)
+__device__ __forceinline__ void dp_fetch_problem(const Ctx &c, long long begin, long long p, const long long *q_off, const long long *t_off, uint8_t *qbuf, uint8_t *tbuf)
 {
-	const long long p = blockIdx.x * 16ll + (threadIdx.x >> 4);
-	if (p >= np) return;
 	const DpDesc &x = c.dp.base[begin + p];
 	uint8_t *q = qbuf + q_off[p], *t = tbuf + t_off[p];
 	const int lane = threadIdx.x & 15;
@@ -1049,6 +1172,14 @@ __global__ __launch_bounds__(256) void k_dp_fetch(Ctx c, long long begin, long l
 		const int j = 16 * nt + lane;
 		if (j < x.tlen) t[j] = (uint8_t)base_at(c.idx.ref_seq, (uint64_t)x.ref_st + (rev ? x.tlen - 1 - j : j));
 	}
+}
+// The grid does not depend on the round: the number of problems comes from the plan record, and nothing is fetched when the plan's
+// verdict says that a buffer is too small (the host grows it and plans again).
+__global__ __launch_bounds__(256) void k_dp_fetch(Ctx c, long long begin, const DpPlanRec *rec, const long long *q_off, const long long *t_off, uint8_t *qbuf, uint8_t *tbuf)
+{
+	if (rec->verdict) return;
+	const long long np = (long long)rec->n;
+	for (long long p = blockIdx.x * 16ll + (threadIdx.x >> 4); p < np; p += gridDim.x * 16ll) dp_fetch_problem(c, begin, p, q_off, t_off, qbuf, tbuf);
 }
 
 // Streams kept per device for the engines of this process.  The first streams of a process each set up a hardware queue (3 - 14 ms a
@@ -1085,10 +1216,11 @@ struct GpuBE {
 	hipStream_t stream = nullptr;
 	hipError_t last = hipSuccess;
 	std::vector<std::pair<std::string, long long>> launches;   // for psvr_engine_stats
-	DevBuf plan_bucket, plan_hist, plan_idx, plan_poff, plan_plen, plan_bstart, plan_qpad, plan_tpad, pslab, strip_ws;
+	DevBuf plan_bucket, plan_work, plan_idx, plan_poff, pslab, strip_ws;
 	DpParams dpP;
 	bool dp_ready = false, dp_lean = false;
 	static constexpr long long kTeamMinProblems = 32768;       // below this a round's DP problems go to the wavefront-per-alignment kernels
+	static constexpr int kTinySmallLds = 4096;                 // tiny-kernel classes up to this (8 anti-diagonals) share a launch, the larger ones another
 	static constexpr int kSide = 3;                            // side streams: the DP kernels of a round are independent of each other
 	int device = -1;                                           // (for the stream pool)
 	hipStream_t side[kSide] = {};
@@ -1262,6 +1394,7 @@ struct GpuBE {
 		if (pin) (void)hipHostFree(pin);
 		if (up_ring) (void)hipHostFree(up_ring);
 		if (ev_early) (void)hipEventDestroy(ev_early);
+		if (ev_plan) (void)hipEventDestroy(ev_plan);
 		for (int i = 0; i < kSide; ++i) {
 			stream_pool().put(device, side[i]);
 			if (ev_join[i]) (void)hipEventDestroy(ev_join[i]);
@@ -1465,14 +1598,6 @@ struct GpuBE {
 		S.cnt[0] = cnt, S.out[0] = out, S.stride[0] = stride, S.off[0] = off, S.base[0] = base;
 		st_scan_set(S, 1, n);
 	}
-	// the same scan over three arrays of one length, in the same three launches
-	void st_scan3(const int32_t *c0, long long *o0, const int32_t *c1, long long *o1, const int32_t *c2, long long *o2, long long n)
-	{
-		ScanSet S = {};
-		S.cnt[0] = c0, S.out[0] = o0, S.cnt[1] = c1, S.out[1] = o1, S.cnt[2] = c2, S.out[2] = o2;
-		for (int k = 0; k < 3; ++k) S.stride[k] = 1;
-		st_scan_set(S, 3, n);
-	}
 	void st_mask_totals(const int32_t *ctot, const uint8_t *mask, long long n, int32_t *out)
 	{
 		if (n > 0) hipLaunchKernelGGL(k_mask_totals, dim3(grid_for(n)), dim3(kBlock), 0, stream, ctot, mask, n, out);
@@ -1493,85 +1618,107 @@ struct GpuBE {
 		note(hipGetLastError());
 	}
 
-	// queue -> lens -> offsets -> byte sequences -> size classes -> one DP launch per class
+	// ---- the DP stage: planned and placed on the device behind the walk (st_dp_plan), launched from the plan record (st_dp)
+	static constexpr bool kDevicePlan = true;                  // (EngineCore::run_slots: the queue tops and flags come with the plan)
+	DpPlanRec plan_rec;                                        // the round's plan, as read back
+	hipEvent_t ev_plan = nullptr;
+	int dp_init(const Ctx &c)
+	{
+		if (dp_ready) return PSVR_OK;
+		psvr_ksw_params_t kp;
+		memset(&kp, 0, sizeof kp);
+		kp.m = 5;
+		memcpy(kp.mat, c.mat, 25);
+		kp.q = (int8_t)c.par.gap_open, kp.e = (int8_t)c.par.gap_ex, kp.q2 = (int8_t)c.par.gap_open2, kp.e2 = (int8_t)c.par.gap_ex2;
+		kp.w = 200, kp.zdrop = c.par.zdrop, kp.end_bonus = -1, kp.flag = 0;   // KSW_ALN_handler::copy_option, rr.cpp:817-827 (bandwith = 200)
+		int rc = make_dp_params(&kp, 0, &dpP);
+		if (rc) return rc;
+		note(dp_allow_big_lds());
+		// the engine reads score, mqe and the CIGAR of its pieces, never ez.max / max_q / max_t: when the z-drop rule cannot trigger for these
+		// scoring parameters (the reference's defaults), the team kernel runs without the per-diagonal maximum
+		dp_lean = dp_zdrop_inert(dpP);
+		dp_ready = true;
+		return PSVR_OK;
+	}
+	// Queued behind k_walk with no synchronisation: the plan pass, the one-workgroup pass, the copy of the plan record (an event behind it),
+	// the placement (k_dp_scatter, k_dp_fetch).  The host waits for the event only -- the round's one wait between the walk and the DP
+	// launches -- and builds the launches from the record while the placement runs.  A buffer that is too small (an engine's first
+	// batches) is in the record's verdict: the placement has done nothing then, the host grows what is needed and plans again.
+	template <class Core> int st_dp_plan(Core &core, long long dp_done, long long &dp_end, long long &cw_end, int32_t *fl)
+	{
+		const Ctx &c = core.c;
+		DpIO &d = core.dp;
+		int rc = dp_init(c);
+		if (rc) return rc;
+		if (!ev_plan) PSVR_HIP(hipEventCreateWithFlags(&ev_plan, hipEventDisableTiming));
+		if (!pinned()) return set_error(PSVR_ERR_NOMEM, "page-locked staging buffer");
+		PSVR_HIP(plan_work.ensure(sizeof(DpPlanWork)));
+		for (int attempt = 0;; ++attempt) {
+			if (!core.ensure_dp(0, 0, 0, 0)) return set_error(PSVR_ERR_NOMEM, "DP buffers");
+			const long long cn = core.dp_cap_n;
+			PSVR_HIP(plan_bucket.ensure(cn * 4)); PSVR_HIP(plan_idx.ensure(cn * 4)); PSVR_HIP(plan_poff.ensure(cn * 8));
+			PSVR_HIP(pslab.ensure(256)); PSVR_HIP(strip_ws.ensure(256));
+			DpPlanDev pd;
+			pd.wk = plan_work.as<DpPlanWork>();
+			pd.qlen = d.qlen, pd.tlen = d.tlen, pd.q_off = d.q_off, pd.t_off = d.t_off, pd.p_off = plan_poff.as<long long>();
+			pd.bucket = plan_bucket.as<int32_t>(), pd.idx = plan_idx.as<int32_t>(), pd.ez = d.ez;
+			const DpCaps cap = {cn, core.dp_cap_q, core.dp_cap_t, core.dp_cap_c, (long long)pslab.bytes, (long long)strip_ws.bytes};
+			PSVR_HIP(hipMemsetAsync(plan_work.p, 0, sizeof(DpPlanWork), stream));
+			// a round with few problems (the re-runs after the first) cannot fill the chip at 32 alignments per wavefront: its time would be one
+			// wavefront's strips x (qlen + 15) steps; a wavefront per alignment needs qlen + tlen steps (the plan pass decides: it knows n)
+			hipLaunchKernelGGL(k_dp_plan, dim3(kDpPlanGrid), dim3(kBlock), 0, stream, c, dp_done, pd, cap, 200, dp_tiny_ok(dpP, true) ? 1 : 0, kTeamMinProblems);
+			hipLaunchKernelGGL(k_dp_plan_starts, dim3(1), dim3(kBlock), 0, stream, c, dp_done, pd, cap);
+			PSVR_HIP(hipMemcpyAsync(pin, &pd.wk->rec, sizeof(DpPlanRec), hipMemcpyDeviceToHost, stream));
+			PSVR_HIP(hipEventRecord(ev_plan, stream));
+			t0("k_dp_fetch");
+			hipLaunchKernelGGL(k_dp_scatter, dim3(kDpPlanGrid), dim3(kBlock), 0, stream, pd);
+			hipLaunchKernelGGL(k_dp_fetch, dim3(kDpFetchGrid), dim3(256), 0, stream, c, dp_done, (const DpPlanRec *)&pd.wk->rec, (const long long *)d.q_off, (const long long *)d.t_off, d.qbuf, d.tbuf);
+			t1();
+			PSVR_HIP(hipGetLastError());
+			if (!note(hipEventSynchronize(ev_plan))) return set_error(PSVR_ERR_DEVICE, "DP plan readback: %s", hipGetErrorString(last));
+			memcpy(&plan_rec, pin, sizeof plan_rec);
+			const DpPlanRec &r = plan_rec;
+			const int grow = (int)(r.verdict & ~(unsigned long long)kDpFull);
+			if ((r.verdict & kDpFull) || !grow) break;
+			if (attempt >= 4) return set_error(PSVR_ERR_DEVICE, "DP plan: buffers still too small after growing (verdict %d)", grow);
+			// (the placement has done nothing; the growth frees buffers, which waits for the device)
+			if (!core.ensure_dp((long long)r.n, (long long)r.tot_q, (long long)r.tot_t, (long long)r.tot_c)) return set_error(PSVR_ERR_NOMEM, "DP sequence buffers");
+			PSVR_HIP(pslab.ensure((size_t)(r.tot_p << 8) + 256));
+			PSVR_HIP(strip_ws.ensure((size_t)r.ws_bytes + 256));
+		}
+		memcpy(fl, plan_rec.flags, 64);
+		dp_end = (long long)plan_rec.dp_top, cw_end = (long long)plan_rec.cw_top;
+		return PSVR_OK;
+	}
+	// the DP launches of the round st_dp_plan has planned
 	template <class Core> int st_dp(Core &core)
 	{
 		const Ctx &c = core.c;
 		DpIO &d = core.dp;
-		const long long n = d.end - d.begin;
-		if (!dp_ready) {
-			psvr_ksw_params_t kp;
-			memset(&kp, 0, sizeof kp);
-			kp.m = 5;
-			memcpy(kp.mat, c.mat, 25);
-			kp.q = (int8_t)c.par.gap_open, kp.e = (int8_t)c.par.gap_ex, kp.q2 = (int8_t)c.par.gap_open2, kp.e2 = (int8_t)c.par.gap_ex2;
-			kp.w = 200, kp.zdrop = c.par.zdrop, kp.end_bonus = -1, kp.flag = 0;   // KSW_ALN_handler::copy_option, rr.cpp:817-827 (bandwith = 200)
-			int rc = make_dp_params(&kp, 0, &dpP);
-			if (rc) return rc;
-			note(dp_allow_big_lds());
-			// the engine reads score, mqe and the CIGAR of its pieces, never ez.max / max_q / max_t: when the z-drop rule cannot trigger for these
-			// scoring parameters (the reference's defaults), the team kernel runs without the per-diagonal maximum
-			dp_lean = dp_zdrop_inert(dpP);
-			dp_ready = true;
-		}
-		// upper bounds for the sequence buffers: every problem has qlen, tlen < 1600; size from the actual lens
-		if (!core.ensure_dp(n, 0, 0, 0)) return set_error(PSVR_ERR_NOMEM, "DP buffers");
-		PSVR_HIP(plan_bucket.ensure(n * 4)); PSVR_HIP(plan_idx.ensure(n * 4)); PSVR_HIP(plan_plen.ensure((n + 1) * 4)); PSVR_HIP(plan_poff.ensure((n + 1) * 8));
-		PSVR_HIP(plan_qpad.ensure((n + 1) * 4)); PSVR_HIP(plan_tpad.ensure((n + 1) * 4));
-		PSVR_HIP(plan_hist.ensure(1056 * 8)); PSVR_HIP(plan_bstart.ensure(512 * 8));
-		PSVR_HIP(hipMemsetAsync(plan_hist.p, 0, 1056 * 8, stream));
-		DpPlanDev pd;
-		pd.desc = c.dp.base + d.begin, pd.n = n, pd.qlen = d.qlen, pd.tlen = d.tlen, pd.q_off = d.q_off, pd.t_off = d.t_off;
-		pd.p_off = plan_poff.as<long long>(), pd.plen = plan_plen.as<int32_t>(), pd.bucket = plan_bucket.as<int32_t>();
-		pd.hist = plan_hist.as<unsigned long long>(), pd.idx = plan_idx.as<int32_t>(), pd.ez = d.ez;
-		pd.qpad = plan_qpad.as<int32_t>(), pd.tpad = plan_tpad.as<int32_t>();
-		// a round with few problems (the re-runs after the first) cannot fill the chip at 16 alignments per wavefront: its time would be one
-		// wavefront's strips x (qlen + 15) steps; a wavefront per alignment needs qlen + tlen steps
-		hipLaunchKernelGGL(k_dp_lens, dim3(grid_for(n)), dim3(kBlock), 0, stream, pd, 200, dp_tiny_ok(dpP, true) ? 1 : 0, n >= kTeamMinProblems ? 1 : 0);
-		st_scan3((const int32_t *)pd.qpad, d.q_off, (const int32_t *)pd.tpad, d.t_off, (const int32_t *)pd.plen, pd.p_off, n + 1);
-		PSVR_HIP(hipGetLastError());
-		unsigned long long hist[512], qmax[18];                // qmax[17]: query + target bytes of the round's problems
-		long long tot[3];
-		if (!d2h({{hist, plan_hist.p, sizeof hist}, {qmax, plan_hist.as<char>() + 1024 * 8, sizeof qmax}, {&tot[0], d.q_off + n, 8}, {&tot[1], d.t_off + n, 8}, {&tot[2], pd.p_off + n, 8}}))
-			return set_error(PSVR_ERR_DEVICE, "DP plan readback: %s", hipGetErrorString(last));
-		// NB: the scans ran over n+1 entries, element n of qlen/tlen/plen is scratch: its value only lands in slot n+1 (never read)
-		core.stats.dp_seq_bytes += (long long)qmax[17];              // query + target bytes the DP launches of this round read (k_dp_lens sums them)
-		if (!core.ensure_dp(n, tot[0], tot[1], tot[0] + tot[1] + 2 * n)) return set_error(PSVR_ERR_NOMEM, "DP sequence buffers");
-		PSVR_HIP(pslab.ensure((size_t)(tot[2] << 8) + 256));
-		// scratch of the team kernel: a wavefront's slice starts at an offset computed from its class (TeamLaunch::add), sized by the class's
-		// longest query -- the same clamp (>= 1) as there
-		unsigned long long ws_bytes = 0, team_cnt[PSVR_DP_NUM_LDS_CLASSES];
-		for (int cls = 0; cls < PSVR_DP_NUM_LDS_CLASSES; ++cls) {
-			team_cnt[cls] = 0;
-			for (int qb = 0; qb < 16; ++qb) team_cnt[cls] += hist[256 + cls * 16 + qb];
-			if (team_cnt[cls]) { const int lanes = dp_team_lanes(cls + 1); ws_bytes += (team_cnt[cls] * lanes + 63) / 64 * dp_team_ws_bytes(qmax[cls] > 0 ? (int)qmax[cls] : 1, cls + 1, lanes); }
-		}
-		PSVR_HIP(strip_ws.ensure((size_t)ws_bytes + 256));
-		long long bstart[512], acc = 0;
-		memset(bstart, 0, sizeof bstart);
+		const DpPlanRec &r = plan_rec;
+		if (r.verdict || (long long)r.n != d.end - d.begin) return set_error(PSVR_ERR_DEVICE, "DP stage without a plan for its round");
+		core.stats.dp_seq_bytes += (long long)r.seq_bytes;           // query + target bytes the DP launches of this round read (k_dp_plan sums them)
+		const unsigned long long ws_bytes = r.ws_bytes;
+		// the launches in the order the ids were placed in (dp_plan_slot_bucket).  The tiny kernel's classes go out as two launches, each at
+		// the LDS size of its largest class: the two populous classes (up to 4 and up to 8 anti-diagonals) together at no more than 16 KB a
+		// block, the rest at up to 40 KB -- one launch per class was six launches of a few hundred wavefronts each, queued one behind the other
 		std::vector<Launch3> ls;
-		const int kind_order[PSVR_DP_NUM_KINDS - 1] = {0, 14, 13, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 11};
-		for (int ko = 0; ko < PSVR_DP_NUM_KINDS - 1; ++ko)
-			for (int cls = PSVR_DP_NUM_LDS_CLASSES - 1; cls >= 0; --cls) {
-				int b = kind_order[ko] * PSVR_DP_NUM_LDS_CLASSES + cls;
-				bstart[b] = acc;
-				if (hist[b]) ls.push_back(Launch3{kind_order[ko], dp_lds_class_bytes(cls), acc, (long long)hist[b]});
-				acc += (long long)hist[b];
-			}
-		// the team kernel's classes, longest first; inside a class the query-length bins in descending order
-		for (int cls = PSVR_DP_NUM_LDS_CLASSES - 1; cls >= 0; --cls) {
-			if (team_cnt[cls]) ls.push_back(Launch3{PSVR_DP_KIND_STRIP, dp_lds_class_bytes(cls), acc, (long long)team_cnt[cls]});
-			for (int qb = 15; qb >= 0; --qb) bstart[256 + cls * 16 + qb] = acc, acc += (long long)hist[256 + cls * 16 + qb];
+		long long acc = 0;
+		for (int k = 0; k < kDpPlanOtherSlots; ++k) {
+			const int b = dp_plan_slot_bucket(k), kind = b / PSVR_DP_NUM_LDS_CLASSES, cls = b % PSVR_DP_NUM_LDS_CLASSES;
+			const long long cnt = (long long)r.cnt[b];
+			if (!cnt) continue;
+			const bool joins = kind == PSVR_DP_KIND_TINY && !ls.empty() && ls.back().kind == kind && (ls.back().lds > kTinySmallLds) == (dp_lds_class_bytes(cls) > kTinySmallLds);
+			if (joins) ls.back().count += cnt;
+			else ls.push_back(Launch3{kind, dp_lds_class_bytes(cls), acc, cnt});
+			acc += cnt;
 		}
-		// no wait for this upload: the staging slot (last 4 KB of the pinned buffer) is not written again before the round's later synchronisations
-		if (pinned()) { memcpy((char *)pin + kPin - 4096, bstart, 512 * 8); PSVR_HIP(hipMemcpyAsync(plan_bstart.p, (char *)pin + kPin - 4096, 512 * 8, hipMemcpyHostToDevice, stream)); }
-		else h2d(plan_bstart.p, bstart, 512 * 8);
-		pd.qlen = d.qlen, pd.tlen = d.tlen, pd.q_off = d.q_off, pd.t_off = d.t_off, pd.ez = d.ez;
-		hipLaunchKernelGGL(k_dp_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, pd, (const long long *)plan_bstart.p);
-		t0("k_dp_fetch");
-		hipLaunchKernelGGL(k_dp_fetch, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, stream, c, d.begin, n, (const long long *)d.q_off, (const long long *)d.t_off, d.qbuf, d.tbuf);
-		t1();
-		PSVR_HIP(hipGetLastError());
+		// the team kernel's classes, longest first; inside a class the queries in descending order of length
+		for (int cls = PSVR_DP_NUM_LDS_CLASSES - 1; cls >= 0; --cls) {
+			if (r.team_cnt[cls]) ls.push_back(Launch3{PSVR_DP_KIND_STRIP, dp_lds_class_bytes(cls), acc, (long long)r.team_cnt[cls]});
+			acc += (long long)r.team_cnt[cls];
+		}
+		const unsigned long long *qmax = r.qmax;
 		DpBatch B;
 		B.qseq = d.qbuf, B.q_off = (const int64_t *)d.q_off, B.qlen = d.qlen;
 		B.tseq = d.tbuf, B.t_off = (const int64_t *)d.t_off, B.tlen = d.tlen;

@@ -122,6 +122,44 @@ struct DpIO {                 // what the DP stage needs beyond Ctx
 	long long qbytes, tbytes, cig_words;
 };
 
+// ---- the launch order of a round's DP problems, shared by the device planner (engine.hip) and the host that builds the launches
+// A problem's bucket: kind * 13 + class for the wavefront / tiny kernels (< 256); the team kernel's problems (kind 12, query of at most
+// 200 bases: the band never clips) have a bucket per (class, query length), 256 + class * 200 + (qlen - 1).  The problem ids are laid
+// out bucket by bucket in the order of the slots below: the wavefront / tiny kernels kind by kind, each with its classes largest
+// first; then the team kernel's classes, most strips first, and inside a class the longest queries first -- the alignments of a
+// wavefront sweep as many steps as the longest of them, so neighbours in that order pad least.
+static const int kDpPlanClasses = 13, kDpPlanKinds = 15, kDpPlanTeamKind = 12, kDpPlanQBins = 200;
+static const int kDpPlanTeam0 = 256;                                               // first team bucket
+static const int kDpPlanBuckets = kDpPlanTeam0 + kDpPlanClasses * kDpPlanQBins;
+static const int kDpPlanOtherSlots = (kDpPlanKinds - 1) * kDpPlanClasses;          // slots of the wavefront / tiny kernels
+static const int kDpPlanSlots = kDpPlanOtherSlots + kDpPlanClasses * kDpPlanQBins;
+PSVR_HD int dp_plan_bucket(int kind, int cls, int qlen)
+{
+	if (kind == kDpPlanTeamKind) return kDpPlanTeam0 + cls * kDpPlanQBins + (qlen < 1 ? 0 : qlen > kDpPlanQBins ? kDpPlanQBins - 1 : qlen - 1);
+	return (kind < 0 ? 0 : kind) * kDpPlanClasses + cls;
+}
+// the bucket whose problems come k-th in launch order (0 <= k < kDpPlanSlots)
+PSVR_HD int dp_plan_slot_bucket(int k)
+{
+	if (k < kDpPlanOtherSlots) {
+		const int kind_order[kDpPlanKinds - 1] = {0, 14, 13, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 11};
+		return kind_order[k / kDpPlanClasses] * kDpPlanClasses + (kDpPlanClasses - 1 - k % kDpPlanClasses);
+	}
+	k -= kDpPlanOtherSlots;
+	return kDpPlanTeam0 + (kDpPlanClasses - 1 - k / kDpPlanQBins) * kDpPlanQBins + (kDpPlanQBins - 1 - k % kDpPlanQBins);
+}
+// bucket counts -> the first position of every bucket (the serial form of what k_dp_plan_starts does with a workgroup); returns the total
+inline long long dp_plan_starts(const unsigned int *hist, long long *start)
+{
+	long long acc = 0;
+	for (int b = 0; b < kDpPlanBuckets; ++b) start[b] = 0;
+	for (int k = 0; k < kDpPlanSlots; ++k) { const int b = dp_plan_slot_bucket(k); start[b] = acc, acc += hist[b]; }
+	return acc;
+}
+// a backend that plans the DP stage on the device says so (kDevicePlan): its st_dp_plan brings the queue tops and flags with the plan
+template <class B, class = void> struct plans_on_device : std::false_type {};
+template <class B> struct plans_on_device<B, std::void_t<decltype(B::kDevicePlan)>> : std::true_type {};
+
 // one device -> host copy: the backends' d2h takes a list of them and synchronises once
 struct Readback { void *h; const void *d; size_t n; };
 typedef std::initializer_list<Readback> Readbacks;
@@ -523,11 +561,19 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 			be.st_chain(c, work, nwork, mate);
 		}
 		be.st_walk(c, work, nwork + nwalk);
-		unsigned long long tops[kTopStride + 1];                             // from the dp counter to the cw counter
 		int32_t fl[16];
-		mem.d2h({{tops, d_atops + 3 * kTopStride, sizeof tops}, {fl, d_flags, 64}});
+		long long dp_end, cw_end;
+		if constexpr (plans_on_device<BE>::value) {
+			// the DP stage is planned and placed on the device behind the walk: the queue tops and the flags come back with the plan, the
+			// round's one readback before the DP launches (nothing is placed when an arena has overflowed)
+			int rc = be.st_dp_plan(*this, dp_done, dp_end, cw_end, fl);
+			if (rc) return rc;
+		} else {
+			unsigned long long tops[kTopStride + 1];                         // from the dp counter to the cw counter
+			mem.d2h({{tops, d_atops + 3 * kTopStride, sizeof tops}, {fl, d_flags, 64}});
+			dp_end = (long long)tops[0], cw_end = (long long)tops[kTopStride];
+		}
 		if (fl[8]) any_h = true;
-		long long dp_end = (long long)tops[0], cw_end = (long long)tops[kTopStride];
 		if (fl[7]) stats.stale_open = 1;
 		// An arena that filled up in the stages so far ends the round here: what follows (assembly, the reads' tails) would walk records
 		// that were never written.  Bits: 1 dp, 2 cw, 4 seg, 8 us, 16 mem.
