@@ -18,7 +18,7 @@
 
 namespace psvr {
 
-int make_dp_params(const psvr_ksw_params_t *par, int variant, DpParams *P);   // ksw_host.hip
+int dp_params(const psvr_ksw_params_t *par, int variant, DpParams *P);   // ksw_host.hip: make_dp_params, its failure as the last error
 
 static const int kBlock = 256;
 static inline unsigned grid_for(long long n, int block = kBlock) { return (unsigned)((n + block - 1) / block); }
@@ -926,10 +926,9 @@ __global__ void k_scatter_u8(uint8_t *a, const int32_t *idx, long long n, uint8_
 
 // ---- DP planning on the device ---------------------------------------------------------------
 // A round's DP stage is planned behind k_walk without the host: k_dp_plan reads the number of queued problems from the queue's counter,
-// classifies them, counts the buckets (dp_plan_bucket, engine_core.h) and hands out the sequence / slab / CIGAR ranges; k_dp_plan_starts
+// routes them (dp_route), counts the buckets (dp_plan_bucket; the rules are dp_plan.h's) and hands out the sequence / slab / CIGAR ranges; k_dp_plan_starts
 // (one workgroup) turns the counts into bucket starts and writes the round's plan record, the one thing the host reads before it
 // launches the DP kernels; k_dp_scatter and k_dp_fetch place the problem ids and the sequences while the host reads it.
-static_assert(kDpPlanClasses == PSVR_DP_NUM_LDS_CLASSES && kDpPlanKinds == PSVR_DP_NUM_KINDS && kDpPlanTeamKind == PSVR_DP_KIND_STRIP, "engine_core.h's launch order follows ksw_device.h");
 struct DpPlanRec {                 // the plan record: one contiguous readback
 	unsigned long long dp_top, cw_top;       // the queue counters the round ended with
 	unsigned long long n;                    // DP problems of this round (0 when an arena overflowed)
@@ -994,15 +993,14 @@ __global__ __launch_bounds__(kBlock) void k_dp_plan(Ctx c, long long dp_done, Dp
 			d.qlen[i] = x.qlen, d.tlen[i] = x.tlen;
 			v[0] = (unsigned int)((x.qlen + 15) & ~15), v[1] = (unsigned int)((x.tlen + 15) & ~15);
 			seq_bytes += (unsigned int)(x.qlen + x.tlen);
-			int need;
-			const int kind = dp_classify(x.qlen, x.tlen, w, true, 0, false, &need, tiny_ok != 0, team_ok != 0);
-			int cls = 0;
-			while (cls < PSVR_DP_NUM_LDS_CLASSES - 1 && dp_lds_class_bytes(cls) < need) ++cls;
-			v[2] = dp_kind_uses_slab(kind) ? (unsigned int)((dp_p_bytes(x.qlen, x.tlen, w) + 255) >> 8) : 0;
+			// (the engine's problems: extd2 with a CIGAR and none of the other flags, sequences far below kDpLongLen)
+			const DpRoute R = dp_route(x.qlen, x.tlen, w, true, 0, false, tiny_ok != 0, team_ok != 0, true);
+			const int cls = dp_lds_class(R.need);
+			v[2] = (unsigned int)(R.slab >> 8);
 			v[3] = v[0] + v[1] + 2;
-			const int b = dp_plan_bucket(kind, cls, x.qlen);
+			const int b = dp_plan_bucket(R.kind, cls, x.qlen);
 			d.bucket[i] = b;
-			if (kind == PSVR_DP_KIND_STRIP) atomicMax(&lq[cls], (unsigned int)x.qlen);
+			if (R.kind == PSVR_DP_KIND_STRIP) atomicMax(&lq[cls], (unsigned int)x.qlen);
 			atomicAdd(&lh[b], 1u);
 		}
 		// ranges by any scheme that keeps them disjoint: a prefix inside the workgroup, one bump per workgroup and quantity
@@ -1081,13 +1079,9 @@ __global__ __launch_bounds__(kBlock) void k_dp_plan_starts(Ctx c, long long dp_d
 	if (threadIdx.x < 16) wk.rec.flags[threadIdx.x] = c.mem.overflow[threadIdx.x];
 	__syncthreads();
 	if (threadIdx.x == 0) {
-		// scratch of the team kernel: a wavefront's slice is sized by its class's longest query (TeamLaunch::add, the same clamp)
+		// scratch of the team kernel: a wavefront's slice is sized by its class's longest query
 		unsigned long long ws = 0;
-		for (int cls = 0; cls < PSVR_DP_NUM_LDS_CLASSES; ++cls)
-			if (team_cnt[cls]) {
-				const int lanes = dp_team_lanes(cls + 1), qm = (int)wk.qmax[cls];
-				ws += (team_cnt[cls] * lanes + 63) / 64 * dp_team_ws_bytes(qm > 0 ? qm : 1, cls + 1, lanes);
-			}
+		for (int cls = 0; cls < PSVR_DP_NUM_LDS_CLASSES; ++cls) ws += dp_team_class_ws(cls, team_cnt[cls], (int)wk.qmax[cls]);
 		DpPlanRec &r = wk.rec;
 		r.dp_top = *c.dp.top, r.cw_top = *c.cw.top, r.n = (unsigned long long)n;
 		r.tot_q = wk.alloc[0], r.tot_t = wk.alloc[1], r.tot_p = wk.alloc[2], r.tot_c = wk.alloc[3], r.ws_bytes = ws, r.seq_bytes = wk.seq_bytes;
@@ -1220,7 +1214,6 @@ struct GpuBE {
 	DpParams dpP;
 	bool dp_ready = false, dp_lean = false;
 	static constexpr long long kTeamMinProblems = 32768;       // below this a round's DP problems go to the wavefront-per-alignment kernels
-	static constexpr int kTinySmallLds = 4096;                 // tiny-kernel classes up to this (8 anti-diagonals) share a launch, the larger ones another
 	static constexpr int kSide = 3;                            // side streams: the DP kernels of a round are independent of each other
 	int device = -1;                                           // (for the stream pool)
 	hipStream_t side[kSide] = {};
@@ -1631,7 +1624,7 @@ struct GpuBE {
 		memcpy(kp.mat, c.mat, 25);
 		kp.q = (int8_t)c.par.gap_open, kp.e = (int8_t)c.par.gap_ex, kp.q2 = (int8_t)c.par.gap_open2, kp.e2 = (int8_t)c.par.gap_ex2;
 		kp.w = 200, kp.zdrop = c.par.zdrop, kp.end_bonus = -1, kp.flag = 0;   // KSW_ALN_handler::copy_option, rr.cpp:817-827 (bandwith = 200)
-		int rc = make_dp_params(&kp, 0, &dpP);
+		int rc = dp_params(&kp, 0, &dpP);
 		if (rc) return rc;
 		note(dp_allow_big_lds());
 		// the engine reads score, mqe and the CIGAR of its pieces, never ez.max / max_q / max_t: when the z-drop rule cannot trigger for these
@@ -1699,26 +1692,8 @@ struct GpuBE {
 		if (r.verdict || (long long)r.n != d.end - d.begin) return set_error(PSVR_ERR_DEVICE, "DP stage without a plan for its round");
 		core.stats.dp_seq_bytes += (long long)r.seq_bytes;           // query + target bytes the DP launches of this round read (k_dp_plan sums them)
 		const unsigned long long ws_bytes = r.ws_bytes;
-		// the launches in the order the ids were placed in (dp_plan_slot_bucket).  The tiny kernel's classes go out as two launches, each at
-		// the LDS size of its largest class: the two populous classes (up to 4 and up to 8 anti-diagonals) together at no more than 16 KB a
-		// block, the rest at up to 40 KB -- one launch per class was six launches of a few hundred wavefronts each, queued one behind the other
-		std::vector<Launch3> ls;
-		long long acc = 0;
-		for (int k = 0; k < kDpPlanOtherSlots; ++k) {
-			const int b = dp_plan_slot_bucket(k), kind = b / PSVR_DP_NUM_LDS_CLASSES, cls = b % PSVR_DP_NUM_LDS_CLASSES;
-			const long long cnt = (long long)r.cnt[b];
-			if (!cnt) continue;
-			const bool joins = kind == PSVR_DP_KIND_TINY && !ls.empty() && ls.back().kind == kind && (ls.back().lds > kTinySmallLds) == (dp_lds_class_bytes(cls) > kTinySmallLds);
-			if (joins) ls.back().count += cnt;
-			else ls.push_back(Launch3{kind, dp_lds_class_bytes(cls), acc, cnt});
-			acc += cnt;
-		}
-		// the team kernel's classes, longest first; inside a class the queries in descending order of length
-		for (int cls = PSVR_DP_NUM_LDS_CLASSES - 1; cls >= 0; --cls) {
-			if (r.team_cnt[cls]) ls.push_back(Launch3{PSVR_DP_KIND_STRIP, dp_lds_class_bytes(cls), acc, (long long)r.team_cnt[cls]});
-			acc += (long long)r.team_cnt[cls];
-		}
-		const unsigned long long *qmax = r.qmax;
+		// the launches in the order the ids were placed in, the tiny kernel's classes merged into two
+		const std::vector<DpLaunch> ls = dp_launch_list(r.cnt, r.team_cnt, r.qmax, true);
 		DpBatch B;
 		B.qseq = d.qbuf, B.q_off = (const int64_t *)d.q_off, B.qlen = d.qlen;
 		B.tseq = d.tbuf, B.t_off = (const int64_t *)d.t_off, B.tlen = d.tlen;
@@ -1727,8 +1702,8 @@ struct GpuBE {
 		B.err = c.err;
 		TeamLaunch team;
 		size_t n_other = 0;
-		for (const Launch3 &L : ls) {
-			if (L.kind == PSVR_DP_KIND_STRIP) team.add(dp_class_of(L.lds) + 1, L.first, L.count, (int)qmax[dp_class_of(L.lds)]);
+		for (const DpLaunch &L : ls) {
+			if (L.kind == PSVR_DP_KIND_STRIP) team.add(L.cls, L.first, L.count, L.qmax);
 			else ++n_other;
 		}
 		// The launches of a round work on disjoint problems, and all but the team kernel's are short of wavefronts (the thread-per-alignment
@@ -1749,7 +1724,7 @@ struct GpuBE {
 			PSVR_HIP(hipGetLastError());
 		}
 		if (fan) PSVR_HIP(hipEventRecord(ev_fork, stream));
-		for (const Launch3 &L : ls) {
+		for (const DpLaunch &L : ls) {
 			if (L.kind == PSVR_DP_KIND_STRIP) continue;
 			hipStream_t s2 = stream;
 			if (fan) {
@@ -1776,7 +1751,7 @@ struct GpuBE {
 			}
 			B.idx = plan_idx.as<int32_t>() + L.first;
 			t0(dp_kind_name(L.kind, 0));
-			PSVR_HIP(dp_launch_kind(L.kind, 0, (unsigned)L.count, L.lds, s2, B, dpP));
+			PSVR_HIP(dp_launch_kind(L.kind, 0, (unsigned)L.count, dp_lds_class_bytes(L.cls), s2, B, dpP));
 			t1();
 			PSVR_HIP(hipGetLastError());
 		}
@@ -1788,7 +1763,6 @@ struct GpuBE {
 		for (int k = 0; k < kSide && k < used; ++k) PSVR_HIP(hipStreamWaitEvent(stream, ev_join[k], 0));
 		return PSVR_OK;
 	}
-	struct Launch3 { int kind, lds; long long first, count; };
 };
 
 } // namespace psvr

@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <vector>
 #include "aln_device.h"
+#include "dp_plan.h"
 
 namespace psvr {
 
@@ -122,40 +123,6 @@ struct DpIO {                 // what the DP stage needs beyond Ctx
 	long long qbytes, tbytes, cig_words;
 };
 
-// ---- the launch order of a round's DP problems, shared by the device planner (engine.hip) and the host that builds the launches
-// A problem's bucket: kind * 13 + class for the wavefront / tiny kernels (< 256); the team kernel's problems (kind 12, query of at most
-// 200 bases: the band never clips) have a bucket per (class, query length), 256 + class * 200 + (qlen - 1).  The problem ids are laid
-// out bucket by bucket in the order of the slots below: the wavefront / tiny kernels kind by kind, each with its classes largest
-// first; then the team kernel's classes, most strips first, and inside a class the longest queries first -- the alignments of a
-// wavefront sweep as many steps as the longest of them, so neighbours in that order pad least.
-static const int kDpPlanClasses = 13, kDpPlanKinds = 15, kDpPlanTeamKind = 12, kDpPlanQBins = 200;
-static const int kDpPlanTeam0 = 256;                                               // first team bucket
-static const int kDpPlanBuckets = kDpPlanTeam0 + kDpPlanClasses * kDpPlanQBins;
-static const int kDpPlanOtherSlots = (kDpPlanKinds - 1) * kDpPlanClasses;          // slots of the wavefront / tiny kernels
-static const int kDpPlanSlots = kDpPlanOtherSlots + kDpPlanClasses * kDpPlanQBins;
-PSVR_HD int dp_plan_bucket(int kind, int cls, int qlen)
-{
-	if (kind == kDpPlanTeamKind) return kDpPlanTeam0 + cls * kDpPlanQBins + (qlen < 1 ? 0 : qlen > kDpPlanQBins ? kDpPlanQBins - 1 : qlen - 1);
-	return (kind < 0 ? 0 : kind) * kDpPlanClasses + cls;
-}
-// the bucket whose problems come k-th in launch order (0 <= k < kDpPlanSlots)
-PSVR_HD int dp_plan_slot_bucket(int k)
-{
-	if (k < kDpPlanOtherSlots) {
-		const int kind_order[kDpPlanKinds - 1] = {0, 14, 13, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1, 11};
-		return kind_order[k / kDpPlanClasses] * kDpPlanClasses + (kDpPlanClasses - 1 - k % kDpPlanClasses);
-	}
-	k -= kDpPlanOtherSlots;
-	return kDpPlanTeam0 + (kDpPlanClasses - 1 - k / kDpPlanQBins) * kDpPlanQBins + (kDpPlanQBins - 1 - k % kDpPlanQBins);
-}
-// bucket counts -> the first position of every bucket (the serial form of what k_dp_plan_starts does with a workgroup); returns the total
-inline long long dp_plan_starts(const unsigned int *hist, long long *start)
-{
-	long long acc = 0;
-	for (int b = 0; b < kDpPlanBuckets; ++b) start[b] = 0;
-	for (int k = 0; k < kDpPlanSlots; ++k) { const int b = dp_plan_slot_bucket(k); start[b] = acc, acc += hist[b]; }
-	return acc;
-}
 // a backend that plans the DP stage on the device says so (kDevicePlan): its st_dp_plan brings the queue tops and flags with the plan
 template <class B, class = void> struct plans_on_device : std::false_type {};
 template <class B> struct plans_on_device<B, std::void_t<decltype(B::kDevicePlan)>> : std::true_type {};

@@ -3,7 +3,9 @@
 // Replaces ksw_extd2_sse / ksw_extz2_sse (reference: src/kswlib/ksw2_extd2_sse.c:26-396,
 // ksw2_extz2_sse.c:23-305) and ksw_backtrack_D / ksw_apply_zdrop (src/kswlib/ksw2.h:119-151,245-261).
 //
-// Design (MI355X-first, not a port of the SSE code).  Four kernels share the recurrences; the planners route a problem by shape:
+// Design (MI355X-first, not a port of the SSE code).  Four kernels share the recurrences; the planners route a problem by shape
+// (dp_plan.h: the one place the size classes, kinds, routing rules, scratch sizes and launch order live -- this header keeps what the
+// kernels themselves need):
 //   * extd2_team_kernel<LANES, CPL> + extd2_team_finish_kernel -- the `aln` path's kernel: band never clips the matrix, values fit
 //     int8 (dp_band_never_binds && nowrap_ok).  2 lanes per alignment, 32 alignments per wavefront, the matrix swept in strips of
 //     16 target columns with the state of 8 columns per lane in registers, a ROW of them per step; see the kernel for the strip
@@ -21,20 +23,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/psvr_engine.h"
+#include "dp_plan.h"
 
 namespace psvr {
-
-struct DpParams {
-	int32_t m;
-	int32_t q, e, q2, e2;       // after the q+e <= q2+e2 swap (ksw2_extd2_sse.c:70)
-	int32_t qe_pre;             // q+e BEFORE the swap: only feeds H[0] at r==0 (:60,351)
-	int32_t sc_mch, sc_mis, sc_N, m1;
-	int32_t w, zdrop, end_bonus, flag;
-	int32_t long_thres, long_diff;
-	int32_t skip;               // 1: parameter set makes the reference return right after reset (:68,93)
-	int32_t nowrap_ok;          // in-band values provably fit int8 for these scoring parameters
-	int8_t  mat[25];
-};
 
 struct DpBatch { // device pointers of one batch
 	const int32_t *idx;        // problem ids handled by this launch (one per workgroup)
@@ -49,12 +40,6 @@ struct DpBatch { // device pointers of one batch
 	int *err;                  // set to 20 if that scratch runs out (cannot happen with the planners' bounds; never silent)
 };
 
-#define PSVR_DP_NUM_LDS_CLASSES 13
-#define PSVR_DP_KIND_TINY 11
-#define PSVR_DP_KIND_STRIP 12
-#define PSVR_DP_STRIP 16               // extd2_team_kernel: size classes count 16-column strips
-#define PSVR_DP_TINY_MAX 16            // extd2_tiny_kernel: qlen, tlen <= 16, one thread per alignment
-static const int kDpWaves = 4;   // alignments (wavefronts) per workgroup of the register-resident kernels
 template <int K, bool PG> __global__ void extd2_reg_kernel(DpBatch B, DpParams P);   // ksw_kernels.hip
 template <int K> __global__ void extd2_ring_kernel(DpBatch B, DpParams P);             // ksw_kernels.hip: the same sweep on a ring of 64 K columns that slides with the band
 template <int VAR> __global__ void extd2_lds_kernel(DpBatch B, DpParams P); // ksw_kernels.hip
@@ -74,134 +59,6 @@ struct TeamPlan {
 };
 template <int LANES, int CPL, int LEAN> __global__ void extd2_team_kernel(DpBatch B, DpParams P, TeamPlan T);          // ksw_kernels.hip: the sweep, a row per lane and step
 template <int LANES, int CPL, int LEAN> __global__ void extd2_team_finish_kernel(DpBatch B, DpParams P, TeamPlan T);   // z-drop / end rules and traceback, a thread per alignment
-// the z-drop rule cannot trigger whatever the sequences are: a gap of any length costs at most q2 (e2 == 0), so an anti-diagonal's maximum
-// is never more than 2 q2 below the running maximum (one insertion + one deletion from the cell that holds it) -- in a matrix whose first
-// row and column are charged with the same (post-swap) pairs as its interior.  The reference charges H[0] at r == 0 with q + e taken
-// BEFORE the swap (qe_pre, ksw2_extd2_sse.c:60,351): when the caller's pairs arrive in the other order, every H is lower by
-// qe_pre - (q + e) than that argument assumes while the running maximum starts at 0, so the threshold rises by that shift (0 for
-// pairs in plain order).  The team kernel's LEAN variant (no per-diagonal maximum) is exact then, for a caller that reads neither
-// ez.max nor max_q / max_t
-inline bool dp_zdrop_inert(const DpParams &P)
-{
-	return P.e2 == 0 && (P.zdrop < 0 || P.zdrop >= 2 * P.q2 + (P.qe_pre - (P.q + P.e))) && !(P.flag & PSVR_EZ_EXTZ_ONLY);
-}
-// the tiny / team kernels need the lean regime (values fit int8, band never clips) and only the flags they implement
-__host__ __device__ inline bool dp_tiny_ok(const DpParams &P, bool fast_ok) { return fast_ok && P.nowrap_ok && !P.skip && (P.w < 0 || P.w >= PSVR_DP_TINY_MAX); }
-// lanes per alignment of the team kernel for the class of problems with n_strips16 16-column strips
-// A team = kDpTeamLanes lanes, each with kDpTeamCpl target columns of a strip in registers (strip width = their product).
-// 4 x 4 was the first shape; 2 x 8 keeps the 16-column strips but spends a step's fixed cost -- neighbour exchange, boundary records,
-// per-diagonal maximum -- on eight cells instead of four, and puts 32 alignments in a wavefront.  Other shapes of the row sweep on the
-// bench batch (profiles/r03e_team_kernel_row_sweep.txt): 1 x 16 at two wavefronts per SIMD as fast, 4 x 4 and 4 x 8 slower.
-static constexpr int kDpTeamLanes = 2, kDpTeamCpl = 8;
-__host__ __device__ inline int dp_team_lanes(int n_strips16) { return kDpTeamLanes; }
-// scratch bytes one wavefront of the team kernel needs for alignments with at most qmax query bases in that class
-__host__ __device__ inline unsigned long long dp_team_ws_bytes(int qmax, int n_strips16, int lanes, int cpl = kDpTeamCpl)
-{
-	const int sw = cpl * lanes, pb = 64 / lanes, n_strips = (n_strips16 * 16 + sw - 1) / sw;
-	// direction bytes (one per cell, 64 x cpl per step), then per row / diagonal and alignment: two boundary dwords (ping-pong), the key D and the
-	// dword with the two band-end values (16 bytes; sized for 20: a fifth dword per diagonal is head-room, not used)
-	return (unsigned long long)(64 * cpl) * n_strips * (qmax + sw - 1) + (unsigned long long)pb * 20 * (qmax + sw * n_strips + 1);
-}
-
-// true when the band [(r-w+1)>>1, (r+w)>>1] never clips the DP matrix: then st0/en0 follow the matrix edges only, every
-// in-band cell's (r-1,t-1)/(r-1,t) neighbours are in-band or one of the explicit boundary values (ksw2_extd2_sse.c:142-156),
-// and the lanes of the 16-rounded blocks outside the band are never read back
-__host__ __device__ inline bool dp_band_never_binds(int qlen, int tlen, int w) { return qlen <= w && tlen <= w + 1; }
-
-// ---- size classes shared by the host planner (ksw_host.hip) and the device-side planner (engine.hip)
-#define PSVR_DP_MAX_LDS (160 * 1024)
-__host__ __device__ inline int dp_lds_class_bytes(int cls)
-{
-	const int t[PSVR_DP_NUM_LDS_CLASSES] = {2048, 4096, 6144, 8192, 12288, 16384, 24576, 32768, 49152, 65536, 98304, 131072, PSVR_DP_MAX_LDS};
-	return t[cls];
-}
-// the band width in effect: w < 0 means unbanded (ksw2_extd2_sse.c:83)
-__host__ __device__ inline int dp_band_w(int qlen, int tlen, int w) { return w < 0 ? (qlen > tlen ? qlen : tlen) : w; }
-// 16-byte blocks of one row of direction bytes (:86-87); the row pitch is 16 times this
-__host__ __device__ inline int dp_n_col(int qlen, int tlen, int w_in)
-{
-	int w = dp_band_w(qlen, tlen, w_in);
-	int n_col = qlen < tlen ? qlen : tlen;
-	n_col = ((n_col < w + 1 ? n_col : w + 1) + 15) / 16 + 1;
-	return n_col;
-}
-__host__ __device__ inline long long dp_reg_lds_need(int qlen, int tlen, int w_in)
-{
-	return (long long)((qlen + 16 + 15) & ~15) + (long long)(qlen + tlen - 1) * dp_n_col(qlen, tlen, w_in) * 16 + 16;
-}
-__host__ __device__ inline long long dp_p_bytes(int qlen, int tlen, int w_in)
-{
-	return ((long long)(qlen + tlen - 1) * dp_n_col(qlen, tlen, w_in) + 1) * 16;
-}
-__host__ __device__ inline int dp_lds_kernel_need(int qlen, int tlen, int variant)
-{
-	int T = (tlen + 15) / 16 * 16, QL = (qlen + 15) / 16 * 16;
-	int narr = variant == 0 ? 7 : 5;
-	int img = narr * T + T + QL + 16;
-	return ((img + 15) & ~15) + 4 * T;
-}
-// Direction bytes stay in LDS only while the whole footprint is at most this (keeps >= 32 waves per CU resident);
-// larger problems stream them to an HBM slab and trace back through L2
-#define PSVR_DP_PG_THRESHOLD 4096
-#define PSVR_DP_NUM_KINDS 15
-#define PSVR_DP_KIND_RING3 13          // extd2_ring_kernel<3>: any tlen, band (+ its 16-lane rounding) within 192 columns
-#define PSVR_DP_KIND_RING4 14          // extd2_ring_kernel<4>: ... within 256 columns
-// kinds only the host planner (ksw_host.hip) uses, for problems the kinds above cannot hold in LDS
-#define PSVR_DP_KIND_RING1_3 15        // extd2_ring1_kernel<3>: as RING3, one wavefront per workgroup (query + target image up to 160 KiB)
-#define PSVR_DP_KIND_RING1_4 16        // extd2_ring1_kernel<4>
-#define PSVR_DP_KIND_HBM 17            // extd2_hbm_kernel<VAR>: any shape, flag and variant
-#define PSVR_DP_NUM_HOST_KINDS 18
-// kinds whose direction bytes live in the HBM slab (DpBatch::pslab)
-__host__ __device__ inline bool dp_kind_uses_slab(int kind) { return kind == 0 || (kind > 5 && kind < PSVR_DP_KIND_TINY) || kind >= PSVR_DP_KIND_RING3; }
-// kind: 1..5 = extd2_reg_kernel<kind,false> (direction bytes in LDS), 6..10 = extd2_reg_kernel<kind-5,true> (in HBM), 13 / 14 = extd2_ring_kernel<3 / 4>,
-// 11 = extd2_tiny_kernel (one thread per alignment; *need = 512 x anti-diagonals, which bins the problems by size),
-// 0 = general kernel, -1 = unsupported; *need = dynamic LDS bytes
-__host__ __device__ inline int dp_classify(int qlen, int tlen, int w, bool fast_ok, int variant, bool skip, int *need, bool tiny_ok = false, bool team_ok = true)
-{
-	if (qlen <= 0 || tlen <= 0 || skip) { *need = 0; return 1; }
-	if (tiny_ok && qlen <= PSVR_DP_TINY_MAX && tlen <= PSVR_DP_TINY_MAX) { *need = (qlen + tlen - 1) * 512; return PSVR_DP_KIND_TINY; }
-	// one thread per alignment, 16-column strips in registers: whenever the band never clips the matrix (the lean regime).
-	// The size class is the number of strips (1..13), expressed through `need` as that class's byte threshold.
-	// (team_ok = false: a batch too small to fill the chip with 16 alignments per wavefront goes to the wavefront-per-alignment kernels,
-	// whose sweep is qlen + tlen steps instead of strips x (qlen + 15))
-	if (tiny_ok && team_ok && dp_band_never_binds(qlen, tlen, dp_band_w(qlen, tlen, w)) && tlen <= PSVR_DP_STRIP * PSVR_DP_NUM_LDS_CLASSES) {
-		*need = dp_lds_class_bytes((tlen + PSVR_DP_STRIP - 1) / PSVR_DP_STRIP - 1);
-		return PSVR_DP_KIND_STRIP;
-	}
-	int T = (tlen + 15) / 16 * 16;
-	long long n = dp_reg_lds_need(qlen, tlen, w);
-	if (fast_ok && T <= 320) {
-		if (n <= PSVR_DP_PG_THRESHOLD) { *need = (int)n; return (T + 63) / 64; }
-		*need = ((qlen + 16 + 15) & ~15) + 16;
-		return 5 + (T + 63) / 64;
-	}
-	if (fast_ok) {
-		// wider than the register-resident kernels' 320 columns: the ring kernels, when the columns an anti-diagonal can touch -- the band,
-		// w + 1 wide at most (and never wider than the shorter sequence), plus the 16-lane rounding at both ends, the stale-score block and
-		// the left neighbour of its first column -- fit their ring.  LDS: the query image and the target.
-		const int wf = dp_band_w(qlen, tlen, w), sh = qlen < tlen ? qlen : tlen;
-		const int span = (wf < sh - 1 ? wf : sh - 1) + 33;
-		if (span <= 256) {
-			*need = ((qlen + 16 + 15) & ~15) + ((tlen + 15) & ~15) + 16;
-			return span <= 192 ? PSVR_DP_KIND_RING3 : PSVR_DP_KIND_RING4;
-		}
-	}
-	int g = dp_lds_kernel_need(qlen, tlen, variant);
-	*need = g;
-	return g <= PSVR_DP_MAX_LDS ? 0 : -1;
-}
-
-// extd2_hbm_kernel's slice of the slab: the direction bytes (none without a CIGAR), then the flat image of extd2_lds_kernel
-// (u|v|x|y|x2|y2|s|sf|qr, 16-aligned) and H (int32 per column)
-__host__ __device__ inline long long dp_hbm_img_off(int qlen, int tlen, int w_in, bool with_cigar)
-{
-	return with_cigar ? (dp_p_bytes(qlen, tlen, w_in) + 255) & ~255LL : 0;
-}
-__host__ __device__ inline long long dp_hbm_img_bytes(int qlen, int tlen, int variant)
-{
-	const long long T = (tlen + 15LL) / 16 * 16, QL = (qlen + 15LL) / 16 * 16;
-	return (((variant == 0 ? 8 : 6) * T + QL + 16 + 15) & ~15LL) + 4 * T;
-}
 
 __device__ __forceinline__ int s8(int v) { return (int)(int8_t)v; }
 

@@ -1,21 +1,9 @@
-// ksw_launch.h -- one place that maps a DP size class to its kernel instantiation
+// ksw_launch.h -- one place that maps a DP kind (dp_plan.h) to its kernel instantiation
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ksw_device.h"
 
 namespace psvr {
-
-inline const char *dp_kind_name(int kind, int variant)
-{
-	static const char *n[PSVR_DP_NUM_KINDS] = {"extd2_lds_kernel", "extd2_reg_kernel<1,lds>", "extd2_reg_kernel<2,lds>", "extd2_reg_kernel<3,lds>", "extd2_reg_kernel<4,lds>",
-	                                           "extd2_reg_kernel<5,lds>", "extd2_reg_kernel<1,hbm>", "extd2_reg_kernel<2,hbm>", "extd2_reg_kernel<3,hbm>", "extd2_reg_kernel<4,hbm>",
-	                                           "extd2_reg_kernel<5,hbm>", "extd2_tiny_kernel", "extd2_team_kernel", "extd2_ring_kernel<3>", "extd2_ring_kernel<4>"};
-	if (kind == 0 && variant == 1) return "extz2_lds_kernel";
-	if (kind == PSVR_DP_KIND_RING1_3) return "extd2_ring1_kernel<3>";
-	if (kind == PSVR_DP_KIND_RING1_4) return "extd2_ring1_kernel<4>";
-	if (kind == PSVR_DP_KIND_HBM) return variant == 0 ? "extd2_hbm_kernel" : "extz2_hbm_kernel";
-	return n[kind];
-}
 
 // (kinds 3..5, extd2_reg_kernel<3..5,lds>, have no kernel: 129 target columns already need more direction bytes than PSVR_DP_PG_THRESHOLD,
 // so no planner produces them; one that did would be an internal error)
@@ -65,17 +53,15 @@ struct TeamLaunch {
 	TeamPlan T;
 	TeamLaunch() { T.n_classes = 0; T.first_block[0] = 0; }
 	unsigned long long ws_next = 0;
-	// qmax: the longest query of the class (a wavefront's scratch slice is sized by it)
-	void add(int n_strips16, long long first_slot, long long count, int qmax)
+	// a class (cls + 1 strips of 16 columns) and the longest query among its `count` problems (a wavefront's scratch slice is sized by it)
+	void add(int cls, long long first_slot, long long count, int qmax)
 	{
 		const int c = T.n_classes++;
-		T.n_strips16[c] = n_strips16, T.first_slot[c] = first_slot, T.count[c] = count;
-		const int lanes = dp_team_lanes(n_strips16), pb = 64 / lanes;
-		const int blocks = (int)((count + pb - 1) / pb);
-		T.first_block[c + 1] = T.first_block[c] + blocks;
-		T.ws_need[c] = dp_team_ws_bytes(qmax > 0 ? qmax : 1, n_strips16, lanes);
+		T.n_strips16[c] = cls + 1, T.first_slot[c] = first_slot, T.count[c] = count;
+		T.first_block[c + 1] = T.first_block[c] + (int)dp_team_waves(cls, (unsigned long long)count);
+		T.ws_need[c] = dp_team_wave_ws(cls, qmax);
 		T.ws_base[c] = ws_next;
-		ws_next += T.ws_need[c] * (unsigned long long)blocks;
+		ws_next += dp_team_class_ws(cls, (unsigned long long)count, qmax);
 	}
 	// lean: the variant without the per-diagonal maximum -- only for a caller that has checked dp_zdrop_inert(P) and reads neither ez.max nor max_q / max_t
 	void launch_sweep(hipStream_t stream, const DpBatch &B, const DpParams &P, bool lean = false) const
@@ -93,14 +79,6 @@ struct TeamLaunch {
 	}
 	void launch(hipStream_t stream, const DpBatch &B, const DpParams &P, bool lean = false) const { launch_sweep(stream, B, P, lean), launch_finish(stream, B, P, lean); }
 };
-// the class index a launch's `lds` value names (team kernel: index + 1 = number of 16-column strips)
-inline int dp_class_of(int lds)
-{
-	int cls = 0;
-	while (cls < PSVR_DP_NUM_LDS_CLASSES - 1 && dp_lds_class_bytes(cls) < lds) ++cls;
-	return cls;
-}
-
 inline hipError_t dp_allow_big_lds()
 {
 	hipError_t e = hipSuccess;

@@ -2,9 +2,9 @@
 flags, shapes and sequence kinds at which those kernels have corners.  Shared by tests/test_ksw_regimes.py (CPU),
 tests/test_ksw_regimes_gpu.py, tests/test_oracle_ksw.py and tests/golden/gen_ksw_kat.py.
 
-The predicates are restated here from pansvr_amd/csrc/ksw_host.hip (make_dp_params, dp_route) and ksw_device.h (dp_tiny_ok,
-dp_band_never_binds, dp_classify); tests/test_ksw_regimes.py holds regime() to the library's own psvr_dp_regime, and the GPU sweep
-holds route() to the plans' descriptions.  dp_zdrop_inert is NOT restated: its only source is the library."""
+The predicates are restated here from pansvr_amd/csrc/dp_plan.h (make_dp_params, dp_tiny_ok, dp_band_never_binds, dp_route);
+tests/test_ksw_regimes.py holds regime() to the library's own psvr_dp_regime, tests/test_dp_host_plan.py holds route() to the host
+planner's plans on the CPU and the GPU sweep holds it to the plans' descriptions.  dp_zdrop_inert is NOT restated: its only source is the library."""
 import numpy as np
 
 from ksw_cases import DEF, rand_seq
@@ -99,7 +99,7 @@ def lds_kernel_need(ql, tl, v):
 
 
 def route(p, flag, variant, ql, tl):
-    """the kernel name psvr_dp_plan_describe prints for this problem (dp_route + dp_classify + dp_kind_name)"""
+    """the kernel name psvr_dp_plan_describe prints for this problem (dp_route + dp_kind_name)"""
     v = VARIANTS.index(variant)
     r = regime(p, v)
     w = p["w"]
