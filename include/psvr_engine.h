@@ -317,6 +317,39 @@ int psvr_engine_rebase(psvr_engine_t *eng, const int64_t pos[3], void *stream);
 /* work counters of the last run (probes, hits, dp problems, cells, speculative re-runs ...) as JSON */
 int psvr_engine_stats(const psvr_engine_t *eng, char *buf, size_t buflen);
 
+/* ---- FASTQ text parsed on the device (step 0 of the batch seam) ---------------------------------------------------------------------------
+ * Replaces, for a caller of seam B1 that holds FASTQ text, load_reads' kseq_read loop + parse_ori_mapping_rst
+ * (src/PanSVgenerateVCF/read_realignment.cpp:121-152, read_realignment.hpp:392-429): the interleaved FASTQ of the `signal` step, four lines
+ * per read and two reads per pair, becomes the three arrays psvr_engine_upload takes -- in device memory, where the engine wants them.
+ * psvr_fastq_parse looks at the window text[0, n_bytes) (host memory, page-locked or pageable, free again when the call returns;
+ * n_bytes >= 2^32: PSVR_ERR_UNSUPPORTED).  A line ends with its '\n'; with at_end != 0 the window's end closes an unterminated last
+ * line, otherwise such a tail is no line.  Only the first 8 * max_pairs lines count; eight lines are a pair.  Leading pairs are kept
+ * while the bases of the pairs in front of them stay below max_bases (load_reads' rule: the first pair is always taken when
+ * max_bases > 0).  For the kept pairs, with every line stripped of its trailing '\n' and '\r' bytes:
+ *   line_start[0 .. 8 n_pairs]   where every line starts in the window; info->used_bytes = line_start[8 n_pairs]
+ *   base_off[0 .. 2 n_pairs]     exclusive prefix sum of the sequence lines' lengths; bases[]: their bytes, unchanged, then a NUL
+ *   name_end[r]                  min(65535, index of the first ' ' or '\t' at or behind byte 1 of the header line, or its length)
+ *   ori[r]                       parse_ori_mapping_rst on what follows that byte: strtok_r(.., "_") tokens 0-4 through atoi (a wrapping
+ *                                32-bit accumulator), direction / unmapped from token 9's first two bytes ('F', 'Y'); every byte is written
+ * Nothing is validated: a malformed text gives what the reference's loop would make of it.  The arrays stay on the device until the next
+ * psvr_fastq_parse; psvr_fastq_download copies them out (any pointer may be NULL; bases has room for total_bases + 1),
+ * psvr_engine_upload_fastq hands pairs [first_pair, first_pair + n_pairs) to an engine of the same device (another device: PSVR_ERR_ARG)
+ * with exactly the effect of psvr_engine_upload on the downloaded arrays, device to device; it returns when `fq` may be parsed into again.
+ * A psvr_fastq_t has a stream of its own and one owner at a time; several run beside each other and beside engines. */
+typedef struct psvr_fastq psvr_fastq_t;          /* device buffers of one parsed window, kept across calls while the next fits */
+typedef struct psvr_fastq_info {
+	int64_t n_pairs, used_bytes, total_bases, n_lines;   /* n_lines: complete lines seen (<= 8*max_pairs) */
+	int32_t stop;                                         /* 0 max_pairs, 1 max_bases, 2 the window ran out of lines */
+	int32_t reserved;
+} psvr_fastq_info_t;
+int  psvr_fastq_create(int device, psvr_fastq_t **out);
+int  psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_bytes, int at_end,
+                      int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info);
+int  psvr_fastq_download(const psvr_fastq_t *fq, uint64_t *line_start, uint16_t *name_end,
+                         int64_t *base_off, psvr_ori_t *ori, char *bases);   /* any pointer may be NULL */
+int  psvr_engine_upload_fastq(psvr_engine_t *eng, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs);
+void psvr_fastq_destroy(psvr_fastq_t *fq);
+
 /* ---- BGZF members on the device (the BAM output's compression) --------------------------------------------------------------
  * Replaces, for the drop-in command's BAM output, htslib's bgzf_compress (htslib bgzf.c: zlib deflate of 0xff00-byte blocks on the host,
  * reached from the reference's sam_write1 calls, read_realignment.cpp:166-176 -> bam_file.c).  `in` (host memory, n_bytes) is cut into

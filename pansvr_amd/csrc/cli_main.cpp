@@ -58,8 +58,16 @@ struct Opt {
 	bool deflate_device = false;                 // the BAM files' BGZF members (the sorted file's too) compressed on the first device, a wavefront per member (psvr_bgzf_compress_members)
 	bool inflate_device = false;                 // BAM input: its BGZF members inflated on the first device (psvr_bgzf_decompress) ...
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
+	bool parse_device = false;                   // FASTQ input: every window parsed on the first device (psvr_fastq_parse), the bases handed to the engine device to device
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 };
+
+// what --parse-device's usage text says about its speed
+#define PSVR_PARSE_DEVICE_MEASURED \
+	"Measured (1 M pairs = 830 MB of text, -t 16, three interleaved runs): it LOSES to the host parser: read stage\n" \
+	"                                 0.21-0.27 s against 0.08-0.12 s, SAM wall 0.36-0.44 s against 0.29-0.32 s, BAM with --deflate-device 0.44-0.55 s\n" \
+	"                                 against 0.44-0.46 s.  The kernels are not the cost (a 65 536-pair piece, 62 MB: newline passes 16 + 18 us, extract\n" \
+	"                                 116 us, all launches ~0.3 ms); the staging copy, the upload and the downloads are"
 
 static int usage()
 {
@@ -113,6 +121,11 @@ static int usage()
 	        "                                 does not win against --inflate-threads 16.  Whether the engine's launches queue behind the inflate\n"
 	        "                                 calls on the shared GPU has not been measured)\n"
 	        "        --inflate-threads   INT  ... or with zlib on INT host threads (also what takes over when the device route fails)\n"
+	        "        --parse-device           FASTQ input (a file, '-' or fq.gz): parse every window on the GPU (the only device of --devices): line index,\n"
+	        "                                 sequence lengths, bases and the comments' numbers; the window is staged in page-locked memory on the -t\n"
+	        "                                 threads, the bases reach the engine device to device, the pieces and the records are the same.  A call\n"
+	        "                                 that fails (a window of 4 GiB or more, a device error) leaves the rest of the input to the host threads.\n"
+	        "                                 " PSVR_PARSE_DEVICE_MEASURED "\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -200,7 +213,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
 	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members);
 	if (argc < 2 || (strcmp(argv[1], "aln") && strcmp(argv[1], "fc_aln"))) {
-		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n"
+		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n"
 		                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 		return 1;
 	}
@@ -208,7 +221,7 @@ int main(int argc, char **argv)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	bool sig_by_name = false;
@@ -243,6 +256,7 @@ int main(int argc, char **argv)
 		case 1010: o.sort = true; break;
 		case 1011: o.inflate_device = true; break;
 		case 1013: o.deflate_device = true; break;
+		case 1014: o.parse_device = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -258,6 +272,10 @@ int main(int argc, char **argv)
 		fprintf(stderr, "--deflate-device cannot be combined with %s: it is a compression route of its own for BAM output (a wavefront per BGZF member on the GPU)\n", sort_conflict);
 		return 1;
 	}
+	if (o.parse_device && o.devices.size() > 1) {
+		fprintf(stderr, "--parse-device cannot be combined with more than one entry in --devices: the parsed bases stay in the first device's memory and would have to travel between devices\n");
+		return 1;
+	}
 	if (argc - optind < 3) return usage();
 	if (!(o.thread_n >= 1 && o.thread_n <= 48)) { fprintf(stderr, "Input error: thread_n cannot be less than 1 or more than 48\n"); abort(); }   // xassert, rr.hpp:121
 	if (o.batch_pairs < 1) o.batch_pairs = 1;
@@ -267,6 +285,7 @@ int main(int argc, char **argv)
 	// position-sorted otherwise) and hands its FASTQ text through a pipe to the reader below; <header.sam> is WRITTEN from the BAM's header
 	const bool from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
 	if (!from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
+	if (from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
 	if (from_bam) {
 		psvr::BamReader rd;
 		if (!rd.open(o.reads.c_str())) { fprintf(stderr, "[panSVR-amd] %s\n", rd.error().c_str()); abort(); }
@@ -348,6 +367,8 @@ int main(int argc, char **argv)
 	};
 	struct Job {
 		FastqBatch fb;
+		psvr_fastq_t *fq = nullptr;        // --parse-device: the slot's parser (its device buffers hold the batch until the engine has taken it)
+		HostBuf stage;                     // ... and the page-locked copy of the window it parses
 		std::vector<Block> blk;
 		long long pair_base = 0;
 		std::vector<psvr::Bytes> mb, ob;   // formatted records of both files, per chunk of pairs
@@ -373,7 +394,11 @@ int main(int argc, char **argv)
 	long long n_batches = 0, n_ref_batches = 0, total_pairs = 0, rebase_iters = 0, d2h_bytes = 0;   // pieces run by the engine; reference-sized batches
 	size_t hbm_first = 0, hbm_last = 0;
 	EmitStats emit_stats;
+	// --parse-device: PSVR_PARSE_DEVICE_MAX_BYTES, the largest window that goes to the device (the tests send every window to the fallback with it)
+	const size_t parse_max_window = getenv("PSVR_PARSE_DEVICE_MAX_BYTES") ? (size_t)strtoull(getenv("PSVR_PARSE_DEVICE_MAX_BYTES"), nullptr, 10) : ~(size_t)0;
+	long long n_dev_pieces = 0, n_host_pieces = 0;       // pieces parsed on the device / on the host threads
 	std::thread reader([&]() {
+		bool on_device = o.parse_device && !from_bam;
 		long long loaded = 0, pair_base = 0, n_read_pieces = 0;
 		const long long kFirstPiece = 8192;
 		// the reference's batch: N_NEEDED pairs or MAX_read_size bases, whichever comes first (rr.cpp:24,109,126); it is read in pieces
@@ -389,7 +414,19 @@ int main(int argc, char **argv)
 			if (o.sub_pairs > 0 && n_read_pieces < 3 && (kFirstPiece << n_read_pieces) < want) want = kFirstPiece << n_read_pieces;
 			if (o.max_use_read - loaded < want) want = o.max_use_read - loaded;
 			double tw = walltime();
-			const bool ok = want > 0 && fq.read(J.fb, want, o.batch_bases - in_batch_bases, o.thread_n);
+			bool ok = false;
+			if (want > 0 && on_device) {
+				std::string why;
+				int r = -1;
+				if (!J.fq && psvr_fastq_create(o.devices[0], &J.fq)) why = psvr_last_error();
+				else r = fq.read_device(J.fb, want, o.batch_bases - in_batch_bases, o.thread_n, J.fq, J.stage, parse_max_window, &why);
+				if (r < 0) {
+					fprintf(stderr, "[panSVR-amd] FASTQ parse on the device failed (%s): parsing on the host threads from here on\n", why.c_str());
+					on_device = false;
+				} else ok = r > 0;
+			}
+			if (want > 0 && !on_device) ok = fq.read(J.fb, want, o.batch_bases - in_batch_bases, o.thread_n);
+			if (ok) ++(J.fb.dev ? n_dev_pieces : n_host_pieces);
 			t_read += walltime() - tw;
 			mark(0, n_read_pieces++, tw, walltime());
 			if (!ok) { J.last = true; J.batch_pairs_done = in_batch_pairs; set_state(J, 1); return; }
@@ -501,7 +538,7 @@ int main(int argc, char **argv)
 			const long long n = bk.hi - bk.lo;
 			const double t0 = walltime();
 			int rc = psvr_engine_set_stream_pos(eng[(size_t)d], pos);        // block 0 starts there; the others are moved below
-			if (!rc) rc = psvr_engine_upload(eng[(size_t)d], n, J.fb.bases, J.fb.base_off + 2 * bk.lo, J.fb.ori + 2 * bk.lo);
+			if (!rc) rc = J.fb.dev ? psvr_engine_upload_fastq(eng[(size_t)d], J.fb.dev, bk.lo, n) : psvr_engine_upload(eng[(size_t)d], n, J.fb.bases, J.fb.base_off + 2 * bk.lo, J.fb.ori + 2 * bk.lo);
 			const double t1 = walltime();
 			if (!rc) rc = psvr_engine_run(eng[(size_t)d], o.trace ? 1 : 0, nullptr);
 			if (cli_timing && d == 0) fprintf(stderr, "[panSVR-amd] batch %lld: engine ready %.1f ms after the batch, upload %.1f ms, run %.1f ms\n", n_batches, (t0 - tw) * 1e3, (t1 - t0) * 1e3, (walltime() - t1) * 1e3);
@@ -595,6 +632,7 @@ int main(int argc, char **argv)
 	}
 	if (frec) fclose(frec);
 	const double wall = walltime() - wall0;              // first FASTQ byte to the files closed; giving the HBM back is reported beside it, like the index load
+	for (Job &J : jobs) if (J.fq) psvr_fastq_destroy(J.fq), J.fq = nullptr;
 	for (int d = 0; d < D; ++d) if (eng[(size_t)d]) psvr_engine_destroy(eng[(size_t)d]);
 	for (int d = 0; d < D; ++d) {
 		bool dup = false;
@@ -616,8 +654,8 @@ int main(int argc, char **argv)
 	fprintf(stderr, "[panSVR-amd] wall: read+parse %.3f s, engine (upload+run+download) %.3f s, format %.3f s, write%s %.3f s\n", t_read, t_engine, t_format, o.sam ? "" : "+compress", t_write);
 	fprintf(stderr,
 	        "[panSVR-amd] e2e_json {\"pairs\":%lld,\"batches\":%lld,\"pieces\":%lld,\"devices\":%d,\"threads\":%d,\"wall_s\":%.4f,\"index_s\":%.4f,\"index_first_s\":%.4f,\"index_clone_s\":%.4f,\"read_parse_s\":%.4f,"
-	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f}\n",
+	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\"}\n",
 	        total_pairs, n_ref_batches, n_batches, D, o.thread_n, wall, t_index, t_idx_first, t_idx_clone, t_read, t_engine, t_exchange, rebase_iters, t_format, t_write, t_sort, t_sort_order, d2h_bytes, hbm_first, hbm_last,
-	        (long long)emit_stats.dropped, t_teardown);
+	        (long long)emit_stats.dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host");
 	return 0;
 }

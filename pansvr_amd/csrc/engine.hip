@@ -10,6 +10,7 @@
 #include <vector>
 #include "common.h"
 #include "engine_core.h"
+#include "fastq_parsed.h"
 #include "host_io.h"
 #include "index_build.h"
 #include "ksw_device.h"
@@ -1313,6 +1314,7 @@ struct GpuBE {
 	// a large upload that the caller waits for later (EngineCore::upload: the host's passes over the batch run beside it)
 	void h2d_start(void *d, const void *h, size_t n) { if (n) note(hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, stream)); }
 	void h2d_wait() { note(hipStreamSynchronize(stream)); synced(); }
+	void d2d_start(void *d, const void *s, size_t n) { if (n) note(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, stream)); }
 	// EngineCore::upload's pass over the batch (k_scan_batch); also the wait for the batch's copies, which are ahead of it on the stream
 	DevBuf scan_out;
 	bool scan_batch(const char *bases, const long long *off, const psvr_ori_t *ori, long long P, int match, int32_t *list, int *lmax, std::vector<int32_t> &out)
@@ -2217,6 +2219,25 @@ extern "C" int psvr_engine_upload(psvr_engine_t *e, int64_t n_pairs, const char 
 	if (!e->committed) { e->core.commit(); e->committed = true; }
 	e->compact_valid = false;
 	int rc = e->core.upload(n_pairs, bases, base_off, ori);
+	return engine_status(e, rc);
+}
+
+extern "C" int psvr_engine_upload_fastq(psvr_engine_t *e, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs)
+{
+	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
+	if (!e || !fq || !fq->valid || first_pair < 0 || n_pairs < 0 || first_pair + n_pairs > fq->last.n_pairs) return set_error(PSVR_ERR_ARG, "psvr_engine_upload_fastq: bad argument");
+	if (fq->device != e->ix->device)
+		return set_error(PSVR_ERR_ARG, "psvr_engine_upload_fastq: the text was parsed on device %d, the engine runs on device %d (the bases would have to travel between them)", fq->device, e->ix->device);
+	PSVR_HIP(hipSetDevice(e->ix->device));
+	e->be.stream = e->own;
+	if (!e->committed) { e->core.commit(); e->committed = true; }
+	e->compact_valid = false;
+	// where the block's bases start and end: the record of the parse knows it for the whole window, two offsets are read back otherwise
+	const int64_t *off = fq->base_off.as<int64_t>() + 2 * first_pair;
+	long long b0 = 0, b1 = fq->last.total_bases;
+	const bool whole = first_pair == 0 && n_pairs == fq->last.n_pairs;
+	if (!whole && n_pairs > 0 && !e->be.d2h({{&b0, off, 8}, {&b1, off + 2 * n_pairs, 8}})) return engine_status(e, PSVR_ERR_DEVICE);
+	const int rc = e->core.upload_device(n_pairs, fq->bases.as<char>(), off, fq->ori.as<psvr_ori_t>() + 2 * first_pair, b0, b1 - b0);
 	return engine_status(e, rc);
 }
 

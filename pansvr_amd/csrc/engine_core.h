@@ -338,10 +338,31 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 	}
 	int place_batch(long long n_pairs, const char *bases, const int64_t *base_off, const psvr_ori_t *ori)
 	{
-		P = n_pairs, R = 2 * n_pairs;
 		// a block of a larger batch may be handed over as a window of the batch's arrays: offsets then start at base_off[0] > 0
-		const long long b0 = R ? base_off[0] : 0;
-		total_bases = R ? base_off[R] - b0 : 0;
+		const long long b0 = n_pairs ? base_off[0] : 0;
+		return place_batch_from(n_pairs, b0, n_pairs ? base_off[2 * n_pairs] - b0 : 0, [&]() {
+			be.h2d_start(d_bases, bases + b0, total_bases);
+			be.h2d_start(d_off, base_off, (R + 1) * 8);
+			be.h2d_start(d_ori, ori, R * sizeof(psvr_ori_t));
+		});
+	}
+	// The same batch from arrays that are already in this device's memory (psvr_engine_upload_fastq: what psvr_fastq_parse left there).
+	// The host cannot read base_off there: the caller says where the window's bases start (b0) and how many there are.
+	int upload_device(long long n_pairs, const char *src_bases, const int64_t *src_off, const psvr_ori_t *src_ori, long long b0, long long n_bases)
+	{
+		const int rc = place_batch_from(n_pairs, b0, n_bases, [&]() {
+			be.d2d_start(d_bases, src_bases + b0, total_bases);
+			be.d2d_start(d_off, src_off, (R + 1) * 8);
+			be.d2d_start(d_ori, src_ori, R * sizeof(psvr_ori_t));
+		});
+		if (rc) be.h2d_wait();
+		return rc;
+	}
+	// start_copies() puts the three arrays' copies into d_bases / d_off / d_ori on the backend's queue
+	template <class Copies> int place_batch_from(long long n_pairs, long long b0, long long n_bases, Copies &&start_copies)
+	{
+		P = n_pairs, R = 2 * n_pairs;
+		total_bases = R ? n_bases : 0;
 		// The three arrays go to the device first, and the DEVICE looks at them (scan_batch: the longest read, the pairs whose reads will
 		// draw for N bases; early-out reads draw nothing, rr.cpp:414 returns first).  Until round 4 the host made those passes over every
 		// base before the transfer started -- 5 of an upload's 12 ms for 1 M pairs on eight threads, which a pipeline's three job slots
@@ -357,9 +378,7 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		V = 0;
 		int lmax = 0;
 		if (R > 0) {
-			be.h2d_start(d_bases, bases + b0, total_bases);
-			be.h2d_start(d_off, base_off, (R + 1) * 8);
-			be.h2d_start(d_ori, ori, R * sizeof(psvr_ori_t));
+			start_copies();
 			std::vector<int32_t> nl;                                     // (pair, counts) pairs as the device appended them
 			if (!be.scan_batch(d_bases - b0, d_off, d_ori, P, c.par.match, d_nlist, &lmax, nl)) { err = "device pass over the batch failed"; return PSVR_ERR_DEVICE; }
 			// (scan_batch has synchronised: the caller's arrays are free again)

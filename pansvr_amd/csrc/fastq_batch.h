@@ -220,6 +220,7 @@ struct FastqBatch {
 	std::vector<uint16_t> name_end;                  // per read: offset of the name's end inside its header line
 	HostBuf bases_buf, off_buf, ori_buf;             // what psvr_engine_upload reads (page-locked)
 	char *bases = nullptr; int64_t *base_off = nullptr; psvr_ori_t *ori = nullptr;
+	const psvr_fastq_t *dev = nullptr;               // --parse-device: the batch was parsed into this parser's device buffers; `bases` is then not filled
 	long long R = 0;
 	long long n_pairs() const { return R / 2; }
 
@@ -306,11 +307,12 @@ public:
 	bool read(FastqBatch &B, long long max_pairs, long long max_bases, int threads)
 	{
 		if (feed_) {
+			B.dev = nullptr;
 			if (!feed_->fill(B, max_pairs, max_bases)) return false;
 			if (!have_first_ && feed_->have_first) first_comment_ = feed_->first_comment, have_first_ = true;
 			return true;
 		}
-		B.R = 0;
+		B.R = 0, B.dev = nullptr;
 		B.ls.clear();
 		B.ls.push_back(0);
 		const size_t want_lines = (size_t)max_pairs * 8;
@@ -391,6 +393,62 @@ public:
 		if (!have_first_) { const char *b; int n; B.comment(0, b, n); first_comment_.assign(b, (size_t)n); have_first_ = true; }
 		return true;
 	}
+
+#ifndef PSVR_NO_ENGINE_LIB
+	// The same batch through the device's parser (psvr_fastq_parse; `panSVR aln --parse-device`): the window is cut as read() cuts it (the
+	// estimate from the previous batch, extended while the device reports that it ran out of lines before the input ended), brought into
+	// the page-locked `stage` on the threads (a mapped file and a vector are pageable, and a pageable copy to the device runs at a third
+	// of the link's rate) and parsed there; the line index, the name ends, the original alignments and the base offsets come back for
+	// the formatter, the bases stay in `fq`'s device memory for psvr_engine_upload_fastq (B.dev = fq, B.bases = nullptr).
+	// 1: a batch; 0: the end of the input; -1: the device route failed (*why says how) and nothing was consumed: read() takes over.
+	int read_device(FastqBatch &B, long long max_pairs, long long max_bases, int threads, psvr_fastq_t *fq, HostBuf &stage, size_t max_window, std::string *why)
+	{
+		B.R = 0, B.dev = nullptr;
+		const size_t step = est_pair_bytes_ * (size_t)max_pairs / 8 * 9 + (1 << 20);
+		if (!src_.mapped()) { B.own.clear(); src_.take_carry(B.own); }
+		auto fail = [&](const std::string &w) {
+			*why = w;
+			if (!src_.mapped()) src_.give_carry(B.own.data(), B.own.size());
+			return -1;
+		};
+		psvr_fastq_info_t info;
+		size_t text_len = 0;
+		bool at_end = false;
+		for (int round = 0;; ++round) {
+			if (src_.mapped()) {
+				size_t avail;
+				B.text = src_.window(&avail);
+				text_len = text_len + step < avail ? text_len + step : avail;
+				at_end = text_len == avail;
+			} else {
+				if ((round > 0 || B.own.size() < step) && !src_.more(B.own, step)) at_end = true;
+				B.text = B.own.data(), text_len = B.own.size();
+			}
+			if (text_len > max_window) return fail("a window of " + std::to_string(text_len) + " bytes, the limit is " + std::to_string(max_window));
+			char *pin = (char *)stage.reserve(text_len + 1);
+			const char *src = B.text;
+			parallel_ranges((long long)text_len, threads, [&](long long a, long long b) { memcpy(pin + a, src + a, (size_t)(b - a)); });
+			if (psvr_fastq_parse(fq, pin, (int64_t)text_len, at_end ? 1 : 0, max_pairs, max_bases, &info)) return fail(psvr_last_error());
+			if (info.stop != 2 || at_end) break;
+		}
+		const long long npairs = info.n_pairs, R = 2 * npairs;
+		if (npairs > 0) {
+			B.ls.resize((size_t)npairs * 8 + 1);
+			B.name_end.resize((size_t)R);
+			B.base_off = (int64_t *)B.off_buf.reserve((size_t)(R + 1) * 8);
+			B.ori = (psvr_ori_t *)B.ori_buf.reserve((size_t)R * sizeof(psvr_ori_t));
+			if (psvr_fastq_download(fq, B.ls.data(), B.name_end.data(), B.base_off, B.ori, nullptr)) return fail(psvr_last_error());
+		}
+		const size_t used = (size_t)info.used_bytes;
+		if (src_.mapped()) src_.consume(used);
+		else src_.give_carry(B.own.data() + used, text_len - used);
+		if (npairs == 0) return 0;
+		est_pair_bytes_ = used / (size_t)npairs + 1;
+		B.R = R, B.bases = nullptr, B.dev = fq;
+		if (!have_first_) { const char *b; int n; B.comment(0, b, n); first_comment_.assign(b, (size_t)n); have_first_ = true; }
+		return 1;
+	}
+#endif
 
 	// STAT_ of the very first read (load_reads, rr.cpp:134-148)
 	void stat_params(psvr_aln_params_t *p) const
