@@ -350,6 +350,42 @@ int  psvr_fastq_download(const psvr_fastq_t *fq, uint64_t *line_start, uint16_t 
 int  psvr_engine_upload_fastq(psvr_engine_t *eng, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs);
 void psvr_fastq_destroy(psvr_fastq_t *fq);
 
+/* ---- The main BAM file's records encoded on the device (step 2 of the batch seam, between the engine and the BGZF writer) -----------------
+ * Replaces, for a caller that parsed its FASTQ text with psvr_fastq_parse, the record formatting of output_BAM for the main output file
+ * (single_end_handler::output_BAM, src/PanSVgenerateVCF/read_realignment.cpp:479-536, reached from output_results :165-176): the BAM
+ * records of a run of pairs are made in device memory from the window a psvr_fastq_t holds (names, comments, bases, qualities, original
+ * alignments) and a set of results.  Per pair p of the run, one of three states:
+ *   0  nothing to write (gain == 0, or every read is skipped: primary == -1, primary == -2 under PSVR_EMIT_NOT_ORI, a chr_id that is
+ *      0xffffffff or outside the header, a position below 1)
+ *   1  bytes[pair_off[p], pair_off[p + 1]) hold the records of its reads (block_size first, as in a BAM stream; mate 0 first) -- exactly
+ *      what the command's host formatter writes for the pair
+ *   2  declined, no bytes: the caller formats the pair on the host.  A read that would be written has a name of length 0 or over 254, a
+ *      quality line that is not as long as the sequence line, a tab or NUL in its comment, an anchor string with a tab, a CIGAR of 0 or
+ *      more than 65535 operations or with an operator beyond 'X' -- or a result index that leaves the arrays it was given (cand_off +
+ *      primary / secondary, cigar_off + n_cigar, an anchor id outside [-1, n_anchor)).  Whatever the results hold, nothing outside the
+ *      given arrays is read.
+ * psvr_bam_emit_results takes the results from the caller (host arrays in the compact form of psvr_engine_download_compact: hdr[2 n_pairs],
+ * pairs[n_pairs], hdr.cand_off indexes cands[0, n_cands), cand.cigar_off indexes cigar[0, n_cigar); uploaded by the call, free again when it
+ * returns) for window pairs [first_pair, first_pair + n_pairs).  psvr_bam_emit_engine takes the results of eng's last run where they lie in
+ * HBM: eng's last upload must have been psvr_engine_upload_fastq(eng, fq, ...), run since, and fq not parsed into since (otherwise
+ * PSVR_ERR_ARG, and psvr_last_error() says which; a psvr_fastq_t remembers how often it was parsed into).  Both run the same kernels.
+ * fq, the engine and the emitter's index must be on one device (PSVR_ERR_ARG otherwise); no device: PSVR_ERR_DEVICE.  *info, if not NULL,
+ * receives the run's totals.  The records stay on the device until the emitter's next run; psvr_bam_emit_download copies out
+ * bytes[0, n_bytes) (cap < n_bytes: PSVR_ERR_OVERFLOW), pair_off[n_pairs + 1] and pair_state[n_pairs]; any pointer may be NULL; a
+ * destination is host memory (page-locked or not) or memory of the emitter's device.  The index must outlive the emitter (its table of the
+ * anchors' strings is made on the device once per index, by the first psvr_bam_emit_create).  A psvr_bam_emit_t has a stream of its own and
+ * one owner at a time; several run beside each other and beside engines. */
+typedef struct psvr_bam_emit psvr_bam_emit_t;      /* device buffers of one emitted run of pairs + a stream; one owner at a time */
+typedef struct psvr_bam_emit_info { int64_t n_bytes, n_records, n_written_pairs, n_declined_pairs; } psvr_bam_emit_info_t;
+#define PSVR_EMIT_NOT_ORI 1                         /* -Q: reads whose primary is the original alignment are not written */
+int  psvr_bam_emit_create(const psvr_index_t *idx, psvr_bam_emit_t **out);
+int  psvr_bam_emit_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs,
+                           const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs, const psvr_cand_t *cands, int64_t n_cands,
+                           const uint32_t *cigar, int64_t n_cigar, int32_t flags, psvr_bam_emit_info_t *info);
+int  psvr_bam_emit_engine(psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fastq_t *fq, int32_t flags, psvr_bam_emit_info_t *info);
+int  psvr_bam_emit_download(const psvr_bam_emit_t *em, void *bytes, int64_t cap, int64_t *pair_off, uint8_t *pair_state);
+void psvr_bam_emit_destroy(psvr_bam_emit_t *em);
+
 /* ---- BGZF members on the device (the BAM output's compression) --------------------------------------------------------------
  * Replaces, for the drop-in command's BAM output, htslib's bgzf_compress (htslib bgzf.c: zlib deflate of 0xff00-byte blocks on the host,
  * reached from the reference's sam_write1 calls, read_realignment.cpp:166-176 -> bam_file.c).  `in` (host memory, n_bytes) is cut into

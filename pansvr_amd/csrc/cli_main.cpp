@@ -59,6 +59,7 @@ struct Opt {
 	bool inflate_device = false;                 // BAM input: its BGZF members inflated on the first device (psvr_bgzf_decompress) ...
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
 	bool parse_device = false;                   // FASTQ input: every window parsed on the first device (psvr_fastq_parse), the bases handed to the engine device to device
+	bool emit_device = false;                    // ... and the main BAM file's records encoded there (psvr_bam_emit_engine); implies parse_device
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 };
 
@@ -213,7 +214,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
 	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members);
 	if (argc < 2 || (strcmp(argv[1], "aln") && strcmp(argv[1], "fc_aln"))) {
-		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n"
+		fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
 		                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 		return 1;
 	}
@@ -221,7 +222,7 @@ int main(int argc, char **argv)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	bool sig_by_name = false;
@@ -257,6 +258,7 @@ int main(int argc, char **argv)
 		case 1011: o.inflate_device = true; break;
 		case 1013: o.deflate_device = true; break;
 		case 1014: o.parse_device = true; break;
+		case 1015: o.emit_device = o.parse_device = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -270,6 +272,14 @@ int main(int argc, char **argv)
 	}
 	if (o.deflate_device && sort_conflict) {
 		fprintf(stderr, "--deflate-device cannot be combined with %s: it is a compression route of its own for BAM output (a wavefront per BGZF member on the GPU)\n", sort_conflict);
+		return 1;
+	}
+	if (o.emit_device && o.devices.size() > 1) {
+		fprintf(stderr, "--emit-device cannot be combined with more than one entry in --devices: the records are encoded from the text and the results in the first device's memory\n");
+		return 1;
+	}
+	if (o.emit_device && o.sam) {
+		fprintf(stderr, "--emit-device cannot be combined with -S: the device encodes BAM records, SAM text is formatted on the host threads\n");
 		return 1;
 	}
 	if (o.parse_device && o.devices.size() > 1) {
@@ -286,6 +296,7 @@ int main(int argc, char **argv)
 	const bool from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
 	if (!from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
 	if (from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
+	if (from_bam && o.emit_device) fprintf(stderr, "[panSVR-amd] --emit-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
 	if (from_bam) {
 		psvr::BamReader rd;
 		if (!rd.open(o.reads.c_str())) { fprintf(stderr, "[panSVR-amd] %s\n", rd.error().c_str()); abort(); }
@@ -369,6 +380,9 @@ int main(int argc, char **argv)
 		FastqBatch fb;
 		psvr_fastq_t *fq = nullptr;        // --parse-device: the slot's parser (its device buffers hold the batch until the engine has taken it)
 		HostBuf stage;                     // ... and the page-locked copy of the window it parses
+		psvr_bam_emit_t *bem = nullptr;    // --emit-device: the slot's record encoder; the piece's records, offsets and states once downloaded (page-locked)
+		HostBuf em_bytes, em_off, em_state;
+		bool emitted = false;              // this piece's main records were encoded on the device
 		std::vector<Block> blk;
 		long long pair_base = 0;
 		std::vector<psvr::Bytes> mb, ob;   // formatted records of both files, per chunk of pairs
@@ -397,6 +411,10 @@ int main(int argc, char **argv)
 	// --parse-device: PSVR_PARSE_DEVICE_MAX_BYTES, the largest window that goes to the device (the tests send every window to the fallback with it)
 	const size_t parse_max_window = getenv("PSVR_PARSE_DEVICE_MAX_BYTES") ? (size_t)strtoull(getenv("PSVR_PARSE_DEVICE_MAX_BYTES"), nullptr, 10) : ~(size_t)0;
 	long long n_dev_pieces = 0, n_host_pieces = 0;       // pieces parsed on the device / on the host threads
+	std::atomic<bool> emit_on_device(o.emit_device && !from_bam);   // --emit-device, until an emit call (engine stage) or its download (formatter stage) fails
+	long long n_emit_pieces = 0, n_emit_host_pieces = 0;   // (the formatter stage's) pieces whose main records came from the device / from the host formatter
+	// pairs the encoder took (state 0 or 1) / declined (state 2) / whose chunk was spliced in from the device's bytes (a chunk with a declined pair is formatted on the host whole)
+	long long emit_device_pairs = 0, emit_declined_pairs = 0, emit_spliced_pairs = 0;
 	std::thread reader([&]() {
 		bool on_device = o.parse_device && !from_bam;
 		long long loaded = 0, pair_base = 0, n_read_pieces = 0;
@@ -471,18 +489,42 @@ int main(int argc, char **argv)
 			mb.resize((size_t)nchunk), ob.resize((size_t)nchunk);
 			for (auto &v : mb) v.clear();        // (capacity is kept from the slot's previous batch: no growth copies in steady state)
 			for (auto &v : ob) v.clear();
-			std::atomic<long long> next(0);
+			// --emit-device: the piece's main records come from the device; a chunk with a declined pair goes through the host formatter whole, so
+			// what it reports and drops is what it always did
+			const uint8_t *dev_bytes = nullptr, *dev_state = nullptr;
+			const int64_t *dev_off = nullptr;
+			if (J.emitted) {
+				int64_t *off = (int64_t *)J.em_off.reserve((size_t)(P + 1) * 8);
+				uint8_t *stt = (uint8_t *)J.em_state.reserve((size_t)P + 1);
+				int rc = psvr_bam_emit_download(J.bem, nullptr, 0, off, stt);
+				uint8_t *bytes = rc ? nullptr : (uint8_t *)J.em_bytes.reserve((size_t)off[P] + 1);
+				if (!rc) rc = psvr_bam_emit_download(J.bem, bytes, off[P], nullptr, nullptr);
+				if (rc) { fprintf(stderr, "[panSVR-amd] BAM records on the device failed (%s): formatting on the host threads from here on\n", psvr_last_error()); J.emitted = false, emit_on_device = false; }
+				else dev_bytes = bytes, dev_off = off, dev_state = stt;
+			}
+			++(J.emitted ? n_emit_pieces : n_emit_host_pieces);
+			std::atomic<long long> next(0), n_dev_pairs(0), n_declined(0), n_spliced(0);
 			auto work = [&]() {
 				for (long long ci = next++; ci < nchunk; ci = next++) {
 					const long long p0 = ci * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+					bool host_main = !dev_state;
+					if (dev_state) {
+						long long nd = 0;
+						for (long long p = p0; p < p1; ++p) nd += dev_state[p] == 2;
+						n_declined += nd, n_dev_pairs += (p1 - p0) - nd;
+						if (nd) host_main = true;
+						else mb[(size_t)ci].insert(mb[(size_t)ci].end(), dev_bytes + dev_off[p0], dev_bytes + dev_off[p1]), n_spliced += p1 - p0;
+					}
 					size_t bi = 0;
 					for (long long p = p0; p < p1; ++p) {
 						while (p >= J.blk[bi].hi) ++bi;
-						em.main_pair(J.fb, J.blk[bi].V, p, mb[(size_t)ci]), em.ori_pair(J.fb, J.blk[bi].V, p, ob[(size_t)ci]);
+						if (host_main) em.main_pair(J.fb, J.blk[bi].V, p, mb[(size_t)ci]);
+						em.ori_pair(J.fb, J.blk[bi].V, p, ob[(size_t)ci]);
 					}
 				}
 			};
 			thread_pool().run((int)(o.thread_n < nchunk ? o.thread_n : nchunk), [&](int) { work(); });
+			emit_device_pairs += n_dev_pairs, emit_declined_pairs += n_declined, emit_spliced_pairs += n_spliced;
 			t_format += walltime() - tw;
 			mark(2, n_fmt_pieces++, tw, walltime());
 			set_state(J, 3);
@@ -545,6 +587,14 @@ int main(int argc, char **argv)
 			if (rc) rcs[(size_t)d] = rc, errs[(size_t)d] = psvr_last_error();
 		});
 		fail_check();
+		// --emit-device: the main file's records of the piece, encoded right after the run where the window's text and the results lie (one device: no exchange below), before either is given its next piece
+		J.emitted = false;
+		if (emit_on_device && J.fb.dev) {
+			int rc = J.bem ? 0 : psvr_bam_emit_create(idx[0], &J.bem);
+			if (!rc) rc = psvr_bam_emit_engine(J.bem, eng[0], J.fb.dev, o.not_ori ? PSVR_EMIT_NOT_ORI : 0, nullptr);
+			if (rc) { fprintf(stderr, "[panSVR-amd] BAM records on the device failed (%s): formatting on the host threads from here on\n", psvr_last_error()); emit_on_device = false; }
+			else J.emitted = true;
+		}
 		// the draw-order exchange: block d starts where block d-1 ended.  A block's draw count almost never depends on where it
 		// starts, so one pass of moves normally settles it; the loop covers the rest.
 		if (D > 1) {
@@ -632,6 +682,7 @@ int main(int argc, char **argv)
 	}
 	if (frec) fclose(frec);
 	const double wall = walltime() - wall0;              // first FASTQ byte to the files closed; giving the HBM back is reported beside it, like the index load
+	for (Job &J : jobs) if (J.bem) psvr_bam_emit_destroy(J.bem), J.bem = nullptr;
 	for (Job &J : jobs) if (J.fq) psvr_fastq_destroy(J.fq), J.fq = nullptr;
 	for (int d = 0; d < D; ++d) if (eng[(size_t)d]) psvr_engine_destroy(eng[(size_t)d]);
 	for (int d = 0; d < D; ++d) {
@@ -654,8 +705,8 @@ int main(int argc, char **argv)
 	fprintf(stderr, "[panSVR-amd] wall: read+parse %.3f s, engine (upload+run+download) %.3f s, format %.3f s, write%s %.3f s\n", t_read, t_engine, t_format, o.sam ? "" : "+compress", t_write);
 	fprintf(stderr,
 	        "[panSVR-amd] e2e_json {\"pairs\":%lld,\"batches\":%lld,\"pieces\":%lld,\"devices\":%d,\"threads\":%d,\"wall_s\":%.4f,\"index_s\":%.4f,\"index_first_s\":%.4f,\"index_clone_s\":%.4f,\"read_parse_s\":%.4f,"
-	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\"}\n",
+	        "\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\",\"emitter\":\"%s\",\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld}\n",
 	        total_pairs, n_ref_batches, n_batches, D, o.thread_n, wall, t_index, t_idx_first, t_idx_clone, t_read, t_engine, t_exchange, rebase_iters, t_format, t_write, t_sort, t_sort_order, d2h_bytes, hbm_first, hbm_last,
-	        (long long)emit_stats.dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host");
+	        (long long)emit_stats.dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host", n_emit_pieces ? (n_emit_host_pieces ? "device+host" : "device") : "host", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs);
 	return 0;
 }

@@ -10,6 +10,7 @@
 #include <vector>
 #include "common.h"
 #include "engine_core.h"
+#include "bam_emit_hooks.h"
 #include "fastq_parsed.h"
 #include "host_io.h"
 #include "index_build.h"
@@ -1811,6 +1812,10 @@ struct psvr_index {
 	DevBuf ref_seq, seq, seqf, pos, posp, hash, off, kmer, chr_end, chr_idx, sv, occ, uid_hint, bloom, hitrec;
 	DevIndex dev;
 	int64_t bytes = 0;
+	// the anchors' strings for the record encoder (bam_emit.hip), made on first use
+	mutable std::mutex emit_mu;
+	mutable bool emit_ready = false;
+	mutable DevBuf emit_text, emit_off, emit_tab;
 };
 
 __global__ void k_scatter_counts(const uint32_t *ids, const uint32_t *cnts, long long n, int32_t *dense)
@@ -2177,6 +2182,11 @@ struct psvr_engine {
 	// the engine's own queue (non-blocking: engines of one process, on one device or several, run beside each other); a caller's
 	// stream, when psvr_engine_run / _rebase is given one, takes its place for that call
 	hipStream_t own = nullptr;
+	// where the batch came from when it came from a parsed window (psvr_engine_upload_fastq), and whether it has been run: psvr_bam_emit_engine asks
+	const psvr_fastq *src_fq = nullptr;
+	int64_t src_first = 0, src_n = 0;
+	uint64_t src_generation = 0;
+	bool ran = false;
 	explicit psvr_engine(const psvr_index *i) : ix(i), core(be) {}
 };
 
@@ -2218,6 +2228,7 @@ extern "C" int psvr_engine_upload(psvr_engine_t *e, int64_t n_pairs, const char 
 	e->be.stream = e->own;
 	if (!e->committed) { e->core.commit(); e->committed = true; }
 	e->compact_valid = false;
+	e->src_fq = nullptr, e->ran = false;
 	int rc = e->core.upload(n_pairs, bases, base_off, ori);
 	return engine_status(e, rc);
 }
@@ -2232,13 +2243,16 @@ extern "C" int psvr_engine_upload_fastq(psvr_engine_t *e, const psvr_fastq_t *fq
 	e->be.stream = e->own;
 	if (!e->committed) { e->core.commit(); e->committed = true; }
 	e->compact_valid = false;
+	e->src_fq = nullptr, e->ran = false;
 	// where the block's bases start and end: the record of the parse knows it for the whole window, two offsets are read back otherwise
 	const int64_t *off = fq->base_off.as<int64_t>() + 2 * first_pair;
 	long long b0 = 0, b1 = fq->last.total_bases;
 	const bool whole = first_pair == 0 && n_pairs == fq->last.n_pairs;
 	if (!whole && n_pairs > 0 && !e->be.d2h({{&b0, off, 8}, {&b1, off + 2 * n_pairs, 8}})) return engine_status(e, PSVR_ERR_DEVICE);
 	const int rc = e->core.upload_device(n_pairs, fq->bases.as<char>(), off, fq->ori.as<psvr_ori_t>() + 2 * first_pair, b0, b1 - b0);
-	return engine_status(e, rc);
+	const int st = engine_status(e, rc);
+	if (!st) e->src_fq = fq, e->src_first = first_pair, e->src_n = n_pairs, e->src_generation = fq->generation;
+	return st;
 }
 
 extern "C" int psvr_engine_run(psvr_engine_t *e, int trace, void *stream)
@@ -2255,7 +2269,9 @@ extern "C" int psvr_engine_run(psvr_engine_t *e, int trace, void *stream)
 	e->be.synced();             // (a caller's stream is not looked at again after this call)
 	e->be.collect_timing();
 	e->committed = false;       // the rand streams advance when the next batch is uploaded (or a stream position is set)
-	return engine_status(e, rc);
+	const int st = engine_status(e, rc);
+	e->ran = st == PSVR_OK;
+	return st;
 }
 
 extern "C" int psvr_engine_set_stream_pos(psvr_engine_t *e, const int64_t pos[3])
@@ -2362,6 +2378,38 @@ extern "C" int psvr_engine_align_batch(psvr_engine_t *e, int64_t n_pairs, const 
 	rc = psvr_engine_run(e, trace, nullptr);
 	if (rc) return rc;
 	return psvr_engine_download(e, reads, pairs, cigar, cigar_cap, nullptr);
+}
+
+// ---- what the record encoder (bam_emit.hip) asks: see bam_emit_hooks.h
+int psvr::index_emit_tables(const psvr_index *ix, BeTables *T, int *device)
+{
+	std::lock_guard<std::mutex> lk(ix->emit_mu);
+	if (!ix->emit_ready) {
+		// (a failure below leaves emit_ready false; DevBuf::alloc frees what it holds first, so the next call starts over without a leak.  The caller's
+		// current device is put back: psvr_bam_emit_create sets the one it needs itself)
+		int cur = -1;
+		(void)hipGetDevice(&cur);
+		struct Back { int d; ~Back() { if (d >= 0) (void)hipSetDevice(d); } } back{cur};
+		PSVR_HIP(hipSetDevice(ix->device));
+		BeTableHost h;
+		h.build((int)ix->host.svh.size(), [&](int i) { return ix->host.svh[(size_t)i].vcf_print_string.c_str(); }, [&](int i) { return ix->host.svh[(size_t)i].vcf_id.c_str(); });
+		PSVR_HIP(ix->emit_text.alloc(h.text.size())); PSVR_HIP(ix->emit_off.alloc(h.off.size() * 4)); PSVR_HIP(ix->emit_tab.alloc(h.tab.size()));
+		PSVR_HIP(hipMemcpy(ix->emit_text.p, h.text.data(), h.text.size(), hipMemcpyHostToDevice));
+		PSVR_HIP(hipMemcpy(ix->emit_off.p, h.off.data(), h.off.size() * 4, hipMemcpyHostToDevice));
+		PSVR_HIP(hipMemcpy(ix->emit_tab.p, h.tab.data(), h.tab.size(), hipMemcpyHostToDevice));
+		ix->emit_ready = true;
+	}
+	T->text = ix->emit_text.as<char>(), T->off = ix->emit_off.as<uint32_t>(), T->tab = ix->emit_tab.as<uint8_t>();
+	T->n_anchor = (int32_t)ix->host.svh.size(), T->n_header = ix->host.n_header;
+	*device = ix->device;
+	return PSVR_OK;
+}
+void psvr::engine_emit_view(const psvr_engine *e, EngineEmitView *v)
+{
+	const Ctx &c = e->core.c;
+	v->device = e->ix->device, v->ran = e->ran && e->core.P > 0;
+	v->fq = e->src_fq, v->first_pair = e->src_first, v->n_pairs = e->src_n, v->generation = e->src_generation;
+	v->hdr = c.rh, v->pairs = c.pres, v->cands = c.cand, v->n_cands = (int64_t)c.cw.cap, v->cig = c.cig.base, v->n_cig = (int64_t)c.cig.cap;
 }
 
 extern "C" int psvr_engine_stats(const psvr_engine_t *e, char *buf, size_t n)

@@ -7,6 +7,7 @@
 // Every phase hands over to the next at a kernel boundary.  Bounds: the newline passes read text[0, n) only (fq_newline_mask); line starts
 // are stored at indices <= cap only; every later pass reads lines between two stored starts <= n.
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include "../../include/psvr_engine.h"
 #include "common.h"
 #include "fastq_device.h"
@@ -86,6 +87,9 @@ __global__ __launch_bounds__(256) void k_fq_extract(const char *text, const uint
 	fq_extract_read(g, text, line_start, (const int64_t *)base_off, r, bases, name_end, ori);
 }
 
+// psvr_fastq::generation
+static uint64_t fq_next_generation() { static std::atomic<uint64_t> g(0); return ++g; }
+
 static inline unsigned fq_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 } // namespace psvr
@@ -100,7 +104,7 @@ extern "C" int psvr_fastq_create(int device, psvr_fastq_t **out)
 	if (!out || device < 0) return set_error(PSVR_ERR_ARG, "psvr_fastq_create: bad argument");
 	PSVR_HIP(hipSetDevice(device));
 	psvr_fastq *fq = new psvr_fastq;
-	fq->device = device;
+	fq->device = device, fq->generation = fq_next_generation();
 	hipError_t e = hipStreamCreateWithFlags(&fq->stream, hipStreamNonBlocking);
 	if (e == hipSuccess) e = hipHostMalloc((void **)&fq->h_info, sizeof(psvr_fastq_info_t), hipHostMallocDefault);
 	if (e != hipSuccess) { psvr_fastq_destroy(fq); return set_error(PSVR_ERR_DEVICE, "psvr_fastq_create: %s", hipGetErrorString(e)); }
@@ -123,7 +127,7 @@ extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_by
 	if (!fq || !info || n_bytes < 0 || max_pairs < 0 || (n_bytes > 0 && !text)) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse: bad argument");
 	if (n_bytes >= ((int64_t)1 << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_fastq_parse: a window of %lld bytes, offsets inside a call are 32-bit (at most 2^32 - 1 bytes)", (long long)n_bytes);
 	PSVR_HIP(hipSetDevice(fq->device));
-	fq->valid = false;
+	fq->valid = false, fq->generation = fq_next_generation();
 	const uint64_t n = (uint64_t)n_bytes, cap = fq_line_cap(n, max_pairs);
 	const int64_t ntile = (int64_t)((n + kFqTileBytes - 1) / kFqTileBytes), p_cap = fq_pair_cap(n, max_pairs), r_cap = 2 * p_cap;
 	const size_t tmp_a = scan_tmp_bytes(1, ntile + 1), tmp_b = scan_tmp_bytes(1, r_cap + 1);

@@ -49,12 +49,14 @@ struct HostIndex {
 	std::vector<SvDev> sv;
 	std::vector<SvHost> svh;
 	int chr_file_n = 0;
+	int n_header = 0;                         // @SQ names of the original genome header that parse_chr was given
 
 	bool parse_chr(const std::string &text, const std::vector<std::string> &header_names, std::string *err)
 	{
 		// the reference xcalloc()s deBGA_INDEX (rr.cpp:36) so chr_file_n starts at 0, names/ends fill from slot 0
 		// and chr_end_n[0] is then overwritten with START_POS_REF + 1 (deBGA_index.cpp:60-72)
 		chr_names.clear(), chr_end_n.clear(), chr_file_n = 0;
+		n_header = (int)header_names.size();
 		size_t p = 0;
 		uint32_t line_n = 0;
 		while (p < text.size()) {

@@ -1,0 +1,78 @@
+"""`panSVR aln` end to end with the record encoder on the host threads and on the device, on the bench batch written as FASTQ (bench.py's
+workload: 10 000 anchors, seed 11; the reads of rank 0, seed 13) in RAM-backed storage.  The routes --deflate-device,
+--parse-device --deflate-device and --emit-device --deflate-device, and the last two with --sort, run interleaved `--reps` times, each
+command in a child of its own; wall_s, read_parse_s, engine_s, format_s and write_s come from the command's e2e_json line.  The unsorted
+routes' inflated payloads are compared with the first route's.  One JSON line.
+    python tools/emit_device_e2e.py [--pairs 1000000] [--threads 16] [--reps 3] [--profile-dir DIR]
+--profile-dir: one more run of the --emit-device route under `rocprofv3 --kernel-trace --stats` (kernel times only, no counters), its
+files left in DIR."""
+import argparse
+import gzip
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+CLI = os.path.join(ROOT, "pansvr_amd", "bin", "panSVR")
+HEADER = "@SQ\tSN:chr1\tLN:250000000\n@SQ\tSN:chr2\tLN:250000000\n"
+ROUTES = (("deflate_device", ["--deflate-device"]), ("parse_device", ["--parse-device", "--deflate-device"]), ("emit_device", ["--emit-device", "--deflate-device"]),
+          ("parse_device_sort", ["--parse-device", "--deflate-device", "--sort"]), ("emit_device_sort", ["--emit-device", "--deflate-device", "--sort"]))
+KEYS = ("wall_s", "read_parse_s", "engine_s", "format_s", "write_s", "sort_s", "emitter", "emit_device_pairs", "emit_declined_pairs", "parser", "pieces")
+
+
+def run(cmd, timeout):
+    r = subprocess.run(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout)
+    err = r.stderr.decode()
+    if r.returncode != 0:
+        raise SystemExit("%s failed (%d):\n%s" % (" ".join(cmd[:3]), r.returncode, err[-2000:]))
+    j = json.loads([l for l in err.split("\n") if "e2e_json" in l][-1].split("e2e_json ", 1)[1])
+    return {k: j[k] for k in KEYS}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pairs", type=int, default=1000000)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--profile-dir", default=None)
+    a = ap.parse_args()
+    import bench_data
+    tmp = tempfile.mkdtemp(prefix="psvr_emit_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    try:
+        anc = bench_data.make_anchors(10000, seed=11)
+        bench_data.write_index_dir(bench_data.build_index_cli(anc, dense=False), os.path.join(tmp, "idx"))
+        bases, base_off, ori, isize = bench_data.make_reads(anc, a.pairs, seed=13)
+        fq = os.path.join(tmp, "block.fq")
+        bench_data.write_fastq(fq, bases, base_off, ori, isize, procs=min(16, os.cpu_count() or 1))
+        del bases, base_off, ori, isize
+        with open(os.path.join(tmp, "header.sam"), "w") as f:
+            f.write(HEADER)
+        pos = [os.path.join(tmp, "idx"), fq, os.path.join(tmp, "header.sam")]
+        res = {"pairs": a.pairs, "threads": a.threads, "fastq_bytes": os.path.getsize(fq)}
+        print("data ready", file=sys.stderr, flush=True)
+        ref = None
+        for rep in range(a.reps):
+            for name, flags in ROUTES:
+                o, p = os.path.join(tmp, "o.bam"), os.path.join(tmp, "p.bam")
+                res.setdefault(name, []).append(run([CLI, "aln", "-t", str(a.threads), "-o", o, "-p", p] + flags + pos, 600))
+                print(name, res[name][-1], file=sys.stderr, flush=True)
+                if rep == 0 and "--sort" not in flags:
+                    pay = gzip.open(o, "rb").read()
+                    ref = pay if ref is None else ref
+                    res.setdefault("same_payload", []).append(pay == ref)
+        if a.profile_dir:
+            os.makedirs(a.profile_dir, exist_ok=True)
+            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.profile_dir, "-o", "emit_device", "--output-format", "csv", "--", CLI, "aln", "-t", str(a.threads),
+                            "-o", os.path.join(tmp, "o.bam"), "-p", os.path.join(tmp, "p.bam"), "--emit-device", "--deflate-device"] + pos, stdout=subprocess.DEVNULL,
+                           stderr=subprocess.DEVNULL, timeout=600, check=True)
+        print(json.dumps(res), flush=True)
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()
