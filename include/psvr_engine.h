@@ -207,6 +207,9 @@ typedef struct psvr_vertex_mem {            /* vertex_MEM, deBGA_index.hpp:24-58
  * read_bits[word_off[i]]; every read needs ceil(len / 32) + 1 words (the reference's read_bit arrays are padded the same way) */
 int psvr_seed_mem_batch(const psvr_index_t *idx, int64_t n, const uint64_t *kmer_index, const uint64_t *read_bits, int64_t n_words,
                         const int64_t *word_off, const uint32_t *read_off, const uint32_t *read_len, psvr_vertex_mem_t *out);
+/* test seam: the Bloom filter over the index's 20-mers as built on the device (aln_device.h bloom_slot), copied to the host;
+ * n_words = 0 only reports its size (64-bit words) and the shift of its word hash */
+int psvr_index_bloom_read(const psvr_index_t *idx, uint64_t *words, int64_t n_words, int64_t *n_words_out, uint32_t *shift_out);
 
 /* ------------------------------------------------------------------------------------------
  * Seam B1: one batch of read pairs through seeding -> chaining -> extension DP -> pairing.

@@ -66,7 +66,9 @@ struct DevIndex {
 	// twice the share of it stays in an XCD's 4 MiB L2 -- a probe is one random 64-byte sector either way, and those sectors are what
 	// bounds the seeding kernel --, and it answers for the 20-mer itself, not for its 14-base bucket: a read k-mer that differs from an
 	// indexed one in its last six bases (every k-mer over a mismatch) passes the bitmap and fails here.
-	const uint64_t *bloom; uint32_t bloom_shift;    // word = (kmer * K) >> bloom_shift
+	// The word is addressed by the canonical form min(kmer, rc20(kmer)), the bits by the orientation (bloom_slot2): the k-mers the two
+	// strands of a read look up at mirrored offsets share their word, so one load answers both (seed_pair_answers).
+	const uint64_t *bloom; uint32_t bloom_shift;    // word = (min(kmer, rc20(kmer)) * K) >> bloom_shift
 	// optional: per index entry (22-mer occurrence) what UNITIG_MEM_search derives from it -- its position in the unipath sequence array, its
 	// unipath, the room to the unipath's two ends, the unipath's number of reference positions -- in one 32-byte record.  Looked up per hit
 	// these are off[hit], two bracket-table entries, three or four steps of a bisection over the unipath starts, the two starts again and
@@ -246,13 +248,47 @@ PSVR_HD bool bucket_occupied(const DevIndex &ix, uint64_t h)
 #endif
 }
 
+// reverse complement of a 20-mer as get_kmer returns it (40 bits, base 0 in the top two)
+PSVR_HD uint64_t rc20(uint64_t x)
+{
+	x = ~x;
+	x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+	x = ((x >> 4) & 0x0f0f0f0f0f0f0f0full) | ((x & 0x0f0f0f0f0f0f0f0full) << 4);
+	return __builtin_bswap64(x) >> (64 - 2 * kLenKmer);
+}
+// The Bloom filter addresses a 20-mer by its canonical form c = min(x, rc20(x)), so a k-mer and its reverse complement -- what the two
+// strands of a read look up at mirrored offsets -- share one 64-bit word, one sector.  The three bits inside the word come from one of
+// two disjoint sets of 6-bit fields of the second hash: `lo` for the orientation that IS the canonical form, `hi` for the other one
+// (a palindrome is its own canonical form: `lo`), so the word still answers for the 20-mer as indexed, not for its reverse complement.
+PSVR_HD uint64_t bloom_hash(uint64_t c, uint32_t shift, uint64_t &word)
+{
+	const uint64_t h = c * 0x9E3779B97F4A7C15ull;
+	word = h >> shift;
+	return (h ^ (h >> 32)) * 0xD6E8FEB86659FD93ull;
+}
+PSVR_HD void bloom_masks(uint64_t g, uint64_t &lo, uint64_t &hi)
+{
+	lo = (1ull << (g >> 58)) | (1ull << ((g >> 52) & 63)) | (1ull << ((g >> 46) & 63));
+	hi = (1ull << ((g >> 40) & 63)) | (1ull << ((g >> 34) & 63)) | (1ull << ((g >> 28) & 63));
+}
+// word of a 20-mer and the bit masks of the k-mer itself and of its reverse complement
+PSVR_HD void bloom_slot2(uint64_t kmer, uint32_t shift, uint64_t &word, uint64_t &mask, uint64_t &mask_rc)
+{
+	const uint64_t r = rc20(kmer);
+	uint64_t lo, hi;
+	bloom_masks(bloom_hash(kmer < r ? kmer : r, shift, word), lo, hi);
+	mask = kmer <= r ? lo : hi, mask_rc = r <= kmer ? lo : hi;
+}
 // word and bit mask of a 20-mer in the Bloom filter
 PSVR_HD void bloom_slot(uint64_t kmer, uint32_t shift, uint64_t &word, uint64_t &mask)
 {
-	const uint64_t h = kmer * 0x9E3779B97F4A7C15ull;
-	const uint64_t g = (h ^ (h >> 32)) * 0xD6E8FEB86659FD93ull;
-	word = h >> shift;
-	mask = (1ull << (g >> 58)) | (1ull << ((g >> 52) & 63)) | (1ull << ((g >> 46) & 63));
+	uint64_t mrc;
+	bloom_slot2(kmer, shift, word, mask, mrc);
+}
+// both orientations' answers from one loaded filter word: bit 0 the k-mer of bloom_slot2, bit 1 its reverse complement
+PSVR_HD uint32_t bloom_answers(uint64_t w, uint64_t mask, uint64_t mask_rc)
+{
+	return (uint32_t)((w & mask) == mask) | ((uint32_t)((w & mask_rc) == mask_rc) << 1);
 }
 // false: the index certainly holds no 22-mer that starts with this 20-mer (no false negatives: every indexed 20-mer has its bits set)
 PSVR_HD bool kmer_maybe_present(const DevIndex &ix, uint64_t kmer)
@@ -568,6 +604,62 @@ PSVR_HD uint32_t mem_for_hit(const DevIndex &ix, uint64_t hit, const uint64_t *r
 // are extended.  Written as `for off: probe; if hit: extend` the rare stages run on nearly every iteration with a handful
 // of lanes active.  Per strand the order of operations -- and every result -- is unchanged.
 // `rb_local`: optional copy of this strand's packed words in fast memory (the GPU kernel stages them in LDS).
+// On the device, with the words staged, the filter of stage 0 is asked up front for both strands of a read at once
+// (seed_pair_answers) where their offsets mirror; stage 0 then reads its bit.  Any filter without false negatives gives the same seeds.
+// The filter's answers for all T = (L - 20) / 5 + 1 offsets of a strand, bit t for offset 5t, when (L - 20) % 5 == 0: strand 1 is the
+// reverse complement of strand 0, so its k-mer at offset 5t is the reverse complement of strand 0's at offset 5(T-1-t) and both live in
+// one filter word.  The two lanes of a read (adjacent lanes, strand = lane parity) split the T words: strand 0 takes its even t,
+// strand 1 the t that mirror strand 0's odd ones; each forms the k-mers from its own packed words and tests its own orientation for
+// itself (`own`) and the other one for its partner's mirrored index (`other`); the partner's `other` completes a lane's `own`.
+// The loads of a batch are independent and issued together; a batch holds a word and its second hash per slot (4 registers).
+// Five per batch: k_seed runs at its 64-register limit, and a batch of seven spills inside the batch (84 B of scratch: 1.59 against 1.40 ms).
+static const int kSeedPairBatch = 5;
+PSVR_HD bool seed_pair_applies(const DevIndex &ix, int L)
+{
+	return ix.bloom && (L - kLenKmer) % kSeedStep == 0 && L - kLenKmer <= 63 * kSeedStep;
+}
+PSVR_HD void seed_pair_half(const DevIndex &ix, const uint64_t *rb, int T, int rev, uint64_t &own, uint64_t &other)
+{
+	const int t0 = rev ? (T & 1) : 0, cnt = rev ? T >> 1 : (T + 1) >> 1;
+	own = other = 0;
+	for (int j0 = 0; j0 < cnt; j0 += kSeedPairBatch) {
+		uint64_t w[kSeedPairBatch], g[kSeedPairBatch];
+		uint32_t canon = 0, pal = 0;                  // per slot: the k-mer is its canonical form / its own reverse complement
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+		for (int q = 0; q < kSeedPairBatch; ++q) {
+			const bool in = j0 + q < cnt;
+			const uint64_t x = get_kmer((uint32_t)((in ? t0 + 2 * (j0 + q) : t0) * kSeedStep), rb), r = rc20(x);
+			canon |= (uint32_t)(x <= r) << q, pal |= (uint32_t)(x == r) << q;
+			uint64_t word;
+			g[q] = bloom_hash(x < r ? x : r, ix.bloom_shift, word);
+			w[q] = in ? ix.bloom[word] : 0;
+		}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+#endif
+		for (int q = 0; q < kSeedPairBatch; ++q) {
+			if (j0 + q >= cnt) break;
+			const int t = t0 + 2 * (j0 + q);
+			uint64_t lo, hi;
+			bloom_masks(g[q], lo, hi);
+			const bool cn = (canon >> q) & 1, pl = (pal >> q) & 1;
+			const uint32_t a = bloom_answers(w[q], cn ? lo : hi, (pl || !cn) ? lo : hi);
+			own |= (uint64_t)(a & 1) << t, other |= (uint64_t)(a >> 1) << (T - 1 - t);
+		}
+	}
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+// every lane pair of the wavefront that gets here does so together: the choice is per read
+__device__ __forceinline__ uint64_t seed_pair_answers(const DevIndex &ix, const uint64_t *rb, int T, int rev)
+{
+	uint64_t own, other;
+	seed_pair_half(ix, rb, T, rev, own, other);
+	return own | (uint64_t)__shfl_xor((unsigned long long)other, 1);
+}
+#endif
+
 template <bool LOCAL> PSVR_HD void seed_strand_t(const Ctx &c, long long rs, const uint64_t *rb_local)
 {
 	const long long read = rs >> 1;
@@ -583,6 +675,15 @@ template <bool LOCAL> PSVR_HD void seed_strand_t(const Ctx &c, long long rs, con
 	// passes into the bump region behind the slots (rare: > 32 MEMs needs repeats)
 	long long base = rs * (long long)kMemSlot;
 	uint32_t total = 0, probes = 0;
+	// one look-up for both strands where the strands' offsets mirror and fit one mask; else (and on the host) the filter is asked per probe
+	bool paired = false;
+	uint64_t answers = 0;
+#if defined(__HIP_DEVICE_COMPILE__)
+	if (LOCAL && seed_pair_applies(ix, L) && !c.has_n4[read]) {
+		answers = seed_pair_answers(ix, rb, (L - kLenKmer) / kSeedStep + 1, rev);
+		paired = true;
+	}
+#endif
 	for (int pass = 0; pass < 3; ++pass) {            // 0: write into slot (counting), 1: count only (skipped), 2: fill arena slice
 		if (pass == 1) continue;
 		uint32_t n = 0, msr = 0, off = 0, nh = 0;
@@ -594,7 +695,7 @@ template <bool LOCAL> PSVR_HD void seed_strand_t(const Ctx &c, long long rs, con
 					if (off + kLenKmer - 1 <= msr || (is_str && seed_list_at(sl, (int)kn, rev, off) == 0)) { off += kSeedStep; continue; }
 					if (pass == 0) ++probes;
 					kmer = get_kmer(off, rb);
-					if (kmer_maybe_present(ix, kmer)) { stage = 1; break; }
+					if (paired ? (answers >> (off / kSeedStep)) & 1 : kmer_maybe_present(ix, kmer)) { stage = 1; break; }
 					off += kSeedStep;
 				}
 				if (stage != 1) break;

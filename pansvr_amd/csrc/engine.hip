@@ -1787,7 +1787,8 @@ __global__ void k_build_occupancy(const uint64_t *hash, uint32_t *occ, long long
 }
 
 // the Bloom filter over the index's 20-mers (kmer_maybe_present, aln_device.h): a thread per first-level bucket, which holds the 22-mers
-// whose first 14 bases are its number; the low 16 bits of an entry are the 22-mer's last 8 bases
+// whose first 14 bases are its number; the low 16 bits of an entry are the 22-mer's last 8 bases.  bloom_slot: the bits of the 20-mer
+// as indexed, in the word of its canonical form.
 __global__ void k_build_bloom(const uint64_t *hash, const uint32_t *kmer, long long nbuckets, unsigned long long *bloom, uint32_t shift)
 {
 	const long long h = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -2136,6 +2137,20 @@ extern "C" int psvr_seed_mem_batch(const psvr_index_t *ix, int64_t n, const uint
 	                   dout.as<psvr_vertex_mem_t>());
 	PSVR_HIP(hipGetLastError());
 	PSVR_HIP(hipMemcpy(out, dout.p, (size_t)n * sizeof(psvr_vertex_mem_t), hipMemcpyDeviceToHost));
+	return PSVR_OK;
+}
+
+// test seam: the device-built Bloom filter read back (n_words = 0 asks for the size only)
+extern "C" int psvr_index_bloom_read(const psvr_index_t *ix, uint64_t *words, int64_t n_words, int64_t *n_words_out, uint32_t *shift_out)
+{
+	if (!ix || n_words < 0 || (n_words && !words)) return set_error(PSVR_ERR_ARG, "psvr_index_bloom_read: bad argument");
+	const int64_t have = (int64_t)(ix->bloom.bytes / 8);
+	if (n_words_out) *n_words_out = have;
+	if (shift_out) *shift_out = ix->dev.bloom_shift;
+	if (n_words == 0) return PSVR_OK;
+	if (n_words != have) return set_error(PSVR_ERR_ARG, "psvr_index_bloom_read: the filter has %lld words", (long long)have);
+	PSVR_HIP(hipSetDevice(ix->device));
+	PSVR_HIP(hipMemcpy(words, ix->bloom.p, (size_t)have * 8, hipMemcpyDeviceToHost));
 	return PSVR_OK;
 }
 
