@@ -416,6 +416,44 @@ int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int3
                                void *out, int64_t out_cap, int64_t *out_bytes,
                                int64_t *member_off, int64_t member_cap, int64_t *n_members);
 
+/* ---- A BGZF stream that lives on the device (the hand-over from psvr_bam_emit_* to the member compressor) ------------------------------
+ * Joins the two sections above: a byte stream in HBM that is cut every member_bytes bytes (as in psvr_bgzf_compress_members: 256..0xff00,
+ * 0 = 0xff00) and whose members the same encoder makes, on the same process-wide buffers and stream.  The contract: concatenate the members
+ * every psvr_bgzf_stream_take of a stream returned, and the result is byte for byte what psvr_bgzf_compress_members returns for the
+ * concatenation of everything appended, at the same member_bytes -- however appends and takes were interleaved.
+ *   append        n_bytes of host memory (the BAM header, records the host formatted) behind what is pending; the bytes are free again when
+ *                 the call returns.
+ *   append_emit   bytes[pair_off[first_pair], pair_off[first_pair + n_pairs]) of em's last run, device to device: one kernel launch that
+ *                 reads the two offsets and the pending count where they lie in HBM, so the call queues and returns without a round trip.
+ *                 `em` MUST NOT BE RUN AGAIN (psvr_bam_emit_results / _engine) or destroyed UNTIL A LATER take, pending or recover ON `s`
+ *                 HAS RETURNED: until then the copy may still be reading its records.  A pair range outside the run, an emitter without a
+ *                 valid run, an emitter on another device: PSVR_ERR_ARG.  A range of zero bytes appends nothing.
+ *   pending       bytes appended and not yet taken (a wait for what is queued); < 0: minus a status.
+ *   take          compresses every whole member that is pending, with finish != 0 also the tail as a last, shorter member (a stream that
+ *                 ends on a member boundary gets no empty member; nothing pending: no members, PSVR_OK).  The members go to
+ *                 out[0, *out_bytes) (host memory), member_off / member_cap / n_members as in psvr_bgzf_compress_members (any may be NULL),
+ *                 *in_bytes = stream bytes consumed.  What stays pending is less than member_bytes and starts the next member.
+ *                 out_cap < psvr_bgzf_members_bound(pending, member_bytes), or more members than member_cap: PSVR_ERR_OVERFLOW and nothing
+ *                 is consumed.  One wait per call (a second, short one in front when an append_emit has been queued since the last call
+ *                 that waited: the count it left is then read back first).
+ *   recover       copies the pending bytes to bytes[0, *n_bytes) (host memory) and empties the stream: what a caller that gives the device
+ *                 route up continues from.  cap too small: PSVR_ERR_OVERFLOW, *n_bytes is set, nothing is lost.
+ * An append_emit that would leave the emitter's bytes or the stream's buffer is not made, and from the call that notices it on (the next one
+ * that reads the count back) every call answers PSVR_ERR_DEVICE; so does every call after one that failed while it changed the pending bytes.
+ * Device memory: the length of a pair range is known on the device only, so until the next call that waits every append_emit reserves room
+ * for em's WHOLE run behind what may be pending (the buffer grows by half on top); many short ranges of a large run between two waits cost
+ * ranges x run bytes of HBM -- ask `pending` in between, as the command does after every piece.
+ * The EOF marker block is the caller's.  A stream has one owner at a time; its calls are serialised with psvr_bgzf_compress_members. */
+typedef struct psvr_bgzf_stream psvr_bgzf_stream_t;
+int     psvr_bgzf_stream_create(int device, int32_t member_bytes, psvr_bgzf_stream_t **out);
+int     psvr_bgzf_stream_append(psvr_bgzf_stream_t *s, const void *bytes, int64_t n_bytes);
+int     psvr_bgzf_stream_append_emit(psvr_bgzf_stream_t *s, const psvr_bam_emit_t *em, int64_t first_pair, int64_t n_pairs);
+int64_t psvr_bgzf_stream_pending(psvr_bgzf_stream_t *s);
+int     psvr_bgzf_stream_take(psvr_bgzf_stream_t *s, int finish, void *out, int64_t out_cap, int64_t *out_bytes,
+                              int64_t *member_off, int64_t member_cap, int64_t *n_members, int64_t *in_bytes);
+int     psvr_bgzf_stream_recover(psvr_bgzf_stream_t *s, void *bytes, int64_t cap, int64_t *n_bytes);
+void    psvr_bgzf_stream_destroy(psvr_bgzf_stream_t *s);
+
 /* ---- BGZF members inflated on the device (the BAM input's decompression) --------------------------------------------------------------
  * Replaces, for the commands that read a BAM (`panSVR signal`, `panSVR sort`, `panSVR aln` with a *.bam read file), htslib's
  * bgzf_read_block -> inflate_block (htslib bgzf.c: zlib inflate of one member at a time on the calling thread).

@@ -62,3 +62,60 @@ def bgzf_compress(data, member_bytes=0xff00, device=0):
     check(L.psvr_bgzf_compress_members(C.c_int(device), buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.c_int32(member_bytes), out.ctypes.data_as(C.c_void_p),
                                        C.c_int64(cap), C.byref(total), offs.ctypes.data_as(C.c_void_p), C.c_int64(nm_cap), C.byref(nm)))
     return out[:total.value], offs[:nm.value + 1]
+
+
+class BgzfStream:
+    """One psvr_bgzf_stream_t: a BGZF byte stream in HBM, cut every member_bytes; the members of all takes, concatenated, are
+    bgzf_compress's for everything appended.  Single-owner."""
+
+    def __init__(self, member_bytes=0xff00, device=0):
+        self.h = C.c_void_p()
+        self.member_bytes = member_bytes or 0xff00
+        L = lib()
+        L.psvr_bgzf_stream_pending.restype = C.c_int64
+        L.psvr_bgzf_members_bound.restype = C.c_int64
+        L.psvr_bgzf_stream_destroy.restype = None
+        check(L.psvr_bgzf_stream_create(C.c_int(device), C.c_int32(member_bytes), C.byref(self.h)))
+
+    def append(self, data):
+        """bytes of the host behind what is pending"""
+        buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+        check(lib().psvr_bgzf_stream_append(self.h, buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf))))
+
+    def append_emit(self, emitter, first_pair, n_pairs):
+        """the records of pairs [first_pair, first_pair + n_pairs) of a BamEmitter's last run, device to device; the emitter must not run
+        again before a later take, pending or recover has returned"""
+        check(lib().psvr_bgzf_stream_append_emit(self.h, emitter.h, C.c_int64(first_pair), C.c_int64(n_pairs)))
+
+    @property
+    def pending(self):
+        n = lib().psvr_bgzf_stream_pending(self.h)
+        if n < 0:
+            check(int(-n))
+        return n
+
+    def take(self, finish=False, out_cap=None):
+        """(uint8 array of the members made, member offsets [n + 1], stream bytes consumed); out_cap: the room offered, the bound by default"""
+        L = lib()
+        n = self.pending
+        cap = L.psvr_bgzf_members_bound(C.c_int64(n), C.c_int32(self.member_bytes)) if out_cap is None else out_cap
+        nm_cap = (n + self.member_bytes - 1) // self.member_bytes
+        out = np.empty(max(cap, 1), dtype=np.uint8)
+        offs = np.zeros(nm_cap + 1, dtype=np.int64)
+        total, nm, used = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        check(L.psvr_bgzf_stream_take(self.h, C.c_int(1 if finish else 0), out.ctypes.data_as(C.c_void_p), C.c_int64(cap), C.byref(total), offs.ctypes.data_as(C.c_void_p),
+                                      C.c_int64(nm_cap), C.byref(nm), C.byref(used)))
+        return out[:total.value], offs[:nm.value + 1], used.value
+
+    def recover(self):
+        """the pending bytes (uint8 array); the stream is empty afterwards"""
+        n = self.pending
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        got = C.c_int64(0)
+        check(lib().psvr_bgzf_stream_recover(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n), C.byref(got)))
+        return out[:got.value]
+
+    def close(self):
+        if self.h:
+            lib().psvr_bgzf_stream_destroy(self.h)
+            self.h = None

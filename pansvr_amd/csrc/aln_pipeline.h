@@ -15,6 +15,8 @@
 //   the two device routes, kNotAvailable from a driver without them (the pipeline then takes the host route without a word):
 //   int parse_window(int slot, FastqReader &, FastqBatch &, long long pairs, long long bases, int threads, std::string *why)   1 / 0 (input ended) / -1
 //   int emit_encode(int slot, const FastqBatch &, bool not_ori) / int emit_download(int slot, long long P, EmitView *)
+// --stream-device does not add to that list: who writes the main file then (MainSink below) reaches the pipeline as an optional last
+// constructor argument, and it is the sink, not the driver, that is asked for the offsets and states of a slot's emitted piece.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -113,6 +115,8 @@ struct Job {
 	FastqBatch fb;
 	int slot = 0;                      // (the driver keeps what its device routes need per slot)
 	bool emitted = false;              // --emit-device: this piece's main records were encoded on the device
+	std::vector<uint8_t> from_dev;     // --stream-device, per chunk: its main records stay in the slot's emitter (mb[ci] is empty) ...
+	const int64_t *dev_off = nullptr;  // ... at [dev_off[p0], dev_off[p1]) of its bytes
 	std::vector<Block> blk;
 	long long pair_base = 0;
 	std::vector<Bytes> mb, ob;         // formatted records of both files, per chunk of pairs
@@ -140,6 +144,18 @@ struct DeviceRoute {
 	void fail(int rc, const char *why) { if (rc != kNotAvailable) fprintf(stderr, message, why); on = false; }
 };
 struct EmitView { const uint8_t *bytes = nullptr, *state = nullptr; const int64_t *off = nullptr; };   // a piece's device-encoded records: [off[p], off[p + 1]) of pair p; state 2 = declined
+// --stream-device: who writes the main file instead of `fo` (cli_main.cpp has the product's, over bgzf_stream_sink.h).  The formatter asks it
+// for a piece's offsets and states only (the records stay in HBM); the writer hands it the piece's chunks in order.  A bool that is false:
+// the file cannot be written whole, the sink has said why, and the command ends.
+struct MainSink {
+	virtual ~MainSink() {}
+	virtual bool on() const = 0;                                             // the device route is on (off after a failure: later pieces take the splice path)
+	virtual int piece_view(int slot, long long P, EmitView *v) = 0;           // off and state of the slot's emitted piece; bytes stays null
+	virtual const char *last_error() = 0;
+	virtual bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) = 0;   // the records of pairs [p0, p1), from the slot's emitter
+	virtual bool host_chunk(const uint8_t *p, size_t n) = 0;
+	virtual bool piece_done() = 0;                                           // the slot's emitter is free again when this returns
+};
 
 // every timer and counter of the `wall:` line and of e2e_json, by the stage that writes it
 struct RunStats {
@@ -158,6 +174,9 @@ struct RunStats {
 	long long emit_device_pairs = 0, emit_declined_pairs = 0, emit_spliced_pairs = 0;
 	EmitStats emit;
 	double t_write = 0;                // writer
+	bool stream_fields = false;        // the command's line ends with the four fields below (it can have a main-file sink; a pipeline built without one prints the line as it was)
+	const char *streamer = "host";     // --stream-device: where the main file's stream was gathered (device / host / device+host) ...
+	long long stream_device_bytes = 0, stream_host_bytes = 0, stream_members = 0;   // ... its bytes that never left HBM / that came from the host, the members the device stream made
 	// PSVR_CLI_TIMING: when each stage had each piece (ms from the first FASTQ byte), printed at the end
 	const bool timing = getenv("PSVR_CLI_TIMING") != nullptr;
 	struct Span { double a = 0, b = 0; };
@@ -183,7 +202,8 @@ struct RunStats {
 		fprintf(stderr, "\"index_s\":%.4f,\"index_first_s\":%.4f,\"index_clone_s\":%.4f,\"read_parse_s\":%.4f,\"engine_s\":%.4f,\"exchange_s\":%.4f,\"rebase_iterations\":%lld,", t_index, t_idx_first, t_idx_clone, t_read, t_engine, t_exchange, rebase_iters);
 		fprintf(stderr, "\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,", t_format, t_write, t_sort, t_sort_order, d2h_bytes, hbm_first, hbm_last);
 		fprintf(stderr, "\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\",\"emitter\":\"%s\",", dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host", n_emit_pieces ? (n_emit_host_pieces ? "device+host" : "device") : "host");
-		fprintf(stderr, "\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld}\n", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs);
+		fprintf(stderr, "\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld%s", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs, stream_fields ? "," : "}\n");
+		if (stream_fields) fprintf(stderr, "\"streamer\":\"%s\",\"stream_device_bytes\":%lld,\"stream_host_bytes\":%lld,\"stream_members\":%lld}\n", streamer, stream_device_bytes, stream_host_bytes, stream_members);
 	}
 };
 
@@ -195,6 +215,7 @@ template <class Driver> struct AlnPipeline {
 	SamEmitter &em;
 	OutFile &fo, &fo_ori;
 	std::function<bool(const uint8_t *, size_t)> keep_main;   // --sort: takes the main file's records (they are kept until the input ends) instead of `fo`; false: malformed
+	MainSink *sink;                    // --stream-device: writes the main file instead of `fo` (null: none)
 	FILE *frec;                        // --records
 	RunStats &st;
 	const int D;
@@ -205,8 +226,9 @@ template <class Driver> struct AlnPipeline {
 	std::vector<std::string> errs;     // ... and the driver's text for it
 	int block_id = 0;
 
-	AlnPipeline(const PipeOpt &opt, Driver &d, FastqReader &r, psvr_aln_params_t &p, SamEmitter &e, OutFile &main, OutFile &ori, std::function<bool(const uint8_t *, size_t)> keep, FILE *rec, RunStats &stats, bool device_routes)
-	    : o(opt), drv(d), fq(r), par(p), em(e), fo(main), fo_ori(ori), keep_main(std::move(keep)), frec(rec), st(stats), D((int)opt.devices.size()), ring(D),
+	AlnPipeline(const PipeOpt &opt, Driver &d, FastqReader &r, psvr_aln_params_t &p, SamEmitter &e, OutFile &main, OutFile &ori, std::function<bool(const uint8_t *, size_t)> keep, FILE *rec, RunStats &stats, bool device_routes,
+	            MainSink *main_sink = nullptr)
+	    : o(opt), drv(d), fq(r), par(p), em(e), fo(main), fo_ori(ori), keep_main(std::move(keep)), sink(main_sink), frec(rec), st(stats), D((int)opt.devices.size()), ring(D),
 	      parse_route(opt.parse_device && device_routes, "[panSVR-amd] FASTQ parse on the device failed (%s): parsing on the host threads from here on\n"),
 	      emit_route(opt.emit_device && device_routes, "[panSVR-amd] BAM records on the device failed (%s): formatting on the host threads from here on\n"),
 	      rcs((size_t)D, 0), errs((size_t)D) {}
@@ -392,11 +414,15 @@ template <class Driver> struct AlnPipeline {
 		for (auto &v : ob) v.clear();
 		// --emit-device: the piece's main records come from the device; a chunk with a declined pair goes through the host formatter whole, so
 		// what it reports and drops is what it always did
+		// --stream-device: only the offsets and the states are fetched; a chunk without a declined pair is marked "from the device" and its records
+		// stay where the encoder wrote them (write_stage hands the range to the sink)
 		EmitView dev;
+		const bool streamed = J.emitted && sink && sink->on();
 		if (J.emitted) {
-			const int rc = drv.emit_download(J.slot, P, &dev);
-			if (rc) { emit_route.fail(rc, drv.last_error()); J.emitted = false, dev = EmitView(); }
+			const int rc = streamed ? sink->piece_view(J.slot, P, &dev) : drv.emit_download(J.slot, P, &dev);
+			if (rc) { emit_route.fail(rc, streamed ? sink->last_error() : drv.last_error()); J.emitted = false, dev = EmitView(); }
 		}
+		J.from_dev.assign((size_t)nchunk, 0), J.dev_off = dev.off;
 		++(J.emitted ? st.n_emit_pieces : st.n_emit_host_pieces);
 		std::atomic<long long> next(0), n_dev_pairs(0), n_declined(0), n_spliced(0);
 		auto work = [&]() {
@@ -408,6 +434,7 @@ template <class Driver> struct AlnPipeline {
 					for (long long p = p0; p < p1; ++p) nd += dev.state[p] == 2;
 					n_declined += nd, n_dev_pairs += (p1 - p0) - nd;
 					if (nd) host_main = true;
+					else if (!dev.bytes) J.from_dev[(size_t)ci] = 1, n_spliced += p1 - p0;
 					else mb[(size_t)ci].insert(mb[(size_t)ci].end(), dev.bytes + dev.off[p0], dev.bytes + dev.off[p1]), n_spliced += p1 - p0;
 				}
 				size_t bi = 0;
@@ -421,6 +448,26 @@ template <class Driver> struct AlnPipeline {
 		thread_pool().run((int)(o.thread_n < nchunk ? o.thread_n : nchunk), [&](int) { work(); });
 		st.emit_device_pairs += n_dev_pairs, st.emit_declined_pairs += n_declined, st.emit_spliced_pairs += n_spliced;
 	}
+	// --stream-device: the chunks in order, adjacent device chunks joined into one range of the slot's emitter
+	void write_to_sink(Job &J)
+	{
+		const long long P = J.fb.n_pairs(), chunk = 4096, nchunk = (long long)J.mb.size();
+		bool fine = true;
+		long long run0 = -1;                                // first pair of the run of device chunks that is open
+		auto flush = [&](long long p1) {
+			if (run0 >= 0 && fine) fine = sink->device_chunks(J.slot, run0, p1, (long long)(J.dev_off[p1] - J.dev_off[run0]));
+			run0 = -1;
+		};
+		for (long long ci = 0; ci < nchunk && fine; ++ci) {
+			const long long p0 = ci * chunk;
+			if (J.from_dev[(size_t)ci]) { if (run0 < 0) run0 = p0; continue; }
+			flush(p0);
+			if (fine) fine = sink->host_chunk(J.mb[(size_t)ci].data(), J.mb[(size_t)ci].size());
+		}
+		flush(P);
+		if (fine) fine = sink->piece_done();
+		if (!fine) { fprintf(stderr, "[panSVR-amd] --stream-device: the main file cannot be written whole; the run ends here with status 2 and BOTH output files (-o and -p) are incomplete\n"); _exit(2); }
+	}
 	void write_stage()
 	{
 		long long n_wr_pieces = 0;
@@ -429,7 +476,10 @@ template <class Driver> struct AlnPipeline {
 			ring.wait_state(J, 3);
 			if (J.last) return;
 			const double tw = walltime();
-			if (keep_main) {
+			if (sink) {
+				write_to_sink(J);
+				for (size_t ci = 0; ci < J.ob.size(); ++ci) fo_ori.write_raw(J.ob[ci]);
+			} else if (keep_main) {
 				try {
 					for (size_t ci = 0; ci < J.mb.size(); ++ci)
 						if (!keep_main(J.mb[ci].data(), J.mb[ci].size())) { fprintf(stderr, "[panSVR-amd] --sort: malformed record from the formatter\n"); abort(); }

@@ -12,19 +12,9 @@
 #include "common.h"
 #include "bam_emit_device.h"
 #include "bam_emit_hooks.h"
+#include "bam_emit_run.h"
 #include "fastq_parsed.h"
 #include "scan.h"
-
-struct psvr_bam_emit {
-	int device = 0;
-	hipStream_t stream = nullptr;
-	psvr::BeTables T = {nullptr, nullptr, nullptr, 0, 0};
-	psvr::DevBuf hdr, pairs, cands, cig;                     // psvr_bam_emit_results: the caller's arrays
-	psvr::DevBuf cnt, pair_off, state, bytes, tmp, counters;
-	long long *h_back = nullptr;                             // page-locked: {bytes, records, written pairs, declined pairs} of a run
-	int64_t n_pairs = 0, n_bytes = 0;
-	bool valid = false;
-};
 
 namespace psvr {
 

@@ -150,6 +150,8 @@ public:
 	// dev_min: PSVR_BGZF_DEVICE_MIN_BLOCKS (tests: small files through the device too)
 	explicit BgzfWriter(size_t gather_blocks = 3072) : dev_min_(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS") ? (size_t)atoll(getenv("PSVR_BGZF_DEVICE_MIN_BLOCKS")) : 64), gather_blocks_(gather_blocks < 1 ? 1 : gather_blocks) {}
 	bool open(const char *fn, int threads = 1, int level = Z_DEFAULT_COMPRESSION) { f_ = fopen(fn, "wb"); threads_ = threads; level_ = level; return f_ != nullptr; }
+	// continues a file that is open already, at a member boundary: whoever wrote it so far has written whole members only (bgzf_stream_sink.h)
+	void adopt(FILE *f, int threads = 1, int level = Z_DEFAULT_COMPRESSION) { f_ = f, threads_ = threads, level_ = level; }
 	bool ok() const { return ok_; }                             // nothing has failed so far; when something has: in compressing, or in writing
 	bool compress_failed() const { return compress_failed_; }
 #ifdef PSVR_BGZF_ON_DEVICE

@@ -21,6 +21,7 @@
 #include <sys/stat.h>
 #include <time.h>
 #include <unistd.h>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -30,6 +31,7 @@
 #include "signal_step.h"
 #include "bam_sort.h"
 #include "sorted_bam.h"
+#include "bgzf_stream_sink.h"
 
 using namespace psvr;
 using aln::walltime;
@@ -47,6 +49,7 @@ struct Opt : aln::PipeOpt {
 	bool deflate_device = false;                 // the BAM files' BGZF members (the sorted file's too) compressed on the first device, a wavefront per member (psvr_bgzf_compress_members)
 	bool inflate_device = false;                 // BAM input: its BGZF members inflated on the first device (psvr_bgzf_decompress) ...
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
+	bool stream_device = false;                  // the main BAM file's stream gathered in HBM: records from the encoder to the member compressor device to device (implies emit_device and deflate_device)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 };
 
@@ -56,6 +59,12 @@ struct Opt : aln::PipeOpt {
 	"                                 0.21-0.27 s against 0.08-0.12 s, SAM wall 0.36-0.44 s against 0.29-0.32 s, BAM with --deflate-device 0.44-0.55 s\n" \
 	"                                 against 0.44-0.46 s.  The kernels are not the cost (a 65 536-pair piece, 62 MB: newline passes 16 + 18 us, extract\n" \
 	"                                 116 us, all launches ~0.3 ms); the staging copy, the upload and the downloads are"
+
+// what --stream-device's usage text says about its speed
+#define PSVR_STREAM_DEVICE_MEASURED \
+	"Measured (1 M pairs, -t 16, three\n" \
+	"                                 interleaved runs, median wall): 0.390 s against 0.525 s for --emit-device --deflate-device and 0.373 s for plain\n" \
+	"                                 --deflate-device (on par: the ranges overlap; DESIGN.md section 8 f3)"
 
 static int usage()
 {
@@ -114,6 +123,13 @@ static int usage()
 	        "                                 threads, the bases reach the engine device to device, the pieces and the records are the same.  A call\n"
 	        "                                 that fails (a window of 4 GiB or more, a device error) leaves the rest of the input to the host threads.\n"
 	        "                                 " PSVR_PARSE_DEVICE_MEASURED "\n"
+	        "        --emit-device            FASTQ input: implies --parse-device; the main BAM file's records are encoded on the GPU as well (a chunk with\n"
+	        "                                 a pair the encoder declines is formatted on the host threads)\n"
+	        "        --stream-device          FASTQ input: implies --emit-device and --deflate-device; the main BAM file's records go from the encoder to\n"
+	        "                                 the BGZF member compressor inside GPU memory (a device-resident stream cut every 0xff00 bytes) and only the\n"
+	        "                                 compressed members come to the host; chunks the host formatted are uploaded into the same stream.  Not with\n"
+	        "                                 --sort, -S or more than one entry in --devices.  A failed stream call hands what is pending and everything\n"
+	        "                                 after it to the host members route, in order.  " PSVR_STREAM_DEVICE_MEASURED "\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -279,10 +295,66 @@ struct EngineDriver {
 	}
 };
 
+// --stream-device: bgzf_stream_sink.h's backend over psvr_bgzf_stream_* and the pipeline slots' emitters (EngineDriver::bem[]), and the sink as
+// the pipeline sees it
+struct StreamBackend {
+	EngineDriver &drv;
+	const int device;
+	psvr_bgzf_stream_t *s = nullptr;
+	long long view_pairs[aln::kSlots] = {};    // pairs of the piece emit_view last looked at, per slot
+	StreamBackend(EngineDriver &d, int dev) : drv(d), device(dev) {}
+	const char *last_error() { return psvr_last_error(); }
+	int create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
+	void destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
+	int append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
+	int append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
+	int64_t pending() { return psvr_bgzf_stream_pending(s); }
+	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
+	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *nm, int64_t *used) { return psvr_bgzf_stream_take(s, finish, out, cap, got, nullptr, 0, nm, used); }
+	int recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
+	int emit_view(int slot, int64_t P, const int64_t **off, const uint8_t **state)
+	{
+		int64_t *o = (int64_t *)drv.em_off[slot].reserve((size_t)(P + 1) * 8);
+		uint8_t *st = (uint8_t *)drv.em_state[slot].reserve((size_t)P + 1);
+		view_pairs[slot] = P, *off = o, *state = st;
+		return psvr_bam_emit_download(drv.bem[slot], nullptr, 0, o, st);
+	}
+	int emit_fetch(int slot, int64_t p0, int64_t p1, std::vector<uint8_t> *out)   // (the failure path: the whole piece comes down for one range of it)
+	{
+		const int64_t *off = (const int64_t *)drv.em_off[slot].reserve((size_t)(view_pairs[slot] + 1) * 8);
+		const int64_t total = off[view_pairs[slot]];
+		uint8_t *bytes = (uint8_t *)drv.em_bytes[slot].reserve((size_t)total + 1);
+		if (int rc = psvr_bam_emit_download(drv.bem[slot], bytes, total, nullptr, nullptr)) return rc;
+		out->assign(bytes + off[p0], bytes + off[p1]);
+		return 0;
+	}
+	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
+	void host_free(void *p) { psvr_host_free(p); }
+	void host_route(BgzfWriter &w) { w.set_device_members(device, &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks); }
+};
+struct StreamMainSink : aln::MainSink {
+	BgzfStreamSink<StreamBackend> &k;
+	explicit StreamMainSink(BgzfStreamSink<StreamBackend> &sink) : k(sink) {}
+	bool on() const override { return k.on(); }
+	int piece_view(int slot, long long P, aln::EmitView *v) override { v->bytes = nullptr; return k.emit_view(slot, P, &v->off, &v->state); }
+	const char *last_error() override { return k.last_error(); }
+	bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) override { return k.device_chunks(slot, p0, p1, n_bytes); }
+	bool host_chunk(const uint8_t *p, size_t n) override { return k.host_chunk(p, n); }
+	bool piece_done() override { return k.piece_done(); }
+};
+
 // what an option combination is refused with (true: a message went out); sort_conflict: the first option on the line that --sort cannot go with
 static bool option_conflict(const Opt &o, const char *sort_conflict)
 {
-	if (o.sort && sort_conflict)
+	if (o.stream_device && o.sort)
+		fprintf(stderr, "--stream-device cannot be combined with --sort: the stream compresses the main file's records in input order as they leave the encoder, a sorted file needs all of them first\n");
+	else if (o.stream_device && o.sam)
+		fprintf(stderr, "--stream-device cannot be combined with -S: it hands BAM records from the device's encoder to the device's BGZF compressor, SAM text is formatted and written on the host threads\n");
+	else if (o.stream_device && sort_conflict)
+		fprintf(stderr, "--stream-device cannot be combined with %s: it implies --deflate-device, a compression route of its own for BAM output (a wavefront per BGZF member on the GPU)\n", sort_conflict);
+	else if (o.stream_device && o.devices.size() > 1)
+		fprintf(stderr, "--stream-device cannot be combined with more than one entry in --devices: the records go from the encoder to the compressor inside the first device's memory\n");
+	else if (o.sort && sort_conflict)
 		fprintf(stderr, "--sort cannot be combined with %s: the sorted file is BAM compressed as `panSVR sort` compresses it\n", sort_conflict);
 	else if (o.deflate_device && sort_conflict)
 		fprintf(stderr, "--deflate-device cannot be combined with %s: it is a compression route of its own for BAM output (a wavefront per BGZF member on the GPU)\n", sort_conflict);
@@ -303,7 +375,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -339,6 +411,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1013: o.deflate_device = true; break;
 		case 1014: o.parse_device = true; break;
 		case 1015: o.emit_device = o.parse_device = true; break;
+		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -354,7 +427,8 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	o.from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
 	if (!o.from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
 	if (o.from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
-	if (o.from_bam && o.emit_device) fprintf(stderr, "[panSVR-amd] --emit-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
+	if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
+	else if (o.from_bam && o.emit_device) fprintf(stderr, "[panSVR-amd] --emit-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
 	return -1;
 }
 
@@ -415,7 +489,7 @@ static int aln_main(int argc, char **argv)
 	std::vector<BamRef> refs;
 	load_header(o, &H, &refs);
 	aln::RunStats st;
-	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam;
+	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam, st.stream_fields = true;
 	EngineDriver drv(o.devices);
 	fprintf(stderr, "Begin loading index @%s\n", o.index_dir.c_str());
 	drv.load_indexes(o, &st);
@@ -433,10 +507,22 @@ static int aln_main(int argc, char **argv)
 	if (o.from_bam) fq.open_feed(&feed);
 	else if (!fq.open(o.reads.c_str())) { fprintf(stderr, "%s\n", fq.error().c_str()); abort(); }
 	aln::OutFile fo, fo_ori;
-	if ((!o.sort && !fo.open(o.out, !o.sam, H, refs, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, refs, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
+	// --stream-device: the main file is the sink's, not `fo`'s (PSVR_STREAM_TAKE_MEMBERS: members pending before a take; the tests take small files in pieces with it)
+	const bool streaming = o.stream_device && !o.from_bam;
+	std::unique_ptr<StreamBackend> stream_backend;
+	std::unique_ptr<BgzfStreamSink<StreamBackend>> stream_sink;
+	std::unique_ptr<StreamMainSink> main_sink;
+	if (streaming) {
+		stream_backend.reset(new StreamBackend(drv, o.devices[0]));
+		stream_sink.reset(new BgzfStreamSink<StreamBackend>(*stream_backend, getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
+		main_sink.reset(new StreamMainSink(*stream_sink));
+		if (!stream_sink->open(o.out.c_str(), H.text, refs, o.thread_n)) { fprintf(stderr, "fail to open output file\n"); abort(); }
+	}
+	if ((!o.sort && !streaming && !fo.open(o.out, !o.sam, H, refs, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, refs, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	SortRecords sorted;                                  // --sort: the main file's records, kept until the input ends
 	if (o.bgzf_device && !o.sam) fo.bam.bgzf().set_device(o.devices[0]), fo_ori.bam.bgzf().set_device(o.devices[0]);
-	if (o.deflate_device) fo.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks), fo_ori.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
+	if (o.deflate_device && !streaming) fo.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
+	if (o.deflate_device) fo_ori.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
 	FILE *frec = o.records.empty() ? nullptr : fopen(o.records.c_str(), "w");
 	fprintf(stderr, "Processing file: [%s].\n", o.reads.c_str());
 
@@ -449,14 +535,22 @@ static int aln_main(int argc, char **argv)
 	em.H = &H, em.sv = &svn, em.as_bam = !o.sam, em.not_ori = o.not_ori, em.stats = &st.emit;
 	std::function<bool(const uint8_t *, size_t)> keep_main;
 	if (o.sort) keep_main = [&sorted](const uint8_t *p, size_t n) { return sorted.add_stream(p, n); };
-	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, !o.from_bam);
+	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, !o.from_bam, main_sink.get());
 	pipe.run();
 	feed.abort();                                        // (a reader that stopped at -R leaves the signal step to run to its end unheard)
 	if (sig_thread.joinable()) {
 		sig_thread.join();
 		if (sig_rc) { fprintf(stderr, "[panSVR-amd] the signal step failed\n"); abort(); }
 	}
-	if ((!o.sort && !fo.close()) || !fo_ori.close()) { fprintf(stderr, "fail to write output file\n"); abort(); }
+	if (streaming) {
+		const double tc = walltime();
+		if (!stream_sink->close()) { fprintf(stderr, "[panSVR-amd] --stream-device: fail to write output file: the main file [%s] is incomplete, and the ori file [%s] was not closed and is incomplete too\n", o.out.c_str(), o.out_ori.c_str()); return 2; }
+		st.t_write += walltime() - tc;
+		const StreamSinkStats &ss = stream_sink->st;
+		st.streamer = ss.device_chunks == 0 ? "host" : ss.host_chunks || ss.left ? "device+host" : "device";
+		st.stream_device_bytes = ss.device_bytes, st.stream_host_bytes = ss.host_bytes, st.stream_members = ss.members;
+	}
+	if ((!o.sort && !streaming && !fo.close()) || !fo_ori.close()) { fprintf(stderr, "fail to write output file\n"); abort(); }
 	if (o.sort) if (const int rc = write_sorted_main(o, H, refs, sorted, &st)) return rc;
 	if (frec) fclose(frec);
 	st.wall = walltime() - st.wall0;                     // first FASTQ byte to the files closed; giving the HBM back is reported beside it, like the index load
@@ -473,6 +567,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members);
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
 	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
+	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
 	                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 	return 1;
 }

@@ -1,10 +1,10 @@
 """`panSVR aln` end to end with the record encoder on the host threads and on the device, on the bench batch written as FASTQ (bench.py's
 workload: 10 000 anchors, seed 11; the reads of rank 0, seed 13) in RAM-backed storage.  The routes --deflate-device,
---parse-device --deflate-device and --emit-device --deflate-device, and the last two with --sort, run interleaved `--reps` times, each
-command in a child of its own; wall_s, read_parse_s, engine_s, format_s and write_s come from the command's e2e_json line.  The unsorted
+--parse-device --deflate-device, --emit-device --deflate-device and --stream-device, and the second and third with --sort, run interleaved
+`--reps` times (--routes: only the named ones), each command in a child of its own; wall_s, read_parse_s, engine_s, format_s and write_s come from the command's e2e_json line.  The unsorted
 routes' inflated payloads are compared with the first route's.  One JSON line.
-    python tools/emit_device_e2e.py [--pairs 1000000] [--threads 16] [--reps 3] [--profile-dir DIR]
---profile-dir: one more run of the --emit-device route under `rocprofv3 --kernel-trace --stats` (kernel times only, no counters), its
+    python tools/emit_device_e2e.py [--pairs 1000000] [--threads 16] [--reps 3] [--routes a,b,...] [--profile-dir DIR] [--profile-route emit_device]
+--profile-dir: one more run of one route (--profile-route) under `rocprofv3 --kernel-trace --stats` (kernel times only, no counters), its
 files left in DIR."""
 import argparse
 import gzip
@@ -20,8 +20,10 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 CLI = os.path.join(ROOT, "pansvr_amd", "bin", "panSVR")
 HEADER = "@SQ\tSN:chr1\tLN:250000000\n@SQ\tSN:chr2\tLN:250000000\n"
 ROUTES = (("deflate_device", ["--deflate-device"]), ("parse_device", ["--parse-device", "--deflate-device"]), ("emit_device", ["--emit-device", "--deflate-device"]),
+          ("stream_device", ["--stream-device"]),
           ("parse_device_sort", ["--parse-device", "--deflate-device", "--sort"]), ("emit_device_sort", ["--emit-device", "--deflate-device", "--sort"]))
-KEYS = ("wall_s", "read_parse_s", "engine_s", "format_s", "write_s", "sort_s", "emitter", "emit_device_pairs", "emit_declined_pairs", "parser", "pieces")
+KEYS = ("wall_s", "read_parse_s", "engine_s", "format_s", "write_s", "sort_s", "emitter", "emit_device_pairs", "emit_declined_pairs", "parser", "pieces", "streamer", "stream_device_bytes",
+        "stream_host_bytes", "stream_members")
 
 
 def run(cmd, timeout):
@@ -39,7 +41,10 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--profile-dir", default=None)
+    ap.add_argument("--routes", default=None)
+    ap.add_argument("--profile-route", default="emit_device")
     a = ap.parse_args()
+    routes = [r for r in ROUTES if a.routes is None or r[0] in a.routes.split(",")]
     import bench_data
     tmp = tempfile.mkdtemp(prefix="psvr_emit_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     try:
@@ -56,7 +61,7 @@ def main():
         print("data ready", file=sys.stderr, flush=True)
         ref = None
         for rep in range(a.reps):
-            for name, flags in ROUTES:
+            for name, flags in routes:
                 o, p = os.path.join(tmp, "o.bam"), os.path.join(tmp, "p.bam")
                 res.setdefault(name, []).append(run([CLI, "aln", "-t", str(a.threads), "-o", o, "-p", p] + flags + pos, 600))
                 print(name, res[name][-1], file=sys.stderr, flush=True)
@@ -66,8 +71,8 @@ def main():
                     res.setdefault("same_payload", []).append(pay == ref)
         if a.profile_dir:
             os.makedirs(a.profile_dir, exist_ok=True)
-            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.profile_dir, "-o", "emit_device", "--output-format", "csv", "--", CLI, "aln", "-t", str(a.threads),
-                            "-o", os.path.join(tmp, "o.bam"), "-p", os.path.join(tmp, "p.bam"), "--emit-device", "--deflate-device"] + pos, stdout=subprocess.DEVNULL,
+            subprocess.run(["rocprofv3", "--kernel-trace", "--stats", "-d", a.profile_dir, "-o", a.profile_route, "--output-format", "csv", "--", CLI, "aln", "-t", str(a.threads),
+                            "-o", os.path.join(tmp, "o.bam"), "-p", os.path.join(tmp, "p.bam")] + dict(ROUTES)[a.profile_route] + pos, stdout=subprocess.DEVNULL,
                            stderr=subprocess.DEVNULL, timeout=600, check=True)
         print(json.dumps(res), flush=True)
     finally:
