@@ -481,6 +481,50 @@ int psvr_bgzf_decompress(int device, const void *in, int64_t n_bytes, int64_t *i
  * (PSVR_ERR_NOMEM with the byte count in psvr_last_error() when it does not fit). */
 int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *order);
 
+/* ---- The main BAM file's records kept and ordered in HBM (the coordinate sort of the BAM output without a host trip) -------------------------
+ * Joins psvr_bam_emit_*, psvr_sort_order_u64 and psvr_bgzf_stream_*: what `samtools sort` + `samtools index` do between the `aln` and `fc_sv`
+ * steps (panSVR_run.sh:53-54), for records that the device encoded and that the device compresses.  A store keeps BAM records (block_size
+ * first, as in a BAM stream) in device memory, in chunks that are allocated once and never moved, with a table of one entry per record that
+ * is built on the device: where the record lies, its length, samtools' key (uint64)tid << 32 | (uint32)(pos + 1) << 1 | reverse, the
+ * reference span of its CIGAR (1 without one) and the bin recomputed from position and span (reg2bin(max(pos, 0), max(pos, 0) + span), as
+ * `panSVR sort` recomputes it).
+ *   append        records back to back from host memory (what the host formatter wrote for a chunk); free again when the call returns (a
+ *                 wait).  The bytes are checked on the host first: a record cut off by the end, a block_size below 32 or a CIGAR that leaves
+ *                 its record: PSVR_ERR_ARG, and nothing is appended (a record of 2 GiB or more: PSVR_ERR_UNSUPPORTED, likewise).
+ *   append_emit   bytes[pair_off[first_pair], pair_off[first_pair + n_pairs]) of em's last run, device to device, queued without a round trip.
+ *                 `em` MUST NOT BE RUN AGAIN or destroyed UNTIL A LATER info, append, order or download ON `st` HAS RETURNED (the rule of
+ *                 psvr_bgzf_stream_append_emit).  A pair range outside the run, an emitter without a valid run or on another device:
+ *                 PSVR_ERR_ARG.  The records are found by walking the block_size chain inside each state-1 pair, bounded by the pair's bytes.
+ *   info          waits for what is queued; key_exact == 0: some position lies outside [-1, 2^31 - 2].
+ *   order         sorts the keys where they lie (the sort of psvr_sort_order_u64: stable, equal keys keep append order) and computes where
+ *                 every record goes in the sorted stream.  Afterwards appends are refused (PSVR_ERR_ARG).  key_exact == 0 or 2^32 and more
+ *                 records: PSVR_ERR_UNSUPPORTED, and nothing changes.  An empty store is ordered too.
+ *   meta          for sorted ranks [first_rank, first_rank + n), what the .bai needs: tid, pos, end = max(pos, 0) + span, len = 4 + block_size,
+ *                 the recomputed bin, flag, and index = the record's number in append order.  Only after order (else PSVR_ERR_ARG).
+ *   stream        appends the records of those ranks, with the recomputed bin in bytes 14-15, behind the pending bytes of a
+ *                 psvr_bgzf_stream_t on the same device, device to device (one gather kernel; returns when the bytes are pending).  The host
+ *                 knows every length after order: the stream's count stays exact and no room is reserved beyond the bytes themselves.
+ *   download      every record in append order, with the recomputed bin, to bytes[0, *n_bytes) (host memory; cap too small:
+ *                 PSVR_ERR_OVERFLOW, *n_bytes is set).  Works before and after order: what a caller that gives the device route up continues from.
+ * An append from an emitter that would leave the emitter's bytes, a chain that leaves its pair, a block_size below 32 or a CIGAR that leaves
+ * its record is noticed on the device: nothing further is copied, and from the next call that waits on every call answers PSVR_ERR_DEVICE.
+ * No device: PSVR_ERR_DEVICE.  A failed device allocation: PSVR_ERR_NOMEM with the byte count in psvr_last_error(), and nothing stored is lost.
+ * Device memory: the records, about 48 bytes per record of table, about 70 more per record from order on; until the next call that waits
+ * every append_emit reserves room for em's WHOLE run in the current chunk (256 MiB, or the run's size) and in the table.
+ * A store has one owner at a time; its calls are serialised with psvr_bgzf_compress_members and the streams'. */
+typedef struct psvr_bam_store psvr_bam_store_t;
+typedef struct psvr_bam_store_info { int64_t n_records, n_bytes; int32_t key_exact, ordered; } psvr_bam_store_info_t;
+typedef struct psvr_bam_rec_meta { int64_t end; int32_t tid, pos; uint32_t len, index; uint16_t bin, flag; uint32_t pad; } psvr_bam_rec_meta_t; /* 32 bytes */
+int  psvr_bam_store_create(int device, psvr_bam_store_t **out);
+int  psvr_bam_store_append(psvr_bam_store_t *st, const void *bytes, int64_t n_bytes);
+int  psvr_bam_store_append_emit(psvr_bam_store_t *st, const psvr_bam_emit_t *em, int64_t first_pair, int64_t n_pairs);
+int  psvr_bam_store_info(psvr_bam_store_t *st, psvr_bam_store_info_t *info);       /* waits for what is queued */
+int  psvr_bam_store_order(psvr_bam_store_t *st);
+int  psvr_bam_store_meta(psvr_bam_store_t *st, int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *meta);
+int  psvr_bam_store_stream(psvr_bam_store_t *st, psvr_bgzf_stream_t *s, int64_t first_rank, int64_t n);
+int  psvr_bam_store_download(psvr_bam_store_t *st, void *bytes, int64_t cap, int64_t *n_bytes);
+void psvr_bam_store_destroy(psvr_bam_store_t *st);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,7 @@ struct MainSink {
 	virtual bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) = 0;   // the records of pairs [p0, p1), from the slot's emitter
 	virtual bool host_chunk(const uint8_t *p, size_t n) = 0;
 	virtual bool piece_done() = 0;                                           // the slot's emitter is free again when this returns
+	virtual const char *option() const { return "--stream-device"; }         // the option that put the sink there (--sort-device has one too), for messages
 };
 
 // every timer and counter of the `wall:` line and of e2e_json, by the stage that writes it
@@ -177,6 +178,9 @@ struct RunStats {
 	bool stream_fields = false;        // the command's line ends with the four fields below (it can have a main-file sink; a pipeline built without one prints the line as it was)
 	const char *streamer = "host";     // --stream-device: where the main file's stream was gathered (device / host / device+host) ...
 	long long stream_device_bytes = 0, stream_host_bytes = 0, stream_members = 0;   // ... its bytes that never left HBM / that came from the host, the members the device stream made
+	bool sort_fields = false;          // ... and with the five fields below behind them
+	const char *sorter = "host";       // --sort-device: where the main file's records were kept and sorted (device / host / device+host when the route was left) ...
+	long long sort_device_bytes = 0, sort_host_bytes = 0, sort_records = 0, sort_members = 0;   // ... record bytes that never left HBM / bytes appended from the host, records and members of the sorted file
 	// PSVR_CLI_TIMING: when each stage had each piece (ms from the first FASTQ byte), printed at the end
 	const bool timing = getenv("PSVR_CLI_TIMING") != nullptr;
 	struct Span { double a = 0, b = 0; };
@@ -203,7 +207,8 @@ struct RunStats {
 		fprintf(stderr, "\"format_s\":%.4f,\"write_s\":%.4f,\"sort_s\":%.4f,\"sort_order_s\":%.4f,\"d2h_bytes\":%lld,\"hbm_used_first\":%zu,\"hbm_used_last\":%zu,", t_format, t_write, t_sort, t_sort_order, d2h_bytes, hbm_first, hbm_last);
 		fprintf(stderr, "\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\",\"emitter\":\"%s\",", dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host", n_emit_pieces ? (n_emit_host_pieces ? "device+host" : "device") : "host");
 		fprintf(stderr, "\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld%s", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs, stream_fields ? "," : "}\n");
-		if (stream_fields) fprintf(stderr, "\"streamer\":\"%s\",\"stream_device_bytes\":%lld,\"stream_host_bytes\":%lld,\"stream_members\":%lld}\n", streamer, stream_device_bytes, stream_host_bytes, stream_members);
+		if (stream_fields) fprintf(stderr, "\"streamer\":\"%s\",\"stream_device_bytes\":%lld,\"stream_host_bytes\":%lld,\"stream_members\":%lld%s", streamer, stream_device_bytes, stream_host_bytes, stream_members, sort_fields ? "," : "}\n");
+		if (stream_fields && sort_fields) fprintf(stderr, "\"sorter\":\"%s\",\"sort_device_bytes\":%lld,\"sort_host_bytes\":%lld,\"sort_records\":%lld,\"sort_members\":%lld}\n", sorter, sort_device_bytes, sort_host_bytes, sort_records, sort_members);
 	}
 };
 
@@ -466,7 +471,7 @@ template <class Driver> struct AlnPipeline {
 		}
 		flush(P);
 		if (fine) fine = sink->piece_done();
-		if (!fine) { fprintf(stderr, "[panSVR-amd] --stream-device: the main file cannot be written whole; the run ends here with status 2 and BOTH output files (-o and -p) are incomplete\n"); _exit(2); }
+		if (!fine) { fprintf(stderr, "[panSVR-amd] %s: the main file cannot be written whole; the run ends here with status 2 and BOTH output files (-o and -p) are incomplete\n", sink->option()); _exit(2); }
 	}
 	void write_stage()
 	{

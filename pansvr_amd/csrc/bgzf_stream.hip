@@ -19,18 +19,7 @@
 #include "bam_emit_run.h"
 #include "bgzf_format.h"
 #include "bgzf_members.h"
-
-struct psvr_bgzf_stream {
-	int device = 0;
-	uint32_t mb = 0;
-	psvr::DevBuf pend, ctl;                                  // the pending bytes [0, count); {count, count, bad append} as long long
-	long long *h_ctl = nullptr;                              // page-locked: [0..2] read-back of ctl, [3] the count an upload sets
-	int cur = 0;                                             // which slot of ctl holds the count
-	long long n = 0, upper = 0;                              // the host's copy of the count; never below what the device holds
-	bool exact = true;                                       // n is the device's count
-	bool bad = false;                                        // an append from an emitter was refused on the device, or a call failed after it had begun to change
-	                                                         // the pending bytes: what is pending cannot be trusted any more, and every later call says so
-};
+#include "bgzf_stream_run.h"
 
 namespace psvr {
 
@@ -64,11 +53,11 @@ __global__ __launch_bounds__(256) void k_bs_append(const uint8_t *__restrict__ s
 }
 
 // what follows runs under DfwCtx's mutex, on its stream, bound to the stream's device
-static int bs_bad(const psvr_bgzf_stream *s)
+int bs_bad(const psvr_bgzf_stream *s)
 {
 	return set_error(PSVR_ERR_DEVICE, "psvr_bgzf_stream: the stream is unusable: an append from an emitter was out of bounds and was not made, or an earlier call failed while it changed the pending bytes");
 }
-static int bs_refresh(psvr_bgzf_stream *s, DfwCtx &c)      // the count as the device holds it (a wait, when the host does not know it); an unusable stream says so
+int bs_refresh(psvr_bgzf_stream *s, DfwCtx &c)      // the count as the device holds it (a wait, when the host does not know it); an unusable stream says so
 {
 	if (s->bad) return bs_bad(s);
 	if (s->exact) return PSVR_OK;
@@ -78,13 +67,13 @@ static int bs_refresh(psvr_bgzf_stream *s, DfwCtx &c)      // the count as the d
 	if (s->h_ctl[2]) { s->bad = true; return bs_bad(s); }
 	return PSVR_OK;
 }
-static int bs_set_count(psvr_bgzf_stream *s, DfwCtx &c, long long n)   // queued; the caller waits
+int bs_set_count(psvr_bgzf_stream *s, DfwCtx &c, long long n)   // queued; the caller waits
 {
 	s->h_ctl[3] = n;
 	PSVR_HIP(hipMemcpyAsync(s->ctl.as<long long>() + s->cur, s->h_ctl + 3, 8, hipMemcpyHostToDevice, c.stream));
 	return PSVR_OK;
 }
-static int bs_room(psvr_bgzf_stream *s, DfwCtx &c, long long need)     // pend holds `need` bytes; what is pending is kept
+int bs_room(psvr_bgzf_stream *s, DfwCtx &c, long long need)     // pend holds `need` bytes; what is pending is kept
 {
 	if ((size_t)need <= s->pend.bytes) return PSVR_OK;
 	DevBuf bigger;

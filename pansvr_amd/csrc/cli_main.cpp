@@ -32,6 +32,7 @@
 #include "bam_sort.h"
 #include "sorted_bam.h"
 #include "bgzf_stream_sink.h"
+#include "sort_store_sink.h"
 
 using namespace psvr;
 using aln::walltime;
@@ -51,6 +52,7 @@ struct Opt : aln::PipeOpt {
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
 	bool stream_device = false;                  // the main BAM file's stream gathered in HBM: records from the encoder to the member compressor device to device (implies emit_device and deflate_device)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
+	bool sort_device = false;                    // ... with the records kept, ordered and compressed in HBM (sort_store_sink.h; implies sort, emit_device and deflate_device)
 };
 
 // what --parse-device's usage text says about its speed
@@ -65,6 +67,12 @@ struct Opt : aln::PipeOpt {
 	"Measured (1 M pairs, -t 16, three\n" \
 	"                                 interleaved runs, median wall): 0.390 s against 0.525 s for --emit-device --deflate-device and 0.373 s for plain\n" \
 	"                                 --deflate-device (on par: the ranges overlap; DESIGN.md section 8 f3)"
+
+// what --sort-device's usage text says about its speed
+#define PSVR_SORT_DEVICE_MEASURED \
+	"Measured (1 M pairs, -t 16,\n" \
+	"                                 three interleaved runs, median wall): 0.587 s against 1.036 s for --sort --deflate-device and 1.300 s with --emit-device\n" \
+	"                                 on top (ahead: the ranges do not overlap); its sort part 0.169 s against 0.645 s (DESIGN.md section 8 f3)"
 
 static int usage()
 {
@@ -130,6 +138,12 @@ static int usage()
 	        "                                 compressed members come to the host; chunks the host formatted are uploaded into the same stream.  Not with\n"
 	        "                                 --sort, -S or more than one entry in --devices.  A failed stream call hands what is pending and everything\n"
 	        "                                 after it to the host members route, in order.  " PSVR_STREAM_DEVICE_MEASURED "\n"
+	        "        --sort-device            FASTQ input: implies --sort, --emit-device and --deflate-device; the main file's records stay in GPU memory until\n"
+	        "                                 the input ends (a record store in chunks that never move), are ordered there, gathered in sorted order into the\n"
+	        "                                 device-resident BGZF stream and compressed: only the members and the index's table come to the host.  The three\n"
+	        "                                 files are those of --sort --deflate-device, byte for byte.  Not with -S, --stream-device, --compress-level,\n"
+	        "                                 --bgzf-fast, --bgzf-device or more than one entry in --devices.  A failed store call downloads the records and\n"
+	        "                                 leaves the rest to the host's sorted writer.  " PSVR_SORT_DEVICE_MEASURED "\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -297,21 +311,11 @@ struct EngineDriver {
 
 // --stream-device: bgzf_stream_sink.h's backend over psvr_bgzf_stream_* and the pipeline slots' emitters (EngineDriver::bem[]), and the sink as
 // the pipeline sees it
-struct StreamBackend {
+// what both sinks' backends ask of the pipeline slots' emitters
+struct EmitterAccess {
 	EngineDriver &drv;
-	const int device;
-	psvr_bgzf_stream_t *s = nullptr;
 	long long view_pairs[aln::kSlots] = {};    // pairs of the piece emit_view last looked at, per slot
-	StreamBackend(EngineDriver &d, int dev) : drv(d), device(dev) {}
-	const char *last_error() { return psvr_last_error(); }
-	int create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
-	void destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
-	int append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
-	int append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
-	int64_t pending() { return psvr_bgzf_stream_pending(s); }
-	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
-	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *nm, int64_t *used) { return psvr_bgzf_stream_take(s, finish, out, cap, got, nullptr, 0, nm, used); }
-	int recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
+	explicit EmitterAccess(EngineDriver &d) : drv(d) {}
 	int emit_view(int slot, int64_t P, const int64_t **off, const uint8_t **state)
 	{
 		int64_t *o = (int64_t *)drv.em_off[slot].reserve((size_t)(P + 1) * 8);
@@ -328,8 +332,22 @@ struct StreamBackend {
 		out->assign(bytes + off[p0], bytes + off[p1]);
 		return 0;
 	}
+	const char *last_error() { return psvr_last_error(); }
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
+};
+struct StreamBackend : EmitterAccess {
+	const int device;
+	psvr_bgzf_stream_t *s = nullptr;
+	StreamBackend(EngineDriver &d, int dev) : EmitterAccess(d), device(dev) {}
+	int create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
+	void destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
+	int append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
+	int append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
+	int64_t pending() { return psvr_bgzf_stream_pending(s); }
+	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
+	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *nm, int64_t *used) { return psvr_bgzf_stream_take(s, finish, out, cap, got, nullptr, 0, nm, used); }
+	int recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
 	void host_route(BgzfWriter &w) { w.set_device_members(device, &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks); }
 };
 struct StreamMainSink : aln::MainSink {
@@ -343,10 +361,58 @@ struct StreamMainSink : aln::MainSink {
 	bool piece_done() override { return k.piece_done(); }
 };
 
+// --sort-device: sort_store_sink.h's backend over psvr_bam_store_*, psvr_bgzf_stream_* and the pipeline slots' emitters, and the sink as the pipeline sees it
+struct SortBackend : EmitterAccess {
+	const int device;
+	psvr_bam_store_t *store = nullptr;
+	psvr_bgzf_stream_t *s = nullptr;
+	SortBackend(EngineDriver &d, int dev) : EmitterAccess(d), device(dev) {}
+	int store_create() { return psvr_bam_store_create(device, &store); }
+	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
+	int store_append(const void *p, int64_t n) { return psvr_bam_store_append(store, p, n); }
+	int store_append_emit(int slot, int64_t first, int64_t n) { return psvr_bam_store_append_emit(store, drv.bem[slot], first, n); }
+	int store_info(int64_t *n_records, int64_t *n_bytes)
+	{
+		psvr_bam_store_info_t i;
+		if (int rc = psvr_bam_store_info(store, &i)) return rc;
+		*n_records = i.n_records, *n_bytes = i.n_bytes;
+		return 0;
+	}
+	int store_order() { return psvr_bam_store_order(store); }
+	int store_meta(int64_t first, int64_t n, psvr_bam_rec_meta_t *m) { return psvr_bam_store_meta(store, first, n, m); }
+	int store_stream(int64_t first, int64_t n) { return psvr_bam_store_stream(store, s, first, n); }
+	int store_download(void *bytes, int64_t cap, int64_t *n) { return psvr_bam_store_download(store, bytes, cap, n); }
+	int stream_create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
+	void stream_destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
+	int stream_append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
+	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
+	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *member_off, int64_t member_cap, int64_t *nm, int64_t *used)
+	{
+		return psvr_bgzf_stream_take(s, finish, out, cap, got, member_off, member_cap, nm, used);
+	}
+};
+struct SortMainSink : aln::MainSink {
+	SortStoreSink<SortBackend> &k;
+	explicit SortMainSink(SortStoreSink<SortBackend> &sink) : k(sink) {}
+	bool on() const override { return k.on(); }
+	int piece_view(int slot, long long P, aln::EmitView *v) override { v->bytes = nullptr; return k.emit_view(slot, P, &v->off, &v->state); }
+	const char *last_error() override { return k.last_error(); }
+	bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) override { return k.device_chunks(slot, p0, p1, n_bytes); }
+	bool host_chunk(const uint8_t *p, size_t n) override { return k.host_chunk(p, n); }
+	bool piece_done() override { return k.piece_done(); }
+	const char *option() const override { return "--sort-device"; }
+};
+
 // what an option combination is refused with (true: a message went out); sort_conflict: the first option on the line that --sort cannot go with
 static bool option_conflict(const Opt &o, const char *sort_conflict)
 {
-	if (o.stream_device && o.sort)
+	if (o.sort_device && o.stream_device)
+		fprintf(stderr, "--sort-device cannot be combined with --stream-device: the stream compresses the main file's records in input order as they leave the encoder, a sorted file needs all of them first\n");
+	else if (o.sort_device && sort_conflict)
+		fprintf(stderr, "--sort-device cannot be combined with %s: the sorted file is BAM, its members compressed on the GPU from records that stay in its memory\n", sort_conflict);
+	else if (o.sort_device && o.devices.size() > 1)
+		fprintf(stderr, "--sort-device cannot be combined with more than one entry in --devices: the records are encoded, kept, ordered and compressed inside the first device's memory\n");
+	else if (o.stream_device && o.sort)
 		fprintf(stderr, "--stream-device cannot be combined with --sort: the stream compresses the main file's records in input order as they leave the encoder, a sorted file needs all of them first\n");
 	else if (o.stream_device && o.sam)
 		fprintf(stderr, "--stream-device cannot be combined with -S: it hands BAM records from the device's encoder to the device's BGZF compressor, SAM text is formatted and written on the host threads\n");
@@ -375,7 +441,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -411,6 +477,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1013: o.deflate_device = true; break;
 		case 1014: o.parse_device = true; break;
 		case 1015: o.emit_device = o.parse_device = true; break;
+		case 1017: o.sort_device = o.sort = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
@@ -427,7 +494,8 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	o.from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
 	if (!o.from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
 	if (o.from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
-	if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
+	if (o.from_bam && o.sort_device) fprintf(stderr, "[panSVR-amd] --sort-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the run is that of --sort --deflate-device)\n", o.reads.c_str());
+	else if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
 	else if (o.from_bam && o.emit_device) fprintf(stderr, "[panSVR-amd] --emit-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
 	return -1;
 }
@@ -489,7 +557,7 @@ static int aln_main(int argc, char **argv)
 	std::vector<BamRef> refs;
 	load_header(o, &H, &refs);
 	aln::RunStats st;
-	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam, st.stream_fields = true;
+	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam, st.stream_fields = st.sort_fields = true;
 	EngineDriver drv(o.devices);
 	fprintf(stderr, "Begin loading index @%s\n", o.index_dir.c_str());
 	drv.load_indexes(o, &st);
@@ -511,12 +579,23 @@ static int aln_main(int argc, char **argv)
 	const bool streaming = o.stream_device && !o.from_bam;
 	std::unique_ptr<StreamBackend> stream_backend;
 	std::unique_ptr<BgzfStreamSink<StreamBackend>> stream_sink;
-	std::unique_ptr<StreamMainSink> main_sink;
+	std::unique_ptr<aln::MainSink> main_sink;
 	if (streaming) {
 		stream_backend.reset(new StreamBackend(drv, o.devices[0]));
 		stream_sink.reset(new BgzfStreamSink<StreamBackend>(*stream_backend, getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
 		main_sink.reset(new StreamMainSink(*stream_sink));
 		if (!stream_sink->open(o.out.c_str(), H.text, refs, o.thread_n)) { fprintf(stderr, "fail to open output file\n"); abort(); }
+	}
+	// --sort-device: the main file's records go to the sink's store; the file is written when the input has ended
+	const bool sorting_device = o.sort_device && !o.from_bam;
+	std::unique_ptr<SortBackend> sort_backend;
+	std::unique_ptr<SortStoreSink<SortBackend>> sort_sink;
+	if (sorting_device) {
+		sort_backend.reset(new SortBackend(drv, o.devices[0]));
+		sort_sink.reset(new SortStoreSink<SortBackend>(*sort_backend, [&](const SortRecords &R) { return write_sorted_main(o, H, refs, R, &st); },
+		                                               getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
+		main_sink.reset(new SortMainSink(*sort_sink));
+		sort_sink->open(o.out.c_str(), H.text, refs);
 	}
 	if ((!o.sort && !streaming && !fo.open(o.out, !o.sam, H, refs, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, refs, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	SortRecords sorted;                                  // --sort: the main file's records, kept until the input ends
@@ -551,7 +630,19 @@ static int aln_main(int argc, char **argv)
 		st.stream_device_bytes = ss.device_bytes, st.stream_host_bytes = ss.host_bytes, st.stream_members = ss.members;
 	}
 	if ((!o.sort && !streaming && !fo.close()) || !fo_ori.close()) { fprintf(stderr, "fail to write output file\n"); abort(); }
-	if (o.sort) if (const int rc = write_sorted_main(o, H, refs, sorted, &st)) return rc;
+	if (sorting_device) {
+		const double ts = walltime();
+		const int rc = sort_sink->finish();
+		const SortSinkStats &ss = sort_sink->st;
+		if (rc) { if (!sort_sink->ok()) fprintf(stderr, "[panSVR-amd] --sort-device: the main file [%s] was not written\n", o.out.c_str()); return rc; }
+		if (!ss.left) {
+			st.t_sort_order = ss.t_order;
+			fprintf(stderr, "[panSVR-amd] --sort-device: %lld records (%.1f MB) ordered on the device in %.1f ms, %lld members\n", ss.records, (ss.device_bytes + ss.host_bytes) / 1e6, ss.t_order * 1e3, ss.members);
+		}
+		st.t_sort = walltime() - ts;
+		st.sorter = sort_sink->sorter();
+		st.sort_device_bytes = ss.device_bytes, st.sort_host_bytes = ss.host_bytes, st.sort_records = ss.records, st.sort_members = ss.members;
+	} else if (o.sort) if (const int rc = write_sorted_main(o, H, refs, sorted, &st)) return rc;
 	if (frec) fclose(frec);
 	st.wall = walltime() - st.wall0;                     // first FASTQ byte to the files closed; giving the HBM back is reported beside it, like the index load
 	drv.release();
@@ -568,6 +659,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
 	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
 	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
+	                "         aln <reads.fq>: --sort-device   (implies --sort, --emit-device and --deflate-device; the records are kept, ordered and compressed in GPU memory)\n"
 	                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 	return 1;
 }

@@ -10,6 +10,7 @@
 #include "../../include/psvr_engine.h"
 #include "common.h"
 #include "scan.h"
+#include "sort_device.h"
 
 namespace psvr {
 
@@ -119,6 +120,49 @@ static SortCtx &sort_ctx() { static SortCtx c; return c; }
 
 using namespace psvr;
 
+
+// the body of the sort over device pointers (sort_device.h): psvr_sort_order_u64 below and psvr_bam_store_order (bam_store.hip) both run it
+int psvr::sort_order_device(hipStream_t st, long long n, uint64_t *d_keys, SortScratch &S, std::vector<uint32_t> &h, const uint32_t **d_order, const char *who)
+{
+	*d_order = nullptr;
+	if (n <= 0) return PSVR_OK;
+	const long long ntile = (n + kSortTile - 1) / kSortTile, ncnt = 256 * ntile;
+	const int nhb = (int)(ntile < kHistBlocks ? ntile : kHistBlocks);
+	// a second key array and two index arrays (ping-pong with the caller's keys), the (digit, tile) counts and offsets, the scan's and the histogram's scratch
+	const size_t need = (size_t)n * 16 + (size_t)ncnt * 12 + scan_tmp_bytes(1, ncnt) + (size_t)(nhb + 1) * 8192;
+	if (S.k1.alloc((size_t)n * 8) || S.i0.alloc((size_t)n * 4) || S.i1.alloc((size_t)n * 4) || S.cnt.alloc((size_t)ncnt * 4) ||
+	    S.off.alloc((size_t)ncnt * 8) || S.tmp.alloc(scan_tmp_bytes(1, ncnt)) || S.slab.alloc((size_t)nhb * 8192) || S.hist.alloc(8192)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "%s: %zu bytes of device memory needed for %lld keys", who, need + (size_t)n * 8, n);
+	}
+	h.assign(2048, 0);
+	StreamDrain drain{st};                                         // (after the buffers: nothing is in flight when they are freed)
+	hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nhb), dim3(256), 0, st, (const uint64_t *)d_keys, n, S.slab.as<uint32_t>());
+	hipLaunchKernelGGL(k_sort_hist_sum, dim3(8), dim3(256), 0, st, (const uint32_t *)S.slab.p, nhb, S.hist.as<uint32_t>());
+	PSVR_HIP(hipGetLastError());
+	PSVR_HIP(hipMemcpyAsync(h.data(), S.hist.p, 8192, hipMemcpyDeviceToHost, st));
+	PSVR_HIP(hipStreamSynchronize(st));
+	uint64_t *kin = d_keys, *kout = S.k1.as<uint64_t>();
+	uint32_t *iin = nullptr, *iout = S.i0.as<uint32_t>();
+	for (int d = 0; d < 8; ++d) {
+		bool constant = false;
+		for (int v = 0; v < 256; ++v) if (h[(size_t)d * 256 + v] == (uint32_t)n) constant = true;
+		if (constant) continue;                                    // this digit orders nothing
+		hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, n, 8 * d, ntile, S.cnt.as<int32_t>());
+		ScanSet X = {};
+		X.cnt[0] = S.cnt.as<int32_t>(), X.out[0] = S.off.as<long long>(), X.stride[0] = 1;
+		scan_launch(X, 1, ncnt, S.tmp.as<long long>(), st);
+		hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (const uint32_t *)iin, n, 8 * d, ntile,
+		                   (const long long *)S.off.p, kout, iout);
+		PSVR_HIP(hipGetLastError());
+		std::swap(kin, kout);
+		iin = iout, iout = (iout == S.i0.as<uint32_t>()) ? S.i1.as<uint32_t>() : S.i0.as<uint32_t>();
+	}
+	drain.armed = false;                                           // (what is queued reads and writes the caller's keys and S only: the caller waits)
+	*d_order = iin;
+	return PSVR_OK;
+}
+
 extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *order)
 {
 	if (n < 0 || (n > 0 && (!keys || !order))) return set_error(PSVR_ERR_ARG, "psvr_sort_order_u64: bad argument");
@@ -136,37 +180,16 @@ extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, 
 	size_t free_b = 0, total_b = 0;
 	PSVR_HIP(hipMemGetInfo(&free_b, &total_b));
 	if (need > free_b) return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_u64: %zu bytes of device memory needed for %lld keys, %zu free", need, (long long)n, free_b);
-	DevBuf k0, k1, i0, i1, cnt, off, tmp, slab, hist;
-	if (k0.alloc((size_t)n * 8) || k1.alloc((size_t)n * 8) || i0.alloc((size_t)n * 4) || i1.alloc((size_t)n * 4) || cnt.alloc((size_t)ncnt * 4) ||
-	    off.alloc((size_t)ncnt * 8) || tmp.alloc(scan_tmp_bytes(1, ncnt)) || slab.alloc((size_t)nhb * 8192) || hist.alloc(8192)) {
+	DevBuf k0;
+	SortScratch S;
+	if (k0.alloc((size_t)n * 8)) {
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_u64: %zu bytes of device memory needed for %lld keys", need, (long long)n);
 	}
-	std::vector<uint32_t> &h = c.h_hist;
-	h.assign(2048, 0);
 	StreamDrain drain{st};                                         // (after the buffers: nothing is in flight when they are freed)
 	PSVR_HIP(hipMemcpyAsync(k0.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, st));
-	hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nhb), dim3(256), 0, st, k0.as<uint64_t>(), (long long)n, slab.as<uint32_t>());
-	hipLaunchKernelGGL(k_sort_hist_sum, dim3(8), dim3(256), 0, st, (const uint32_t *)slab.p, nhb, hist.as<uint32_t>());
-	PSVR_HIP(hipGetLastError());
-	PSVR_HIP(hipMemcpyAsync(h.data(), hist.p, 8192, hipMemcpyDeviceToHost, st));
-	PSVR_HIP(hipStreamSynchronize(st));
-	uint64_t *kin = k0.as<uint64_t>(), *kout = k1.as<uint64_t>();
-	uint32_t *iin = nullptr, *iout = i0.as<uint32_t>();
-	for (int d = 0; d < 8; ++d) {
-		bool constant = false;
-		for (int v = 0; v < 256; ++v) if (h[(size_t)d * 256 + v] == (uint32_t)n) constant = true;
-		if (constant) continue;                                    // this digit orders nothing
-		hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (long long)n, 8 * d, ntile, cnt.as<int32_t>());
-		ScanSet S = {};
-		S.cnt[0] = cnt.as<int32_t>(), S.out[0] = off.as<long long>(), S.stride[0] = 1;
-		scan_launch(S, 1, ncnt, tmp.as<long long>(), st);
-		hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (const uint32_t *)iin, (long long)n, 8 * d, ntile,
-		                   (const long long *)off.p, kout, iout);
-		PSVR_HIP(hipGetLastError());
-		std::swap(kin, kout);
-		iin = iout, iout = (iout == i0.as<uint32_t>()) ? i1.as<uint32_t>() : i0.as<uint32_t>();
-	}
+	const uint32_t *iin = nullptr;
+	if (int rc = sort_order_device(st, (long long)n, k0.as<uint64_t>(), S, c.h_hist, &iin, "psvr_sort_order_u64")) return rc;
 	if (iin) PSVR_HIP(hipMemcpyAsync(order, iin, (size_t)n * 4, hipMemcpyDeviceToHost, st));
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(st));

@@ -127,70 +127,56 @@ inline void name_order(const SortRecords &R, std::vector<uint32_t> &ord)
 	});
 }
 
-// writes out_fn (and out_fn + ".bai" unless by_name); false with the reason in *err
-inline bool write_sorted_bam(const std::string &out_fn, const std::string &header_text, const std::vector<std::pair<std::string, int32_t>> &refs,
-                             const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err,
-                             BgzfMembersFn dev_fn = nullptr, int device = 0, size_t dev_window_blocks = kDeflateDeviceBlocks)
+// the header text with the sort order stated, as samtools rewrites it
+inline std::string sorted_header_text(const std::string &header_text, bool by_name)
 {
-	// header with the sort order stated, as samtools rewrites it
 	std::string text = header_text;
 	while (!text.empty() && text.back() == '\0') text.pop_back();
-	{
-		const std::string so = by_name ? "queryname" : "coordinate";
-		if (text.compare(0, 3, "@HD") == 0) {
-			const size_t eol = text.find('\n');
-			std::string hd = text.substr(0, eol);
-			const size_t p = hd.find("\tSO:");
-			if (p != std::string::npos) { size_t e = hd.find('\t', p + 1); hd.erase(p, (e == std::string::npos ? hd.size() : e) - p); }
-			hd += "\tSO:" + so;
-			text = hd + text.substr(eol == std::string::npos ? text.size() : eol);
-		} else text = "@HD\tVN:1.6\tSO:" + so + "\n" + text;
-	}
-	std::vector<BamRef> brefs;
-	for (auto &rf : refs) brefs.push_back({rf.first, (uint32_t)rf.second});
-	const std::vector<uint8_t> head = bam_header_block(text, brefs);
-	const uint64_t header_bytes = head.size();
-	BgzfWriter w(dev_window_blocks);
-	if (!w.open(out_fn.c_str(), threads)) { *err = "fail to open file '" + out_fn + "'"; return false; }
-	w.log_block_starts();
-	if (dev_fn) w.set_device_members(device, dev_fn), w.set_device_min_blocks(1);       // (the tail of the stream goes to the device too)
-	w.write(head.data(), head.size());
-	for (size_t i = 0; i < ord.size() && w.ok(); ++i) {
-		const uint8_t *r = R.rec(ord[i]);
-		w.write(r, 4 + SortRecords::u32(r));
-	}
-	if (!w.close()) { *err = w.compress_failed() ? "compression failed" : "fail to write file '" + out_fn + "'"; return false; }
-	if (by_name) return true;
-	// ---- .bai
-	// the stream's blocks of 0xff00 bytes, the header included: their file offsets give the virtual offsets
-	const std::vector<uint64_t> &cstart = w.block_starts();
+	const std::string so = by_name ? "queryname" : "coordinate";
+	if (text.compare(0, 3, "@HD") == 0) {
+		const size_t eol = text.find('\n');
+		std::string hd = text.substr(0, eol);
+		const size_t p = hd.find("\tSO:");
+		if (p != std::string::npos) { size_t e = hd.find('\t', p + 1); hd.erase(p, (e == std::string::npos ? hd.size() : e) - p); }
+		hd += "\tSO:" + so;
+		text = hd + text.substr(eol == std::string::npos ? text.size() : eol);
+	} else text = "@HD\tVN:1.6\tSO:" + so + "\n" + text;
+	return text;
+}
+
+// what the .bai needs of one record of the sorted stream: end = max(pos, 0) + the CIGAR's reference span (1 base without one), len = 4 + block_size
+struct BaiRecord { int32_t tid, pos; int64_t end; uint32_t bin, flag, len; };
+
+// The .bai of SAMv1 section 5.2 for a sorted stream of n records behind header_bytes of BAM header, cut into blocks of 0xff00 bytes: cstart =
+// the file offset at which every block starts, the EOF block's last (BgzfWriter::block_starts); view(i) = record i in sorted order.  The one
+// builder: write_sorted_bam calls it over SortRecords, sort_store_sink.h over psvr_bam_store_meta's table.
+template <class View> inline std::vector<uint8_t> build_bai(size_t n_refs, size_t n, uint64_t header_bytes, const std::vector<uint64_t> &cstart, View view)
+{
 	const size_t nb = cstart.size() - 1, kBlock = kBgzfBlock;
 	auto voff = [&](uint64_t u) { const size_t b = (size_t)(u / kBlock); return b < nb ? (cstart[b] << 16) | (u % kBlock) : (cstart[nb] << 16); };   // (the end of the data = the EOF block)
 	struct RefIdx { std::map<uint32_t, std::vector<std::pair<uint64_t, uint64_t>>> bins; std::vector<uint64_t> lin; uint64_t beg = ~0ull, end = 0, n_mapped = 0, n_unmapped = 0; };
-	std::vector<RefIdx> ri(refs.size());
+	std::vector<RefIdx> ri(n_refs);
 	uint64_t n_no_coor = 0, u = header_bytes;
-	for (size_t i = 0; i < ord.size(); ++i) {
-		const uint8_t *h = R.rec(ord[i]);
+	for (size_t i = 0; i < n; ++i) {
+		const BaiRecord h = view(i);
 		const uint64_t us = u;
-		u += 4 + SortRecords::u32(h);
-		const uint32_t tid = SortRecords::u32(h + 4);
-		if ((int32_t)tid < 0 || tid >= ri.size()) { ++n_no_coor; continue; }
-		const int32_t pos = (int32_t)SortRecords::u32(h + 8);
-		const uint32_t bin = h[14] | (uint32_t)h[15] << 8;
+		u += h.len;
+		const uint32_t tid = (uint32_t)h.tid;
+		if (h.tid < 0 || tid >= ri.size()) { ++n_no_coor; continue; }
 		const uint64_t vb = voff(us), ve = voff(u);
 		RefIdx &X = ri[tid];
-		auto &ch = X.bins[bin];
+		auto &ch = X.bins[h.bin];
 		if (!ch.empty() && ch.back().second == vb) ch.back().second = ve;       // adjacent records of a bin share a chunk
 		else ch.push_back({vb, ve});
 		// reference span from the CIGAR (1 base without one), for the linear index
-		const int64_t rlen = SortRecords::ref_span(h), beg = pos < 0 ? 0 : pos, end = beg + (rlen > 0 ? rlen : 1);
+		const int64_t beg = h.pos < 0 ? 0 : h.pos, end = h.end;
 		for (int64_t w = beg >> 14; w <= (end - 1) >> 14; ++w) {
 			if ((size_t)w >= X.lin.size()) X.lin.resize((size_t)w + 1, 0);
 			if (X.lin[(size_t)w] == 0) X.lin[(size_t)w] = vb;
 		}
 		if (vb < X.beg) X.beg = vb;
 		if (ve > X.end) X.end = ve;
-		if ((h[18] | h[19] << 8) & 0x4) ++X.n_unmapped; else ++X.n_mapped;
+		if (h.flag & 0x4) ++X.n_unmapped; else ++X.n_mapped;
 	}
 	std::vector<uint8_t> bai = {'B', 'A', 'I', 1};
 	auto b32 = [&](uint32_t v) { for (int k = 0; k < 4; ++k) bai.push_back((uint8_t)(v >> (8 * k))); };
@@ -206,9 +192,45 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 		for (uint64_t v : X.lin) b64(v);
 	}
 	b64(n_no_coor);
+	return bai;
+}
+inline bool write_bai(const std::string &out_fn, const std::vector<uint8_t> &bai, std::string *err)
+{
 	FILE *fi = fopen((out_fn + ".bai").c_str(), "wb");
 	if (!fi || fwrite(bai.data(), 1, bai.size(), fi) != bai.size() || fclose(fi) != 0) { *err = "fail to write file '" + out_fn + ".bai'"; return false; }
 	return true;
+}
+// record i of SortRecords as the .bai builder sees it
+inline BaiRecord bai_record(const uint8_t *h)
+{
+	const int32_t pos = (int32_t)SortRecords::u32(h + 8);
+	const int64_t rlen = SortRecords::ref_span(h), beg = pos < 0 ? 0 : pos;
+	return {(int32_t)SortRecords::u32(h + 4), pos, beg + (rlen > 0 ? rlen : 1), h[14] | (uint32_t)h[15] << 8, h[18] | (uint32_t)h[19] << 8, 4 + SortRecords::u32(h)};
+}
+
+// writes out_fn (and out_fn + ".bai" unless by_name); false with the reason in *err
+inline bool write_sorted_bam(const std::string &out_fn, const std::string &header_text, const std::vector<std::pair<std::string, int32_t>> &refs,
+                             const SortRecords &R, const std::vector<uint32_t> &ord, bool by_name, int threads, std::string *err,
+                             BgzfMembersFn dev_fn = nullptr, int device = 0, size_t dev_window_blocks = kDeflateDeviceBlocks)
+{
+	const std::string text = sorted_header_text(header_text, by_name);
+	std::vector<BamRef> brefs;
+	for (auto &rf : refs) brefs.push_back({rf.first, (uint32_t)rf.second});
+	const std::vector<uint8_t> head = bam_header_block(text, brefs);
+	const uint64_t header_bytes = head.size();
+	BgzfWriter w(dev_window_blocks);
+	if (!w.open(out_fn.c_str(), threads)) { *err = "fail to open file '" + out_fn + "'"; return false; }
+	w.log_block_starts();
+	if (dev_fn) w.set_device_members(device, dev_fn), w.set_device_min_blocks(1);       // (the tail of the stream goes to the device too)
+	w.write(head.data(), head.size());
+	for (size_t i = 0; i < ord.size() && w.ok(); ++i) {
+		const uint8_t *r = R.rec(ord[i]);
+		w.write(r, 4 + SortRecords::u32(r));
+	}
+	if (!w.close()) { *err = w.compress_failed() ? "compression failed" : "fail to write file '" + out_fn + "'"; return false; }
+	if (by_name) return true;
+	// ---- .bai: from the stream's blocks of 0xff00 bytes, the header included (their file offsets give the virtual offsets)
+	return write_bai(out_fn, build_bai(refs.size(), ord.size(), header_bytes, w.block_starts(), [&](size_t i) { return bai_record(R.rec(ord[i])); }), err);
 }
 
 } // namespace psvr

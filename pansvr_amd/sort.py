@@ -1,9 +1,9 @@
-"""Stable device order of 64-bit keys through the C ABI (psvr_sort_order_u64)."""
+"""Stable device order of 64-bit keys (psvr_sort_order_u64) and the device-resident record store (psvr_bam_store_*) through the C ABI."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib
+from ._lib import EngineError, check, lib  # noqa: F401
 
 
 def sort_order(keys, device=0):
@@ -14,3 +14,69 @@ def sort_order(keys, device=0):
     out = np.empty(len(k), dtype=np.uint32)
     check(lib().psvr_sort_order_u64(C.c_int(device), C.c_int64(len(k)), k.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
     return out
+
+
+class StoreInfo(C.Structure):  # psvr_bam_store_info_t
+    _fields_ = [("n_records", C.c_int64), ("n_bytes", C.c_int64), ("key_exact", C.c_int32), ("ordered", C.c_int32)]
+
+
+class RecMeta(C.Structure):  # psvr_bam_rec_meta_t
+    _fields_ = [("end", C.c_int64), ("tid", C.c_int32), ("pos", C.c_int32), ("len", C.c_uint32), ("index", C.c_uint32), ("bin", C.c_uint16), ("flag", C.c_uint16),
+                ("pad", C.c_uint32)]
+
+
+META_DTYPE = np.dtype([("end", "<i8"), ("tid", "<i4"), ("pos", "<i4"), ("len", "<u4"), ("index", "<u4"), ("bin", "<u2"), ("flag", "<u2"), ("pad", "<u4")])
+
+
+class BamStore:
+    """One psvr_bam_store_t: BAM records kept in HBM, ordered there by samtools' coordinate key and handed to a BgzfStream in sorted order.
+    Single-owner."""
+
+    def __init__(self, device=0):
+        self.h = C.c_void_p()
+        lib().psvr_bam_store_destroy.restype = None
+        check(lib().psvr_bam_store_create(C.c_int(device), C.byref(self.h)))
+
+    def append(self, data):
+        """BAM records back to back (block_size first) from the host"""
+        buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+        check(lib().psvr_bam_store_append(self.h, buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf))))
+
+    def append_emit(self, emitter, first_pair, n_pairs):
+        """the records of pairs [first_pair, first_pair + n_pairs) of a BamEmitter's last run, device to device; the emitter must not run
+        again before a later info, append, order or download has returned"""
+        check(lib().psvr_bam_store_append_emit(self.h, emitter.h, C.c_int64(first_pair), C.c_int64(n_pairs)))
+
+    def info(self):
+        """StoreInfo (n_records, n_bytes, key_exact, ordered), after a wait for what is queued"""
+        i = StoreInfo()
+        check(lib().psvr_bam_store_info(self.h, C.byref(i)))
+        return i
+
+    def order(self):
+        check(lib().psvr_bam_store_order(self.h))
+
+    def meta(self, first_rank=0, n=None):
+        """structured array (META_DTYPE) of sorted ranks [first_rank, first_rank + n); n = None: to the end"""
+        if n is None:
+            n = self.info().n_records - first_rank
+        out = np.zeros(max(n, 1), dtype=META_DTYPE)
+        check(lib().psvr_bam_store_meta(self.h, C.c_int64(first_rank), C.c_int64(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def stream(self, bgzf_stream, first_rank, n):
+        """the records of those sorted ranks behind the pending bytes of a BgzfStream, device to device"""
+        check(lib().psvr_bam_store_stream(self.h, bgzf_stream.h, C.c_int64(first_rank), C.c_int64(n)))
+
+    def download(self):
+        """every record in append order, with the recomputed bin (uint8 array)"""
+        n = self.info().n_bytes
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        got = C.c_int64(0)
+        check(lib().psvr_bam_store_download(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n), C.byref(got)))
+        return out[:got.value]
+
+    def close(self):
+        if self.h:
+            lib().psvr_bam_store_destroy(self.h)
+            self.h = None

@@ -1,8 +1,8 @@
 """`panSVR aln` end to end with the record encoder on the host threads and on the device, on the bench batch written as FASTQ (bench.py's
 workload: 10 000 anchors, seed 11; the reads of rank 0, seed 13) in RAM-backed storage.  The routes --deflate-device,
---parse-device --deflate-device, --emit-device --deflate-device and --stream-device, and the second and third with --sort, run interleaved
+--parse-device --deflate-device, --emit-device --deflate-device and --stream-device, the first three with --sort, and --sort-device, run interleaved
 `--reps` times (--routes: only the named ones), each command in a child of its own; wall_s, read_parse_s, engine_s, format_s and write_s come from the command's e2e_json line.  The unsorted
-routes' inflated payloads are compared with the first route's.  One JSON line.
+routes' inflated payloads are compared with the first route's, the sorted routes' files (BAM and .bai, byte for byte) with the first sorted route's.  One JSON line.
     python tools/emit_device_e2e.py [--pairs 1000000] [--threads 16] [--reps 3] [--routes a,b,...] [--profile-dir DIR] [--profile-route emit_device]
 --profile-dir: one more run of one route (--profile-route) under `rocprofv3 --kernel-trace --stats` (kernel times only, no counters), its
 files left in DIR."""
@@ -21,8 +21,9 @@ CLI = os.path.join(ROOT, "pansvr_amd", "bin", "panSVR")
 HEADER = "@SQ\tSN:chr1\tLN:250000000\n@SQ\tSN:chr2\tLN:250000000\n"
 ROUTES = (("deflate_device", ["--deflate-device"]), ("parse_device", ["--parse-device", "--deflate-device"]), ("emit_device", ["--emit-device", "--deflate-device"]),
           ("stream_device", ["--stream-device"]),
-          ("parse_device_sort", ["--parse-device", "--deflate-device", "--sort"]), ("emit_device_sort", ["--emit-device", "--deflate-device", "--sort"]))
-KEYS = ("wall_s", "read_parse_s", "engine_s", "format_s", "write_s", "sort_s", "emitter", "emit_device_pairs", "emit_declined_pairs", "parser", "pieces", "streamer", "stream_device_bytes",
+          ("deflate_device_sort", ["--deflate-device", "--sort"]), ("parse_device_sort", ["--parse-device", "--deflate-device", "--sort"]),
+          ("emit_device_sort", ["--emit-device", "--deflate-device", "--sort"]), ("sort_device", ["--sort-device"]))
+KEYS = ("wall_s", "read_parse_s", "engine_s", "format_s", "write_s", "sort_s", "sort_order_s", "sorter", "sort_device_bytes", "sort_host_bytes", "sort_records", "sort_members", "emitter", "emit_device_pairs", "emit_declined_pairs", "parser", "pieces", "streamer", "stream_device_bytes",
         "stream_host_bytes", "stream_members")
 
 
@@ -59,13 +60,17 @@ def main():
         pos = [os.path.join(tmp, "idx"), fq, os.path.join(tmp, "header.sam")]
         res = {"pairs": a.pairs, "threads": a.threads, "fastq_bytes": os.path.getsize(fq)}
         print("data ready", file=sys.stderr, flush=True)
-        ref = None
+        ref = ref_sorted = None
         for rep in range(a.reps):
             for name, flags in routes:
                 o, p = os.path.join(tmp, "o.bam"), os.path.join(tmp, "p.bam")
                 res.setdefault(name, []).append(run([CLI, "aln", "-t", str(a.threads), "-o", o, "-p", p] + flags + pos, 600))
                 print(name, res[name][-1], file=sys.stderr, flush=True)
-                if rep == 0 and "--sort" not in flags:
+                if rep == 0 and ("--sort" in flags or "--sort-device" in flags):
+                    files = (open(o, "rb").read(), open(o + ".bai", "rb").read())
+                    ref_sorted = files if ref_sorted is None else ref_sorted
+                    res.setdefault("same_sorted_files", []).append(files == ref_sorted)
+                elif rep == 0:
                     pay = gzip.open(o, "rb").read()
                     ref = pay if ref is None else ref
                     res.setdefault("same_payload", []).append(pay == ref)
