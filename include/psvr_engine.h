@@ -495,6 +495,22 @@ int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *o
  *                 `em` MUST NOT BE RUN AGAIN or destroyed UNTIL A LATER info, append, order or download ON `st` HAS RETURNED (the rule of
  *                 psvr_bgzf_stream_append_emit).  A pair range outside the run, an emitter without a valid run or on another device:
  *                 PSVR_ERR_ARG.  The records are found by walking the block_size chain inside each state-1 pair, bounded by the pair's bytes.
+ *   append_bgzf   a BAM file's own bytes: in[0, n_bytes) holds whole BGZF members back to back (host memory; *in_used: the longest prefix made of
+ *                 whole members, what is behind it is the caller's to complete).  The members are inflated on the device, a wavefront each,
+ *                 straight into the store, and the records are found there: the block_size chain of an inflated stream is serial, so the
+ *                 stream is cut into segments (16 KiB; PSVR_BAM_STORE_SEG_BYTES, at least 64) that each guess their first record start
+ *                 and walk from it, and one pass settles the guesses against the known start and walks again where a guess was wrong --
+ *                 exact for every stream, fast for real ones.  `skip`: inflated bytes at the front of this call that are no records (the BAM
+ *                 header's remainder; 0, or less than the first member's ISIZE on a call that continues no record); n_ref >= 0: the
+ *                 file's reference count, a hint for the guesses only.  Every whole record is appended; the bytes behind the last one
+ *                 (the tail) stay in the store for the next call to complete.  While the tail is not empty append and append_emit are
+ *                 refused (PSVR_ERR_ARG), and so is order ("truncated BAM stream").  The header rules and the ISIZE check are
+ *                 psvr_bgzf_decompress's; a header that is none, or a member that does not inflate to its ISIZE and CRC32: PSVR_ERR_IO,
+ *                 *bad_member its index, nothing of the call is appended and the store stays usable.  A record on the chain that
+ *                 BamReader's rules refuse (block_size < 32 or > 0x7ffffff0, l_seq < 0, fields that leave the record, a name without NUL):
+ *                 PSVR_ERR_DEVICE, from then on for every call.  The call waits.
+ *   chain_info    waits; the chain finder's counters summed over all append_bgzf calls (segments, segments without a guess, guesses
+ *                 that were wrong, segments walked again) and the tail's length.
  *   info          waits for what is queued; key_exact == 0: some position lies outside [-1, 2^31 - 2].
  *   order         sorts the keys where they lie (the sort of psvr_sort_order_u64: stable, equal keys keep append order) and computes where
  *                 every record goes in the sorted stream.  Afterwards appends are refused (PSVR_ERR_ARG).  key_exact == 0 or 2^32 and more
@@ -514,10 +530,13 @@ int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *o
  * A store has one owner at a time; its calls are serialised with psvr_bgzf_compress_members and the streams'. */
 typedef struct psvr_bam_store psvr_bam_store_t;
 typedef struct psvr_bam_store_info { int64_t n_records, n_bytes; int32_t key_exact, ordered; } psvr_bam_store_info_t;
+typedef struct psvr_bam_chain_info { int64_t segments, no_guess, wrong_guess, rewalked, tail_bytes; } psvr_bam_chain_info_t;
 typedef struct psvr_bam_rec_meta { int64_t end; int32_t tid, pos; uint32_t len, index; uint16_t bin, flag; uint32_t pad; } psvr_bam_rec_meta_t; /* 32 bytes */
 int  psvr_bam_store_create(int device, psvr_bam_store_t **out);
 int  psvr_bam_store_append(psvr_bam_store_t *st, const void *bytes, int64_t n_bytes);
 int  psvr_bam_store_append_emit(psvr_bam_store_t *st, const psvr_bam_emit_t *em, int64_t first_pair, int64_t n_pairs);
+int  psvr_bam_store_append_bgzf(psvr_bam_store_t *st, const void *in, int64_t n_bytes, int64_t skip, int32_t n_ref, int64_t *in_used, int64_t *bad_member);
+int  psvr_bam_store_chain_info(psvr_bam_store_t *st, psvr_bam_chain_info_t *info);   /* waits; counters summed over all appends */
 int  psvr_bam_store_info(psvr_bam_store_t *st, psvr_bam_store_info_t *info);       /* waits for what is queued */
 int  psvr_bam_store_order(psvr_bam_store_t *st);
 int  psvr_bam_store_meta(psvr_bam_store_t *st, int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *meta);

@@ -65,6 +65,7 @@ class BgzfReader {
 	const uint8_t *cur_p = nullptr;       // the inflated bytes being handed out: `out` (serial) or a slot's (batched)
 	size_t cur_n = 0;
 	size_t pos = 0;                       // read position in them
+	size_t taken = 0;                     // inflated bytes handed out so far
 	bool eof = false;
 	std::string err;
 
@@ -297,6 +298,7 @@ public:
 	}
 	~BgzfReader() { close(); }
 	const std::string &error() const { return err; }
+	size_t bytes_read() const { return taken; }
 	// exactly n bytes, or false at the end of the file (err is set when the end comes inside a request)
 	bool read(void *dst, size_t n)
 	{
@@ -309,7 +311,7 @@ public:
 			}
 			const size_t k = cur_n - pos < n - done ? cur_n - pos : n - done;
 			memcpy(d + done, cur_p + pos, k);
-			pos += k, done += k;
+			pos += k, done += k, taken += k;
 		}
 		return true;
 	}
@@ -395,6 +397,7 @@ class BamReader {
 public:
 	std::string header_text;
 	std::vector<std::pair<std::string, int32_t>> refs;
+	size_t header_bytes = 0;              // inflated bytes in front of the first record (set by open)
 	const std::string &error() const { return err.empty() ? z.error() : err; }
 	void set_batched(int device, int threads) { z.set_batched(device, threads); }   // before open(): see BgzfReader
 	bool open(const char *path)
@@ -416,6 +419,7 @@ public:
 			name.resize(strlen(name.c_str()));
 			refs.push_back({name, l_ref});
 		}
+		header_bytes = z.bytes_read();
 		return true;
 	}
 	// sam_read1: false at the end of the file (error() is empty then) or on a malformed record

@@ -1,27 +1,139 @@
 // bam_sort.h -- `panSVR sort`: what panSVR_run.sh does after the `aln` step with `samtools sort` + `samtools index`
 // (panSVR_run.sh:53-54), so the drop-in does not depend on an external binary.  Host C++ only.
 //   panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device] in.bam      coordinate order (default) + out.bam.bai, or name order (-n)
+//   panSVR sort --sort-device [-t threads] [-o out.bam] in.bam          the same files as with --deflate-device, the records kept in GPU memory (below)
 // Coordinate order is samtools' (bam_sort.c bam1_lt): reference id as unsigned (unplaced records last), position, forward strand
 // before reverse, ties in input order; name order compares the names with strcmp, first read before second.  The whole file is held
 // in memory (the aln step's output is the signal subset of a run, not the full BAM).  The order and the writing are sorted_bam.h's, which
 // `panSVR aln --sort` shares: the coordinate order is computed on the device when one is visible.
+// --sort-device (sort_device_route): the file's own BGZF members go to the device as they are read, a piece of PSVR_INFLATE_BATCH compressed
+// bytes at a time while the next piece is read; they are inflated into a device-resident record store and cut into records there
+// (psvr_bam_store_append_bgzf, include/psvr_engine.h), and at the end of the file the store is ordered, gathered, compressed and indexed by
+// sort_store_sink.h's writer: no inflated byte and no record visits the host.  Whatever fails -- no device, memory, a position the key cannot
+// hold, a corrupt member, a malformed record, a truncated file -- is named on one line, the store is destroyed, and the --deflate-device
+// route below runs on the same file from its beginning: its messages and its exit status are the command's.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <time.h>
 #include <string>
 #include <vector>
+#include <functional>
+#include <future>
 #include "bam_reader.h"
 #include "sorted_bam.h"
+#include "sort_store_sink.h"
 
 namespace psvr {
 
+// The device route of `panSVR sort --sort-device` over a backend (cli_main.cpp: psvr_bam_store_* and psvr_bgzf_stream_*): sort_store_sink.h's
+// calls, and int store_append_bgzf(const void *, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad_member),
+// int store_chain_info(psvr_bam_chain_info_t *).  0: out_fn and its .bai are written; -1: the route was left (one line said why), the caller
+// sorts the file its other way; 2: the output cannot be written.
+template <class Backend> int sort_device_route(Backend &be, const std::string &in_fn, const std::string &out_fn)
+{
+	auto left = [&](const char *call, const std::string &why) {
+		fprintf(stderr, "[panSVR-amd] sort --sort-device: %s failed (%s): the file is read again and sorted by the --deflate-device route\n", call, why.c_str());
+		return -1;
+	};
+	if (in_fn == "-") return left("opening the input", "a pipe cannot be read twice");
+	std::string text;
+	std::vector<BamRef> refs;
+	size_t header_bytes = 0;
+	{
+		BamReader rd;                                            // the serial reader: the header's text, the references, and how many inflated bytes they took
+		if (!rd.open(in_fn.c_str())) return left("reading the header", rd.error());
+		text = rd.header_text, header_bytes = rd.header_bytes;
+		for (auto &rf : rd.refs) refs.push_back({rf.first, (uint32_t)rf.second});
+	}
+	FILE *f = fopen(in_fn.c_str(), "rb");
+	if (!f) return left("opening the input", "cannot open " + in_fn);
+	struct Closer { FILE *f; Backend &be; uint8_t *buf[2]; ~Closer() { fclose(f); for (uint8_t *b : buf) if (b) be.host_free(b); be.store_destroy(); } } guard{f, be, {nullptr, nullptr}};
+	// the first member to send is the one that holds the first record's first byte; `skip` bytes of it are the header's
+	long long first_off = 0, cum = 0, skip = 0;
+	for (std::vector<uint8_t> h(12 + 65536);;) {
+		const size_t k = fread(h.data(), 1, 12, f);
+		if (k == 0) break;                                       // (the header ends the file: no member to send)
+		uint32_t bsize = 0, xlen = k == 12 ? h[10] | (uint32_t)h[11] << 8 : 0;
+		uint8_t t[4];
+		if (k != 12 || fread(h.data() + 12, 1, xlen, f) != xlen || bgzf_member_header(h.data(), 12 + (uint64_t)xlen, &bsize, &xlen) != 0 || fseek(f, first_off + bsize - 4, SEEK_SET) != 0 ||
+		    fread(t, 1, 4, f) != 4)
+			return left("finding the first record's member", "not a whole BGZF block");
+		const long long isize = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
+		if (cum + isize > (long long)header_bytes) { skip = (long long)header_bytes - cum; break; }
+		cum += isize, first_off += bsize;
+	}
+	if (fseek(f, first_off, SEEK_SET) != 0) return left("finding the first record's member", "seek");
+	if (be.store_create()) return left("store create", be.last_error());
+	// pieces of PSVR_INFLATE_BATCH compressed bytes (bam_reader.h's batch); what lies behind a piece's last whole member (less than a member:
+	// below 64 KiB) is put in front of the next piece, which a second thread reads while the call runs
+	const char *e_piece = getenv("PSVR_INFLATE_BATCH");
+	const size_t piece = e_piece && atoll(e_piece) >= 1 ? (size_t)atoll(e_piece) : (size_t)16 << 20, front = 65536;
+	for (uint8_t *&b : guard.buf) if (!(b = (uint8_t *)be.host_alloc(front + piece))) return left("host_alloc", be.last_error());
+	auto read_piece = [&](int b) { return fread(guard.buf[b] + front, 1, piece, f); };
+	auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
+	const double t0 = now();
+	long long members_in = 0;
+	size_t carry = 0, got = read_piece(0);
+	bool first = true;
+	for (int cur = 0;; cur ^= 1) {
+		const bool eof = got < piece;
+		uint8_t *p = guard.buf[cur] + front - carry;
+		const size_t have = carry + got;
+		std::future<size_t> next;
+		if (!eof) next = std::async(std::launch::async, read_piece, cur ^ 1);
+		int64_t used = 0, bad = -1;
+		const int rc = have ? be.store_append_bgzf(p, (int64_t)have, first ? skip : 0, (int32_t)refs.size(), &used, &bad) : 0;
+		const std::string why = rc ? be.last_error() : "";
+		if (!eof) got = next.get();                              // (the reader is through before anything is given up)
+		if (rc) return left("append_bgzf", why);
+		for (size_t at = 0; at < (size_t)used;) {                // the members the call took, for the statistics line
+			uint32_t bsize = 0, xlen = 0;
+			if (bgzf_member_header(p + at, (uint64_t)used - at, &bsize, &xlen) != 0) break;
+			at += bsize, ++members_in;
+		}
+		if (used > 0) first = false;
+		carry = have - (size_t)used;
+		if (eof) {
+			if (carry) return left("reading the input", carry < 18 ? "not a BGZF block" : "truncated BGZF block");
+			break;
+		}
+		if (carry >= front) return left("reading the input", "a BGZF block of more than 64 KiB");
+		memcpy(guard.buf[cur ^ 1] + front - carry, p + used, carry);
+	}
+	psvr_bam_chain_info_t ci;
+	if (be.store_chain_info(&ci)) return left("chain_info", be.last_error());
+	if (ci.tail_bytes) return left("the end of the input", "truncated BAM stream: the file ends " + std::to_string((long long)ci.tail_bytes) + " bytes into a record");
+	int64_t n_rec = 0, n_bytes = 0;
+	if (be.store_info(&n_rec, &n_bytes)) return left("info", be.last_error());
+	const double t1 = now();
+	SortStoreSink<Backend> sink(be, [](const SortRecords &) { return 2; });
+	sink.adopt(out_fn.c_str(), text, refs);
+	if (const int rc = sink.finish_store()) return rc;
+	const double t2 = now();
+	fprintf(stderr, "[panSVR-amd] sort: %lld records -> %s (coordinate order, ordered on the device, records kept on the device)\n", sink.st.records, out_fn.c_str());
+	fprintf(stderr, "[panSVR-amd] sort --sort-device: %lld records, %lld record bytes, %lld members in, %lld members out, %lld segments: %lld without a guess, %lld wrong guesses, %lld walked again; append %.3f s, order %.3f s, write %.3f s\n",
+	        (long long)n_rec, (long long)n_bytes, members_in, sink.st.members, (long long)ci.segments, (long long)ci.no_guess, (long long)ci.wrong_guess, (long long)ci.rewalked,
+	        t1 - t0, sink.st.t_order, t2 - t1 - sink.st.t_order);
+	return 0;
+}
+
+// what bam_sort_main's --sort-device calls: (in.bam, out.bam) -> sort_device_route's answer over the caller's backend
+typedef std::function<int(const std::string &, const std::string &)> SortDeviceFn;
+
+// what --sort-device's usage text says about its speed
+#define PSVR_SORT_CMD_DEVICE_MEASURED \
+	"Measured on the 1.6 M records of\n" \
+	"                                1 M pairs, -t 16 (three interleaved runs, median wall): 0.522 s against 2.359 s for --deflate-device, 1.303 s with\n" \
+	"                                --inflate-device and 1.162 s with --inflate-threads 16 on top (DESIGN.md section 8 f3)"
+
 // deflate_fn: the compressor --deflate-device uses (the CLI hands in &psvr_bgzf_compress_members)
-inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullptr)
+inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullptr, SortDeviceFn sort_device_fn = nullptr)
 {
 	bool by_name = false;
 	int threads = 4, inflate_device = -1, inflate_threads = 0;
-	bool bad_arg = false, deflate_device = false;
+	bool bad_arg = false, deflate_device = false, sort_device = false;
 	std::string out_fn, in_fn;
 	for (int i = 2; i < argc; ++i) {
 		if (!strcmp(argv[i], "-n")) by_name = true;
@@ -29,23 +141,34 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		else if (!strcmp(argv[i], "-o") && i + 1 < argc) out_fn = argv[++i];
 		else if (!strcmp(argv[i], "--inflate-device")) inflate_device = 0;
 		else if (!strcmp(argv[i], "--deflate-device")) deflate_device = true;
+		else if (!strcmp(argv[i], "--sort-device")) sort_device = deflate_device = true;
 		else if (!strcmp(argv[i], "--inflate-threads") && i + 1 < argc) { inflate_threads = atoi(argv[++i]); bad_arg |= inflate_threads < 1; }
 		else in_fn = argv[i];
 	}
 	if (bad_arg) fprintf(stderr, "--inflate-threads wants a positive number\n");
 	if (in_fn.empty() || bad_arg) {
-		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device] in.bam\n"
+		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device | --sort-device] in.bam\n"
 		                "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
 		                "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
 		                "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n"
 		                "         --deflate-device       compress the output's BGZF members on the GPU (device 0), a wavefront per member of 0xff00 bytes, 1024\n"
 		                "                                members a call.  Measured on the 2 M records of 1 M pairs, -t 16: 2.24-2.28 s against 2.45-3.04 s by\n"
 		                "                                default (reading the input is most of both), the file 23 %% larger than zlib's default level makes it;\n"
-		                "                                a call of 201 MB: 14.9 ms = 13.5 GB/s with its copies, zlib's default level on 16 threads 491 ms\n");
+		                "                                a call of 201 MB: 14.9 ms = 13.5 GB/s with its copies, zlib's default level on 16 threads 491 ms\n"
+		                "         --sort-device          coordinate order only; implies --deflate-device.  The file's BGZF members are inflated on the GPU (device 0)\n"
+		                "                                into a record store in its memory, the records are found, ordered, gathered and compressed there: the files\n"
+		                "                                are those of --deflate-device, byte for byte.  Whatever the device route cannot do (no device, memory, a\n"
+		                "                                malformed or truncated file) is named, and the --deflate-device route sorts the file.  " PSVR_SORT_CMD_DEVICE_MEASURED "\n");
 		return 1;
 	}
+	if (sort_device && by_name) { fprintf(stderr, "--sort-device cannot be combined with -n: name order is not built on the device\n"); return 1; }
 	if (out_fn.empty()) out_fn = in_fn + (by_name ? ".nsorted.bam" : ".sorted.bam");
 	if (threads < 1) threads = 1;
+	if (sort_device) {
+		const int rc = sort_device_fn ? sort_device_fn(in_fn, out_fn) : -1;
+		if (!sort_device_fn) fprintf(stderr, "[panSVR-amd] sort --sort-device: this build has no device route: the file is sorted by the --deflate-device route\n");
+		if (rc >= 0) return rc;
+	}
 	BamReader rd;
 	if (inflate_device >= 0 || inflate_threads > 0) rd.set_batched(inflate_device, inflate_threads);
 	if (!rd.open(in_fn.c_str())) { fprintf(stderr, "[panSVR-amd] sort: %s\n", rd.error().c_str()); return 2; }

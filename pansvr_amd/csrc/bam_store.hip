@@ -18,6 +18,13 @@
 // all later appends does nothing.  The next call that waits sees the flag and marks the store unusable: from then on every call answers
 // PSVR_ERR_DEVICE.  Everything runs under DfwCtx's mutex on its stream (bgzf_members.h), as the BGZF stream's calls do: the two are
 // serialised, and psvr_bam_store_stream writes the stream's pending bytes directly (bgzf_stream_run.h).
+//   from a BAM file  psvr_bam_store_append_bgzf: whole BGZF members are uploaded and inflated, a wavefront per member (inflate_device.h), straight
+//                 into the chunk, behind everything inflated into it so far.  Where the records begin is found there too (bam_chain_device.h): a
+//                 wavefront per segment guesses and walks (k_chain_guess), one wavefront settles the guesses (k_chain_settle), and the entries
+//                 of the segments are the "pairs" of k_store_count / k_store_fill: the table is built by the same kernels, the bytes lie where
+//                 they stay.  What is behind the last whole record (the tail: the start of a record that the next call completes) stays in
+//                 the chunk behind its count, and the next call inflates right behind it; a call that does not fit the chunk moves the tail
+//                 to a fresh one.  The call waits for the members' statuses and the chain's result: the host's counts are exact between calls.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -30,6 +37,8 @@
 #include "bam_emit_run.h"
 #include "bgzf_members.h"
 #include "bgzf_stream_run.h"
+#include "inflate_layout.h"
+#include "bam_chain_device.h"
 
 struct psvr_bam_store {
 	int device = 0;
@@ -47,12 +56,21 @@ struct psvr_bam_store {
 	std::vector<uint32_t> h_hist;
 	psvr::DevBuf g_src, smeta, slen, rank_off;               // per sorted rank: address, meta, length, exclusive scan of the lengths (n + 1)
 	std::vector<long long> h_rank_off;
+	// append_bgzf: the tail lies in the last chunk at [fill, fill + tail); the rest is a call's scratch
+	long long tail = 0, seg_bytes = 0;
+	psvr_bam_chain_info_t chain = {0, 0, 0, 0, 0};
+	psvr::DevBuf zin, zmem, zstatus, cseg, centry, ccnt, cres;
+	std::vector<psvr::InfMember> h_mem;                      // (what asynchronous copies touch on the host lives as long as the store)
+	std::vector<int32_t> h_status;
+	psvr::ChainResult *h_res = nullptr;                      // page-locked, behind h_ctl's entries
 };
 
 namespace psvr {
 
 static const size_t kStoreChunk = (size_t)256 << 20;
 static const uint32_t kStoreMaxBlock = 0x7ffffff0u;          // block_size: the lengths go through an int32 scan
+static const long long kStoreSeg = 16 << 10;                 // append_bgzf: a segment of the record-chain finder (PSVR_BAM_STORE_SEG_BYTES)
+static_assert(kStoreMaxBlock == kChainMaxBlock, "the chain finder and the table builder accept the same block sizes");
 
 // the range of a run that an append takes: bytes[pair_off[first], pair_off[first + n_pairs]); state == nullptr: every pair is walked
 struct StoreSrc {
@@ -186,6 +204,35 @@ __global__ void k_store_commit(StoreSrc S, long long *ctl, long long room, const
 	ctl[0] += off[S.n_pairs], ctl[1] += s1 - s0, ctl[2] += s1 - s0;
 }
 
+// ---- append_bgzf: the members inflated into the chunk, and where the records begin in what they hold
+// a wavefront per member, k_bgzf_inflate's body (inflate.hip); out is the chunk behind everything inflated into it so far
+__global__ __launch_bounds__(64) void k_store_inflate(const uint8_t *__restrict__ in, const InfMember *__restrict__ mem, uint8_t *out, int32_t *status)
+{
+	__shared__ InfLds lds;
+	const InfMember m = mem[blockIdx.x];
+	const int rc = inf_member<64>(in + m.in_off, m.bsize, m.hdr, out + m.out_off, m.isize, &lds, (int)threadIdx.x);
+	if (threadIdx.x == 0) status[blockIdx.x] = rc;
+}
+// a wavefront per segment of bytes[0, end) (four to a workgroup): its guess and the walk from it
+__global__ __launch_bounds__(256) void k_chain_guess(const uint8_t *__restrict__ bytes, long long end, long long seg, int32_t n_ref, long long n_seg, ChainSeg *sg)
+{
+	const long long s = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+	if (s >= n_seg) return;                                  // (the whole wavefront)
+	chain_guess<64>(bytes, end, seg, 0, n_ref, s, sg, (int)(threadIdx.x & 63u));
+}
+// one wavefront: the guesses settled into entry[0 .. n_seg], the result for the host
+__global__ __launch_bounds__(64) void k_chain_settle(const uint8_t *__restrict__ bytes, long long end, long long seg, long long n_seg, const ChainSeg *sg, long long *entry, int32_t *cnt,
+                                                     ChainResult *res)
+{
+	const ChainResult R = chain_settle<64>(bytes, end, seg, 0, n_seg, sg, entry, cnt, (int)threadIdx.x);
+	if (threadIdx.x == 0) *res = R;
+}
+// bytes at the front of a file's first call that are no records (the BAM header's remainder) stay in the chunk, in front of the records
+__global__ void k_store_skip(long long *ctl, long long skip)
+{
+	if (ctl[3] == 0) ctl[1] += skip;
+}
+
 // per list position r (a sorted rank, or the append index when order == nullptr and n_order == 0): address, meta and length of its record
 __global__ __launch_bounds__(256) void k_store_rank(const uint32_t *order, const uint64_t *addr, const psvr_bam_rec_meta_t *meta, long long n, uint64_t *g_src, psvr_bam_rec_meta_t *smeta,
                                                     int32_t *slen)
@@ -248,6 +295,10 @@ __global__ __launch_bounds__(256) void k_store_gather(const uint64_t *__restrict
 static int st_bad()
 {
 	return set_error(PSVR_ERR_DEVICE, "psvr_bam_store: the store is unusable: an append was refused on the device (a range or a record chain out of bounds) and was not made, or an earlier call failed while it changed the store");
+}
+static int st_open_tail(const char *who, const psvr_bam_store *st)
+{
+	return set_error(PSVR_ERR_ARG, "%s: the last append_bgzf ended %lld bytes into a record: only append_bgzf can complete it", who, st->tail);
 }
 static int st_no_device() { return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path"); }
 static int st_refresh(psvr_bam_store *st, DfwCtx &c, bool wait)   // the counts as the device holds them; an unusable store says so
@@ -354,8 +405,12 @@ extern "C" int psvr_bam_store_create(int device, psvr_bam_store_t **out)
 	// PSVR_BAM_STORE_CHUNK_BYTES: the size of a chunk (the tests fill several small ones)
 	const char *e_chunk = getenv("PSVR_BAM_STORE_CHUNK_BYTES");
 	st->chunk_bytes = e_chunk && atoll(e_chunk) > 0 ? (size_t)atoll(e_chunk) : kStoreChunk;
+	// PSVR_BAM_STORE_SEG_BYTES: the segment of append_bgzf's record-chain finder (the tests make it small: few records, many segments)
+	const char *e_seg = getenv("PSVR_BAM_STORE_SEG_BYTES");
+	st->seg_bytes = e_seg && atoll(e_seg) > 0 ? std::max((long long)atoll(e_seg), kChainMinSeg) : kStoreSeg;
 	hipError_t e = st->ctl.alloc(8 * 8);
-	if (e == hipSuccess) e = hipHostMalloc((void **)&st->h_ctl, 8 * sizeof(long long), hipHostMallocDefault);
+	if (e == hipSuccess) e = hipHostMalloc((void **)&st->h_ctl, 8 * sizeof(long long) + sizeof(ChainResult), hipHostMallocDefault);
+	if (e == hipSuccess) st->h_res = (ChainResult *)(st->h_ctl + 8);
 	if (e == hipSuccess) e = hipMemsetAsync(st->ctl.p, 0, 8 * 8, c.stream);
 	if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
 	if (e != hipSuccess) {
@@ -383,6 +438,7 @@ extern "C" int psvr_bam_store_append(psvr_bam_store_t *st, const void *bytes, in
 	if (!st || n_bytes < 0 || (n_bytes > 0 && !bytes)) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append: bad argument");
 	if (st->bad) return st_bad();
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append: the store has been ordered, it takes no more records");
+	if (st->tail) return st_open_tail("psvr_bam_store_append", st);
 	// SortRecords::add_stream's rules (sorted_bam.h), before anything is uploaded; every record is a "pair" of the device's walk
 	const uint8_t *p = (const uint8_t *)bytes;
 	std::vector<long long> off(1, 0);
@@ -425,6 +481,7 @@ extern "C" int psvr_bam_store_append_emit(psvr_bam_store_t *st, const psvr_bam_e
 	if (!st || !em) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_emit: null argument");
 	if (st->bad) return st_bad();
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_emit: the store has been ordered, it takes no more records");
+	if (st->tail) return st_open_tail("psvr_bam_store_append_emit", st);
 	if (!em->valid) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_emit: no emitted run of pairs");
 	if (em->device != st->device) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_emit: the records were encoded on device %d, the store is on device %d", em->device, st->device);
 	if (first_pair < 0 || n_pairs < 0 || first_pair > em->n_pairs || n_pairs > em->n_pairs - first_pair)
@@ -442,6 +499,101 @@ extern "C" int psvr_bam_store_append_emit(psvr_bam_store_t *st, const psvr_bam_e
 	const StoreSrc S = {em->bytes.as<uint8_t>(), (long long)em->n_bytes, (const long long *)em->pair_off.p, em->state.as<uint8_t>(), (long long)first_pair, (long long)n_pairs};
 	st->exact = false, st->fill_upper += em->n_bytes, st->rec_upper += run_records;
 	if (int rc = st_queue_append(st, c, S, true)) { st->bad = true; return rc; }
+	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_store_append_bgzf(psvr_bam_store_t *st, const void *in_, int64_t n_bytes, int64_t skip, int32_t n_ref, int64_t *in_used, int64_t *bad_member)
+{
+	if (psvr_device_count() <= 0) return st_no_device();
+	if (!st || n_bytes < 0 || (n_bytes > 0 && !in_) || skip < 0 || !in_used) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_bgzf: bad argument");
+	*in_used = 0;
+	if (bad_member) *bad_member = -1;
+	if (st->bad) return st_bad();
+	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_bgzf: the store has been ordered, it takes no more records");
+	const uint8_t *in = (const uint8_t *)in_;
+	// the BSIZE chain, by psvr_bgzf_decompress's rules: whole members only, a header that is none ends the call before anything is done
+	std::vector<InfMember> &mem = st->h_mem;
+	mem.clear();
+	long long used = 0, total = 0;
+	const long long bad = inf_layout(in, n_bytes, mem, &used, &total);
+	const long long nm = (long long)mem.size();
+	auto io_error = [&](long long m, int status) {
+		if (bad_member) *bad_member = m;
+		return set_error(PSVR_ERR_IO, "psvr_bam_store_append_bgzf: corrupt BGZF block: member %lld at byte %lld (status %d; nothing of this call was appended)", m, m < nm ? mem[(size_t)m].in_off : used, status);
+	};
+	if (bad >= 0) return io_error(bad, kInfHeader);
+	if (nm == 0) return PSVR_OK;                                 // (no whole member: the caller's to complete)
+	if (skip > 0 && (skip >= (long long)mem[0].isize || st->tail))
+		return set_error(PSVR_ERR_ARG, "psvr_bam_store_append_bgzf: skip = %lld: it lies inside the first member (%lld bytes) of a call that continues no record", (long long)skip,
+		                 (long long)mem[0].isize);
+	*in_used = used;
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, st->device)) return rc;
+	if (int rc = st_refresh(st, c, false)) return rc;            // (where the bytes go is the chunk's count)
+	// the stream of this call: the tail, then what the members hold, less the skipped bytes; it lies at chunk + fill + skip
+	const long long end = st->tail + total - skip, n_seg = chain_segments(end, st->seg_bytes);
+	if (st->zin.ensure((size_t)used) || st->zmem.ensure((size_t)nm * sizeof(InfMember)) || st->zstatus.ensure((size_t)nm * 4) || st->cseg.ensure((size_t)(n_seg + 1) * sizeof(ChainSeg)) ||
+	    st->centry.ensure((size_t)(n_seg + 1) * 8) || st->ccnt.ensure((size_t)(n_seg + 1) * 4) || st->cres.ensure(sizeof(ChainResult))) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_bam_store_append_bgzf: device allocation failed for a call of %lld bytes in %lld members and %lld segments", used, nm, n_seg);
+	}
+	const uint8_t *old_tail = st->tail ? st->chunks.back()->as<uint8_t>() + st->fill : nullptr;
+	if (int rc = st_chunk(st, c, st->fill, st->tail + total)) return rc;
+	uint8_t *base = st->chunks.back()->as<uint8_t>() + st->fill;
+	StreamDrain drain{c.stream};
+	if (old_tail && old_tail != base) PSVR_HIP(hipMemcpyAsync(base, old_tail, (size_t)st->tail, hipMemcpyDeviceToDevice, c.stream));   // a fresh chunk: at most one record moves
+	st->h_status.assign((size_t)nm, -1);
+	PSVR_HIP(hipMemcpyAsync(st->zin.p, in, (size_t)used, hipMemcpyHostToDevice, c.stream));
+	PSVR_HIP(hipMemcpyAsync(st->zmem.p, mem.data(), (size_t)nm * sizeof(InfMember), hipMemcpyHostToDevice, c.stream));
+	hipLaunchKernelGGL(k_store_inflate, dim3((unsigned)nm), dim3(64), 0, c.stream, st->zin.as<uint8_t>(), st->zmem.as<InfMember>(), base + st->tail, st->zstatus.as<int32_t>());
+	const uint8_t *bytes = base + skip;
+	if (n_seg) {
+		hipLaunchKernelGGL(k_chain_guess, dim3((unsigned)((n_seg + 3) / 4)), dim3(256), 0, c.stream, bytes, end, st->seg_bytes, n_ref, n_seg, st->cseg.as<ChainSeg>());
+		hipLaunchKernelGGL(k_chain_settle, dim3(1), dim3(64), 0, c.stream, bytes, end, st->seg_bytes, n_seg, (const ChainSeg *)st->cseg.p, st->centry.as<long long>(), st->ccnt.as<int32_t>(),
+		                   st->cres.as<ChainResult>());
+		PSVR_HIP(hipMemcpyAsync(st->h_res, st->cres.p, sizeof(ChainResult), hipMemcpyDeviceToHost, c.stream));
+	}
+	PSVR_HIP(hipGetLastError());
+	PSVR_HIP(hipMemcpyAsync(st->h_status.data(), st->zstatus.p, (size_t)nm * 4, hipMemcpyDeviceToHost, c.stream));
+	drain.armed = false;
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	// (bytes behind the chunk's count and the tail are not part of the store: a refused call leaves it as it was)
+	for (long long i = 0; i < nm; ++i) if (st->h_status[(size_t)i] != kInfOk) { *in_used = 0; return io_error(i, st->h_status[(size_t)i]); }
+	if (n_seg == 0) return PSVR_OK;
+	const ChainResult R = *st->h_res;
+	st->chain.segments += n_seg, st->chain.no_guess += R.no_guess, st->chain.wrong_guess += R.wrong_guess, st->chain.rewalked += R.rewalked;
+	if (R.bad_seg >= 0) {                                        // the store's rule for a record chain that cannot be followed
+		st->bad = true;
+		return set_error(PSVR_ERR_DEVICE, "psvr_bam_store_append_bgzf: malformed BAM record at byte %lld of this call's stream, behind %lld whole records (the store is unusable from here on)",
+		                 R.bad_at + (long long)skip - st->tail, R.total);
+	}
+	if (R.total < 0 || R.tail < 0 || R.tail > end) { st->bad = true; return st_bad(); }
+	if (int rc = st_table(st, c, st->n_rec + R.total)) return rc;
+	if (int rc = st_scratch(st, n_seg)) return rc;
+	// the records are walked where they lie: the run is this call's stream, its "pairs" are the segments' entries
+	const StoreSrc S = {bytes, end, (const long long *)st->centry.p, nullptr, 0, n_seg};
+	const long long want_rec = st->n_rec + R.total, want_bytes = st->n_bytes + (end - R.tail);
+	st->exact = false;
+	if (skip) hipLaunchKernelGGL(k_store_skip, dim3(1), dim3(1), 0, c.stream, st->ctl.as<long long>(), (long long)skip);
+	int rc = st_queue_append(st, c, S, false);
+	if (!rc) rc = st_refresh(st, c, true);
+	if (!rc && (st->n_rec != want_rec || st->n_bytes != want_bytes))
+		rc = set_error(PSVR_ERR_DEVICE, "psvr_bam_store_append_bgzf: the table holds %lld records in %lld bytes, the chain has %lld in %lld", st->n_rec, st->n_bytes, want_rec, want_bytes);
+	if (rc) { st->bad = true; return rc; }
+	st->tail = R.tail;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_store_chain_info(psvr_bam_store_t *st, psvr_bam_chain_info_t *info)
+{
+	if (psvr_device_count() <= 0) return st_no_device();
+	if (!st) return set_error(PSVR_ERR_ARG, "psvr_bam_store_chain_info: null argument");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, st->device)) return rc;
+	if (int rc = st_refresh(st, c, true)) return rc;
+	if (info) *info = st->chain, info->tail_bytes = st->tail;
 	return PSVR_OK;
 }
 
@@ -464,6 +616,7 @@ extern "C" int psvr_bam_store_order(psvr_bam_store_t *st)
 	if (int rc = dfw_bind(c, st->device)) return rc;
 	if (int rc = st_refresh(st, c, true)) return rc;
 	if (st->ordered) return PSVR_OK;
+	if (st->tail) return set_error(PSVR_ERR_ARG, "psvr_bam_store_order: truncated BAM stream: the last append_bgzf ended %lld bytes into a record", st->tail);
 	if (!st->key_exact) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_order: a position outside [-1, 2^31 - 2]: the 64-bit key does not order as samtools' comparator");
 	if (st->n_rec >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_order: %lld records, the order is 32-bit (at most 2^32 - 1 records)", st->n_rec);
 	if (st->keys_spent) return set_error(PSVR_ERR_DEVICE, "psvr_bam_store_order: an earlier order failed after it had begun to move the keys");

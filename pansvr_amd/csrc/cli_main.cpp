@@ -362,15 +362,15 @@ struct StreamMainSink : aln::MainSink {
 };
 
 // --sort-device: sort_store_sink.h's backend over psvr_bam_store_*, psvr_bgzf_stream_* and the pipeline slots' emitters, and the sink as the pipeline sees it
-struct SortBackend : EmitterAccess {
+// the store and stream calls themselves, shared with `panSVR sort --sort-device`
+struct StoreCalls {
 	const int device;
 	psvr_bam_store_t *store = nullptr;
 	psvr_bgzf_stream_t *s = nullptr;
-	SortBackend(EngineDriver &d, int dev) : EmitterAccess(d), device(dev) {}
+	explicit StoreCalls(int dev) : device(dev) {}
 	int store_create() { return psvr_bam_store_create(device, &store); }
 	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
 	int store_append(const void *p, int64_t n) { return psvr_bam_store_append(store, p, n); }
-	int store_append_emit(int slot, int64_t first, int64_t n) { return psvr_bam_store_append_emit(store, drv.bem[slot], first, n); }
 	int store_info(int64_t *n_records, int64_t *n_bytes)
 	{
 		psvr_bam_store_info_t i;
@@ -390,6 +390,19 @@ struct SortBackend : EmitterAccess {
 	{
 		return psvr_bgzf_stream_take(s, finish, out, cap, got, member_off, member_cap, nm, used);
 	}
+};
+struct SortBackend : EmitterAccess, StoreCalls {
+	SortBackend(EngineDriver &d, int dev) : EmitterAccess(d), StoreCalls(dev) {}
+	int store_append_emit(int slot, int64_t first, int64_t n) { return psvr_bam_store_append_emit(store, drv.bem[slot], first, n); }
+};
+// `panSVR sort --sort-device` (bam_sort.h: sort_device_route): the same store and stream calls without an engine, the store filled from the file's own members
+struct SortCmdBackend : StoreCalls {
+	explicit SortCmdBackend(int dev) : StoreCalls(dev) {}
+	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
+	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
+	const char *last_error() { return psvr_last_error(); }
+	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
+	void host_free(void *p) { psvr_host_free(p); }
 };
 struct SortMainSink : aln::MainSink {
 	SortStoreSink<SortBackend> &k;
@@ -655,9 +668,13 @@ int main(int argc, char **argv)
 {
 	if (argc >= 2 && !strcmp(argv[1], "index")) return index_main(argc, argv);
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
-	if (argc >= 2 && !strcmp(argv[1], "sort")) return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members);
+	if (argc >= 2 && !strcmp(argv[1], "sort"))
+		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out) {
+			SortCmdBackend be(0);
+			return psvr::sort_device_route(be, in, out);
+		});
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
-	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
+	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         panSVR sort --sort-device [-t threads] [-o out.bam] in.bam      (the same files, the records inflated, kept, ordered and compressed in GPU memory)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
 	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
 	                "         aln <reads.fq>: --sort-device   (implies --sort, --emit-device and --deflate-device; the records are kept, ordered and compressed in GPU memory)\n"
 	                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");

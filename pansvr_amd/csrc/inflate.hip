@@ -7,13 +7,9 @@
 #include "../../include/psvr_engine.h"
 #include "common.h"
 #include "inflate_device.h"
+#include "inflate_layout.h"
 
 namespace psvr {
-
-struct InfMember {                       // where a member lies in the batch and where its bytes go
-	long long in_off, out_off;
-	uint32_t bsize, hdr, isize, pad;
-};
 
 __global__ __launch_bounds__(64) void k_bgzf_inflate(const uint8_t *__restrict__ in, const InfMember *__restrict__ mem, uint8_t *out, int32_t *status)
 {
@@ -44,18 +40,8 @@ extern "C" int psvr_bgzf_decompress(int device, const void *in_, int64_t n_bytes
 	if (bad_member) *bad_member = -1;
 	// the BSIZE chain: whole members only; a header that is no BGZF header (or an ISIZE its payload cannot reach) ends it as the bad member
 	std::vector<InfMember> mem;
-	long long at = 0, total = 0, bad = -1;
-	while (at < n_bytes) {
-		uint32_t bsize = 0, xlen = 0;
-		const int h = bgzf_member_header(in + at, (uint64_t)(n_bytes - at), &bsize, &xlen);
-		if (h == 1 || (h == 0 && (long long)bsize > n_bytes - at)) break;                     // cut off: the caller's to complete
-		if (h == 2) { bad = (long long)mem.size(); break; }
-		const uint8_t *t = in + at + bsize - 4;
-		const uint32_t isize = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-		if (!inf_isize_possible(isize, bsize - 12 - xlen - 8)) { bad = (long long)mem.size(); break; }
-		mem.push_back({at, total, bsize, 12 + xlen, isize, 0});
-		at += bsize, total += isize;
-	}
+	long long at = 0, total = 0;
+	const long long bad = inf_layout(in, n_bytes, mem, &at, &total);
 	const long long nm = (long long)mem.size();
 	*in_used = at, *out_bytes = total;
 	if (n_members) *n_members = nm;

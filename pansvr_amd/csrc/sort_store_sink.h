@@ -71,6 +71,20 @@ public:
 			on_ = false, st.left = true;
 		}
 	}
+	// A store that the caller has created through the backend and fills itself (`panSVR sort --sort-device`, bam_sort.h, from the file's own
+	// members): finish_store() writes the sorted file and its index from it.  The caller has its input still, so a failed call downloads nothing.
+	void adopt(const char *fn, const std::string &header_text, const std::vector<BamRef> &refs)
+	{
+		fn_ = fn, text_ = sorted_header_text(header_text, false), refs_ = refs;
+		on_ = foreign_ = true;
+	}
+	// 0: written; -1: a backend call failed and has been named, the caller starts over from its input; 2: the file cannot be written.  The store is destroyed
+	int finish_store()
+	{
+		const bool done = on_ && foreign_ && write_device();
+		be_.store_destroy();
+		return done ? 0 : fatal_ ? 2 : -1;
+	}
 	bool on() const { return on_; }
 	bool ok() const { return !fatal_; }
 	const char *sorter() const { return st.left ? "device+host" : "device"; }   // the e2e_json line's "sorter" (host: the option was not in effect)
@@ -134,7 +148,7 @@ private:
 	std::string fn_, text_;
 	std::vector<BamRef> refs_;
 	std::atomic<bool> on_{false};                        // (the formatter's thread asks, the writer's thread answers)
-	bool fatal_ = false;
+	bool fatal_ = false, foreign_ = false;               // foreign_: the store was adopted, its records are not this sink's to rescue
 	SortRecords host_;                                   // the records, once the device route is left
 	uint8_t *pin_ = nullptr;
 	size_t pin_cap_ = 0;
@@ -156,6 +170,11 @@ private:
 	// the device route ends here: every record of the store goes to the host's SortRecords, in append order.  false: they could not be had
 	bool leave(const char *what)
 	{
+		if (foreign_) {
+			fprintf(stderr, "[panSVR-amd] record store on the device failed (%s: %s): the input is read again and sorted by the host's route\n", what, be_.last_error());
+			on_ = false, st.left = true, st.members = 0;
+			return true;
+		}
 		fprintf(stderr, "[panSVR-amd] record store on the device failed (%s: %s): the main file's records are kept and sorted on the host from here on\n", what, be_.last_error());
 		on_ = false, st.left = true, st.members = 0;
 		int64_t n = 0;

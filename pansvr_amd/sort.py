@@ -20,6 +20,10 @@ class StoreInfo(C.Structure):  # psvr_bam_store_info_t
     _fields_ = [("n_records", C.c_int64), ("n_bytes", C.c_int64), ("key_exact", C.c_int32), ("ordered", C.c_int32)]
 
 
+class ChainInfo(C.Structure):  # psvr_bam_chain_info_t
+    _fields_ = [("segments", C.c_int64), ("no_guess", C.c_int64), ("wrong_guess", C.c_int64), ("rewalked", C.c_int64), ("tail_bytes", C.c_int64)]
+
+
 class RecMeta(C.Structure):  # psvr_bam_rec_meta_t
     _fields_ = [("end", C.c_int64), ("tid", C.c_int32), ("pos", C.c_int32), ("len", C.c_uint32), ("index", C.c_uint32), ("bin", C.c_uint16), ("flag", C.c_uint16),
                 ("pad", C.c_uint32)]
@@ -46,6 +50,25 @@ class BamStore:
         """the records of pairs [first_pair, first_pair + n_pairs) of a BamEmitter's last run, device to device; the emitter must not run
         again before a later info, append, order or download has returned"""
         check(lib().psvr_bam_store_append_emit(self.h, emitter.h, C.c_int64(first_pair), C.c_int64(n_pairs)))
+
+    def append_bgzf(self, data, skip=0, n_ref=-1):
+        """whole BGZF members of a BAM file back to back, inflated and cut into records on the device; `skip` inflated bytes at the front are
+        no records (the header's remainder), n_ref is the file's reference count (a hint).  Returns the bytes used (the whole members); a
+        corrupt member raises EngineError (PSVR_ERR_IO) with the member's index as its `bad_member`"""
+        buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
+        used, bad = C.c_int64(0), C.c_int64(-1)
+        try:
+            check(lib().psvr_bam_store_append_bgzf(self.h, buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.c_int64(skip), C.c_int32(n_ref), C.byref(used), C.byref(bad)))
+        except EngineError as e:
+            e.bad_member = bad.value
+            raise
+        return used.value
+
+    def chain_info(self):
+        """ChainInfo (segments, no_guess, wrong_guess, rewalked summed over all append_bgzf calls, tail_bytes), after a wait"""
+        i = ChainInfo()
+        check(lib().psvr_bam_store_chain_info(self.h, C.byref(i)))
+        return i
 
     def info(self):
         """StoreInfo (n_records, n_bytes, key_exact, ordered), after a wait for what is queued"""
