@@ -5,9 +5,9 @@
 // thing that is known, the start of the first record, and walks again only the segments whose guess was wrong.  Compiled for the device (the
 // bodies of k_chain_guess and k_chain_settle, bam_store.hip: a wavefront per segment, then one wavefront) and, with one "lane", for the host
 // (tests/tools/bam_chain_check.cpp: the very same code under AddressSanitizer), as inflate_device.h is.
-//   chain_record   the verdict on the record that starts at `at` when `end` bytes of the stream are there.  The rules are BamReader::next's
-//                  (bam_reader.h: block_size >= 32, l_seq >= 0, name + CIGAR + bases + qualities inside the record, a name of at least its
-//                  NUL) and the store's (bam_store.hip: block_size <= 0x7ffffff0), in the reader's order: a record whose end is not there
+//   chain_record   the verdict on the record that starts at `at` when `end` bytes of the stream are there.  The rules are bam_record.h's:
+//                  the reader's (block_size >= 32, l_seq >= 0, name + CIGAR + bases + qualities inside the record, a name of at least its
+//                  NUL) and the store's cap on block_size (kBamRecStoreMaxBlock), in the reader's order: a record whose end is not there
 //                  is cut off, whatever its head says
 //   chain_guess    the lowest offset of the segment that chain_record calls good, that passes the hints (reference ids in [-1, n_ref),
 //                  positions >= -1, a head that holds its own fields) and whose successor is good too or lies beyond the bytes; where the
@@ -23,6 +23,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include "bam_record.h"
 
 #if defined(__HIPCC__)
 #define PSVR_CF __host__ __device__ inline
@@ -35,7 +36,6 @@ namespace psvr {
 enum { kChainGood = 0, kChainBad = 1, kChainCutHead = 2, kChainCutEnd = 3 };   // chain_record's verdicts
 enum { kChainSegOk = 0, kChainSegBad = 1, kChainSegCut = 2 };                 // how a segment's walk ended
 static const long long kChainMinSeg = 64;
-static const uint32_t kChainMaxBlock = 0x7ffffff0u;
 
 struct ChainSeg {                        // what a segment found out on its own
 	long long guess;                     // -1: none
@@ -67,40 +67,31 @@ PSVR_CF long long chain_first(long long v) { return v; }
 PSVR_CF long long chain_sum(long long v) { return v; }
 #endif
 
-PSVR_CF uint32_t chain_u32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 PSVR_CF int chain_ctz(uint64_t m) { return __builtin_ctzll(m); }
 
-// what the fixed part says about its own record: the fields lie inside block_size, and there is a name
-PSVR_CF bool chain_head_fits(const uint8_t *r, uint32_t bs)
-{
-	const uint64_t l_name = r[12], n_cig = r[16] | (uint32_t)r[17] << 8;
-	const int32_t l_seq = (int32_t)chain_u32(r + 20);
-	if (l_seq < 0) return false;
-	return l_name >= 1 && l_name + 4 * n_cig + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq <= (uint64_t)bs - 32;
-}
-
+// bam_rec_frame's three tests in the order that tells a record the bytes cut off from a malformed one, then the reader's rule
 PSVR_CF int chain_record(const uint8_t *bytes, long long at, long long end, long long *len)
 {
 	*len = 0;
 	if (end - at < 4) return kChainCutHead;
-	const uint32_t bs = chain_u32(bytes + at);
-	if (bs < 32 || bs > kChainMaxBlock) return kChainBad;
-	if (end - at < 36) return kChainCutHead;
+	const uint8_t *r = bytes + at;
+	const uint32_t bs = bam_u32(r);
+	if (bs < kBamRecMinBlock || bs > kBamRecStoreMaxBlock) return kChainBad;
+	if (end - at < kBamRecHead) return kChainCutHead;
 	*len = 4 + (long long)bs;
 	if (*len > end - at) return kChainCutEnd;
-	const uint8_t *r = bytes + at;
-	if (!chain_head_fits(r, bs)) return kChainBad;
-	if (r[36 + r[12] - 1] != 0) return kChainBad;                // the name's last byte
+	if (!bam_rec_reader_fits(r, bs) || !bam_rec_name_ends(r)) return kChainBad;
 	return kChainGood;
 }
 
-// the hints: what a record's head looks like.  For guessing only (n_ref < 0: the reference ids are not looked at)
+// the hints: what the head of a record looks like whose block_size chain_record has passed.  For guessing only (n_ref < 0: the reference ids
+// are not looked at)
 PSVR_CF bool chain_hint(const uint8_t *r, uint32_t bs, int32_t n_ref)
 {
-	const int32_t tid = (int32_t)chain_u32(r + 4), pos = (int32_t)chain_u32(r + 8), mtid = (int32_t)chain_u32(r + 24), mpos = (int32_t)chain_u32(r + 28);
+	const int32_t tid = bam_i32(r + 4), pos = bam_i32(r + 8), mtid = bam_i32(r + 24), mpos = bam_i32(r + 28);
 	if (pos < -1 || mpos < -1 || tid < -1 || mtid < -1) return false;
 	if (n_ref >= 0 && (tid >= n_ref || mtid >= n_ref)) return false;
-	return chain_head_fits(r, bs);
+	return bam_rec_reader_fits(r, bs);
 }
 
 // could a record of the chain start at o?  0: no; 1: a whole record that looks like one, and so does what stands behind it (or nothing does:

@@ -24,6 +24,7 @@
 #include <string.h>
 #include "../../include/psvr_engine.h"
 #include "fastq_device.h"
+#include "bam_record.h"
 
 namespace psvr {
 
@@ -133,22 +134,10 @@ PSVR_FQ uint32_t be_rc_code(uint8_t c)
 	}
 	return 15;
 }
-// the length a CIGAR word carries after the host's round trip through "%d" of an int16 (negative lengths keep their sign bits), and the word
+// the CIGAR word after the host's round trip of its length through "%d" of an int16 (negative lengths keep their sign bits), and the reference
+// bases that word covers (bam_record.h, as the bin's bam_reg2bin)
 PSVR_FQ uint32_t be_cigar_word(uint32_t len16, uint32_t op) { return (uint32_t)(int32_t)(int16_t)(uint16_t)len16 << 4 | op; }
-PSVR_FQ int64_t be_cigar_span(uint32_t len16, uint32_t op)
-{
-	return op == 0 || op == 2 || op == 3 || op == 7 || op == 8 ? (int64_t)((uint32_t)(int32_t)(int16_t)(uint16_t)len16 & 0xfffffffu) : 0;
-}
-PSVR_FQ int be_reg2bin(int64_t beg, int64_t end)               // bam_reg2bin
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
+PSVR_FQ int64_t be_cigar_span(uint32_t len16, uint32_t op) { return bam_cigar_ref_len(be_cigar_word(len16, op)); }
 
 // base + k stays inside [0, n): *at = base + k
 PSVR_FQ bool be_index(int64_t base, int32_t k, int64_t n, int64_t *at)
@@ -288,7 +277,7 @@ template <class S> PSVR_FQ void be_record(const FqGroup &g, const BeInput &in, i
 	const int64_t p0 = (int64_t)R.pos - 1;
 	be_u32(g, body, (uint32_t)R.chr_id), be_u32(g, body, (uint32_t)p0);
 	be_u8(g, body, R.nn + 1), be_u8(g, body, (unsigned)R.mapq);
-	be_u16(g, body, (unsigned)be_reg2bin(p0, p0 + R.rlen));
+	be_u16(g, body, (unsigned)bam_reg2bin(p0, p0 + R.rlen));
 	be_u16(g, body, R.n_cigar), be_u16(g, body, flag), be_u32(g, body, R.read_l);
 	int32_t mtid = -1;
 	int64_t pnext = 0;

@@ -19,6 +19,7 @@
 #include <vector>
 #include "inflate_device.h"
 #include "worker_pool.h"
+#include "bam_record.h"
 #ifdef PSVR_BGZF_ON_DEVICE                            /* (the CLI, which links the engine library: psvr_bgzf_decompress, page-locked slots) */
 #include "../../include/psvr_engine.h"
 #endif
@@ -425,19 +426,18 @@ public:
 	// sam_read1: false at the end of the file (error() is empty then) or on a malformed record
 	bool next(BamRecord &r)
 	{
-		int32_t block = 0;
-		if (!z.read(&block, 4)) return false;
-		if (block < 32) { err = "bad BAM record"; return false; }
-		uint8_t c[32];
-		if (!z.read(c, 32)) { err = "truncated BAM record"; return false; }
-		auto i32 = [&](int o) { return (int32_t)(c[o] | (uint32_t)c[o + 1] << 8 | (uint32_t)c[o + 2] << 16 | (uint32_t)c[o + 3] << 24); };
-		r.tid = i32(0), r.pos = i32(4);
-		r.l_qname = c[8], r.mapq = c[9];
-		r.n_cigar = (uint16_t)(c[12] | (uint16_t)c[13] << 8), r.flag = (uint16_t)(c[14] | (uint16_t)c[15] << 8);
-		r.l_qseq = i32(16), r.mtid = i32(20), r.mpos = i32(24), r.isize = i32(28);
+		uint8_t h[kBamRecHead];                                      // the record's head as bam_record.h takes it: block_size first
+		if (!z.read(h, 4)) return false;
+		const int32_t block = bam_i32(h);
+		if (block < (int32_t)kBamRecMinBlock) { err = "bad BAM record"; return false; }
+		if (!z.read(h + 4, 32)) { err = "truncated BAM record"; return false; }
+		r.tid = bam_i32(h + 4), r.pos = bam_i32(h + 8);
+		r.l_qname = h[12], r.mapq = h[13];
+		r.n_cigar = bam_u16(h + 16), r.flag = bam_u16(h + 18);
+		r.l_qseq = bam_i32(h + 20), r.mtid = bam_i32(h + 24), r.mpos = bam_i32(h + 28), r.isize = bam_i32(h + 32);
 		r.data.resize((size_t)block - 32);
 		if (block > 32 && !z.read(r.data.data(), (size_t)block - 32)) { err = "truncated BAM record"; return false; }
-		if (r.l_qseq < 0 || (size_t)r.l_qname + 4 * (size_t)r.n_cigar + (size_t)((size_t)r.l_qseq + 1) / 2 + (size_t)r.l_qseq > r.data.size()) { err = "bad BAM record"; return false; }
+		if (!bam_rec_fields_inside(h)) { err = "bad BAM record"; return false; }
 		if (r.l_qname == 0 || r.data[(size_t)r.l_qname - 1] != 0) { err = "bad BAM record (read name not NUL-terminated)"; return false; }   // qname() is used as a C string
 		return true;
 	}

@@ -3,7 +3,8 @@
 //   the records   lie in chunks of device memory that are allocated once and never moved (SortRecords::kChunk's idea); a range that is
 //                 appended lies in one chunk, so a record is one address.  Records the encoder left in HBM are copied device to device
 //                 (k_store_copy, k_bs_append's shape), host bytes are uploaded in place
-//   the table     per record its address, its psvr_bam_rec_meta_t (the bin recomputed from position and CIGAR span) and samtools' key, built
+//   the table     per record its address, its psvr_bam_rec_meta_t (the bin recomputed from position and CIGAR span) and samtools' key (what
+//                 a record is, its span, bin and key: bam_record.h, the rules SortRecords runs on the host), built
 //                 on the device for both sources: k_store_count walks the block_size chain of every pair of the range (bounded by the pair's
 //                 own bytes), the scan of scan.h gives every pair its first slot, k_store_fill walks again and writes the entries
 //   the counts    records, bytes of the current chunk in use and bytes in all live in ctl[] on the device; an append from an emitter queues
@@ -38,7 +39,9 @@
 #include "bgzf_members.h"
 #include "bgzf_stream_run.h"
 #include "inflate_layout.h"
+#include "bam_record.h"
 #include "bam_chain_device.h"
+#include "copy_aligned_device.h"
 
 struct psvr_bam_store {
 	int device = 0;
@@ -68,9 +71,7 @@ struct psvr_bam_store {
 namespace psvr {
 
 static const size_t kStoreChunk = (size_t)256 << 20;
-static const uint32_t kStoreMaxBlock = 0x7ffffff0u;          // block_size: the lengths go through an int32 scan
 static const long long kStoreSeg = 16 << 10;                 // append_bgzf: a segment of the record-chain finder (PSVR_BAM_STORE_SEG_BYTES)
-static_assert(kStoreMaxBlock == kChainMaxBlock, "the chain finder and the table builder accept the same block sizes");
 
 // the range of a run that an append takes: bytes[pair_off[first], pair_off[first + n_pairs]); state == nullptr: every pair is walked
 struct StoreSrc {
@@ -81,32 +82,19 @@ struct StoreSrc {
 	long long first, n_pairs;
 };
 
-__device__ inline uint32_t st_u32(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ inline int st_reg2bin(long long beg, long long end)   // SAMv1 section 5.3, as bam_reg2bin (bam_writer.h)
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
 // the range itself: inside the run, and short enough for the chunk's room behind what is in use
 __device__ inline bool st_range(const StoreSrc &S, const long long *ctl, long long room, long long *s0, long long *s1)
 {
 	*s0 = S.pair_off[S.first], *s1 = S.pair_off[S.first + S.n_pairs];
 	return *s0 >= 0 && *s0 <= *s1 && *s1 <= S.n_bytes && ctl[1] >= 0 && ctl[1] <= room && *s1 - *s0 <= room - ctl[1];
 }
-// one record at bytes[at, b): its block_size, or 0 when it is malformed by SortRecords::add_stream's rules (sorted_bam.h)
-__device__ inline uint32_t st_record(const uint8_t *bytes, long long at, long long b)
+// What the store takes, for the kernels' walks and the host's pre-walk alike: a whole record by the formatter's rule (bam_record.h, as
+// SortRecords::add_stream), no longer than the cap (the lengths go through an int32 scan); `avail` bytes are there from rec on
+enum { kStoreRecFine = 0, kStoreRecMalformed = 1, kStoreRecTooLong = 2 };
+__host__ __device__ inline int st_record(const uint8_t *rec, long long avail)
 {
-	if (b - at < 36) return 0;
-	const uint32_t bs = st_u32(bytes + at);
-	if (bs < 32 || bs > kStoreMaxBlock || (long long)bs > b - at - 4) return 0;
-	const uint32_t l_qname = bytes[at + 12], n_cig = bytes[at + 16] | (uint32_t)bytes[at + 17] << 8;
-	if (l_qname + 4 * n_cig > bs - 32) return 0;             // the CIGAR lies inside the record
-	return bs;
+	if (!bam_rec_frame(rec, (uint64_t)avail) || !bam_rec_cigar_inside(rec)) return kStoreRecMalformed;
+	return bam_u32(rec) > kBamRecStoreMaxBlock ? kStoreRecTooLong : kStoreRecFine;
 }
 
 // records of pair first + i -> cnt[i] (cnt[n_pairs] = 0: the scan's last entry is the total); a lane per pair
@@ -125,9 +113,8 @@ __global__ __launch_bounds__(256) void k_store_count(StoreSrc S, long long *ctl,
 		else {
 			long long at = a;
 			while (at < b) {
-				const uint32_t bs = st_record(S.bytes, at, b);
-				if (!bs) { refuse = true; break; }
-				at += 4 + (long long)bs, ++c;
+				if (st_record(S.bytes + at, b - at) != kStoreRecFine) { refuse = true; break; }
+				at += 4 + (long long)bam_u32(S.bytes + at), ++c;
 			}
 		}
 	}
@@ -152,48 +139,26 @@ __global__ __launch_bounds__(256) void k_store_fill(StoreSrc S, long long *ctl, 
 	long long at = S.pair_off[S.first + i], slot = n0 + off[i];
 	const long long last = n0 + off[i + 1];
 	while (at < b && slot < last) {
-		const uint32_t bs = st_record(S.bytes, at, b);
-		if (!bs) return;                                     // (k_store_count has seen every record of the pair: never)
 		const uint8_t *r = S.bytes + at;
-		const int32_t tid = (int32_t)st_u32(r + 4), pos = (int32_t)st_u32(r + 8);
-		const uint32_t l_qname = r[12], n_cig = r[16] | (uint32_t)r[17] << 8, flag = r[18] | (uint32_t)r[19] << 8;
-		long long rlen = 0;
-		for (uint32_t k = 0; k < n_cig; ++k) {
-			const uint32_t c = st_u32(r + 36 + l_qname + 4 * k), op = c & 0xf;
-			if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4;
-		}
-		const long long beg = pos < 0 ? 0 : pos, end = beg + (rlen > 0 ? rlen : 1);
+		if (st_record(r, b - at) != kStoreRecFine) return;   // (k_store_count has seen every record of the pair: never)
 		psvr_bam_rec_meta_t m;
-		m.end = end, m.tid = tid, m.pos = pos, m.len = 4 + bs, m.index = (uint32_t)slot, m.bin = (uint16_t)st_reg2bin(beg, end), m.flag = (uint16_t)flag, m.pad = 0;
+		bam_rec_derived(r, &m);
+		m.index = (uint32_t)slot, m.pad = 0;
 		meta[slot] = m;
 		addr[slot] = (uint64_t)(uintptr_t)(chunk + ctl[1] + (at - s0));
-		key[slot] = (uint64_t)(uint32_t)tid << 32 | (uint64_t)(((uint32_t)pos + 1u) << 1) | ((flag >> 4) & 1);
-		if (pos < -1 || pos > 0x7ffffffe) ctl[4] = 1;
-		at += 4 + (long long)bs, ++slot;
+		key[slot] = bam_sort_key(m.tid, m.pos, m.flag);
+		if (!bam_key_exact(m.pos)) ctl[4] = 1;
+		at += m.len, ++slot;
 	}
 }
 
-// the range's bytes behind what the chunk holds: k_bs_append's shape (16 bytes per lane, the stores aligned on the destination)
+// the range's bytes behind what the chunk holds: k_bs_append's copy (copy_aligned_device.h)
 __global__ __launch_bounds__(256) void k_store_copy(StoreSrc S, const long long *ctl, long long room, uint8_t *__restrict__ chunk)
 {
 	long long s0, s1;
 	if (ctl[3] != 0 || !st_range(S, ctl, room, &s0, &s1)) return;
-	const long long len = s1 - s0;
-	if (len == 0) return;
-	const uint8_t *s = S.bytes + s0;
-	uint8_t *d = chunk + ctl[1];
-	long long lead = (long long)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u);
-	if (lead > len) lead = len;
-	const long long nv = (len - lead) / 16, done = lead + 16 * nv;
-	for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
-		uint4 x;
-		__builtin_memcpy(&x, s + lead + 16 * v, 16);
-		*(uint4 *)(d + lead + 16 * v) = x;
-	}
-	if (blockIdx.x == 0) {
-		if ((long long)threadIdx.x < lead) d[threadIdx.x] = s[threadIdx.x];
-		if ((long long)threadIdx.x < len - done) d[done + threadIdx.x] = s[done + threadIdx.x];
-	}
+	if (s1 == s0) return;
+	copy_aligned_grid(S.bytes + s0, chunk + ctl[1], s1 - s0);
 }
 
 // the append counts: one lane, behind everything of the append that read the counts
@@ -271,9 +236,7 @@ __global__ __launch_bounds__(256) void k_store_gather(const uint64_t *__restrict
 		const uint8_t *s = (const uint8_t *)(uintptr_t)src[i];
 		uint8_t *d = dst + (off[i] - base);
 		const uint32_t len = M[i].len, bin = M[i].bin;
-		uint32_t lead = (16u - (uint32_t)((uintptr_t)d & 15u)) & 15u;
-		if (lead > len) lead = len;
-		const uint32_t nv = (len - lead) / 16u, done = lead + 16u * nv;
+		const uint32_t lead = copy_lead(d, len), nv = (len - lead) / 16u, done = lead + 16u * nv;
 		for (uint32_t v = sub; v < nv; v += 32u) {
 			const bool two = v + 16u < nv;
 			uint4 x, y = {0, 0, 0, 0};
@@ -439,16 +402,14 @@ extern "C" int psvr_bam_store_append(psvr_bam_store_t *st, const void *bytes, in
 	if (st->bad) return st_bad();
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append: the store has been ordered, it takes no more records");
 	if (st->tail) return st_open_tail("psvr_bam_store_append", st);
-	// SortRecords::add_stream's rules (sorted_bam.h), before anything is uploaded; every record is a "pair" of the device's walk
+	// the kernels' own rule (st_record), before anything is uploaded; every record is a "pair" of the device's walk
 	const uint8_t *p = (const uint8_t *)bytes;
 	std::vector<long long> off(1, 0);
 	for (size_t i = 0, n = (size_t)n_bytes; i < n;) {
-		uint32_t bs = 0;
-		bool fine = n - i >= 36;
-		if (fine) bs = p[i] | (uint32_t)p[i + 1] << 8 | (uint32_t)p[i + 2] << 16 | (uint32_t)p[i + 3] << 24, fine = bs >= 32 && bs <= n - i - 4;
-		if (fine) fine = (size_t)p[i + 12] + 4 * (size_t)(p[i + 16] | p[i + 17] << 8) <= bs - 32;
-		if (!fine) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append: malformed record at byte %zu of %zu (nothing was appended)", i, n);
-		if (bs > kStoreMaxBlock) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_append: a record of %u bytes at byte %zu (2 GiB and more are not stored; nothing was appended)", bs, i);
+		const int v = st_record(p + i, (long long)(n - i));
+		if (v == kStoreRecMalformed) return set_error(PSVR_ERR_ARG, "psvr_bam_store_append: malformed record at byte %zu of %zu (nothing was appended)", i, n);
+		const uint32_t bs = bam_u32(p + i);
+		if (v == kStoreRecTooLong) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_append: a record of %u bytes at byte %zu (2 GiB and more are not stored; nothing was appended)", bs, i);
 		i += 4 + (size_t)bs;
 		off.push_back((long long)i);
 	}

@@ -6,7 +6,8 @@
 // format (SAM/BAM specification v1, sections 4.1 BGZF and 4.2 BAM) and the typing rules of htslib's sam_parse1:
 //   * integer tags take the smallest type that holds the value (c/C/s/S/i/I),
 //   * bin = reg2bin(pos, pos + reference length of the CIGAR), or reg2bin(pos, pos + 1) without a CIGAR or with FLAG 0x4
-//     (sam_parse1 takes a span of 1 for an unmapped record whatever its CIGAR, htslib sam.c:1270-1278),
+//     (sam_parse1 takes a span of 1 for an unmapped record whatever its CIGAR, htslib sam.c:1270-1278; bam_reg2bin and the length a CIGAR
+//     word covers are bam_record.h's, the 0x4 / no-CIGAR decision is this encoder's),
 //   * sequence as 4-bit codes of "=ACMGRSVTWYHKDBN", qualities as phred (text - 33), '*' -> 0xff.
 // BgzfWriter is the one BGZF block writer: the stream cut every 0xff00 bytes, each block one member (bgzf_format.h has the framing), made
 // by zlib or the built-in encoder on the worker pool or, a batch gathered in page-locked memory at a time, by a device compressor of the
@@ -27,6 +28,7 @@
 #include <vector>
 #include "worker_pool.h"
 #include "deflate_device.h"
+#include "bam_record.h"
 #ifdef PSVR_BGZF_ON_DEVICE                            /* (the CLI, which links the engine library: psvr_bgzf_compress) */
 #include "../../include/psvr_engine.h"
 #endif
@@ -233,17 +235,6 @@ inline const uint8_t *nt16_table() { static const Nt16Table t; return t.code; } 
 
 struct BamRef { std::string name; uint32_t len; };
 
-inline int bam_reg2bin(int64_t beg, int64_t end)             // SAMv1 section 5.3
-{
-	--end;
-	if (beg >> 14 == end >> 14) return (int)(((1 << 15) - 1) / 7 + (beg >> 14));
-	if (beg >> 17 == end >> 17) return (int)(((1 << 12) - 1) / 7 + (beg >> 17));
-	if (beg >> 20 == end >> 20) return (int)(((1 << 9) - 1) / 7 + (beg >> 20));
-	if (beg >> 23 == end >> 23) return (int)(((1 << 6) - 1) / 7 + (beg >> 23));
-	if (beg >> 26 == end >> 26) return (int)(((1 << 3) - 1) / 7 + (beg >> 26));
-	return 0;
-}
-
 // what a BAM stream starts with (SAMv1 4.2): magic, header text, reference names and lengths
 inline std::vector<uint8_t> bam_header_block(const std::string &text, const std::vector<BamRef> &refs)
 {
@@ -344,7 +335,7 @@ public:
 				if (neg) n = -n;
 				const int op = (int)(q - ops);
 				cig.push_back((uint32_t)n << 4 | (uint32_t)op);
-				if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += (uint32_t)n & 0xfffffff;
+				rlen += bam_cigar_ref_len(cig.back());
 				n = 0, neg = false;
 			}
 		}

@@ -20,11 +20,11 @@
 #include "bgzf_format.h"
 #include "bgzf_members.h"
 #include "bgzf_stream_run.h"
+#include "copy_aligned_device.h"
 
 namespace psvr {
 
-// bytes[pair_off[first], pair_off[first + n_pairs]) of an emitted run behind the pending bytes: 16 bytes per lane, the stores aligned on
-// the destination (source and destination differ modulo 16: the loads are not), head and tail bytes by the first workgroup
+// bytes[pair_off[first], pair_off[first + n_pairs]) of an emitted run behind the pending bytes (the copy itself: copy_aligned_device.h)
 __global__ __launch_bounds__(256) void k_bs_append(const uint8_t *__restrict__ src, long long src_bytes, const long long *__restrict__ pair_off, long long first, long long n_pairs,
                                                    uint8_t *__restrict__ dst, long long dst_cap, long long *ctl, int cur)
 {
@@ -36,20 +36,7 @@ __global__ __launch_bounds__(256) void k_bs_append(const uint8_t *__restrict__ s
 		if (!ok) ctl[2] = 1;
 	}
 	if (len == 0) return;
-	const uint8_t *s = src + s0;
-	uint8_t *d = dst + at;
-	long long lead = (long long)((16u - (uint32_t)((uintptr_t)d & 15u)) & 15u);
-	if (lead > len) lead = len;
-	const long long nv = (len - lead) / 16, done = lead + 16 * nv;
-	for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
-		uint4 x;
-		__builtin_memcpy(&x, s + lead + 16 * v, 16);
-		*(uint4 *)(d + lead + 16 * v) = x;
-	}
-	if (blockIdx.x == 0) {
-		if ((long long)threadIdx.x < lead) d[threadIdx.x] = s[threadIdx.x];
-		if ((long long)threadIdx.x < len - done) d[done + threadIdx.x] = s[done + threadIdx.x];
-	}
+	copy_aligned_grid(src + s0, dst + at, len);
 }
 
 // what follows runs under DfwCtx's mutex, on its stream, bound to the stream's device

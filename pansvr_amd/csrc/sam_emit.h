@@ -542,8 +542,9 @@ public:
 					o.put(nt, (size_t)nn), o.u8(0);
 					int64_t rlen = 0;
 					auto cig_op = [&](long long len, unsigned op) {            // (lengths are printed as int16 and parsed back: negative ones keep their sign bits)
-						o.u32((uint32_t)len << 4 | op);
-						if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += (uint32_t)len & 0xfffffff;
+						const uint32_t word = (uint32_t)len << 4 | op;
+						o.u32(word);
+						rlen += bam_cigar_ref_len(word);
 					};
 					if (cd) for (uint32_t j = 0; j < cd->n_cigar; ++j) { const uint32_t w = V.cig[cd->cigar_off + j]; cig_op((int)(int16_t)(w >> 4), w & 0xf); }
 					else {

@@ -1,7 +1,7 @@
 // sorted_bam.h -- the sorted BAM writer shared by `panSVR sort` (bam_sort.h) and `panSVR aln --sort` (cli_main.cpp): what
 // `samtools sort` + `samtools index` produce between the `aln` and `fc_sv` steps of panSVR_run.sh (lines 53-54).  Host C++ above the C ABI.
 //   SortRecords          the encoded records (block_size + body, the fixed part re-encoded with the bin taken from the CIGAR's span)
-//                        and samtools' coordinate key of each
+//                        and samtools' coordinate key of each; what a record is, its span, bin and key are bam_record.h's
 //   coordinate_order     samtools' order (bam_sort.c bam1_lt): reference id as unsigned (unplaced records last), position, forward strand
 //                        before reverse, ties in input order.  On the device (psvr_sort_order_u64) when one is visible and every
 //                        position lies in SAMv1's range; otherwise std::stable_sort on the host.
@@ -25,25 +25,23 @@
 
 namespace psvr {
 
+// what the sorter and the .bai need of one record (bam_rec_derived, bam_record.h): end = max(pos, 0) + the CIGAR's reference span (1 base without
+// one), len = 4 + block_size
+struct BaiRecord { int32_t tid, pos; int64_t end; uint32_t bin, flag, len; };
+
 struct SortRecords {
 	// every record (block_size + body) in chunks of kChunk bytes that are allocated once and never grow: the records take their own
 	// size in memory, not the up to 3x of one vector that doubles as it fills
 	static const size_t kChunk = (size_t)64 << 20;
 	std::vector<std::vector<uint8_t>> chunk;
 	std::vector<uint64_t> off;              // record i: chunk index << 32 | offset in the chunk
-	std::vector<uint64_t> key;              // (uint64)tid << 32 | (uint32)(pos + 1) << 1 | reverse
-	bool key_exact = true;                  // every pos in [-1, 2^31 - 2]: the key orders exactly as the comparator
+	std::vector<uint64_t> key;              // bam_sort_key (bam_record.h)
+	bool key_exact = true;                  // bam_key_exact for every record: the key orders exactly as the comparator
 	uint64_t bytes = 0;                     // the records' total size
 	size_t size() const { return off.size(); }
 	const uint8_t *rec(size_t i) const { return chunk[(size_t)(off[i] >> 32)].data() + (off[i] & 0xffffffffu); }
-	static uint32_t u32(const uint8_t *p) { return p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
-	static int64_t ref_span(const uint8_t *r)       // reference bases the CIGAR covers (M, D, N, =, X)
-	{
-		const uint32_t l_qname = r[12], n_cig = r[16] | (uint32_t)r[17] << 8;
-		int64_t rlen = 0;
-		for (uint32_t k = 0; k < n_cig; ++k) { const uint32_t c = u32(r + 36 + l_qname + 4 * k); const int op = (int)(c & 0xf); if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rlen += c >> 4; }
-		return rlen;
-	}
+	static uint32_t u32(const uint8_t *p) { return bam_u32(p); }                   // (the names the sink's stand-in store reads a record by)
+	static int64_t ref_span(const uint8_t *r) { return bam_rec_ref_span(r); }
 	// one record: `fixed` = the 32 bytes after block_size (bam1_core_t as in the file), `data` = qname | cigar | seq | qual | aux.
 	// The bin is recomputed from pos and the CIGAR's span (1 base without one); every other byte is kept.
 	void add(const uint8_t fixed[32], const uint8_t *data, size_t n_data)
@@ -61,28 +59,20 @@ struct SortRecords {
 		for (int k = 0; k < 4; ++k) r[k] = (uint8_t)(bs >> (8 * k));
 		memcpy(r + 4, fixed, 32);
 		if (n_data) memcpy(r + 36, data, n_data);
-		const int32_t tid = (int32_t)u32(r + 4), pos = (int32_t)u32(r + 8);
-		const int64_t rlen = ref_span(r), beg = pos < 0 ? 0 : pos;
-		const int bin = bam_reg2bin(beg, beg + (rlen > 0 ? rlen : 1));
-		r[14] = (uint8_t)bin, r[15] = (uint8_t)(bin >> 8);
-		const uint16_t flag = (uint16_t)(r[18] | r[19] << 8);
-		if (pos < -1 || pos > 0x7ffffffe) key_exact = false;
+		BaiRecord m;
+		bam_rec_derived(r, &m);
+		r[14] = (uint8_t)m.bin, r[15] = (uint8_t)(m.bin >> 8);
+		if (!bam_key_exact(m.pos)) key_exact = false;
 		off.push_back((uint64_t)(chunk.size() - 1) << 32 | o);
 		bytes += len;
-		key.push_back((uint64_t)(uint32_t)tid << 32 | (uint64_t)(((uint32_t)pos + 1u) << 1) | ((flag >> 4) & 1));
+		key.push_back(bam_sort_key(m.tid, m.pos, m.flag));
 	}
 	// records back to back as in a BAM stream (what the formatter produces for the main file); false on a malformed one
 	bool add_stream(const uint8_t *p, size_t n)
 	{
-		size_t i = 0;
-		while (i < n) {
-			if (n - i < 36) return false;
-			const uint32_t bs = u32(p + i);
-			if (bs < 32 || bs > n - i - 4) return false;
-			const uint8_t *f = p + i + 4;
-			if ((size_t)f[8] + 4 * (size_t)(f[12] | f[13] << 8) > bs - 32) return false;   // the CIGAR lies inside the record
-			add(f, f + 32, bs - 32);
-			i += 4 + bs;
+		for (size_t i = 0; i < n; i += 4 + (size_t)bam_u32(p + i)) {
+			if (!bam_rec_frame(p + i, n - i) || !bam_rec_cigar_inside(p + i)) return false;
+			add(p + i + 4, p + i + 36, bam_u32(p + i) - 32);
 		}
 		return true;
 	}
@@ -105,9 +95,9 @@ inline bool coordinate_order(const SortRecords &R, int device, std::vector<uint3
 	for (size_t i = 0; i < n; ++i) ord[i] = (uint32_t)i;
 	std::stable_sort(ord.begin(), ord.end(), [&](uint32_t a, uint32_t b) {
 		const uint8_t *x = R.rec(a), *y = R.rec(b);
-		const uint32_t xt = SortRecords::u32(x + 4), yt = SortRecords::u32(y + 4);
+		const uint32_t xt = bam_u32(x + 4), yt = bam_u32(y + 4);
 		if (xt != yt) return xt < yt;
-		const int32_t xp = (int32_t)SortRecords::u32(x + 8), yp = (int32_t)SortRecords::u32(y + 8);
+		const int32_t xp = bam_i32(x + 8), yp = bam_i32(y + 8);
 		if (xp != yp) return xp < yp;
 		return (x[18] & 0x10) < (y[18] & 0x10);
 	});
@@ -143,9 +133,6 @@ inline std::string sorted_header_text(const std::string &header_text, bool by_na
 	} else text = "@HD\tVN:1.6\tSO:" + so + "\n" + text;
 	return text;
 }
-
-// what the .bai needs of one record of the sorted stream: end = max(pos, 0) + the CIGAR's reference span (1 base without one), len = 4 + block_size
-struct BaiRecord { int32_t tid, pos; int64_t end; uint32_t bin, flag, len; };
 
 // The .bai of SAMv1 section 5.2 for a sorted stream of n records behind header_bytes of BAM header, cut into blocks of 0xff00 bytes: cstart =
 // the file offset at which every block starts, the EOF block's last (BgzfWriter::block_starts); view(i) = record i in sorted order.  The one
@@ -203,9 +190,9 @@ inline bool write_bai(const std::string &out_fn, const std::vector<uint8_t> &bai
 // record i of SortRecords as the .bai builder sees it
 inline BaiRecord bai_record(const uint8_t *h)
 {
-	const int32_t pos = (int32_t)SortRecords::u32(h + 8);
-	const int64_t rlen = SortRecords::ref_span(h), beg = pos < 0 ? 0 : pos;
-	return {(int32_t)SortRecords::u32(h + 4), pos, beg + (rlen > 0 ? rlen : 1), h[14] | (uint32_t)h[15] << 8, h[18] | (uint32_t)h[19] << 8, 4 + SortRecords::u32(h)};
+	BaiRecord m;
+	bam_rec_derived(h, &m);                          // (its bin is the record's own: SortRecords::add has written it)
+	return m;
 }
 
 // writes out_fn (and out_fn + ".bai" unless by_name); false with the reason in *err
@@ -225,7 +212,7 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 	w.write(head.data(), head.size());
 	for (size_t i = 0; i < ord.size() && w.ok(); ++i) {
 		const uint8_t *r = R.rec(ord[i]);
-		w.write(r, 4 + SortRecords::u32(r));
+		w.write(r, 4 + bam_u32(r));
 	}
 	if (!w.close()) { *err = w.compress_failed() ? "compression failed" : "fail to write file '" + out_fn + "'"; return false; }
 	if (by_name) return true;
