@@ -478,8 +478,20 @@ int psvr_bgzf_decompress(int device, const void *in, int64_t n_bytes, int64_t *i
  * order[i] = index of the i-th smallest key; equal keys keep ascending index (stable).
  * Host pointers; 0 <= n < 2^32 (else PSVR_ERR_UNSUPPORTED); runs on HIP device `device`.  An LSD radix sort with 8-bit digits in tiles of
  * 2048 keys; passes whose digit is the same for every key are skipped.  Device memory: about 24 bytes per key, allocated per call
- * (PSVR_ERR_NOMEM with the byte count in psvr_last_error() when it does not fit). */
+ * (PSVR_ERR_NOMEM with the byte count in psvr_last_error() when it does not fit).  The arguments are looked at before the device: n == 0
+ * answers PSVR_OK without one (psvr_sort_order_names below asks for the device first, and answers PSVR_ERR_DEVICE even then). */
 int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *order);
+
+/* ---- Name order on the device (`panSVR sort -n`) --------------------------------------------------------------------------------------------
+ * order[i] = index of the i-th name.  Name i is the NUL-terminated string at names + name_off[i] (names[0, n_bytes), host pointers); the order
+ * is strcmp's (unsigned bytes up to the first NUL), equal names by tie[i] ascending (tie == NULL: all equal; `panSVR sort -n` passes
+ * flag & 0xc0, first read before second), then by ascending index (stable).  This project's name order, not samtools' natural one.
+ * The names are cut into big-endian 8-byte chunks, NUL-padded, and ordered by runs of psvr_sort_order_u64's radix sort: the tie key, then the
+ * chunks from the last to the first, each run stable over the order of the run before; a chunk that is the same for every name costs one
+ * histogram.  n >= 2^32 or a name longer than 254 bytes: PSVR_ERR_UNSUPPORTED; an offset outside the blob or a name without a NUL before the
+ * blob's end: PSVR_ERR_ARG; no device: PSVR_ERR_DEVICE (asked first); n == 0 is fine.  Device memory: n_bytes + about 41 bytes per name,
+ * allocated per call (PSVR_ERR_NOMEM with the byte count in psvr_last_error() when it does not fit). */
+int psvr_sort_order_names(int device, int64_t n, const void *names, int64_t n_bytes, const int64_t *name_off, const uint8_t *tie, uint32_t *order);
 
 /* ---- The main BAM file's records kept and ordered in HBM (the coordinate sort of the BAM output without a host trip) -------------------------
  * Joins psvr_bam_emit_*, psvr_sort_order_u64 and psvr_bgzf_stream_*: what `samtools sort` + `samtools index` do between the `aln` and `fc_sv`
@@ -515,6 +527,13 @@ int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, uint32_t *o
  *   order         sorts the keys where they lie (the sort of psvr_sort_order_u64: stable, equal keys keep append order) and computes where
  *                 every record goes in the sorted stream.  Afterwards appends are refused (PSVR_ERR_ARG).  key_exact == 0 or 2^32 and more
  *                 records: PSVR_ERR_UNSUPPORTED, and nothing changes.  An empty store is ordered too.
+ *   order_names   order, by name instead of by coordinate (psvr_sort_order_names' order: the name with strcmp, flag & 0xc0, append order); the
+ *                 names are read where the records lie, through the table's addresses.  A record's name ends at its first NUL, and at
+ *                 l_read_name bytes at the latest: a name field without a NUL (append from the host takes one; append_bgzf and
+ *                 `panSVR sort`'s reader refuse it) is compared as its l_read_name bytes, never beyond.  It needs no key: key_exact == 0 is no obstacle.  Refused
+ *                 like order while a tail is pending, and once the store has been ordered the other way (PSVR_ERR_ARG).  Afterwards
+ *                 info.ordered == 2 (1 after order), and appends, meta, stream and download behave as after order.  A failure before
+ *                 the first key has moved leaves the store unchanged.
  *   meta          for sorted ranks [first_rank, first_rank + n), what the .bai needs: tid, pos, end = max(pos, 0) + span, len = 4 + block_size,
  *                 the recomputed bin, flag, and index = the record's number in append order.  Only after order (else PSVR_ERR_ARG).
  *   stream        appends the records of those ranks, with the recomputed bin in bytes 14-15, behind the pending bytes of a
@@ -539,6 +558,7 @@ int  psvr_bam_store_append_bgzf(psvr_bam_store_t *st, const void *in, int64_t n_
 int  psvr_bam_store_chain_info(psvr_bam_store_t *st, psvr_bam_chain_info_t *info);   /* waits; counters summed over all appends */
 int  psvr_bam_store_info(psvr_bam_store_t *st, psvr_bam_store_info_t *info);       /* waits for what is queued */
 int  psvr_bam_store_order(psvr_bam_store_t *st);
+int  psvr_bam_store_order_names(psvr_bam_store_t *st);
 int  psvr_bam_store_meta(psvr_bam_store_t *st, int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *meta);
 int  psvr_bam_store_stream(psvr_bam_store_t *st, psvr_bgzf_stream_t *s, int64_t first_rank, int64_t n);
 int  psvr_bam_store_download(psvr_bam_store_t *st, void *bytes, int64_t cap, int64_t *n_bytes);

@@ -12,6 +12,9 @@
 // sort_store_sink.h's writer: no inflated byte and no record visits the host.  Whatever fails -- no device, memory, a position the key cannot
 // hold, a corrupt member, a malformed record, a truncated file -- is named on one line, the store is destroyed, and the --deflate-device
 // route below runs on the same file from its beginning: its messages and its exit status are the command's.
+//   panSVR sort --nsort-device [-t threads] [-o out.bam] in.bam         name order by the same route: the store is ordered by psvr_bam_store_order_names,
+// the header says SO:queryname and no index is written; the file is that of -n --deflate-device, which is also what takes over.  Plain -n
+// computes its order on the device as well when one is visible (name_order_device: the names in one blob, psvr_sort_order_names).
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -22,6 +25,7 @@
 #include <functional>
 #include <future>
 #include "bam_reader.h"
+#include "name_key.h"
 #include "sorted_bam.h"
 #include "sort_store_sink.h"
 
@@ -30,11 +34,12 @@ namespace psvr {
 // The device route of `panSVR sort --sort-device` over a backend (cli_main.cpp: psvr_bam_store_* and psvr_bgzf_stream_*): sort_store_sink.h's
 // calls, and int store_append_bgzf(const void *, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad_member),
 // int store_chain_info(psvr_bam_chain_info_t *).  0: out_fn and its .bai are written; -1: the route was left (one line said why), the caller
-// sorts the file its other way; 2: the output cannot be written.
-template <class Backend> int sort_device_route(Backend &be, const std::string &in_fn, const std::string &out_fn)
+// sorts the file its other way; 2: the output cannot be written.  by_name (--nsort-device): name order, no index; the backend has store_order_names().
+template <class Backend> int sort_device_route(Backend &be, const std::string &in_fn, const std::string &out_fn, bool by_name = false)
 {
+	const char *opt = by_name ? "--nsort-device" : "--sort-device";
 	auto left = [&](const char *call, const std::string &why) {
-		fprintf(stderr, "[panSVR-amd] sort --sort-device: %s failed (%s): the file is read again and sorted by the --deflate-device route\n", call, why.c_str());
+		fprintf(stderr, "[panSVR-amd] sort %s: %s failed (%s): the file is read again and sorted by the %s--deflate-device route\n", opt, call, why.c_str(), by_name ? "-n " : "");
 		return -1;
 	};
 	if (in_fn == "-") return left("opening the input", "a pipe cannot be read twice");
@@ -109,18 +114,37 @@ template <class Backend> int sort_device_route(Backend &be, const std::string &i
 	if (be.store_info(&n_rec, &n_bytes)) return left("info", be.last_error());
 	const double t1 = now();
 	SortStoreSink<Backend> sink(be, [](const SortRecords &) { return 2; });
-	sink.adopt(out_fn.c_str(), text, refs);
+	sink.adopt(out_fn.c_str(), text, refs, by_name);
 	if (const int rc = sink.finish_store()) return rc;
 	const double t2 = now();
-	fprintf(stderr, "[panSVR-amd] sort: %lld records -> %s (coordinate order, ordered on the device, records kept on the device)\n", sink.st.records, out_fn.c_str());
-	fprintf(stderr, "[panSVR-amd] sort --sort-device: %lld records, %lld record bytes, %lld members in, %lld members out, %lld segments: %lld without a guess, %lld wrong guesses, %lld walked again; append %.3f s, order %.3f s, write %.3f s\n",
-	        (long long)n_rec, (long long)n_bytes, members_in, sink.st.members, (long long)ci.segments, (long long)ci.no_guess, (long long)ci.wrong_guess, (long long)ci.rewalked,
+	fprintf(stderr, "[panSVR-amd] sort: %lld records -> %s (%s order, ordered on the device, records kept on the device)\n", sink.st.records, out_fn.c_str(), by_name ? "name" : "coordinate");
+	fprintf(stderr, "[panSVR-amd] sort %s: %lld records, %lld record bytes, %lld members in, %lld members out, %lld segments: %lld without a guess, %lld wrong guesses, %lld walked again; append %.3f s, order %.3f s, write %.3f s\n",
+	        opt, (long long)n_rec, (long long)n_bytes, members_in, sink.st.members, (long long)ci.segments, (long long)ci.no_guess, (long long)ci.wrong_guess, (long long)ci.rewalked,
 	        t1 - t0, sink.st.t_order, t2 - t1 - sink.st.t_order);
 	return 0;
 }
 
-// what bam_sort_main's --sort-device calls: (in.bam, out.bam) -> sort_device_route's answer over the caller's backend
-typedef std::function<int(const std::string &, const std::string &)> SortDeviceFn;
+// what bam_sort_main's --sort-device and --nsort-device call: (in.bam, out.bam, by_name) -> sort_device_route's answer over the caller's backend
+typedef std::function<int(const std::string &, const std::string &, bool)> SortDeviceFn;
+
+// `panSVR sort -n` on the device: the names of R in one blob (each up to its first NUL inside the name field), flag & 0xc0 as the tie key,
+// ordered by psvr_sort_order_names: name_order's order.  false with the reason: the caller orders with name_order
+inline bool name_order_device(const SortRecords &R, int device, std::vector<uint32_t> &ord, std::string *err)
+{
+	const size_t n = R.size();
+	std::vector<uint8_t> blob, tie(n);
+	std::vector<int64_t> off(n);
+	blob.reserve(n * 32);
+	for (size_t i = 0; i < n; ++i) {
+		const uint8_t *r = R.rec(i);
+		off[i] = (int64_t)blob.size(), tie[i] = (uint8_t)name_tie_key(r[18]);
+		blob.insert(blob.end(), r + 36, r + 36 + name_len_rec(r));
+		blob.push_back(0);
+	}
+	ord.resize(n);
+	if (psvr_sort_order_names(device, (int64_t)n, blob.data(), (int64_t)blob.size(), off.data(), tie.data(), ord.data())) { *err = psvr_last_error(); return false; }
+	return true;
+}
 
 // what --sort-device's usage text says about its speed
 #define PSVR_SORT_CMD_DEVICE_MEASURED \
@@ -128,15 +152,23 @@ typedef std::function<int(const std::string &, const std::string &)> SortDeviceF
 	"                                1 M pairs, -t 16 (three interleaved runs, median wall): 0.522 s against 2.359 s for --deflate-device, 1.303 s with\n" \
 	"                                --inflate-device and 1.162 s with --inflate-threads 16 on top (DESIGN.md section 8 f3)"
 
+// what --nsort-device's usage text says about its speed
+#define PSVR_NSORT_CMD_DEVICE_MEASURED \
+	"Measured on the 1.6 M records of 1 M pairs,\n" \
+	"                                -t 16 (three interleaved runs, median wall): 0.520 s against 2.361 s for -n --deflate-device with the order on one\n" \
+	"                                host thread and 1.188 s with --inflate-threads 16 on top (ahead: the ranges do not overlap); plain -n --deflate-device\n" \
+	"                                with its order from the GPU 2.079 s (DESIGN.md section 8 f3)"
+
 // deflate_fn: the compressor --deflate-device uses (the CLI hands in &psvr_bgzf_compress_members)
 inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullptr, SortDeviceFn sort_device_fn = nullptr)
 {
 	bool by_name = false;
 	int threads = 4, inflate_device = -1, inflate_threads = 0;
-	bool bad_arg = false, deflate_device = false, sort_device = false;
+	bool bad_arg = false, deflate_device = false, sort_device = false, nsort_device = false;
 	std::string out_fn, in_fn;
 	for (int i = 2; i < argc; ++i) {
 		if (!strcmp(argv[i], "-n")) by_name = true;
+		else if (!strcmp(argv[i], "--nsort-device")) nsort_device = deflate_device = true;
 		else if ((!strcmp(argv[i], "-t") || !strcmp(argv[i], "-@")) && i + 1 < argc) threads = atoi(argv[++i]);
 		else if (!strcmp(argv[i], "-o") && i + 1 < argc) out_fn = argv[++i];
 		else if (!strcmp(argv[i], "--inflate-device")) inflate_device = 0;
@@ -147,7 +179,9 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 	}
 	if (bad_arg) fprintf(stderr, "--inflate-threads wants a positive number\n");
 	if (in_fn.empty() || bad_arg) {
-		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device | --sort-device] in.bam\n"
+		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device | --sort-device | --nsort-device] in.bam\n"
+		                "         -n                     name order (the names as strcmp compares them, first read before second, ties in input order), no index;\n"
+		                "                                the order is computed on the GPU (device 0) when one is visible, on one host thread otherwise\n"
 		                "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
 		                "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
 		                "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n"
@@ -158,15 +192,21 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		                "         --sort-device          coordinate order only; implies --deflate-device.  The file's BGZF members are inflated on the GPU (device 0)\n"
 		                "                                into a record store in its memory, the records are found, ordered, gathered and compressed there: the files\n"
 		                "                                are those of --deflate-device, byte for byte.  Whatever the device route cannot do (no device, memory, a\n"
-		                "                                malformed or truncated file) is named, and the --deflate-device route sorts the file.  " PSVR_SORT_CMD_DEVICE_MEASURED "\n");
+		                "                                malformed or truncated file) is named, and the --deflate-device route sorts the file.  " PSVR_SORT_CMD_DEVICE_MEASURED "\n"
+		                "         --nsort-device         name order by the same route; implies -n and --deflate-device.  The store is ordered by name on the GPU (the\n"
+		                "                                names cut into 8-byte chunks, a stable radix sort per chunk); the file is that of -n --deflate-device, byte\n"
+		                "                                for byte, and no index is written.  Whatever the device route cannot do is named, and the -n --deflate-device\n"
+		                "                                route sorts the file.  Not with --sort-device.  " PSVR_NSORT_CMD_DEVICE_MEASURED "\n");
 		return 1;
 	}
-	if (sort_device && by_name) { fprintf(stderr, "--sort-device cannot be combined with -n: name order is not built on the device\n"); return 1; }
+	if (sort_device && nsort_device) { fprintf(stderr, "--nsort-device cannot be combined with --sort-device: a file has one order, name (--nsort-device) or coordinate (--sort-device)\n"); return 1; }
+	if (sort_device && by_name) { fprintf(stderr, "--sort-device cannot be combined with -n: name order is not built on the device by this option; --nsort-device is the name order's device route\n"); return 1; }
+	if (nsort_device) by_name = true;
 	if (out_fn.empty()) out_fn = in_fn + (by_name ? ".nsorted.bam" : ".sorted.bam");
 	if (threads < 1) threads = 1;
-	if (sort_device) {
-		const int rc = sort_device_fn ? sort_device_fn(in_fn, out_fn) : -1;
-		if (!sort_device_fn) fprintf(stderr, "[panSVR-amd] sort --sort-device: this build has no device route: the file is sorted by the --deflate-device route\n");
+	if (sort_device || nsort_device) {
+		const int rc = sort_device_fn ? sort_device_fn(in_fn, out_fn, nsort_device) : -1;
+		if (!sort_device_fn) fprintf(stderr, "[panSVR-amd] sort %s: this build has no device route: the file is sorted by the %s--deflate-device route\n", nsort_device ? "--nsort-device" : "--sort-device", nsort_device ? "-n " : "");
 		if (rc >= 0) return rc;
 	}
 	BamReader rd;
@@ -188,7 +228,14 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 	std::vector<uint32_t> ord;
 	bool on_device = false;
 	std::string err;
-	if (by_name) name_order(R, ord);
+	if (by_name) {
+		// on the device when one is visible, as coordinate_order; a call that fails says so and the host orders (name_order is the rule either way)
+		if (R.size() > 0 && R.size() < ((size_t)1 << 32) && psvr_device_count() > 0) {
+			on_device = name_order_device(R, 0, ord, &err);
+			if (!on_device) fprintf(stderr, "[panSVR-amd] sort: device name order failed (%s): the names are ordered on the host\n", err.c_str());
+		}
+		if (!on_device) name_order(R, ord);
+	}
 	else if (!coordinate_order(R, 0, ord, &on_device, &err)) { fprintf(stderr, "[panSVR-amd] sort: device order: %s\n", err.c_str()); return 2; }
 	if (!write_sorted_bam(out_fn, rd.header_text, rd.refs, R, ord, by_name, threads, &err, deflate_device ? deflate_fn : nullptr, 0)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
 	fprintf(stderr, "[panSVR-amd] sort: %zu records -> %s (%s order%s)\n", ord.size(), out_fn.c_str(), by_name ? "name" : "coordinate", on_device ? ", ordered on the device" : "");

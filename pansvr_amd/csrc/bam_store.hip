@@ -12,6 +12,8 @@
 //                 the next call that waits (info, a host append, order, download)
 //   order         the keys sorted where they lie (sort_device.h), then per rank the source address, the meta and the exclusive scan of the
 //                 lengths: where every record goes in the sorted stream, on the device for the gather and on the host for the window sizes
+//   order_names   the same with name order (name_sort.hip: the names are read where the records lie, through the table's addresses; the keys'
+//                 array is the runs' key buffer), for `panSVR sort --nsort-device`
 //   the gather    k_store_gather: a group of 16 lanes per record, four records per wavefront; 16-byte stores aligned on the destination,
 //                 16-byte loads from the unaligned source, at most 15 head and 15 tail bytes as byte stores, the bin patched in registers
 // Bounds: a range that leaves the emitter's bytes or the chunk's room, a chain that leaves its pair, a block_size below 32 (or of 2 GiB and
@@ -53,7 +55,8 @@ struct psvr_bam_store {
 	long long *h_ctl = nullptr;                              // page-locked read-back of ctl
 	long long n_rec = 0, fill = 0, n_bytes = 0;              // the host's copies, exact when `exact`
 	long long rec_upper = 0, fill_upper = 0;                 // never below what the device holds
-	bool exact = true, key_exact = true, bad = false, ordered = false, keys_spent = false;
+	bool exact = true, key_exact = true, bad = false, keys_spent = false;
+	int ordered = 0;                                         // 1: by samtools' coordinate key, 2: by name
 	psvr::DevBuf cnt, off, tmp, poff;                        // an append's scratch: records per pair, their scan, the scan's scratch, a host append's offsets
 	psvr::SortScratch S;                                     // order
 	std::vector<uint32_t> h_hist;
@@ -283,7 +286,8 @@ static int st_chunk(psvr_bam_store *st, DfwCtx &c, long long used, long long nee
 {
 	if (!st->chunks.empty() && (long long)st->chunks.back()->bytes - used >= need) return PSVR_OK;
 	std::unique_ptr<DevBuf> b(new DevBuf);
-	const size_t n = (size_t)need > st->chunk_bytes ? (size_t)need : st->chunk_bytes;
+	// (whole 8-byte words: k_name_chunk loads the aligned words that a name touches, also of a record that ends with its name at the chunk's end)
+	const size_t n = (((size_t)need > st->chunk_bytes ? (size_t)need : st->chunk_bytes) + 7) / 8 * 8;
 	if (b->alloc(n) != hipSuccess) {
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "psvr_bam_store: device allocation failed for a chunk of %zu bytes (%lld bytes of records are stored)", n, st->n_bytes);
@@ -565,36 +569,36 @@ extern "C" int psvr_bam_store_info(psvr_bam_store_t *st, psvr_bam_store_info_t *
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, st->device)) return rc;
 	if (int rc = st_refresh(st, c, true)) return rc;
-	if (info) info->n_records = st->n_rec, info->n_bytes = st->n_bytes, info->key_exact = st->key_exact ? 1 : 0, info->ordered = st->ordered ? 1 : 0;
+	if (info) info->n_records = st->n_rec, info->n_bytes = st->n_bytes, info->key_exact = st->key_exact ? 1 : 0, info->ordered = st->ordered;
 	return PSVR_OK;
 }
 
-extern "C" int psvr_bam_store_order(psvr_bam_store_t *st)
+// what both orders share: the store can be ordered now, and its sorted table has room.  *done: nothing more to do (ordered this way already, or empty)
+static int st_order_begin(psvr_bam_store *st, DfwCtx &c, int kind, const char *who, bool *done)
 {
-	if (!st) return set_error(PSVR_ERR_ARG, "psvr_bam_store_order: null argument");
-	DfwCtx &c = dfw_ctx();
-	std::lock_guard<std::mutex> lk(c.mu);
+	*done = false;
 	if (int rc = dfw_bind(c, st->device)) return rc;
 	if (int rc = st_refresh(st, c, true)) return rc;
-	if (st->ordered) return PSVR_OK;
-	if (st->tail) return set_error(PSVR_ERR_ARG, "psvr_bam_store_order: truncated BAM stream: the last append_bgzf ended %lld bytes into a record", st->tail);
-	if (!st->key_exact) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_order: a position outside [-1, 2^31 - 2]: the 64-bit key does not order as samtools' comparator");
-	if (st->n_rec >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_bam_store_order: %lld records, the order is 32-bit (at most 2^32 - 1 records)", st->n_rec);
-	if (st->keys_spent) return set_error(PSVR_ERR_DEVICE, "psvr_bam_store_order: an earlier order failed after it had begun to move the keys");
+	if (st->ordered == kind) { *done = true; return PSVR_OK; }
+	if (st->ordered) return set_error(PSVR_ERR_ARG, "%s: the store has been ordered %s already", who, st->ordered == 2 ? "by name" : "by coordinate");
+	if (st->tail) return set_error(PSVR_ERR_ARG, "%s: truncated BAM stream: the last append_bgzf ended %lld bytes into a record", who, st->tail);
+	if (kind == 1 && !st->key_exact) return set_error(PSVR_ERR_UNSUPPORTED, "%s: a position outside [-1, 2^31 - 2]: the 64-bit key does not order as samtools' comparator", who);
+	if (st->n_rec >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "%s: %lld records, the order is 32-bit (at most 2^32 - 1 records)", who, st->n_rec);
+	if (st->keys_spent) return set_error(PSVR_ERR_DEVICE, "%s: an earlier order failed after it had begun to move the keys", who);
 	const long long n = st->n_rec;
 	st->h_rank_off.assign((size_t)n + 1, 0);
-	if (n == 0) { st->ordered = true; return PSVR_OK; }
+	if (n == 0) { st->ordered = kind, *done = true; return PSVR_OK; }
 	if (st->g_src.alloc((size_t)n * 8) || st->smeta.alloc((size_t)n * sizeof(psvr_bam_rec_meta_t)) || st->slen.alloc((size_t)(n + 1) * 4) || st->rank_off.alloc((size_t)(n + 1) * 8) ||
 	    st->tmp.ensure(scan_tmp_bytes(1, n + 1))) {
 		(void)hipGetLastError();
-		return set_error(PSVR_ERR_NOMEM, "psvr_bam_store_order: device allocation failed for the sorted table of %lld records (%zu bytes)", n, (size_t)n * 52);
+		return set_error(PSVR_ERR_NOMEM, "%s: device allocation failed for the sorted table of %lld records (%zu bytes)", who, n, (size_t)n * 52);
 	}
-	const uint32_t *d_order = nullptr;
-	if (int rc = sort_order_device(c.stream, n, st->key.as<uint64_t>(), st->S, st->h_hist, &d_order, "psvr_bam_store_order")) {
-		st->keys_spent = rc != PSVR_ERR_NOMEM;                     // (nothing has been launched when the scratch does not fit)
-		return rc;
-	}
-	st->keys_spent = true;
+	return PSVR_OK;
+}
+// ... and the order applied: per rank the address, the meta and where the record goes in the sorted stream
+static int st_order_apply(psvr_bam_store *st, DfwCtx &c, const uint32_t *d_order, int kind, const char *who)
+{
+	const long long n = st->n_rec;
 	StreamDrain drain{c.stream};
 	hipLaunchKernelGGL(k_store_rank, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, c.stream, d_order, (const uint64_t *)st->addr.p, (const psvr_bam_rec_meta_t *)st->meta.p, n,
 	                   st->g_src.as<uint64_t>(), st->smeta.as<psvr_bam_rec_meta_t>(), st->slen.as<int32_t>());
@@ -605,11 +609,51 @@ extern "C" int psvr_bam_store_order(psvr_bam_store_t *st)
 	PSVR_HIP(hipMemcpyAsync(st->h_rank_off.data(), st->rank_off.p, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, c.stream));
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(c.stream));
-	if (st->h_rank_off[(size_t)n] != st->n_bytes) return set_error(PSVR_ERR_DEVICE, "psvr_bam_store_order: the sorted lengths add up to %lld bytes, the store holds %lld", st->h_rank_off[(size_t)n], st->n_bytes);
+	if (st->h_rank_off[(size_t)n] != st->n_bytes) return set_error(PSVR_ERR_DEVICE, "%s: the sorted lengths add up to %lld bytes, the store holds %lld", who, st->h_rank_off[(size_t)n], st->n_bytes);
 	st->S.release();                                              // (the order has been applied: its scratch and the keys go back)
 	st->key.release(), st->slen.release();
-	st->ordered = true;
+	st->ordered = kind;
 	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_store_order(psvr_bam_store_t *st)
+{
+	const char *who = "psvr_bam_store_order";
+	if (!st) return set_error(PSVR_ERR_ARG, "%s: null argument", who);
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	bool done = false;
+	if (int rc = st_order_begin(st, c, 1, who, &done)) return rc;
+	if (done) return PSVR_OK;
+	const uint32_t *d_order = nullptr;
+	if (int rc = sort_order_device(c.stream, st->n_rec, st->key.as<uint64_t>(), st->S, st->h_hist, &d_order, who)) {
+		st->keys_spent = rc != PSVR_ERR_NOMEM;                     // (nothing has been launched when the scratch does not fit)
+		return rc;
+	}
+	st->keys_spent = true;
+	return st_order_apply(st, c, d_order, 1, who);
+}
+
+// name order: the names are read where the records lie (the table's addresses), the keys' array is the runs' key buffer
+extern "C" int psvr_bam_store_order_names(psvr_bam_store_t *st)
+{
+	const char *who = "psvr_bam_store_order_names";
+	if (psvr_device_count() <= 0) return st_no_device();
+	if (!st) return set_error(PSVR_ERR_ARG, "%s: null argument", who);
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	bool done = false;
+	if (int rc = st_order_begin(st, c, 2, who, &done)) return rc;
+	if (done) return PSVR_OK;
+	const NameSrc src = {(const uint64_t *)st->addr.p, nullptr, 0, nullptr, nullptr};
+	NameScratch N;
+	const uint32_t *d_order = nullptr;
+	// the first k_name_chunk overwrites the coordinate keys; every allocation of the call comes before it (sort_device.h), so a call that
+	// failed for want of memory has not written them, and N says whether a write was queued
+	const int rc_sort = sort_order_names_device(c.stream, st->n_rec, src, st->key.as<uint64_t>(), N, st->S, st->h_hist, &d_order, who);
+	st->keys_spent = N.keys_written;
+	if (rc_sort) return rc_sort;
+	return st_order_apply(st, c, d_order, 2, who);                 // (it waits: N's entries are free to go)
 }
 
 extern "C" int psvr_bam_store_meta(psvr_bam_store_t *st, int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *meta)

@@ -379,6 +379,7 @@ struct StoreCalls {
 		return 0;
 	}
 	int store_order() { return psvr_bam_store_order(store); }
+	int store_order_names() { return psvr_bam_store_order_names(store); }
 	int store_meta(int64_t first, int64_t n, psvr_bam_rec_meta_t *m) { return psvr_bam_store_meta(store, first, n, m); }
 	int store_stream(int64_t first, int64_t n) { return psvr_bam_store_stream(store, s, first, n); }
 	int store_download(void *bytes, int64_t cap, int64_t *n) { return psvr_bam_store_download(store, bytes, cap, n); }
@@ -669,12 +670,12 @@ int main(int argc, char **argv)
 	if (argc >= 2 && !strcmp(argv[1], "index")) return index_main(argc, argv);
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
 	if (argc >= 2 && !strcmp(argv[1], "sort"))
-		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out) {
+		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name) {
 			SortCmdBackend be(0);
-			return psvr::sort_device_route(be, in, out);
+			return psvr::sort_device_route(be, in, out, by_name);
 		});
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
-	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         panSVR sort --sort-device [-t threads] [-o out.bam] in.bam      (the same files, the records inflated, kept, ordered and compressed in GPU memory)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
+	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         panSVR sort --sort-device [-t threads] [-o out.bam] in.bam      (the same files, the records inflated, kept, ordered and compressed in GPU memory)\n         panSVR sort --nsort-device [-t threads] [-o out.bam] in.bam     (name order by the same route: the file of sort -n --deflate-device, no index)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
 	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
 	                "         aln <reads.fq>: --sort-device   (implies --sort, --emit-device and --deflate-device; the records are kept, ordered and compressed in GPU memory)\n"
 	                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");

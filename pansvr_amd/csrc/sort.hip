@@ -122,19 +122,32 @@ using namespace psvr;
 
 
 // the body of the sort over device pointers (sort_device.h): psvr_sort_order_u64 below and psvr_bam_store_order (bam_store.hip) both run it
-int psvr::sort_order_device(hipStream_t st, long long n, uint64_t *d_keys, SortScratch &S, std::vector<uint32_t> &h, const uint32_t **d_order, const char *who)
+// the scratch of a sort of n keys (sort_device.h): nothing is launched, nothing but S is touched
+int psvr::sort_scratch_reserve(long long n, SortScratch &S, const char *who)
 {
-	*d_order = nullptr;
 	if (n <= 0) return PSVR_OK;
 	const long long ntile = (n + kSortTile - 1) / kSortTile, ncnt = 256 * ntile;
 	const int nhb = (int)(ntile < kHistBlocks ? ntile : kHistBlocks);
 	// a second key array and two index arrays (ping-pong with the caller's keys), the (digit, tile) counts and offsets, the scan's and the histogram's scratch
 	const size_t need = (size_t)n * 16 + (size_t)ncnt * 12 + scan_tmp_bytes(1, ncnt) + (size_t)(nhb + 1) * 8192;
-	if (S.k1.alloc((size_t)n * 8) || S.i0.alloc((size_t)n * 4) || S.i1.alloc((size_t)n * 4) || S.cnt.alloc((size_t)ncnt * 4) ||
-	    S.off.alloc((size_t)ncnt * 8) || S.tmp.alloc(scan_tmp_bytes(1, ncnt)) || S.slab.alloc((size_t)nhb * 8192) || S.hist.alloc(8192)) {
+	// (a buffer that is large enough stays: a run that continues an order finds it in S.i0 or S.i1, where the run before left it)
+	auto room = [](DevBuf &b, size_t bytes) { return b.p && b.bytes >= bytes ? hipSuccess : b.alloc(bytes); };
+	if (room(S.k1, (size_t)n * 8) || room(S.i0, (size_t)n * 4) || room(S.i1, (size_t)n * 4) || room(S.cnt, (size_t)ncnt * 4) ||
+	    room(S.off, (size_t)ncnt * 8) || room(S.tmp, scan_tmp_bytes(1, ncnt)) || room(S.slab, (size_t)nhb * 8192) || room(S.hist, 8192)) {
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "%s: %zu bytes of device memory needed for %lld keys", who, need + (size_t)n * 8, n);
 	}
+	return PSVR_OK;
+}
+
+int psvr::sort_order_device(hipStream_t st, long long n, uint64_t *d_keys, SortScratch &S, std::vector<uint32_t> &h, const uint32_t **d_order, const char *who,
+                            const uint32_t *d_order_in)
+{
+	*d_order = d_order_in;
+	if (n <= 0) return PSVR_OK;
+	if (int rc = sort_scratch_reserve(n, S, who)) return rc;       // (no allocation when a run before, or the caller, has made the room)
+	const long long ntile = (n + kSortTile - 1) / kSortTile, ncnt = 256 * ntile;
+	const int nhb = (int)(ntile < kHistBlocks ? ntile : kHistBlocks);
 	h.assign(2048, 0);
 	StreamDrain drain{st};                                         // (after the buffers: nothing is in flight when they are freed)
 	hipLaunchKernelGGL(k_sort_hist, dim3((unsigned)nhb), dim3(256), 0, st, (const uint64_t *)d_keys, n, S.slab.as<uint32_t>());
@@ -143,7 +156,9 @@ int psvr::sort_order_device(hipStream_t st, long long n, uint64_t *d_keys, SortS
 	PSVR_HIP(hipMemcpyAsync(h.data(), S.hist.p, 8192, hipMemcpyDeviceToHost, st));
 	PSVR_HIP(hipStreamSynchronize(st));
 	uint64_t *kin = d_keys, *kout = S.k1.as<uint64_t>();
-	uint32_t *iin = nullptr, *iout = S.i0.as<uint32_t>();
+	// the incoming order is read by the first pass that runs: that pass writes the other index array
+	const uint32_t *iin = d_order_in;
+	uint32_t *iout = d_order_in == S.i0.as<uint32_t>() ? S.i1.as<uint32_t>() : S.i0.as<uint32_t>();
 	for (int d = 0; d < 8; ++d) {
 		bool constant = false;
 		for (int v = 0; v < 256; ++v) if (h[(size_t)d * 256 + v] == (uint32_t)n) constant = true;
@@ -152,7 +167,7 @@ int psvr::sort_order_device(hipStream_t st, long long n, uint64_t *d_keys, SortS
 		ScanSet X = {};
 		X.cnt[0] = S.cnt.as<int32_t>(), X.out[0] = S.off.as<long long>(), X.stride[0] = 1;
 		scan_launch(X, 1, ncnt, S.tmp.as<long long>(), st);
-		hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, (const uint32_t *)iin, n, 8 * d, ntile,
+		hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntile), dim3(kSortThreads), 0, st, (const uint64_t *)kin, iin, n, 8 * d, ntile,
 		                   (const long long *)S.off.p, kout, iout);
 		PSVR_HIP(hipGetLastError());
 		std::swap(kin, kout);
@@ -194,5 +209,41 @@ extern "C" int psvr_sort_order_u64(int device, int64_t n, const uint64_t *keys, 
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(st));
 	if (!iin) for (int64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;   // every digit constant: all keys equal, the input order stands
+	return PSVR_OK;
+}
+
+extern "C" int psvr_sort_order_names(int device, int64_t n, const void *names, int64_t n_bytes, const int64_t *name_off, const uint8_t *tie, uint32_t *order)
+{
+	if (psvr_device_count() <= 0) return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path");
+	if (n < 0 || n_bytes < 0 || (n > 0 && (!names || !name_off || !order))) return set_error(PSVR_ERR_ARG, "psvr_sort_order_names: bad argument");
+	if (n >= ((int64_t)1 << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_sort_order_names: %lld names, the order is 32-bit (at most 2^32 - 1 names)", (long long)n);
+	if (n == 0) return PSVR_OK;
+	for (int64_t i = 0; i < n; ++i)                                // (the kernel asks again; here nothing has been uploaded yet)
+		if (name_off[i] < 0 || name_off[i] >= n_bytes) return set_error(PSVR_ERR_ARG, "psvr_sort_order_names: name %lld begins at byte %lld of %lld", (long long)i, (long long)name_off[i], (long long)n_bytes);
+	SortCtx &c = sort_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = c.bind(device, false, [] {})) return rc;                                  // (the buffers are the call's own)
+	hipStream_t st = c.stream;
+	// the names (in whole 8-byte words: k_name_chunk loads the aligned words a name touches), their offsets and tie keys, the keys, the entries
+	const size_t blob_bytes = ((size_t)n_bytes + 7) / 8 * 8;
+	DevBuf blob, off, tk, k0;
+	NameScratch N;
+	SortScratch S;
+	if (blob.alloc(blob_bytes) || off.alloc((size_t)n * 8) || (tie && tk.alloc((size_t)n)) || k0.alloc((size_t)n * 8)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_sort_order_names: %zu bytes of device memory needed for %lld names in %lld bytes", blob_bytes + (size_t)n * 41, (long long)n, (long long)n_bytes);
+	}
+	StreamDrain drain{st};                                         // (after the buffers: nothing is in flight when they are freed)
+	PSVR_HIP(hipMemsetAsync((uint8_t *)blob.p + (blob_bytes - 8), 0, 8, st));
+	PSVR_HIP(hipMemcpyAsync(blob.p, names, (size_t)n_bytes, hipMemcpyHostToDevice, st));
+	PSVR_HIP(hipMemcpyAsync(off.p, name_off, (size_t)n * 8, hipMemcpyHostToDevice, st));
+	if (tie) PSVR_HIP(hipMemcpyAsync(tk.p, tie, (size_t)n, hipMemcpyHostToDevice, st));
+	const NameSrc src = {nullptr, blob.as<uint8_t>(), (long long)n_bytes, off.as<long long>(), tie ? tk.as<uint8_t>() : nullptr};
+	const uint32_t *ord = nullptr;
+	if (int rc = sort_order_names_device(st, (long long)n, src, k0.as<uint64_t>(), N, S, c.h_hist, &ord, "psvr_sort_order_names")) return rc;
+	if (ord) PSVR_HIP(hipMemcpyAsync(order, ord, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+	drain.armed = false;
+	PSVR_HIP(hipStreamSynchronize(st));
+	if (!ord) for (int64_t i = 0; i < n; ++i) order[i] = (uint32_t)i;   // every key equal: the input order stands
 	return PSVR_OK;
 }

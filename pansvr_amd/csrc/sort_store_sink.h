@@ -27,6 +27,7 @@
 //   int store_append(const void *, int64_t) / int store_append_emit(int slot, int64_t first_pair, int64_t n_pairs)
 //   int store_info(int64_t *n_records, int64_t *n_bytes)       waits for the queued appends
 //   int store_order() / int store_meta(int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *)
+//   int store_order_names()                                    optional: what adopt(..., by_name) orders by (tests/tools/nsort_sink_check.cpp has one)
 //   int store_stream(int64_t first_rank, int64_t n)            those ranks' records behind the stream's pending bytes
 //   int store_download(void *bytes, int64_t cap, int64_t *n)
 //   int stream_create() / void stream_destroy() / int stream_append(const void *, int64_t)
@@ -41,6 +42,8 @@
 #include <atomic>
 #include <functional>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "sorted_bam.h"
 
@@ -53,6 +56,10 @@ struct SortSinkStats {
 	double t_order = 0;                                  // the order's own time
 	bool left = false;                                   // the device route was given up
 };
+
+// a backend that offers int store_order_names(): the store ordered by name (psvr_bam_store_order_names); only such a backend instantiates the call
+template <class B, class = void> struct HasStoreOrderNames : std::false_type {};
+template <class B> struct HasStoreOrderNames<B, std::void_t<decltype(std::declval<B &>().store_order_names())>> : std::true_type {};
 
 template <class Backend> class SortStoreSink {
 public:
@@ -73,10 +80,12 @@ public:
 	}
 	// A store that the caller has created through the backend and fills itself (`panSVR sort --sort-device`, bam_sort.h, from the file's own
 	// members): finish_store() writes the sorted file and its index from it.  The caller has its input still, so a failed call downloads nothing.
-	void adopt(const char *fn, const std::string &header_text, const std::vector<BamRef> &refs)
+	// by_name (`panSVR sort --nsort-device`): the header says SO:queryname, the store is ordered by store_order_names(), and there is no .bai;
+	// the windows, the takes and the EOF block are the same
+	void adopt(const char *fn, const std::string &header_text, const std::vector<BamRef> &refs, bool by_name = false)
 	{
-		fn_ = fn, text_ = sorted_header_text(header_text, false), refs_ = refs;
-		on_ = foreign_ = true;
+		fn_ = fn, text_ = sorted_header_text(header_text, by_name), refs_ = refs;
+		on_ = foreign_ = true, by_name_ = by_name;
 	}
 	// 0: written; -1: a backend call failed and has been named, the caller starts over from its input; 2: the file cannot be written.  The store is destroyed
 	int finish_store()
@@ -149,6 +158,7 @@ private:
 	std::vector<BamRef> refs_;
 	std::atomic<bool> on_{false};                        // (the formatter's thread asks, the writer's thread answers)
 	bool fatal_ = false, foreign_ = false;               // foreign_: the store was adopted, its records are not this sink's to rescue
+	bool by_name_ = false;                               // (adopt) name order, no index
 	SortRecords host_;                                   // the records, once the device route is left
 	uint8_t *pin_ = nullptr;
 	size_t pin_cap_ = 0;
@@ -212,7 +222,7 @@ private:
 	bool write_device()
 	{
 		const double t0 = now();
-		if (be_.store_order()) { leave("order"); return false; }
+		if (order_store()) { leave("order"); return false; }
 		st.t_order = now() - t0;
 		int64_t n = 0, nb = 0;
 		if (be_.store_info(&n, &nb)) { leave("info"); return false; }
@@ -251,14 +261,22 @@ private:
 		if (fwrite(kBgzfEof, 1, sizeof kBgzfEof, f) != sizeof kBgzfEof) wrote = false;
 		if (fclose(f) != 0) wrote = false;
 		if (!wrote) { fprintf(stderr, "fail to write file '%s'\n", fn_.c_str()); fatal_ = true; return false; }
-		std::string err;
-		const std::vector<uint8_t> bai = build_bai(refs_.size(), (size_t)n, head.size(), starts, [&](size_t i) {
-			const psvr_bam_rec_meta_t &m = meta[i];
-			return BaiRecord{m.tid, m.pos, m.end, m.bin, m.flag, m.len};
-		});
-		if (!write_bai(fn_, bai, &err)) { fprintf(stderr, "%s\n", err.c_str()); fatal_ = true; return false; }
+		if (!by_name_) {                                     // (a name-sorted file has no index)
+			std::string err;
+			const std::vector<uint8_t> bai = build_bai(refs_.size(), (size_t)n, head.size(), starts, [&](size_t i) {
+				const psvr_bam_rec_meta_t &m = meta[i];
+				return BaiRecord{m.tid, m.pos, m.end, m.bin, m.flag, m.len};
+			});
+			if (!write_bai(fn_, bai, &err)) { fprintf(stderr, "%s\n", err.c_str()); fatal_ = true; return false; }
+		}
 		st.records = n, st.host_bytes += (long long)head.size();   // (the BAM header is the stream's first host append)
 		return true;
+	}
+	int order_store()
+	{
+		if constexpr (HasStoreOrderNames<Backend>::value) { if (by_name_) return be_.store_order_names(); }
+		else if (by_name_) return -1;                        // (last_error() is the backend's: it has said nothing of a call it does not have)
+		return be_.store_order();
 	}
 	static double now()
 	{

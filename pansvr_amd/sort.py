@@ -16,6 +16,26 @@ def sort_order(keys, device=0):
     return out
 
 
+def sort_order_names(names, tie=None, device=0):
+    """names: a list of bytes (none holds a NUL); tie: None or one uint8 per name.  Returns the uint32 order of
+    sorted(range(n), key=lambda i: (names[i], tie[i], i)), computed on HIP device `device` (psvr_sort_order_names)."""
+    names = [bytes(x) for x in names]
+    if any(b"\0" in x for x in names):
+        raise ValueError("sort_order_names wants names without a NUL")
+    n = len(names)
+    blob = np.frombuffer(b"".join(x + b"\0" for x in names) or b"\0", dtype=np.uint8)
+    off = np.zeros(max(n, 1), dtype=np.int64)
+    if n > 1:
+        off[1:n] = np.cumsum([len(x) + 1 for x in names[:-1]])
+    t = None if tie is None else np.ascontiguousarray(tie, dtype=np.uint8)
+    if t is not None and t.shape != (n,):
+        raise ValueError("sort_order_names wants one tie key per name")
+    out = np.empty(n, dtype=np.uint32)
+    check(lib().psvr_sort_order_names(C.c_int(device), C.c_int64(n), blob.ctypes.data_as(C.c_void_p), C.c_int64(len(blob) if n else 0), off.ctypes.data_as(C.c_void_p),
+                                      None if t is None or n == 0 else t.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
 class StoreInfo(C.Structure):  # psvr_bam_store_info_t
     _fields_ = [("n_records", C.c_int64), ("n_bytes", C.c_int64), ("key_exact", C.c_int32), ("ordered", C.c_int32)]
 
@@ -78,6 +98,10 @@ class BamStore:
 
     def order(self):
         check(lib().psvr_bam_store_order(self.h))
+
+    def order_names(self):
+        """name order instead: the names with strcmp, flag & 0xc0, append order; info().ordered is 2 afterwards"""
+        check(lib().psvr_bam_store_order_names(self.h))
 
     def meta(self, first_rank=0, n=None):
         """structured array (META_DTYPE) of sorted ranks [first_rank, first_rank + n); n = None: to the end"""
