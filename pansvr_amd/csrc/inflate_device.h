@@ -18,6 +18,12 @@
 //   * malformed input is a status.  No load leaves [member, member + bsize), no store leaves out[0, isize); every loop consumes input
 //     bits or is bounded by a table size.  The verdict is zlib's: accepted exactly when raw inflate of the payload reaches the end of the
 //     stream having produced ISIZE bytes whose CRC32 is the trailer's (bytes between the end of the stream and the trailer are tolerated).
+//     Which status a refused member gets is the first rule it breaks in stream order, and the trailer is looked at last.  Where one token
+//     breaks two rules the order is: the input before the output (a stored block longer than what is left is kInfTruncated even when
+//     ISIZE is too small for it as well); a code that cannot be told apart from one the payload's end cut off -- no code matches, fewer
+//     than 15 bits are left and none follow -- is kInfTruncated, not kInfLitCode / kInfDistCode / kInfCodeLengths; a match is held to
+//     the bytes in front of it before it is held to the room behind it (kInfFarBack before kInfTooLong).  tests/inflate_cases.py
+//     holds every rule to its status.
 #pragma once
 #include <stdint.h>
 #include <string.h>

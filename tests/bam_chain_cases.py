@@ -88,6 +88,88 @@ def decoy_stream(tail):
     return out
 
 
+# ---- block_size at the edges of chain_record's rules, at the edges of a segment ----------------------------------------------------------------------
+EDGE_SEG = 16384
+MIN_BLOCK, HEAD, STORE_MAX_BLOCK = 32, 36, 0x7ffffff0                          # bam_record.h: kBamRecMinBlock, kBamRecHead, kBamRecStoreMaxBlock
+PLACES = (("at the segment's first byte", 0), ("in its last four bytes", -4), ("across the edge", -2))
+
+
+def fill(n, seed, most=99):
+    """whole records of n bytes altogether (n = 0, or n >= 37), none longer than `most`"""
+    out, k = [], 0
+    assert n == 0 or n >= 37, n
+    while n > most + 37:
+        s = most - (seed + 7 * k) % 62
+        out.append(record(s, seed * 1009 + k))
+        n -= s
+        k += 1
+    if n > most:
+        out.append(record(n - 50, seed * 1009 + k))
+        n = 50
+    if n:
+        out.append(record(n, seed * 1009 + k + 1))
+    return out
+
+
+def head(block_size, l_name=1, name=b"\0"):
+    """the first 36 bytes of a record that passes every hint, with this block_size, and its name"""
+    return struct.pack("<IiiBBHHHiiii", block_size, 0, 5, l_name, 60, 4680, 0, 0, 0, -1, -1, 0) + name
+
+
+def edge_stream(seg=EDGE_SEG):
+    """One stream of whole records, its segments `seg` bytes: records with block_size 33 (the shortest the reader takes: a name of one NUL), 35, 36
+    and 37 (around kBamRecHead), each once at every place of PLACES; then per decoy one long record that covers three segments whole and holds the
+    decoy at every place of PLACES -- decoys: 36 bytes with block_size 31, 32 (no record), 33 and 36 with a small record behind them (guessed,
+    wrongly), and a head with block_size kBamRecStoreMaxBlock - 1, kBamRecStoreMaxBlock (a record the stream cuts off: guessed, wrongly) and
+    kBamRecStoreMaxBlock + 1 (no record).  Nothing of that length is ever allocated.  -> (stream, number of records)"""
+    parts, at, k = [], 0, 1
+
+    def upto(target, seed):
+        nonlocal at
+        for r in fill(target - at, seed, most=8000):
+            parts.append(r)
+            at += len(r)
+    for length in (4 + MIN_BLOCK + 1, 4 + HEAD - 1, 4 + HEAD, 4 + HEAD + 1):
+        for _, off in PLACES:
+            upto(k * seg + off, 31 * k)
+            parts.append(record(length, 77 * k + length))
+            at += length
+            k += 1
+    small = record(40, 4242, tid=1, pos=9)
+    for bs in (MIN_BLOCK - 1, MIN_BLOCK, MIN_BLOCK + 1, HEAD, STORE_MAX_BLOCK - 1, STORE_MAX_BLOCK, STORE_MAX_BLOCK + 1):
+        decoy = head(bs, 0, b"") if bs <= MIN_BLOCK else head(bs) + bytes(bs - 33) + small if bs < 100 else head(bs)
+        upto(k * seg - 300, 57 * k)
+        body = bytearray(record(3 * seg + 600, 999 + bs % 1000))
+        for j, (_, off) in enumerate(PLACES):
+            o = 300 + (j + 1) * seg + off - (seg if off == 0 else 0)            # the decoy's block_size: at k*seg, (k+2)*seg - 4, (k+3)*seg - 2
+            assert body[o:o + len(decoy)] == bytes(len(decoy))
+            body[o:o + len(decoy)] = decoy
+        parts.append(bytes(body))
+        at += len(body)
+        k += 4
+    upto(at + 200, 5)
+    return b"".join(parts), len(parts)
+
+
+def edge_ends(seg=EDGE_SEG):
+    """[(name, stream)]: whole records up to a place of PLACES in the second segment, and there the stream's last thing:
+    block_size 31 (malformed) and 32 with its 36 bytes (malformed: no room for the name's NUL -- the reader's rule, not the frame's);
+    block_size 32 with fewer than 36 bytes left (the head is cut off: a tail, whatever block_size says);
+    a record of exactly the bytes that are left, one byte more than that (cut off: a tail), one byte less (a tail of one byte);
+    a head with block_size kBamRecStoreMaxBlock - 1 and kBamRecStoreMaxBlock (cut off: a tail) and kBamRecStoreMaxBlock + 1 (malformed)"""
+    out = []
+    whole = record(60, 8)
+    for place, off in PLACES:
+        front = b"".join(fill(seg + off, 13, most=8000))
+        for name, last in (("block_size 31", head(31, 0, b"")), ("block_size 32, 36 bytes", head(32, 0, b"")), ("block_size 32, 35 bytes", head(32, 0, b"")[:35]),
+                           ("block_size 32, 4 bytes", head(32, 0, b"")[:4]), ("block_size 33, 35 bytes", head(33)[:35]), ("block_size 33, 36 bytes", head(33)[:36]), ("block_size 33, whole", head(33)),
+                           ("the last record ends the stream", whole), ("the last record lacks a byte", whole[:-1]), ("a byte behind the last record", whole + b"\x25"), ("three bytes behind the last record", whole + b"\x25\0\0"),
+                           ("block_size kBamRecStoreMaxBlock - 1", head(STORE_MAX_BLOCK - 1) + bytes(40)), ("block_size kBamRecStoreMaxBlock", head(STORE_MAX_BLOCK) + bytes(40)),
+                           ("block_size kBamRecStoreMaxBlock + 1", head(STORE_MAX_BLOCK + 1) + bytes(40))):
+            out.append(("%s %s" % (name, place), front + last))
+    return out
+
+
 def build_checker(tmp, sanitize):
     exe = os.path.join(tmp, "bam_chain_check_asan" if sanitize else "bam_chain_check")
     flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else ["-O2"]

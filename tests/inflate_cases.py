@@ -35,6 +35,13 @@ def header_rules(buf):
     return bsize, xlen
 
 
+def inf_isize_possible(buf):
+    """inflate_device.h's rule of that name for the member buf starts with (its header passes): a payload of n bytes holds 1032 n bytes at most;
+    a member whose ISIZE is beyond that is refused where the batch is laid out, as a bad header is"""
+    bsize, xlen = header_rules(buf)
+    return struct.unpack_from("<I", buf, bsize - 4)[0] <= 1032 * (bsize - 12 - xlen - 8)
+
+
 def oracle(buf):
     """The inflated bytes of the member at the start of buf, or None when it must be refused."""
     h = header_rules(buf)
@@ -355,112 +362,400 @@ def hand_valid():
 
 
 def hand_bad():
-    """[(name, member, accepted)]: one member for every way of refusing, built by hand; and a few odd ones that must pass."""
+    """[(name, member, status)]: one member for every way of refusing, built by hand, with the name of the status inflate_device.h must
+    give it (the first rule it breaks in stream order); and a few odd ones that must pass ("kInfOk").  Every refused member but "crc" and
+    the ISIZE ones carries the CRC32 and ISIZE of the data it was meant to hold: a decoder that lacked the rule would be caught by the
+    trailer all the same, which is why the status is asserted and not only the refusal.  Where a member breaks two rules:
+      stored-longer-than-the-input   LEN is more than the payload has left and more than ISIZE: the input is looked at first, kInfTruncated
+      no-end-of-block                the padding bits behind the last literal are the start of a code the payload's end cuts off: kInfTruncated
+      isize-out-of-reach             refused where the batch is laid out (inf_isize_possible), before the decoder runs: the host checker
+                                     calls that kInfTooShort, psvr_bgzf_decompress reports the member as a bad header (kInfHeader)"""
     out = []
     ok_lit = lens(258, {97: 1, 256: 2, 257: 2})
 
-    def add(name, b, data=b"", accepted=False, **kw):
+    def add(name, status, b, data=b"", **kw):
         payload = b.bytes() if isinstance(b, Bits) else b
-        out.append((name, wrap(payload, data, **kw), accepted))
+        out.append((name, wrap(payload, data, **kw), status))
     b = Bits()
     b.put(1, 1), b.put(3, 2), b.put(0, 13)
-    add("block-type-3", b)
+    add("block-type-3", "kInfBlockType", b)
     b = Bits()
     b.put(1, 1), b.put(0, 2), b.align(), b.put(3, 16), b.put(3 ^ 0xfffe, 16)
     b.out += b"abc"
-    add("stored-len-nlen", b, b"abc")
+    add("stored-len-nlen", "kInfStored", b, b"abc")
     b = Bits()
     b.put(1, 1), b.put(0, 2), b.align(), b.put(30, 16), b.put(30 ^ 0xffff, 16)
     b.out += b"abc"
-    add("stored-longer-than-the-input", b, b"abc")
+    add("stored-longer-than-the-input", "kInfTruncated", b, b"abc")
     b = Bits()
     b.put(1, 1), b.put(0, 2), b.align(), b.put(3, 16)
-    add("stored-header-cut", b, b"")
+    add("stored-header-cut", "kInfTruncated", b, b"")
     b = Bits()
     dynamic_block(b, [97], lens(286, {97: 1, 256: 2, 257: 2}), [1], hlit=30)
-    add("hlit-287", b, b"a")
+    add("hlit-287", "kInfCounts", b, b"a")
     b = Bits()
     dynamic_block(b, [97], ok_lit, [1] + [0] * 29, hdist=30)
-    add("hdist-31", b, b"a")
+    add("hdist-31", "kInfCounts", b, b"a")
     b = Bits()
     dynamic_block(b, [97], lens(258, {97: 1, 98: 1, 256: 2, 257: 2}), [1])
-    add("literal-code-over-subscribed", b, b"a")
+    add("literal-code-over-subscribed", "kInfLitTable", b, b"a")
     b = Bits()
     dynamic_block(b, [97], lens(258, {97: 2, 256: 2, 257: 2}), [1])
-    add("literal-code-incomplete", b, b"a")
+    add("literal-code-incomplete", "kInfLitTable", b, b"a")
     b = Bits()
     dynamic_block(b, [97], ok_lit, [1, 1, 1])
-    add("distance-code-over-subscribed", b, b"a")
+    add("distance-code-over-subscribed", "kInfDistTable", b, b"a")
     b = Bits()
     dynamic_block(b, [97], ok_lit, [2, 2])
-    add("distance-code-incomplete", b, b"a")
+    add("distance-code-incomplete", "kInfDistTable", b, b"a")
     b = Bits()
     dynamic_block(b, [97], ok_lit, [1], cl=[4] * 15 + [0, 0, 0, 0])
-    add("code-length-code-incomplete", b, b"a")
+    add("code-length-code-incomplete", "kInfCodeLengths", b, b"a")
     b = Bits()
     dynamic_block(b, [97], ok_lit, [1], cl=[3] * 9 + [0] * 10, clsyms=[0] * 259)
-    add("code-length-code-over-subscribed", b, b"a")
+    add("code-length-code-over-subscribed", "kInfCodeLengths", b, b"a")
     b = Bits()
     dynamic_header(b, ok_lit, [1], cl=CL_RUNS, clsyms=[(16, 0)] + [0] * 256)
-    add("repeat-without-a-previous-length", b)
+    add("repeat-without-a-previous-length", "kInfCodeLengths", b)
     b = Bits()
-    dynamic_header(b, ok_lit, [1], cl=CL_RUNS, clsyms=[0] * 97 + [1] + [0] * 158 + [2, 2, 1, (16, 0)])
-    add("repeat-past-the-end", b)
+    dynamic_header(b, ok_lit, [1], cl=CL_RUNS, clsyms=[0] * 97 + [1] + [0] * 158 + [2, 2, (16, 0)])         # (258 lengths, then 3 more for the 1 that is left)
+    add("repeat-past-the-end", "kInfCodeLengths", b)
     b = Bits()
     dynamic_header(b, ok_lit, [1], cl=CL_RUNS, clsyms=[0] * 97 + [1] + [0] * 158 + [2, 2, (17, 0)])
-    add("zero-run-past-the-end", b)
+    add("zero-run-past-the-end", "kInfCodeLengths", b)
     b = Bits()
     dynamic_header(b, lens(258, {97: 1, 257: 1}), [1])
     b.put(0, 16)
-    add("no-end-of-block-code", b, b"a")
+    add("no-end-of-block-code", "kInfNoEob", b, b"a")
     for s in (286, 287):
         b = Bits()
         fixed_block(b, [97, ("lit", s)])
-        add("fixed-symbol-%d" % s, b, b"a")
+        add("fixed-symbol-%d" % s, "kInfLitCode", b, b"a")
     for s in (30, 31):
         b = Bits()
         fixed_block(b, [97, 97, 97, ("dist", 3, s, 0)])
-        add("fixed-distance-symbol-%d" % s, b, b"aaa")
+        add("fixed-distance-symbol-%d" % s, "kInfDistCode", b, b"aaa")
     b = Bits()
     fixed_block(b, [97, 98, (3, 3)])
-    add("distance-in-front-of-the-member", b, b"ab")
+    add("distance-in-front-of-the-member", "kInfFarBack", b, b"ab")
     b = Bits()
     dynamic_header(b, lens(258, {97: 2, 256: 2, 257: 1}), [1])
     cl_ = canon(lens(258, {97: 2, 256: 2, 257: 1}))
     b.code(cl_[97]), b.code(cl_[257]), b.put(1, 1)                         # the lone distance code is "0"; "1" is unassigned
     b.put(0, 16)
-    add("unassigned-distance-code", b, b"a")
+    add("unassigned-distance-code", "kInfDistCode", b, b"a")
     b = Bits()
     dynamic_header(b, lens(257, {97: 1, 256: 1}), [0])
     b.put(0, 1), b.put(1, 1)
-    add("a-block-of-two-1-bit-codes", b, b"a", accepted=True)
+    add("a-block-of-two-1-bit-codes", "kInfOk", b, b"a")
     b = Bits()
     dynamic_header(b, lens(258, {97: 2, 256: 2, 257: 1}), [0])
     b.code(cl_[97]), b.code(cl_[257]), b.put(0, 16)
-    add("match-without-a-distance-code", b, b"aaaa")
+    add("match-without-a-distance-code", "kInfDistCode", b, b"aaaa")
     b = Bits()
     fixed_block(b, [97, 98, 99])
-    add("longer-than-isize", b, b"ab", crc=zlib.crc32(b"ab"))
-    add("shorter-than-isize", b, b"abcd")
+    add("longer-than-isize", "kInfTooLong", b, b"ab", crc=zlib.crc32(b"ab"))
+    add("shorter-than-isize", "kInfTooShort", b, b"abcd")
     b = Bits()
     fixed_block(b, [97, (258, 1), (258, 1)])
-    add("a-match-longer-than-isize", b, b"a" * 300)
-    add("crc", b, b"a" * 517, crc=zlib.crc32(b"a" * 517) ^ 0x100)
-    add("isize-out-of-reach", b, b"", crc=0, isize=0xfff00000)
+    add("a-match-longer-than-isize", "kInfTooLong", b, b"a" * 300)
+    add("crc", "kInfCrc", b, b"a" * 517, crc=zlib.crc32(b"a" * 517) ^ 0x100)
+    add("isize-out-of-reach", "kInfTooShort", b, b"", crc=0, isize=0xfff00000)
     b = Bits()
     fixed_block(b, [97, 98, 99], eob=False)
-    add("no-end-of-block", b, b"abc")
+    add("no-end-of-block", "kInfTruncated", b, b"abc")
     b = Bits()
     fixed_block(b, [97, 98, 99], final=False)
-    add("no-final-block", b, b"abc")
-    add("empty-payload", b"", b"")
+    add("no-final-block", "kInfTruncated", b, b"abc")
+    add("empty-payload", "kInfTruncated", b"", b"")
     b = Bits()
     fixed_block(b, [97, 98, 99])
-    add("bytes-behind-the-stream", b.bytes() + b"\xff\x00\x12garbage", b"abc", accepted=True)
-    add("a-second-subfield", b.bytes(), b"abc", accepted=True, extra=b"XY\x03\x00abcBC\x02\x00\x00\x00ZZ\x00\x00")
+    add("bytes-behind-the-stream", "kInfOk", b.bytes() + b"\xff\x00\x12garbage", b"abc")
+    add("a-second-subfield", "kInfOk", b.bytes(), b"abc", extra=b"XY\x03\x00abcBC\x02\x00\x00\x00ZZ\x00\x00")
     b = Bits()
     b.put(1, 1), b.put(0, 2), b.put(0, 5), b.put(0, 16), b.put(0xffff, 16)
-    add("an-empty-stored-block", b, b"", accepted=True)
+    add("an-empty-stored-block", "kInfOk", b, b"")
+    return out
+
+
+PRE = bytes(range(32, 96))                            # what every member of rule_edges() holds in a stored block in front of the block in question
+FORGED_ISIZE = 0xff00
+# the code-length code of rule_edges(): 0 and 18 in two bits, the lengths 1..15 and 16 in five (complete; no 17)
+CL_EDGE = [2] + [5] * 16 + [0, 2]
+
+
+def zeros(n):
+    """n zero lengths as code-length symbols: runs of 11..138 by symbol 18, the rest one by one"""
+    out = []
+    while n >= 11:
+        k = min(n, 138)
+        out.append((18, k - 11))
+        n -= k
+    return out + [0] * n
+
+
+def run_lengths(lengths):
+    """the code-length symbols for these lengths: the zero runs by zeros(), everything else as itself"""
+    out, k = [], 0
+    for l in list(lengths) + [None]:
+        if l == 0:
+            k += 1
+            continue
+        out += zeros(k)
+        k = 0
+        if l is not None:
+            out.append(l)
+    return out
+
+
+def rule_edges():
+    """[(name, member, status, data or None)]: for every rule of inflate_device.h a member just inside its edge (status "kInfOk", `data` the bytes
+    it holds, which must be zlib's) and members just outside, each with the status of that very rule.  An outside member comes twice: as
+    ".../trailer" with the CRC32 and ISIZE of the data it was meant to hold, and as ".../forged" with ISIZE = 0xff00 and another CRC32 -- a
+    trailer that does not know the right answer, so that the refusal cannot be the trailer check's.  Every member starts with a stored block
+    of 64 bytes (PRE), not the final one: an ISIZE of 0xff00 is out of reach of a payload of fewer than 64 bytes (inf_isize_possible), and
+    such a member would be refused before the decoder ran.  The symbols no code may use (286, 287; 30, 31) stand first in their block, behind
+    a few literals, and as the last code before the payload ends.
+    Where a member breaks two rules (the order is the one of inflate_device.h's head comment):
+      distance-and-room               a match that starts in front of the member and ends behind ISIZE: kInfFarBack
+      unassigned-*-code-at-the-end    no code matches and the payload ends within 15 bits: kInfTruncated; with two more bytes of payload
+                                      (".../padded") the same bits are kInfLitCode / kInfDistCode"""
+    out = []
+    FL, FD = canon(FIXED_LIT), canon(FIXED_DIST)
+    ok_lit = lens(258, {97: 1, 256: 2, 257: 2})
+
+    def start():
+        b = Bits()
+        b.put(0, 1), b.put(0, 2), b.align(), b.put(len(PRE), 16), b.put(len(PRE) ^ 0xffff, 16)
+        b.out += PRE
+        return b
+
+    def inside(name, b, data):
+        payload = b.bytes() if isinstance(b, Bits) else b
+        out.append((name, wrap(payload, PRE + data), "kInfOk", PRE + data))
+
+    def outside(name, status, b, data=b"", forged=True):
+        payload = b.bytes() if isinstance(b, Bits) else b
+        out.append((name + "/trailer", wrap(payload, PRE + data), status, None))
+        if forged:
+            assert len(payload) >= 64
+            out.append((name + "/forged", wrap(payload, crc=zlib.crc32(PRE + data) ^ 0x5a5a5a5a, isize=FORGED_ISIZE), status, None))
+
+    def fixed(b, items, eob=True):
+        """a final fixed block of literals, ("L", symbol) and ("D", symbol) raw codes and ("X", value, bits) raw bits"""
+        b.put(1, 1), b.put(1, 2)
+        for it in items:
+            if isinstance(it, int):
+                b.code(FL[it])
+            elif it[0] == "L":
+                b.code(FL[it[1]])
+            elif it[0] == "D":
+                b.code(FD[it[1]])
+            else:
+                b.put(it[1], it[2])
+        if eob:
+            b.code(FL[256])
+        return b
+
+    def dyn(b, toks, litlens, distlens, cl=CL_EDGE, clsyms=None, eob=True, **kw):
+        dynamic_header(b, litlens, distlens, cl=cl, clsyms=clsyms if clsyms is not None else run_lengths(list(litlens) + list(distlens)), **kw)
+        if toks is not None:
+            tokens(b, toks, canon(litlens), canon(distlens))
+            if eob:
+                b.code(canon(litlens)[256])
+        return b
+
+    def held(toks):
+        return expand(list(PRE) + toks)[len(PRE):]
+
+    # ---- HLIT and HDIST: 286 / 30 codes are the most; the members outside are whole and consistent for a decoder that counted further
+    for nl in (286, 287, 288):
+        b = dyn(start(), [97], lens(nl, {97: 1, 256: 2, 257: 2}), [1])
+        inside("hlit-286", b, b"a") if nl == 286 else outside("hlit-%d" % nl, "kInfCounts", b, b"a")
+    for nd in (30, 31, 32):
+        b = dyn(start(), [97, (3, 1)], lens(259, {97: 1, 256: 2, 257: 3, 258: 3}), [1] + [0] * (nd - 1))
+        inside("hdist-30", b, b"aaaa") if nd == 30 else outside("hdist-%d" % nd, "kInfCounts", b, b"aaaa")
+    # ---- literal/length symbols 285 | 286, 287 and distance symbols 29 | 30, 31 of the fixed code, at three places
+    far = [0] + [(258, 1)] * 96                                                # 24 833 bytes lie in front: distance symbol 29 starts at 24 577
+    for place, front, back, eob in (("first", [], [97, 98], True), ("behind-literals", [97, 98, 99], [100], True), ("last", [97, 98, 99], [], False)):
+        toks = front + [(258, 1)] + (back if eob else [])
+        b = start()
+        fixed_block(b, toks)
+        inside("symbol-285-%s" % place, b, held(toks))
+        toks = front + [(3, 24577)] + (back if eob else [])
+        b = start()
+        fixed_block(b, far, final=False)
+        fixed_block(b, toks)
+        inside("distance-symbol-29-%s" % place, b, held(far + toks))
+        for s in (286, 287):
+            # behind the symbol, where there is a behind: what a decoder that took it for a length would go on with (a distance code, literals)
+            b = fixed(start(), front + [("L", s)] + ([("D", 0)] + back if eob else []), eob=eob)
+            outside("symbol-%d-%s" % (s, place), "kInfLitCode", b, bytes(front))
+        for s in (30, 31):
+            b = fixed(start(), front + [("L", 257), ("D", s)] + ([("X", 0, 13)] + back if eob else []), eob=eob)
+            outside("distance-symbol-%d-%s" % (s, place), "kInfDistCode", b, bytes(front))
+    # ---- block types and the stored block's LEN / NLEN
+    inside("btype-1", fixed(start(), [97]), b"a")
+    inside("btype-2", dyn(start(), [97], ok_lit, [1]), b"a")
+    b = start()
+    b.put(1, 1), b.put(3, 2), b.put(0, 29)
+    outside("btype-3", "kInfBlockType", b)
+    for flip in (0, 1, 0x8000):
+        b = start()
+        b.put(1, 1), b.put(0, 2), b.align(), b.put(3, 16), b.put(3 ^ 0xffff ^ flip, 16)
+        b.out += b"abc"
+        inside("stored-len-nlen", b, b"abc") if not flip else outside("stored-len-nlen-bit-%x" % flip, "kInfStored", b, b"abc")
+    b = start()                                                                  # (the member above: a stored block may reach the payload's last byte)
+    b.put(1, 1), b.put(0, 2), b.align(), b.put(4, 16), b.put(4 ^ 0xffff, 16)
+    b.out += b"abc"
+    outside("stored-block-a-byte-longer-than-the-payload", "kInfTruncated", b, b"abc")
+    # ---- the code lengths: a repeat needs a length in front of it, and no run may pass the last length
+    inside("repeat-behind-a-length", dyn(start(), [0, 1, 2, 3], lens(257, {0: 3, 1: 3, 2: 3, 3: 3, 256: 1}), [0], clsyms=[3, (16, 0)] + zeros(252) + [1, 0]), bytes([0, 1, 2, 3]))
+    outside("repeat-without-a-previous-length", "kInfCodeLengths",                # (a decoder that repeated "0": lengths for 3, 4, 5, 6)
+            dyn(start(), [3, 4, 5, 6], lens(257, {3: 3, 4: 3, 5: 3, 6: 3, 256: 1}), [0], clsyms=[(16, 0), 3, (16, 0)] + zeros(249) + [1, 0]), bytes([3, 4, 5, 6]))
+    front = zeros(97) + [1] + zeros(158) + [2, 2]                                 # ok_lit
+    cl_runs = lens(19, {0: 2, 18: 2, 1: 3, 2: 3, 16: 3, 17: 3})
+    for sym, tail, nd in ((16, [2, (16, 0)], 4), (17, [1, (17, 0)], 4), (18, [1, (18, 0)], 12)):
+        dl = [2] * 4 if sym == 16 else [1] + [0] * (nd - 1)
+        inside("run-%d-to-the-end" % sym, dyn(start(), [97], ok_lit, dl, cl=cl_runs, clsyms=front + tail), b"a")
+        outside("run-%d-past-the-end" % sym, "kInfCodeLengths", dyn(start(), [97], ok_lit, dl[:nd - 1], cl=cl_runs, clsyms=front + tail), b"a")
+    # ---- the end-of-block symbol needs a code
+    b = dyn(start(), None, lens(258, {97: 1, 257: 1}), [1])
+    b.put(0, 16)
+    outside("no-end-of-block-code", "kInfNoEob", b, b"a")
+    # ---- complete | over-subscribed, incomplete -- by one code of the longest length -- for each of the three codes
+    full = dict([(97, 1), (256, 2), (257, 3)] + [(k, k + 4) for k in range(12)] + [(12, 15)])      # 1, 2, ..., 15, 15 bits
+    inside("literal-code-complete", dyn(start(), [97, 0, 12], lens(258, full), [1]), bytes([97, 0, 12]))
+    over, under = dict(full), dict(full)
+    over[13] = 15
+    del under[12]
+    b = dyn(start(), None, lens(258, over), [1])
+    b.put(0, 16)
+    outside("literal-code-over-subscribed-by-one", "kInfLitTable", b, b"a")
+    outside("literal-code-incomplete-by-one", "kInfLitTable", dyn(start(), [97, 0], lens(258, under), [1]), bytes([97, 0]))
+    inside("literal-code-of-one-bit", dyn(start(), [], lens(257, {256: 1}), [0]), b"")
+    outside("literal-code-of-two-bits", "kInfLitTable", dyn(start(), [], lens(257, {256: 2}), [0]))
+    dfull = list(range(1, 16)) + [15]
+    inside("distance-code-complete", dyn(start(), [97, (3, 1)], ok_lit, dfull), b"aaaa")
+    b = dyn(start(), None, ok_lit, dfull + [15])
+    b.put(0, 16)
+    outside("distance-code-over-subscribed-by-one", "kInfDistTable", b, b"a")
+    outside("distance-code-incomplete-by-one", "kInfDistTable", dyn(start(), [97, (3, 1)], ok_lit, dfull[:15]), b"aaaa")
+    inside("distance-code-of-one-bit", dyn(start(), [97, (3, 1)], ok_lit, [1]), b"aaaa")
+    outside("distance-code-of-two-bits", "kInfDistTable", dyn(start(), [97, (3, 1)], ok_lit, [2]), b"aaaa")
+    cfull = lens(19, {18: 1, 0: 2, 1: 3, 2: 4, 3: 5, 4: 6, 5: 7, 6: 7})            # the code-length code has 7 bits at most
+    inside("code-length-code-complete", dyn(start(), [97], ok_lit, [1], cl=cfull), b"a")
+    cover, cunder = list(cfull), list(cfull)
+    cover[7], cunder[6] = 7, 0
+    b = start()
+    dynamic_header(b, ok_lit, [1], cl=cover, clsyms=[])
+    b.put(0, 32)
+    outside("code-length-code-over-subscribed-by-one", "kInfCodeLengths", b, b"a")
+    outside("code-length-code-incomplete-by-one", "kInfCodeLengths", dyn(start(), [97], ok_lit, [1], cl=cunder), b"a")
+    # ---- a match may reach the member's first byte and no further
+    for name, toks in (("first", []), ("behind-literals", [97, 98])):
+        at = len(PRE) + len(toks)
+        b = start()
+        fixed_block(b, toks + [(3, at)])
+        inside("distance-to-the-first-byte-%s" % name, b, held(toks + [(3, at)]))
+        b = start()
+        fixed_block(b, toks + [(3, at + 1)])
+        outside("distance-in-front-of-the-member-%s" % name, "kInfFarBack", b, bytes(toks))
+    b = start()
+    fixed_block(b, [97, 98, (258, len(PRE) + 3)])
+    out.append(("distance-and-room/trailer", wrap(b.bytes(), PRE + b"ab" + bytes(10)), "kInfFarBack", None))
+    # ---- a code no symbol has, in front of more payload and at its end
+    one, two = lens(257, {256: 1}), lens(258, {97: 2, 256: 2, 257: 1})
+    for pad in (16, 0):
+        b = dyn(start(), None, one, [0])
+        b.put(1, 1), b.put(0, pad)                                               # "0" is the end of the block, "1" is nothing
+        outside("unassigned-literal-code-" + ("padded" if pad else "at-the-end"), "kInfLitCode" if pad else "kInfTruncated", b)
+        b = dyn(start(), None, two, [1])
+        b.code(canon(two)[97]), b.code(canon(two)[257]), b.put(1, 1), b.put(0, pad)   # the lone distance code is "0"
+        outside("unassigned-distance-code-" + ("padded" if pad else "at-the-end"), "kInfDistCode" if pad else "kInfTruncated", b, b"a")
+    # ... and exactly at the rule's edge: with 14 bits left a code of 15 may have been cut off, with 15 left there is no such code
+    cl_few = lens(19, {0: 2, 1: 3, 2: 3, 18: 1})
+
+    def with_bits_left(make, left):
+        for cl, ncl in ((CL_EDGE, 19), (cl_few, 19), (cl_few, 18)):               # (headers of odd and even lengths)
+            for k in range(4):
+                b = start()
+                for _ in range(k):
+                    fixed_block(b, [], final=False)                               # 10 bits
+                make(b, cl, ncl)
+                if (b.n + left) % 8 == 0:
+                    b.put(1, 1), b.put(0, left - 1)
+                    assert b.n == 0
+                    return b
+        raise AssertionError(left)
+
+    def lit_at(b, cl, ncl):
+        dyn(b, None, one, [0], cl=cl, ncl=ncl)
+
+    def dist_at(b, cl, ncl):
+        dyn(b, None, two, [1], cl=cl, ncl=ncl)
+        b.code(canon(two)[97]), b.code(canon(two)[257])
+    for left in (14, 15):
+        outside("unassigned-literal-code-%d-bits-left" % left, "kInfLitCode" if left == 15 else "kInfTruncated", with_bits_left(lit_at, left))
+        outside("unassigned-distance-code-%d-bits-left" % left, "kInfDistCode" if left == 15 else "kInfTruncated", with_bits_left(dist_at, left), b"a")
+    # ---- the payload ends one bit short of what a field needs (a decoder that did not count would read the absent bit as 0 and go on)
+    def cut(name, b, data=b""):
+        assert b.n == 0, name                                                     # the missing bit would be the payload's next
+        outside(name + "-cut-by-a-bit", "kInfTruncated", b, data)
+    b = start()
+    fixed_block(b, [200] * 4, final=False)                                        # 3 + 4 x 9 + 7 bits
+    b.put(1, 2)
+    cut("block-header", b, bytes([200] * 4))
+    b = start()
+    b.put(1, 1), b.put(2, 2), b.put(0, 13)
+    cut("dynamic-header", b)
+    b = start()
+    b.put(1, 1), b.put(2, 2), b.put(0, 5), b.put(0, 5), b.put(15, 4)
+    for _ in range(7):
+        b.put(1, 3)
+    b.put(1, 2)
+    cut("code-length-code-length", b)
+    b = start()
+    dynamic_header(b, ok_lit, [1], cl=cfull, clsyms=[])
+    v, k = canon(cfull)[5]
+    assert k == 7
+    for i in range(k - 1, 0, -1):
+        b.put(v >> i & 1, 1)
+    cut("code-length-code", b)
+    b = start()
+    dynamic_header(b, ok_lit, [1], cl=cfull, clsyms=[1, 0, 0])
+    b.code(canon(cfull)[18]), b.put(0, 6)
+    cut("zero-run-extra-bits", b)
+    b = fixed(start(), [200, 200, 200, ("L", 277), ("X", 0, 3)], eob=False)         # symbol 277: 4 extra bits
+    cut("length-extra-bits", b, bytes([200] * 3))
+    b = fixed(start(), [("L", 257), ("D", 6), ("X", 0, 1)], eob=False)             # distance symbol 6: 2 extra bits
+    cut("distance-extra-bits", b)
+    # ---- ISIZE bytes and ISIZE + 1: by a literal, by a match, by a stored block; the trailer's ISIZE is the rule here, so these come once
+    def isize_pair(name, b, data):
+        inside("isize-reached-by-" + name, b, data)
+        short = PRE + data[:-1]
+        out.append(("isize-passed-by-%s/trailer" % name, wrap(b.bytes(), short), "kInfTooLong", None))
+    b = start()
+    fixed_block(b, [97, 98, 99])
+    isize_pair("a-literal", b, b"abc")
+    b = start()
+    fixed_block(b, [97, (3, 1)])
+    isize_pair("a-match", b, b"aaaa")
+    b = start()
+    b.put(1, 1), b.put(0, 2), b.align(), b.put(3, 16), b.put(3 ^ 0xffff, 16)
+    b.out += b"abc"
+    isize_pair("a-stored-block", b, b"abc")
+    # ... and at ISIZE = 0xff00 with a CRC32 that is not the data's: 0xff01 bytes are refused for their number, 0xff00 for the CRC32
+    for extra, status in ((0, "kInfCrc"), (1, "kInfTooLong")):
+        toks = [97] + [(258, 1)] * 252 + [(199 + extra, 1)]
+        assert len(PRE) + len(held(toks)) == FORGED_ISIZE + extra
+        b = start()
+        fixed_block(b, toks)
+        out.append(("isize-0xff00-%s/forged" % ("passed" if extra else "reached"), wrap(b.bytes(), crc=zlib.crc32(PRE + held(toks)) ^ 0x5a5a5a5a, isize=FORGED_ISIZE), status, None))
+        if not extra:
+            inside("isize-0xff00-reached", b, held(toks))
+    names = [c[0] for c in out]
+    assert len(set(names)) == len(names)
     return out
 
 
@@ -514,14 +809,21 @@ def build_checker(tmp, sanitize):
     return exe
 
 
-def run_checker(exe, bufs, timeout=600):
-    """[(status, bytes or None)] of the decoder's host build for every buffer; the sanitizer's report, if any, fails the call."""
+def constants(exe):
+    """{name: number} of inflate_device.h's statuses, as the checker prints them"""
+    w = subprocess.run([exe, "constants"], stdout=subprocess.PIPE, check=True).stdout.split()
+    return {w[i].decode(): int(w[i + 1]) for i in range(0, len(w), 2)}
+
+
+def run_checker(exe, bufs, timeout=600, direct=False):
+    """[(status, bytes or None)] of the decoder's host build for every buffer; the sanitizer's report, if any, fails the call.
+    direct: every buffer is u32 hdr, u32 isize and a member, and inf_member is called with just that (no bgzf_member_header in front)"""
     tmp = tempfile.mkdtemp(prefix="psvr_infl_")
     with open(os.path.join(tmp, "cases"), "wb") as f:
         f.write(struct.pack("<I", len(bufs)))
         for b in bufs:
             f.write(struct.pack("<I", len(b)) + bytes(b))
-    r = subprocess.run([exe, os.path.join(tmp, "cases"), os.path.join(tmp, "results")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
+    r = subprocess.run([exe] + (["direct"] if direct else []) + [os.path.join(tmp, "cases"), os.path.join(tmp, "results")], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout)
     assert r.returncode == 0 and not r.stderr, "inflate_check: exit status %d\n%s" % (r.returncode, r.stderr.decode()[-4000:])
     raw = open(os.path.join(tmp, "results"), "rb").read()
     out, at = [], 0
@@ -539,7 +841,7 @@ def run_checker(exe, bufs, timeout=600):
 
 def malformed_sets(members):
     """name -> buffers; every buffer is judged by oracle()"""
-    return {"by hand": [m for _, m, _ in hand_bad()], "truncations": truncations(), "payload mutations": payload_mutations(members), "header mutations": header_mutations(members)}
+    return {"by hand": [m for _, m, _ in hand_bad()], "rule edges": [c[1] for c in rule_edges()], "truncations": truncations(), "payload mutations": payload_mutations(members), "header mutations": header_mutations(members)}
 
 
 def classify(buf):

@@ -1,6 +1,8 @@
 """The one-wavefront-per-member BGZF decoder behind psvr_bgzf_decompress (pansvr_amd/csrc/inflate_device.h), compiled for the host
 (tests/tools/inflate_check.cpp) twice: -O2, and -O1 with AddressSanitizer + UBSan where every member and every output slice lives in a heap
-block of exactly its size.  Valid members must give zlib's bytes; malformed ones zlib's verdict, without a report from the sanitizer."""
+block of exactly its size.  Valid members must give zlib's bytes; malformed ones zlib's verdict, without a report from the sanitizer; and a
+member made by hand for one rule (inflate_cases.hand_bad, rule_edges) the status of that rule, not merely a refusal: most of them carry the
+trailer of the data they were meant to hold, which would refuse them whatever the decoder did (tools/mutants.py keeps the evidence)."""
 import os
 import struct
 import tempfile
@@ -85,16 +87,72 @@ def same_verdict(checker, bufs):
     return accepted
 
 
-def test_each_failure_class_by_hand(asan_checker):
+STATUSES = ("kInfOk", "kInfHeader", "kInfBlockType", "kInfStored", "kInfTruncated", "kInfCounts", "kInfCodeLengths", "kInfNoEob", "kInfLitTable", "kInfDistTable", "kInfLitCode",
+            "kInfDistCode", "kInfFarBack", "kInfTooLong", "kInfTooShort", "kInfCrc")
+
+
+def test_constants_are_printed(checker, asan_checker):
+    k = ic.constants(checker)
+    assert k == ic.constants(asan_checker)
+    assert set(k) == set(STATUSES) and k["kInfOk"] == 0 and len(set(k.values())) == len(STATUSES)
+
+
+def named_status(checker, cases):
+    """every member gets the status its case names -- not merely a refusal -- and an accepted one holds zlib's bytes"""
+    k = ic.constants(checker)
+    got = ic.run_checker(checker, [c[1] for c in cases])
+    for (name, m, want), (status, out) in zip((c[:3] for c in cases), got):
+        assert status == k[want], "%s: status %d, not %s = %d" % (name, status, want, k[want])
+        if status == 0:
+            assert out == ic.oracle(m), name
+
+
+def test_each_failure_class_by_hand(checker):
     cases = ic.hand_bad()
     assert len(cases) >= 35
-    for name, m, accepted in cases:
-        assert (ic.oracle(m) is not None) == accepted, name
-    got = ic.run_checker(asan_checker, [c[1] for c in cases])
-    for (name, m, accepted), (status, out) in zip(cases, got):
-        assert (status == 0) == accepted, "%s: status %d" % (name, status)
-        if accepted:
-            assert out == ic.oracle(m), name
+    for name, m, status in cases:
+        assert (ic.oracle(m) is not None) == (status == "kInfOk"), name
+    # every status but kInfHeader, which is not the decoder's to find (bgzf_member_header comes first: test_500_header_mutations)
+    assert {c[2] for c in cases} == set(STATUSES) - {"kInfHeader"}
+    named_status(checker, cases)
+
+
+def test_each_rule_at_its_edge(checker):
+    """zlib decides what is inside: an inside member is one zlib inflates to the bytes the case was built from"""
+    cases = ic.rule_edges()
+    assert len(cases) >= 100
+    for name, m, status, data in cases:
+        assert (status == "kInfOk") == (data is not None), name
+        assert ic.oracle(m) == data, name                                       # (None: zlib refuses, or the trailer does not fit what zlib made)
+        if data is None and not name.startswith("isize-"):                      # ... and for every rule but ISIZE it is zlib's inflate that refuses
+            h = ic.header_rules(m)
+            with pytest.raises(zlib.error):
+                d = zlib.decompressobj(-15)
+                d.decompress(m[12 + h[1]:h[0] - 8])
+                if not d.eof:
+                    raise zlib.error("the stream does not end")
+    kinds = {n.rsplit("/", 1)[1] for n, _, s, _ in cases if s != "kInfOk"}
+    assert kinds == {"trailer", "forged"}
+    forged = [c for c in cases if c[0].endswith("/forged")]
+    assert len(forged) >= 40 and all(struct.unpack("<I", c[1][-4:])[0] == ic.FORGED_ISIZE for c in forged)
+    assert {c[2] for c in cases} >= set(STATUSES) - {"kInfHeader", "kInfTooShort"}
+    named_status(checker, cases)
+
+
+def test_inf_member_holds_its_caller_to_the_layout(checker):
+    """inf_member as a caller with a layout of its own would call it (hdr, bsize and the slice's size are arguments): a member that has no room
+    for its header and trailer is kInfHeader before a byte of it is read, and a slice of the right size under a trailer that names another is
+    kInfTooShort"""
+    k = ic.constants(checker)
+    m = ic.wrap(ic.deflate(b"abc"), b"abc")
+    empty = m[:18] + m[-8:]                                                    # header and trailer, nothing between
+    lying = m[:-4] + struct.pack("<I", 4)
+    cases = [(18, 3, m, "kInfOk"), (18, 0, empty, "kInfTruncated"), (18, 0, empty[:-1], "kInfHeader"), (18, 0, empty[:8], "kInfHeader"), (12, 3, m[:12] + m[18:], "kInfOk"),
+             (11, 3, m[:11] + m[18:], "kInfHeader"), (0, 3, m[18:], "kInfHeader"), (18, 3, lying, "kInfTooShort"), (18, 4, lying, "kInfTooShort"), (18, 3, m[:-4] + struct.pack("<I", 2), "kInfTooShort"), (18, 2, m, "kInfTooLong")]
+    got = ic.run_checker(checker, [struct.pack("<II", hdr, isize) + mem for hdr, isize, mem, _ in cases], direct=True)
+    for (hdr, isize, mem, want), (status, out) in zip(cases, got):
+        assert status == k[want], (hdr, isize, len(mem), status, want)
+        assert out is None or out == b"abc"
 
 
 def test_every_truncation_point(asan_checker):

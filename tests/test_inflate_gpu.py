@@ -1,6 +1,8 @@
 """psvr_bgzf_decompress on the device (k_bgzf_inflate: a wavefront per member, pansvr_amd/csrc/inflate_device.h) against zlib: the valid
-members of tests/test_inflate.py, one batch of 256 MB, and the malformed sets -- PSVR_ERR_IO naming the right member, the process alive,
-the members in front of the bad one intact."""
+members of tests/test_inflate.py, one batch of 256 MB, and the malformed sets -- PSVR_ERR_IO naming the right member and the status the host
+build of the decoder gives it (for the members made by hand: the status of the rule they break), the process alive, the members in front
+of the bad one intact, and in one batch of refused and good members in turn every good member's bytes."""
+import struct
 import tempfile
 
 import numpy as np
@@ -65,16 +67,25 @@ def test_malformed_members_are_an_answer():
     sets = ic.malformed_sets(golden)
     assert len(sets["payload mutations"]) == 2000 and len(sets["header mutations"]) == 500
     checker = ic.build_checker(tempfile.mkdtemp(prefix="psvr_inflate_"), True)
+    K = ic.constants(checker)
+    named = {"by hand": ic.hand_bad(), "rule edges": ic.rule_edges()}           # the sets whose members name the status they must get
+    host = {}
     for name, bufs in sets.items():
         got = ic.run_checker(checker, bufs)
+        host[name] = [status for status, _ in got]
         for k, (buf, (status, out)) in enumerate(zip(bufs, got)):
             want = ic.oracle(buf)
             assert (status == 0) == (want is not None) and out == want, "host build, %s, case %d" % (name, k)
+        if name in named:
+            assert [c[1] for c in named[name]] == bufs
+            for c, status in zip(named[name], host[name]):
+                assert status == K[c[2]], "host build, %s: status %d, not %s" % (c[0], status, c[2])
     front = [m for m in golden if 200 < len(m) < 3000][:2]
     assert len(front) == 2
     front_data = b"".join(ic.oracle(m) for m in front)
     head = b"".join(front)
     seen = {"ok": 0, "bad": 0, "cut": 0}
+    statuses = {}
     for name, bufs in sets.items():
         for k, buf in enumerate(bufs):
             kind = ic.classify(buf)
@@ -86,6 +97,13 @@ def test_malformed_members_are_an_answer():
                 assert kind == "bad", what
                 assert e.bad_member == 2 and "member 2 at byte %d" % len(head) in str(e), what + ": " + str(e)
                 assert e.valid_bytes == front_data, what
+                # the device's status is the host build's, member for member; for the members made by hand, the one the case names.  (A member
+                # refused where the batch is laid out -- its header, or an ISIZE out of its payload's reach -- never reaches the decoder.)
+                want = host[name][k] if ic.header_rules(buf) and ic.inf_isize_possible(buf) else K["kInfHeader"]
+                assert "(status %d)" % want in str(e), what + ": " + str(e) + ", the host build says %d" % want
+                if name in named and want != K["kInfHeader"]:
+                    assert want == K[named[name][k][2]], what
+                statuses.setdefault(name, set()).add(want)
                 continue
             assert kind != "bad", what
             if kind == "cut":
@@ -93,7 +111,48 @@ def test_malformed_members_are_an_answer():
             else:
                 assert used == len(head) + ic.header_rules(buf)[0] and out.tobytes() == front_data + ic.oracle(buf), what
     assert min(seen.values()) > 0, seen
+    rev = {v: k for k, v in K.items()}
+    for name in named:
+        print("%s: the device returned %s" % (name, " ".join(sorted(rev[s] for s in statuses[name]))))
+        assert statuses[name] >= {K[c[2]] for c in named[name] if c[2] != "kInfOk"}, name
     through_device(golden[:20], [ic.oracle(m) for m in golden[:20]])      # the process and the context are alive
+
+
+def test_one_batch_of_rule_edges_refused_members_leave_their_neighbours_alone():
+    """every member of inflate_cases.rule_edges() in ONE call, a good member between any two: one launch, a wavefront per member.  The call names the
+    first refused member and its status; psvr_bgzf_decompress has copied the whole batch's output back by then, and in it every good member and
+    every inside-the-edge member holds its bytes, whatever the refused members next to them did with their own slices."""
+    import ctypes as C
+    from pansvr_amd import bgzf, lib
+    cases = ic.rule_edges()
+    checker = ic.build_checker(tempfile.mkdtemp(prefix="psvr_inflate_"), True)
+    K = ic.constants(checker)
+    host = ic.run_checker(checker, [c[1] for c in cases])                       # the sanitizer build first, on the identical bytes
+    assert [s for s, _ in host] == [K[c[2]] for c in cases]
+    good = [m for m in ic.golden_members() if 200 < len(m) < 3000][:3]
+    good_data = [ic.oracle(m) for m in good]
+    members, want = [good[0]], [good_data[0]]
+    for k, c in enumerate(cases):
+        members += [c[1], good[(k + 1) % 3]]
+        want += [c[3], good_data[(k + 1) % 3]]
+    assert 200 < len(members) < 1000
+    buf = np.frombuffer(b"".join(members), dtype=np.uint8)
+    rc, used, total, nm, bad = bgzf._call(0, buf, None, 0, None, 0)
+    assert (rc, used, nm, bad) == (0, len(buf), len(members), -1)                # every header passes, every ISIZE is within its payload's reach
+    isizes = [struct.unpack("<I", m[-4:])[0] for m in members]
+    assert total == sum(isizes)
+    out = np.full(total + 64, 0xa5, dtype=np.uint8)
+    offs = np.zeros(nm + 1, dtype=np.int64)
+    rc, used, total, nm, bad = bgzf._call(0, buf, out.ctypes.data_as(C.c_void_p), total, offs.ctypes.data_as(C.c_void_p), nm)
+    first = next(k for k, w in enumerate(want) if w is None)
+    assert rc == 5 and bad == first and list(offs) == list(np.cumsum([0] + isizes))
+    msg = lib().psvr_last_error().decode()
+    assert "member %d at byte" % first in msg and "(status %d)" % K[cases[(first - 1) // 2][2]] in msg, msg
+    assert out[total:].tobytes() == b"\xa5" * 64                                 # nothing behind the batch's last slice
+    for k, w in enumerate(want):
+        if w is not None:
+            assert out[offs[k]:offs[k + 1]].tobytes() == w, "member %d (%s)" % (k, "a good one" if k % 2 == 0 else cases[(k - 1) // 2][0])
+    through_device(good, good_data)
 
 
 def test_commands_with_inflate_device_write_the_same_files():

@@ -49,7 +49,12 @@ _SETS = {}
 def record_set(n):
     """(records, their stream behind SKIP bytes that are no records, the expectation) -- made once, shared, never changed"""
     if n not in _SETS:
-        recs = make_records(n, 7 + n, shortest=37)
+        if n == "edges":                                                       # block_size at chain_record's edges, at the edges of 16 KiB segments
+            buf, count = cc.edge_stream()
+            recs = bam_stream.split(b"BAM\1\0\0\0\0\0\0\0\0" + buf)[1]
+            assert len(recs) == count <= 200 and cc.EDGE_SEG == 16384
+        else:
+            recs = make_records(n, 7 + n, shortest=37)
         skip = SKIP if n else 0
         _SETS[n] = (recs, bytes(range(1, skip + 1)) + b"".join(recs), skip, expectation(recs))
     return _SETS[n]
@@ -83,10 +88,11 @@ def hold_store(st, recs, exp):
     (0, 0xff00, 0, 0, 0), (1, 0xff00, 64, 0, 1), (1, 100, 0, 4096, 0), (2, 100, 64, 4096, 1), (2, 333, 256, 0, 7),
     (2047, 0xff00, 0, 0, 0), (2047, 0xff00, 256, 4096, 1), (2047, 100, 64, 4096, 7), (2047, 333, 256, 0, 1), (2047, 333, 0, 4096, 0),
     (4 * 2048 + 7, 0xff00, 0, 0, 0), (4 * 2048 + 7, 0xff00, 64, 4096, 7), (4 * 2048 + 7, 100, 256, 0, 7), (4 * 2048 + 7, 333, 0, 4096, 7), (4 * 2048 + 7, 333, 64, 0, 0),
-    (4 * 2048 + 7, 0xff00, 256, 0, 1)])
+    (4 * 2048 + 7, 0xff00, 256, 0, 1), ("edges", 0xff00, 16384, 0, 3)])
 def test_members_in_records_out(n, block, seg, chunk, every):
     recs, stream, skip, exp = record_set(n)
     ms = members(n, block)
+    n = len(recs)
     st = make_store(seg, chunk)
     every = every or len(ms)
     inflated, tails, last, count = bytearray(), set(), skip, 0
@@ -103,7 +109,7 @@ def test_members_in_records_out(n, block, seg, chunk, every):
         assert st.info().n_records == count
         tails.add(ci.tail_bytes != 0)
     assert bytes(inflated) == stream and count == n
-    if n >= 2047 and every < len(ms):
+    if n >= 100 and every < len(ms):
         assert True in tails                                                   # calls ended inside records
     ci = st.chain_info()
     assert ci.segments >= (len(stream) - skip + (seg or 16384) - 1) // (seg or 16384) and ci.rewalked <= ci.segments
@@ -112,20 +118,21 @@ def test_members_in_records_out(n, block, seg, chunk, every):
     st.close()
 
 
-@pytest.mark.parametrize("tail", [5, 0])
+@pytest.mark.parametrize("tail", [5, 0, "edges"])
 def test_decoy_streams_are_repaired_as_on_the_host(tail):
-    """the two decoy streams of tests/test_bam_chain.py: the device's counters are those of the host build of the same header (the ABI does not hand the
-    entries out: the records, and with them every entry that starts one, are compared instead)"""
-    buf = cc.decoy_stream(tail)
-    host, = cc.run_checker(cc.build_checker(tempfile.mkdtemp(prefix="psvr_sdev_"), False), [(buf, 0, cc.N_REF, 256)])
-    st = make_store(256)
+    """the two decoy streams of tests/test_bam_chain.py and its stream of block_size edges (decoys with block_size 31 .. 36 and around
+    kBamRecStoreMaxBlock at the edges of 16 KiB segments): the device's counters are those of the host build of the same header (the ABI does not hand
+    the entries out: the records, and with them every entry that starts one, are compared instead)"""
+    buf, seg, n = (cc.edge_stream()[0], cc.EDGE_SEG, cc.edge_stream()[1]) if tail == "edges" else (cc.decoy_stream(tail), 256, 26)
+    host, = cc.run_checker(cc.build_checker(tempfile.mkdtemp(prefix="psvr_sdev_"), False), [(buf, 0, cc.N_REF, seg)])
+    st = make_store(seg)
     data = b"".join(ic.members_of(buf, level=1, block=0xff00))
     assert st.append_bgzf(data, n_ref=cc.N_REF) == len(data)
     ci = st.chain_info()
     assert (ci.segments, ci.no_guess, ci.wrong_guess, ci.rewalked, ci.tail_bytes) == (host["segments"], host["no_guess"], host["wrong_guess"], host["rewalked"], 0)
-    assert ci.wrong_guess >= 1 and st.info().n_records == host["total"] == 26
+    assert ci.wrong_guess >= 1 and st.info().n_records == host["total"] == n
     recs = bam_stream.split(b"BAM\1\0\0\0\0\0\0\0\0" + buf)[1]
-    assert len(recs) == 26 and st.download().tobytes() == b"".join(expectation(recs)[0])
+    assert len(recs) == n and st.download().tobytes() == b"".join(expectation(recs)[0])
     st.close()
 
 
@@ -195,6 +202,36 @@ def test_a_corrupt_member_refuses_its_call_only():
     with pytest.raises(EngineError, match="psvr error 5") as e:
         st.append_bgzf(not_bgzf, n_ref=len(REFS))
     assert e.value.bad_member == 2 and (st.info().n_records, st.chain_info().tail_bytes) == before
+    st.append_bgzf(b"".join(small[3:]), n_ref=len(REFS))                         # the good call still works
+    hold_store(st, recs, exp)
+    st.close()
+
+
+def test_every_refused_rule_edge_member_refuses_its_call_and_names_its_status():
+    """k_store_inflate is the decoder's second instantiation (it writes into a chunk): every refused member of inflate_cases.rule_edges(), between
+    good members of a BAM stream, refuses its call with the member's index and the status of the rule it breaks -- the host build's, which is run
+    first under the sanitizers on the identical bytes -- and the store goes on as if the call had not been made"""
+    from pansvr_amd._lib import EngineError
+    recs, stream, skip, exp = record_set(2047)
+    small = ic.members_of(stream, level=1, block=7001)
+    cases = [c for c in ic.rule_edges() if c[2] != "kInfOk"]
+    assert len(cases) >= 80
+    checker = ic.build_checker(tempfile.mkdtemp(prefix="psvr_sdev_"), True)
+    K = ic.constants(checker)
+    assert [s for s, _ in ic.run_checker(checker, [c[1] for c in cases])] == [K[c[2]] for c in cases]
+    st = make_store(256)
+    st.append_bgzf(b"".join(small[:3]), skip=skip, n_ref=len(REFS))
+    before = (st.info().n_records, st.chain_info().tail_bytes)
+    front = b"".join(small[3:5])
+    seen = set()
+    for name, m, status, _ in cases:
+        with pytest.raises(EngineError, match="psvr error 5") as e:             # PSVR_ERR_IO
+            st.append_bgzf(front + m + small[5], n_ref=len(REFS))
+        assert e.value.bad_member == 2 and "member 2 at byte %d" % len(front) in str(e.value), name + ": " + str(e.value)
+        assert "(status %d;" % K[status] in str(e.value), "%s: %s, not %s = %d" % (name, e.value, status, K[status])
+        seen.add(status)
+    assert (st.info().n_records, st.chain_info().tail_bytes) == before
+    print("k_store_inflate returned", " ".join(sorted(seen)))
     st.append_bgzf(b"".join(small[3:]), n_ref=len(REFS))                         # the good call still works
     hold_store(st, recs, exp)
     st.close()
