@@ -563,6 +563,57 @@ int  psvr_bam_store_meta(psvr_bam_store_t *st, int64_t first_rank, int64_t n, ps
 int  psvr_bam_store_stream(psvr_bam_store_t *st, psvr_bgzf_stream_t *s, int64_t first_rank, int64_t n);
 int  psvr_bam_store_download(psvr_bam_store_t *st, void *bytes, int64_t cap, int64_t *n_bytes);
 void psvr_bam_store_destroy(psvr_bam_store_t *st);
+/*   drop          the first n_front records (append order) cease to exist: n_records and n_bytes fall, the table's entries of the rest slide to
+ *                 the front and meta.index counts from the first record kept.  A pending tail stays pending (the next append_bgzf completes
+ *                 it).  Every chunk that holds none of the remaining records and is not the one being filled is released; one released
+ *                 chunk of the standard size is kept as a spare for the next chunk the store needs.  After order / order_names, or with
+ *                 n_front outside [0, n_records]: PSVR_ERR_ARG.  The call waits.  What a caller that works through a long file piece by
+ *                 piece (psvr_signal_run below) bounds its device memory with: a piece's inflated bytes plus a chunk.
+ *   footprint     what the store holds in device memory for records: the live chunks and the spare one, and their bytes. */
+int  psvr_bam_store_drop(psvr_bam_store_t *st, int64_t n_front);
+int  psvr_bam_store_footprint(psvr_bam_store_t *st, int64_t *chunks, int64_t *bytes);
+
+/* ---- `panSVR signal -N` over a record store: pair, judge and format FASTQ text in HBM ---------------------------------------------------------
+ * The per-pair rules of the name-sorted `signal` step (SignalStep::pair and write_fastq, pansvr_amd/csrc/signal_step.h) over the records of a
+ * psvr_bam_store_t, read where they lie through the store's address table (pansvr_amd/csrc/signal_device.h holds the rules for host and
+ * device).  Only FASTQ text and a small per-pair table come back.
+ *   create        the options of the step: the six scores, max_tid, -D (not_use_filter), -U (discard_full_match) with its insert-size window,
+ *                 and the four numbers of the STAT_ field, which the first pair that is written at all carries, once per object.
+ *   run           over the store's records [first_record, n_records) in append order: the primary records (!(flag & 0x900)) are compacted and
+ *                 paired (2j, 2j + 1); with an odd count the last primary is not consumed and info->consumed is its record index, otherwise
+ *                 n_records (`finish` changes nothing: the host loop drops a lone last record too).  Every pair gets a state:
+ *                   0 not written   1 written into the text buffer   2 to be written, but formatted by the host (a base code outside
+ *                   {1, 2, 4, 8, 15}, a quality of 223, or a text of 2 GiB)   3 the names differ   4 not first / second in template
+ *                   5 would be written but l_qseq of read 1 >= 2048
+ *                 and a note (bit 0: "wrong ISIZE").  The text holds the state-1 pairs in front of the first pair of state >= 3, back to
+ *                 back in pair order.  Both records of every pair in front of that pair are added to the two histograms of BamStat::collect,
+ *                 which accumulate over all runs.  A record that BamReader's rules refuse: PSVR_ERR_IO, nothing is counted.  The store must
+ *                 not be ordered and must be on the object's device (PSVR_ERR_ARG).  The call waits.
+ *   text          the text of the last run to text[0, info.text_bytes) (cap too small: PSVR_ERR_OVERFLOW).
+ *   pairs         the table of the last run, pairs[0, info.pairs) (40 bytes per pair): rec1 / rec2 are record indices of the store as it was at the run.
+ *   side          the records the host needs, gathered by the run and downloaded in one piece, side[0, info.side_bytes): of every pair in
+ *                 front of the first error pair that is declined or carries a note, and of the error pair, the two records back to
+ *                 back (block_size first) at the pair's side_off (-1: the pair has none).  One download per run, however many pairs
+ *                 the host formats.
+ *   pair_records  the bytes of the two records of pair p of the last run, back to back (block_size first), for the host formatter; the store
+ *                 must hold the records still (no drop in between).
+ *   stats         isize_n[100000] and len_n[1000], accumulated over all runs.
+ * No device: PSVR_ERR_DEVICE.  Calls run under the store's mutex on its stream, serialised with the store's. */
+typedef struct psvr_signal psvr_signal_t;
+typedef struct psvr_signal_opt {
+	int32_t gap_open, gap_ex, gap_open2, gap_ex2, match, mismatch, max_tid, not_use_filter, discard_full_match, isize_min, isize_max;
+	int32_t stat[4];                                    /* read_len, min_i, mid_i, max_i of STAT_ */
+} psvr_signal_opt_t;
+typedef struct psvr_signal_info { int64_t pairs, written, declined, first_error, text_bytes, consumed, side_bytes; } psvr_signal_info_t;
+typedef struct psvr_signal_pair { int64_t text_off, rec1, rec2, side_off; int32_t bytes; uint8_t state, note; uint16_t pad; } psvr_signal_pair_t; /* 40 bytes */
+int  psvr_signal_create(int device, const psvr_signal_opt_t *opt, psvr_signal_t **out);
+int  psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t first_record, int32_t finish, psvr_signal_info_t *info);
+int  psvr_signal_text(psvr_signal_t *sg, void *text, int64_t cap);
+int  psvr_signal_pairs(psvr_signal_t *sg, psvr_signal_pair_t *pairs, int64_t cap);
+int  psvr_signal_side(psvr_signal_t *sg, void *bytes, int64_t cap);
+int  psvr_signal_pair_records(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t pair, void *bytes, int64_t cap, int64_t *n_bytes);
+int  psvr_signal_stats(psvr_signal_t *sg, uint64_t *isize_n, uint64_t *len_n);
+void psvr_signal_destroy(psvr_signal_t *sg);
 
 #ifdef __cplusplus
 }

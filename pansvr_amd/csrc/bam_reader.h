@@ -332,43 +332,7 @@ struct BamRecord {                     // one alignment, fields as in bam1_core_
 	// bam_aux_get: pointer to the type byte of the tag, or null.  A tag is only returned when its whole value lies inside the
 	// record (Z/H: including the terminating NUL), so num_tag()/string_tag() and their callers never read past the end of a
 	// malformed record.
-	const uint8_t *aux_get(const char tag[2]) const
-	{
-		const uint8_t *p = aux(), *e = aux_end();
-		while (p + 3 <= e) {
-			const bool hit = p[0] == (uint8_t)tag[0] && p[1] == (uint8_t)tag[1];
-			const uint8_t *v = p + 2;
-			const char t = (char)v[0];
-			const uint8_t *val = v + 1;
-			size_t sz = 0;
-			switch (t) {
-			case 'A': case 'c': case 'C': sz = 1; break;
-			case 's': case 'S': sz = 2; break;
-			case 'i': case 'I': case 'f': sz = 4; break;
-			case 'd': sz = 8; break;
-			case 'Z': case 'H': {
-				const uint8_t *q = val;
-				while (q < e && *q) ++q;
-				if (q >= e) return nullptr;                      // no terminator inside the record
-				sz = (size_t)(q - val) + 1;
-				break;
-			}
-			case 'B': {
-				if (val + 5 > e) return nullptr;
-				const char st = (char)val[0];
-				const uint32_t cnt = val[1] | (uint32_t)val[2] << 8 | (uint32_t)val[3] << 16 | (uint32_t)val[4] << 24;
-				const size_t es = (st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4;
-				sz = 5 + es * (size_t)cnt;
-				break;
-			}
-			default: return nullptr;
-			}
-			if (sz > (size_t)(e - val)) return nullptr;          // the value runs past the record
-			if (hit) return v;
-			p = val + sz;
-		}
-		return nullptr;
-	}
+	const uint8_t *aux_get(const char tag[2]) const { return bam_aux_find(aux(), aux_end(), tag[0], tag[1]); }   // (bam_record.h: the device walks the same function)
 	// bam_get_string_tag (clib/bam_file.c:427-438): only 'Z'
 	const char *string_tag(const char tag[2]) const
 	{
@@ -376,20 +340,33 @@ struct BamRecord {                     // one alignment, fields as in bam1_core_
 		return p && p[0] == 'Z' ? (const char *)(p + 1) : nullptr;
 	}
 	// bam_get_num_tag (clib/bam_file.c:456-468): integer codes only
-	bool num_tag(const char tag[2], int32_t *num) const
-	{
-		const uint8_t *p = aux_get(tag);
-		if (!p) return false;
-		switch ((char)p[0]) {
-		case 'c': *num = (int8_t)p[1]; return true;
-		case 'C': *num = p[1]; return true;
-		case 's': *num = (int16_t)(p[1] | (uint16_t)p[2] << 8); return true;
-		case 'S': *num = (uint16_t)(p[1] | (uint16_t)p[2] << 8); return true;
-		case 'i': case 'I': *num = (int32_t)(p[1] | (uint32_t)p[2] << 8 | (uint32_t)p[3] << 16 | (uint32_t)p[4] << 24); return true;
-		default: return false;
-		}
-	}
+	bool num_tag(const char tag[2], int32_t *num) const { return bam_aux_int(aux_get(tag), num); }
 };
+
+// the fixed part of a record (h: its first 36 bytes, block_size first) into r's fields
+inline void bam_record_head(const uint8_t *h, BamRecord &r)
+{
+	r.tid = bam_i32(h + 4), r.pos = bam_i32(h + 8);
+	r.l_qname = h[12], r.mapq = h[13];
+	r.n_cigar = bam_u16(h + 16), r.flag = bam_u16(h + 18);
+	r.l_qseq = bam_i32(h + 20), r.mtid = bam_i32(h + 24), r.mpos = bam_i32(h + 28), r.isize = bam_i32(h + 32);
+}
+// what BamReader::next asks of a record whose head and data are there: null, or what is wrong with it
+inline const char *bam_record_check(const uint8_t *h, const BamRecord &r)
+{
+	if (!bam_rec_fields_inside(h)) return "bad BAM record";
+	if (r.l_qname == 0 || r.data[(size_t)r.l_qname - 1] != 0) return "bad BAM record (read name not NUL-terminated)";   // qname() is used as a C string
+	return nullptr;
+}
+// a BamRecord from a record's bytes (block_size first, `avail` bytes are there), by the reader's rules: null, or what is wrong with it
+inline const char *bam_record_from_bytes(const uint8_t *rec, size_t avail, BamRecord &r)
+{
+	if (avail < 4 || bam_i32(rec) < (int32_t)kBamRecMinBlock) return "bad BAM record";
+	if (avail - 4 < (size_t)bam_u32(rec)) return "truncated BAM record";
+	bam_record_head(rec, r);
+	r.data.assign(rec + kBamRecHead, rec + 4 + (size_t)bam_u32(rec));
+	return bam_record_check(rec, r);
+}
 
 class BamReader {
 	BgzfReader z;
@@ -431,14 +408,10 @@ public:
 		const int32_t block = bam_i32(h);
 		if (block < (int32_t)kBamRecMinBlock) { err = "bad BAM record"; return false; }
 		if (!z.read(h + 4, 32)) { err = "truncated BAM record"; return false; }
-		r.tid = bam_i32(h + 4), r.pos = bam_i32(h + 8);
-		r.l_qname = h[12], r.mapq = h[13];
-		r.n_cigar = bam_u16(h + 16), r.flag = bam_u16(h + 18);
-		r.l_qseq = bam_i32(h + 20), r.mtid = bam_i32(h + 24), r.mpos = bam_i32(h + 28), r.isize = bam_i32(h + 32);
+		bam_record_head(h, r);
 		r.data.resize((size_t)block - 32);
 		if (block > 32 && !z.read(r.data.data(), (size_t)block - 32)) { err = "truncated BAM record"; return false; }
-		if (!bam_rec_fields_inside(h)) { err = "bad BAM record"; return false; }
-		if (r.l_qname == 0 || r.data[(size_t)r.l_qname - 1] != 0) { err = "bad BAM record (read name not NUL-terminated)"; return false; }   // qname() is used as a C string
+		if (const char *bad = bam_record_check(h, r)) { err = bad; return false; }
 		return true;
 	}
 };

@@ -14,6 +14,7 @@
 //   the fields     bam_rec_derived(rec, &m): tid, pos, end, len, bin and flag as the sorter, the store's table and the .bai builder use them
 //   the validity   bam_rec_frame -> bam_rec_cigar_inside (the formatter's rule) or bam_rec_reader_fits -> bam_rec_name_ends (the reader's);
 //                  every layer reads only what the layers before it have vouched for
+//   the tags       bam_aux_find(aux begin, aux end, t0, t1): the reader's bam_aux_get walk with its size rules; bam_aux_int: the integer codes
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -115,5 +116,55 @@ PSVR_BR bool bam_rec_reader_fits(const uint8_t *rec, uint32_t bs) { return bam_r
 PSVR_BR bool bam_rec_reader_fits(const uint8_t *rec) { return bam_rec_reader_fits(rec, bam_u32(rec)); }
 // The name's NUL (the reader's again: the name is used as a C string), of a record that is there and passes bam_rec_reader_fits
 PSVR_BR bool bam_rec_name_ends(const uint8_t *rec) { return rec[kBamRecHead + rec[12] - 1] == 0; }
+
+// ---- the optional fields [p, e) behind the qualities (SAMv1 section 4.2.4)
+// bam_aux_get: the type byte of tag t0 t1, or null.  The walk ends with "not found" at an unknown type and at a value that leaves [p, e)
+// (Z / H: its NUL included), so whoever reads the value it returns stays inside the record.
+PSVR_BR const uint8_t *bam_aux_find(const uint8_t *p, const uint8_t *e, char t0, char t1)
+{
+	while (e - p >= 3) {
+		const bool hit = p[0] == (uint8_t)t0 && p[1] == (uint8_t)t1;
+		const uint8_t *v = p + 2, *val = v + 1;
+		uint64_t sz = 0;
+		switch ((char)v[0]) {
+		case 'A': case 'c': case 'C': sz = 1; break;
+		case 's': case 'S': sz = 2; break;
+		case 'i': case 'I': case 'f': sz = 4; break;
+		case 'd': sz = 8; break;
+		case 'Z': case 'H': {
+			const uint8_t *q = val;
+			while (q < e && *q) ++q;
+			if (q >= e) return nullptr;                          // no terminator inside the record
+			sz = (uint64_t)(q - val) + 1;
+			break;
+		}
+		case 'B': {
+			if (e - val < 5) return nullptr;
+			const char st = (char)val[0];
+			const uint32_t cnt = bam_u32(val + 1);
+			sz = 5 + (uint64_t)((st == 'c' || st == 'C') ? 1 : (st == 's' || st == 'S') ? 2 : 4) * cnt;
+			break;
+		}
+		default: return nullptr;
+		}
+		if (sz > (uint64_t)(e - val)) return nullptr;            // the value runs past the record
+		if (hit) return v;
+		p = val + sz;
+	}
+	return nullptr;
+}
+// bam_get_num_tag (clib/bam_file.c:456-468) of a type byte bam_aux_find returned: the six integer codes only
+PSVR_BR bool bam_aux_int(const uint8_t *v, int32_t *num)
+{
+	if (!v) return false;
+	switch ((char)v[0]) {
+	case 'c': *num = (int8_t)v[1]; return true;
+	case 'C': *num = v[1]; return true;
+	case 's': *num = (int16_t)bam_u16(v + 1); return true;
+	case 'S': *num = bam_u16(v + 1); return true;
+	case 'i': case 'I': *num = bam_i32(v + 1); return true;
+	}
+	return false;
+}
 
 } // namespace psvr

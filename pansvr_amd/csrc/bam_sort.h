@@ -25,6 +25,7 @@
 #include <functional>
 #include <future>
 #include "bam_reader.h"
+#include "bgzf_pieces.h"
 #include "name_key.h"
 #include "sorted_bam.h"
 #include "sort_store_sink.h"
@@ -54,59 +55,26 @@ template <class Backend> int sort_device_route(Backend &be, const std::string &i
 	}
 	FILE *f = fopen(in_fn.c_str(), "rb");
 	if (!f) return left("opening the input", "cannot open " + in_fn);
-	struct Closer { FILE *f; Backend &be; uint8_t *buf[2]; ~Closer() { fclose(f); for (uint8_t *b : buf) if (b) be.host_free(b); be.store_destroy(); } } guard{f, be, {nullptr, nullptr}};
-	// the first member to send is the one that holds the first record's first byte; `skip` bytes of it are the header's
-	long long first_off = 0, cum = 0, skip = 0;
-	for (std::vector<uint8_t> h(12 + 65536);;) {
-		const size_t k = fread(h.data(), 1, 12, f);
-		if (k == 0) break;                                       // (the header ends the file: no member to send)
-		uint32_t bsize = 0, xlen = k == 12 ? h[10] | (uint32_t)h[11] << 8 : 0;
-		uint8_t t[4];
-		if (k != 12 || fread(h.data() + 12, 1, xlen, f) != xlen || bgzf_member_header(h.data(), 12 + (uint64_t)xlen, &bsize, &xlen) != 0 || fseek(f, first_off + bsize - 4, SEEK_SET) != 0 ||
-		    fread(t, 1, 4, f) != 4)
-			return left("finding the first record's member", "not a whole BGZF block");
-		const long long isize = t[0] | (uint32_t)t[1] << 8 | (uint32_t)t[2] << 16 | (uint32_t)t[3] << 24;
-		if (cum + isize > (long long)header_bytes) { skip = (long long)header_bytes - cum; break; }
-		cum += isize, first_off += bsize;
-	}
-	if (fseek(f, first_off, SEEK_SET) != 0) return left("finding the first record's member", "seek");
+	struct Closer { FILE *f; Backend &be; ~Closer() { fclose(f); be.store_destroy(); } } guard{f, be};
+	// the first member to send is the one that holds the first record's first byte; `skip` bytes of it are the header's (bgzf_pieces.h)
+	PieceFail fail;
+	long long skip = 0;
+	if (!bgzf_seek_first_record(f, header_bytes, &skip, &fail)) return left(fail.call.c_str(), fail.why);
 	if (be.store_create()) return left("store create", be.last_error());
-	// pieces of PSVR_INFLATE_BATCH compressed bytes (bam_reader.h's batch); what lies behind a piece's last whole member (less than a member:
-	// below 64 KiB) is put in front of the next piece, which a second thread reads while the call runs
-	const char *e_piece = getenv("PSVR_INFLATE_BATCH");
-	const size_t piece = e_piece && atoll(e_piece) >= 1 ? (size_t)atoll(e_piece) : (size_t)16 << 20, front = 65536;
-	for (uint8_t *&b : guard.buf) if (!(b = (uint8_t *)be.host_alloc(front + piece))) return left("host_alloc", be.last_error());
-	auto read_piece = [&](int b) { return fread(guard.buf[b] + front, 1, piece, f); };
 	auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
 	const double t0 = now();
 	long long members_in = 0;
-	size_t carry = 0, got = read_piece(0);
-	bool first = true;
-	for (int cur = 0;; cur ^= 1) {
-		const bool eof = got < piece;
-		uint8_t *p = guard.buf[cur] + front - carry;
-		const size_t have = carry + got;
-		std::future<size_t> next;
-		if (!eof) next = std::async(std::launch::async, read_piece, cur ^ 1);
-		int64_t used = 0, bad = -1;
-		const int rc = have ? be.store_append_bgzf(p, (int64_t)have, first ? skip : 0, (int32_t)refs.size(), &used, &bad) : 0;
-		const std::string why = rc ? be.last_error() : "";
-		if (!eof) got = next.get();                              // (the reader is through before anything is given up)
-		if (rc) return left("append_bgzf", why);
-		for (size_t at = 0; at < (size_t)used;) {                // the members the call took, for the statistics line
+	const bool walked = bgzf_for_pieces(be, f, skip, &fail, [&](const uint8_t *p, size_t have, long long skip_now, int64_t *used, PieceFail *why) {
+		int64_t bad = -1;
+		if (be.store_append_bgzf(p, (int64_t)have, skip_now, (int32_t)refs.size(), used, &bad)) { *why = {"append_bgzf", be.last_error()}; return false; }
+		for (size_t at = 0; at < (size_t)*used;) {               // the members the call took, for the statistics line
 			uint32_t bsize = 0, xlen = 0;
-			if (bgzf_member_header(p + at, (uint64_t)used - at, &bsize, &xlen) != 0) break;
+			if (bgzf_member_header(p + at, (uint64_t)*used - at, &bsize, &xlen) != 0) break;
 			at += bsize, ++members_in;
 		}
-		if (used > 0) first = false;
-		carry = have - (size_t)used;
-		if (eof) {
-			if (carry) return left("reading the input", carry < 18 ? "not a BGZF block" : "truncated BGZF block");
-			break;
-		}
-		if (carry >= front) return left("reading the input", "a BGZF block of more than 64 KiB");
-		memcpy(guard.buf[cur ^ 1] + front - carry, p + used, carry);
-	}
+		return true;
+	});
+	if (!walked) return left(fail.call.c_str(), fail.why);
 	psvr_bam_chain_info_t ci;
 	if (be.store_chain_info(&ci)) return left("chain_info", be.last_error());
 	if (ci.tail_bytes) return left("the end of the input", "truncated BAM stream: the file ends " + std::to_string((long long)ci.tail_bytes) + " bytes into a record");

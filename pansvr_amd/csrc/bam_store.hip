@@ -44,32 +44,7 @@
 #include "bam_record.h"
 #include "bam_chain_device.h"
 #include "copy_aligned_device.h"
-
-struct psvr_bam_store {
-	int device = 0;
-	size_t chunk_bytes = 0;                                  // what a fresh chunk holds (a longer append gets a chunk of its own size)
-	std::vector<std::unique_ptr<psvr::DevBuf>> chunks;       // the records; the last one is being filled
-	psvr::DevBuf addr, meta, key;                            // the table, in append order: uint64 address, psvr_bam_rec_meta_t, uint64 key
-	long long cap_rec = 0;
-	psvr::DevBuf ctl;                                        // long long: {records, bytes of the last chunk in use, bytes in all, refused, a position outside the key's range}
-	long long *h_ctl = nullptr;                              // page-locked read-back of ctl
-	long long n_rec = 0, fill = 0, n_bytes = 0;              // the host's copies, exact when `exact`
-	long long rec_upper = 0, fill_upper = 0;                 // never below what the device holds
-	bool exact = true, key_exact = true, bad = false, keys_spent = false;
-	int ordered = 0;                                         // 1: by samtools' coordinate key, 2: by name
-	psvr::DevBuf cnt, off, tmp, poff;                        // an append's scratch: records per pair, their scan, the scan's scratch, a host append's offsets
-	psvr::SortScratch S;                                     // order
-	std::vector<uint32_t> h_hist;
-	psvr::DevBuf g_src, smeta, slen, rank_off;               // per sorted rank: address, meta, length, exclusive scan of the lengths (n + 1)
-	std::vector<long long> h_rank_off;
-	// append_bgzf: the tail lies in the last chunk at [fill, fill + tail); the rest is a call's scratch
-	long long tail = 0, seg_bytes = 0;
-	psvr_bam_chain_info_t chain = {0, 0, 0, 0, 0};
-	psvr::DevBuf zin, zmem, zstatus, cseg, centry, ccnt, cres;
-	std::vector<psvr::InfMember> h_mem;                      // (what asynchronous copies touch on the host lives as long as the store)
-	std::vector<int32_t> h_status;
-	psvr::ChainResult *h_res = nullptr;                      // page-locked, behind h_ctl's entries
-};
+#include "bam_store_run.h"
 
 namespace psvr {
 
@@ -257,6 +232,31 @@ __global__ __launch_bounds__(256) void k_store_gather(const uint64_t *__restrict
 	}
 }
 
+// drop: the table's entries [n_front, n) slide to the front of its other half, index counting from the first one kept; the dropped records'
+// bytes are added up into ctl[5]
+__global__ __launch_bounds__(256) void k_store_slide(const uint64_t *addr, const psvr_bam_rec_meta_t *meta, const uint64_t *key, long long n_front, long long n, uint64_t *addr2,
+                                                     psvr_bam_rec_meta_t *meta2, uint64_t *key2, long long *ctl)
+{
+	__shared__ unsigned long long sum;
+	if (threadIdx.x == 0) sum = 0;
+	__syncthreads();
+	unsigned long long mine = 0;
+	for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+		psvr_bam_rec_meta_t m = meta[i];
+		if (i < n_front) { mine += m.len; continue; }
+		m.index = (uint32_t)(i - n_front);
+		addr2[i - n_front] = addr[i], meta2[i - n_front] = m, key2[i - n_front] = key[i];
+	}
+	if (mine) atomicAdd(&sum, mine);
+	__syncthreads();
+	if (threadIdx.x == 0 && sum) atomicAdd((unsigned long long *)&ctl[5], sum);
+}
+__global__ void k_store_dropped(long long *ctl, long long n_front)
+{
+	if (ctl[3] != 0) return;
+	ctl[0] -= n_front, ctl[2] -= ctl[5];
+}
+
 // ---- host side: everything below runs under DfwCtx's mutex, on its stream, bound to the store's device
 static int st_bad()
 {
@@ -281,14 +281,17 @@ static int st_refresh(psvr_bam_store *st, DfwCtx &c, bool wait)   // the counts 
 	st->key_exact = st->h_ctl[4] == 0, st->exact = true;
 	return PSVR_OK;
 }
+int store_refresh(psvr_bam_store *st, DfwCtx &c, bool wait) { return st_refresh(st, c, wait); }
 // a chunk whose room behind `used` holds `need` bytes: the last one, or a fresh one (nothing stored moves)
 static int st_chunk(psvr_bam_store *st, DfwCtx &c, long long used, long long need)
 {
 	if (!st->chunks.empty() && (long long)st->chunks.back()->bytes - used >= need) return PSVR_OK;
-	std::unique_ptr<DevBuf> b(new DevBuf);
+	std::unique_ptr<DevBuf> b;
 	// (whole 8-byte words: k_name_chunk loads the aligned words that a name touches, also of a record that ends with its name at the chunk's end)
 	const size_t n = (((size_t)need > st->chunk_bytes ? (size_t)need : st->chunk_bytes) + 7) / 8 * 8;
-	if (b->alloc(n) != hipSuccess) {
+	if (st->spare && st->spare->bytes >= n) b = std::move(st->spare);   // (what psvr_bam_store_drop kept)
+	else b.reset(new DevBuf);
+	if (!b->p && b->alloc(n) != hipSuccess) {
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "psvr_bam_store: device allocation failed for a chunk of %zu bytes (%lld bytes of records are stored)", n, st->n_bytes);
 	}
@@ -745,5 +748,68 @@ extern "C" int psvr_bam_store_download(psvr_bam_store_t *st, void *bytes, int64_
 		a = b;
 	}
 	drain.armed = false;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_store_drop(psvr_bam_store_t *st, int64_t n_front)
+{
+	if (psvr_device_count() <= 0) return st_no_device();
+	if (!st) return set_error(PSVR_ERR_ARG, "psvr_bam_store_drop: null argument");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, st->device)) return rc;
+	if (int rc = st_refresh(st, c, true)) return rc;
+	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_bam_store_drop: the store has been ordered: its sorted table names every record");
+	if (n_front < 0 || n_front > st->n_rec) return set_error(PSVR_ERR_ARG, "psvr_bam_store_drop: %lld records of %lld", (long long)n_front, st->n_rec);
+	if (n_front == 0) return PSVR_OK;
+	const long long n = st->n_rec;
+	if (st->addr2.ensure((size_t)st->cap_rec * 8) || st->meta2.ensure((size_t)st->cap_rec * sizeof(psvr_bam_rec_meta_t)) || st->key2.ensure((size_t)st->cap_rec * 8)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_bam_store_drop: device allocation failed for the table of %lld records (%zu bytes); nothing was dropped", st->cap_rec, (size_t)st->cap_rec * 48);
+	}
+	// the first record kept says which chunks are free: records lie in the chunks in append order
+	st->h_ctl[6] = 0;                                            // (page-locked, behind what st_refresh reads back)
+	if (n_front < n) PSVR_HIP(hipMemcpyAsync(st->h_ctl + 6, st->addr.as<uint64_t>() + n_front, 8, hipMemcpyDeviceToHost, c.stream));
+	long long *ctl = st->ctl.as<long long>();
+	PSVR_HIP(hipMemsetAsync(ctl + 5, 0, 8, c.stream));
+	const long long g = (n + 255) / 256;
+	hipLaunchKernelGGL(k_store_slide, dim3((unsigned)(g < 1024 ? g : 1024)), dim3(256), 0, c.stream, (const uint64_t *)st->addr.p, (const psvr_bam_rec_meta_t *)st->meta.p, (const uint64_t *)st->key.p,
+	                   (long long)n_front, n, st->addr2.as<uint64_t>(), st->meta2.as<psvr_bam_rec_meta_t>(), st->key2.as<uint64_t>(), ctl);
+	hipLaunchKernelGGL(k_store_dropped, dim3(1), dim3(1), 0, c.stream, ctl, (long long)n_front);
+	st->exact = false;
+	int rc = hipGetLastError() == hipSuccess ? PSVR_OK : set_error(PSVR_ERR_DEVICE, "psvr_bam_store_drop: launch failed");
+	if (!rc) rc = st_refresh(st, c, true);
+	if (!rc && st->n_rec != n - n_front) rc = set_error(PSVR_ERR_DEVICE, "psvr_bam_store_drop: the table holds %lld records, %lld were to stay", st->n_rec, n - (long long)n_front);
+	if (rc) { st->bad = true; return rc; }
+	const uint64_t first_kept = (uint64_t)st->h_ctl[6];
+	++st->generation;
+	std::swap(st->addr.p, st->addr2.p), std::swap(st->addr.bytes, st->addr2.bytes);
+	std::swap(st->meta.p, st->meta2.p), std::swap(st->meta.bytes, st->meta2.bytes);
+	std::swap(st->key.p, st->key2.p), std::swap(st->key.bytes, st->key2.bytes);
+	// every chunk in front of the first record kept's -- without one: in front of the chunk being filled, which also holds a pending tail
+	size_t keep_from = st->chunks.empty() ? 0 : st->chunks.size() - 1;
+	if (st->n_rec > 0)
+		for (size_t k = 0; k < st->chunks.size(); ++k) {
+			const uint64_t b = (uint64_t)(uintptr_t)st->chunks[k]->p;
+			if (first_kept >= b && first_kept < b + st->chunks[k]->bytes) { keep_from = k; break; }
+		}
+	const size_t standard = (st->chunk_bytes + 7) / 8 * 8;
+	for (size_t k = 0; k < keep_from; ++k)
+		if (!st->spare && st->chunks[k]->bytes == standard) st->spare = std::move(st->chunks[k]);
+	st->chunks.erase(st->chunks.begin(), st->chunks.begin() + (long)keep_from);   // (the others free themselves)
+	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_store_footprint(psvr_bam_store_t *st, int64_t *chunks, int64_t *bytes)
+{
+	if (psvr_device_count() <= 0) return st_no_device();
+	if (!st) return set_error(PSVR_ERR_ARG, "psvr_bam_store_footprint: null argument");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	long long n = 0, b = 0;
+	for (auto &ch : st->chunks) ++n, b += (long long)ch->bytes;
+	if (st->spare) ++n, b += (long long)st->spare->bytes;
+	if (chunks) *chunks = n;
+	if (bytes) *bytes = b;
 	return PSVR_OK;
 }

@@ -29,6 +29,7 @@
 #include "aln_pipeline.h"
 #include "index_build.h"
 #include "signal_step.h"
+#include "signal_device_route.h"
 #include "bam_sort.h"
 #include "sorted_bam.h"
 #include "bgzf_stream_sink.h"
@@ -405,6 +406,29 @@ struct SortCmdBackend : StoreCalls {
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
 };
+// `panSVR signal -N --signal-device` (signal_device_route.h): the store filled from the file's own members, and psvr_signal_* over it
+struct SignalCmdBackend {
+	const int device;
+	psvr_bam_store_t *store = nullptr;
+	psvr_signal_t *sg = nullptr;
+	explicit SignalCmdBackend(int dev) : device(dev) {}
+	int store_create() { return psvr_bam_store_create(device, &store); }
+	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
+	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
+	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
+	int store_drop(int64_t n) { return psvr_bam_store_drop(store, n); }
+	int store_footprint(int64_t *chunks, int64_t *bytes) { return psvr_bam_store_footprint(store, chunks, bytes); }
+	int signal_create(const psvr_signal_opt_t *o) { return psvr_signal_create(device, o, &sg); }
+	void signal_destroy() { if (sg) psvr_signal_destroy(sg), sg = nullptr; }
+	int signal_run(int64_t first, int finish, psvr_signal_info_t *i) { return psvr_signal_run(sg, store, first, finish, i); }
+	int signal_text(void *t, int64_t cap) { return psvr_signal_text(sg, t, cap); }
+	int signal_pairs(psvr_signal_pair_t *t, int64_t cap) { return psvr_signal_pairs(sg, t, cap); }
+	int signal_side(void *b, int64_t cap) { return psvr_signal_side(sg, b, cap); }
+	int signal_stats(uint64_t *isize_n, uint64_t *len_n) { return psvr_signal_stats(sg, isize_n, len_n); }
+	const char *last_error() { return psvr_last_error(); }
+	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
+	void host_free(void *p) { psvr_host_free(p); }
+};
 struct SortMainSink : aln::MainSink {
 	SortStoreSink<SortBackend> &k;
 	explicit SortMainSink(SortStoreSink<SortBackend> &sink) : k(sink) {}
@@ -455,7 +479,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -493,6 +517,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1015: o.emit_device = o.parse_device = true; break;
 		case 1017: o.sort_device = o.sort = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
+		case 1018: fprintf(stderr, "[panSVR-amd] --signal-device is `panSVR signal -N`'s route to FASTQ text: ignored by aln (a *.bam read file hands its pairs over on the host threads)\n"); break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -668,7 +693,10 @@ static int aln_main(int argc, char **argv)
 int main(int argc, char **argv)
 {
 	if (argc >= 2 && !strcmp(argv[1], "index")) return index_main(argc, argv);
-	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv);
+	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv, [](psvr::SignalStep &S, long long *pairs_done) {
+			SignalCmdBackend be(0);
+			return psvr::signal_device_route(be, S, pairs_done);
+		});
 	if (argc >= 2 && !strcmp(argv[1], "sort"))
 		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name) {
 			SortCmdBackend be(0);

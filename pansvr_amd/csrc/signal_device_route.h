@@ -1,0 +1,184 @@
+// signal_device_route.h -- `panSVR signal -N --signal-device`: the name-sorted signal step with its records in GPU memory.  Host C++ only, a
+// template over the backend, as bam_sort.h's sort_device_route is: cli_main.cpp has the product's (psvr_bam_store_* and psvr_signal_*);
+// tests/tools/signal_device_route_check.cpp has one that keeps the store in host memory and runs the rules of signal_device.h with one lane,
+// so every rule in here runs without a GPU (tests/test_signal_device_route.py).
+//
+// The file's own BGZF members go to the device a piece of PSVR_INFLATE_BATCH compressed bytes at a time (bgzf_pieces.h).  Per piece:
+//   store_append_bgzf     the members inflated into the record store, the records found there
+//   signal_run            from the first record no earlier run consumed: pairs, states, notes, text (include/psvr_engine.h)
+//   signal_pairs / text / side   the per-pair table, the text and -- in one piece -- the records of the pairs the host has to look at come back;
+//                         the state-1 ranges go to S.out in pair order, a state-2 pair is formatted by SignalStep::pair from its downloaded
+//                         records at its place; the wrong-ISIZE lines and the progress lines
+//   store_drop            everything the run consumed ceases to exist: the store holds a piece's records and a carried one, whatever the file's length
+// A pair in an error state (3, 4, 5): what lies in front of it is written and flushed, the device objects are destroyed, the host route's
+// message for that state is printed, and the state is returned: SignalStep::run calls abort() on it as the host loop does.
+// Leaving the route: a backend call fails, there is no device, the input is a pipe, a member is corrupt, a record is malformed, the end is
+// truncated -- one line names the call and the reason, *pairs_done says how many pairs' text is on S.out, and -1 is returned: SignalStep::run
+// reads the file from its beginning on the host route, muted for those pairs, so the statistics, the messages and the exit status are the
+// host route's by construction.  0: done; S.bs holds the device's histograms and the count, the caller prints the last line.
+//
+// What a backend offers (every int is 0 or a status whose text last_error() gives):
+//   int store_create() / void store_destroy() / int store_append_bgzf(const void *, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad_member)
+//   int store_chain_info(psvr_bam_chain_info_t *) / int store_drop(int64_t n_front) / int store_footprint(int64_t *chunks, int64_t *bytes)
+//   int signal_create(const psvr_signal_opt_t *) / void signal_destroy() / int signal_run(int64_t first_record, int finish, psvr_signal_info_t *)
+//   int signal_text(void *, int64_t cap) / int signal_pairs(psvr_signal_pair_t *, int64_t cap)
+//   int signal_side(void *bytes, int64_t cap) / int signal_stats(uint64_t *isize_n, uint64_t *len_n)
+//   void *host_alloc(size_t) / void host_free(void *) / const char *last_error()
+#pragma once
+#include <sys/stat.h>
+#include <string>
+#include <vector>
+#include "../../include/psvr_engine.h"
+#include "bgzf_pieces.h"
+#include "signal_step.h"
+
+namespace psvr {
+
+struct SignalRouteStats { long long pairs = 0, written = 0, declined = 0, runs = 0, text_bytes = 0, peak_chunks = 0, peak_bytes = 0; };
+
+inline psvr_signal_opt_t signal_device_options(const SignalStep &S)
+{
+	psvr_signal_opt_t o;
+	o.gap_open = S.o.gap_open, o.gap_ex = S.o.gap_ex, o.gap_open2 = S.o.gap_open2, o.gap_ex2 = S.o.gap_ex2, o.match = S.o.match, o.mismatch = S.o.mismatch;
+	o.max_tid = S.o.max_tid, o.not_use_filter = S.o.not_use_filter, o.discard_full_match = S.o.discard_full_match, o.isize_min = S.isize_min, o.isize_max = S.isize_max;
+	o.stat[0] = S.bs.read_len, o.stat[1] = (int32_t)S.bs.min_i, o.stat[2] = (int32_t)S.bs.mid_i, o.stat[3] = (int32_t)S.bs.max_i;
+	return o;
+}
+
+template <class Backend> int signal_device_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr)
+{
+	*pairs_done = 0;
+	SignalRouteStats R;
+	auto left = [&](const std::string &call, const std::string &why) {
+		fprintf(stderr, "[panSVR-amd] signal --signal-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
+		        *pairs_done);
+		return -1;
+	};
+	struct stat sb;
+	if (S.o.input == "-" || stat(S.o.input.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return left("opening the input", "a pipe cannot be read twice");
+	size_t header_bytes = 0, n_ref = 0;
+	{
+		BamReader rd;                                            // the serial reader: how many inflated bytes the header took
+		if (!rd.open(S.o.input.c_str())) return left("reading the header", rd.error());
+		header_bytes = rd.header_bytes, n_ref = rd.refs.size();
+	}
+	FILE *f = fopen(S.o.input.c_str(), "rb");
+	if (!f) return left("opening the input", "cannot open " + S.o.input);
+	struct Closer {
+		FILE *f; Backend &be; uint8_t *text, *side;
+		~Closer() { fclose(f); if (text) be.host_free(text); if (side) be.host_free(side); be.signal_destroy(); be.store_destroy(); }
+	} guard{f, be, nullptr, nullptr};
+	PieceFail fail;
+	long long skip = 0;
+	if (!bgzf_seek_first_record(f, header_bytes, &skip, &fail)) return left(fail.call, fail.why);
+	if (be.store_create()) return left("store create", be.last_error());
+	const psvr_signal_opt_t opt = signal_device_options(S);
+	if (be.signal_create(&opt)) return left("signal create", be.last_error());
+	size_t text_cap = 0, side_cap = 0;
+	std::vector<psvr_signal_pair_t> tab;
+	int64_t side_bytes = 0;
+	long long total = 0;                                         // S.bs.total of the host loop: two per pair
+	int error_state = 0;
+	bool any_written = false;
+	// the two records of pair p of the last run as the host's reader holds them, out of the run's side records
+	auto fetch = [&](int64_t p, BamRecord *a, BamRecord *b, PieceFail *why) {
+		const int64_t at = tab[(size_t)p].side_off;
+		const char *bad = at < 0 || at > side_bytes ? "the pair has no side records" : bam_record_from_bytes(guard.side + at, (size_t)(side_bytes - at), *a);
+		const size_t n1 = bad ? 0 : 4 + (size_t)bam_u32(guard.side + at);
+		if (!bad) bad = bam_record_from_bytes(guard.side + at + n1, (size_t)(side_bytes - at) - n1, *b);
+		if (bad) { *why = {"signal side", bad}; return false; }
+		return true;
+	};
+	// a page-locked buffer of at least n bytes
+	auto room = [&](uint8_t **buf, size_t *cap, size_t n, PieceFail *why) {
+		if (n <= *cap) return true;
+		if (*buf) be.host_free(*buf), *buf = nullptr, *cap = 0;
+		if (!(*buf = (uint8_t *)be.host_alloc(n + n / 4))) { *why = {"host_alloc", be.last_error()}; return false; }
+		*cap = n + n / 4;
+		return true;
+	};
+	auto write_out = [&](const uint8_t *p, size_t n) { if (n) fwrite(p, 1, n, S.out); };
+	const bool walked = bgzf_for_pieces(be, f, skip, &fail, [&](const uint8_t *p, size_t have, long long skip_now, int64_t *used, PieceFail *why) {
+		int64_t bad = -1;
+		if (be.store_append_bgzf(p, (int64_t)have, skip_now, (int32_t)n_ref, used, &bad)) { *why = {"append_bgzf", be.last_error()}; return false; }
+		int64_t chunks = 0, bytes = 0;
+		if (be.store_footprint(&chunks, &bytes)) { *why = {"store footprint", be.last_error()}; return false; }
+		if (chunks > R.peak_chunks) R.peak_chunks = chunks;
+		if (bytes > R.peak_bytes) R.peak_bytes = bytes;
+		psvr_signal_info_t info;
+		// (the store's front is what no run has consumed: a lone last primary record and what lies behind it)
+		if (be.signal_run(0, 0, &info)) { *why = {"signal run", be.last_error()}; return false; }
+		++R.runs;
+		tab.resize((size_t)info.pairs);
+		if (info.pairs && be.signal_pairs(tab.data(), info.pairs)) { *why = {"signal pairs", be.last_error()}; return false; }
+		if (!room(&guard.text, &text_cap, (size_t)info.text_bytes, why) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
+		if (info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
+		if (info.side_bytes && be.signal_side(guard.side, (int64_t)side_cap)) { *why = {"signal side", be.last_error()}; return false; }
+		side_bytes = info.side_bytes;
+		// the pairs in order: text ranges of state-1 pairs as they lie, a state-2 pair from the host formatter at its place
+		const int64_t n_front = info.first_error >= 0 ? info.first_error : info.pairs;
+		int64_t flushed = 0;                                     // text bytes of this run that are on S.out
+		BamRecord a, b;
+		auto flush_to = [&](int64_t q) {                         // the text in front of pair q is on S.out, and *pairs_done says so
+			const int64_t upto = q < info.pairs ? tab[(size_t)q].text_off : info.text_bytes;
+			write_out(guard.text + flushed, (size_t)(upto - flushed)), flushed = upto;
+			*pairs_done = R.pairs + q;
+		};
+		for (int64_t q = 0; q < n_front; ++q) {
+			const psvr_signal_pair_t &t = tab[(size_t)q];
+			total += 2;
+			if (total % 100000 == 0) fprintf(stderr, "%ld\r", (long)total);
+			if (t.state == 2) {
+				flush_to(q);
+				if (!fetch(q, &a, &b, why)) return false;
+				S.stat_written = any_written;
+				S.pair(a, b, true);
+				any_written = true, ++R.declined;
+				*pairs_done = R.pairs + q + 1;
+				continue;
+			}
+			if (t.note & 1) {
+				flush_to(q);
+				if (!fetch(q, &a, &b, why)) return false;
+				fprintf(stderr, " wrong ISIZE: %d  %d \n", a.isize, b.isize);
+			}
+			if (t.state == 1) any_written = true, ++R.written;
+		}
+		flush_to(n_front);
+		R.pairs += n_front, R.text_bytes += info.text_bytes;
+		if (info.first_error >= 0) {                             // the pair the host loop aborts on
+			const psvr_signal_pair_t &t = tab[(size_t)info.first_error];
+			fflush(S.out);
+			error_state = t.state;
+			std::string n1 = "?", n2 = "?";
+			int i1 = 0, i2 = 0;
+			PieceFail ignored;
+			if (fetch(info.first_error, &a, &b, &ignored)) n1 = a.qname(), n2 = b.qname(), i1 = a.isize, i2 = b.isize;
+			if (t.state == 3) fprintf(stderr, "[panSVR-amd] signal: consecutive records [%s] [%s] are not a pair: is the input sorted by name?\n", n1.c_str(), n2.c_str());
+			else if (t.state == 4) fprintf(stderr, "[panSVR-amd] signal: records of [%s] are not first/second in template\n", n1.c_str());
+			else {
+				total += 2;
+				if (total % 100000 == 0) fprintf(stderr, "%ld\r", (long)total);
+				if (t.note & 1) fprintf(stderr, " wrong ISIZE: %d  %d \n", i1, i2);
+				fprintf(stderr, "[panSVR-amd] signal: read longer than 2047 bases\n");
+			}
+			*why = {"", ""};
+			return false;
+		}
+		if (be.store_drop(info.consumed)) { *why = {"store drop", be.last_error()}; return false; }
+		return true;
+	});
+	if (error_state) return error_state;
+	if (!walked) return left(fail.call, fail.why);
+	psvr_bam_chain_info_t ci;
+	if (be.store_chain_info(&ci)) return left("chain_info", be.last_error());
+	if (ci.tail_bytes) return left("the end of the input", "truncated BAM stream: the file ends " + std::to_string((long long)ci.tail_bytes) + " bytes into a record");
+	if (be.signal_stats(S.bs.isize_n.data(), S.bs.len_n.data())) return left("signal stats", be.last_error());
+	S.bs.total = (uint64_t)total;
+	fprintf(stderr, "[panSVR-amd] signal --signal-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld runs, %lld text bytes, peak footprint %lld chunks (%lld bytes)\n", R.pairs, R.written,
+	        R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
+	if (stats) *stats = R;
+	return 0;
+}
+
+} // namespace psvr

@@ -1,6 +1,8 @@
 // signal_step.h -- `panSVR signal` (= the reference's `fc_signal`): BAM -> interleaved FASTQ whose comment carries
-// the original alignment, i.e. the wire format `aln` parses.  Host C++ only (the work is record parsing; nothing here runs on the
-// GPU).  Restated from PanSVgenerateVCF/getSignalRead.cpp / .hpp and the helpers of clib/bam_file.c it calls; PARITY UNPINNED:
+// the original alignment, i.e. the wire format `aln` parses.  Host C++, with one device route: with `-N --signal-device` the records are
+// inflated, paired, judged and formatted in GPU memory (signal_device_route.h over psvr_signal_*).  This file's pair() stays the
+// specification: it formats the few pairs the device declines, and it takes over, muted up to the pairs already written, whenever that route
+// is left.  Restated from PanSVgenerateVCF/getSignalRead.cpp / .hpp and the helpers of clib/bam_file.c it calls; PARITY UNPINNED:
 // the reference's build of this step needs htslib, which cannot be built in this image, so the only checker is the independent
 // restatement in oracle/signal_oracle.py (tests/test_signal.py).
 //
@@ -21,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 #include "bam_reader.h"
@@ -36,6 +39,7 @@ struct SignalOpt {
 	std::string header_fn = "./header.sam", status_fn = "./status.sam", input;
 	int isize_override[3] = {-1, -1, -1};                                                   // --isize MIN,MID,MAX
 	int inflate_device = -1, inflate_threads = 0;                                           // --inflate-device / --inflate-threads N: the batched BGZF reader (bam_reader.h)
+	bool signal_device = false;                                                             // --signal-device: signal_device_route.h (with -N)
 };
 
 struct BamStat {                                            // BAM_STAT, getSignalRead.hpp:33-190
@@ -99,6 +103,10 @@ struct SignalStep {
 	int sample_max = 0;
 	FILE *out = stdout;
 	PairFeed *feed = nullptr;          // fused with `aln`: records go to the batch being built instead of FASTQ text on `out`
+	bool muted = false;                // write_fastq writes nothing: the pair's text is on `out` already (the device route wrote it before it was left)
+	// --signal-device (signal_device_route.h over the caller's backend): 0 done, bs holds the histograms; -1 the route was left with *pairs_done
+	// pairs written; 3, 4, 5: the host route's abort() for a pair in that state is due (the message has been printed)
+	std::function<int(SignalStep &, long long *pairs_done)> signal_device_fn;
 
 	static bool primary(const BamRecord &r) { return !(r.flag & 0x100) && !(r.flag & 0x800); }
 
@@ -156,7 +164,7 @@ struct SignalStep {
 			for (int i = 0; i < half + 1 && len > 0; ++i) { const int ri = len - 1 - i; std::swap(qual[(size_t)i], qual[(size_t)ri]); }
 		}
 		if (feed) feed->put(b.qname(), comment, seq, qual, ori);
-		else fprintf(out, "@%s %s\n%s\n+\n%s\n", b.qname(), comment.c_str(), seq.c_str(), qual.c_str());
+		else if (!muted) fprintf(out, "@%s %s\n%s\n+\n%s\n", b.qname(), comment.c_str(), seq.c_str(), qual.c_str());
 	}
 
 	// all_signal_records_read_pair, :100-256
@@ -417,6 +425,27 @@ struct SignalStep {
 			fwrite(rd.header_text.data(), 1, rd.header_text.size(), h);
 			fclose(h);
 		}
+		long long mute = 0;                                 // pairs whose text the device route has written
+		if (o.signal_device) {
+			const char *no = feed              ? "the fused aln route hands its pairs over on the host"
+			                 : !o.sort_by_name ? "it is the name-sorted mode's route: give -N"
+			                 : o.sample_rate < 0.9999 ? "-R draws rand() per pair in the host loop's order"
+			                 : !signal_device_fn ? "this build has no device route"
+			                                     : nullptr;
+			if (no) fprintf(stderr, "[panSVR-amd] signal --signal-device: refused (%s): the host route runs\n", no);
+			else {
+				const int rc = signal_device_fn(*this, &mute);
+				if (rc > 0) abort();                            // (a pair the host loop aborts on; the route has written what lies in front of it and said why)
+				if (rc == 0) {
+					fflush(out);
+					bs.global();
+					fprintf(stderr, "BAM/CRAM status: ave_read_depth: [%f] read length: [Normal: %d @ %f%%, AVE: %f] ISIZE: [MIN: %d MAX: %d]\n", bs.depth, bs.read_len, bs.normal_percent * 100,
+					        bs.ave_len, bs.min_l2, bs.max_l2);
+					return 0;
+				}
+				bs.reset(), stat_written = false;               // the host route from the file's beginning, muted for the pairs that are written
+			}
+		}
 		if (!o.sort_by_name) {
 			if (!run_pos_sorted(rd)) { fprintf(stderr, "[panSVR-amd] signal: %s\n", rd.error().c_str()); return 1; }
 			fflush(out);
@@ -433,12 +462,14 @@ struct SignalStep {
 			if (!g1 || !g2) break;
 			if (strcmp(b1.qname(), b2.qname())) { fprintf(stderr, "[panSVR-amd] signal: consecutive records [%s] [%s] are not a pair: is the input sorted by name?\n", b1.qname(), b2.qname()); abort(); }
 			if (!(b1.flag & 0x40) || !(b2.flag & 0x80)) { fprintf(stderr, "[panSVR-amd] signal: records of [%s] are not first/second in template\n", b1.qname()); abort(); }
+			muted = (long long)(bs.total / 2) < mute;
 			bs.total += 2;
 			if (bs.total % 100000 == 0) fprintf(stderr, "%ld\r", (long)bs.total);
 			bool used = true;
 			if (o.sample_rate < 0.9999 && rand() > sample_max) used = false;   // signal_be_used, :268-274
 			pair(b1, b2, used);
 		}
+		muted = false;
 		if (!rd.error().empty()) { fprintf(stderr, "[panSVR-amd] signal: %s\n", rd.error().c_str()); return 1; }
 		fflush(out);
 		bs.global();
@@ -448,17 +479,22 @@ struct SignalStep {
 	}
 };
 
-inline int signal_main(int argc, char **argv)
+inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, long long *)> signal_device_fn = nullptr)
 {
 	SignalStep S;
+	S.signal_device_fn = std::move(signal_device_fn);
 	static struct option lo[] = {{"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'}, {"match-score", 1, 0, 'M'},
 	                             {"mis-score", 1, 0, 'm'}, {"max-tid-filter", 1, 0, 'I'}, {"sort-by-name", 0, 0, 'N'}, {"not-ignore-low-q", 0, 0, 'L'}, {"reference", 1, 0, 'r'},
 	                             {"header-file", 1, 0, 'H'}, {"status-file", 1, 0, 'S'}, {"tmp_file_pairing", 1, 0, 't'}, {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'},
-	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {"inflate-device", 0, 0, 1001}, {"inflate-threads", 1, 0, 1002}, {0, 0, 0, 0}};
+	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {"inflate-device", 0, 0, 1001}, {"inflate-threads", 1, 0, 1002}, {"signal-device", 0, 0, 1003}, {0, 0, 0, 0}};
 	static const char *usage = "usage: panSVR signal|fc_signal [-N] [options] <in.bam>  > reads.fq\n"
 	                           "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
 	                           "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
-	                           "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n";
+	                           "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n"
+	                           "         --signal-device        with -N: the records are inflated, paired, judged and formatted in the GPU's memory (device 0), a piece of\n"
+	                           "                                the file at a time; only FASTQ text comes back.  The output, the header file and the status file are those\n"
+	                           "                                of -N.  Whatever the device route cannot do (no device, a pipe, a corrupt or truncated file) is named, and\n"
+	                           "                                the host route reads the file again, silent for the pairs already written.  Not without -N, not with -R\n";
 	int c;
 	optind = 2;
 	while ((c = getopt_long(argc, argv, "O:P:E:F:M:m:I:NLr:H:S:t:DUR:", lo, NULL)) >= 0) {
@@ -479,6 +515,7 @@ inline int signal_main(int argc, char **argv)
 		case 'R': S.o.sample_rate = atof(optarg); break;
 		case 1000: if (sscanf(optarg, "%d,%d,%d", &S.o.isize_override[0], &S.o.isize_override[1], &S.o.isize_override[2]) != 3) { fprintf(stderr, "--isize wants MIN,MID,MAX\n"); return 1; } break;
 		case 1001: S.o.inflate_device = 0; break;
+		case 1003: S.o.signal_device = true; break;
 		case 1002: S.o.inflate_threads = atoi(optarg); if (S.o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		default: fputs(usage, stderr); return 1;
 		}

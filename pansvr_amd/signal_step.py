@@ -1,0 +1,89 @@
+"""`panSVR signal -N` over a device-resident record store (psvr_signal_*, include/psvr_engine.h) through the C ABI: the pairs of a BamStore's
+records judged and formatted as FASTQ text on the device."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import EngineError, check, lib  # noqa: F401
+
+MAX_ISIZE, MAX_LEN = 100000, 1000            # BamStat's two histograms
+
+
+class SignalOpt(C.Structure):  # psvr_signal_opt_t
+    _fields_ = [(n, C.c_int32) for n in ("gap_open", "gap_ex", "gap_open2", "gap_ex2", "match", "mismatch", "max_tid", "not_use_filter", "discard_full_match", "isize_min",
+                                          "isize_max")] + [("stat", C.c_int32 * 4)]
+
+
+class SignalInfo(C.Structure):  # psvr_signal_info_t
+    _fields_ = [(n, C.c_int64) for n in ("pairs", "written", "declined", "first_error", "text_bytes", "consumed", "side_bytes")]
+
+
+PAIR_DTYPE = np.dtype([("text_off", "<i8"), ("rec1", "<i8"), ("rec2", "<i8"), ("side_off", "<i8"), ("bytes", "<i4"), ("state", "u1"), ("note", "u1"), ("pad", "<u2")])   # psvr_signal_pair_t
+
+
+def signal_opt(stat, isize_min, isize_max, not_use_filter=False, discard_full_match=False, max_tid=24, gap_open=16, gap_ex=1, gap_open2=32, gap_ex2=0, match=2, mismatch=12):
+    """the step's options with the command's defaults; stat: the four numbers of STAT_ (read_len, min_i, mid_i, max_i)"""
+    o = SignalOpt(gap_open, gap_ex, gap_open2, gap_ex2, match, mismatch, max_tid, int(not_use_filter), int(discard_full_match), isize_min, isize_max)
+    for k in range(4):
+        o.stat[k] = int(stat[k])
+    return o
+
+
+class Signal:
+    """One psvr_signal_t.  Single-owner."""
+
+    def __init__(self, opt, device=0):
+        self.h = C.c_void_p()
+        lib().psvr_signal_destroy.restype = None
+        check(lib().psvr_signal_create(C.c_int(device), C.byref(opt), C.byref(self.h)))
+        self.info = None
+
+    def run(self, store, first_record=0, finish=False):
+        """the store's records [first_record, n_records) paired, judged and formatted; returns SignalInfo"""
+        i = SignalInfo()
+        check(lib().psvr_signal_run(self.h, store.h, C.c_int64(first_record), C.c_int32(int(finish)), C.byref(i)))
+        self.info = i
+        return i
+
+    def text(self):
+        """the last run's text (bytes): its state-1 pairs in front of the first error pair"""
+        n = self.info.text_bytes if self.info else 0
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        check(lib().psvr_signal_text(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n].tobytes()
+
+    def pairs(self):
+        """the last run's table (PAIR_DTYPE)"""
+        n = self.info.pairs if self.info else 0
+        out = np.zeros(max(n, 1), dtype=PAIR_DTYPE)
+        check(lib().psvr_signal_pairs(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n]
+
+    def side(self):
+        """the last run's side records (bytes): at a pair's side_off the two records of a declined or noted pair, or of the error pair"""
+        n = self.info.side_bytes if self.info else 0
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        check(lib().psvr_signal_side(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n].tobytes()
+
+    def pair_records(self, store, pair):
+        """the two records of a pair of the last run, back to back (bytes)"""
+        out = np.empty(1 << 16, dtype=np.uint8)
+        got = C.c_int64(0)
+        rc = lib().psvr_signal_pair_records(self.h, store.h, C.c_int64(pair), out.ctypes.data_as(C.c_void_p), C.c_int64(len(out)), C.byref(got))
+        if rc == 6:                                                      # PSVR_ERR_OVERFLOW: the size came with the refusal
+            out = np.empty(got.value, dtype=np.uint8)
+            rc = lib().psvr_signal_pair_records(self.h, store.h, C.c_int64(pair), out.ctypes.data_as(C.c_void_p), C.c_int64(len(out)), C.byref(got))
+        check(rc)
+        return out[:got.value].tobytes()
+
+    def stats(self):
+        """(isize_n, len_n): BamStat::collect's histograms over every pair of all runs (uint64 arrays)"""
+        a, b = np.zeros(MAX_ISIZE, dtype=np.uint64), np.zeros(MAX_LEN, dtype=np.uint64)
+        check(lib().psvr_signal_stats(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
+        return a, b
+
+    def close(self):
+        if self.h:
+            lib().psvr_signal_destroy(self.h)
+            self.h = None

@@ -123,6 +123,16 @@ class BamStore:
         check(lib().psvr_bam_store_download(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n), C.byref(got)))
         return out[:got.value]
 
+    def drop(self, n_front):
+        """the first n_front records (append order) cease to exist; chunks that hold none of the rest are released (one is kept as a spare)"""
+        check(lib().psvr_bam_store_drop(self.h, C.c_int64(n_front)))
+
+    def footprint(self):
+        """(chunks, bytes) the store holds in device memory for records: the live chunks and the spare one"""
+        n, b = C.c_int64(0), C.c_int64(0)
+        check(lib().psvr_bam_store_footprint(self.h, C.byref(n), C.byref(b)))
+        return n.value, b.value
+
     def close(self):
         if self.h:
             lib().psvr_bam_store_destroy(self.h)
