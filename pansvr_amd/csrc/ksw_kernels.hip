@@ -523,6 +523,16 @@ __global__ __launch_bounds__(64) void extd2_tiny_kernel(DpBatch B, DpParams P, i
 // vector issue: see the price list in profiles/r01j_valu_op_rates.txt (add/sub/logic/right shift ~2 cycles,
 // max/min/cmp/three-operand/DPP ~4) -- which is why the differences are kept x 8 with the candidate's priority in the low
 // bits (below): ~47 vector instructions per cell.
+// The order of a step (ksw_row_step.inc) and its one wait.  A step reads a query base, a strip-boundary dword and (full instantiation)
+// a D record, and writes the direction bytes plus a boundary dword or a last-column H.  It performs ONE s_waitcnt vmcnt(0), at its very
+// top, for the loads the step BEFORE issued; then come the uses of those values (qc4, vl / xl / x2l, d_row), then -- between two
+// scheduling barriers, in straight-line code -- the step's memory cluster: the stores of what the step before computed (dirw[], and in the
+// lean instantiation `carry`) and the unconditional, index-clamped loads for the step after; then ~400 vector instructions of cells that
+// look at none of it.  So every operation of the cluster has a whole step to complete before the next wait.  Written the other way
+// round (loads in branches at the top, stores at the end) the compiler waited vmcnt(0) twice per step, ~50 instructions behind the
+// loads and right behind the stores: a third of the wavefront cycles were parked (counters and times before and
+// after: profiles/team_sweep_waits.txt).  The strip prologue issues its target bytes and step 0's values together and waits once.  The full
+// instantiation has no register for `carry` (168 VGPRs, spills outside the step loop): it stores those two values at the end of the step.
 // wavefronts per SIMD the register allocation aims at: 2 lanes x 8 columns needs 168 VGPRs (3 per SIMD); 1 x 16 at two per SIMD runs as
 // fast (1.84 vs 1.88 ms), 2 x 8 at two 2.29 ms, 4 x 4 at five 2.17 ms, 4 x 8 at three 2.54 ms: profiles/r03e
 static constexpr int kTeamWaves = 3;
@@ -540,6 +550,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 
 	static_assert(CPL == 4 || CPL == 8 || CPL == 16, "columns per lane: direction bytes go out as dwords");
 	constexpr int SW = CPL * LANES, PB = 64 / LANES;                 // strip width, alignments per wavefront
 	constexpr int kNone = (int)0x80000000;                           // "no cell yet" in the per-diagonal maximum
+	constexpr bool CARRY = LEAN != 0;                                // a step's boundary dword / last-column H is stored by the next step's cluster
 	const int lane = threadIdx.x, team = lane / LANES, ql = lane % LANES;
 	// substitution scores of every (target, query) code pair, scaled and tagged like the other candidates (see below), written by
 	// all 64 lanes before any of them leaves
@@ -615,6 +626,24 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 
 		const int jb = CPL * ql, cb = c0 + jb;                          // this lane's first column: in the strip, in the target
 		const int jx = tlen - 1 - cb;                                   // the last target column, if this lane holds it
 		const bool own = (unsigned)jx < (unsigned)CPL;
+		const bool eown = ql == LANES - 1 && s + 1 < ns;                // this lane's last column is handed to the next strip (never both: own is in the last strip)
+		// for the carried stores of a step (CARRY): the query length where the lane has something to store, and its offset from row k's base
+		const unsigned qlen_e = eown ? (unsigned)qlen : 0u, qlen_o = own ? (unsigned)qlen : 0u;
+		const int eoff = (int)t4 - ql * (4 * PB), ooff = (int)t4 + (tlen - 1 - ql) * (4 * PB);
+		uint8_t *const Ein = (s & 1) ? uE0 : uE1, *const Eout = (s & 1) ? uE1 : uE0;
+		// What the strip reads before its first step, issued together ahead of the register set-up and waited for once: the lane's target
+		// bytes (column index clamped: a column outside the target has inr false and its byte is dropped) and what step 0 looks at -- the
+		// first query base, the previous strip's boundary values and D of the strip's first diagonal (looked at for s > 0 only).
+		unsigned tb[CPL];
+#pragma unroll
+		for (int jj = 0; jj < CPL; ++jj) tb[jj] = target[min(cb + jj, tlen - 1)];
+		// what a step reads from memory (query base, the previous strip's boundary values, the diagonal's running maximum) is
+		// loaded one step ahead, by the step's memory cluster
+		unsigned q_cur = query[0];                                      // query[k - ql] for k = 0 (raw byte: masking it here would wait for the load)
+		unsigned e_prev = (unsigned)at4(Ein, 0);
+		int d_cur = kNone, out_prev = kNone;
+		if (!LEAN) d_cur = at4(uD, c0);
+		__builtin_amdgcn_sched_barrier(0);
 		int U[CPL], V[CPL], X[CPL], Y[CPL], X2[CPL], Y2[CPL], H[CPL], TC[CPL];
 		int M[CPL], K[CPL], G[CPL];                                   // per anti-diagonal passing the column: maximum so far, tail threshold; per column: rank bits of place = t
 		bool inr[CPL];                                                // column inside the target
@@ -624,24 +653,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 
 			V[jj] = 8 * neg_qe, X[jj] = x_init, Y[jj] = y_init, X2[jj] = x2_init, Y2[jj] = y2_init;
 			H[jj] = 8 * h_above(cb + jj);
 			inr[jj] = jb + jj < ncols;
-			TC[jj] = inr[jj] ? (target[cb + jj] & 7) * 32 : 0;          // row of the score table (codes are 0..4)
 			M[jj] = kNone, G[jj] = frank(cb + jj);
 			const int d = cb + jj - ql;                                 // the anti-diagonal of column jj in this lane's row of step 0
 			const int st = max(0, d - qlen + 1), en = min(tlen - 1, d);
 			K[jj] = st + ((en - st) & ~3) - cb;
 		}
 		(void)M, (void)K, (void)G;
-		uint8_t *const Ein = (s & 1) ? uE0 : uE1, *const Eout = (s & 1) ? uE1 : uE0;
-		// what a step reads from memory (query base, the previous strip's boundary values, the diagonal's running maximum) is
-		// loaded one step ahead, so the loads have a whole step to arrive
-		unsigned e_prev = 0;
+		__builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+		for (int jj = 0; jj < CPL; ++jj) TC[jj] = inr[jj] ? (int)(tb[jj] & 7) * 32 : 0;   // row of the score table (codes are 0..4)
 		unsigned dirw[CPL / 4];                                       // the direction bytes of the step before
-		int d_cur = kNone, out_prev = kNone;
-		if (s > 0) {
-			e_prev = (unsigned)at4(Ein, 0);
-			if (!LEAN && 0 <= ksteps - LANES) d_cur = at4(uD, c0);
-		}
-		unsigned q_cur = ql == 0 ? query[0] : 0u;                       // query[k - ql] for k = 0 (raw byte: masking it here would wait for the load)
+		unsigned carry = 0;                                           // its boundary dword (eown) or last-column H (own)
 		for (int kv = 0; kv < LANES - 1; ++kv) {
 			const int k = uni(kv);
 #define TEAM_MASKED 1
@@ -670,6 +692,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kTeamWaves, 
 			uint32_t *const dst = (uint32_t *)(w0 + (size_t)(s * R + ksteps - 1) * (64 * CPL) + lc);
 #pragma unroll
 			for (int g = 0; g < CPL / 4; ++g) dst[g] = dirw[g];
+		}
+		if (CARRY) {
+			const int ip = ksteps - 1 - ql;                              // the last step's row
+			if ((unsigned)ip < qlen_e) at4(Eout, ip) = (int)carry;
+			if ((unsigned)ip < qlen_o) atD2(ip + tlen - 1) = (short)carry;
 		}
 		// what is still on its way through the lanes: anti-diagonals c0 + ksteps and later, none of which an earlier strip wrote
 		if (LEAN) { __threadfence_block(); continue; }

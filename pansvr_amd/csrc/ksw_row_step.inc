@@ -3,13 +3,12 @@
 // LANES - 1 steps (a lane that has not started must keep its state), TEAM_MASKED 0 afterwards (what a lane computes past its last row
 // is never looked at); TEAM_TOPROW 1 for the steps in which some lane is in row 0 (k < LANES).
 		const int i = k - ql;                                           // this lane's row
-		if (with_cigar && k > 0) {
-			uint32_t *const dst = (uint32_t *)(w0 + (size_t)(s * R + k - 1) * (64 * CPL) + lc);
-#pragma unroll
-			for (int g = 0; g < CPL / 4; ++g) dst[g] = dirw[g];
-		}
 		const bool act = (unsigned)i < (unsigned)qlen;
-		const unsigned q_nxt = (unsigned)(i + 1) < (unsigned)qlen ? query[i + 1] : 0u;
+		// -- first, everything that looks at what the step before loaded (q_cur, e_prev, d_cur): the one wait of the step stands here.
+		// The empty statement names the three as used, so the compiler waits for them here, at the top, whatever it sinks into the
+		// branches below or into the cluster (left alone it waited behind the cluster's first store, for a register it reuses).
+		asm volatile("" : "+v"(q_cur), "+v"(e_prev));
+		if (!LEAN) asm volatile("" : "+v"(d_cur));
 		const int qc4 = (int)((q_cur << 2) & 0x1cu);                    // the row's query code, times four: column offset in the score table
 		// the column left of this lane's first one, same row: the neighbour lane's last column (it did this row one step ago), or for the
 		// team's first lane column -1 (:142-152) / the previous strip's last column
@@ -23,18 +22,35 @@
 				M[CPL - 2] = max(M[CPL - 2], ql == LANES - 1 ? kNone : inc);
 			}
 		}
-		unsigned e_next = 0;
-		int d_nxt = kNone;
-		if (s > 0) {
-			e_next = (unsigned)at4(Ein, k + 1);
-			if (!LEAN && k + 1 <= ksteps - LANES) d_nxt = at4(uD, c0 + k + 1);       // as far as the previous strip wrote D (its drain ends at c0 + ksteps - LANES)
-		}
+		// D of this step's diagonal as the strips before left it: they wrote it as far as their drain went (it ends at c0 + ksteps - LANES)
+		const int d_row = (!LEAN && s > 0 && k <= ksteps - LANES) ? d_cur : kNone;
 		if (ql == 0) {
 			// the previous strip's last column, one dword: v / 8, (x - 3) / 8, (x2 - 1) / 8 as signed bytes (v is a multiple of 8, x and x2 are
 			// multiples of 8 plus their constant priority tag, and the true differences fit int8 in this regime)
 			if (s > 0) vl = __builtin_amdgcn_sbfe((int)e_prev, 0, 8) << 3, xl = (__builtin_amdgcn_sbfe((int)e_prev, 8, 8) << 3) | 3, x2l = (__builtin_amdgcn_sbfe((int)e_prev, 16, 8) << 3) | 1;
 			else vl = 8 * ur_of(i), xl = x_init, x2l = x2_init;
 		}
+		// -- then the step's memory operations, as one cluster in straight-line code: what the step before left to store (its direction
+		// bytes, its strip-boundary dword or last-column H) and the loads for the step after.  Nothing below looks at them, so they have
+		// the whole step to complete.  The loads are unconditional: a row index past the query is clamped, Ein / uD rows that no strip
+		// wrote lie inside the wavefront's scratch, and what they return is never looked at (act, s > 0, d_row above).
+		__builtin_amdgcn_sched_barrier(0);
+		if (with_cigar && (!TEAM_MASKED || k > 0)) {
+			uint32_t *const dst = (uint32_t *)(w0 + (size_t)(s * R + k - 1) * (64 * CPL) + lc);
+#pragma unroll
+			for (int g = 0; g < CPL / 4; ++g) dst[g] = dirw[g];
+		}
+		if (CARRY) {
+			// row i - 1, the one this lane did a step ago (none in step 0): a wave-uniform row base plus the lane's constant offset; the
+			// lane's predicate and "that row was inside the query" are one compare (qlen_e / qlen_o are 0 in a lane that stores nothing)
+			const long long rowb = (long long)(k - 1) * (4 * PB);
+			if ((unsigned)(i - 1) < qlen_e) *(int *)(Eout + rowb + eoff) = (int)carry;
+			if ((unsigned)(i - 1) < qlen_o) *(short *)(uD23 + rowb + ooff) = (short)carry;
+		}
+		q_cur = query[min(TEAM_MASKED ? max(i + 1, 0) : i + 1, qlen - 1)];   // (i + 1 >= 1 once every lane has started)
+		e_prev = (unsigned)at4(Ein, k + 1);
+		if (!LEAN) d_cur = at4(uD, c0 + k + 1);
+		__builtin_amdgcn_sched_barrier(0);
 		// The reference's order among equal H on an anti-diagonal (:322-349): whole 4-cell groups first, by (place & 3, place), then the
 		// tail in place order; the cell at en0, which it looks at first, is settled afterwards.  place = t - st0 is the column itself while
 		// the diagonal starts in row >= 0 of column 0 (t <= qlen - 1 - i) and qlen - 1 - i, the same for the whole row, below that; rank
@@ -76,7 +92,7 @@
 		// anti-diagonal i + cb is complete as far as this lane and the ones right of it go: on to the left neighbour, or -- first lane --
 		// merged with what the strips before left
 		const int out = LEAN ? 0 : M[0];
-		if (!LEAN && ql == 0) at4(uD, c0 + k) = max(out, d_cur);
+		if (!LEAN && ql == 0) at4(uD, c0 + k) = max(out, d_row);
 		if (!LEAN) {
 			const int d_in = i + cb + CPL;                              // the diagonal that enters at the last column with the next row
 			const int st_in = max(0, d_in - qlen + 1), en_in = min(tlen - 1, d_in);
@@ -84,30 +100,45 @@
 			for (int jj = 0; jj + 1 < CPL; ++jj) M[jj] = M[jj + 1], K[jj] = K[jj + 1] + 0;
 			M[CPL - 1] = kNone, K[CPL - 1] = st_in + ((en_in - st_in) & ~3) - cb;
 		}
-		// one byte per cell, the lane's CPL cells of a step side by side: [step][lane][cell]; stored at the start of the NEXT step, together
-		// with its loads, so that the wait for those at the end of a step does not also wait for a store issued moments before
+		// one byte per cell, the lane's CPL cells of a step side by side: [step][lane][cell]; stored by the NEXT step's cluster (above),
+		// so that no store stands right in front of the step's wait
 #pragma unroll
 		for (int g = 0; g < CPL; g += 4) {
 			const unsigned lo = __builtin_amdgcn_perm((unsigned)acc[g + 1], (unsigned)acc[g], 0x0c0c0400u);
 			const unsigned hi = __builtin_amdgcn_perm((unsigned)acc[g + 3], (unsigned)acc[g + 2], 0x04000c0cu);
 			dirw[g >> 2] = lo | hi;
 		}
-		if (ql == LANES - 1 && s + 1 < ns && act)
-			at4(Eout, i) = (int)((((unsigned)V[CPL - 1] >> 3) & 0xffu) | ((((unsigned)X[CPL - 1] >> 3) & 0xffu) << 8) | ((((unsigned)X2[CPL - 1] >> 3) & 0xffu) << 16));
+		// what crosses into the next strip -- v, x, x2 of the strip's last column, one dword -- or, in the alignment's last strip, H of the
+		// last target column (cell (i, tlen - 1), see below): one value per lane and step, stored with the next step's cluster like dirw
+		// (CARRY 0: stored here, at the end of the step, and waited for by the next step moments later)
+		if (CARRY) {
+			unsigned c = 0;                                             // (set afresh in every step: nothing rides round the loop in it)
+			if (eown) c = (((unsigned)V[CPL - 1] >> 3) & 0xffu) | ((((unsigned)X[CPL - 1] >> 3) & 0xffu) << 8) | ((((unsigned)X2[CPL - 1] >> 3) & 0xffu) << 16);
+			if (own) {
+				int hx = H[CPL - 1];
+#pragma unroll
+				for (int u = CPL - 2; u >= 0; --u) hx = jx == u ? H[u] : hx;
+				c = (unsigned)(hx >> 3);
+			}
+			carry = c;
+		} else {
+			if (eown & act)
+				at4(Eout, i) = (int)((((unsigned)V[CPL - 1] >> 3) & 0xffu) | ((((unsigned)X[CPL - 1] >> 3) & 0xffu) << 8) | ((((unsigned)X2[CPL - 1] >> 3) & 0xffu) << 16));
+			if (own & act) {
+				int hx = H[CPL - 1];
+#pragma unroll
+				for (int u = CPL - 2; u >= 0; --u) hx = jx == u ? H[u] : hx;
+				atD2(i + tlen - 1) = (short)(hx >> 3);
+			}
+		}
 		// H at the band ends, for the maximum's tie rule / mte / mqe / score: cell (r - en0, en0) is in the top row (r < tlen) or in the last
 		// column, cell (qlen - 1, r - qlen + 1) in the last row
 		if (TEAM_TOPROW && i == 0) {
 #pragma unroll
 			for (int jj = 0; jj < CPL; ++jj) if (inr[jj]) atD2(cb + jj) = (short)(H[jj] >> 3);
 		}
-		if (own & act) {
-			int hx = H[CPL - 1];
-#pragma unroll
-			for (int u = CPL - 2; u >= 0; --u) hx = jx == u ? H[u] : hx;
-			atD2(i + tlen - 1) = (short)(hx >> 3);
-		}
 		if (k >= k_last && i == qlen - 1) {                            // (k_last: the first step in which a lane of this wavefront is in its last row)
 #pragma unroll
 			for (int jj = 0; jj < CPL; ++jj) if (inr[jj]) atD3(qlen - 1 + cb + jj) = (short)(H[jj] >> 3);
 		}
-		out_prev = out, e_prev = e_next, d_cur = d_nxt, q_cur = q_nxt;
+		out_prev = out;
