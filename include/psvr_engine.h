@@ -598,6 +598,22 @@ int  psvr_bam_store_footprint(psvr_bam_store_t *st, int64_t *chunks, int64_t *by
  *   pair_records  the bytes of the two records of pair p of the last run, back to back (block_size first), for the host formatter; the store
  *                 must hold the records still (no drop in between).
  *   stats         isize_n[100000] and len_n[1000], accumulated over all runs.
+ *   window        the text SignalStep's host loop would have written for the pairs in front of the last run's first error pair, complete and
+ *                 in pair order, in device memory (pansvr_amd/csrc/signal_window_device.h): the state-1 ranges come from the run's text buffer,
+ *                 the state-2 pairs from host_text, whose bytes [host_off[i], host_off[i + 1]) are the host formatter's text of the i-th
+ *                 state-2 pair in front of the first error pair (uploaded by the call), each at its place; state-0 pairs contribute nothing.
+ *                 n_host is not the number of such pairs, host_off is not monotone from 0 or does not end at host_bytes: PSVR_ERR_ARG;
+ *                 a window of 2^32 bytes or more: PSVR_ERR_UNSUPPORTED.  info: n_bytes of the window, n_pairs whose text it holds (states 1
+ *                 and 2), n_host_pairs of them from the host.  The call waits; the window stays until the next run or window call.
+ *   window_text   bytes [first, first + n) of the window to dst, which is host memory or memory of the object's device (outside the
+ *                 window: PSVR_ERR_ARG).
+ *   psvr_fastq_parse_signal   exactly the effect of psvr_fastq_parse on the bytes [first_byte, n_bytes) of sg's window with at_end = 1, the
+ *                 bytes copied device to device into fq's own text buffer: sg may be run again once the call returns, and the emitter
+ *                 finds names, comments and qualities in fq as it does behind psvr_fastq_parse.  fq and sg on two devices, no window, or
+ *                 first_byte outside [0, n_bytes]: PSVR_ERR_ARG.  info->used_bytes lets the caller come back with first_byte + used_bytes
+ *                 when max_pairs / max_bases wanted fewer pairs than the window holds.
+ *   psvr_fastq_text   bytes [first, first + n) of the text fq was last parsed from (either way) to dst in host memory, for a caller that
+ *                 never held the text (outside that text: PSVR_ERR_ARG).
  * No device: PSVR_ERR_DEVICE.  Calls run under the store's mutex on its stream, serialised with the store's. */
 typedef struct psvr_signal psvr_signal_t;
 typedef struct psvr_signal_opt {
@@ -613,6 +629,11 @@ int  psvr_signal_pairs(psvr_signal_t *sg, psvr_signal_pair_t *pairs, int64_t cap
 int  psvr_signal_side(psvr_signal_t *sg, void *bytes, int64_t cap);
 int  psvr_signal_pair_records(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t pair, void *bytes, int64_t cap, int64_t *n_bytes);
 int  psvr_signal_stats(psvr_signal_t *sg, uint64_t *isize_n, uint64_t *len_n);
+typedef struct psvr_signal_window_info { int64_t n_bytes, n_pairs, n_host_pairs; } psvr_signal_window_info_t;
+int  psvr_signal_window(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *info);
+int  psvr_signal_window_text(psvr_signal_t *sg, void *dst, int64_t first, int64_t n);   /* dst: host memory or memory of sg's device */
+int  psvr_fastq_parse_signal(psvr_fastq_t *fq, const psvr_signal_t *sg, int64_t first_byte, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info);
+int  psvr_fastq_text(const psvr_fastq_t *fq, void *dst, int64_t first, int64_t n);
 void psvr_signal_destroy(psvr_signal_t *sg);
 
 #ifdef __cplusplus

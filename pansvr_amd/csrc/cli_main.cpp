@@ -53,6 +53,7 @@ struct Opt : aln::PipeOpt {
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
 	bool stream_device = false;                  // the main BAM file's stream gathered in HBM: records from the encoder to the member compressor device to device (implies emit_device and deflate_device)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
+	bool bam_device = false;                     // a name-sorted *.bam read file: the signal step's device route hands windows of FASTQ text in HBM to the reader stage
 	bool sort_device = false;                    // ... with the records kept, ordered and compressed in HBM (sort_store_sink.h; implies sort, emit_device and deflate_device)
 };
 
@@ -145,6 +146,12 @@ static int usage()
 	        "                                 files are those of --sort --deflate-device, byte for byte.  Not with -S, --stream-device, --compress-level,\n"
 	        "                                 --bgzf-fast, --bgzf-device or more than one entry in --devices.  A failed store call downloads the records and\n"
 	        "                                 leaves the rest to the host's sorted writer.  " PSVR_SORT_DEVICE_MEASURED "\n"
+	        "        --bam-device             with -N and a *.bam read file: the file's members are inflated, paired, judged and formatted as FASTQ text in GPU\n"
+	        "                                 memory (the route of `signal -N --signal-device`), and the reader stage parses that text where it lies: only\n"
+	        "                                 the compressed members of the input cross to the device.  Implies --parse-device; --emit-device, --stream-device\n"
+	        "                                 and --sort-device then apply to the BAM input.  Whatever the route cannot do (no device, a pipe, a corrupt or\n"
+	        "                                 truncated file, a failing call on either side) is named on one line, and the host fused route reads the file\n"
+	        "                                 again, silent for the pairs already handed over.  Not with more than one entry in --devices\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -291,7 +298,15 @@ struct EngineDriver {
 	}
 	int parse_window(int slot, FastqReader &rd, FastqBatch &fb, long long pairs, long long bases, int threads, std::string *why)
 	{
-		if (!fq[slot] && psvr_fastq_create(devices[0], &fq[slot])) { *why = psvr_last_error(); return -1; }
+		const bool made = fq[slot] || !psvr_fastq_create(devices[0], &fq[slot]);
+		if (rd.has_windows()) {
+			// --bam-device: the text is in the signal object's memory.  Whichever side fails, the route's producer knows, and its one line
+			// names the call, the reason and the pairs handed over: the pipeline goes over to the PairFeed without a line of its own
+			if (!made) { rd.fail_windows(*why = std::string("fastq create: ") + psvr_last_error()); return aln::kNotAvailable; }
+			const int r = rd.read_window(fb, pairs, bases, fq[slot], stage[slot], why);
+			return r < 0 ? aln::kNotAvailable : r;
+		}
+		if (!made) { *why = psvr_last_error(); return -1; }
 		return rd.read_device(fb, pairs, bases, threads, fq[slot], stage[slot], parse_max_window, why);
 	}
 	int emit_encode(int slot, const FastqBatch &fb, bool not_ori)
@@ -425,6 +440,7 @@ struct SignalCmdBackend {
 	int signal_pairs(psvr_signal_pair_t *t, int64_t cap) { return psvr_signal_pairs(sg, t, cap); }
 	int signal_side(void *b, int64_t cap) { return psvr_signal_side(sg, b, cap); }
 	int signal_stats(uint64_t *isize_n, uint64_t *len_n) { return psvr_signal_stats(sg, isize_n, len_n); }
+	int signal_window(const void *t, int64_t n, const int64_t *off, int64_t n_host, psvr_signal_window_info_t *i) { return psvr_signal_window(sg, t, n, off, n_host, i); }
 	const char *last_error() { return psvr_last_error(); }
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
@@ -466,6 +482,8 @@ static bool option_conflict(const Opt &o, const char *sort_conflict)
 		fprintf(stderr, "--emit-device cannot be combined with more than one entry in --devices: the records are encoded from the text and the results in the first device's memory\n");
 	else if (o.emit_device && o.sam)
 		fprintf(stderr, "--emit-device cannot be combined with -S: the device encodes BAM records, SAM text is formatted on the host threads\n");
+	else if (o.bam_device && o.devices.size() > 1)
+		fprintf(stderr, "--bam-device cannot be combined with more than one entry in --devices: the text is made and parsed in the first device's memory\n");
 	else if (o.parse_device && o.devices.size() > 1)
 		fprintf(stderr, "--parse-device cannot be combined with more than one entry in --devices: the parsed bases stay in the first device's memory and would have to travel between devices\n");
 	else return false;
@@ -479,7 +497,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -518,6 +536,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1017: o.sort_device = o.sort = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1018: fprintf(stderr, "[panSVR-amd] --signal-device is `panSVR signal -N`'s route to FASTQ text: ignored by aln (a *.bam read file hands its pairs over on the host threads)\n"); break;
+		case 1019: o.bam_device = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -532,6 +551,9 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	o.index_dir = argv[optind], o.reads = argv[optind + 1], o.header = argv[optind + 2];
 	o.from_bam = o.reads.size() > 4 && o.reads.compare(o.reads.size() - 4, 4, ".bam") == 0;
 	if (!o.from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
+	if (o.bam_device && !o.from_bam) fprintf(stderr, "[panSVR-amd] --bam-device applies to a *.bam read file: ignored for [%s]\n", o.reads.c_str()), o.bam_device = false;
+	if (o.bam_device && !o.sig_by_name) fprintf(stderr, "[panSVR-amd] aln --bam-device: refused (it is the name-sorted mode's route: give -N): the host fused route runs\n"), o.bam_device = false;
+	if (o.bam_device) { o.parse_device = true; return -1; }   // (the device stages behind the reader apply to the BAM input)
 	if (o.from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
 	if (o.from_bam && o.sort_device) fprintf(stderr, "[panSVR-amd] --sort-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the run is that of --sort --deflate-device)\n", o.reads.c_str());
 	else if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
@@ -557,15 +579,23 @@ static void load_header(const Opt &o, HeaderInfo *H, std::vector<BamRef> *refs)
 }
 
 // f2 fused: the signal step's thread hands its pairs straight to the batch being built (PairFeed, fastq_batch.h) -- no FASTQ text, no pipe
-static std::thread start_signal_step(const Opt &o, psvr::SignalStep &sig, PairFeed &feed, int *sig_rc)
+static std::thread start_signal_step(const Opt &o, psvr::SignalStep &sig, PairFeed &feed, WindowFeed *windows, int *sig_rc)
 {
 	sig.o.sort_by_name = o.sig_by_name, sig.o.input = o.reads, sig.o.header_fn = o.header, sig.o.status_fn = o.header + ".status";
 	sig.o.not_use_filter = o.sig_all, sig.o.discard_full_match = o.sig_discard;
 	sig.o.inflate_device = o.inflate_device ? o.devices[0] : -1, sig.o.inflate_threads = o.inflate_threads;
 	sig.o.match = o.match, sig.o.mismatch = o.mismatch, sig.o.gap_open = o.gap_open, sig.o.gap_ex = o.gap_ex, sig.o.gap_open2 = o.gap_open2, sig.o.gap_ex2 = o.gap_ex2;
 	sig.feed = &feed;
-	return std::thread([&sig, sig_rc, &feed]() { *sig_rc = sig.run(); feed.close(); });
+	return psvr::signal_step_thread(sig, feed, windows, sig_rc);
 }
+
+// --bam-device: who takes the windows of the signal step's device route -- the reader stage, through the WindowFeed
+struct ReaderWindowTaker : psvr::SignalWindowTaker {
+	SignalCmdBackend &be;
+	WindowFeed &windows;
+	ReaderWindowTaker(SignalCmdBackend &b, WindowFeed &w) : be(b), windows(w) {}
+	long long offer(const psvr_signal_window_info_t &info, std::string *why) override { return windows.offer(be.sg, info.n_pairs, why); }
+};
 
 // --sort: the main file, its records ordered on the first device, written with the index.  0, or the command's exit status
 static int write_sorted_main(const Opt &o, const HeaderInfo &H, const std::vector<BamRef> &bam_refs, const SortRecords &sorted, aln::RunStats *st)
@@ -609,13 +639,26 @@ static int aln_main(int argc, char **argv)
 	std::thread sig_thread;
 	int sig_rc = 0;
 	PairFeed feed;
-	if (o.from_bam) sig_thread = start_signal_step(o, sig, feed, &sig_rc);
+	WindowFeed windows;
+	if (o.bam_device) {
+		sig.o.bam_device = true;
+		sig.signal_device_fn = [&o, &windows](psvr::SignalStep &S, long long *pairs_done) {
+			SignalCmdBackend be(o.devices[0]);
+			ReaderWindowTaker taker(be, windows);
+			const int rc = psvr::signal_device_route(be, S, pairs_done, nullptr, &taker);
+			windows.close(rc != 0);                              // (left: the host fused route hands the rest over through the PairFeed)
+			return rc;
+		};
+	}
+	if (o.from_bam) sig_thread = start_signal_step(o, sig, feed, o.bam_device ? &windows : nullptr, &sig_rc);
 	FastqReader fq;
+	if (o.bam_device) fq.open_windows(&windows);
 	if (o.from_bam) fq.open_feed(&feed);
 	else if (!fq.open(o.reads.c_str())) { fprintf(stderr, "%s\n", fq.error().c_str()); abort(); }
 	aln::OutFile fo, fo_ori;
 	// --stream-device: the main file is the sink's, not `fo`'s (PSVR_STREAM_TAKE_MEMBERS: members pending before a take; the tests take small files in pieces with it)
-	const bool streaming = o.stream_device && !o.from_bam;
+	const bool device_routes = !o.from_bam || o.bam_device;
+	const bool streaming = o.stream_device && device_routes;
 	std::unique_ptr<StreamBackend> stream_backend;
 	std::unique_ptr<BgzfStreamSink<StreamBackend>> stream_sink;
 	std::unique_ptr<aln::MainSink> main_sink;
@@ -626,7 +669,7 @@ static int aln_main(int argc, char **argv)
 		if (!stream_sink->open(o.out.c_str(), H.text, refs, o.thread_n)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	}
 	// --sort-device: the main file's records go to the sink's store; the file is written when the input has ended
-	const bool sorting_device = o.sort_device && !o.from_bam;
+	const bool sorting_device = o.sort_device && device_routes;
 	std::unique_ptr<SortBackend> sort_backend;
 	std::unique_ptr<SortStoreSink<SortBackend>> sort_sink;
 	if (sorting_device) {
@@ -653,8 +696,9 @@ static int aln_main(int argc, char **argv)
 	em.H = &H, em.sv = &svn, em.as_bam = !o.sam, em.not_ori = o.not_ori, em.stats = &st.emit;
 	std::function<bool(const uint8_t *, size_t)> keep_main;
 	if (o.sort) keep_main = [&sorted](const uint8_t *p, size_t n) { return sorted.add_stream(p, n); };
-	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, !o.from_bam, main_sink.get());
+	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, device_routes, main_sink.get());
 	pipe.run();
+	windows.abort();
 	feed.abort();                                        // (a reader that stopped at -R leaves the signal step to run to its end unheard)
 	if (sig_thread.joinable()) {
 		sig_thread.join();

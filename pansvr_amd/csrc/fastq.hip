@@ -1,7 +1,7 @@
 // fastq.hip -- psvr_fastq_* (include/psvr_engine.h): a window of interleaved FASTQ text parsed on the device into the arrays the engine
 // takes (line index, name ends, base offsets, original alignments, bases).  The rules are fastq_device.h's, which the host build holds to
 // fastq_batch.h byte for byte; this file is their launch order on one stream:
-//   copy of the text -> k_fq_count -> scan (scan.h) -> k_fq_lines -> k_fq_meta -> k_fq_slen -> scan -> k_fq_cut -> k_fq_extract -> info
+//   copy of the text (from the host, or device to device from a signal run's window: psvr_fastq_parse_signal) -> k_fq_count -> scan (scan.h) -> k_fq_lines -> k_fq_meta -> k_fq_slen -> scan -> k_fq_cut -> k_fq_extract -> info
 // The host reads back the one psvr_fastq_info_t at the end; every count in between (newlines, pairs that count, pairs kept) stays on the
 // device, and the launches that depend on one are sized by what the window's size and max_pairs allow (fq_line_cap, fq_pair_cap).
 // Every phase hands over to the next at a kernel boundary.  Bounds: the newline passes read text[0, n) only (fq_newline_mask); line starts
@@ -12,6 +12,7 @@
 #include "common.h"
 #include "fastq_device.h"
 #include "fastq_parsed.h"
+#include "signal_run.h"
 #include "scan.h"
 
 namespace psvr {
@@ -121,13 +122,13 @@ extern "C" void psvr_fastq_destroy(psvr_fastq_t *fq)
 	delete fq;                                               // (its DevBufs free themselves)
 }
 
-extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_bytes, int at_end, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info)
+// the one body of psvr_fastq_parse and psvr_fastq_parse_signal: text[0, n_bytes) is host memory (kind: host to device) or memory of fq's
+// device (device to device); the callers have looked at their arguments
+static int fq_parse_from(const char *who, psvr_fastq_t *fq, const void *text, hipMemcpyKind kind, int64_t n_bytes, int at_end, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info)
 {
-	if (psvr_device_count() <= 0) return fq_no_device();
-	if (!fq || !info || n_bytes < 0 || max_pairs < 0 || (n_bytes > 0 && !text)) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse: bad argument");
-	if (n_bytes >= ((int64_t)1 << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_fastq_parse: a window of %lld bytes, offsets inside a call are 32-bit (at most 2^32 - 1 bytes)", (long long)n_bytes);
+	if (n_bytes >= ((int64_t)1 << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "%s: a window of %lld bytes, offsets inside a call are 32-bit (at most 2^32 - 1 bytes)", who, (long long)n_bytes);
 	PSVR_HIP(hipSetDevice(fq->device));
-	fq->valid = false, fq->generation = fq_next_generation();
+	fq->valid = false, fq->generation = fq_next_generation(), fq->n_text = 0;
 	const uint64_t n = (uint64_t)n_bytes, cap = fq_line_cap(n, max_pairs);
 	const int64_t ntile = (int64_t)((n + kFqTileBytes - 1) / kFqTileBytes), p_cap = fq_pair_cap(n, max_pairs), r_cap = 2 * p_cap;
 	const size_t tmp_a = scan_tmp_bytes(1, ntile + 1), tmp_b = scan_tmp_bytes(1, r_cap + 1);
@@ -136,7 +137,7 @@ extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_by
 	    fq->name_end.ensure((size_t)(r_cap + 1) * 2) || fq->ori.ensure((size_t)(r_cap + 1) * sizeof(psvr_ori_t)) || fq->bases.ensure(n + 1 + 64) ||
 	    fq->meta.ensure(sizeof(FqMeta)) || fq->info.ensure(sizeof(psvr_fastq_info_t))) {
 		(void)hipGetLastError();
-		return set_error(PSVR_ERR_NOMEM, "psvr_fastq_parse: device allocation failed for a window of %lld bytes and up to %lld pairs", (long long)n_bytes, (long long)p_cap);
+		return set_error(PSVR_ERR_NOMEM, "%s: device allocation failed for a window of %lld bytes and up to %lld pairs", who, (long long)n_bytes, (long long)p_cap);
 	}
 	hipStream_t st = fq->stream;
 	const char *d_text = fq->text.as<char>();
@@ -145,7 +146,7 @@ extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_by
 	FqMeta *d_meta = fq->meta.as<FqMeta>();
 	psvr_fastq_info_t *d_info = fq->info.as<psvr_fastq_info_t>();
 	StreamDrain drain{st};
-	if (n) PSVR_HIP(hipMemcpyAsync(fq->text.p, text, n, hipMemcpyHostToDevice, st));
+	if (n) PSVR_HIP(hipMemcpyAsync(fq->text.p, text, n, kind, st));
 	PSVR_HIP(hipMemsetAsync(fq->cnt.as<int32_t>() + ntile, 0, 4, st));                    // the scan's last entry: its offset is the total
 	if (ntile) hipLaunchKernelGGL(k_fq_count, dim3((unsigned)ntile), dim3(kFqTileLanes), 0, st, d_text, n, fq->cnt.as<int32_t>());
 	ScanSet S = {};
@@ -166,7 +167,38 @@ extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_by
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(st));
 	fq->last = *info = *fq->h_info;
-	fq->valid = true;
+	fq->valid = true, fq->n_text = n_bytes;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_fastq_parse(psvr_fastq_t *fq, const char *text, int64_t n_bytes, int at_end, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info)
+{
+	if (psvr_device_count() <= 0) return fq_no_device();
+	if (!fq || !info || n_bytes < 0 || max_pairs < 0 || (n_bytes > 0 && !text)) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse: bad argument");
+	return fq_parse_from("psvr_fastq_parse", fq, text, hipMemcpyHostToDevice, n_bytes, at_end, max_pairs, max_bases, info);
+}
+
+extern "C" int psvr_fastq_parse_signal(psvr_fastq_t *fq, const psvr_signal_t *sg, int64_t first_byte, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info)
+{
+	if (psvr_device_count() <= 0) return fq_no_device();
+	if (!fq || !sg || !info || max_pairs < 0) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: bad argument");
+	if (!sg->valid || !sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: the signal object has no window");
+	if (fq->device != sg->device) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: the parser is on device %d, the signal object on device %d", fq->device, sg->device);
+	if (first_byte < 0 || first_byte > sg->win_bytes) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: first byte %lld of a window of %lld", (long long)first_byte, sg->win_bytes);
+	// (the window is whole: psvr_signal_window waited for it)
+	return fq_parse_from("psvr_fastq_parse_signal", fq, sg->window.as<char>() + first_byte, hipMemcpyDeviceToDevice, sg->win_bytes - first_byte, 1, max_pairs, max_bases, info);
+}
+
+extern "C" int psvr_fastq_text(const psvr_fastq_t *fq, void *dst, int64_t first, int64_t n)
+{
+	if (psvr_device_count() <= 0) return fq_no_device();
+	if (!fq || first < 0 || n < 0 || (n > 0 && !dst)) return set_error(PSVR_ERR_ARG, "psvr_fastq_text: bad argument");
+	if (!fq->valid) return set_error(PSVR_ERR_ARG, "psvr_fastq_text: no parsed window");
+	if (first > fq->n_text || n > fq->n_text - first) return set_error(PSVR_ERR_ARG, "psvr_fastq_text: bytes [%lld, %lld) of a text of %lld", (long long)first, (long long)(first + n), (long long)fq->n_text);
+	if (n == 0) return PSVR_OK;
+	PSVR_HIP(hipSetDevice(fq->device));
+	PSVR_HIP(hipMemcpyAsync(dst, fq->text.as<char>() + first, (size_t)n, hipMemcpyDeviceToHost, fq->stream));
+	PSVR_HIP(hipStreamSynchronize(fq->stream));
 	return PSVR_OK;
 }
 

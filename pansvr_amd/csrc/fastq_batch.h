@@ -272,9 +272,53 @@ public:
 	bool fill(FastqBatch &B, long long max_pairs, long long max_bases);
 };
 
+// `aln -N --bam-device`: PairFeed's counterpart for pairs that are FASTQ text in device memory.  The signal step's device route (the
+// producer, signal_device_route.h in window mode) offers the window of a run (psvr_signal_window) and waits; the reader stage (the
+// consumer, FastqReader::read_window) parses it where it lies, a piece at a time by the piece rule's limits, and says what it took.  The
+// producer goes on when every pair of the window is taken.  A piece never spans two windows.  When there are no more windows the producer
+// says whether the input has ended or the route was left: the host fused route then hands the rest over through the PairFeed.
+class WindowFeed {
+	std::mutex mu_;
+	std::condition_variable cv_;
+	const psvr_signal_t *sg_ = nullptr;
+	long long n_pairs_ = 0, taken_ = 0, at_byte_ = 0;
+	bool offered_ = false, closed_ = false, left_ = false, failed_ = false, aborted_ = false;
+	std::string why_;
+
+public:
+	// producer: the window of `sg` with n_pairs pairs; returns the pairs the consumer took (n_pairs, or fewer with *why)
+	long long offer(const psvr_signal_t *sg, long long n_pairs, std::string *why)
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		if (n_pairs <= 0 || aborted_) return n_pairs;
+		if (failed_) { *why = why_; return 0; }
+		sg_ = sg, n_pairs_ = n_pairs, taken_ = 0, at_byte_ = 0, offered_ = true;
+		cv_.notify_all();
+		cv_.wait(lk, [&] { return aborted_ || failed_ || taken_ == n_pairs_; });
+		offered_ = false, sg_ = nullptr;
+		if (failed_ && !aborted_ && taken_ < n_pairs_) { *why = why_; return taken_; }
+		return n_pairs;
+	}
+	// (the first call says how it ended: the route closes when it is done or left, the signal step's thread closes again on whatever way it ends)
+	void close(bool left) { { std::lock_guard<std::mutex> lk(mu_); if (!closed_) closed_ = true, left_ = left; } cv_.notify_all(); }
+	void abort() { { std::lock_guard<std::mutex> lk(mu_); aborted_ = true; } cv_.notify_all(); }      // the consumer stopped early (-R): the producer runs to its end unheard
+	// consumer: 1 a window with pairs left, from *first_byte on; 0 the input has ended; -1 the route was left (or a call of the consumer's failed)
+	int next(const psvr_signal_t **sg, long long *first_byte, long long *pairs_left)
+	{
+		std::unique_lock<std::mutex> lk(mu_);
+		cv_.wait(lk, [&] { return failed_ || closed_ || (offered_ && taken_ < n_pairs_); });
+		if (failed_) return -1;
+		if (offered_ && taken_ < n_pairs_) { *sg = sg_, *first_byte = at_byte_, *pairs_left = n_pairs_ - taken_; return 1; }
+		return left_ ? -1 : 0;
+	}
+	void took(long long used_bytes, long long pairs) { { std::lock_guard<std::mutex> lk(mu_); at_byte_ += used_bytes, taken_ += pairs; } cv_.notify_all(); }
+	void fail(const std::string &why) { { std::lock_guard<std::mutex> lk(mu_); failed_ = true, why_ = why; } cv_.notify_all(); }
+};
+
 class FastqReader {
 	TextSource src_;
 	PairFeed *feed_ = nullptr;
+	WindowFeed *windows_ = nullptr;
 	size_t est_pair_bytes_ = 1024;                   // bytes of text per pair, refined from the previous batch
 	std::vector<int32_t> slen_;                      // scratch: sequence length per candidate read of the batch being cut
 	std::string first_comment_;
@@ -446,6 +490,40 @@ public:
 		est_pair_bytes_ = used / (size_t)npairs + 1;
 		B.R = R, B.bases = nullptr, B.dev = fq;
 		if (!have_first_) { const char *b; int n; B.comment(0, b, n); first_comment_.assign(b, (size_t)n); have_first_ = true; }
+		return 1;
+	}
+
+	// `aln -N --bam-device`: a piece out of the window the signal step's device route offers (WindowFeed), parsed where it lies
+	// (psvr_fastq_parse_signal, with the piece rule's limits).  What read_device brings back comes back here as well, and the text the piece
+	// used, into the page-locked `stage`, for the host formatter; B.dev = fq as read_device sets it.
+	// 1: a piece; 0: the end of the input; -1: the call failed (*why says how; the route's producer is told and leaves the route);
+	// -2: the producer has left the route.  After -1 and -2 the pairs come through the PairFeed: read() takes over.  `why` names the call.
+	void open_windows(WindowFeed *w) { windows_ = w; }
+	bool has_windows() const { return windows_ != nullptr; }
+	// a call of the reader's side failed in front of read_window (its parser could not be made): the producer is told as read_window tells it
+	void fail_windows(const std::string &why) { if (windows_) windows_->fail(why), windows_ = nullptr; }
+	int read_window(FastqBatch &B, long long max_pairs, long long max_bases, psvr_fastq_t *fq, HostBuf &stage, std::string *why)
+	{
+		B.R = 0, B.dev = nullptr;
+		const psvr_signal_t *sg = nullptr;
+		long long first_byte = 0, pairs_left = 0;
+		const int r = windows_->next(&sg, &first_byte, &pairs_left);
+		if (r <= 0) { if (r < 0) windows_ = nullptr; return r < 0 ? -2 : 0; }
+		auto fail = [&](const std::string &w) { *why = w; windows_->fail(w); windows_ = nullptr; return -1; };
+		psvr_fastq_info_t info;
+		if (psvr_fastq_parse_signal(fq, sg, first_byte, max_pairs, max_bases, &info)) return fail(std::string("fastq parse_signal: ") + psvr_last_error());
+		const long long npairs = info.n_pairs, R = 2 * npairs;
+		if (npairs < 1 || npairs > pairs_left) return fail("fastq parse_signal: the window's text holds " + std::to_string(npairs) + " pairs where the run counted " + std::to_string(pairs_left) + " more");
+		B.ls.resize((size_t)npairs * 8 + 1);
+		B.name_end.resize((size_t)R);
+		B.base_off = (int64_t *)B.off_buf.reserve((size_t)(R + 1) * 8);
+		B.ori = (psvr_ori_t *)B.ori_buf.reserve((size_t)R * sizeof(psvr_ori_t));
+		char *text = (char *)stage.reserve((size_t)info.used_bytes + 1);
+		if (psvr_fastq_download(fq, B.ls.data(), B.name_end.data(), B.base_off, B.ori, nullptr)) return fail(std::string("fastq download: ") + psvr_last_error());
+		if (psvr_fastq_text(fq, text, 0, info.used_bytes)) return fail(std::string("fastq text: ") + psvr_last_error());
+		B.text = text, B.R = R, B.bases = nullptr, B.dev = fq;
+		if (!have_first_) { const char *b; int n; B.comment(0, b, n); first_comment_.assign(b, (size_t)n); have_first_ = true; }
+		windows_->took(info.used_bytes, npairs);
 		return 1;
 	}
 #endif

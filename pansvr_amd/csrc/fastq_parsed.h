@@ -10,6 +10,7 @@ struct psvr_fastq {
 	psvr_fastq_info_t *h_info = nullptr;                     // page-locked: the one record a call reads back
 	psvr_fastq_info_t last = {0, 0, 0, 0, 0, 0};             // of the window the buffers hold
 	bool valid = false;
+	int64_t n_text = 0;                                      // bytes of text[] the window was parsed from (psvr_fastq_text)
 	uint64_t generation = 0;                                 // of the window the buffers hold: drawn from one process-wide counter at create and by every parse, so no
 	                                                         // two windows of a process share one, whatever address their parser has: who remembers a window can tell that it is gone
 };

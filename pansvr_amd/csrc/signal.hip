@@ -14,6 +14,9 @@
 //   k_sg_hist      a lane per pair in front of the first error pair: BamStat::collect of both records.  len_n is privatised per workgroup in
 //                  LDS and flushed once (nearly all reads have one length: global atomics would serialise on one address); isize_n spreads over
 //                  hundreds of bins and takes global atomics.
+// psvr_signal_window, behind a run: the run's text and the host formatter's text of the state-2 pairs become one window in pair order
+// (signal_window_device.h), on the same stream:
+//   k_sg_wflag, scan, k_sg_wcut, k_sg_wseg   the segment table from the pair table     k_sg_window   an output tile per workgroup
 // Bounds: a record is read only after k_sg_mark has vouched for name, CIGAR, bases and qualities; the tag walk (bam_aux_find) stays inside
 // the record by its own rules; a pair's text is written into exactly the bytes the size pass counted for it, and a write pass that ends
 // anywhere else raises the refusal flag.
@@ -27,18 +30,8 @@
 #include "bgzf_members.h"
 #include "bam_store_run.h"
 #include "signal_device.h"
-
-struct psvr_signal {
-	int device = 0;
-	psvr_signal_opt_t opt;
-	bool spent = false;                                      // STAT_ has been given to a pair
-	psvr::DevBuf mark, poff, prim, state, note, bytes, toff, tmp, text, ctl, isize_n, len_n, sbytes, soff, side;
-	long long *h_ctl = nullptr;                              // page-locked read-back of ctl
-	// the last run
-	bool valid = false;
-	const psvr_bam_store *store = nullptr;
-	long long store_generation = 0, first_record = 0, pairs = 0, text_bytes = 0, side_bytes = 0;
-};
+#include "signal_run.h"
+#include "signal_window_device.h"
 
 namespace psvr {
 
@@ -178,6 +171,34 @@ __global__ __launch_bounds__(256) void k_sg_hist(const uint64_t *addr, long long
 	for (int k = threadIdx.x; k < kSgMaxLen; k += 256) if (len_l[k]) atomicAdd(&len_n[k], (unsigned long long)len_l[k]);
 }
 
+// ---- the window (signal_window_device.h) ----
+__global__ __launch_bounds__(256) void k_sg_wflag(const uint8_t *state, long long n_front, int32_t *flag)
+{
+	const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (p <= n_front) flag[p] = sw_flag(p, n_front, state);
+}
+__global__ __launch_bounds__(256) void k_sg_wcut(const int32_t *flag, const long long *rank, const long long *toff, long long n_front, long long n_host, long long *cut, long long *ctl)
+{
+	const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (p >= n_front || !flag[p]) return;
+	if (rank[p] < 0 || rank[p] >= n_host) { ctl[kSgRefused] = 3; return; }
+	cut[rank[p]] = toff[p];
+}
+__global__ __launch_bounds__(256) void k_sg_wseg(const long long *cut, const long long *host_off, long long n_host, long long text_bytes, long long host_bytes, SwSeg *seg, long long *ctl)
+{
+	const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (k > 2 * n_host) return;
+	const SwSeg s = sw_segment(k, n_host, (const int64_t *)cut, (const int64_t *)host_off, text_bytes);
+	// (inside its source and inside the window, whatever the tables say: the tiles trust the table)
+	if (s.len < 0 || s.off < 0 || s.off + s.len > (s.src ? host_bytes : text_bytes) || s.out < 0 || s.out + s.len > text_bytes + host_bytes) ctl[kSgRefused] = 3;
+	seg[k] = s;
+}
+__global__ __launch_bounds__(256) void k_sg_window(const SwSeg *seg, long long n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, long long n_out, const long long *ctl)
+{
+	if (ctl[kSgRefused] != 0) return;                        // (the whole launch)
+	sw_tile(blockIdx.x, seg, n_seg, text, host, out, n_out, threadIdx.x, 256);
+}
+
 static int sg_no_device() { return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path"); }
 
 } // namespace psvr
@@ -232,7 +253,7 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
 	if (int rc = store_refresh(st, c, true)) return rc;
-	sg->valid = false;
+	sg->valid = false, sg->win_valid = false;
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_signal_run: the store has been ordered: the pairs are those of its append order");
 	if (first_record < 0 || first_record > st->n_rec) return set_error(PSVR_ERR_ARG, "psvr_signal_run: first record %lld of %lld", (long long)first_record, st->n_rec);
 	const long long m = st->n_rec - first_record, p_max = m / 2;
@@ -297,6 +318,7 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run: the write pass did not end where the size pass said (the text is not used)");
 	if (h[kSgStatPair] >= 0) sg->spent = true;
 	sg->valid = true, sg->store = st, sg->store_generation = st->generation, sg->first_record = first_record, sg->pairs = P, sg->text_bytes = text_bytes, sg->side_bytes = side_bytes;
+	sg->n_front = n_front, sg->written = h[kSgWritten], sg->declined = h[kSgDeclined];
 	info->side_bytes = side_bytes;
 	info->pairs = P, info->written = h[kSgWritten], info->declined = h[kSgDeclined], info->first_error = first_err, info->text_bytes = text_bytes;
 	info->consumed = (n_prim & 1) ? first_record + h[kSgLastPrim] : st->n_rec;
@@ -314,6 +336,70 @@ extern "C" int psvr_signal_text(psvr_signal_t *sg, void *text, int64_t cap)
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
 	PSVR_HIP(hipMemcpyAsync(text, sg->text.p, (size_t)sg->text_bytes, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_window(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *info)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || !info || (host_bytes > 0 && !host_text)) return set_error(PSVR_ERR_ARG, "psvr_signal_window: null argument");
+	if (!sg->valid) return set_error(PSVR_ERR_ARG, "psvr_signal_window: no run");
+	if (const char *bad = sw_args_bad(host_bytes, host_off, n_host, sg->declined))
+		return set_error(PSVR_ERR_ARG, "psvr_signal_window: %s (%lld host pairs with %lld bytes, the run has %lld)", bad, (long long)n_host, (long long)host_bytes, sg->declined);
+	const long long n_front = sg->n_front, text_bytes = sg->text_bytes, n_out = text_bytes + host_bytes, n_seg = 2 * n_host + 1;
+	if (n_out >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_window: a window of %lld bytes (at most 2^32 - 1: the parser's offsets)", n_out);
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	sg->win_valid = false;
+	if (sg->wflag.ensure((size_t)(n_front + 1) * 4) || sg->wrank.ensure((size_t)(n_front + 1) * 8) || sg->wcut.ensure((size_t)(n_host + 1) * 8) || sg->wseg.ensure((size_t)n_seg * sizeof(SwSeg)) ||
+	    sg->whost.ensure((size_t)host_bytes + 16) || sg->whoff.ensure((size_t)(n_host + 1) * 8) || sg->window.ensure((size_t)n_out + 16) || sg->tmp.ensure(scan_tmp_bytes(1, n_front + 1)) ||
+	    (!sg->text.p && sg->text.ensure(16))) {             // (a run without text: the kernel still gets a pointer; a run's text is never reallocated here)
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_signal_window: device allocation failed for a window of %lld bytes and %lld segments", n_out, n_seg);
+	}
+	long long *ctl = sg->ctl.as<long long>();
+	long long *h = sg->h_ctl;
+	h[kSgRefused] = 0;
+	StreamDrain drain{c.stream};
+	PSVR_HIP(hipMemcpyAsync(ctl + kSgRefused, h + kSgRefused, 8, hipMemcpyHostToDevice, c.stream));
+	if (n_host) {
+		if (host_bytes) PSVR_HIP(hipMemcpyAsync(sg->whost.p, host_text, (size_t)host_bytes, hipMemcpyHostToDevice, c.stream));
+		PSVR_HIP(hipMemcpyAsync(sg->whoff.p, host_off, (size_t)(n_host + 1) * 8, hipMemcpyHostToDevice, c.stream));
+		hipLaunchKernelGGL(k_sg_wflag, dim3((unsigned)((n_front + 256) / 256)), dim3(256), 0, c.stream, (const uint8_t *)sg->state.p, n_front, sg->wflag.as<int32_t>());
+		ScanSet X = {};
+		X.cnt[0] = sg->wflag.as<int32_t>(), X.out[0] = sg->wrank.as<long long>(), X.stride[0] = 1;
+		scan_launch(X, 1, n_front + 1, sg->tmp.as<long long>(), c.stream);
+		hipLaunchKernelGGL(k_sg_wcut, dim3((unsigned)((n_front + 255) / 256)), dim3(256), 0, c.stream, (const int32_t *)sg->wflag.p, (const long long *)sg->wrank.p, (const long long *)sg->toff.p, n_front,
+		                   (long long)n_host, sg->wcut.as<long long>(), ctl);
+	}
+	hipLaunchKernelGGL(k_sg_wseg, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, c.stream, (const long long *)sg->wcut.p, (const long long *)sg->whoff.p, (long long)n_host, text_bytes,
+	                   (long long)host_bytes, sg->wseg.as<SwSeg>(), ctl);
+	if (n_out)
+		hipLaunchKernelGGL(k_sg_window, dim3((unsigned)((n_out + kSwTileBytes - 1) / kSwTileBytes)), dim3(256), 0, c.stream, (const SwSeg *)sg->wseg.p, n_seg, (const uint8_t *)sg->text.p,
+		                   (const uint8_t *)sg->whost.p, sg->window.as<uint8_t>(), n_out, (const long long *)ctl);
+	PSVR_HIP(hipGetLastError());
+	PSVR_HIP(hipMemcpyAsync(h + kSgRefused, ctl + kSgRefused, 8, hipMemcpyDeviceToHost, c.stream));
+	drain.armed = false;
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "psvr_signal_window: the segment table does not fit the run's text and the host text (the window is not used)");
+	sg->win_valid = true, sg->win_bytes = n_out;
+	info->n_bytes = n_out, info->n_pairs = sg->written + sg->declined, info->n_host_pairs = n_host;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_window_text(psvr_signal_t *sg, void *dst, int64_t first, int64_t n)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || first < 0 || n < 0 || (n > 0 && !dst)) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: bad argument");
+	if (!sg->valid || !sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: no window");
+	if (first > sg->win_bytes || n > sg->win_bytes - first) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: bytes [%lld, %lld) of a window of %lld", (long long)first, (long long)(first + n), sg->win_bytes);
+	if (n == 0) return PSVR_OK;
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	PSVR_HIP(hipMemcpyAsync(dst, sg->window.as<uint8_t>() + first, (size_t)n, hipMemcpyDefault, c.stream));
 	PSVR_HIP(hipStreamSynchronize(c.stream));
 	return PSVR_OK;
 }

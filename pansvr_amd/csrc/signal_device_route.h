@@ -24,6 +24,14 @@
 //   int signal_text(void *, int64_t cap) / int signal_pairs(psvr_signal_pair_t *, int64_t cap)
 //   int signal_side(void *bytes, int64_t cap) / int signal_stats(uint64_t *isize_n, uint64_t *len_n)
 //   void *host_alloc(size_t) / void host_free(void *) / const char *last_error()
+//
+// The route has two consumers, and one body for both.  `panSVR signal` takes text: what is described above.  `panSVR aln -N --bam-device`
+// takes windows (SignalWindowTaker below, window mode): the run's text is not downloaded; SignalStep::pair formats the state-2 pairs into a
+// buffer with offsets instead of S.out; the backend's
+//   int signal_window(const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *)
+// puts both together where the run's text lies (include/psvr_engine.h), and the taker is offered the window: it returns when the reader
+// stage has taken every pair of it (or could not: the route is left then, like after any failing call).  *pairs_done counts the pairs, of any
+// state, in front of which everything has been handed over.  The messages carry the command's name; everything else is one code.
 #pragma once
 #include <sys/stat.h>
 #include <string>
@@ -33,6 +41,13 @@
 #include "signal_step.h"
 
 namespace psvr {
+
+// window mode: who takes the windows.  offer() blocks until the pairs are taken and returns how many were (info.n_pairs: all; fewer: *why
+// says what failed on the taker's side).  The backend is the taker's to know: it reads the window out of the backend's signal object.
+struct SignalWindowTaker {
+	virtual ~SignalWindowTaker() {}
+	virtual long long offer(const psvr_signal_window_info_t &info, std::string *why) = 0;
+};
 
 struct SignalRouteStats { long long pairs = 0, written = 0, declined = 0, runs = 0, text_bytes = 0, peak_chunks = 0, peak_bytes = 0; };
 
@@ -45,13 +60,22 @@ inline psvr_signal_opt_t signal_device_options(const SignalStep &S)
 	return o;
 }
 
-template <class Backend> int signal_device_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr)
+// the backend's window call, where it has one (the text consumer's backend needs none)
+template <class Backend> auto signal_route_window(Backend &be, const void *t, int64_t n, const int64_t *off, int64_t n_host, psvr_signal_window_info_t *i, int) -> decltype(be.signal_window(t, n, off, n_host, i))
+{
+	return be.signal_window(t, n, off, n_host, i);
+}
+template <class Backend> int signal_route_window(Backend &, const void *, int64_t, const int64_t *, int64_t, psvr_signal_window_info_t *, long) { return PSVR_ERR_UNSUPPORTED; }
+
+template <class Backend> int signal_device_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr, SignalWindowTaker *taker = nullptr)
 {
 	*pairs_done = 0;
 	SignalRouteStats R;
 	auto left = [&](const std::string &call, const std::string &why) {
-		fprintf(stderr, "[panSVR-amd] signal --signal-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
-		        *pairs_done);
+		if (taker) fprintf(stderr, "[panSVR-amd] aln --bam-device: %s failed (%s): %lld pairs are handed over, the host fused route reads the file from its beginning, silent up to there\n", call.c_str(),
+		                   why.c_str(), *pairs_done);
+		else fprintf(stderr, "[panSVR-amd] signal --signal-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
+		             *pairs_done);
 		return -1;
 	};
 	struct stat sb;
@@ -98,6 +122,16 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 		return true;
 	};
 	auto write_out = [&](const uint8_t *p, size_t n) { if (n) fwrite(p, 1, n, S.out); };
+	// window mode: SignalStep::pair writes a state-2 pair's text here (the fused command's S.feed and S.out are put back when the route ends)
+	struct HostText {
+		SignalStep &S; FILE *out; PairFeed *feed; char *buf = nullptr; size_t len = 0; FILE *mem = nullptr;
+		std::vector<int64_t> off;
+		HostText(SignalStep &s, bool on) : S(s), out(s.out), feed(s.feed) { if (on && (mem = open_memstream(&buf, &len))) S.out = mem, S.feed = nullptr; }
+		void restart() { fflush(mem); rewind(mem); off.assign(1, 0); }
+		void pair_done() { fflush(mem); off.push_back((int64_t)ftello(mem)); }
+		~HostText() { S.out = out, S.feed = feed; if (mem) fclose(mem), free(buf); }
+	} host_text(S, taker != nullptr);
+	if (taker && !host_text.mem) return left("open_memstream", "out of memory");
 	const bool walked = bgzf_for_pieces(be, f, skip, &fail, [&](const uint8_t *p, size_t have, long long skip_now, int64_t *used, PieceFail *why) {
 		int64_t bad = -1;
 		if (be.store_append_bgzf(p, (int64_t)have, skip_now, (int32_t)n_ref, used, &bad)) { *why = {"append_bgzf", be.last_error()}; return false; }
@@ -111,8 +145,9 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 		++R.runs;
 		tab.resize((size_t)info.pairs);
 		if (info.pairs && be.signal_pairs(tab.data(), info.pairs)) { *why = {"signal pairs", be.last_error()}; return false; }
-		if (!room(&guard.text, &text_cap, (size_t)info.text_bytes, why) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
-		if (info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
+		if ((!taker && !room(&guard.text, &text_cap, (size_t)info.text_bytes, why)) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
+		if (!taker && info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
+		if (taker) host_text.restart();
 		if (info.side_bytes && be.signal_side(guard.side, (int64_t)side_cap)) { *why = {"signal side", be.last_error()}; return false; }
 		side_bytes = info.side_bytes;
 		// the pairs in order: text ranges of state-1 pairs as they lie, a state-2 pair from the host formatter at its place
@@ -120,6 +155,7 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 		int64_t flushed = 0;                                     // text bytes of this run that are on S.out
 		BamRecord a, b;
 		auto flush_to = [&](int64_t q) {                         // the text in front of pair q is on S.out, and *pairs_done says so
+			if (taker) return;                                   // (window mode: nothing is handed over before the window is)
 			const int64_t upto = q < info.pairs ? tab[(size_t)q].text_off : info.text_bytes;
 			write_out(guard.text + flushed, (size_t)(upto - flushed)), flushed = upto;
 			*pairs_done = R.pairs + q;
@@ -134,7 +170,8 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 				S.stat_written = any_written;
 				S.pair(a, b, true);
 				any_written = true, ++R.declined;
-				*pairs_done = R.pairs + q + 1;
+				if (taker) host_text.pair_done();
+				else *pairs_done = R.pairs + q + 1;
 				continue;
 			}
 			if (t.note & 1) {
@@ -145,6 +182,23 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 			if (t.state == 1) any_written = true, ++R.written;
 		}
 		flush_to(n_front);
+		if (taker) {                                             // the window: the run's text and the host's, in pair order, offered to the reader
+			psvr_signal_window_info_t wi;
+			const int64_t n_host = (int64_t)host_text.off.size() - 1, host_bytes = host_text.off.back();
+			if (signal_route_window(be, host_text.buf, host_bytes, host_text.off.data(), n_host, &wi, 0)) { *why = {"signal window", be.last_error()}; return false; }
+			std::string taker_why;
+			const long long taken = taker->offer(wi, &taker_why);
+			if (taken != wi.n_pairs) {                           // the pairs in front of the first one that was not taken are handed over
+				long long seen = 0;
+				int64_t q = 0;
+				for (; q < n_front && seen < taken; ++q) seen += tab[(size_t)q].state == 1 || tab[(size_t)q].state == 2;
+				*pairs_done = R.pairs + q;
+				*why = {"taking a window", taker_why};
+				return false;
+			}
+			*pairs_done = R.pairs + n_front;
+			R.text_bytes += wi.n_bytes - info.text_bytes;
+		}
 		R.pairs += n_front, R.text_bytes += info.text_bytes;
 		if (info.first_error >= 0) {                             // the pair the host loop aborts on
 			const psvr_signal_pair_t &t = tab[(size_t)info.first_error];
@@ -175,8 +229,10 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 	if (ci.tail_bytes) return left("the end of the input", "truncated BAM stream: the file ends " + std::to_string((long long)ci.tail_bytes) + " bytes into a record");
 	if (be.signal_stats(S.bs.isize_n.data(), S.bs.len_n.data())) return left("signal stats", be.last_error());
 	S.bs.total = (uint64_t)total;
-	fprintf(stderr, "[panSVR-amd] signal --signal-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld runs, %lld text bytes, peak footprint %lld chunks (%lld bytes)\n", R.pairs, R.written,
-	        R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
+	if (taker) fprintf(stderr, "[panSVR-amd] aln --bam-device: %lld pairs, %lld formatted on the device, %lld formatted by the host, %lld runs, %lld window bytes, peak footprint %lld chunks (%lld bytes)\n", R.pairs,
+	                   R.written, R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
+	else fprintf(stderr, "[panSVR-amd] signal --signal-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld runs, %lld text bytes, peak footprint %lld chunks (%lld bytes)\n", R.pairs, R.written,
+	             R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
 	if (stats) *stats = R;
 	return 0;
 }

@@ -1,6 +1,7 @@
 // signal_step.h -- `panSVR signal` (= the reference's `fc_signal`): BAM -> interleaved FASTQ whose comment carries
 // the original alignment, i.e. the wire format `aln` parses.  Host C++, with one device route: with `-N --signal-device` the records are
-// inflated, paired, judged and formatted in GPU memory (signal_device_route.h over psvr_signal_*).  This file's pair() stays the
+// inflated, paired, judged and formatted in GPU memory (signal_device_route.h over psvr_signal_*; the fused `aln -N --bam-device` runs the
+// same route and hands the text to aln's reader stage where it lies, a window per run).  This file's pair() stays the
 // specification: it formats the few pairs the device declines, and it takes over, muted up to the pairs already written, whenever that route
 // is left.  Restated from PanSVgenerateVCF/getSignalRead.cpp / .hpp and the helpers of clib/bam_file.c it calls; PARITY UNPINNED:
 // the reference's build of this step needs htslib, which cannot be built in this image, so the only checker is the independent
@@ -25,6 +26,7 @@
 #include <cstring>
 #include <functional>
 #include <string>
+#include <thread>
 #include <vector>
 #include "bam_reader.h"
 #include "fastq_batch.h"
@@ -40,6 +42,7 @@ struct SignalOpt {
 	int isize_override[3] = {-1, -1, -1};                                                   // --isize MIN,MID,MAX
 	int inflate_device = -1, inflate_threads = 0;                                           // --inflate-device / --inflate-threads N: the batched BGZF reader (bam_reader.h)
 	bool signal_device = false;                                                             // --signal-device: signal_device_route.h (with -N)
+	bool bam_device = false;                                                                // aln --bam-device: the same route, its windows handed to aln's reader stage
 };
 
 struct BamStat {                                            // BAM_STAT, getSignalRead.hpp:33-190
@@ -103,7 +106,8 @@ struct SignalStep {
 	int sample_max = 0;
 	FILE *out = stdout;
 	PairFeed *feed = nullptr;          // fused with `aln`: records go to the batch being built instead of FASTQ text on `out`
-	bool muted = false;                // write_fastq writes nothing: the pair's text is on `out` already (the device route wrote it before it was left)
+	bool muted = false;                // write_fastq writes nothing and feeds nothing: the pair's text is on `out` already, or the pair has been handed to
+	                                   // aln's reader (the device route did that before it was left)
 	// --signal-device (signal_device_route.h over the caller's backend): 0 done, bs holds the histograms; -1 the route was left with *pairs_done
 	// pairs written; 3, 4, 5: the host route's abort() for a pair in that state is due (the message has been printed)
 	std::function<int(SignalStep &, long long *pairs_done)> signal_device_fn;
@@ -163,7 +167,7 @@ struct SignalStep {
 			}
 			for (int i = 0; i < half + 1 && len > 0; ++i) { const int ri = len - 1 - i; std::swap(qual[(size_t)i], qual[(size_t)ri]); }
 		}
-		if (feed) feed->put(b.qname(), comment, seq, qual, ori);
+		if (feed) { if (!muted) feed->put(b.qname(), comment, seq, qual, ori); }
 		else if (!muted) fprintf(out, "@%s %s\n%s\n+\n%s\n", b.qname(), comment.c_str(), seq.c_str(), qual.c_str());
 	}
 
@@ -425,14 +429,17 @@ struct SignalStep {
 			fwrite(rd.header_text.data(), 1, rd.header_text.size(), h);
 			fclose(h);
 		}
-		long long mute = 0;                                 // pairs whose text the device route has written
-		if (o.signal_device) {
-			const char *no = feed              ? "the fused aln route hands its pairs over on the host"
+		long long mute = 0;                                 // pairs whose text the device route has written (or handed to aln's reader)
+		if (o.signal_device || o.bam_device) {
+			// (aln --bam-device is the fused command's form of the route: it needs the feed, `signal --signal-device` must not have one)
+			const bool fused = o.bam_device;
+			const char *no = !fused && feed    ? "the fused aln route hands its pairs over on the host"
 			                 : !o.sort_by_name ? "it is the name-sorted mode's route: give -N"
 			                 : o.sample_rate < 0.9999 ? "-R draws rand() per pair in the host loop's order"
 			                 : !signal_device_fn ? "this build has no device route"
 			                                     : nullptr;
-			if (no) fprintf(stderr, "[panSVR-amd] signal --signal-device: refused (%s): the host route runs\n", no);
+			if (no && fused) fprintf(stderr, "[panSVR-amd] aln --bam-device: refused (%s): the host fused route runs\n", no);
+			else if (no) fprintf(stderr, "[panSVR-amd] signal --signal-device: refused (%s): the host route runs\n", no);
 			else {
 				const int rc = signal_device_fn(*this, &mute);
 				if (rc > 0) abort();                            // (a pair the host loop aborts on; the route has written what lies in front of it and said why)
@@ -478,6 +485,18 @@ struct SignalStep {
 		return 0;
 	}
 };
+
+// The fused command's signal thread.  Whatever way the step ends -- the statistics pass refusing a damaged file, a file that cannot be opened,
+// a refused device route, its regular end -- both hand-overs are closed behind it, so the reader stage never waits for a producer that is
+// gone: a WindowFeed the device route has not closed itself counts as left, and the PairFeed then says that there are no more pairs.
+inline std::thread signal_step_thread(SignalStep &sig, PairFeed &feed, WindowFeed *windows, int *rc)
+{
+	return std::thread([&sig, &feed, windows, rc]() {
+		*rc = sig.run();
+		if (windows) windows->close(true);
+		feed.close();
+	});
+}
 
 inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, long long *)> signal_device_fn = nullptr)
 {

@@ -29,6 +29,19 @@ class FastqParser:
         self.info = info
         return info
 
+    def parse_signal(self, signal, first_byte, max_pairs, max_bases):
+        """psvr_fastq_parse_signal: the bytes from first_byte on of the window of a pansvr_amd.signal_step.Signal, parsed where they lie."""
+        info = FastqInfo()
+        check(lib().psvr_fastq_parse_signal(self.h, signal.h, C.c_int64(first_byte), C.c_int64(max_pairs), C.c_int64(max_bases), C.byref(info)))
+        self.info = info
+        return info
+
+    def text(self, first, n):
+        """psvr_fastq_text: bytes [first, first + n) of the text the last parse looked at"""
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        check(lib().psvr_fastq_text(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(first), C.c_int64(n)))
+        return out[:n].tobytes()
+
     def download(self, bases=True):
         """dict: line_start uint64[8P + 1], name_end uint16[2P], base_off int64[2P + 1], ori ORI_DTYPE[2P] and, on request, bases
         uint8[total_bases + 1] (the NUL included)."""

@@ -18,6 +18,10 @@ class SignalInfo(C.Structure):  # psvr_signal_info_t
     _fields_ = [(n, C.c_int64) for n in ("pairs", "written", "declined", "first_error", "text_bytes", "consumed", "side_bytes")]
 
 
+class SignalWindowInfo(C.Structure):  # psvr_signal_window_info_t
+    _fields_ = [(n, C.c_int64) for n in ("n_bytes", "n_pairs", "n_host_pairs")]
+
+
 PAIR_DTYPE = np.dtype([("text_off", "<i8"), ("rec1", "<i8"), ("rec2", "<i8"), ("side_off", "<i8"), ("bytes", "<i4"), ("state", "u1"), ("note", "u1"), ("pad", "<u2")])   # psvr_signal_pair_t
 
 
@@ -82,6 +86,24 @@ class Signal:
         a, b = np.zeros(MAX_ISIZE, dtype=np.uint64), np.zeros(MAX_LEN, dtype=np.uint64)
         check(lib().psvr_signal_stats(self.h, a.ctypes.data_as(C.c_void_p), b.ctypes.data_as(C.c_void_p)))
         return a, b
+
+    def window(self, host_text=b"", host_off=(0,)):
+        """psvr_signal_window: the last run's text and the host formatter's text of its state-2 pairs (host_text[host_off[i]:host_off[i + 1]]
+        for the i-th of them in front of the first error pair) become one window in pair order on the device; returns SignalWindowInfo"""
+        text = np.frombuffer(bytes(host_text) or b"\0", dtype=np.uint8)
+        off = np.ascontiguousarray(host_off, dtype=np.int64)
+        i = SignalWindowInfo()
+        check(lib().psvr_signal_window(self.h, text.ctypes.data_as(C.c_void_p), C.c_int64(len(host_text)), off.ctypes.data_as(C.c_void_p), C.c_int64(len(off) - 1), C.byref(i)))
+        self.window_info = i
+        return i
+
+    def window_text(self, first=0, n=None):
+        """bytes [first, first + n) of the window (to its end by default)"""
+        if n is None:
+            n = self.window_info.n_bytes - first
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        check(lib().psvr_signal_window_text(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(first), C.c_int64(n)))
+        return out[:n].tobytes()
 
     def close(self):
         if self.h:
