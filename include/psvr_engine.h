@@ -636,6 +636,45 @@ int  psvr_fastq_parse_signal(psvr_fastq_t *fq, const psvr_signal_t *sg, int64_t 
 int  psvr_fastq_text(const psvr_fastq_t *fq, void *dst, int64_t first, int64_t n);
 void psvr_signal_destroy(psvr_signal_t *sg);
 
+/* ---- `panSVR signal --mate-device`: the blocks of the position-sorted mode, mated where the records lie ------------------------------------
+ * SignalStep::run_pos_sorted's block rules (pansvr_amd/csrc/signal_mate_device.h holds them for host and device) over the primary records of
+ * the store behind first_record, in append order.
+ *   run_pos   A block: up to opt->block_records primaries (0: 1 000 000); the first one on another chromosome than the block's first, or more
+ *             than opt->block_span (0: 60 000 000) behind it, is its last.  A block that is not complete, with finish == 0: pos_info->complete
+ *             = 0, nothing is consumed, nothing else is filled (a mark and a scan).  Otherwise the mates are found exactly as the host loop
+ *             finds them, the pairs (the record without flag 0x80 first, in that record's order) go through psvr_signal_run's size, fix,
+ *             side, write and hist passes -- info, text, pairs, side and stats answer as behind psvr_signal_run, state 3 cannot occur --
+ *             and the records without mate are gathered in block order for psvr_signal_left.  pos_info: the block's primaries, the record
+ *             index the caller drops the store to (consumed), the unmated records and their bytes, the "Mate failed" turns of all blocks
+ *             so far, the notes that wait, the records the one-lane replay walked.  A finished input of fewer than two primaries is
+ *             consumed and gives nothing (the host loop drops a single record).
+ *             Declined with PSVR_ERR_UNSUPPORTED and the reason in psvr_last_error(), nothing consumed: positions that decrease inside the
+ *             block (its last record on another chromosome excepted), a position that overflows the host loop's 1 M-entry index.
+ *   mate_notes  for every 1000th "Mate failed" turn of the last block what the host loop's line says: number, index in block, block size,
+ *             tid, pos, name.
+ *             Every block's unmated records are also copied, device to device, into a second record store that the object owns.
+ *   left      the last block's unmated records back to back (block_size first), left[0, pos_info.left_bytes) (what went into that store).
+ *   run_left  The by-name pass over that store.  The first call orders it by the host comparator (name by strcmp, records with flag 0x40
+ *             first, append order) and builds the pair list: a run of L equal names gives floor(L / 2) pairs and, when L is odd and the run
+ *             is not the last, one pairing-error step.  Every call runs pairs [first_pair, first_pair + max_pairs) of that list through
+ *             psvr_signal_run's passes; a slice whose text would reach 2 GiB is halved until it does not, so left_info.n_pairs may be
+ *             smaller than max_pairs and the caller goes on from first_pair + n_pairs: info, text, pairs (rec1 / rec2 are
+ *             indices into the left store, in append order), side and stats answer as behind a run.  left_info: the store's records, the
+ *             pairs and error steps of the whole pass, the slice, and whether pairs remain.  An odd number of records: PSVR_ERR_UNSUPPORTED.
+ *   left_errors  per pair of the last slice, the pairing-error steps of the whole pass in front of it (left_info.errors - the last pair's
+ *             figure lie behind the last pair).
+ * No device: PSVR_ERR_DEVICE. */
+typedef struct psvr_signal_pos_opt { int64_t block_records, block_span; } psvr_signal_pos_opt_t;
+typedef struct psvr_signal_pos_info { int64_t complete, primaries, consumed, unmated, left_bytes, mate_failed, notes, replayed; } psvr_signal_pos_info_t;   /* 64 bytes */
+typedef struct psvr_signal_mate_note { int64_t number; int32_t index, block, tid, pos; char name[256]; } psvr_signal_mate_note_t;                         /* 280 bytes */
+int  psvr_signal_run_pos(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t first_record, int32_t finish, const psvr_signal_pos_opt_t *opt, psvr_signal_info_t *info,
+                         psvr_signal_pos_info_t *pos_info);
+int  psvr_signal_mate_notes(psvr_signal_t *sg, psvr_signal_mate_note_t *notes, int64_t cap);
+int  psvr_signal_left(psvr_signal_t *sg, void *bytes, int64_t cap);
+typedef struct psvr_signal_left_info { int64_t records, pairs, errors, first_pair, n_pairs, more; } psvr_signal_left_info_t;                               /* 48 bytes */
+int  psvr_signal_run_left(psvr_signal_t *sg, int64_t first_pair, int64_t max_pairs, psvr_signal_info_t *info, psvr_signal_left_info_t *left_info);
+int  psvr_signal_left_errors(psvr_signal_t *sg, int64_t *errors, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -440,6 +440,11 @@ struct SignalCmdBackend {
 	int signal_pairs(psvr_signal_pair_t *t, int64_t cap) { return psvr_signal_pairs(sg, t, cap); }
 	int signal_side(void *b, int64_t cap) { return psvr_signal_side(sg, b, cap); }
 	int signal_stats(uint64_t *isize_n, uint64_t *len_n) { return psvr_signal_stats(sg, isize_n, len_n); }
+	// --mate-device
+	int signal_run_pos(int64_t first, int finish, const psvr_signal_pos_opt_t *o, psvr_signal_info_t *i, psvr_signal_pos_info_t *pi) { return psvr_signal_run_pos(sg, store, first, finish, o, i, pi); }
+	int signal_mate_notes(psvr_signal_mate_note_t *t, int64_t cap) { return psvr_signal_mate_notes(sg, t, cap); }
+	int signal_run_left(int64_t first, int64_t max_pairs, psvr_signal_info_t *i, psvr_signal_left_info_t *li) { return psvr_signal_run_left(sg, first, max_pairs, i, li); }
+	int signal_left_errors(int64_t *e, int64_t cap) { return psvr_signal_left_errors(sg, e, cap); }
 	int signal_window(const void *t, int64_t n, const int64_t *off, int64_t n_host, psvr_signal_window_info_t *i) { return psvr_signal_window(sg, t, n, off, n_host, i); }
 	const char *last_error() { return psvr_last_error(); }
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
@@ -740,6 +745,9 @@ int main(int argc, char **argv)
 	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv, [](psvr::SignalStep &S, long long *pairs_done) {
 			SignalCmdBackend be(0);
 			return psvr::signal_device_route(be, S, pairs_done);
+		}, [](psvr::SignalStep &S, long long *pairs_done) {
+			SignalCmdBackend be(0);
+			return psvr::signal_mate_route(be, S, pairs_done);
 		});
 	if (argc >= 2 && !strcmp(argv[1], "sort"))
 		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name) {

@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void k_name_len(NameSrc src, long long n, uint
 		uint32_t tie = 0;
 		if (src.rec_addr) {
 			const uint8_t *rec = (const uint8_t *)(uintptr_t)src.rec_addr[i];
-			p = rec + 36, len = name_len_rec(rec), tie = name_tie_key(rec[18]);
+			p = rec + 36, len = name_len_rec(rec), tie = src.first_read_tie ? (rec[18] & 0x40u ? 0u : 1u) : name_tie_key(rec[18]);   // (signal_mate_device.h: sm_left_tie)
 		} else {
 			const long long o = src.off[i];
 			if (o < 0 || o >= src.n_bytes) bad = kNameNoEnd;

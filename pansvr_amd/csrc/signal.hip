@@ -22,7 +22,9 @@
 // anywhere else raises the refusal flag.
 #include <hip/hip_runtime.h>
 #include <limits.h>
+#include <stdlib.h>
 #include <algorithm>
+#include <memory>
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "common.h"
@@ -30,6 +32,8 @@
 #include "bgzf_members.h"
 #include "bam_store_run.h"
 #include "signal_device.h"
+#include "signal_mate_device.h"
+#include "copy_aligned_device.h"
 #include "signal_run.h"
 #include "signal_window_device.h"
 
@@ -200,6 +204,7 @@ __global__ __launch_bounds__(256) void k_sg_window(const SwSeg *seg, long long n
 }
 
 static int sg_no_device() { return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path"); }
+static int sg_run_pairs(psvr_signal *sg, const uint64_t *addr, const psvr_bam_store *st, DfwCtx &c, int64_t first_record, const long long *poff, long long p_max, const char *who, psvr_signal_info_t *info, long long text_limit = 0);
 
 } // namespace psvr
 
@@ -240,6 +245,7 @@ extern "C" void psvr_signal_destroy(psvr_signal_t *sg)
 	(void)hipSetDevice(sg->device);
 	if (c.stream) (void)hipStreamSynchronize(c.stream);
 	if (sg->h_ctl) (void)hipHostFree(sg->h_ctl);
+	if (sg->h_mctl) (void)hipHostFree(sg->h_mctl);
 	delete sg;
 }
 
@@ -270,9 +276,8 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	for (int k = 0; k < kSgCtl; ++k) h[k] = 0;
 	h[kSgFirstErr] = h[kSgFirstWritten] = kSgNone, h[kSgStatPair] = -1, h[kSgLastPrim] = -1;
 	const uint64_t *addr = (const uint64_t *)st->addr.p;
-	const uint32_t *prim = (const uint32_t *)sg->prim.p;
 	const long long *poff = (const long long *)sg->poff.p;
-	const unsigned g_rec = (unsigned)((m + 256) / 256), g_grp = (unsigned)((p_max + 1 + 256 / kFqGroup - 1) / (256 / kFqGroup)), g_pair = (unsigned)((p_max + 256) / 256);
+	const unsigned g_rec = (unsigned)((m + 256) / 256);
 	StreamDrain drain{c.stream};
 	PSVR_HIP(hipMemcpyAsync(ctl, h, kSgCtl * 8, hipMemcpyHostToDevice, c.stream));
 	hipLaunchKernelGGL(k_sg_mark, dim3(g_rec), dim3(256), 0, c.stream, addr, (long long)first_record, m, sg->mark.as<int32_t>(), ctl);
@@ -280,6 +285,23 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	X.cnt[0] = sg->mark.as<int32_t>(), X.out[0] = sg->poff.as<long long>(), X.stride[0] = 1;
 	scan_launch(X, 1, m + 1, sg->tmp.as<long long>(), c.stream);
 	hipLaunchKernelGGL(k_sg_compact, dim3(g_rec), dim3(256), 0, c.stream, (const int32_t *)sg->mark.p, poff, m, sg->prim.as<uint32_t>());
+	drain.armed = false;
+	if (int rc = sg_run_pairs(sg, addr, st, c, first_record, poff + m, p_max, "psvr_signal_run", info)) return rc;
+	info->consumed = (sg->h_ctl[kSgPrim] & 1) ? first_record + sg->h_ctl[kSgLastPrim] : st->n_rec;
+	return PSVR_OK;
+}
+
+namespace psvr {
+// The pairs (prim[2p], prim[2p + 1]) of sg->prim, *n_listed / 2 of them (a device cell; p_max is the host's upper bound): size, fix, side,
+// write and hist, behind whatever the caller has queued on the stream (the ctl upload among it).  Fills info but for `consumed`.
+static int sg_run_pairs(psvr_signal *sg, const uint64_t *addr, const psvr_bam_store *st, DfwCtx &c, int64_t first_record, const long long *poff, long long p_max, const char *who, psvr_signal_info_t *info, long long text_limit)
+{
+	const long long m = 0;                                   // (the kernels read the count at poff[m])
+	long long *ctl = sg->ctl.as<long long>();
+	long long *h = sg->h_ctl;
+	const uint32_t *prim = (const uint32_t *)sg->prim.p;
+	const unsigned g_grp = (unsigned)((p_max + 1 + 256 / kFqGroup - 1) / (256 / kFqGroup)), g_pair = (unsigned)((p_max + 256) / 256);
+	StreamDrain drain{c.stream};
 	hipLaunchKernelGGL(k_sg_size, dim3(g_grp), dim3(256), 0, c.stream, sg->opt, addr, (long long)first_record, prim, poff, m, p_max, sg->state.as<uint8_t>(), sg->note.as<uint8_t>(),
 	                   sg->bytes.as<int32_t>(), ctl);
 	hipLaunchKernelGGL(k_sg_fix, dim3(g_pair), dim3(256), 0, c.stream, sg->opt, sg->spent ? 1 : 0, addr, (long long)first_record, prim, poff, m, p_max, (const uint8_t *)sg->state.p,
@@ -292,12 +314,14 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	PSVR_HIP(hipGetLastError());
 	PSVR_HIP(hipMemcpyAsync(h, ctl, kSgCtl * 8, hipMemcpyDeviceToHost, c.stream));
 	PSVR_HIP(hipStreamSynchronize(c.stream));
-	if (h[kSgRefused]) return set_error(PSVR_ERR_IO, "psvr_signal_run: malformed BAM record among records [%lld, %lld) of the store (BamReader's rules refuse it)", (long long)first_record, st->n_rec);
+	if (h[kSgRefused]) return set_error(PSVR_ERR_IO, "%s: malformed BAM record among the records behind record %lld of the store (BamReader's rules refuse it)", who, (long long)first_record);
 	const long long n_prim = h[kSgPrim], P = n_prim / 2, first_err = h[kSgFirstErr] == kSgNone ? -1 : h[kSgFirstErr], text_bytes = h[kSgText];
 	const long long n_front = first_err >= 0 ? first_err : P;
 	const long long side_bytes = h[kSgSide];
-	if (n_prim < 0 || n_prim > m || text_bytes < 0 || side_bytes < 0) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run: the run's counts are inconsistent (%lld primaries of %lld records, %lld text bytes)", n_prim, m, text_bytes);
-	if (sg->text.ensure((size_t)text_bytes) || sg->side.ensure((size_t)side_bytes)) { (void)hipGetLastError(); return set_error(PSVR_ERR_NOMEM, "psvr_signal_run: device allocation failed for %lld bytes of text and %lld of records", text_bytes, side_bytes); }
+	// (text_limit: the caller comes back with fewer pairs; nothing has been written, counted or spent)
+	if (text_limit > 0 && text_bytes > text_limit) return set_error(PSVR_ERR_OVERFLOW, "%s: the text of %lld pairs has %lld bytes (at most %lld)", who, n_prim / 2, text_bytes, text_limit);
+	if (n_prim < 0 || n_prim > 2 * p_max + 1 || text_bytes < 0 || side_bytes < 0) return set_error(PSVR_ERR_DEVICE, "%s: the run's counts are inconsistent (%lld listed records, room for %lld pairs, %lld text bytes)", who, n_prim, p_max, text_bytes);
+	if (sg->text.ensure((size_t)text_bytes) || sg->side.ensure((size_t)side_bytes)) { (void)hipGetLastError(); return set_error(PSVR_ERR_NOMEM, "%s: device allocation failed for %lld bytes of text and %lld of records", who, text_bytes, side_bytes); }
 	if (side_bytes > 0) {                                        // (the error pair is behind the front: P pairs are looked at)
 		const unsigned gs = (unsigned)((P + 256 / kFqGroup - 1) / (256 / kFqGroup));
 		hipLaunchKernelGGL(k_sg_side, dim3(gs), dim3(256), 0, c.stream, addr, (long long)first_record, prim, P, (const int32_t *)sg->sbytes.p, (const long long *)sg->soff.p, sg->side.as<uint8_t>(),
@@ -315,15 +339,16 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	}
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(c.stream));
-	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run: the write pass did not end where the size pass said (the text is not used)");
+	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "%s: the write pass did not end where the size pass said (the text is not used)", who);
 	if (h[kSgStatPair] >= 0) sg->spent = true;
-	sg->valid = true, sg->store = st, sg->store_generation = st->generation, sg->first_record = first_record, sg->pairs = P, sg->text_bytes = text_bytes, sg->side_bytes = side_bytes;
+	sg->valid = true, sg->store = st, sg->store_generation = st ? st->generation : 0, sg->first_record = first_record, sg->pairs = P, sg->text_bytes = text_bytes, sg->side_bytes = side_bytes;
 	sg->n_front = n_front, sg->written = h[kSgWritten], sg->declined = h[kSgDeclined];
 	info->side_bytes = side_bytes;
 	info->pairs = P, info->written = h[kSgWritten], info->declined = h[kSgDeclined], info->first_error = first_err, info->text_bytes = text_bytes;
-	info->consumed = (n_prim & 1) ? first_record + h[kSgLastPrim] : st->n_rec;
 	return PSVR_OK;
 }
+} // namespace psvr
+
 
 extern "C" int psvr_signal_text(psvr_signal_t *sg, void *text, int64_t cap)
 {
@@ -498,6 +523,470 @@ extern "C" int psvr_signal_stats(psvr_signal_t *sg, uint64_t *isize_n, uint64_t 
 	PSVR_HIP(hipMemcpyAsync(isize_n, sg->isize_n.p, (size_t)kSgMaxIsize * 8, hipMemcpyDeviceToHost, c.stream));
 	PSVR_HIP(hipMemcpyAsync(len_n, sg->len_n.p, (size_t)kSgMaxLen * 8, hipMemcpyDeviceToHost, c.stream));
 	drain.armed = false;
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	return PSVR_OK;
+}
+
+// ---- psvr_signal_run_pos: the blocks of the position-sorted mode (signal_mate_device.h) -------------------------------------------------------
+//   k_sg_mark, scan, k_sg_compact   the primaries behind first_record (as psvr_signal_run)     k_sm_end   the record that ends the block
+//   k_sm_fill      a lane per record: pos / mpos / flag / tid == mtid side by side, filled once; the positions the rules do not serve
+//   k_sm_cand      kFqGroup lanes per record: cand(i) over the 4-byte streams, names compared where the records lie; in-degrees by atomicAdd
+//   k_sm_settle    a lane per record: the clean components' links, plain stores      k_sm_class   who is for the replay, whose turn failed
+//   scan, k_sm_dlist, k_sm_replay   the replay list in index order; ONE lane walks it (launched only when the list is not empty)
+//   k_sm_flags, scan x3, k_sm_lists   pair list (into prim, for the passes of psvr_signal_run), the unmated records' indices and lengths, notes
+//   scan, k_sm_left   the unmated records side by side
+// Bounds: every index a kernel follows (cand, mate, list entries) is checked against n where it is read from memory another kernel wrote.
+namespace psvr {
+
+// mctl[]: 0 the first primary that ends the block, 1 positions not served (1 decreasing, 2 index overflow), 2 2 x pairs, 3 unmated, 4 failed turns,
+// 5 the block's last record behind first_record, 6 unmated bytes, 7 an index out of range
+enum { kSmEnd = 0, kSmBad, kSmPairs2, kSmLeft, kSmFail, kSmLastRec, kSmLeftBytes, kSmRange, kSmCtl = 8 };
+
+struct SmRec {
+	const uint64_t *addr;
+	long long first;
+	const uint32_t *bprim;
+	__device__ const uint8_t *operator()(int32_t i) const { return (const uint8_t *)(uintptr_t)addr[first + bprim[i]]; }
+};
+
+__global__ __launch_bounds__(256) void k_sm_end(SmRec R, const long long *n_prim, long long limit, long long span, long long *mctl)
+{
+	const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (j < 1 || j >= *n_prim || j >= limit) return;
+	const uint8_t *r0 = R(0), *r = R((int32_t)j);
+	if (sm_ends_block(bam_i32(r0 + 4), bam_i32(r0 + 8), bam_i32(r + 4), bam_i32(r + 8), span)) atomicMin((unsigned long long *)&mctl[kSmEnd], (unsigned long long)j);
+}
+__global__ __launch_bounds__(256) void k_sm_fill(SmRec R, long long n, int32_t *pos, int32_t *mpos, uint32_t *flag, int32_t *same, long long *mctl)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const uint8_t *r0 = R(0), *r = R((int32_t)i);
+	const int32_t tid = bam_i32(r + 4), p = bam_i32(r + 8);
+	pos[i] = p, mpos[i] = bam_i32(r + 28), flag[i] = bam_u16(r + 18), same[i] = tid == bam_i32(r + 24);
+	const int bad = sm_pos_bad(n, i, bam_i32(r0 + 4), bam_i32(r0 + 8), i > 0 ? bam_i32(R((int32_t)i - 1) + 8) : 0, tid, p);
+	if (bad) atomicMin((unsigned long long *)&mctl[kSmBad], (unsigned long long)bad);   // (the smaller code wins, as in the host build)
+}
+__global__ __launch_bounds__(256) void k_sm_cand(SmRec R, long long n, const int32_t *pos, const int32_t *mpos, const int32_t *same, int32_t *cand, int32_t *indeg)
+{
+	const SgGroupIds G = sg_group();
+	if (G.p >= n) return;                                    // (the whole group)
+	const int32_t c = sm_cand(G.g, (int32_t)n, bam_i32(R(0) + 4), pos, mpos, same, R, (int32_t)G.p);
+	if (G.g.lane == 0) {
+		cand[G.p] = c;
+		if (c >= 0) atomicAdd(&indeg[c], 1);
+	}
+}
+__global__ __launch_bounds__(256) void k_sm_settle(long long n, const int32_t *cand, const int32_t *indeg, int32_t *mate, long long *mctl)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i >= n) return;
+	const int32_t m = cand[i];
+	if (m >= n || m == i) { mctl[kSmRange] = 1; return; }
+	if (m >= 0 && (cand[m] >= n || cand[m] == m)) return;    // (that lane reports it)
+	if (sm_clean(cand, indeg, (int32_t)i)) mate[i] = m, mate[m] = (int32_t)i;
+}
+__global__ __launch_bounds__(256) void k_sm_class(long long n, const int32_t *cand, const int32_t *indeg, const int32_t *mate, int32_t *dirty, int32_t *fail)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i > n) return;
+	int32_t f = 0;
+	const bool d = i < n && sm_dirty(cand, indeg, mate, (int32_t)i, &f);
+	dirty[i] = d, fail[i] = f;
+}
+__global__ __launch_bounds__(256) void k_sm_dlist(long long n, const int32_t *dirty, const long long *doff, int32_t *dlist)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i < n && dirty[i] && doff[i] >= 0 && doff[i] < n) dlist[doff[i]] = (int32_t)i;
+}
+__global__ void k_sm_replay(const int32_t *dlist, long long n_list, const int32_t *cand, int32_t *mate, int32_t *fail) { sm_replay(dlist, n_list, cand, mate, fail); }
+__global__ __launch_bounds__(256) void k_sm_flags(long long n, const int32_t *mate, const uint32_t *flag, int32_t *pflag, int32_t *lflag, int32_t *lbytes)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i > n) return;
+	pflag[i] = i < n && sm_is_pair(n, mate, flag, i), lflag[i] = i < n && mate[i] == kSmFree, lbytes[i] = 0;
+}
+__global__ __launch_bounds__(256) void k_sm_lists(SmRec R, long long n, const int32_t *pos, const int32_t *mate, const int32_t *pflag, const int32_t *lflag, const int32_t *fail, const long long *pfoff,
+                                                  const long long *lfoff, const long long *ffoff, long long fail_base, long long note_cap, uint32_t *prim, uint32_t *llist, int32_t *lbytes,
+                                                  psvr_signal_mate_note_t *notes, long long *mctl)
+{
+	const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (i > n) return;
+	if (i == n) {
+		mctl[kSmPairs2] = 2 * pfoff[n], mctl[kSmLeft] = lfoff[n], mctl[kSmFail] = ffoff[n], mctl[kSmLastRec] = n > 0 ? (long long)R.bprim[n - 1] : -1;
+		return;
+	}
+	if (pflag[i]) {
+		const int32_t m = mate[i];
+		const long long r = pfoff[i];
+		if (m < 0 || m >= n || r < 0 || r >= n) mctl[kSmRange] = 1;
+		else prim[2 * r] = R.bprim[i], prim[2 * r + 1] = R.bprim[m];
+	}
+	if (lflag[i]) {
+		const long long r = lfoff[i];
+		if (r < 0 || r >= n) mctl[kSmRange] = 1;
+		else llist[r] = R.bprim[i], lbytes[r] = (int32_t)(4 + bam_u32(R((int32_t)i)));   // (a record the store holds has at most 0x7ffffff0 + 4 bytes)
+	}
+	if (fail[i]) {
+		const long long turn = fail_base + ffoff[i] + 1, slot = sm_note_slot(fail_base, turn);
+		if (slot >= note_cap) mctl[kSmRange] = 1;
+		else if (slot >= 0) {
+			const uint8_t *r = R((int32_t)i);
+			psvr_signal_mate_note_t &o = notes[slot];
+			o.number = turn, o.index = (int32_t)i, o.block = (int32_t)n, o.tid = bam_i32(r + 4), o.pos = pos[i];
+			uint32_t k = 0;
+			for (; k < r[12] && k < 255 && r[kBamRecHead + k]; ++k) o.name[k] = (char)r[kBamRecHead + k];
+			for (; k < 256; ++k) o.name[k] = 0;
+		}
+	}
+}
+__global__ void k_sm_left_sum(const long long *lboff, long long n, long long *mctl) { mctl[kSmLeftBytes] = lboff[n]; }
+__global__ __launch_bounds__(256) void k_sm_left(const uint64_t *addr, long long first, const uint32_t *llist, long long n_left, const int32_t *lbytes, const long long *lboff, uint8_t *left,
+                                                 long long left_bytes, uint64_t *laddr, long long *mctl)
+{
+	const SgGroupIds G = sg_group();
+	if (G.p >= n_left) return;                               // (the whole group)
+	const uint8_t *r = (const uint8_t *)(uintptr_t)addr[first + llist[G.p]];
+	const long long at = lboff[G.p], len = lbytes[G.p];
+	if (at < 0 || len != 4 + (long long)bam_u32(r) || at + len > left_bytes) { if (G.g.lane == 0) mctl[kSmRange] = 1; return; }
+	copy_aligned_lanes(r, left + at, len, G.g.lane, kFqGroup);
+	if (G.g.lane == 0) laddr[G.p] = (uint64_t)(uintptr_t)(left + at);   // the left store's table: where the copy lies
+}
+
+// ---- psvr_signal_run_left: the by-name pass over the left store ----
+//   sort_order_names_device   the host comparator's order: name by strcmp, records with 0x40 first, append order
+//   k_sl_head      kFqGroup lanes per rank: does a run of equal names begin here?     scan, k_sl_start   where every run begins
+//   k_sl_flags     a lane per rank: an even place in its run with a partner behind it is a pair; an even last place of a run that is not the
+//                  last run is a pairing-error step     scan x2, k_sl_pairs   the pair list and, per pair, the error steps in front of it
+struct SlRec {
+	const uint64_t *laddr;
+	const uint32_t *ord;                                     // nullptr: the append order stands
+	__device__ uint32_t at(long long j) const { return ord ? ord[j] : (uint32_t)j; }
+	__device__ const uint8_t *operator()(long long j) const { return (const uint8_t *)(uintptr_t)laddr[at(j)]; }
+};
+__global__ __launch_bounds__(256) void k_sl_head(SlRec R, long long n, int32_t *head)
+{
+	const SgGroupIds G = sg_group();
+	if (G.p > n) return;                                     // (the whole group)
+	bool h = G.p == 0 && n > 0;
+	if (G.p > 0 && G.p < n) {
+		if (R.at(G.p) >= n || R.at(G.p - 1) >= n) return;    // (an order is a permutation: always)
+		h = !sg_same_name(G.g, R(G.p - 1), R(G.p));
+	}
+	if (G.g.lane == 0) head[G.p] = h;
+}
+__global__ __launch_bounds__(256) void k_sl_start(long long n, const int32_t *head, const long long *hoff, int32_t *start)
+{
+	const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (j < n && head[j] && hoff[j] >= 0 && hoff[j] < n) start[hoff[j]] = (int32_t)j;
+}
+__global__ __launch_bounds__(256) void k_sl_flags(long long n, const int32_t *head, const long long *hoff, const int32_t *start, int32_t *pflag, int32_t *eflag)
+{
+	const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (j > n) return;
+	int32_t p = 0, e = 0;
+	if (j < n) {
+		const long long run = hoff[j] + head[j] - 1;         // (head[0] is 1: never negative)
+		const long long off = run >= 0 && run < n ? j - start[run] : 1;   // (an odd place is neither)
+		const bool partner = j + 1 < n && !head[j + 1];
+		p = sm_left_is_pair(off, partner), e = sm_left_is_error(off, partner, j + 1 == n);
+	}
+	pflag[j] = p, eflag[j] = e;
+}
+__global__ __launch_bounds__(256) void k_sl_pairs(SlRec R, long long n, const int32_t *pflag, const long long *pfoff, const long long *efoff, uint32_t *lprim, long long *lerr, long long *lctl)
+{
+	const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+	if (j > n) return;
+	if (j == n) { lctl[0] = pfoff[n], lctl[1] = efoff[n]; return; }
+	if (!pflag[j]) return;
+	const long long r = pfoff[j];
+	if (r < 0 || 2 * r + 1 >= n || R.at(j) >= n || R.at(j + 1) >= n) { lctl[2] = 1; return; }
+	lprim[2 * r] = R.at(j), lprim[2 * r + 1] = R.at(j + 1), lerr[r] = efoff[j];
+}
+
+} // namespace psvr
+
+extern "C" int psvr_signal_run_pos(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t first_record, int32_t finish, const psvr_signal_pos_opt_t *opt, psvr_signal_info_t *info,
+                                   psvr_signal_pos_info_t *pi)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || !st || !info || !pi) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: null argument");
+	if (st->device != sg->device) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: the store is on device %d, the signal object on device %d", st->device, sg->device);
+	const long long limit = opt && opt->block_records ? opt->block_records : kSmRecords, span = opt && opt->block_span ? opt->block_span : kSmSpan;
+	if (limit < 2 || limit >= (1ll << 31) - 1 || span < 0) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: a block of %lld records and a span of %lld", limit, span);
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	if (int rc = store_refresh(st, c, true)) return rc;
+	sg->valid = false, sg->win_valid = false, sg->pos_valid = false;
+	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: the store has been ordered: the blocks are those of its append order");
+	if (first_record < 0 || first_record > st->n_rec) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: first record %lld of %lld", (long long)first_record, st->n_rec);
+	const long long m = st->n_rec - first_record;
+	if (m >= (1ll << 31) - 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_pos: %lld records behind the first (at most 2^31 - 2)", m);
+	*pi = psvr_signal_pos_info_t{0, 0, 0, 0, 0, sg->mate_failed, 0, 0};
+	*info = psvr_signal_info_t{0, 0, 0, -1, 0, 0, 0};
+	if (!sg->h_mctl && hipHostMalloc((void **)&sg->h_mctl, kSmCtl * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); sg->h_mctl = nullptr; return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_pos: no page-locked memory"); }
+	if (sg->mark.ensure((size_t)(m + 1) * 4) || sg->poff.ensure((size_t)(m + 1) * 8) || sg->prim.ensure((size_t)(2 * m + 4) * 4) || sg->tmp.ensure(scan_tmp_bytes(3, m + 2)) || sg->mctl.ensure(kSmCtl * 8)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_pos: device allocation failed for the tables of %lld records", m);
+	}
+	long long *ctl = sg->ctl.as<long long>(), *mctl = sg->mctl.as<long long>();
+	long long *h = sg->h_ctl, *hm = sg->h_mctl;
+	for (int k = 0; k < kSgCtl; ++k) h[k] = 0;
+	h[kSgFirstErr] = h[kSgFirstWritten] = kSgNone, h[kSgStatPair] = -1, h[kSgLastPrim] = -1;
+	for (int k = 0; k < kSmCtl; ++k) hm[k] = 0;
+	hm[kSmEnd] = hm[kSmBad] = kSgNone;
+	const uint64_t *addr = (const uint64_t *)st->addr.p;
+	const long long *poff = (const long long *)sg->poff.p;
+	const unsigned g_rec = (unsigned)((m + 256) / 256);
+	StreamDrain drain{c.stream};
+	// the primaries behind first_record and the record that ends the block
+	PSVR_HIP(hipMemcpyAsync(ctl, h, kSgCtl * 8, hipMemcpyHostToDevice, c.stream));
+	PSVR_HIP(hipMemcpyAsync(mctl, hm, kSmCtl * 8, hipMemcpyHostToDevice, c.stream));
+	hipLaunchKernelGGL(k_sg_mark, dim3(g_rec), dim3(256), 0, c.stream, addr, (long long)first_record, m, sg->mark.as<int32_t>(), ctl);
+	ScanSet X = {};
+	X.cnt[0] = sg->mark.as<int32_t>(), X.out[0] = sg->poff.as<long long>(), X.stride[0] = 1;
+	scan_launch(X, 1, m + 1, sg->tmp.as<long long>(), c.stream);
+	hipLaunchKernelGGL(k_sg_compact, dim3(g_rec), dim3(256), 0, c.stream, (const int32_t *)sg->mark.p, poff, m, sg->prim.as<uint32_t>());
+	SmRec R0{addr, (long long)first_record, (const uint32_t *)sg->prim.p};
+	hipLaunchKernelGGL(k_sm_end, dim3((unsigned)((std::min(m, limit) + 256) / 256)), dim3(256), 0, c.stream, R0, poff + m, limit, span, mctl);
+	PSVR_HIP(hipGetLastError());
+	long long avail = 0;
+	PSVR_HIP(hipMemcpyAsync(&avail, poff + m, 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipMemcpyAsync(hm, mctl, kSmCtl * 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipMemcpyAsync(h + kSgRefused, ctl + kSgRefused, 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	if (h[kSgRefused]) return set_error(PSVR_ERR_IO, "psvr_signal_run_pos: malformed BAM record among records [%lld, %lld) of the store (BamReader's rules refuse it)", (long long)first_record, st->n_rec);
+	if (avail < 0 || avail > m) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run_pos: %lld primaries of %lld records", avail, m);
+	bool complete = false;
+	const long long end = hm[kSmEnd] == kSgNone ? avail : hm[kSmEnd];
+	const long long n = sm_block_size(avail, end, limit, finish != 0, &complete);
+	if (!complete) return PSVR_OK;
+	pi->complete = 1, pi->primaries = n;
+	if (n < 2) {                                             // (the input has ended: the host loop drops a single record)
+		sg->valid = true, sg->pos_valid = true, sg->store = st, sg->store_generation = st->generation, sg->first_record = first_record;
+		sg->pairs = sg->text_bytes = sg->side_bytes = sg->n_front = sg->written = sg->declined = sg->left_bytes = sg->n_notes = 0;
+		pi->consumed = info->consumed = st->n_rec;
+		return PSVR_OK;
+	}
+	const long long p_max = n, note_cap = n / 1000 + 2;   // (records without flag 0x80 on both sides of a link make two pairs: up to n - 1)
+	const size_t n4 = (size_t)(n + 1) * 4, n8 = (size_t)(n + 1) * 8;
+	if (sg->bprim.ensure(n4) || sg->spos.ensure(n4) || sg->smpos.ensure(n4) || sg->sflag.ensure(n4) || sg->ssame.ensure(n4) || sg->cand.ensure(n4) || sg->indeg.ensure(n4) || sg->mate.ensure(n4) ||
+	    sg->dirty.ensure(n4) || sg->fail.ensure(n4) || sg->doff.ensure(n8) || sg->dlist.ensure(n4) || sg->pflag.ensure(n4) || sg->lflag.ensure(n4) || sg->pfoff.ensure(n8) || sg->lfoff.ensure(n8) ||
+	    sg->ffoff.ensure(n8) || sg->lbytes.ensure(n4) || sg->lboff.ensure(n8) || sg->notes.ensure((size_t)note_cap * sizeof(psvr_signal_mate_note_t)) || sg->state.ensure((size_t)p_max + 1) ||
+	    sg->note.ensure((size_t)p_max + 1) || sg->bytes.ensure((size_t)(p_max + 1) * 4) || sg->toff.ensure((size_t)(p_max + 1) * 8) || sg->sbytes.ensure((size_t)(p_max + 1) * 4) ||
+	    sg->soff.ensure((size_t)(p_max + 1) * 8)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_pos: device allocation failed for the tables of a block of %lld records", n);
+	}
+	const unsigned g_n = (unsigned)((n + 256) / 256), g_ngrp = (unsigned)((n + 256 / kFqGroup - 1) / (256 / kFqGroup));
+	int32_t *pos = sg->spos.as<int32_t>(), *mpos = sg->smpos.as<int32_t>(), *same = sg->ssame.as<int32_t>(), *cand = sg->cand.as<int32_t>(), *indeg = sg->indeg.as<int32_t>(), *mate = sg->mate.as<int32_t>();
+	uint32_t *flag = sg->sflag.as<uint32_t>();
+	PSVR_HIP(hipMemcpyAsync(sg->bprim.p, sg->prim.p, (size_t)n * 4, hipMemcpyDeviceToDevice, c.stream));
+	PSVR_HIP(hipMemsetAsync(indeg, 0, n4, c.stream));
+	PSVR_HIP(hipMemsetAsync(mate, 0xff, n4, c.stream));
+	SmRec R{addr, (long long)first_record, (const uint32_t *)sg->bprim.p};
+	hipLaunchKernelGGL(k_sm_fill, dim3(g_n), dim3(256), 0, c.stream, R, n, pos, mpos, flag, same, mctl);
+	hipLaunchKernelGGL(k_sm_cand, dim3(g_ngrp), dim3(256), 0, c.stream, R, n, (const int32_t *)pos, (const int32_t *)mpos, (const int32_t *)same, cand, indeg);
+	hipLaunchKernelGGL(k_sm_settle, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)cand, (const int32_t *)indeg, mate, mctl);
+	hipLaunchKernelGGL(k_sm_class, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)cand, (const int32_t *)indeg, (const int32_t *)mate, sg->dirty.as<int32_t>(), sg->fail.as<int32_t>());
+	ScanSet D = {};
+	D.cnt[0] = sg->dirty.as<int32_t>(), D.out[0] = sg->doff.as<long long>(), D.stride[0] = 1;
+	scan_launch(D, 1, n + 1, sg->tmp.as<long long>(), c.stream);
+	hipLaunchKernelGGL(k_sm_dlist, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)sg->dirty.p, (const long long *)sg->doff.p, sg->dlist.as<int32_t>());
+	PSVR_HIP(hipGetLastError());
+	long long n_dirty = 0;
+	PSVR_HIP(hipMemcpyAsync(&n_dirty, sg->doff.as<long long>() + n, 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipMemcpyAsync(hm, mctl, kSmCtl * 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	if (hm[kSmBad] == kSgNone) hm[kSmBad] = 0;
+	if (hm[kSmBad] == 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_pos: positions decrease inside a block of %lld records (is the input sorted by position?)", n);
+	if (hm[kSmBad]) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_pos: a position of the block overflows the host loop's position index");
+	if (hm[kSmRange] || n_dirty < 0 || n_dirty > n) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run_pos: the candidate table of a block of %lld records is inconsistent", n);
+	if (n_dirty > 0) hipLaunchKernelGGL(k_sm_replay, dim3(1), dim3(1), 0, c.stream, (const int32_t *)sg->dlist.p, n_dirty, (const int32_t *)cand, mate, sg->fail.as<int32_t>());
+	hipLaunchKernelGGL(k_sm_flags, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)mate, (const uint32_t *)flag, sg->pflag.as<int32_t>(), sg->lflag.as<int32_t>(), sg->lbytes.as<int32_t>());
+	ScanSet F = {};
+	F.cnt[0] = sg->pflag.as<int32_t>(), F.out[0] = sg->pfoff.as<long long>(), F.stride[0] = 1;
+	F.cnt[1] = sg->lflag.as<int32_t>(), F.out[1] = sg->lfoff.as<long long>(), F.stride[1] = 1;
+	F.cnt[2] = sg->fail.as<int32_t>(), F.out[2] = sg->ffoff.as<long long>(), F.stride[2] = 1;
+	scan_launch(F, 3, n + 1, sg->tmp.as<long long>(), c.stream);
+	hipLaunchKernelGGL(k_sm_lists, dim3(g_n), dim3(256), 0, c.stream, R, n, (const int32_t *)pos, (const int32_t *)mate, (const int32_t *)sg->pflag.p, (const int32_t *)sg->lflag.p,
+	                   (const int32_t *)sg->fail.p, (const long long *)sg->pfoff.p, (const long long *)sg->lfoff.p, (const long long *)sg->ffoff.p, sg->mate_failed, note_cap, sg->prim.as<uint32_t>(),
+	                   sg->dlist.as<uint32_t>(), sg->lbytes.as<int32_t>(), sg->notes.as<psvr_signal_mate_note_t>(), mctl);
+	ScanSet L = {};
+	L.cnt[0] = sg->lbytes.as<int32_t>(), L.out[0] = sg->lboff.as<long long>(), L.stride[0] = 1;
+	scan_launch(L, 1, n + 1, sg->tmp.as<long long>(), c.stream);
+	hipLaunchKernelGGL(k_sm_left_sum, dim3(1), dim3(1), 0, c.stream, (const long long *)sg->lboff.p, n, mctl);
+	PSVR_HIP(hipGetLastError());
+	PSVR_HIP(hipMemcpyAsync(hm, mctl, kSmCtl * 8, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	const long long n_left = hm[kSmLeft], left_bytes = hm[kSmLeftBytes], fails = hm[kSmFail];
+	if (hm[kSmRange] || hm[kSmPairs2] < 0 || hm[kSmPairs2] / 2 > p_max || n_left < 0 || n_left > n || left_bytes < 0 || fails < 0 || fails > n || hm[kSmLastRec] < 0 || hm[kSmLastRec] >= m)
+		return set_error(PSVR_ERR_DEVICE, "psvr_signal_run_pos: the lists of a block of %lld records are inconsistent", n);
+	// the left store takes them, device to device: a chunk per block, and the table grows by doubling
+	std::unique_ptr<DevBuf> chunk(new DevBuf);
+	// (whole 8-byte words: k_name_chunk loads the aligned words a name touches)
+	if (chunk->alloc(((size_t)left_bytes + 7) & ~(size_t)7)) { (void)hipGetLastError(); return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_pos: device allocation failed for %lld bytes of unmated records", left_bytes); }
+	if (sg->left_n + n_left > sg->laddr_cap) {
+		const long long cap = std::max(2 * sg->laddr_cap, sg->left_n + n_left + 1024);
+		DevBuf grown;
+		if (grown.alloc((size_t)cap * 8)) { (void)hipGetLastError(); return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_pos: device allocation failed for the table of %lld unmated records", cap); }
+		if (sg->left_n) PSVR_HIP(hipMemcpyAsync(grown.p, sg->laddr.p, (size_t)sg->left_n * 8, hipMemcpyDeviceToDevice, c.stream));
+		PSVR_HIP(hipStreamSynchronize(c.stream));
+		std::swap(sg->laddr.p, grown.p), std::swap(sg->laddr.bytes, grown.bytes);
+		sg->laddr_cap = cap;
+	}
+	if (n_left > 0) {
+		hipLaunchKernelGGL(k_sm_left, dim3((unsigned)((n_left + 256 / kFqGroup - 1) / (256 / kFqGroup))), dim3(256), 0, c.stream, addr, (long long)first_record, (const uint32_t *)sg->dlist.p, n_left,
+		                   (const int32_t *)sg->lbytes.p, (const long long *)sg->lboff.p, chunk->as<uint8_t>(), left_bytes, sg->laddr.as<uint64_t>() + sg->left_n, mctl);
+		PSVR_HIP(hipGetLastError());
+		PSVR_HIP(hipMemcpyAsync(hm + kSmRange, mctl + kSmRange, 8, hipMemcpyDeviceToHost, c.stream));
+		PSVR_HIP(hipStreamSynchronize(c.stream));
+		if (hm[kSmRange]) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run_pos: the unmated records do not lie where their lengths said");
+	}
+	drain.armed = false;
+	// the pairs through the passes of psvr_signal_run (the ctl upload lies in front of them on the stream)
+	if (int rc = sg_run_pairs(sg, addr, st, c, first_record, (const long long *)(mctl + kSmPairs2), p_max, "psvr_signal_run_pos", info)) return rc;
+	sg->left_chunks.push_back(std::move(chunk)), sg->left_n += n_left, sg->left_ordered = false, sg->left_valid = false;   // (a block whose pair passes failed keeps its unmated records out)
+	sg->pos_valid = true, sg->left_bytes = left_bytes, sg->n_notes = sm_note_count(sg->mate_failed, fails), sg->mate_failed += fails;
+	pi->consumed = info->consumed = first_record + hm[kSmLastRec] + 1;
+	pi->unmated = n_left, pi->left_bytes = left_bytes, pi->mate_failed = sg->mate_failed, pi->notes = sg->n_notes, pi->replayed = n_dirty;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_mate_notes(psvr_signal_t *sg, psvr_signal_mate_note_t *notes, int64_t cap)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || cap < 0 || (cap > 0 && !notes)) return set_error(PSVR_ERR_ARG, "psvr_signal_mate_notes: bad argument");
+	if (!sg->valid || !sg->pos_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_mate_notes: no block");
+	if (cap < sg->n_notes) return set_error(PSVR_ERR_OVERFLOW, "psvr_signal_mate_notes: the block has %lld notes, the table has room for %lld", sg->n_notes, (long long)cap);
+	if (sg->n_notes == 0) return PSVR_OK;
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	PSVR_HIP(hipMemcpyAsync(notes, sg->notes.p, (size_t)sg->n_notes * sizeof(psvr_signal_mate_note_t), hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_left(psvr_signal_t *sg, void *bytes, int64_t cap)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || cap < 0 || (cap > 0 && !bytes)) return set_error(PSVR_ERR_ARG, "psvr_signal_left: bad argument");
+	if (!sg->valid || !sg->pos_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_left: no block");
+	if (cap < sg->left_bytes) return set_error(PSVR_ERR_OVERFLOW, "psvr_signal_left: the block's unmated records have %lld bytes, the buffer has %lld", sg->left_bytes, (long long)cap);
+	if (sg->left_bytes == 0 || sg->left_chunks.empty()) return PSVR_OK;
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	PSVR_HIP(hipMemcpyAsync(bytes, sg->left_chunks.back()->p, (size_t)sg->left_bytes, hipMemcpyDeviceToHost, c.stream));
+	PSVR_HIP(hipStreamSynchronize(c.stream));
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_run_left(psvr_signal_t *sg, int64_t first_pair, int64_t max_pairs, psvr_signal_info_t *info, psvr_signal_left_info_t *li)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || !info || !li || first_pair < 0 || max_pairs < 1) return set_error(PSVR_ERR_ARG, "psvr_signal_run_left: bad argument");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	sg->valid = false, sg->win_valid = false, sg->pos_valid = false, sg->left_valid = false;
+	const long long n = sg->left_n;
+	if (n >= (1ll << 31) - 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_left: %lld unmated records (at most 2^31 - 2)", n);
+	if (n & 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_left: an odd number of records found no mate (%lld): the host loop ends there", n);
+	*info = psvr_signal_info_t{0, 0, 0, -1, 0, 0, 0};
+	long long *hm = sg->h_mctl;
+	if (!hm && n > 0) return set_error(PSVR_ERR_ARG, "psvr_signal_run_left: no block has been run");
+	if (!sg->left_ordered && n > 0) {
+		const size_t n4 = (size_t)(n + 1) * 4, n8 = (size_t)(n + 1) * 8;
+		if (sg->lkeys.ensure(n8) || sg->dirty.ensure(n4) || sg->doff.ensure(n8) || sg->dlist.ensure(n4) || sg->pflag.ensure(n4) || sg->lflag.ensure(n4) || sg->pfoff.ensure(n8) || sg->lfoff.ensure(n8) ||
+		    sg->lprim.ensure(n4 + 8) || sg->lerr.ensure(n8) || sg->lctl.ensure(32) || sg->tmp.ensure(scan_tmp_bytes(2, n + 1))) {
+			(void)hipGetLastError();
+			return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_left: device allocation failed for the tables of %lld unmated records", n);
+		}
+		const NameSrc src = {(const uint64_t *)sg->laddr.p, nullptr, 0, nullptr, nullptr, 1};
+		const uint32_t *ord = nullptr;
+		if (int rc = sort_order_names_device(c.stream, n, src, sg->lkeys.as<uint64_t>(), sg->lN, sg->lS, sg->lhist, &ord, "psvr_signal_run_left")) return rc;
+		const SlRec R{(const uint64_t *)sg->laddr.p, ord};
+		const unsigned g_n = (unsigned)((n + 256) / 256), g_grp = (unsigned)((n + 1 + 256 / kFqGroup - 1) / (256 / kFqGroup));
+		int32_t *head = sg->dirty.as<int32_t>(), *start = sg->dlist.as<int32_t>();
+		StreamDrain drain{c.stream};
+		PSVR_HIP(hipMemsetAsync(sg->lctl.p, 0, 32, c.stream));
+		PSVR_HIP(hipMemsetAsync(head, 0, n4, c.stream));
+		hipLaunchKernelGGL(k_sl_head, dim3(g_grp), dim3(256), 0, c.stream, R, n, head);
+		ScanSet H = {};
+		H.cnt[0] = head, H.out[0] = sg->doff.as<long long>(), H.stride[0] = 1;
+		scan_launch(H, 1, n + 1, sg->tmp.as<long long>(), c.stream);
+		hipLaunchKernelGGL(k_sl_start, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)head, (const long long *)sg->doff.p, start);
+		hipLaunchKernelGGL(k_sl_flags, dim3(g_n), dim3(256), 0, c.stream, n, (const int32_t *)head, (const long long *)sg->doff.p, (const int32_t *)start, sg->pflag.as<int32_t>(), sg->lflag.as<int32_t>());
+		ScanSet F = {};
+		F.cnt[0] = sg->pflag.as<int32_t>(), F.out[0] = sg->pfoff.as<long long>(), F.stride[0] = 1;
+		F.cnt[1] = sg->lflag.as<int32_t>(), F.out[1] = sg->lfoff.as<long long>(), F.stride[1] = 1;
+		scan_launch(F, 2, n + 1, sg->tmp.as<long long>(), c.stream);
+		hipLaunchKernelGGL(k_sl_pairs, dim3(g_n), dim3(256), 0, c.stream, R, n, (const int32_t *)sg->pflag.p, (const long long *)sg->pfoff.p, (const long long *)sg->lfoff.p, sg->lprim.as<uint32_t>(),
+		                   sg->lerr.as<long long>(), sg->lctl.as<long long>());
+		PSVR_HIP(hipGetLastError());
+		PSVR_HIP(hipMemcpyAsync(hm, sg->lctl.p, 24, hipMemcpyDeviceToHost, c.stream));
+		drain.armed = false;
+		PSVR_HIP(hipStreamSynchronize(c.stream));
+		if (hm[2] || hm[0] < 0 || 2 * hm[0] > n || hm[1] < 0 || hm[1] > n) return set_error(PSVR_ERR_DEVICE, "psvr_signal_run_left: the pair list of %lld unmated records is inconsistent", n);
+		sg->left_pairs = hm[0], sg->left_errors = hm[1], sg->left_ordered = true;
+	}
+	if (n == 0) sg->left_pairs = sg->left_errors = 0, sg->left_ordered = true;
+	const long long P = sg->left_pairs;
+	if (first_pair > P) return set_error(PSVR_ERR_ARG, "psvr_signal_run_left: first pair %lld of %lld", (long long)first_pair, P);
+	// A slice's text stays below 2 GiB whatever the file: a slice whose size pass counts more is halved until it fits (one pair always does:
+	// a pair of 2 GiB of text is the host formatter's).  PSVR_SIGNAL_TEXT_LIMIT: a smaller limit, for the tests.
+	const char *e_limit = getenv("PSVR_SIGNAL_TEXT_LIMIT");
+	const long long text_limit = e_limit && atoll(e_limit) > 0 ? atoll(e_limit) : 0x7fffffffll;
+	long long cnt = std::min<long long>(max_pairs, P - first_pair);
+	if (cnt == 0) {
+		*li = psvr_signal_left_info_t{n, P, sg->left_errors, first_pair, 0, 0};
+		sg->slice_first = first_pair, sg->slice_pairs = 0;
+		sg->valid = true, sg->left_valid = true, sg->store = nullptr;
+		sg->pairs = sg->text_bytes = sg->side_bytes = sg->n_front = sg->written = sg->declined = 0;
+		return PSVR_OK;
+	}
+	if (sg->prim.ensure((size_t)(2 * cnt + 4) * 4) || sg->state.ensure((size_t)cnt + 1) || sg->note.ensure((size_t)cnt + 1) || sg->bytes.ensure((size_t)(cnt + 1) * 4) || sg->toff.ensure((size_t)(cnt + 1) * 8) ||
+	    sg->sbytes.ensure((size_t)(cnt + 1) * 4) || sg->soff.ensure((size_t)(cnt + 1) * 8) || sg->tmp.ensure(scan_tmp_bytes(2, cnt + 1)) || sg->mctl.ensure(kSmCtl * 8)) {
+		(void)hipGetLastError();
+		return set_error(PSVR_ERR_NOMEM, "psvr_signal_run_left: device allocation failed for the tables of %lld pairs", cnt);
+	}
+	for (;; cnt = (cnt + 1) / 2) {
+		long long *h = sg->h_ctl;
+		for (int k = 0; k < kSgCtl; ++k) h[k] = 0;
+		h[kSgFirstErr] = h[kSgFirstWritten] = kSgNone, h[kSgStatPair] = -1, h[kSgLastPrim] = -1;
+		for (int k = 0; k < kSmCtl; ++k) hm[k] = 0;
+		hm[kSmPairs2] = 2 * cnt;
+		{
+			StreamDrain drain{c.stream};
+			PSVR_HIP(hipMemcpyAsync(sg->ctl.p, h, kSgCtl * 8, hipMemcpyHostToDevice, c.stream));
+			PSVR_HIP(hipMemcpyAsync(sg->mctl.p, hm, kSmCtl * 8, hipMemcpyHostToDevice, c.stream));
+			PSVR_HIP(hipMemcpyAsync(sg->prim.p, sg->lprim.as<uint32_t>() + 2 * first_pair, (size_t)cnt * 8, hipMemcpyDeviceToDevice, c.stream));
+			drain.armed = false;
+		}
+		const int rc = sg_run_pairs(sg, (const uint64_t *)sg->laddr.p, nullptr, c, 0, (const long long *)(sg->mctl.as<long long>() + kSmPairs2), cnt, "psvr_signal_run_left", info, cnt > 1 ? text_limit : 0);
+		if (rc == PSVR_ERR_OVERFLOW && cnt > 1) continue;        // (every wait of the refused pass is over: the tables are free to be filled again)
+		if (rc) return rc;
+		break;
+	}
+	*li = psvr_signal_left_info_t{n, P, sg->left_errors, first_pair, cnt, first_pair + cnt < P};
+	sg->slice_first = first_pair, sg->slice_pairs = cnt;
+	sg->left_valid = true;
+	return PSVR_OK;
+}
+
+extern "C" int psvr_signal_left_errors(psvr_signal_t *sg, int64_t *errors, int64_t cap)
+{
+	if (psvr_device_count() <= 0) return sg_no_device();
+	if (!sg || cap < 0 || (cap > 0 && !errors)) return set_error(PSVR_ERR_ARG, "psvr_signal_left_errors: bad argument");
+	if (!sg->valid || !sg->left_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_left_errors: no slice");
+	if (cap < sg->slice_pairs) return set_error(PSVR_ERR_OVERFLOW, "psvr_signal_left_errors: the slice has %lld pairs, the table has room for %lld", sg->slice_pairs, (long long)cap);
+	if (sg->slice_pairs == 0) return PSVR_OK;
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);
+	if (int rc = dfw_bind(c, sg->device)) return rc;
+	PSVR_HIP(hipMemcpyAsync(errors, sg->lerr.as<long long>() + sg->slice_first, (size_t)sg->slice_pairs * 8, hipMemcpyDeviceToHost, c.stream));
 	PSVR_HIP(hipStreamSynchronize(c.stream));
 	return PSVR_OK;
 }

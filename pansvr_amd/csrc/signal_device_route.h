@@ -34,6 +34,7 @@
 // state, in front of which everything has been handed over.  The messages carry the command's name; everything else is one code.
 #pragma once
 #include <sys/stat.h>
+#include <chrono>
 #include <string>
 #include <vector>
 #include "../../include/psvr_engine.h"
@@ -49,7 +50,11 @@ struct SignalWindowTaker {
 	virtual long long offer(const psvr_signal_window_info_t &info, std::string *why) = 0;
 };
 
-struct SignalRouteStats { long long pairs = 0, written = 0, declined = 0, runs = 0, text_bytes = 0, peak_chunks = 0, peak_bytes = 0; };
+struct SignalRouteStats {
+	long long pairs = 0, written = 0, declined = 0, runs = 0, text_bytes = 0, peak_chunks = 0, peak_bytes = 0;
+	long long left_pairs = 0, last_chunks = 0, last_bytes = 0;   // --mate-device: pairs of the by-name pass; the store's footprint behind the last block
+	double append_s = 0, mate_s = 0, fetch_s = 0, write_s = 0;   // --mate-device: wall seconds of the route's phases
+};
 
 inline psvr_signal_opt_t signal_device_options(const SignalStep &S)
 {
@@ -233,6 +238,215 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 	                   R.written, R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
 	else fprintf(stderr, "[panSVR-amd] signal --signal-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld runs, %lld text bytes, peak footprint %lld chunks (%lld bytes)\n", R.pairs, R.written,
 	             R.declined, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes);
+	if (stats) *stats = R;
+	return 0;
+}
+
+// ---- `panSVR signal --mate-device`: the position-sorted mode (SignalStep::run_pos_sorted) over the same backend plus
+//   int signal_run_pos(int64_t first_record, int finish, const psvr_signal_pos_opt_t *, psvr_signal_info_t *, psvr_signal_pos_info_t *)
+//   int signal_mate_notes(psvr_signal_mate_note_t *, int64_t cap)
+//   int signal_run_left(int64_t first_pair, int64_t max_pairs, psvr_signal_info_t *, psvr_signal_left_info_t *) / int signal_left_errors(int64_t *, int64_t cap)
+// Pieces are appended until signal_run_pos reports a complete block (a piece may hold several); behind the last piece it is asked with
+// finish = 1 until fewer than two primaries are left.  Per block: the "Mate failed" lines from the notes, the WARNING line from the counts,
+// the pairs as on the -N route (progress in the position mode's form, and counted in front of the template test as that loop does),
+// store_drop; the unmated records stay on the device, in the signal object's left store.  Behind the last block the two `phase 2:` lines,
+// then signal_run_left slice by slice (--block-records pairs a slice at the most; the call takes fewer where the text would reach 2 GiB), the pairing-error lines at their
+// places from signal_left_errors.  *pairs_done counts SignalStep::pair calls, which is what run_pos_sorted is muted by; leaving and the
+// error states 4 and 5 work as above.  An odd number of left-overs is the call's to decline: the host route reads the file and ends as it does.
+// R (and the summary line) carries the phases' wall times: append (read, upload, inflate, chain), mate (run_pos, run_left), fetch (tables,
+// text, side records), write (S.out, the host-formatted pairs).
+template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr)
+{
+	*pairs_done = 0;
+	SignalRouteStats R;
+	auto left_route = [&](const std::string &call, const std::string &why) {
+		fprintf(stderr, "[panSVR-amd] signal --mate-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
+		        *pairs_done);
+		return -1;
+	};
+	struct Clock {
+		double *into; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+		~Clock() { *into += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+	};
+	struct stat sb;
+	if (S.o.input == "-" || stat(S.o.input.c_str(), &sb) != 0 || !S_ISREG(sb.st_mode)) return left_route("opening the input", "a pipe cannot be read twice");
+	size_t header_bytes = 0, n_ref = 0;
+	{
+		BamReader rd;
+		if (!rd.open(S.o.input.c_str())) return left_route("reading the header", rd.error());
+		header_bytes = rd.header_bytes, n_ref = rd.refs.size();
+	}
+	FILE *f = fopen(S.o.input.c_str(), "rb");
+	if (!f) return left_route("opening the input", "cannot open " + S.o.input);
+	struct Closer {
+		FILE *f; Backend &be; uint8_t *text, *side;
+		~Closer() { fclose(f); if (text) be.host_free(text); if (side) be.host_free(side); be.signal_destroy(); be.store_destroy(); }
+	} guard{f, be, nullptr, nullptr};
+	PieceFail fail;
+	long long skip = 0;
+	if (!bgzf_seek_first_record(f, header_bytes, &skip, &fail)) return left_route(fail.call, fail.why);
+	if (be.store_create()) return left_route("store create", be.last_error());
+	const psvr_signal_opt_t opt = signal_device_options(S);
+	if (be.signal_create(&opt)) return left_route("signal create", be.last_error());
+	const psvr_signal_pos_opt_t popt = {S.o.block_records, 0};
+	size_t text_cap = 0, side_cap = 0;
+	std::vector<psvr_signal_pair_t> tab;
+	std::vector<psvr_signal_mate_note_t> notes;
+	std::vector<int64_t> errs;
+	int64_t side_bytes = 0;
+	long long total = 0, errs_printed = 0;
+	int error_state = 0;
+	bool any_written = false;
+	auto fetch = [&](int64_t p, BamRecord *a, BamRecord *b, PieceFail *why) {
+		const int64_t at = tab[(size_t)p].side_off;
+		const char *bad = at < 0 || at > side_bytes ? "the pair has no side records" : bam_record_from_bytes(guard.side + at, (size_t)(side_bytes - at), *a);
+		const size_t n1 = bad ? 0 : 4 + (size_t)bam_u32(guard.side + at);
+		if (!bad) bad = bam_record_from_bytes(guard.side + at + n1, (size_t)(side_bytes - at) - n1, *b);
+		if (bad) { *why = {"signal side", bad}; return false; }
+		return true;
+	};
+	auto room = [&](uint8_t **buf, size_t *cap, size_t n, PieceFail *why) {
+		if (n <= *cap) return true;
+		if (*buf) be.host_free(*buf), *buf = nullptr, *cap = 0;
+		if (!(*buf = (uint8_t *)be.host_alloc(n + n / 4))) { *why = {"host_alloc", be.last_error()}; return false; }
+		*cap = n + n / 4;
+		return true;
+	};
+	auto progress = [&]() { total += 2; if (total % 100000 == 0) fprintf(stderr, "%ld\n", (long)total); };
+	// the pairing-error steps in front of pair q of a slice (errs: signal_left_errors; empty for a block)
+	auto error_steps = [&](long long upto) {
+		for (; errs_printed < upto; ++errs_printed) {
+			progress();
+			fprintf(stderr, "Read Pairing error!, reads names are not same, please confirm the completeness of BAM/CRAM file.\n");
+		}
+	};
+	// the pairs of the last run (a block's or a slice's): table, text and side records come back, the text goes out in pair order with the
+	// host-formatted pairs at their places.  false: *why says which call failed, or error_state is set (and *why is empty)
+	auto pairs_out = [&](const psvr_signal_info_t &info, bool slice, PieceFail *why) {
+		{
+			Clock clock{&R.fetch_s};
+			tab.resize((size_t)info.pairs);
+			if (info.pairs && be.signal_pairs(tab.data(), info.pairs)) { *why = {"signal pairs", be.last_error()}; return false; }
+			errs.assign(slice ? (size_t)info.pairs : 0, 0);
+			if (slice && info.pairs && be.signal_left_errors(errs.data(), info.pairs)) { *why = {"signal left_errors", be.last_error()}; return false; }
+			if (!room(&guard.text, &text_cap, (size_t)info.text_bytes, why) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
+			if (info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
+			if (info.side_bytes && be.signal_side(guard.side, (int64_t)side_cap)) { *why = {"signal side", be.last_error()}; return false; }
+			side_bytes = info.side_bytes;
+		}
+		Clock clock{&R.write_s};
+		const int64_t n_front = info.first_error >= 0 ? info.first_error : info.pairs;
+		int64_t flushed = 0;
+		BamRecord a, b;
+		auto flush_to = [&](int64_t q) {
+			const int64_t upto = q < info.pairs ? tab[(size_t)q].text_off : info.text_bytes;
+			if (upto > flushed) fwrite(guard.text + flushed, 1, (size_t)(upto - flushed), S.out);
+			flushed = upto;
+			*pairs_done = R.pairs + q;
+		};
+		for (int64_t q = 0; q < n_front; ++q) {
+			const psvr_signal_pair_t &t = tab[(size_t)q];
+			if (slice) error_steps(errs[(size_t)q]);
+			progress();
+			if (t.state == 2) {
+				flush_to(q);
+				if (!fetch(q, &a, &b, why)) return false;
+				S.stat_written = any_written;
+				S.pair(a, b, true);
+				any_written = true, ++R.declined;
+				*pairs_done = R.pairs + q + 1;
+				continue;
+			}
+			if (t.note & 1) {
+				flush_to(q);
+				if (!fetch(q, &a, &b, why)) return false;
+				fprintf(stderr, " wrong ISIZE: %d  %d \n", a.isize, b.isize);
+			}
+			if (t.state == 1) any_written = true, ++R.written;
+		}
+		flush_to(n_front);
+		R.pairs += n_front, R.text_bytes += info.text_bytes;
+		if (slice) R.left_pairs += n_front;
+		if (info.first_error < 0) return true;
+		const psvr_signal_pair_t &t = tab[(size_t)info.first_error];   // the pair the host loop aborts on
+		fflush(S.out);
+		error_state = t.state;
+		std::string n1 = "?";
+		int i1 = 0, i2 = 0;
+		PieceFail ignored;
+		if (fetch(info.first_error, &a, &b, &ignored)) n1 = a.qname(), i1 = a.isize, i2 = b.isize;
+		if (slice) error_steps(errs[(size_t)info.first_error]);
+		progress();
+		if (t.state == 5) {
+			if (t.note & 1) fprintf(stderr, " wrong ISIZE: %d  %d \n", i1, i2);
+			fprintf(stderr, "[panSVR-amd] signal: read longer than 2047 bases\n");
+		} else fprintf(stderr, "[panSVR-amd] signal: records of [%s] are not first/second in template\n", n1.c_str());
+		*why = {"", ""};
+		return false;
+	};
+	// the blocks that are complete in the store
+	auto blocks = [&](int finish, PieceFail *why) {
+		for (;;) {
+			psvr_signal_info_t info;
+			psvr_signal_pos_info_t pi;
+			{
+				Clock clock{&R.mate_s};
+				if (be.signal_run_pos(0, finish, &popt, &info, &pi)) { *why = {"signal run_pos", be.last_error()}; return false; }
+			}
+			if (!pi.complete) return true;
+			if (pi.primaries < 2) {
+				if (be.store_drop(pi.consumed)) { *why = {"store drop", be.last_error()}; return false; }
+				return true;
+			}
+			++R.runs;
+			notes.resize((size_t)pi.notes);
+			if (pi.notes && be.signal_mate_notes(notes.data(), pi.notes)) { *why = {"signal mate_notes", be.last_error()}; return false; }
+			for (const psvr_signal_mate_note_t &t : notes)
+				fprintf(stderr, "NUM: [%lld]: Mate failed, index:[%d] in [%d] size block, tid: [ %d ], pos [%d] name [%s]\n", (long long)t.number, t.index, t.block, t.tid, t.pos, t.name);
+			if (pi.unmated * 20 > pi.primaries) fprintf(stderr, "WARNING, too many total_unmated_read![ %d %d %f]\n", (int)pi.unmated, (int)pi.primaries, (float)(int)pi.unmated / (float)(int)pi.primaries);
+			if (!pairs_out(info, false, why)) return false;
+			if (be.store_drop(pi.consumed)) { *why = {"store drop", be.last_error()}; return false; }
+			int64_t chunks = 0, bytes = 0;
+			if (be.store_footprint(&chunks, &bytes)) { *why = {"store footprint", be.last_error()}; return false; }
+			R.last_chunks = chunks, R.last_bytes = bytes;
+		}
+	};
+	const bool walked = bgzf_for_pieces(be, f, skip, &fail, [&](const uint8_t *p, size_t have, long long skip_now, int64_t *used, PieceFail *why) {
+		int64_t bad = -1;
+		{
+			Clock clock{&R.append_s};
+			if (be.store_append_bgzf(p, (int64_t)have, skip_now, (int32_t)n_ref, used, &bad)) { *why = {"append_bgzf", be.last_error()}; return false; }
+		}
+		int64_t chunks = 0, bytes = 0;
+		if (be.store_footprint(&chunks, &bytes)) { *why = {"store footprint", be.last_error()}; return false; }
+		if (chunks > R.peak_chunks) R.peak_chunks = chunks;
+		if (bytes > R.peak_bytes) R.peak_bytes = bytes;
+		return blocks(0, why);
+	});
+	if (error_state) return error_state;
+	if (!walked) return left_route(fail.call, fail.why);
+	psvr_bam_chain_info_t ci;
+	if (be.store_chain_info(&ci)) return left_route("chain_info", be.last_error());
+	if (ci.tail_bytes) return left_route("the end of the input", "truncated BAM stream: the file ends " + std::to_string((long long)ci.tail_bytes) + " bytes into a record");
+	if (!blocks(1, &fail)) return error_state ? error_state : left_route(fail.call, fail.why);
+	// phase 2: the left store in the host comparator's order, a slice of its pairs at a time
+	psvr_signal_left_info_t li;
+	for (int64_t first = 0;;) {
+		psvr_signal_info_t info;
+		{
+			Clock clock{&R.mate_s};
+			if (be.signal_run_left(first, S.o.block_records, &info, &li)) return left_route("signal run_left", be.last_error());
+		}
+		if (first == 0) fprintf(stderr, "phase 2:\nSort all unpaired records: [%zu] in total\n", (size_t)li.records);
+		if (!pairs_out(info, true, &fail)) return error_state ? error_state : left_route(fail.call, fail.why);
+		if (!li.more) break;
+		first += li.n_pairs;
+	}
+	error_steps(li.errors);
+	if (be.signal_stats(S.bs.isize_n.data(), S.bs.len_n.data())) return left_route("signal stats", be.last_error());
+	S.bs.total = (uint64_t)total;
+	fprintf(stderr, "[panSVR-amd] signal --mate-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld paired by name, %lld blocks, %lld text bytes, peak footprint %lld chunks (%lld bytes), %lld chunks (%lld bytes) behind the last block; append %.3f s, mate %.3f s, fetch %.3f s, write %.3f s\n",
+	        R.pairs, R.written, R.declined, R.left_pairs, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes, R.last_chunks, R.last_bytes, R.append_s, R.mate_s, R.fetch_s, R.write_s);
 	if (stats) *stats = R;
 	return 0;
 }

@@ -1,7 +1,9 @@
 // signal_step.h -- `panSVR signal` (= the reference's `fc_signal`): BAM -> interleaved FASTQ whose comment carries
 // the original alignment, i.e. the wire format `aln` parses.  Host C++, with one device route: with `-N --signal-device` the records are
 // inflated, paired, judged and formatted in GPU memory (signal_device_route.h over psvr_signal_*; the fused `aln -N --bam-device` runs the
-// same route and hands the text to aln's reader stage where it lies, a window per run).  This file's pair() stays the
+// same route and hands the text to aln's reader stage where it lies, a window per run); without -N, `--mate-device` runs the blocks of the
+// position-sorted mode the same way (signal_mate_route over psvr_signal_run_pos: the mates found on the device by the rules of
+// signal_mate_device.h, the left-overs kept in a second store there and paired by psvr_signal_run_left).  This file's pair() stays the
 // specification: it formats the few pairs the device declines, and it takes over, muted up to the pairs already written, whenever that route
 // is left.  Restated from PanSVgenerateVCF/getSignalRead.cpp / .hpp and the helpers of clib/bam_file.c it calls; PARITY UNPINNED:
 // the reference's build of this step needs htslib, which cannot be built in this image, so the only checker is the independent
@@ -43,6 +45,8 @@ struct SignalOpt {
 	int inflate_device = -1, inflate_threads = 0;                                           // --inflate-device / --inflate-threads N: the batched BGZF reader (bam_reader.h)
 	bool signal_device = false;                                                             // --signal-device: signal_device_route.h (with -N)
 	bool bam_device = false;                                                                // aln --bam-device: the same route, its windows handed to aln's reader stage
+	bool mate_device = false;                                                               // --mate-device: the position-sorted mode's blocks mated on the device (signal_device_route.h)
+	int block_records = 1000000;                                                            // --block-records N: SAM_LOAD_BUFF_SIZE, the primary records of a block at the most
 };
 
 struct BamStat {                                            // BAM_STAT, getSignalRead.hpp:33-190
@@ -111,6 +115,7 @@ struct SignalStep {
 	// --signal-device (signal_device_route.h over the caller's backend): 0 done, bs holds the histograms; -1 the route was left with *pairs_done
 	// pairs written; 3, 4, 5: the host route's abort() for a pair in that state is due (the message has been printed)
 	std::function<int(SignalStep &, long long *pairs_done)> signal_device_fn;
+	std::function<int(SignalStep &, long long *pairs_done)> mate_device_fn;   // --mate-device: the same contract, *pairs_done counts pair() calls of run_pos_sorted
 
 	static bool primary(const BamRecord &r) { return !(r.flag & 0x100) && !(r.flag & 0x800); }
 
@@ -299,9 +304,11 @@ struct SignalStep {
 	}
 
 	// SURVIVOR_SV_region_get_all_signal_records_SORT_BY_pos, getSignalRead.cpp:285-489
-	bool run_pos_sorted(BamReader &rd)
+	bool run_pos_sorted(BamReader &rd, long long mute = 0)
 	{
-		static const int kBuf = 1000000, kStep = 64, kIndex = 1000000, kRegion = 60000000;   // SAM_LOAD_BUFF_SIZE, SEARCH_STEP, SEARCH_POS_INDEX_SIZE, SEARCH_REGION_MAX
+		const int kBuf = o.block_records;                        // SAM_LOAD_BUFF_SIZE
+		long long pair_no = 0;                                   // pair() calls so far: the first `mute` of them are silent (their text is written)
+		static const int kStep = 64, kIndex = 1000000, kRegion = 60000000;   // SEARCH_STEP, SEARCH_POS_INDEX_SIZE, SEARCH_REGION_MAX
 		std::vector<BamRecord> buf, left;                        // the block; the records no mate was found for
 		std::vector<uint32_t> mate, index((size_t)kIndex);
 		const uint32_t none = 0xffffffffu;
@@ -371,6 +378,7 @@ struct SignalStep {
 				if (!(b1.flag & 0x40) || !(b2.flag & 0x80)) { fprintf(stderr, "[panSVR-amd] signal: records of [%s] are not first/second in template\n", b1.qname()); abort(); }
 				bool used = true;
 				if (o.sample_rate < 0.9999 && rand() > sample_max) used = false;
+				muted = pair_no++ < mute;
 				pair(b1, b2, used);
 			}
 			for (int i = 0; i < n; ++i) if (mate[(size_t)i] == none) left.push_back(std::move(buf[(size_t)i]));
@@ -398,8 +406,10 @@ struct SignalStep {
 			if (!(b1.flag & 0x40) || !(b2.flag & 0x80)) { fprintf(stderr, "[panSVR-amd] signal: records of [%s] are not first/second in template\n", b1.qname()); abort(); }
 			bool used = true;
 			if (o.sample_rate < 0.9999 && rand() > sample_max) used = false;
+			muted = pair_no++ < mute;
 			pair(b1, b2, used);
 		}
+		muted = false;
 		return true;
 	}
 
@@ -453,8 +463,29 @@ struct SignalStep {
 				bs.reset(), stat_written = false;               // the host route from the file's beginning, muted for the pairs that are written
 			}
 		}
+		if (o.mate_device) {
+			const char *no = o.sort_by_name           ? "it is the position-sorted mode's route: -N has --signal-device"
+			                 : o.sample_rate < 0.9999 ? "-R draws rand() per pair in the host loop's order"
+			                 : o.signal_device        ? "--signal-device is the name-sorted mode's route: give one of the two"
+			                 : feed                   ? "the fused aln route hands its pairs over on the host"
+			                 : !mate_device_fn        ? "this build has no device route"
+			                                          : nullptr;
+			if (no) fprintf(stderr, "[panSVR-amd] signal --mate-device: refused (%s): the host route runs\n", no);
+			else {
+				const int rc = mate_device_fn(*this, &mute);
+				if (rc > 0) abort();                            // (a pair the host loop aborts on; the route has written what lies in front of it and said why)
+				if (rc == 0) {
+					fflush(out);
+					bs.global();
+					fprintf(stderr, "BAM/CRAM status: ave_read_depth: [%f] read length: [Normal: %d @ %f%%, AVE: %f] ISIZE: [MIN: %d MAX: %d]\n", bs.depth, bs.read_len, bs.normal_percent * 100,
+					        bs.ave_len, bs.min_l2, bs.max_l2);
+					return 0;
+				}
+				bs.reset(), stat_written = false;               // the host route from the file's beginning, muted for the pairs that are written
+			}
+		}
 		if (!o.sort_by_name) {
-			if (!run_pos_sorted(rd)) { fprintf(stderr, "[panSVR-amd] signal: %s\n", rd.error().c_str()); return 1; }
+			if (!run_pos_sorted(rd, mute)) { fprintf(stderr, "[panSVR-amd] signal: %s\n", rd.error().c_str()); return 1; }
 			fflush(out);
 			bs.global();
 			fprintf(stderr, "BAM/CRAM status: ave_read_depth: [%f] read length: [Normal: %d @ %f%%, AVE: %f] ISIZE: [MIN: %d MAX: %d]\n", bs.depth, bs.read_len, bs.normal_percent * 100, bs.ave_len,
@@ -498,14 +529,14 @@ inline std::thread signal_step_thread(SignalStep &sig, PairFeed &feed, WindowFee
 	});
 }
 
-inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, long long *)> signal_device_fn = nullptr)
+inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, long long *)> signal_device_fn = nullptr, std::function<int(SignalStep &, long long *)> mate_device_fn = nullptr)
 {
 	SignalStep S;
-	S.signal_device_fn = std::move(signal_device_fn);
+	S.signal_device_fn = std::move(signal_device_fn), S.mate_device_fn = std::move(mate_device_fn);
 	static struct option lo[] = {{"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'}, {"match-score", 1, 0, 'M'},
 	                             {"mis-score", 1, 0, 'm'}, {"max-tid-filter", 1, 0, 'I'}, {"sort-by-name", 0, 0, 'N'}, {"not-ignore-low-q", 0, 0, 'L'}, {"reference", 1, 0, 'r'},
 	                             {"header-file", 1, 0, 'H'}, {"status-file", 1, 0, 'S'}, {"tmp_file_pairing", 1, 0, 't'}, {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'},
-	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {"inflate-device", 0, 0, 1001}, {"inflate-threads", 1, 0, 1002}, {"signal-device", 0, 0, 1003}, {0, 0, 0, 0}};
+	                             {"sample-rate", 1, 0, 'R'}, {"isize", 1, 0, 1000}, {"inflate-device", 0, 0, 1001}, {"inflate-threads", 1, 0, 1002}, {"signal-device", 0, 0, 1003}, {"mate-device", 0, 0, 1004}, {"block-records", 1, 0, 1005}, {0, 0, 0, 0}};
 	static const char *usage = "usage: panSVR signal|fc_signal [-N] [options] <in.bam>  > reads.fq\n"
 	                           "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
 	                           "                                (faster than the default reader; it does not win against --inflate-threads 16)\n"
@@ -513,7 +544,12 @@ inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, lo
 	                           "         --signal-device        with -N: the records are inflated, paired, judged and formatted in the GPU's memory (device 0), a piece of\n"
 	                           "                                the file at a time; only FASTQ text comes back.  The output, the header file and the status file are those\n"
 	                           "                                of -N.  Whatever the device route cannot do (no device, a pipe, a corrupt or truncated file) is named, and\n"
-	                           "                                the host route reads the file again, silent for the pairs already written.  Not without -N, not with -R\n";
+	                           "                                the host route reads the file again, silent for the pairs already written.  Not without -N, not with -R\n"
+	                           "         --mate-device          without -N (input sorted by position): the blocks' records are inflated, mated, judged and formatted in the GPU's\n"
+	                           "                                memory (device 0), the records that found no mate in their block are ordered by name and paired there as\n"
+	                           "                                well; only FASTQ text comes back.  Output, header file and status file are those of the default mode; whatever\n"
+	                           "                                the route cannot do is named and the host route takes over.  Not with -N, -R or --signal-device\n"
+	                           "         --block-records INT    primary records of a block of the position-sorted mode at the most [1000000]\n";
 	int c;
 	optind = 2;
 	while ((c = getopt_long(argc, argv, "O:P:E:F:M:m:I:NLr:H:S:t:DUR:", lo, NULL)) >= 0) {
@@ -535,6 +571,8 @@ inline int signal_main(int argc, char **argv, std::function<int(SignalStep &, lo
 		case 1000: if (sscanf(optarg, "%d,%d,%d", &S.o.isize_override[0], &S.o.isize_override[1], &S.o.isize_override[2]) != 3) { fprintf(stderr, "--isize wants MIN,MID,MAX\n"); return 1; } break;
 		case 1001: S.o.inflate_device = 0; break;
 		case 1003: S.o.signal_device = true; break;
+		case 1004: S.o.mate_device = true; break;
+		case 1005: S.o.block_records = atoi(optarg); if (S.o.block_records < 2) { fprintf(stderr, "--block-records wants a number of at least 2\n"); return 1; } break;
 		case 1002: S.o.inflate_threads = atoi(optarg); if (S.o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		default: fputs(usage, stderr); return 1;
 		}

@@ -25,13 +25,15 @@ int sort_scratch_reserve(long long n, SortScratch &S, const char *who);
 
 // Name order (name_sort.hip; the rules are name_key.h's): the names compared as strcmp compares them, then the tie key, then the index.
 // Where the names are: records of a store (rec_addr[i] = the record's address, the name at +36 inside l_read_name bytes, the tie key from
-// its flag), or a blob (name i at blob + off[i], ending before blob + n_bytes; tie[i] or, with tie == nullptr, nothing).
+// its flag), or a blob (name i at blob + off[i], ending before blob + n_bytes; tie[i] or, with tie == nullptr, nothing).  The records' tie key is the
+// caller's choice: name_tie_key for everyone but SignalStep's by-name pass over its left-overs, which has records with 0x40 first.
 struct NameSrc {
 	const uint64_t *rec_addr;
 	const uint8_t *blob;
 	long long n_bytes;
 	const long long *off;
 	const uint8_t *tie;
+	int first_read_tie;                                           // records: the tie key is !(flag & 0x40) (SignalStep's by-name pass) instead of name_tie_key's flag & 0xc0
 };
 struct NameScratch {                                              // 8 bytes per name: address | length << 48 | tie key << 56
 	DevBuf nent, ctl;

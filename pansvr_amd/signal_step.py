@@ -22,6 +22,19 @@ class SignalWindowInfo(C.Structure):  # psvr_signal_window_info_t
     _fields_ = [(n, C.c_int64) for n in ("n_bytes", "n_pairs", "n_host_pairs")]
 
 
+class SignalPosOpt(C.Structure):  # psvr_signal_pos_opt_t (0: the default)
+    _fields_ = [("block_records", C.c_int64), ("block_span", C.c_int64)]
+
+
+class SignalPosInfo(C.Structure):  # psvr_signal_pos_info_t
+    _fields_ = [(n, C.c_int64) for n in ("complete", "primaries", "consumed", "unmated", "left_bytes", "mate_failed", "notes", "replayed")]
+
+
+class SignalLeftInfo(C.Structure):  # psvr_signal_left_info_t
+    _fields_ = [(n, C.c_int64) for n in ("records", "pairs", "errors", "first_pair", "n_pairs", "more")]
+
+
+NOTE_DTYPE = np.dtype([("number", "<i8"), ("index", "<i4"), ("block", "<i4"), ("tid", "<i4"), ("pos", "<i4"), ("name", "S256")])   # psvr_signal_mate_note_t
 PAIR_DTYPE = np.dtype([("text_off", "<i8"), ("rec1", "<i8"), ("rec2", "<i8"), ("side_off", "<i8"), ("bytes", "<i4"), ("state", "u1"), ("note", "u1"), ("pad", "<u2")])   # psvr_signal_pair_t
 
 
@@ -40,7 +53,7 @@ class Signal:
         self.h = C.c_void_p()
         lib().psvr_signal_destroy.restype = None
         check(lib().psvr_signal_create(C.c_int(device), C.byref(opt), C.byref(self.h)))
-        self.info = None
+        self.info = self.pos_info = None
 
     def run(self, store, first_record=0, finish=False):
         """the store's records [first_record, n_records) paired, judged and formatted; returns SignalInfo"""
@@ -48,6 +61,43 @@ class Signal:
         check(lib().psvr_signal_run(self.h, store.h, C.c_int64(first_record), C.c_int32(int(finish)), C.byref(i)))
         self.info = i
         return i
+
+    def run_pos(self, store, first_record=0, finish=False, block_records=0, block_span=0):
+        """the block of the position-sorted mode at the store's front (psvr_signal_run_pos); returns (SignalInfo, SignalPosInfo); text(), pairs(),
+        side() and stats() answer behind it as behind run(), when the block was complete"""
+        i, pi, o = SignalInfo(), SignalPosInfo(), SignalPosOpt(block_records, block_span)
+        check(lib().psvr_signal_run_pos(self.h, store.h, C.c_int64(first_record), C.c_int32(int(finish)), C.byref(o), C.byref(i), C.byref(pi)))
+        self.info, self.pos_info = (i if pi.complete else None), pi
+        return i, pi
+
+    def mate_notes(self):
+        """the last block's notes (NOTE_DTYPE): every 1000th "Mate failed" turn"""
+        n = self.pos_info.notes if self.pos_info else 0
+        out = np.zeros(max(n, 1), dtype=NOTE_DTYPE)
+        check(lib().psvr_signal_mate_notes(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n]
+
+    def left(self):
+        """the last block's unmated records back to back (bytes), in block order"""
+        n = self.pos_info.left_bytes if self.pos_info else 0
+        out = np.empty(max(n, 1), dtype=np.uint8)
+        check(lib().psvr_signal_left(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n].tobytes()
+
+    def run_left(self, first_pair=0, max_pairs=1 << 20):
+        """a slice of the by-name pass over the object's left store (psvr_signal_run_left; the first call orders the store); returns
+        (SignalInfo, SignalLeftInfo); text(), pairs() (rec1 / rec2: indices into the left store), side() and stats() answer behind it"""
+        i, li = SignalInfo(), SignalLeftInfo()
+        check(lib().psvr_signal_run_left(self.h, C.c_int64(first_pair), C.c_int64(max_pairs), C.byref(i), C.byref(li)))
+        self.info, self.pos_info, self.left_info = i, None, li
+        return i, li
+
+    def left_errors(self):
+        """per pair of the last slice, the pairing-error steps of the whole pass in front of it (int64 array)"""
+        n = self.left_info.n_pairs
+        out = np.zeros(max(n, 1), dtype=np.int64)
+        check(lib().psvr_signal_left_errors(self.h, out.ctypes.data_as(C.c_void_p), C.c_int64(n)))
+        return out[:n]
 
     def text(self):
         """the last run's text (bytes): its state-1 pairs in front of the first error pair"""
