@@ -605,6 +605,11 @@ int  psvr_bam_store_footprint(psvr_bam_store_t *st, int64_t *chunks, int64_t *by
  *                 n_host is not the number of such pairs, host_off is not monotone from 0 or does not end at host_bytes: PSVR_ERR_ARG;
  *                 a window of 2^32 bytes or more: PSVR_ERR_UNSUPPORTED.  info: n_bytes of the window, n_pairs whose text it holds (states 1
  *                 and 2), n_host_pairs of them from the host.  The call waits; the window stays until the next run or window call.
+ *   window_add    the same for the last run (run, run_pos or run_left), written behind the bytes the object's kept window already holds: a kept
+ *                 window grows run by run and survives later runs, until an add with restart != 0 (which empties it first), a window call
+ *                 or destroy.  info carries the kept window's totals.  Refused as window is (a total of 2^32 bytes or more:
+ *                 PSVR_ERR_UNSUPPORTED; no memory: PSVR_ERR_NOMEM), and a refused or failed add leaves the kept window's bytes and counts
+ *                 as they were.  window_text and psvr_fastq_parse_signal read a kept window as they read the other.
  *   window_text   bytes [first, first + n) of the window to dst, which is host memory or memory of the object's device (outside the
  *                 window: PSVR_ERR_ARG).
  *   psvr_fastq_parse_signal   exactly the effect of psvr_fastq_parse on the bytes [first_byte, n_bytes) of sg's window with at_end = 1, the
@@ -631,6 +636,8 @@ int  psvr_signal_pair_records(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t p
 int  psvr_signal_stats(psvr_signal_t *sg, uint64_t *isize_n, uint64_t *len_n);
 typedef struct psvr_signal_window_info { int64_t n_bytes, n_pairs, n_host_pairs; } psvr_signal_window_info_t;
 int  psvr_signal_window(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *info);
+int  psvr_signal_window_add(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, int32_t restart,
+                            psvr_signal_window_info_t *info);
 int  psvr_signal_window_text(psvr_signal_t *sg, void *dst, int64_t first, int64_t n);   /* dst: host memory or memory of sg's device */
 int  psvr_fastq_parse_signal(psvr_fastq_t *fq, const psvr_signal_t *sg, int64_t first_byte, int64_t max_pairs, int64_t max_bases, psvr_fastq_info_t *info);
 int  psvr_fastq_text(const psvr_fastq_t *fq, void *dst, int64_t first, int64_t n);

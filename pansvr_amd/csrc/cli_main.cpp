@@ -54,6 +54,8 @@ struct Opt : aln::PipeOpt {
 	bool stream_device = false;                  // the main BAM file's stream gathered in HBM: records from the encoder to the member compressor device to device (implies emit_device and deflate_device)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 	bool bam_device = false;                     // a name-sorted *.bam read file: the signal step's device route hands windows of FASTQ text in HBM to the reader stage
+	bool mate_device = false;                    // a position-sorted *.bam read file: the same through the position-sorted mode's route, the runs of its blocks added to one kept window
+	int block_records = 0;                       // --block-records: the signal step's block limit on both routes (0: its default)
 	bool sort_device = false;                    // ... with the records kept, ordered and compressed in HBM (sort_store_sink.h; implies sort, emit_device and deflate_device)
 };
 
@@ -152,6 +154,13 @@ static int usage()
 	        "                                 and --sort-device then apply to the BAM input.  Whatever the route cannot do (no device, a pipe, a corrupt or\n"
 	        "                                 truncated file, a failing call on either side) is named on one line, and the host fused route reads the file\n"
 	        "                                 again, silent for the pairs already handed over.  Not with more than one entry in --devices\n"
+	        "        --mate-device            without -N and a *.bam read file sorted by position: the same through the route of `signal --mate-device` (blocks mated\n"
+	        "                                 in GPU memory, the left-overs paired by name there).  The windows of consecutive blocks and slices are put\n"
+	        "                                 together on the device until they hold --sub-batch pairs (0: a batch's pair limit), so a file with many small\n"
+	        "                                 blocks does not become as many pieces.  Implies --parse-device; --emit-device, --stream-device and --sort-device\n"
+	        "                                 apply as behind --bam-device, and the route is left the same way.  Not with -N (that is --bam-device), not with\n"
+	        "                                 more than one entry in --devices\n"
+	        "        --block-records     INT  BAM input without -N: primary records of a block of the position-sorted mode at the most, on both routes [1000000]\n"
 	        "        --records           STR  dump per-pair decision records (JSON lines) for parity checks\n"
 	        "        --trace                  add per-strand seed/chain hashes to --records\n\n");
 	return 1;
@@ -446,6 +455,7 @@ struct SignalCmdBackend {
 	int signal_run_left(int64_t first, int64_t max_pairs, psvr_signal_info_t *i, psvr_signal_left_info_t *li) { return psvr_signal_run_left(sg, first, max_pairs, i, li); }
 	int signal_left_errors(int64_t *e, int64_t cap) { return psvr_signal_left_errors(sg, e, cap); }
 	int signal_window(const void *t, int64_t n, const int64_t *off, int64_t n_host, psvr_signal_window_info_t *i) { return psvr_signal_window(sg, t, n, off, n_host, i); }
+	int signal_window_add(const void *t, int64_t n, const int64_t *off, int64_t n_host, int32_t restart, psvr_signal_window_info_t *i) { return psvr_signal_window_add(sg, t, n, off, n_host, restart, i); }
 	const char *last_error() { return psvr_last_error(); }
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
@@ -489,6 +499,8 @@ static bool option_conflict(const Opt &o, const char *sort_conflict)
 		fprintf(stderr, "--emit-device cannot be combined with -S: the device encodes BAM records, SAM text is formatted on the host threads\n");
 	else if (o.bam_device && o.devices.size() > 1)
 		fprintf(stderr, "--bam-device cannot be combined with more than one entry in --devices: the text is made and parsed in the first device's memory\n");
+	else if (o.mate_device && o.devices.size() > 1)
+		fprintf(stderr, "--mate-device cannot be combined with more than one entry in --devices: the text is made and parsed in the first device's memory\n");
 	else if (o.parse_device && o.devices.size() > 1)
 		fprintf(stderr, "--parse-device cannot be combined with more than one entry in --devices: the parsed bases stay in the first device's memory and would have to travel between devices\n");
 	else return false;
@@ -502,7 +514,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019}, {"mate-device", 0, 0, 1020}, {"block-records", 1, 0, 1021},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -542,6 +554,8 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1018: fprintf(stderr, "[panSVR-amd] --signal-device is `panSVR signal -N`'s route to FASTQ text: ignored by aln (a *.bam read file hands its pairs over on the host threads)\n"); break;
 		case 1019: o.bam_device = true; break;
+		case 1020: o.mate_device = true; break;
+		case 1021: o.block_records = atoi(optarg); if (o.block_records < 2) { fprintf(stderr, "--block-records wants a number of at least 2\n"); return 1; } break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -558,7 +572,9 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	if (!o.from_bam && (o.inflate_device || o.inflate_threads > 0)) fprintf(stderr, "[panSVR-amd] --inflate-device / --inflate-threads apply to a *.bam read file: ignored for [%s]\n", o.reads.c_str());
 	if (o.bam_device && !o.from_bam) fprintf(stderr, "[panSVR-amd] --bam-device applies to a *.bam read file: ignored for [%s]\n", o.reads.c_str()), o.bam_device = false;
 	if (o.bam_device && !o.sig_by_name) fprintf(stderr, "[panSVR-amd] aln --bam-device: refused (it is the name-sorted mode's route: give -N): the host fused route runs\n"), o.bam_device = false;
-	if (o.bam_device) { o.parse_device = true; return -1; }   // (the device stages behind the reader apply to the BAM input)
+	if (o.mate_device && !o.from_bam) fprintf(stderr, "[panSVR-amd] --mate-device applies to a *.bam read file: ignored for [%s]\n", o.reads.c_str()), o.mate_device = false;
+	if (o.mate_device && o.sig_by_name) fprintf(stderr, "[panSVR-amd] aln --mate-device: refused (it is the position-sorted mode's route: -N has --bam-device): the host fused route runs\n"), o.mate_device = false;
+	if (o.bam_device || o.mate_device) { o.parse_device = true; return -1; }   // (the device stages behind the reader apply to the BAM input)
 	if (o.from_bam && o.parse_device) fprintf(stderr, "[panSVR-amd] --parse-device applies to FASTQ text: ignored for [%s] (a *.bam read file hands its pairs over without text)\n", o.reads.c_str());
 	if (o.from_bam && o.sort_device) fprintf(stderr, "[panSVR-amd] --sort-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the run is that of --sort --deflate-device)\n", o.reads.c_str());
 	else if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
@@ -590,11 +606,12 @@ static std::thread start_signal_step(const Opt &o, psvr::SignalStep &sig, PairFe
 	sig.o.not_use_filter = o.sig_all, sig.o.discard_full_match = o.sig_discard;
 	sig.o.inflate_device = o.inflate_device ? o.devices[0] : -1, sig.o.inflate_threads = o.inflate_threads;
 	sig.o.match = o.match, sig.o.mismatch = o.mismatch, sig.o.gap_open = o.gap_open, sig.o.gap_ex = o.gap_ex, sig.o.gap_open2 = o.gap_open2, sig.o.gap_ex2 = o.gap_ex2;
+	if (o.block_records) sig.o.block_records = o.block_records;
 	sig.feed = &feed;
 	return psvr::signal_step_thread(sig, feed, windows, sig_rc);
 }
 
-// --bam-device: who takes the windows of the signal step's device route -- the reader stage, through the WindowFeed
+// --bam-device, --mate-device: who takes the windows of the signal step's device route -- the reader stage, through the WindowFeed
 struct ReaderWindowTaker : psvr::SignalWindowTaker {
 	SignalCmdBackend &be;
 	WindowFeed &windows;
@@ -655,14 +672,26 @@ static int aln_main(int argc, char **argv)
 			return rc;
 		};
 	}
-	if (o.from_bam) sig_thread = start_signal_step(o, sig, feed, o.bam_device ? &windows : nullptr, &sig_rc);
+	if (o.mate_device) {
+		sig.o.mate_fused = true;
+		sig.mate_device_fn = [&o, &windows](psvr::SignalStep &S, long long *pairs_done) {
+			SignalCmdBackend be(o.devices[0]);
+			ReaderWindowTaker taker(be, windows);
+			// (a kept window is offered when it holds a piece's pairs: the reader cuts it by the piece rule, and few pieces end short at a window's end)
+			const int rc = psvr::signal_mate_route(be, S, pairs_done, nullptr, &taker, o.sub_pairs > 0 ? o.sub_pairs : o.batch_pairs);
+			windows.close(rc != 0);                              // (left: the host fused route hands the rest over through the PairFeed)
+			return rc;
+		};
+	}
+	const bool device_input = o.bam_device || o.mate_device;   // the reader stage takes windows of text in HBM
+	if (o.from_bam) sig_thread = start_signal_step(o, sig, feed, device_input ? &windows : nullptr, &sig_rc);
 	FastqReader fq;
-	if (o.bam_device) fq.open_windows(&windows);
+	if (device_input) fq.open_windows(&windows);
 	if (o.from_bam) fq.open_feed(&feed);
 	else if (!fq.open(o.reads.c_str())) { fprintf(stderr, "%s\n", fq.error().c_str()); abort(); }
 	aln::OutFile fo, fo_ori;
 	// --stream-device: the main file is the sink's, not `fo`'s (PSVR_STREAM_TAKE_MEMBERS: members pending before a take; the tests take small files in pieces with it)
-	const bool device_routes = !o.from_bam || o.bam_device;
+	const bool device_routes = !o.from_bam || device_input;
 	const bool streaming = o.stream_device && device_routes;
 	std::unique_ptr<StreamBackend> stream_backend;
 	std::unique_ptr<BgzfStreamSink<StreamBackend>> stream_sink;

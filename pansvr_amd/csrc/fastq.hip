@@ -182,7 +182,7 @@ extern "C" int psvr_fastq_parse_signal(psvr_fastq_t *fq, const psvr_signal_t *sg
 {
 	if (psvr_device_count() <= 0) return fq_no_device();
 	if (!fq || !sg || !info || max_pairs < 0) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: bad argument");
-	if (!sg->valid || !sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: the signal object has no window");
+	if (!sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: the signal object has no window");
 	if (fq->device != sg->device) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: the parser is on device %d, the signal object on device %d", fq->device, sg->device);
 	if (first_byte < 0 || first_byte > sg->win_bytes) return set_error(PSVR_ERR_ARG, "psvr_fastq_parse_signal: first byte %lld of a window of %lld", (long long)first_byte, sg->win_bytes);
 	// (the window is whole: psvr_signal_window waited for it)

@@ -17,6 +17,8 @@
 // psvr_signal_window, behind a run: the run's text and the host formatter's text of the state-2 pairs become one window in pair order
 // (signal_window_device.h), on the same stream:
 //   k_sg_wflag, scan, k_sg_wcut, k_sg_wseg   the segment table from the pair table     k_sg_window   an output tile per workgroup
+// psvr_signal_window_add is the same body (sg_window_add) at a base: the run's window goes behind the bytes of a kept window, which grows run
+// by run and survives the runs; a workgroup per tile of the whole window that meets the add's bytes, each writing the add's bytes only.
 // Bounds: a record is read only after k_sg_mark has vouched for name, CIGAR, bases and qualities; the tag walk (bam_aux_find) stays inside
 // the record by its own rules; a pair's text is written into exactly the bytes the size pass counted for it, and a write pass that ends
 // anywhere else raises the refusal flag.
@@ -188,19 +190,21 @@ __global__ __launch_bounds__(256) void k_sg_wcut(const int32_t *flag, const long
 	if (rank[p] < 0 || rank[p] >= n_host) { ctl[kSgRefused] = 3; return; }
 	cut[rank[p]] = toff[p];
 }
-__global__ __launch_bounds__(256) void k_sg_wseg(const long long *cut, const long long *host_off, long long n_host, long long text_bytes, long long host_bytes, SwSeg *seg, long long *ctl)
+__global__ __launch_bounds__(256) void k_sg_wseg(const long long *cut, const long long *host_off, long long n_host, long long text_bytes, long long host_bytes, long long base, SwSeg *seg, long long *ctl)
 {
 	const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
 	if (k > 2 * n_host) return;
-	const SwSeg s = sw_segment(k, n_host, (const int64_t *)cut, (const int64_t *)host_off, text_bytes);
-	// (inside its source and inside the window, whatever the tables say: the tiles trust the table)
-	if (s.len < 0 || s.off < 0 || s.off + s.len > (s.src ? host_bytes : text_bytes) || s.out < 0 || s.out + s.len > text_bytes + host_bytes) ctl[kSgRefused] = 3;
+	const SwSeg s = sw_segment_add(k, n_host, (const int64_t *)cut, (const int64_t *)host_off, text_bytes, base);
+	// (inside its source and inside the add's bytes of the window, whatever the tables say: the tiles trust the table)
+	if (s.len < 0 || s.off < 0 || s.off + s.len > (s.src ? host_bytes : text_bytes) || s.out < base || s.out + s.len > base + text_bytes + host_bytes) ctl[kSgRefused] = 3;
 	seg[k] = s;
 }
-__global__ __launch_bounds__(256) void k_sg_window(const SwSeg *seg, long long n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, long long n_out, const long long *ctl)
+// a workgroup per tile of the whole window that meets the add's bytes [base, end): first_tile is the one base lies in
+__global__ __launch_bounds__(256) void k_sg_window(const SwSeg *seg, long long n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, long long base, long long end, long long first_tile,
+                                                   const long long *ctl)
 {
 	if (ctl[kSgRefused] != 0) return;                        // (the whole launch)
-	sw_tile(blockIdx.x, seg, n_seg, text, host, out, n_out, threadIdx.x, 256);
+	sw_tile_add(first_tile + blockIdx.x, seg, n_seg, text, host, out, base, end, threadIdx.x, 256);
 }
 
 static int sg_no_device() { return set_error(PSVR_ERR_DEVICE, "no HIP device visible: the engine has no CPU path"); }
@@ -259,7 +263,7 @@ extern "C" int psvr_signal_run(psvr_signal_t *sg, psvr_bam_store_t *st, int64_t 
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
 	if (int rc = store_refresh(st, c, true)) return rc;
-	sg->valid = false, sg->win_valid = false;
+	sg->run_begins();
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_signal_run: the store has been ordered: the pairs are those of its append order");
 	if (first_record < 0 || first_record > st->n_rec) return set_error(PSVR_ERR_ARG, "psvr_signal_run: first record %lld of %lld", (long long)first_record, st->n_rec);
 	const long long m = st->n_rec - first_record, p_max = m / 2;
@@ -365,24 +369,44 @@ extern "C" int psvr_signal_text(psvr_signal_t *sg, void *text, int64_t cap)
 	return PSVR_OK;
 }
 
-extern "C" int psvr_signal_window(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *info)
+namespace psvr {
+// The one body of psvr_signal_window and psvr_signal_window_add: the last run's window written at `base` of sg->window.  keep: the add -- base
+// is what the kept window holds (0 behind a restart), and nothing of the object changes unless the call succeeds; otherwise base is 0 and the
+// window is the run's, which dies with it.
+static int sg_window_add(psvr_signal *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, bool keep, bool restart, const char *who, psvr_signal_window_info_t *info)
 {
 	if (psvr_device_count() <= 0) return sg_no_device();
-	if (!sg || !info || (host_bytes > 0 && !host_text)) return set_error(PSVR_ERR_ARG, "psvr_signal_window: null argument");
-	if (!sg->valid) return set_error(PSVR_ERR_ARG, "psvr_signal_window: no run");
+	if (!sg || !info || (host_bytes > 0 && !host_text)) return set_error(PSVR_ERR_ARG, "%s: null argument", who);
+	if (!sg->valid) return set_error(PSVR_ERR_ARG, "%s: no run", who);
 	if (const char *bad = sw_args_bad(host_bytes, host_off, n_host, sg->declined))
-		return set_error(PSVR_ERR_ARG, "psvr_signal_window: %s (%lld host pairs with %lld bytes, the run has %lld)", bad, (long long)n_host, (long long)host_bytes, sg->declined);
-	const long long n_front = sg->n_front, text_bytes = sg->text_bytes, n_out = text_bytes + host_bytes, n_seg = 2 * n_host + 1;
-	if (n_out >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_window: a window of %lld bytes (at most 2^32 - 1: the parser's offsets)", n_out);
+		return set_error(PSVR_ERR_ARG, "%s: %s (%lld host pairs with %lld bytes, the run has %lld)", who, bad, (long long)n_host, (long long)host_bytes, sg->declined);
+	const bool grows = keep && !restart && sg->win_kept && sg->win_valid;
+	const long long base = grows ? sg->win_bytes : 0, base_pairs = grows ? sg->win_pairs : 0, base_host = grows ? sg->win_host_pairs : 0;
+	const long long n_front = sg->n_front, text_bytes = sg->text_bytes, n_out = text_bytes + host_bytes, n_seg = 2 * n_host + 1, end = base + n_out;
+	if (end >= (1ll << 32)) return set_error(PSVR_ERR_UNSUPPORTED, "%s: a window of %lld bytes (at most 2^32 - 1: the parser's offsets)", who, end);
 	DfwCtx &c = dfw_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
-	sg->win_valid = false;
+	if (!keep) sg->win_valid = false, sg->win_kept = false;
+	// (the window buffer grows geometrically into a new allocation; the old one is the window until the copy has succeeded)
+	DevBuf grown;
+	const size_t need = (size_t)end + 16;
 	if (sg->wflag.ensure((size_t)(n_front + 1) * 4) || sg->wrank.ensure((size_t)(n_front + 1) * 8) || sg->wcut.ensure((size_t)(n_host + 1) * 8) || sg->wseg.ensure((size_t)n_seg * sizeof(SwSeg)) ||
-	    sg->whost.ensure((size_t)host_bytes + 16) || sg->whoff.ensure((size_t)(n_host + 1) * 8) || sg->window.ensure((size_t)n_out + 16) || sg->tmp.ensure(scan_tmp_bytes(1, n_front + 1)) ||
-	    (!sg->text.p && sg->text.ensure(16))) {             // (a run without text: the kernel still gets a pointer; a run's text is never reallocated here)
+	    sg->whost.ensure((size_t)host_bytes + 16) || sg->whoff.ensure((size_t)(n_host + 1) * 8) || sg->tmp.ensure(scan_tmp_bytes(1, n_front + 1)) ||
+	    (!sg->text.p && sg->text.ensure(16)) ||                  // (a run without text: the kernel still gets a pointer; a run's text is never reallocated here)
+	    (need > sg->window.bytes && grown.alloc(std::max(need + need / 4, keep ? std::min(2 * sg->window.bytes, ((size_t)1 << 32) + 16) : (size_t)0)))) {
 		(void)hipGetLastError();
-		return set_error(PSVR_ERR_NOMEM, "psvr_signal_window: device allocation failed for a window of %lld bytes and %lld segments", n_out, n_seg);
+		return set_error(PSVR_ERR_NOMEM, "%s: device allocation failed for a window of %lld bytes and %lld segments", who, end, n_seg);
+	}
+	if (grown.p) {
+		const long long held = keep && sg->win_kept && sg->win_valid ? sg->win_bytes : 0;   // (behind a restart too: a failed add leaves them readable)
+		if (held > 0) {
+			StreamDrain drain{c.stream};
+			PSVR_HIP(hipMemcpyAsync(grown.p, sg->window.p, (size_t)held, hipMemcpyDeviceToDevice, c.stream));
+			drain.armed = false;
+			PSVR_HIP(hipStreamSynchronize(c.stream));
+		}
+		std::swap(grown.p, sg->window.p), std::swap(grown.bytes, sg->window.bytes);
 	}
 	long long *ctl = sg->ctl.as<long long>();
 	long long *h = sg->h_ctl;
@@ -400,25 +424,37 @@ extern "C" int psvr_signal_window(psvr_signal_t *sg, const void *host_text, int6
 		                   (long long)n_host, sg->wcut.as<long long>(), ctl);
 	}
 	hipLaunchKernelGGL(k_sg_wseg, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, c.stream, (const long long *)sg->wcut.p, (const long long *)sg->whoff.p, (long long)n_host, text_bytes,
-	                   (long long)host_bytes, sg->wseg.as<SwSeg>(), ctl);
+	                   (long long)host_bytes, base, sg->wseg.as<SwSeg>(), ctl);
 	if (n_out)
-		hipLaunchKernelGGL(k_sg_window, dim3((unsigned)((n_out + kSwTileBytes - 1) / kSwTileBytes)), dim3(256), 0, c.stream, (const SwSeg *)sg->wseg.p, n_seg, (const uint8_t *)sg->text.p,
-		                   (const uint8_t *)sg->whost.p, sg->window.as<uint8_t>(), n_out, (const long long *)ctl);
+		hipLaunchKernelGGL(k_sg_window, dim3((unsigned)sw_add_tiles(base, n_out)), dim3(256), 0, c.stream, (const SwSeg *)sg->wseg.p, n_seg, (const uint8_t *)sg->text.p, (const uint8_t *)sg->whost.p,
+		                   sg->window.as<uint8_t>(), base, end, (long long)sw_add_first_tile(base), (const long long *)ctl);
 	PSVR_HIP(hipGetLastError());
 	PSVR_HIP(hipMemcpyAsync(h + kSgRefused, ctl + kSgRefused, 8, hipMemcpyDeviceToHost, c.stream));
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(c.stream));
-	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "psvr_signal_window: the segment table does not fit the run's text and the host text (the window is not used)");
-	sg->win_valid = true, sg->win_bytes = n_out;
-	info->n_bytes = n_out, info->n_pairs = sg->written + sg->declined, info->n_host_pairs = n_host;
+	// (a refused table: no tile has written, so a kept window's bytes [0, base) and its counts stand)
+	if (h[kSgRefused]) return set_error(PSVR_ERR_DEVICE, "%s: the segment table does not fit the run's text and the host text (the window is not used)", who);
+	sg->win_valid = true, sg->win_kept = keep, sg->win_bytes = end, sg->win_pairs = base_pairs + sg->written + sg->declined, sg->win_host_pairs = base_host + n_host;
+	info->n_bytes = sg->win_bytes, info->n_pairs = sg->win_pairs, info->n_host_pairs = sg->win_host_pairs;
 	return PSVR_OK;
+}
+} // namespace psvr
+
+extern "C" int psvr_signal_window(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, psvr_signal_window_info_t *info)
+{
+	return sg_window_add(sg, host_text, host_bytes, host_off, n_host, false, true, "psvr_signal_window", info);
+}
+
+extern "C" int psvr_signal_window_add(psvr_signal_t *sg, const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, int32_t restart, psvr_signal_window_info_t *info)
+{
+	return sg_window_add(sg, host_text, host_bytes, host_off, n_host, true, restart != 0, "psvr_signal_window_add", info);
 }
 
 extern "C" int psvr_signal_window_text(psvr_signal_t *sg, void *dst, int64_t first, int64_t n)
 {
 	if (psvr_device_count() <= 0) return sg_no_device();
 	if (!sg || first < 0 || n < 0 || (n > 0 && !dst)) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: bad argument");
-	if (!sg->valid || !sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: no window");
+	if (!sg->win_valid) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: no window");
 	if (first > sg->win_bytes || n > sg->win_bytes - first) return set_error(PSVR_ERR_ARG, "psvr_signal_window_text: bytes [%lld, %lld) of a window of %lld", (long long)first, (long long)(first + n), sg->win_bytes);
 	if (n == 0) return PSVR_OK;
 	DfwCtx &c = dfw_ctx();
@@ -717,7 +753,7 @@ extern "C" int psvr_signal_run_pos(psvr_signal_t *sg, psvr_bam_store_t *st, int6
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
 	if (int rc = store_refresh(st, c, true)) return rc;
-	sg->valid = false, sg->win_valid = false, sg->pos_valid = false;
+	sg->run_begins(), sg->pos_valid = false;
 	if (st->ordered) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: the store has been ordered: the blocks are those of its append order");
 	if (first_record < 0 || first_record > st->n_rec) return set_error(PSVR_ERR_ARG, "psvr_signal_run_pos: first record %lld of %lld", (long long)first_record, st->n_rec);
 	const long long m = st->n_rec - first_record;
@@ -890,7 +926,7 @@ extern "C" int psvr_signal_run_left(psvr_signal_t *sg, int64_t first_pair, int64
 	DfwCtx &c = dfw_ctx();
 	std::lock_guard<std::mutex> lk(c.mu);
 	if (int rc = dfw_bind(c, sg->device)) return rc;
-	sg->valid = false, sg->win_valid = false, sg->pos_valid = false, sg->left_valid = false;
+	sg->run_begins(), sg->pos_valid = false, sg->left_valid = false;
 	const long long n = sg->left_n;
 	if (n >= (1ll << 31) - 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_left: %lld unmated records (at most 2^31 - 2)", n);
 	if (n & 1) return set_error(PSVR_ERR_UNSUPPORTED, "psvr_signal_run_left: an odd number of records found no mate (%lld): the host loop ends there", n);

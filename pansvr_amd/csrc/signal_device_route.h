@@ -54,6 +54,7 @@ struct SignalRouteStats {
 	long long pairs = 0, written = 0, declined = 0, runs = 0, text_bytes = 0, peak_chunks = 0, peak_bytes = 0;
 	long long left_pairs = 0, last_chunks = 0, last_bytes = 0;   // --mate-device: pairs of the by-name pass; the store's footprint behind the last block
 	double append_s = 0, mate_s = 0, fetch_s = 0, write_s = 0;   // --mate-device: wall seconds of the route's phases
+	long long windows = 0, window_bytes = 0;                     // aln --mate-device: kept windows offered to the taker, and their bytes
 };
 
 inline psvr_signal_opt_t signal_device_options(const SignalStep &S)
@@ -71,6 +72,25 @@ template <class Backend> auto signal_route_window(Backend &be, const void *t, in
 	return be.signal_window(t, n, off, n_host, i);
 }
 template <class Backend> int signal_route_window(Backend &, const void *, int64_t, const int64_t *, int64_t, psvr_signal_window_info_t *, long) { return PSVR_ERR_UNSUPPORTED; }
+
+// the same for the add to the kept window (signal_mate_route in window mode)
+template <class Backend> auto signal_route_window_add(Backend &be, const void *t, int64_t n, const int64_t *off, int64_t n_host, int32_t restart, psvr_signal_window_info_t *i, int)
+	-> decltype(be.signal_window_add(t, n, off, n_host, restart, i))
+{
+	return be.signal_window_add(t, n, off, n_host, restart, i);
+}
+template <class Backend> int signal_route_window_add(Backend &, const void *, int64_t, const int64_t *, int64_t, int32_t, psvr_signal_window_info_t *, long) { return PSVR_ERR_UNSUPPORTED; }
+
+// window mode of both routes: SignalStep::pair writes a state-2 pair's text here, with offsets (the fused command's S.feed and S.out are put
+// back when the route ends)
+struct SignalHostText {
+	SignalStep &S; FILE *out; PairFeed *feed; char *buf = nullptr; size_t len = 0; FILE *mem = nullptr;
+	std::vector<int64_t> off;
+	SignalHostText(SignalStep &s, bool on) : S(s), out(s.out), feed(s.feed) { if (on && (mem = open_memstream(&buf, &len))) S.out = mem, S.feed = nullptr; }
+	void restart() { fflush(mem); rewind(mem); off.assign(1, 0); }
+	void pair_done() { fflush(mem); off.push_back((int64_t)ftello(mem)); }
+	~SignalHostText() { S.out = out, S.feed = feed; if (mem) fclose(mem), free(buf); }
+};
 
 template <class Backend> int signal_device_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr, SignalWindowTaker *taker = nullptr)
 {
@@ -127,15 +147,7 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 		return true;
 	};
 	auto write_out = [&](const uint8_t *p, size_t n) { if (n) fwrite(p, 1, n, S.out); };
-	// window mode: SignalStep::pair writes a state-2 pair's text here (the fused command's S.feed and S.out are put back when the route ends)
-	struct HostText {
-		SignalStep &S; FILE *out; PairFeed *feed; char *buf = nullptr; size_t len = 0; FILE *mem = nullptr;
-		std::vector<int64_t> off;
-		HostText(SignalStep &s, bool on) : S(s), out(s.out), feed(s.feed) { if (on && (mem = open_memstream(&buf, &len))) S.out = mem, S.feed = nullptr; }
-		void restart() { fflush(mem); rewind(mem); off.assign(1, 0); }
-		void pair_done() { fflush(mem); off.push_back((int64_t)ftello(mem)); }
-		~HostText() { S.out = out, S.feed = feed; if (mem) fclose(mem), free(buf); }
-	} host_text(S, taker != nullptr);
+	SignalHostText host_text(S, taker != nullptr);
 	if (taker && !host_text.mem) return left("open_memstream", "out of memory");
 	const bool walked = bgzf_for_pieces(be, f, skip, &fail, [&](const uint8_t *p, size_t have, long long skip_now, int64_t *used, PieceFail *why) {
 		int64_t bad = -1;
@@ -255,13 +267,24 @@ template <class Backend> int signal_device_route(Backend &be, SignalStep &S, lon
 // error states 4 and 5 work as above.  An odd number of left-overs is the call's to decline: the host route reads the file and ends as it does.
 // R (and the summary line) carries the phases' wall times: append (read, upload, inflate, chain), mate (run_pos, run_left), fetch (tables,
 // text, side records), write (S.out, the host-formatted pairs).
-template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr)
+//
+// The route has the same two consumers as the one above, and one body for both.  `panSVR aln --mate-device` takes windows: a run's text is
+// not downloaded; SignalStep::pair formats the state-2 pairs into SignalHostText; the backend's
+//   int signal_window_add(const void *host_text, int64_t host_bytes, const int64_t *host_off, int64_t n_host, int32_t restart, psvr_signal_window_info_t *)
+// writes the run's window behind what the kept window holds (include/psvr_engine.h), so the many small blocks of a position-sorted file
+// become few windows.  The kept window is offered to the taker when it holds window_pairs pairs, before an add that would take it to 2^32
+// bytes (window_bytes_max: that add restarts it), in front of an error pair, and behind the last slice -- not between phase 1 and phase 2.  *pairs_done
+// advances only when an offer returns; after a partial take it is translated back through the added runs' pairs (Kept::has_text).
+template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long long *pairs_done, SignalRouteStats *stats = nullptr, SignalWindowTaker *taker = nullptr, long long window_pairs = 1,
+                                               long long window_bytes_max = (long long)1 << 32)
 {
 	*pairs_done = 0;
 	SignalRouteStats R;
 	auto left_route = [&](const std::string &call, const std::string &why) {
-		fprintf(stderr, "[panSVR-amd] signal --mate-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
-		        *pairs_done);
+		if (taker) fprintf(stderr, "[panSVR-amd] aln --mate-device: %s failed (%s): %lld pairs are handed over, the host fused route reads the file from its beginning, silent up to there\n", call.c_str(),
+		                   why.c_str(), *pairs_done);
+		else fprintf(stderr, "[panSVR-amd] signal --mate-device: %s failed (%s): %lld pairs are written, the host route reads the file from its beginning, silent up to there\n", call.c_str(), why.c_str(),
+		             *pairs_done);
 		return -1;
 	};
 	struct Clock {
@@ -312,6 +335,33 @@ template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long 
 		*cap = n + n / 4;
 		return true;
 	};
+	SignalHostText host_text(S, taker != nullptr);
+	if (taker && !host_text.mem) return left_route("open_memstream", "out of memory");
+	// window mode: the kept window -- the pairs in front of it, and per pair added since its restart whether the window holds text of it
+	struct Kept {
+		bool open = false;
+		psvr_signal_window_info_t info = {0, 0, 0};
+		long long first_pair = 0;
+		std::vector<uint8_t> has_text;
+	} kept;
+	// the kept window goes to the taker; behind it the next add restarts.  false: fewer pairs were taken, *pairs_done says how far
+	auto offer = [&](PieceFail *why) {
+		if (!kept.open) return true;
+		std::string taker_why;
+		const long long taken = kept.info.n_pairs > 0 ? taker->offer(kept.info, &taker_why) : 0;
+		if (kept.info.n_pairs > 0) ++R.windows, R.window_bytes += kept.info.n_bytes;
+		if (taken != kept.info.n_pairs) {                        // the pairs in front of the first one that was not taken are handed over
+			long long seen = 0;
+			size_t q = 0;
+			for (; q < kept.has_text.size() && seen < taken; ++q) seen += kept.has_text[q];
+			*pairs_done = kept.first_pair + (long long)q;
+			*why = {"taking a window", taker_why};
+			return false;
+		}
+		*pairs_done = kept.first_pair + (long long)kept.has_text.size();
+		kept.open = false;
+		return true;
+	};
 	auto progress = [&]() { total += 2; if (total % 100000 == 0) fprintf(stderr, "%ld\n", (long)total); };
 	// the pairing-error steps in front of pair q of a slice (errs: signal_left_errors; empty for a block)
 	auto error_steps = [&](long long upto) {
@@ -329,16 +379,18 @@ template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long 
 			if (info.pairs && be.signal_pairs(tab.data(), info.pairs)) { *why = {"signal pairs", be.last_error()}; return false; }
 			errs.assign(slice ? (size_t)info.pairs : 0, 0);
 			if (slice && info.pairs && be.signal_left_errors(errs.data(), info.pairs)) { *why = {"signal left_errors", be.last_error()}; return false; }
-			if (!room(&guard.text, &text_cap, (size_t)info.text_bytes, why) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
-			if (info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
+			if ((!taker && !room(&guard.text, &text_cap, (size_t)info.text_bytes, why)) || !room(&guard.side, &side_cap, (size_t)info.side_bytes, why)) return false;
+			if (!taker && info.text_bytes && be.signal_text(guard.text, (int64_t)text_cap)) { *why = {"signal text", be.last_error()}; return false; }
 			if (info.side_bytes && be.signal_side(guard.side, (int64_t)side_cap)) { *why = {"signal side", be.last_error()}; return false; }
 			side_bytes = info.side_bytes;
 		}
 		Clock clock{&R.write_s};
+		if (taker) host_text.restart();
 		const int64_t n_front = info.first_error >= 0 ? info.first_error : info.pairs;
 		int64_t flushed = 0;
 		BamRecord a, b;
 		auto flush_to = [&](int64_t q) {
+			if (taker) return;                                   // (window mode: nothing is handed over before a window is)
 			const int64_t upto = q < info.pairs ? tab[(size_t)q].text_off : info.text_bytes;
 			if (upto > flushed) fwrite(guard.text + flushed, 1, (size_t)(upto - flushed), S.out);
 			flushed = upto;
@@ -354,7 +406,8 @@ template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long 
 				S.stat_written = any_written;
 				S.pair(a, b, true);
 				any_written = true, ++R.declined;
-				*pairs_done = R.pairs + q + 1;
+				if (taker) host_text.pair_done();
+				else *pairs_done = R.pairs + q + 1;
 				continue;
 			}
 			if (t.note & 1) {
@@ -365,8 +418,19 @@ template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long 
 			if (t.state == 1) any_written = true, ++R.written;
 		}
 		flush_to(n_front);
+		if (taker) {                                             // the run's window behind what the kept window holds
+			const int64_t n_host = (int64_t)host_text.off.size() - 1, host_bytes = host_text.off.back();
+			if (kept.open && kept.info.n_bytes + info.text_bytes + host_bytes >= window_bytes_max && !offer(why)) return false;
+			const bool restart = !kept.open;
+			psvr_signal_window_info_t wi;
+			if (signal_route_window_add(be, host_text.buf, host_bytes, host_text.off.data(), n_host, restart ? 1 : 0, &wi, 0)) { *why = {"signal window_add", be.last_error()}; return false; }
+			if (restart) kept.first_pair = R.pairs, kept.has_text.clear();
+			kept.open = true, kept.info = wi;
+			for (int64_t q = 0; q < n_front; ++q) kept.has_text.push_back(tab[(size_t)q].state == 1 || tab[(size_t)q].state == 2);
+		}
 		R.pairs += n_front, R.text_bytes += info.text_bytes;
 		if (slice) R.left_pairs += n_front;
+		if (taker && (kept.info.n_pairs >= window_pairs || info.first_error >= 0) && !offer(why)) return false;
 		if (info.first_error < 0) return true;
 		const psvr_signal_pair_t &t = tab[(size_t)info.first_error];   // the pair the host loop aborts on
 		fflush(S.out);
@@ -443,9 +507,12 @@ template <class Backend> int signal_mate_route(Backend &be, SignalStep &S, long 
 		first += li.n_pairs;
 	}
 	error_steps(li.errors);
+	if (taker && !offer(&fail)) return left_route(fail.call, fail.why);   // what the kept window still holds
 	if (be.signal_stats(S.bs.isize_n.data(), S.bs.len_n.data())) return left_route("signal stats", be.last_error());
 	S.bs.total = (uint64_t)total;
-	fprintf(stderr, "[panSVR-amd] signal --mate-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld paired by name, %lld blocks, %lld text bytes, peak footprint %lld chunks (%lld bytes), %lld chunks (%lld bytes) behind the last block; append %.3f s, mate %.3f s, fetch %.3f s, write %.3f s\n",
+	if (taker) fprintf(stderr, "[panSVR-amd] aln --mate-device: %lld pairs, %lld formatted on the device, %lld formatted by the host, %lld paired by name, %lld blocks, %lld windows offered, %lld window bytes, peak footprint %lld chunks (%lld bytes), %lld chunks (%lld bytes) behind the last block; append %.3f s, mate %.3f s, fetch %.3f s, write %.3f s\n",
+	                   R.pairs, R.written, R.declined, R.left_pairs, R.runs, R.windows, R.window_bytes, R.peak_chunks, R.peak_bytes, R.last_chunks, R.last_bytes, R.append_s, R.mate_s, R.fetch_s, R.write_s);
+	else fprintf(stderr, "[panSVR-amd] signal --mate-device: %lld pairs, %lld written on the device, %lld declined to the host, %lld paired by name, %lld blocks, %lld text bytes, peak footprint %lld chunks (%lld bytes), %lld chunks (%lld bytes) behind the last block; append %.3f s, mate %.3f s, fetch %.3f s, write %.3f s\n",
 	        R.pairs, R.written, R.declined, R.left_pairs, R.runs, R.text_bytes, R.peak_chunks, R.peak_bytes, R.last_chunks, R.last_bytes, R.append_s, R.mate_s, R.fetch_s, R.write_s);
 	if (stats) *stats = R;
 	return 0;

@@ -19,10 +19,12 @@ struct psvr_signal {
 	const psvr_bam_store *store = nullptr;
 	long long store_generation = 0, first_record = 0, pairs = 0, text_bytes = 0, side_bytes = 0;
 	long long n_front = 0, written = 0, declined = 0;        // pairs in front of the first error pair; of those in state 1, in state 2
-	// the last run's window (psvr_signal_window): gone with the next run
+	// the window: the last run's (psvr_signal_window), gone with the next run, or a kept one (psvr_signal_window_add), which grows run by run
+	// and stays until a restart or a psvr_signal_window call
 	psvr::DevBuf wflag, wrank, wcut, wseg, whost, whoff, window;
-	bool win_valid = false;
-	long long win_bytes = 0;
+	bool win_valid = false, win_kept = false;
+	long long win_bytes = 0, win_pairs = 0, win_host_pairs = 0;
+	void run_begins() { valid = false; if (!win_kept) win_valid = false; }
 	// psvr_signal_run_pos: the block's structure of arrays, the mate tables, the lists, the unmated records side by side, the notes
 	psvr::DevBuf bprim, spos, smpos, sflag, ssame, cand, indeg, mate, dirty, fail, doff, dlist, pflag, lflag, pfoff, lfoff, ffoff, lbytes, lboff, left, notes, mctl;
 	long long *h_mctl = nullptr;                             // page-locked read-back of mctl

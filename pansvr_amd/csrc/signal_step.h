@@ -3,7 +3,8 @@
 // inflated, paired, judged and formatted in GPU memory (signal_device_route.h over psvr_signal_*; the fused `aln -N --bam-device` runs the
 // same route and hands the text to aln's reader stage where it lies, a window per run); without -N, `--mate-device` runs the blocks of the
 // position-sorted mode the same way (signal_mate_route over psvr_signal_run_pos: the mates found on the device by the rules of
-// signal_mate_device.h, the left-overs kept in a second store there and paired by psvr_signal_run_left).  This file's pair() stays the
+// signal_mate_device.h, the left-overs kept in a second store there and paired by psvr_signal_run_left; the fused `aln --mate-device` runs
+// that route and hands over a kept window that the runs of many blocks have been added to).  This file's pair() stays the
 // specification: it formats the few pairs the device declines, and it takes over, muted up to the pairs already written, whenever that route
 // is left.  Restated from PanSVgenerateVCF/getSignalRead.cpp / .hpp and the helpers of clib/bam_file.c it calls; PARITY UNPINNED:
 // the reference's build of this step needs htslib, which cannot be built in this image, so the only checker is the independent
@@ -46,6 +47,7 @@ struct SignalOpt {
 	bool signal_device = false;                                                             // --signal-device: signal_device_route.h (with -N)
 	bool bam_device = false;                                                                // aln --bam-device: the same route, its windows handed to aln's reader stage
 	bool mate_device = false;                                                               // --mate-device: the position-sorted mode's blocks mated on the device (signal_device_route.h)
+	bool mate_fused = false;                                                                // aln --mate-device: the same route, its kept windows handed to aln's reader stage
 	int block_records = 1000000;                                                            // --block-records N: SAM_LOAD_BUFF_SIZE, the primary records of a block at the most
 };
 
@@ -463,14 +465,17 @@ struct SignalStep {
 				bs.reset(), stat_written = false;               // the host route from the file's beginning, muted for the pairs that are written
 			}
 		}
-		if (o.mate_device) {
-			const char *no = o.sort_by_name           ? "it is the position-sorted mode's route: -N has --signal-device"
+		if (o.mate_device || o.mate_fused) {
+			// (aln --mate-device is the fused command's form of the route: it needs the feed, `signal --mate-device` must not have one)
+			const bool fused = o.mate_fused;
+			const char *no = o.sort_by_name           ? (fused ? "it is the position-sorted mode's route: -N has --bam-device" : "it is the position-sorted mode's route: -N has --signal-device")
 			                 : o.sample_rate < 0.9999 ? "-R draws rand() per pair in the host loop's order"
 			                 : o.signal_device        ? "--signal-device is the name-sorted mode's route: give one of the two"
-			                 : feed                   ? "the fused aln route hands its pairs over on the host"
+			                 : !fused && feed         ? "the fused aln route hands its pairs over on the host"
 			                 : !mate_device_fn        ? "this build has no device route"
 			                                          : nullptr;
-			if (no) fprintf(stderr, "[panSVR-amd] signal --mate-device: refused (%s): the host route runs\n", no);
+			if (no && fused) fprintf(stderr, "[panSVR-amd] aln --mate-device: refused (%s): the host fused route runs\n", no);
+			else if (no) fprintf(stderr, "[panSVR-amd] signal --mate-device: refused (%s): the host route runs\n", no);
 			else {
 				const int rc = mate_device_fn(*this, &mute);
 				if (rc > 0) abort();                            // (a pair the host loop aborts on; the route has written what lies in front of it and said why)

@@ -17,6 +17,13 @@
 // Bounds: sw_args_bad has refused offsets that are not monotone or do not end at host_bytes; cut[] comes from the run's own scan and is
 // monotone inside [0, text_bytes]; so every segment lies inside its source, the output offsets run from 0 to text_bytes + host_bytes
 // without a gap, and a tile writes out[a, b) only.
+//
+// The add (psvr_signal_window_add): the same passes write a run's window behind the bytes a kept window already holds, at `base`.  The output
+// is window bytes [base, base + n_out); the segments' output offsets are the ones above plus base (sw_segment_add); the tiles are the
+// kSwTileBytes-aligned tiles of the whole window that meet that range (sw_add_tiles), so only an add's first tile can begin off a 16-byte
+// boundary -- copy_aligned_lanes takes any destination residue, and a later tile pays a comparison for it; a tile writes
+// [max(a, base), min(b, base + n_out)) and nothing else (sw_tile_add), so two adds that share a tile never touch each other's bytes.  The
+// window of a run is the add at base 0: sw_tile and sw_window_host are that.
 #pragma once
 #include <stdint.h>
 #include "copy_aligned_device.h"
@@ -57,7 +64,19 @@ PSVR_COPY SwSeg sw_segment(int64_t k, int64_t H, const int64_t *cut, const int64
 	return s;
 }
 
-// the last segment whose output offset is <= at (segment 0 starts at 0: there always is one)
+// segment k of an add at base: the same segment, its place in the window base bytes further on
+PSVR_COPY SwSeg sw_segment_add(int64_t k, int64_t H, const int64_t *cut, const int64_t *host_off, int64_t text_bytes, int64_t base)
+{
+	SwSeg s = sw_segment(k, H, cut, host_off, text_bytes);
+	s.out += base;
+	return s;
+}
+
+// the tiles of the whole window that meet [base, base + n_out): the first one, and how many
+PSVR_COPY int64_t sw_add_first_tile(int64_t base) { return base / kSwTileBytes; }
+PSVR_COPY int64_t sw_add_tiles(int64_t base, int64_t n_out) { return n_out > 0 ? (base + n_out + kSwTileBytes - 1) / kSwTileBytes - base / kSwTileBytes : 0; }
+
+// the last segment whose output offset is <= at (segment 0 starts at the first byte anybody asks for: there always is one)
 PSVR_COPY int64_t sw_first_segment(const SwSeg *seg, int64_t n_seg, int64_t at)
 {
 	int64_t lo = 0, hi = n_seg;                              // seg[lo].out <= at < seg[hi].out
@@ -68,10 +87,11 @@ PSVR_COPY int64_t sw_first_segment(const SwSeg *seg, int64_t n_seg, int64_t at)
 	return lo;
 }
 
-// tile t of the window out[0, n_out) by lanes [0, n_lanes) that all come here
-PSVR_COPY void sw_tile(int64_t t, const SwSeg *seg, int64_t n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, int64_t n_out, long long lane, long long n_lanes)
+// tile t of the whole window, for the add whose bytes are out[base, end): by lanes [0, n_lanes) that all come here
+PSVR_COPY void sw_tile_add(int64_t t, const SwSeg *seg, int64_t n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, int64_t base, int64_t end, long long lane, long long n_lanes)
 {
-	const int64_t a = t * kSwTileBytes, b = a + kSwTileBytes < n_out ? a + kSwTileBytes : n_out;
+	const int64_t ta = t * kSwTileBytes, tb = ta + kSwTileBytes;
+	const int64_t a = ta > base ? ta : base, b = tb < end ? tb : end;
 	if (a >= b) return;
 	for (int64_t k = sw_first_segment(seg, n_seg, a); k < n_seg && seg[k].out < b; ++k) {
 		const SwSeg s = seg[k];
@@ -81,6 +101,12 @@ PSVR_COPY void sw_tile(int64_t t, const SwSeg *seg, int64_t n_seg, const uint8_t
 	}
 }
 
+// tile t of the window out[0, n_out) by lanes [0, n_lanes) that all come here
+PSVR_COPY void sw_tile(int64_t t, const SwSeg *seg, int64_t n_seg, const uint8_t *text, const uint8_t *host, uint8_t *out, int64_t n_out, long long lane, long long n_lanes)
+{
+	sw_tile_add(t, seg, n_seg, text, host, out, 0, n_out, lane, n_lanes);
+}
+
 } // namespace psvr
 
 #if !defined(__HIPCC__)
@@ -88,18 +114,26 @@ PSVR_COPY void sw_tile(int64_t t, const SwSeg *seg, int64_t n_seg, const uint8_t
 #include <vector>
 namespace psvr {
 
-// state[n_front], toff[n_front] of a run with text[0, text_bytes); out has text_bytes + host_off[n_host] bytes.  The segment table comes back.
-inline std::vector<SwSeg> sw_window_host(const uint8_t *state, const int64_t *toff, int64_t n_front, const uint8_t *text, int64_t text_bytes, const uint8_t *host,
-                                         const int64_t *host_off, int64_t n_host, uint8_t *out)
+// state[n_front], toff[n_front] of a run with text[0, text_bytes), added at base: out is the whole window and has base + text_bytes +
+// host_off[n_host] bytes, of which [0, base) are not touched.  The segment table comes back.
+inline std::vector<SwSeg> sw_window_add_host(const uint8_t *state, const int64_t *toff, int64_t n_front, const uint8_t *text, int64_t text_bytes, const uint8_t *host,
+                                             const int64_t *host_off, int64_t n_host, uint8_t *out, int64_t base)
 {
 	std::vector<int64_t> rank((size_t)n_front + 1, 0), cut((size_t)n_host, 0);
 	for (int64_t p = 0; p < n_front; ++p) rank[(size_t)p + 1] = rank[(size_t)p] + sw_flag(p, n_front, state);
 	for (int64_t p = 0; p < n_front; ++p) if (sw_flag(p, n_front, state)) cut[(size_t)rank[(size_t)p]] = toff[p];
 	std::vector<SwSeg> seg((size_t)(2 * n_host + 1));
-	for (int64_t k = 0; k < 2 * n_host + 1; ++k) seg[(size_t)k] = sw_segment(k, n_host, cut.data(), host_off, text_bytes);
-	const int64_t n_out = text_bytes + (n_host ? host_off[n_host] : 0);
-	for (int64_t t = 0; t * kSwTileBytes < n_out; ++t) sw_tile(t, seg.data(), (int64_t)seg.size(), text, host, out, n_out, 0, 1);
+	for (int64_t k = 0; k < 2 * n_host + 1; ++k) seg[(size_t)k] = sw_segment_add(k, n_host, cut.data(), host_off, text_bytes, base);
+	const int64_t n_out = text_bytes + (n_host ? host_off[n_host] : 0), t0 = sw_add_first_tile(base);
+	for (int64_t t = 0; t < sw_add_tiles(base, n_out); ++t) sw_tile_add(t0 + t, seg.data(), (int64_t)seg.size(), text, host, out, base, base + n_out, 0, 1);
 	return seg;
+}
+
+// the window of a run: the add at base 0.  out has text_bytes + host_off[n_host] bytes.
+inline std::vector<SwSeg> sw_window_host(const uint8_t *state, const int64_t *toff, int64_t n_front, const uint8_t *text, int64_t text_bytes, const uint8_t *host,
+                                         const int64_t *host_off, int64_t n_host, uint8_t *out)
+{
+	return sw_window_add_host(state, toff, n_front, text, text_bytes, host, host_off, n_host, out, 0);
 }
 
 } // namespace psvr

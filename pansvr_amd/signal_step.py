@@ -147,6 +147,17 @@ class Signal:
         self.window_info = i
         return i
 
+    def window_add(self, host_text=b"", off=(0,), restart=False):
+        """psvr_signal_window_add: the last run's window (as window() makes it) written behind what the object's kept window holds; restart
+        empties the kept window first.  Returns SignalWindowInfo with the kept window's totals; window_text() reads it"""
+        text = np.frombuffer(bytes(host_text) or b"\0", dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        i = SignalWindowInfo()
+        check(lib().psvr_signal_window_add(self.h, text.ctypes.data_as(C.c_void_p), C.c_int64(len(host_text)), off.ctypes.data_as(C.c_void_p), C.c_int64(len(off) - 1),
+                                           C.c_int32(int(restart)), C.byref(i)))
+        self.window_info = i
+        return i
+
     def window_text(self, first=0, n=None):
         """bytes [first, first + n) of the window (to its end by default)"""
         if n is None:

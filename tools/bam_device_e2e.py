@@ -1,4 +1,4 @@
-"""`panSVR aln -N` on a name-sorted BAM end to end, the host fused routes against `--bam-device`, on the bench batch (bench.py's workload: 10 000
+"""`panSVR aln` on a BAM end to end -- by default `aln -N` on a name-sorted one, the host fused routes against `--bam-device`, on the bench batch (bench.py's workload: 10 000
 anchors, seed 11; the reads of rank 0, seed 13) written as a BAM by tests/test_fused_signal.py's rule -- every read keeps its original
 alignment, second reads carry 0x80 -- once, outside any timed region, into RAM-backed storage.  Routes:
     parent_serial, parent_threads16     aln -N -D in.bam --deflate-device [--inflate-threads 16]        the parent commit's binary
@@ -9,7 +9,11 @@ The parent's binary is parent_bin/bin/panSVR beside its library (git-ignored); w
 One discarded process, then --reps interleaved repetitions, every command in a fresh child under its own time limit; the wall is the host
 clock around the child (for two steps: the sum), the stage times come from the command's e2e_json line.  The files of corresponding routes
 are compared byte for byte (the unsorted routes by their inflated payloads: the member cuts differ between the host writer and the stream).
-    python tools/bam_device_e2e.py OUT.json [--pairs 1000000] [--threads 16] [--reps 3] [--kernel-stats FILE.csv]"""
+    python tools/bam_device_e2e.py OUT.json [--pairs 1000000] [--threads 16] [--reps 3] [--kernel-stats FILE.csv] [--order position]
+--order position: the same for `panSVR aln` without -N and `--mate-device`.  The BAM is put in coordinate order by `panSVR sort` outside every
+timed region; the parent's two steps are signal -D --mate-device > fq, then aln --stream-device fq; the new routes are mate_device,
+mate_device_stream and mate_device_sort.  One further run of each new route at --block-records 8192 reports the blocks, the windows offered
+and the pieces (many small blocks put together into few windows)."""
 import argparse
 import glob
 import gzip
@@ -113,6 +117,7 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--kernel-stats")
+    ap.add_argument("--order", choices=("name", "position"), default="name")
     a = ap.parse_args()
     if not os.path.exists(PARENT):
         raise SystemExit("no parent binary at %s: the build under test is never its own baseline" % PARENT)
@@ -125,16 +130,22 @@ def main():
         inp = os.path.join(tmp, "in.bam")
         raw = write_bam(inp, bases, base_off, ori, isize, min(16, os.cpu_count() or 1))
         del bases, base_off, ori, isize
+        pos = a.order == "position"
+        option, key, sig = ("--mate-device", "mate_device", ("-D",)) if pos else ("--bam-device", "bam_device", ("-N", "-D"))
+        if pos:                                                          # coordinate order, by the command's own sort
+            child([NEW, "sort", "-t", str(a.threads), "-o", os.path.join(tmp, "sorted.bam"), inp])
+            os.remove(inp)
+            inp = os.path.join(tmp, "sorted.bam")
         print("input ready: %d bytes (%d inflated)" % (os.path.getsize(inp), raw), flush=True)
         idx, hdr, t = os.path.join(tmp, "idx"), os.path.join(tmp, "h.sam"), ["-t", str(a.threads)]
 
-        def aln(exe, tag, flags, reads=inp, signal_flags=("-N", "-D")):
+        def aln(exe, tag, flags, reads=inp, signal_flags=sig):
             return [exe, "aln"] + t + list(signal_flags) + ["-o", os.path.join(tmp, tag + ".bam"), "-p", os.path.join(tmp, tag + ".ori.bam")] + flags + [idx, reads, hdr]
 
         def two_steps(tag):
             fq = os.path.join(tmp, "two.fq")
             with open(fq, "wb") as f:
-                w1, _ = child([PARENT, "signal", "-N", "-D", "--signal-device", "-H", os.path.join(tmp, "h2.sam"), "-S", os.path.join(tmp, "s2.txt"), inp], f)
+                w1, _ = child([PARENT, "signal"] + list(sig) + ["--mate-device" if pos else "--signal-device", "-H", os.path.join(tmp, "h2.sam"), "-S", os.path.join(tmp, "s2.txt"), inp], f)
             hdr2 = os.path.join(tmp, "h2.sam")
             w2, err = child([PARENT, "aln"] + t + ["-o", os.path.join(tmp, tag + ".bam"), "-p", os.path.join(tmp, tag + ".ori.bam"), "--stream-device", idx, fq, hdr2])
             return w1 + w2, err, {"signal_wall_s": round(w1, 4), "aln_wall_s": round(w2, 4)}
@@ -143,33 +154,46 @@ def main():
                   ("parent_threads16", lambda: child(aln(PARENT, "parent_threads16", ["--deflate-device", "--inflate-threads", "16"]))),
                   ("parent_two_steps", lambda: two_steps("parent_two_steps")),
                   ("parent_sort", lambda: child(aln(PARENT, "parent_sort", ["--sort", "--deflate-device"]))),
-                  ("bam_device", lambda: child(aln(NEW, "bam_device", ["--bam-device", "--deflate-device"]))),
-                  ("bam_device_stream", lambda: child(aln(NEW, "bam_device_stream", ["--bam-device", "--stream-device"]))),
-                  ("bam_device_sort", lambda: child(aln(NEW, "bam_device_sort", ["--bam-device", "--sort-device"])))]
-        res = {"pairs": a.pairs, "threads": a.threads, "reps": a.reps, "input_bytes": os.path.getsize(inp), "inflated_bytes": raw, "runs": {k: [] for k, _ in routes}, "stages": {}, "lines": {}}
+                  (key, lambda: child(aln(NEW, key, [option, "--deflate-device"]))),
+                  (key + "_stream", lambda: child(aln(NEW, key + "_stream", [option, "--stream-device"]))),
+                  (key + "_sort", lambda: child(aln(NEW, key + "_sort", [option, "--sort-device"])))]
+        res = {"order": a.order, "pairs": a.pairs, "threads": a.threads, "reps": a.reps, "input_bytes": os.path.getsize(inp), "inflated_bytes": raw, "runs": {k: [] for k, _ in routes}, "stages": {}, "lines": {}}
+        def route_line(err):
+            """the device route's summary line; a route that was left or refused ends the measurement"""
+            line = [l for l in err.split("\n") if "aln %s:" % option in l]
+            if not line or " failed (" in line[-1] or "refused" in line[-1]:
+                raise SystemExit("%s left the device route:\n" % option + err[-2000:])
+            return line[-1].split("aln %s: " % option, 1)[1]
+
         routes[0][1]()                                                   # the discarded first process
         for rep in range(a.reps):
             for name, fn in routes:
                 got = fn()
                 res["runs"][name].append(round(got[0], 4))
                 res["stages"].setdefault(name, []).append(dict(stages(got[1]), **(got[2] if len(got) > 2 else {})))
-                if name.startswith("bam_device"):
-                    line = [l for l in got[1].split("\n") if "aln --bam-device:" in l]
-                    if not line or "failed" in line[-1] or "refused" in line[-1]:
-                        raise SystemExit("--bam-device left the device route:\n" + got[1][-2000:])
-                    res["lines"][name] = line[-1].split("aln --bam-device: ", 1)[1]
+                if name.startswith(key):
+                    res["lines"][name] = route_line(got[1])
                 print(rep, name, "%.3f" % got[0], flush=True)
 
         def payload(tag, ext):
             return gzip.open(os.path.join(tmp, tag + ext), "rb").read()
         ref = [payload("parent_serial", e) for e in (".bam", ".ori.bam")]
-        res["same_payload"] = {k: [payload(k, e) for e in (".bam", ".ori.bam")] == ref for k in ("parent_threads16", "parent_two_steps", "bam_device", "bam_device_stream")}
+        res["same_payload"] = {k: [payload(k, e) for e in (".bam", ".ori.bam")] == ref for k in ("parent_threads16", "parent_two_steps", key, key + "_stream")}
         del ref
-        res["same_sorted_files"] = all(open(os.path.join(tmp, "bam_device_sort" + e), "rb").read() == open(os.path.join(tmp, "parent_sort" + e), "rb").read() for e in (".bam", ".bam.bai", ".ori.bam"))
+        res["same_sorted_files"] = all(open(os.path.join(tmp, key + "_sort" + e), "rb").read() == open(os.path.join(tmp, "parent_sort" + e), "rb").read() for e in (".bam", ".bam.bai", ".ori.bam"))
         res["summary"] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in res["runs"].items()}
+        if pos:                                                          # many small blocks: what becomes of them
+            res["block_records_8192"] = {}
+            for name, flags in ((key, ["--deflate-device"]), (key + "_stream", ["--stream-device"]), (key + "_sort", ["--sort-device"])):
+                wall, err = child(aln(NEW, name + "_8192", [option, "--block-records", "8192"] + flags))
+                line = route_line(err)
+                w = line.replace(",", "").split()
+                res["block_records_8192"][name] = {"wall_s": round(wall, 4), "blocks": int(w[w.index("blocks") - 1]), "windows": int(w[w.index("windows") - 1]),
+                                                   "pieces": stages(err).get("pieces"), "line": line}
+                print("8192", name, "%.3f" % wall, flush=True)
         if a.kernel_stats:
             d = os.path.join(tmp, "prof")
-            wall, _ = child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "bamdev", "--output-format", "csv", "--"] + aln(NEW, "traced", ["--bam-device", "--stream-device"]))
+            wall, _ = child(["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "bamdev", "--output-format", "csv", "--"] + aln(NEW, "traced", [option, "--stream-device"]))
             found = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
             if not found:
                 raise SystemExit("rocprofv3 left no kernel_stats.csv under " + d)
