@@ -618,6 +618,25 @@ struct ReaderWindowTaker : psvr::SignalWindowTaker {
 	ReaderWindowTaker(SignalCmdBackend &b, WindowFeed &w) : be(b), windows(w) {}
 	long long offer(const psvr_signal_window_info_t &info, std::string *why) override { return windows.offer(be.sg, info.n_pairs, why); }
 };
+// the fused command's device route: route(be, S, pairs_done, &taker) is signal_device_route or signal_mate_route in window mode
+template <class Route> static std::function<int(psvr::SignalStep &, long long *)> window_route_fn(const Opt &o, WindowFeed &windows, Route route)
+{
+	return [&o, &windows, route](psvr::SignalStep &S, long long *pairs_done) {
+		SignalCmdBackend be(o.devices[0]);
+		ReaderWindowTaker taker(be, windows);
+		const int rc = route(be, S, pairs_done, &taker);
+		windows.close(rc != 0);                              // (left: the host fused route hands the rest over through the PairFeed)
+		return rc;
+	};
+}
+// `panSVR signal`'s: route(be, S, pairs_done) is one of the two with text for its consumer
+template <class Route> static std::function<int(psvr::SignalStep &, long long *)> text_route_fn(Route route)
+{
+	return [route](psvr::SignalStep &S, long long *pairs_done) {
+		SignalCmdBackend be(0);
+		return route(be, S, pairs_done);
+	};
+}
 
 // --sort: the main file, its records ordered on the first device, written with the index.  0, or the command's exit status
 static int write_sorted_main(const Opt &o, const HeaderInfo &H, const std::vector<BamRef> &bam_refs, const SortRecords &sorted, aln::RunStats *st)
@@ -664,24 +683,16 @@ static int aln_main(int argc, char **argv)
 	WindowFeed windows;
 	if (o.bam_device) {
 		sig.o.bam_device = true;
-		sig.signal_device_fn = [&o, &windows](psvr::SignalStep &S, long long *pairs_done) {
-			SignalCmdBackend be(o.devices[0]);
-			ReaderWindowTaker taker(be, windows);
-			const int rc = psvr::signal_device_route(be, S, pairs_done, nullptr, &taker);
-			windows.close(rc != 0);                              // (left: the host fused route hands the rest over through the PairFeed)
-			return rc;
-		};
+		sig.signal_device_fn = window_route_fn(o, windows, [](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done, ReaderWindowTaker *taker) {
+			return psvr::signal_device_route(be, S, pairs_done, nullptr, taker);
+		});
 	}
 	if (o.mate_device) {
 		sig.o.mate_fused = true;
-		sig.mate_device_fn = [&o, &windows](psvr::SignalStep &S, long long *pairs_done) {
-			SignalCmdBackend be(o.devices[0]);
-			ReaderWindowTaker taker(be, windows);
+		sig.mate_device_fn = window_route_fn(o, windows, [&o](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done, ReaderWindowTaker *taker) {
 			// (a kept window is offered when it holds a piece's pairs: the reader cuts it by the piece rule, and few pieces end short at a window's end)
-			const int rc = psvr::signal_mate_route(be, S, pairs_done, nullptr, &taker, o.sub_pairs > 0 ? o.sub_pairs : o.batch_pairs);
-			windows.close(rc != 0);                              // (left: the host fused route hands the rest over through the PairFeed)
-			return rc;
-		};
+			return psvr::signal_mate_route(be, S, pairs_done, nullptr, taker, o.sub_pairs > 0 ? o.sub_pairs : o.batch_pairs);
+		});
 	}
 	const bool device_input = o.bam_device || o.mate_device;   // the reader stage takes windows of text in HBM
 	if (o.from_bam) sig_thread = start_signal_step(o, sig, feed, device_input ? &windows : nullptr, &sig_rc);
@@ -771,13 +782,9 @@ static int aln_main(int argc, char **argv)
 int main(int argc, char **argv)
 {
 	if (argc >= 2 && !strcmp(argv[1], "index")) return index_main(argc, argv);
-	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv, [](psvr::SignalStep &S, long long *pairs_done) {
-			SignalCmdBackend be(0);
-			return psvr::signal_device_route(be, S, pairs_done);
-		}, [](psvr::SignalStep &S, long long *pairs_done) {
-			SignalCmdBackend be(0);
-			return psvr::signal_mate_route(be, S, pairs_done);
-		});
+	if (argc >= 2 && (!strcmp(argv[1], "signal") || !strcmp(argv[1], "fc_signal"))) return psvr::signal_main(argc, argv,
+			text_route_fn([](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done) { return psvr::signal_device_route(be, S, pairs_done); }),
+			text_route_fn([](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done) { return psvr::signal_mate_route(be, S, pairs_done); }));
 	if (argc >= 2 && !strcmp(argv[1], "sort"))
 		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name) {
 			SortCmdBackend be(0);

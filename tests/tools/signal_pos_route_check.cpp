@@ -1,251 +1,14 @@
-// signal_pos_route_check -- `panSVR signal --mate-device` without a GPU: signal_mate_route (pansvr_amd/csrc/signal_device_route.h) over the
-// host-memory backend of signal_device_route_check.cpp plus the three calls of the position-sorted mode, which run the rules of
-// signal_mate_device.h with one lane (signal_mate_host.h) and the per-pair rules of signal_device.h over the pair list, by
-// psvr_signal_run_pos's steps.  The command line is `panSVR signal`'s (tests/test_signal_pos_route.py compares with the command's host route).
-//   PSVR_CHECK_FAIL=call:n     as there; the new names are signal_run_pos, signal_mate_notes, signal_run_left, signal_left_errors
+// signal_pos_route_check -- `panSVR signal --mate-device` without a GPU: signal_mate_route (pansvr_amd/csrc/signal_device_route.h) over
+// signal_route_host.h's host-memory backend.  The command line is `panSVR signal`'s (tests/test_signal_pos_route.py compares with the
+// command's host route); the variables are that header's (tests/test_signal_mate_gpu.py reads the PSVR_CHECK_DUMP files).
 // An error state that the route returns (4, 5) ends the program with status 30 + state instead of SignalStep::run's abort().
-#define main signal_device_route_check_main
-#include "signal_device_route_check.cpp"
-#undef main
-#include "signal_mate_host.h"
-
-struct PosBackend : HostBackend {
-	long long mate_failed = 0;
-	std::vector<psvr_signal_mate_note_t> notes;
-	std::string left;
-	std::vector<std::string> left_store;                     // the unmated records of all blocks, in append order
-	std::vector<size_t> left_ord;
-	std::vector<std::pair<size_t, size_t>> left_pairs;       // indices into left_store
-	std::vector<int64_t> left_errs, slice_errs;              // per pair: the error steps in front of it
-	int64_t left_err_total = 0;
-	bool left_ordered = false;
-
-	// PSVR_CHECK_DUMP=prefix: what every call answered, for tests/test_signal_mate_gpu.py to hold the device to.  prefix.calls has per call
-	//   O <the 15 numbers of psvr_signal_opt_t>                                            (signal_create)
-	//   B primaries consumed unmated left_bytes mate_failed notes replayed | L records pairs errors first_pair n_pairs more
-	//   I pairs written declined first_error text_bytes side_bytes
-	//   P state note bytes rec1 rec2 side_off text_off errors_in_front   (per pair; the last is 0 for a block)
-	//   N number index block tid pos name                                  (per note)
-	// and prefix.<call>.text / .side / .left hold the call's bytes.
-	FILE *dump_f = nullptr;
-	std::string dump_prefix;
-	long long dump_calls = 0;
-	void dump_blob(const char *what, const std::string &b)
-	{
-		FILE *f = fopen((dump_prefix + "." + std::to_string(dump_calls) + "." + what).c_str(), "wb");
-		if (f) fwrite(b.data(), 1, b.size(), f), fclose(f);
-	}
-	void dump_call(const std::string &head, const psvr_signal_info_t &info, const std::vector<int64_t> *errs)
-	{
-		if (!dump_f) return;
-		fprintf(dump_f, "%s\nI %lld %lld %lld %lld %lld %lld\n", head.c_str(), (long long)info.pairs, (long long)info.written, (long long)info.declined, (long long)info.first_error, (long long)info.text_bytes,
-		        (long long)info.side_bytes);
-		for (size_t p = 0; p < tab.size(); ++p)
-			fprintf(dump_f, "P %d %d %d %lld %lld %lld %lld %lld\n", tab[p].state, tab[p].note, tab[p].bytes, (long long)tab[p].rec1, (long long)tab[p].rec2, (long long)tab[p].side_off, (long long)tab[p].text_off,
-			        errs ? (long long)(*errs)[p] : 0ll);
-		for (const psvr_signal_mate_note_t &t : notes) fprintf(dump_f, "N %lld %d %d %d %d %s\n", (long long)t.number, t.index, t.block, t.tid, t.pos, t.name);
-		dump_blob("text", text), dump_blob("side", side), dump_blob("left", left);
-		fflush(dump_f);
-		++dump_calls;
-	}
-	PosBackend()
-	{
-		if (const char *e = getenv("PSVR_CHECK_DUMP")) dump_prefix = e, dump_f = fopen((dump_prefix + ".calls").c_str(), "w");
-	}
-	~PosBackend() { if (dump_f) fclose(dump_f); }
-	int signal_create(const psvr_signal_opt_t *o)
-	{
-		const int rc = HostBackend::signal_create(o);
-		if (!rc && dump_f) {
-			const int32_t *v = (const int32_t *)o;
-			fprintf(dump_f, "O");
-			for (size_t k = 0; k < sizeof *o / 4; ++k) fprintf(dump_f, " %d", v[k]);
-			fprintf(dump_f, "\n");
-		}
-		return rc;
-	}
-
-	// psvr_signal_run's passes over a pair list: r1 / r2 the records, i1 / i2 what the table says about them
-	int pairs_pass(const std::vector<const uint8_t *> &r1, const std::vector<const uint8_t *> &r2, const std::vector<int64_t> &i1, const std::vector<int64_t> &i2, psvr_signal_info_t *info)
-	{
-		const FqGroup g;
-		const int64_t P = (int64_t)r1.size();
-		tab.assign((size_t)P, psvr_signal_pair_t());
-		text.clear(), side.clear();
-		int64_t first_err = -1, first_written = -1;
-		for (int64_t p = 0; p < P; ++p) {
-			psvr_signal_pair_t &t = tab[(size_t)p];
-			uint32_t note = 0;
-			t.rec1 = i1[(size_t)p], t.rec2 = i2[(size_t)p];
-			t.state = (uint8_t)sg_pair_size(g, opt, r1[(size_t)p], r2[(size_t)p], &t.bytes, &note);
-			t.note = (uint8_t)note, t.pad = 0;
-			if (t.state >= 3 && first_err < 0) first_err = p;
-			if ((t.state == 1 || t.state == 2) && first_written < 0) first_written = p;
-		}
-		const int64_t n_front = first_err >= 0 ? first_err : P;
-		int64_t stat_pair = -1;
-		if (!spent && first_written >= 0 && first_written < n_front) {
-			stat_pair = first_written, spent = true;
-			if (tab[(size_t)stat_pair].state == 1) tab[(size_t)stat_pair].bytes += sg_stat_bytes(g, opt);
-		}
-		int64_t off = 0;
-		info->written = info->declined = 0;
-		for (int64_t p = 0; p < P; ++p) {
-			if (p >= n_front) tab[(size_t)p].bytes = 0;
-			tab[(size_t)p].text_off = off, off += tab[(size_t)p].bytes;
-			if (p < n_front) info->written += tab[(size_t)p].state == 1, info->declined += tab[(size_t)p].state == 2;
-		}
-		text.assign((size_t)off, '\xEE');
-		for (int64_t p = 0; p < n_front; ++p) {
-			const psvr_signal_pair_t &t = tab[(size_t)p];
-			for (int k = 0; k < 2; ++k) {
-				int32_t ib, lb;
-				sg_collect_bins(k ? r2[(size_t)p] : r1[(size_t)p], &ib, &lb);
-				if (ib >= 0) isize_n[(size_t)ib]++;
-				if (lb >= 0) len_n[(size_t)lb]++;
-			}
-			if (t.state != 1) continue;
-			BeWrite w;
-			w.out = (uint8_t *)&text[0], w.pos = (uint64_t)t.text_off;
-			uint32_t note = 0;
-			if (sg_pair(g, opt, r1[(size_t)p], r2[(size_t)p], p == stat_pair, w, &note) != 1 || w.pos != (uint64_t)(t.text_off + t.bytes)) { err = "the passes disagree"; return 3; }
-		}
-		for (int64_t p = 0; p < P; ++p) {
-			psvr_signal_pair_t &t = tab[(size_t)p];
-			t.side_off = -1;
-			if (!(p == first_err || (p < n_front && (t.state == 2 || t.note)))) continue;
-			t.side_off = (int64_t)side.size();
-			for (int k = 0; k < 2; ++k) {
-				const uint8_t *r = k ? r2[(size_t)p] : r1[(size_t)p];
-				side.append((const char *)r, 4 + (size_t)bam_u32(r));
-			}
-		}
-		info->side_bytes = (int64_t)side.size(), info->pairs = P, info->first_error = first_err, info->text_bytes = off;
-		return 0;
-	}
-
-	int signal_run_pos(int64_t first, int finish, const psvr_signal_pos_opt_t *po, psvr_signal_info_t *info, psvr_signal_pos_info_t *pi)
-	{
-		if (failing("signal_run_pos")) return 3;
-		memset(info, 0, sizeof *info), memset(pi, 0, sizeof *pi);
-		info->first_error = -1, pi->mate_failed = mate_failed;
-		std::vector<int64_t> where;
-		std::vector<const uint8_t *> prim;
-		for (size_t i = (size_t)first; i < recs.size(); ++i) if (sg_primary(rec(i))) where.push_back((int64_t)i), prim.push_back(rec(i));
-		const SmHostBlock B = sm_host_block(prim, po && po->block_records ? po->block_records : kSmRecords, po && po->block_span ? po->block_span : kSmSpan, finish != 0);
-		if (!B.complete) return 0;
-		pi->complete = 1, pi->primaries = B.n;
-		tab.clear(), text.clear(), side.clear(), left.clear(), notes.clear();
-		if (B.n < 2) { pi->consumed = info->consumed = (int64_t)recs.size(); return 0; }
-		if (B.bad) { err = B.bad == 1 ? "positions decrease inside a block (is the input sorted by position?)" : "a position of the block overflows the host loop's position index"; return 7; }
-		std::vector<const uint8_t *> r1, r2;
-		std::vector<int64_t> i1, i2;
-		for (const auto &p : B.pairs) r1.push_back(prim[(size_t)p.first]), r2.push_back(prim[(size_t)p.second]), i1.push_back(where[(size_t)p.first]), i2.push_back(where[(size_t)p.second]);
-		if (int rc = pairs_pass(r1, r2, i1, i2, info)) return rc;
-		// the unmated records (into the left store) and the notes
-		for (int32_t i : B.left) {
-			left.append((const char *)prim[(size_t)i], 4 + (size_t)bam_u32(prim[(size_t)i]));
-			left_store.emplace_back((const char *)prim[(size_t)i], 4 + (size_t)bam_u32(prim[(size_t)i]));
-		}
-		left_ordered = false;
-		long long rank = 0;
-		for (int64_t i = 0; i < B.n; ++i) {
-			if (!B.fail[(size_t)i]) continue;
-			const long long turn = mate_failed + ++rank;
-			if (sm_note_slot(mate_failed, turn) < 0) continue;
-			psvr_signal_mate_note_t t;
-			memset(&t, 0, sizeof t);
-			const uint8_t *r = prim[(size_t)i];
-			t.number = turn, t.index = (int32_t)i, t.block = (int32_t)B.n, t.tid = bam_i32(r + 4), t.pos = bam_i32(r + 8);
-			strncpy(t.name, (const char *)r + kBamRecHead, 255);
-			notes.push_back(t);
-		}
-		mate_failed += B.fails;
-		pi->consumed = info->consumed = where[(size_t)B.n - 1] + 1;
-		pi->unmated = (int64_t)B.left.size(), pi->left_bytes = (int64_t)left.size(), pi->mate_failed = mate_failed, pi->notes = (int64_t)notes.size(), pi->replayed = B.replayed;
-		char head[256];
-		snprintf(head, sizeof head, "B %lld %lld %lld %lld %lld %lld %lld", (long long)pi->primaries, (long long)pi->consumed, (long long)pi->unmated, (long long)pi->left_bytes, (long long)pi->mate_failed,
-		         (long long)pi->notes, (long long)pi->replayed);
-		dump_call(head, *info, nullptr);
-		return 0;
-	}
-	int signal_mate_notes(psvr_signal_mate_note_t *t, int64_t cap)
-	{
-		if (failing("signal_mate_notes")) return 3;
-		if (cap < (int64_t)notes.size()) { err = "note overflow"; return 6; }
-		for (size_t i = 0; i < notes.size(); ++i) t[i] = notes[i];
-		return 0;
-	}
-	int signal_left(void *bytes, int64_t cap)
-	{
-		if (failing("signal_left")) return 3;
-		if (cap < (int64_t)left.size()) { err = "left overflow"; return 6; }
-		memcpy(bytes, left.data(), left.size());
-		return 0;
-	}
-	const uint8_t *lrec(size_t i) const { return (const uint8_t *)left_store[i].data(); }
-	int signal_run_left(int64_t first_pair, int64_t max_pairs, psvr_signal_info_t *info, psvr_signal_left_info_t *li)
-	{
-		if (failing("signal_run_left")) return 3;
-		memset(info, 0, sizeof *info), memset(li, 0, sizeof *li);
-		info->first_error = -1;
-		if (left_store.size() & 1) { err = "an odd number of records found no mate: the host loop ends there"; return 7; }
-		const FqGroup g;
-		if (!left_ordered) {
-			left_ord.resize(left_store.size());
-			for (size_t i = 0; i < left_ord.size(); ++i) left_ord[i] = i;
-			// (the device sorts by 8-byte chunks of the name and sm_left_tie; the order is the one this comparator gives)
-			std::stable_sort(left_ord.begin(), left_ord.end(), [&](size_t a, size_t b) {
-				const int c = strcmp((const char *)lrec(a) + kBamRecHead, (const char *)lrec(b) + kBamRecHead);
-				if (c) return c < 0;
-				return sm_left_tie(bam_u16(lrec(a) + 18)) < sm_left_tie(bam_u16(lrec(b) + 18));
-			});
-			left_pairs.clear(), left_errs.clear();
-			int64_t errs = 0;
-			for (const auto &ev : sm_phase2_events(left_ord.size(), [&](size_t a, size_t b) { return sg_same_name(g, lrec(left_ord[a]), lrec(left_ord[b])); })) {
-				if (!ev.second) { ++errs; continue; }
-				left_pairs.push_back({left_ord[ev.first], left_ord[ev.first + 1]}), left_errs.push_back(errs);
-			}
-			left_err_total = errs;
-			left_ordered = true;
-		}
-		const int64_t P = (int64_t)left_pairs.size();
-		if (first_pair < 0 || first_pair > P || max_pairs < 1) { err = "slice outside the pair list"; return 1; }
-		const int64_t cnt = std::min(max_pairs, P - first_pair);
-		li->records = (int64_t)left_store.size(), li->pairs = P, li->errors = left_err_total, li->first_pair = first_pair, li->n_pairs = cnt, li->more = first_pair + cnt < P;
-		std::vector<const uint8_t *> r1, r2;
-		std::vector<int64_t> i1, i2;
-		slice_errs.clear();
-		for (int64_t p = first_pair; p < first_pair + cnt; ++p) {
-			r1.push_back(lrec(left_pairs[(size_t)p].first)), r2.push_back(lrec(left_pairs[(size_t)p].second));
-			i1.push_back((int64_t)left_pairs[(size_t)p].first), i2.push_back((int64_t)left_pairs[(size_t)p].second), slice_errs.push_back(left_errs[(size_t)p]);
-		}
-		notes.clear(), left.clear();
-		if (int rc = pairs_pass(r1, r2, i1, i2, info)) return rc;
-		char head[256];
-		snprintf(head, sizeof head, "L %lld %lld %lld %lld %lld %lld", (long long)li->records, (long long)li->pairs, (long long)li->errors, (long long)li->first_pair, (long long)li->n_pairs, (long long)li->more);
-		dump_call(head, *info, &slice_errs);
-		return 0;
-	}
-	int signal_left_errors(int64_t *e, int64_t cap)
-	{
-		if (failing("signal_left_errors")) return 3;
-		if (cap < (int64_t)slice_errs.size()) { err = "error table overflow"; return 6; }
-		for (size_t i = 0; i < slice_errs.size(); ++i) e[i] = slice_errs[i];
-		return 0;
-	}
-};
+#include "signal_route_host.h"
 
 int main(int argc, char **argv)
 {
 	return signal_main(argc, argv, nullptr, [](SignalStep &S, long long *pairs_done) {
-		PosBackend be;
+		HostBackend be;
 		const int rc = signal_mate_route(be, S, pairs_done);
-		if (rc > 0) {                                            // (SignalStep::run would abort(): the code is what the test looks at)
-			fflush(S.out);
-			fprintf(stderr, "route returned state %d behind %lld pairs\n", rc, *pairs_done);
-			exit(30 + rc);
-		}
-		return rc;
+		return route_status(rc, *pairs_done, S.out);
 	});
 }
