@@ -410,17 +410,28 @@ int psvr_bgzf_compress(int device, const void *in, int64_t n_bytes, void *out, i
  * and in the encoder's host build (tests/tools/deflate_wave_check.cpp).  Any BGZF / gzip reader decodes them; they differ from zlib's.
  * n_bytes == 0: no members, PSVR_OK.  out_cap or member_cap too small: PSVR_ERR_OVERFLOW (*out_bytes and *n_members are still set when the
  * device ran).  Bytes of `out` behind *out_bytes are unspecified.  Device buffers and the call's stream (of the lowest priority) are kept
- * across calls; calls are serialised. */
+ * across calls; calls are serialised.
+ * psvr_bgzf_compress_members_effort is the same call with the encoder's effort, 0..3 (anything else: PSVR_ERR_ARG); psvr_bgzf_compress_members
+ * is that call at effort 0.  Effort 0 tries one hash-table candidate per position besides the distances 1 and 2 and takes every match it
+ * finds (greedy).  Efforts 1, 2 and 3 walk a hash chain of 4, 8 and 16 candidates and match lazily (a match gives way to a longer one at
+ * the next position), zlib's two means: smaller members for more time in the member kernel.  The chains live in device scratch (2 bytes per
+ * input byte) that only a call at effort > 0 allocates.  At every effort a member's bytes depend on its input bytes and the effort alone
+ * (the host build: tests/tools/deflate_effort_check.cpp), and every effort's members hold the same data. */
 int64_t psvr_bgzf_members_bound(int64_t n_bytes, int32_t member_bytes);
 int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int32_t member_bytes,
                                void *out, int64_t out_cap, int64_t *out_bytes,
                                int64_t *member_off, int64_t member_cap, int64_t *n_members);
+int psvr_bgzf_compress_members_effort(int device, const void *in, int64_t n_bytes, int32_t member_bytes,
+                                      void *out, int64_t out_cap, int64_t *out_bytes,
+                                      int64_t *member_off, int64_t member_cap, int64_t *n_members, int32_t effort);
 
 /* ---- A BGZF stream that lives on the device (the hand-over from psvr_bam_emit_* to the member compressor) ------------------------------
  * Joins the two sections above: a byte stream in HBM that is cut every member_bytes bytes (as in psvr_bgzf_compress_members: 256..0xff00,
  * 0 = 0xff00) and whose members the same encoder makes, on the same process-wide buffers and stream.  The contract: concatenate the members
  * every psvr_bgzf_stream_take of a stream returned, and the result is byte for byte what psvr_bgzf_compress_members returns for the
- * concatenation of everything appended, at the same member_bytes -- however appends and takes were interleaved.
+ * concatenation of everything appended, at the same member_bytes and effort -- however appends and takes were interleaved.
+ *   set_effort    the encoder's effort (0..3, as in psvr_bgzf_compress_members_effort; anything else: PSVR_ERR_ARG) of every take from the
+ *                 next one on; a new stream is at effort 0.  Members of takes at different efforts concatenate to a valid stream of the same data.
  *   append        n_bytes of host memory (the BAM header, records the host formatted) behind what is pending; the bytes are free again when
  *                 the call returns.
  *   append_emit   bytes[pair_off[first_pair], pair_off[first_pair + n_pairs]) of em's last run, device to device: one kernel launch that
@@ -446,6 +457,7 @@ int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int3
  * The EOF marker block is the caller's.  A stream has one owner at a time; its calls are serialised with psvr_bgzf_compress_members. */
 typedef struct psvr_bgzf_stream psvr_bgzf_stream_t;
 int     psvr_bgzf_stream_create(int device, int32_t member_bytes, psvr_bgzf_stream_t **out);
+int     psvr_bgzf_stream_set_effort(psvr_bgzf_stream_t *s, int32_t effort);
 int     psvr_bgzf_stream_append(psvr_bgzf_stream_t *s, const void *bytes, int64_t n_bytes);
 int     psvr_bgzf_stream_append_emit(psvr_bgzf_stream_t *s, const psvr_bam_emit_t *em, int64_t first_pair, int64_t n_pairs);
 int64_t psvr_bgzf_stream_pending(psvr_bgzf_stream_t *s);

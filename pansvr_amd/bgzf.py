@@ -47,9 +47,10 @@ def bgzf_decompress(data, device=0):
     return out[:total], offs, used
 
 
-def bgzf_compress(data, member_bytes=0xff00, device=0):
+def bgzf_compress(data, member_bytes=0xff00, device=0, effort=0):
     """`data` cut into members of member_bytes input bytes, each compressed by a wavefront of HIP device `device`:
-    (uint8 array of the members side by side, member offsets [n + 1])."""
+    (uint8 array of the members side by side, member offsets [n + 1]).  effort 0..3: 0 is the greedy encoder with one hash-table candidate
+    (psvr_bgzf_compress_members), 1 / 2 / 3 walk a hash chain of 4 / 8 / 16 candidates and match lazily (psvr_bgzf_compress_members_effort)."""
     buf = np.frombuffer(bytes(data) or b"\0", dtype=np.uint8)[:len(data)]
     L = lib()
     L.psvr_bgzf_members_bound.restype = C.c_int64
@@ -59,16 +60,17 @@ def bgzf_compress(data, member_bytes=0xff00, device=0):
     out = np.empty(max(cap, 1), dtype=np.uint8)
     offs = np.zeros(nm_cap + 1, dtype=np.int64)
     total, nm = C.c_int64(0), C.c_int64(0)
-    check(L.psvr_bgzf_compress_members(C.c_int(device), buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.c_int32(member_bytes), out.ctypes.data_as(C.c_void_p),
-                                       C.c_int64(cap), C.byref(total), offs.ctypes.data_as(C.c_void_p), C.c_int64(nm_cap), C.byref(nm)))
+    args = (C.c_int(device), buf.ctypes.data_as(C.c_void_p), C.c_int64(len(buf)), C.c_int32(member_bytes), out.ctypes.data_as(C.c_void_p), C.c_int64(cap), C.byref(total),
+            offs.ctypes.data_as(C.c_void_p), C.c_int64(nm_cap), C.byref(nm))
+    check(L.psvr_bgzf_compress_members(*args) if effort == 0 else L.psvr_bgzf_compress_members_effort(*args, C.c_int32(effort)))
     return out[:total.value], offs[:nm.value + 1]
 
 
 class BgzfStream:
     """One psvr_bgzf_stream_t: a BGZF byte stream in HBM, cut every member_bytes; the members of all takes, concatenated, are
-    bgzf_compress's for everything appended.  Single-owner."""
+    bgzf_compress's for everything appended at the same effort.  Single-owner."""
 
-    def __init__(self, member_bytes=0xff00, device=0):
+    def __init__(self, member_bytes=0xff00, device=0, effort=0):
         self.h = C.c_void_p()
         self.member_bytes = member_bytes or 0xff00
         L = lib()
@@ -76,6 +78,16 @@ class BgzfStream:
         L.psvr_bgzf_members_bound.restype = C.c_int64
         L.psvr_bgzf_stream_destroy.restype = None
         check(L.psvr_bgzf_stream_create(C.c_int(device), C.c_int32(member_bytes), C.byref(self.h)))
+        if effort:
+            try:
+                self.set_effort(effort)
+            except EngineError:
+                self.close()                                                   # (no stream is left behind by a constructor that raises)
+                raise
+
+    def set_effort(self, effort):
+        """the encoder's effort (0..3, as bgzf_compress's) of every take from the next one on"""
+        check(lib().psvr_bgzf_stream_set_effort(self.h, C.c_int32(effort)))
 
     def append(self, data):
         """bytes of the host behind what is pending"""

@@ -181,6 +181,8 @@ struct RunStats {
 	bool sort_fields = false;          // ... and with the five fields below behind them
 	const char *sorter = "host";       // --sort-device: where the main file's records were kept and sorted (device / host / device+host when the route was left) ...
 	long long sort_device_bytes = 0, sort_host_bytes = 0, sort_records = 0, sort_members = 0;   // ... record bytes that never left HBM / bytes appended from the host, records and members of the sorted file
+	bool effort_field = false;         // ... and with the field below behind them
+	int deflate_effort = 0;            // --deflate-effort: the wavefront BGZF encoder's effort on the routes that compress through it
 	// PSVR_CLI_TIMING: when each stage had each piece (ms from the first FASTQ byte), printed at the end
 	const bool timing = getenv("PSVR_CLI_TIMING") != nullptr;
 	struct Span { double a = 0, b = 0; };
@@ -208,7 +210,8 @@ struct RunStats {
 		fprintf(stderr, "\"dropped\":%lld,\"teardown_s\":%.4f,\"parser\":\"%s\",\"emitter\":\"%s\",", dropped, t_teardown, n_dev_pieces ? (n_host_pieces ? "device+host" : "device") : "host", n_emit_pieces ? (n_emit_host_pieces ? "device+host" : "device") : "host");
 		fprintf(stderr, "\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld%s", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs, stream_fields ? "," : "}\n");
 		if (stream_fields) fprintf(stderr, "\"streamer\":\"%s\",\"stream_device_bytes\":%lld,\"stream_host_bytes\":%lld,\"stream_members\":%lld%s", streamer, stream_device_bytes, stream_host_bytes, stream_members, sort_fields ? "," : "}\n");
-		if (stream_fields && sort_fields) fprintf(stderr, "\"sorter\":\"%s\",\"sort_device_bytes\":%lld,\"sort_host_bytes\":%lld,\"sort_records\":%lld,\"sort_members\":%lld}\n", sorter, sort_device_bytes, sort_host_bytes, sort_records, sort_members);
+		if (stream_fields && sort_fields) fprintf(stderr, "\"sorter\":\"%s\",\"sort_device_bytes\":%lld,\"sort_host_bytes\":%lld,\"sort_records\":%lld,\"sort_members\":%lld%s", sorter, sort_device_bytes, sort_host_bytes, sort_records, sort_members, effort_field ? "," : "}\n");
+		if (stream_fields && sort_fields && effort_field) fprintf(stderr, "\"deflate_effort\":%d}\n", deflate_effort);
 	}
 };
 

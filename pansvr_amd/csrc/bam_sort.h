@@ -92,8 +92,11 @@ template <class Backend> int sort_device_route(Backend &be, const std::string &i
 	return 0;
 }
 
-// what bam_sort_main's --sort-device and --nsort-device call: (in.bam, out.bam, by_name) -> sort_device_route's answer over the caller's backend
-typedef std::function<int(const std::string &, const std::string &, bool)> SortDeviceFn;
+// what bam_sort_main's --sort-device and --nsort-device call: (in.bam, out.bam, by_name, --deflate-effort) -> sort_device_route's answer over the
+// caller's backend, whose stream compresses at that effort
+typedef std::function<int(const std::string &, const std::string &, bool, int)> SortDeviceFn;
+// the compressor of --deflate-device at an effort of 0..3 (the CLI hands in adapters over psvr_bgzf_compress_members_effort)
+typedef BgzfMembersFn (*BgzfMembersAtFn)(int effort);
 
 // `panSVR sort -n` on the device: the names of R in one blob (each up to its first NUL inside the name field), flag & 0xc0 as the tie key,
 // ordered by psvr_sort_order_names: name_order's order.  false with the reason: the caller orders with name_order
@@ -127,12 +130,27 @@ inline bool name_order_device(const SortRecords &R, int device, std::vector<uint
 	"                                host thread and 1.188 s with --inflate-threads 16 on top (ahead: the ranges do not overlap); plain -n --deflate-device\n" \
 	"                                with its order from the GPU 2.079 s (DESIGN.md section 8 f3)"
 
-// deflate_fn: the compressor --deflate-device uses (the CLI hands in &psvr_bgzf_compress_members)
-inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullptr, SortDeviceFn sort_device_fn = nullptr)
+// what --deflate-effort's usage text says about its sizes and speed
+#define PSVR_DEFLATE_EFFORT_MEASURED \
+	"Measured on the 1.6 M records\n" \
+	"                                 of 1 M pairs (-t 16, three interleaved runs): the sorted file 118.5 MB at effort 0 (+22.9 %% on zlib's default\n" \
+	"                                 level, 96.4 MB), 99.8 MB at 1 (+3.5 %%), 97.6 MB at 2 (+1.2 %%), 96.3 MB at 3 (-0.1 %%); sort --sort-device's write\n" \
+	"                                 phase 0.16 s at effort 0 (the parent build: 0.16 s, unchanged), 0.24 / 0.33 / 0.49 s at 1 / 2 / 3, aln\n" \
+	"                                 --sort-device's sort part 0.16 s (parent 0.16) / 0.24-0.26 / 0.33 / 0.49 s: every effort stays ahead of the host\n" \
+	"                                 routes.  A call of 201 MB with its copies: 14.8 / 23.5 / 37.0 / 58.4 ms (parent 14.9), the member kernel alone\n" \
+	"                                 7.7 / 16.3 / 29.9 / 51.3 ms (parent 7.7) (DESIGN.md section 4 (6))"
+
+// --deflate-effort's argument: "0" .. "3" and nothing else; -1 for anything else (no argument, text, a number with a tail), which the commands refuse
+inline int parse_deflate_effort(const char *s) { return s && s[0] >= '0' && s[0] <= '3' && !s[1] ? s[0] - '0' : -1; }
+
+// deflate_fn: the compressor --deflate-device uses (the CLI hands in &psvr_bgzf_compress_members); deflate_at: the same per --deflate-effort
+// (null: the option is refused, this build has one effort)
+inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullptr, SortDeviceFn sort_device_fn = nullptr, BgzfMembersAtFn deflate_at = nullptr)
 {
 	bool by_name = false;
 	int threads = 4, inflate_device = -1, inflate_threads = 0;
-	bool bad_arg = false, deflate_device = false, sort_device = false, nsort_device = false;
+	bool bad_arg = false, deflate_device = false, sort_device = false, nsort_device = false, effort_given = false;
+	int effort = 0;
 	std::string out_fn, in_fn;
 	for (int i = 2; i < argc; ++i) {
 		if (!strcmp(argv[i], "-n")) by_name = true;
@@ -142,12 +160,13 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		else if (!strcmp(argv[i], "--inflate-device")) inflate_device = 0;
 		else if (!strcmp(argv[i], "--deflate-device")) deflate_device = true;
 		else if (!strcmp(argv[i], "--sort-device")) sort_device = deflate_device = true;
+		else if (!strcmp(argv[i], "--deflate-effort")) effort = parse_deflate_effort(i + 1 < argc ? argv[++i] : nullptr), effort_given = true;
 		else if (!strcmp(argv[i], "--inflate-threads") && i + 1 < argc) { inflate_threads = atoi(argv[++i]); bad_arg |= inflate_threads < 1; }
 		else in_fn = argv[i];
 	}
 	if (bad_arg) fprintf(stderr, "--inflate-threads wants a positive number\n");
 	if (in_fn.empty() || bad_arg) {
-		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device | --sort-device | --nsort-device] in.bam\n"
+		fprintf(stderr, "usage: panSVR sort [-n] [-t threads] [-o out.bam] [--inflate-device | --inflate-threads N] [--deflate-device | --sort-device | --nsort-device] [--deflate-effort N] in.bam\n"
 		                "         -n                     name order (the names as strcmp compares them, first read before second, ties in input order), no index;\n"
 		                "                                the order is computed on the GPU (device 0) when one is visible, on one host thread otherwise\n"
 		                "         --inflate-device       inflate the input's BGZF members on the GPU (device 0), a chunk of the file at a time\n"
@@ -155,8 +174,11 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		                "         --inflate-threads INT  inflate them with zlib on INT host threads (also what takes over when the device route fails)\n"
 		                "         --deflate-device       compress the output's BGZF members on the GPU (device 0), a wavefront per member of 0xff00 bytes, 1024\n"
 		                "                                members a call.  Measured on the 2 M records of 1 M pairs, -t 16: 2.24-2.28 s against 2.45-3.04 s by\n"
-		                "                                default (reading the input is most of both), the file 23 %% larger than zlib's default level makes it;\n"
+		                "                                default (reading the input is most of both), the file 23 %% larger than zlib's default level makes it (--deflate-effort);\n"
 		                "                                a call of 201 MB: 14.9 ms = 13.5 GB/s with its copies, zlib's default level on 16 threads 491 ms\n"
+		                "         --deflate-effort INT   0-3: how hard that encoder searches; with --deflate-device, --sort-device or --nsort-device only [0].\n"
+		                "                                0: one hash-table candidate per position and the distances 1 and 2, every match taken (greedy).  1 / 2 / 3: a\n"
+		                "                                hash chain of 4 / 8 / 16 candidates and lazy matching, zlib's means.  " PSVR_DEFLATE_EFFORT_MEASURED "\n"
 		                "         --sort-device          coordinate order only; implies --deflate-device.  The file's BGZF members are inflated on the GPU (device 0)\n"
 		                "                                into a record store in its memory, the records are found, ordered, gathered and compressed there: the files\n"
 		                "                                are those of --deflate-device, byte for byte.  Whatever the device route cannot do (no device, memory, a\n"
@@ -167,13 +189,15 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		                "                                route sorts the file.  Not with --sort-device.  " PSVR_NSORT_CMD_DEVICE_MEASURED "\n");
 		return 1;
 	}
+	if (effort_given && (effort < 0 || effort > 3)) { fprintf(stderr, "--deflate-effort wants 0 .. 3\n"); return 1; }
+	if (effort_given && (!deflate_device || !deflate_at)) { fprintf(stderr, "--deflate-effort cannot be given without --deflate-device, --sort-device or --nsort-device: it is the effort of the GPU's BGZF encoder (a wavefront per member), which only those routes use\n"); return 1; }
 	if (sort_device && nsort_device) { fprintf(stderr, "--nsort-device cannot be combined with --sort-device: a file has one order, name (--nsort-device) or coordinate (--sort-device)\n"); return 1; }
 	if (sort_device && by_name) { fprintf(stderr, "--sort-device cannot be combined with -n: name order is not built on the device by this option; --nsort-device is the name order's device route\n"); return 1; }
 	if (nsort_device) by_name = true;
 	if (out_fn.empty()) out_fn = in_fn + (by_name ? ".nsorted.bam" : ".sorted.bam");
 	if (threads < 1) threads = 1;
 	if (sort_device || nsort_device) {
-		const int rc = sort_device_fn ? sort_device_fn(in_fn, out_fn, nsort_device) : -1;
+		const int rc = sort_device_fn ? sort_device_fn(in_fn, out_fn, nsort_device, effort) : -1;
 		if (!sort_device_fn) fprintf(stderr, "[panSVR-amd] sort %s: this build has no device route: the file is sorted by the %s--deflate-device route\n", nsort_device ? "--nsort-device" : "--sort-device", nsort_device ? "-n " : "");
 		if (rc >= 0) return rc;
 	}
@@ -205,7 +229,7 @@ inline int bam_sort_main(int argc, char **argv, BgzfMembersFn deflate_fn = nullp
 		if (!on_device) name_order(R, ord);
 	}
 	else if (!coordinate_order(R, 0, ord, &on_device, &err)) { fprintf(stderr, "[panSVR-amd] sort: device order: %s\n", err.c_str()); return 2; }
-	if (!write_sorted_bam(out_fn, rd.header_text, rd.refs, R, ord, by_name, threads, &err, deflate_device ? deflate_fn : nullptr, 0)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
+	if (!write_sorted_bam(out_fn, rd.header_text, rd.refs, R, ord, by_name, threads, &err, deflate_device ? (deflate_at ? deflate_at(effort) : deflate_fn) : nullptr, 0)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
 	fprintf(stderr, "[panSVR-amd] sort: %zu records -> %s (%s order%s)\n", ord.size(), out_fn.c_str(), by_name ? "name" : "coordinate", on_device ? ", ordered on the device" : "");
 	return 0;
 }

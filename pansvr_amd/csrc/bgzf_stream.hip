@@ -114,6 +114,15 @@ extern "C" void psvr_bgzf_stream_destroy(psvr_bgzf_stream_t *s)
 	delete s;                                                // (its DevBufs free themselves)
 }
 
+extern "C" int psvr_bgzf_stream_set_effort(psvr_bgzf_stream_t *s, int32_t effort)
+{
+	if (!s || !dfw_effort_ok(effort)) return set_error(PSVR_ERR_ARG, "psvr_bgzf_stream_set_effort: %s", s ? "the effort is outside 0..3" : "null argument");
+	DfwCtx &c = dfw_ctx();
+	std::lock_guard<std::mutex> lk(c.mu);                    // (a take reads it under the same mutex)
+	s->effort = (int)effort;
+	return PSVR_OK;
+}
+
 extern "C" int psvr_bgzf_stream_append(psvr_bgzf_stream_t *s, const void *bytes, int64_t n_bytes)
 {
 	if (!s || n_bytes < 0 || (n_bytes > 0 && !bytes)) return set_error(PSVR_ERR_ARG, "psvr_bgzf_stream_append: bad argument");
@@ -192,7 +201,7 @@ extern "C" int psvr_bgzf_stream_take(psvr_bgzf_stream_t *s, int finish, void *ou
 	if (whole == 0) return PSVR_OK;
 	StreamDrain drain{c.stream};
 	DfwCall call;
-	if (int rc = dfw_members_queue(c, s->pend.as<uint8_t>(), whole, (uint32_t)mb, out, (long long)out_cap, &call)) return rc;
+	if (int rc = dfw_members_queue(c, s->pend.as<uint8_t>(), whole, (uint32_t)mb, s->effort, out, (long long)out_cap, &call)) return rc;
 	// behind the members: what is left, less than a member, to the front (whole >= mb > rest: the two ranges do not overlap), and its count.
 	// From the first of the two on the pending bytes change: a failure then leaves a stream whose bytes nobody may take for good ones
 	hipError_t e = rest ? hipMemcpyAsync(s->pend.p, s->pend.as<uint8_t>() + whole, (size_t)rest, hipMemcpyDeviceToDevice, c.stream) : hipSuccess;

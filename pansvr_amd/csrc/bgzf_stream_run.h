@@ -8,6 +8,7 @@
 struct psvr_bgzf_stream {
 	int device = 0;
 	uint32_t mb = 0;
+	int effort = 0;                                          // the encoder's effort of the next take (psvr_bgzf_stream_set_effort)
 	psvr::DevBuf pend, ctl;                                  // the pending bytes [0, count); {count, count, bad append} as long long
 	long long *h_ctl = nullptr;                              // page-locked: [0..2] read-back of ctl, [3] the count an upload sets
 	int cur = 0;                                             // which slot of ctl holds the count

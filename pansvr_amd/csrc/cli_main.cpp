@@ -51,6 +51,8 @@ struct Opt : aln::PipeOpt {
 	bool deflate_device = false;                 // the BAM files' BGZF members (the sorted file's too) compressed on the first device, a wavefront per member (psvr_bgzf_compress_members)
 	bool inflate_device = false;                 // BAM input: its BGZF members inflated on the first device (psvr_bgzf_decompress) ...
 	int inflate_threads = 0;                     // ... or with zlib on this many host threads (bam_reader.h's batched mode)
+	int deflate_effort = 0;                      // --deflate-effort: the wavefront encoder's effort, 0..3 (deflate_wave_device.h); wants one of the routes that compress through it
+	bool deflate_effort_given = false;
 	bool stream_device = false;                  // the main BAM file's stream gathered in HBM: records from the encoder to the member compressor device to device (implies emit_device and deflate_device)
 	bool sort = false;                           // --sort: the main file coordinate-sorted + its .bai (sorted_bam.h), ordered on the first device
 	bool bam_device = false;                     // a name-sorted *.bam read file: the signal step's device route hands windows of FASTQ text in HBM to the reader stage
@@ -123,8 +125,11 @@ static int usage()
 	        "                                 than zlib level 1's and 4.8 %% larger than the default level's on those records.  1 M pairs, -t 16:\n"
 	        "                                 `aln` 0.44 s against 1.05-1.12 s by default and 0.47 s with --bgzf-fast; `aln --sort` 1.03-1.17 s against\n"
 	        "                                 1.33-1.83 s (its sort part 0.65-0.74 s against 0.91-1.35 s), the sorted file 23 %% larger than the default\n"
-	        "                                 level's.  Whether the engine's launches queue behind the deflate calls (a stream of the lowest priority\n"
+	        "                                 level's (--deflate-effort closes that gap).  Whether the engine's launches queue behind the deflate calls (a stream of the lowest priority\n"
 	        "                                 beside the engine's) has not been looked at\n"
+	        "        --deflate-effort    INT  0-3: how hard that encoder searches; with --deflate-device, --stream-device or --sort-device only [0].\n"
+	        "                                 0: one hash-table candidate per position and the distances 1 and 2, every match taken (greedy).  1 / 2 / 3: a\n"
+	        "                                 hash chain of 4 / 8 / 16 candidates and lazy matching, zlib's means.  " PSVR_DEFLATE_EFFORT_MEASURED "\n"
 	        "        --inflate-device         a *.bam read file: inflate its BGZF members on the GPU (the first device; a wavefront per member,\n"
 	        "                                 a chunk of the file at a time, on a stream of its own; faster than the default reader, but it\n"
 	        "                                 does not win against --inflate-threads 16.  Whether the engine's launches queue behind the inflate\n"
@@ -361,11 +366,27 @@ struct EmitterAccess {
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
 };
+// --deflate-effort: the members call at one effort, in the shape the writers take their compressor in (BgzfMembersFn, bam_writer.h)
+template <int EFFORT> static int members_at_effort(int device, const void *in, int64_t n, int32_t mb, void *out, int64_t cap, int64_t *got, int64_t *off, int64_t off_cap, int64_t *nm)
+{
+	return psvr_bgzf_compress_members_effort(device, in, n, mb, out, cap, got, off, off_cap, nm, EFFORT);
+}
+static psvr::BgzfMembersFn members_fn(int effort)
+{
+	static const psvr::BgzfMembersFn at[4] = {&psvr_bgzf_compress_members, &members_at_effort<1>, &members_at_effort<2>, &members_at_effort<3>};
+	return at[effort];
+}
+// a device stream at the command's effort
+static int stream_create_at(int device, int effort, psvr_bgzf_stream_t **s)
+{
+	if (int rc = psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, s)) return rc;
+	return effort ? psvr_bgzf_stream_set_effort(*s, effort) : 0;
+}
 struct StreamBackend : EmitterAccess {
-	const int device;
+	const int device, effort;
 	psvr_bgzf_stream_t *s = nullptr;
-	StreamBackend(EngineDriver &d, int dev) : EmitterAccess(d), device(dev) {}
-	int create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
+	StreamBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), device(dev), effort(eff) {}
+	int create() { return stream_create_at(device, effort, &s); }
 	void destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
 	int append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
 	int append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
@@ -373,7 +394,7 @@ struct StreamBackend : EmitterAccess {
 	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
 	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *nm, int64_t *used) { return psvr_bgzf_stream_take(s, finish, out, cap, got, nullptr, 0, nm, used); }
 	int recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
-	void host_route(BgzfWriter &w) { w.set_device_members(device, &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks); }
+	void host_route(BgzfWriter &w) { w.set_device_members(device, members_fn(effort), psvr::kDeflateDeviceBlocks); }
 };
 struct StreamMainSink : aln::MainSink {
 	BgzfStreamSink<StreamBackend> &k;
@@ -389,10 +410,10 @@ struct StreamMainSink : aln::MainSink {
 // --sort-device: sort_store_sink.h's backend over psvr_bam_store_*, psvr_bgzf_stream_* and the pipeline slots' emitters, and the sink as the pipeline sees it
 // the store and stream calls themselves, shared with `panSVR sort --sort-device`
 struct StoreCalls {
-	const int device;
+	const int device, effort;
 	psvr_bam_store_t *store = nullptr;
 	psvr_bgzf_stream_t *s = nullptr;
-	explicit StoreCalls(int dev) : device(dev) {}
+	explicit StoreCalls(int dev, int eff = 0) : device(dev), effort(eff) {}
 	int store_create() { return psvr_bam_store_create(device, &store); }
 	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
 	int store_append(const void *p, int64_t n) { return psvr_bam_store_append(store, p, n); }
@@ -408,7 +429,7 @@ struct StoreCalls {
 	int store_meta(int64_t first, int64_t n, psvr_bam_rec_meta_t *m) { return psvr_bam_store_meta(store, first, n, m); }
 	int store_stream(int64_t first, int64_t n) { return psvr_bam_store_stream(store, s, first, n); }
 	int store_download(void *bytes, int64_t cap, int64_t *n) { return psvr_bam_store_download(store, bytes, cap, n); }
-	int stream_create() { return psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, &s); }
+	int stream_create() { return stream_create_at(device, effort, &s); }
 	void stream_destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
 	int stream_append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
 	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
@@ -418,12 +439,12 @@ struct StoreCalls {
 	}
 };
 struct SortBackend : EmitterAccess, StoreCalls {
-	SortBackend(EngineDriver &d, int dev) : EmitterAccess(d), StoreCalls(dev) {}
+	SortBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), StoreCalls(dev, eff) {}
 	int store_append_emit(int slot, int64_t first, int64_t n) { return psvr_bam_store_append_emit(store, drv.bem[slot], first, n); }
 };
 // `panSVR sort --sort-device` (bam_sort.h: sort_device_route): the same store and stream calls without an engine, the store filled from the file's own members
 struct SortCmdBackend : StoreCalls {
-	explicit SortCmdBackend(int dev) : StoreCalls(dev) {}
+	explicit SortCmdBackend(int dev, int eff = 0) : StoreCalls(dev, eff) {}
 	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
 	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
 	const char *last_error() { return psvr_last_error(); }
@@ -475,7 +496,11 @@ struct SortMainSink : aln::MainSink {
 // what an option combination is refused with (true: a message went out); sort_conflict: the first option on the line that --sort cannot go with
 static bool option_conflict(const Opt &o, const char *sort_conflict)
 {
-	if (o.sort_device && o.stream_device)
+	if (o.deflate_effort_given && (o.deflate_effort < 0 || o.deflate_effort > 3))
+		fprintf(stderr, "--deflate-effort wants 0 .. 3\n");
+	else if (o.deflate_effort_given && !o.deflate_device)
+		fprintf(stderr, "--deflate-effort cannot be given without --deflate-device, --stream-device or --sort-device: it is the effort of the GPU's BGZF encoder (a wavefront per member), which only those routes use\n");
+	else if (o.sort_device && o.stream_device)
 		fprintf(stderr, "--sort-device cannot be combined with --stream-device: the stream compresses the main file's records in input order as they leave the encoder, a sorted file needs all of them first\n");
 	else if (o.sort_device && sort_conflict)
 		fprintf(stderr, "--sort-device cannot be combined with %s: the sorted file is BAM, its members compressed on the GPU from records that stay in its memory\n", sort_conflict);
@@ -514,7 +539,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019}, {"mate-device", 0, 0, 1020}, {"block-records", 1, 0, 1021},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019}, {"mate-device", 0, 0, 1020}, {"block-records", 1, 0, 1021}, {"deflate-effort", 1, 0, 1022},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -556,6 +581,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1019: o.bam_device = true; break;
 		case 1020: o.mate_device = true; break;
 		case 1021: o.block_records = atoi(optarg); if (o.block_records < 2) { fprintf(stderr, "--block-records wants a number of at least 2\n"); return 1; } break;
+		case 1022: o.deflate_effort = psvr::parse_deflate_effort(optarg), o.deflate_effort_given = true; break;
 		case 1012: o.inflate_threads = atoi(optarg); if (o.inflate_threads < 1) { fprintf(stderr, "--inflate-threads wants a positive number\n"); return 1; } break;
 		case 'D': o.sig_all = true; break;
 		case 'U': o.sig_discard = true; break;
@@ -652,7 +678,7 @@ static int write_sorted_main(const Opt &o, const HeaderInfo &H, const std::vecto
 		        st->t_sort_order * 1e3);
 		std::vector<std::pair<std::string, int32_t>> refs;
 		for (const BamRef &r : bam_refs) refs.push_back({r.name, (int32_t)r.len});
-		if (!write_sorted_bam(o.out, H.text, refs, sorted, ord, false, o.thread_n, &err, o.deflate_device ? &psvr_bgzf_compress_members : nullptr, o.devices[0], psvr::kDeflateDeviceBlocks)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
+		if (!write_sorted_bam(o.out, H.text, refs, sorted, ord, false, o.thread_n, &err, o.deflate_device ? members_fn(o.deflate_effort) : nullptr, o.devices[0], psvr::kDeflateDeviceBlocks)) { fprintf(stderr, "%s\n", err.c_str()); return 2; }
 	} catch (const std::bad_alloc &) { fputs(aln::kSortNoMem, stderr); return 2; }
 	st->t_sort = walltime() - ts;
 	return 0;
@@ -667,7 +693,7 @@ static int aln_main(int argc, char **argv)
 	std::vector<BamRef> refs;
 	load_header(o, &H, &refs);
 	aln::RunStats st;
-	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam, st.stream_fields = st.sort_fields = true;
+	st.devices = (int)o.devices.size(), st.threads = o.thread_n, st.sam = o.sam, st.deflate_effort = o.deflate_effort, st.stream_fields = st.sort_fields = st.effort_field = true;
 	EngineDriver drv(o.devices);
 	fprintf(stderr, "Begin loading index @%s\n", o.index_dir.c_str());
 	drv.load_indexes(o, &st);
@@ -708,7 +734,7 @@ static int aln_main(int argc, char **argv)
 	std::unique_ptr<BgzfStreamSink<StreamBackend>> stream_sink;
 	std::unique_ptr<aln::MainSink> main_sink;
 	if (streaming) {
-		stream_backend.reset(new StreamBackend(drv, o.devices[0]));
+		stream_backend.reset(new StreamBackend(drv, o.devices[0], o.deflate_effort));
 		stream_sink.reset(new BgzfStreamSink<StreamBackend>(*stream_backend, getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
 		main_sink.reset(new StreamMainSink(*stream_sink));
 		if (!stream_sink->open(o.out.c_str(), H.text, refs, o.thread_n)) { fprintf(stderr, "fail to open output file\n"); abort(); }
@@ -718,7 +744,7 @@ static int aln_main(int argc, char **argv)
 	std::unique_ptr<SortBackend> sort_backend;
 	std::unique_ptr<SortStoreSink<SortBackend>> sort_sink;
 	if (sorting_device) {
-		sort_backend.reset(new SortBackend(drv, o.devices[0]));
+		sort_backend.reset(new SortBackend(drv, o.devices[0], o.deflate_effort));
 		sort_sink.reset(new SortStoreSink<SortBackend>(*sort_backend, [&](const SortRecords &R) { return write_sorted_main(o, H, refs, R, &st); },
 		                                               getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
 		main_sink.reset(new SortMainSink(*sort_sink));
@@ -727,8 +753,8 @@ static int aln_main(int argc, char **argv)
 	if ((!o.sort && !streaming && !fo.open(o.out, !o.sam, H, refs, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, refs, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	SortRecords sorted;                                  // --sort: the main file's records, kept until the input ends
 	if (o.bgzf_device && !o.sam) fo.bam.bgzf().set_device(o.devices[0]), fo_ori.bam.bgzf().set_device(o.devices[0]);
-	if (o.deflate_device && !streaming) fo.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
-	if (o.deflate_device) fo_ori.bam.bgzf().set_device_members(o.devices[0], &psvr_bgzf_compress_members, psvr::kDeflateDeviceBlocks);
+	if (o.deflate_device && !streaming) fo.bam.bgzf().set_device_members(o.devices[0], members_fn(o.deflate_effort), psvr::kDeflateDeviceBlocks);
+	if (o.deflate_device) fo_ori.bam.bgzf().set_device_members(o.devices[0], members_fn(o.deflate_effort), psvr::kDeflateDeviceBlocks);
 	FILE *frec = o.records.empty() ? nullptr : fopen(o.records.c_str(), "w");
 	fprintf(stderr, "Processing file: [%s].\n", o.reads.c_str());
 
@@ -786,10 +812,10 @@ int main(int argc, char **argv)
 			text_route_fn([](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done) { return psvr::signal_device_route(be, S, pairs_done); }),
 			text_route_fn([](SignalCmdBackend &be, psvr::SignalStep &S, long long *pairs_done) { return psvr::signal_mate_route(be, S, pairs_done); }));
 	if (argc >= 2 && !strcmp(argv[1], "sort"))
-		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name) {
-			SortCmdBackend be(0);
+		return psvr::bam_sort_main(argc, argv, &psvr_bgzf_compress_members, [](const std::string &in, const std::string &out, bool by_name, int effort) {
+			SortCmdBackend be(0, effort);
 			return psvr::sort_device_route(be, in, out, by_name);
-		});
+		}, &members_fn);
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
 	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         panSVR sort --sort-device [-t threads] [-o out.bam] in.bam      (the same files, the records inflated, kept, ordered and compressed in GPU memory)\n         panSVR sort --nsort-device [-t threads] [-o out.bam] in.bam     (name order by the same route: the file of sort -n --deflate-device, no index)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
 	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"

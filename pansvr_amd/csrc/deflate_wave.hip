@@ -13,13 +13,16 @@
 
 namespace psvr {
 
+// link: tok_stride half-words per member at efforts 1..3 (the chains of deflate_wave_device.h), not touched at effort 0
+template <int EFFORT>
 __global__ __launch_bounds__(64) void k_bgzf_deflate_wave(const uint8_t *__restrict__ in, long long n_bytes, uint32_t mb, uint8_t *slots, uint32_t slot, uint32_t *tok,
-                                                          uint32_t tok_stride, int32_t *len)
+                                                          uint32_t tok_stride, uint16_t *link, int32_t *len)
 {
 	__shared__ DfwLds lds;
 	const long long b = blockIdx.x, at = b * (long long)mb;
 	const uint32_t n = (uint32_t)(n_bytes - at < (long long)mb ? n_bytes - at : (long long)mb);
-	const uint32_t size = dfw_member<64>(in + at, n, slots + b * (long long)slot, tok + b * (long long)tok_stride, &lds, (int)threadIdx.x);
+	uint16_t *lk = EFFORT ? link + b * (long long)tok_stride : nullptr;
+	const uint32_t size = dfw_member_effort<64, EFFORT>(in + at, n, slots + b * (long long)slot, tok + b * (long long)tok_stride, lk, &lds, (int)threadIdx.x);
 	if (threadIdx.x == 0) len[b] = (int32_t)size;
 }
 // the members side by side: a workgroup per member, whole dwords once the destination is aligned
@@ -45,17 +48,18 @@ __global__ __launch_bounds__(256) void k_bgzf_pack_members(const uint8_t *__rest
 DfwCtx &dfw_ctx() { static DfwCtx c; return c; }
 
 bool dfw_member_bytes_ok(int32_t mb) { return mb == 0 || (mb >= 256 && mb <= (int32_t)kDfMaxIn); }
+bool dfw_effort_ok(int32_t effort) { return effort >= 0 && effort <= kDfwMaxEffort; }
 
 int dfw_bind(DfwCtx &c, int device)
 {
 	// (a device-resident stream may have work queued on the stream that a change of device is about to destroy: it is waited for first)
 	return c.bind(device, true, [&] {
 		if (c.stream) (void)hipStreamSynchronize(c.stream);
-		c.in.release(), c.slots.release(), c.tok.release(), c.len.release(), c.off.release(), c.tmp.release(), c.packed.release();
+		c.in.release(), c.slots.release(), c.tok.release(), c.link.release(), c.len.release(), c.off.release(), c.tmp.release(), c.packed.release();
 	});
 }
 
-int dfw_members_queue(DfwCtx &c, const uint8_t *d_in, long long n_bytes, uint32_t mb, void *out, long long out_cap, DfwCall *call)
+int dfw_members_queue(DfwCtx &c, const uint8_t *d_in, long long n_bytes, uint32_t mb, int effort, void *out, long long out_cap, DfwCall *call)
 {
 	const long long nm = (n_bytes + mb - 1) / mb;
 	const uint32_t slot = dfw_slot_bytes(mb), tok_stride = (mb + 1u + 63u) & ~63u;         // (words: a token per input byte at most, and the end of block)
@@ -63,14 +67,24 @@ int dfw_members_queue(DfwCtx &c, const uint8_t *d_in, long long n_bytes, uint32_
 	call->nm = nm, call->bound = bound;
 	PSVR_HIP(c.slots.ensure((size_t)nm * slot));
 	PSVR_HIP(c.tok.ensure((size_t)nm * tok_stride * 4));
+	if (effort > 0) PSVR_HIP(c.link.ensure((size_t)nm * tok_stride * 2));                  // (the chains: only a call that walks them pays for them)
 	PSVR_HIP(c.len.ensure((size_t)(nm + 1) * 4));
 	PSVR_HIP(c.off.ensure((size_t)(nm + 1) * 8));
 	PSVR_HIP(c.tmp.ensure(scan_tmp_bytes(1, nm + 1)));
 	PSVR_HIP(c.packed.ensure((size_t)bound));
 	c.h_off.assign((size_t)nm + 1, 0);
 	PSVR_HIP(hipMemsetAsync(c.len.as<int32_t>() + nm, 0, 4, c.stream));                     // (the scan runs over nm + 1 sizes: its last offset is the total)
-	hipLaunchKernelGGL(k_bgzf_deflate_wave, dim3((unsigned)nm), dim3(64), 0, c.stream, d_in, n_bytes, mb, c.slots.as<uint8_t>(), slot, c.tok.as<uint32_t>(), tok_stride,
-	                   c.len.as<int32_t>());
+	auto launch = [&](auto kernel) {
+		hipLaunchKernelGGL(kernel, dim3((unsigned)nm), dim3(64), 0, c.stream, d_in, n_bytes, mb, c.slots.as<uint8_t>(), slot, c.tok.as<uint32_t>(), tok_stride,
+		                   effort > 0 ? c.link.as<uint16_t>() : (uint16_t *)nullptr, c.len.as<int32_t>());
+	};
+	switch (effort) {
+	case 0: launch(k_bgzf_deflate_wave<0>); break;
+	case 1: launch(k_bgzf_deflate_wave<1>); break;
+	case 2: launch(k_bgzf_deflate_wave<2>); break;
+	case 3: launch(k_bgzf_deflate_wave<3>); break;
+	default: return set_error(PSVR_ERR_ARG, "BGZF members: effort %d is outside 0..%d", effort, kDfwMaxEffort);
+	}
 	PSVR_HIP(hipGetLastError());
 	ScanSet S = {};
 	S.cnt[0] = c.len.as<int32_t>(), S.out[0] = c.off.as<long long>(), S.stride[0] = 1, S.off[0] = 0, S.base[0] = 0;
@@ -112,6 +126,13 @@ extern "C" int64_t psvr_bgzf_members_bound(int64_t n_bytes, int32_t member_bytes
 extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_bytes, int32_t member_bytes, void *out, int64_t out_cap, int64_t *out_bytes,
                                           int64_t *member_off, int64_t member_cap, int64_t *n_members)
 {
+	return psvr_bgzf_compress_members_effort(device, in, n_bytes, member_bytes, out, out_cap, out_bytes, member_off, member_cap, n_members, 0);
+}
+
+extern "C" int psvr_bgzf_compress_members_effort(int device, const void *in, int64_t n_bytes, int32_t member_bytes, void *out, int64_t out_cap, int64_t *out_bytes,
+                                                 int64_t *member_off, int64_t member_cap, int64_t *n_members, int32_t effort)
+{
+	if (!dfw_effort_ok(effort)) return set_error(PSVR_ERR_ARG, "psvr_bgzf_compress_members: effort %d is outside 0..%d", (int)effort, kDfwMaxEffort);
 	if (n_bytes < 0 || (n_bytes > 0 && (!in || !out)) || !out_bytes || out_cap < 0 || !dfw_member_bytes_ok(member_bytes) || (member_off && member_cap < 0))
 		return set_error(PSVR_ERR_ARG, "psvr_bgzf_compress_members: bad argument");
 	*out_bytes = 0;
@@ -129,7 +150,7 @@ extern "C" int psvr_bgzf_compress_members(int device, const void *in, int64_t n_
 	StreamDrain drain{c.stream};
 	PSVR_HIP(hipMemcpyAsync(c.in.p, in, (size_t)n_bytes, hipMemcpyHostToDevice, c.stream));   // the upload is this entry point's; the rest is the shared scaffold
 	DfwCall call;
-	if (int rc = dfw_members_queue(c, c.in.as<uint8_t>(), (long long)n_bytes, mb, out, (long long)out_cap, &call)) return rc;
+	if (int rc = dfw_members_queue(c, c.in.as<uint8_t>(), (long long)n_bytes, mb, (int)effort, out, (long long)out_cap, &call)) return rc;
 	drain.armed = false;
 	return dfw_members_wait(c, call, (long long)out_cap, out_bytes, member_off, n_members, "psvr_bgzf_compress_members");
 }

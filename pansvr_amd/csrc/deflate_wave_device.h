@@ -15,6 +15,16 @@
 //     the ballot of "has a match": a match is taken and jumped over, a run of literals is skipped with one count-trailing-zeros.  Each
 //     token start then finds its index by a population count and writes its token to the member's scratch slice, counts its symbols by LDS
 //     atomics and enters its position into the table by an LDS max: the greatest position wins.
+//     Efforts 1, 2, 3 (dfw_member_effort; 0 is the rule above, unchanged) add zlib's two means to it, hash chains and lazy evaluation:
+//     * links: every position p with p + 4 <= n, covered by an earlier match or not, stores link[p] = the table entry it read (position + 1,
+//       0 = none): the state after all earlier groups, so positions of one group do not link to one another.  After the distances 1 and 2
+//       the candidates are c = head[h], link[c - 1], ... : 4, 8, 16 entries at most, until 0 or a distance above 32768; positions strictly
+//       decrease; an entry at distance 1 or 2 (tried already) is passed over and counts as one of the 4, 8, 16.  Longest wins, then nearest
+//       (the walk goes nearest first, the comparison is strict).  A link is read only for a position that entered the table, and such a
+//       position has written its own link: scratch that was never written is never read.
+//     * lazy: in the wave-uniform walk a match at `cur` whose successor in the same group has a strictly longer one goes out as a literal
+//       and the walk continues at cur + 1, where the same test applies; a group's last position has no look-ahead.  The demotions are a
+//       wave-uniform mask beside the token starts.
 //   2 code lengths: the symbols are ranked by (frequency, symbol) with the lanes, each counting the symbols in front of its own; Moffat's
 //     in-place algorithm and the 15-bit limit are deflate_device.h's (df_lengths_sorted: one lane, O(symbols)); canonical codes likewise.
 //   3 the sizes of the three block types follow from the frequencies alone, so the smallest is chosen BEFORE anything is emitted and BSIZE
@@ -24,7 +34,9 @@
 //     (at most 48), the lengths are prefix-summed across the wavefront, each lane ORs its bits into a zeroed LDS window at its offset, and
 //     the window's complete words leave as one coalesced dword store.  CRC32 (inflate_device.h's 64 slices) and ISIZE end the string.
 // Bounds: every load of input is inside in[0, n), every store inside slot[0, dfw_slot_bytes(n)) or tok[0, n + 1); every loop consumes input
-// positions or tokens or is bounded by a table size; nothing waits for another workgroup.
+// positions or tokens or is bounded by a table size; nothing waits for another workgroup.  link (efforts 1-3: n half-words per member): every
+// index is a position < n, so every store and every chain load lies inside link[0, n); a link is written by one lane and read by another
+// in a later group, so the group ends with the fence tok gets before phase 4 (inf_fence, then inf_sync).
 #pragma once
 #include <stdint.h>
 #include "deflate_device.h"
@@ -36,6 +48,9 @@ static const int kDfwHashBits = 12;
 static const uint32_t kDfwNear = 2;                  // the fixed distances tried besides the table's candidate
 static const uint32_t kDfwWindow = 128;              // words of the emission window: 64 tokens of 48 bits are 96, plus the carried word
 static const uint32_t kDfwTooFar = 4096;             // a 3-byte match farther back costs more than its literals (zlib's TOO_FAR)
+static const int kDfwMaxEffort = 3;
+// table candidates tried per position: one at effort 0, a chain of 4, 8, 16 at efforts 1, 2, 3
+PSVR_IF constexpr uint32_t dfw_depth(int effort) { return effort > 0 ? 2u << effort : 1u; }
 
 struct DfwLds {
 	union {
@@ -164,14 +179,17 @@ PSVR_IF void dfw_build_code(const uint32_t *f, int n, uint8_t *len, uint32_t *co
 	inf_sync();
 }
 
-// One member: in[0, n), 1 <= n <= 0xff00, into slot[0, dfw_slot_bytes(n)) (dword aligned); tok: n + 1 words of scratch.  Returns the member's size;
-// every lane returns the same.
-template <int NL>
-PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32_t *tok, DfwLds *t, int lane)
+// One member: in[0, n), 1 <= n <= 0xff00, into slot[0, dfw_slot_bytes(n)) (dword aligned); tok: n + 1 words of scratch; link: n half-words of
+// scratch when EFFORT > 0, not touched (and may be null) at effort 0.  Returns the member's size; every lane returns the same.
+template <int NL, int EFFORT>
+PSVR_IF uint32_t dfw_member_effort(const uint8_t *in, uint32_t n, uint8_t *slot, uint32_t *tok, uint16_t *link, DfwLds *t, int lane)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
 	static_assert(NL == 64, "a wavefront");
 #endif
+	static_assert(EFFORT >= 0 && EFFORT <= kDfwMaxEffort, "effort 0..3");
+	constexpr uint32_t depth = dfw_depth(EFFORT);
+	constexpr bool lazy = EFFORT > 0;
 	const uint32_t hmask = (1u << kDfwHashBits) - 1u;
 	auto ld32 = [&](uint32_t p) { uint32_t v; __builtin_memcpy(&v, in + p, 4); return v; };                   // p + 4 <= n
 	for (uint32_t i = (uint32_t)lane; i <= hmask; i += NL) t->z.head[i] = 0;
@@ -188,13 +206,23 @@ PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32
 				const uint32_t cur = ld32(p);
 				byte = cur & 0xffu;
 				h = ((cur & 0xffffffu) * 0x9E3779B1u >> (32 - kDfwHashBits)) & hmask;
+				uint32_t c = 0;
+				if (lazy) c = t->z.head[h], link[p] = (uint16_t)c;                 // the chain behind p: covered positions enter the table too
 				if (k >= carry) {
 					const uint32_t lim = n - p < 258u ? n - p : 258u;
-					const uint32_t c = t->z.head[h];
-					for (uint32_t j = 0; j <= kDfwNear; ++j) {
+					if (!lazy) c = t->z.head[h];
+					// the fixed distances, then the chain, nearest first: c > link[c - 1] > ..., `depth` entries at most
+					for (uint32_t j = 0; j < kDfwNear + depth; ++j) {
 						uint32_t d;
 						if (j < kDfwNear) { d = j + 1; if (d > p) continue; }
-						else { if (!c) continue; d = p + 1 - c; if (d > 32768u || d <= kDfwNear) continue; }
+						else if (!lazy) { if (!c) continue; d = p + 1 - c; if (d > 32768u || d <= kDfwNear) continue; }   // (effort 0 keeps the form its code was measured in)
+						else {
+							if (!c) break;
+							d = p + 1 - c;
+							if (d > 32768u) break;
+							c = j + 1 < kDfwNear + depth ? link[c - 1] : 0u;       // (entered the table, so it wrote its link: c - 1 < p)
+							if (d <= kDfwNear) continue;
+						}
 						const uint32_t cp = p - d;
 						if ((ld32(cp) ^ cur) & 0xffffffu) continue;
 						uint32_t l = 3;
@@ -212,14 +240,19 @@ PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32
 		}
 		inf_sync();
 		// the token starts of the group: wave-uniform, a step per match and per run of literals
-		uint64_t start = 0;
+		uint64_t start = 0, demoted = 0;                                       // (demoted: a match that goes out as a literal, the next position's is longer)
 		uint32_t cur = carry;
 		if (cur < cnt) {
 			const uint64_t mask = dfw_ballot_match(t->z.glen, cnt, lane);
 			const uint32_t own = dfw_own(t->z.glen, lane);
 			while (cur < cnt) {
 				const uint64_t rest = mask >> cur;
-				if (rest & 1u) { start |= 1ull << cur; cur += dfw_pick(t->z.glen, own, cur); }
+				if (rest & 1u) {
+					const uint32_t l = dfw_pick(t->z.glen, own, cur);
+					start |= 1ull << cur;
+					if (lazy && (rest & 2u) && dfw_pick(t->z.glen, own, cur + 1) > l) demoted |= 1ull << cur, cur += 1;
+					else cur += l;
+				}
 				else {
 					const uint32_t run = rest ? df_ctz64(rest) : cnt - cur;
 					start |= (run >= 64u ? ~0ull : (1ull << run) - 1ull) << cur;
@@ -234,7 +267,7 @@ PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32
 			if (!(start >> k & 1u)) continue;
 			const uint32_t at = nt + dfw_popc64(start & ((1ull << k) - 1ull));
 			const uint32_t l = t->z.glen[k];
-			if (l >= 3) {
+			if (l >= 3 && !(lazy && (demoted >> k & 1u))) {
 				const uint32_t d1 = t->z.gdist[k];
 				uint32_t s, d, eb, ev;
 				df_len_code(l, s, eb, ev);
@@ -248,6 +281,7 @@ PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32
 			}
 		}
 		nt += dfw_popc64(start);
+		if (lazy) inf_fence();                                                 // the links are read by other lanes, in later groups
 		inf_sync();
 	}
 	if (lane == 0) tok[nt] = 0x40000100u, t->freq[256] = 1;                    // end of block, a token like the others
@@ -358,6 +392,13 @@ PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32
 	o.bp += 64;
 	o.template flush<NL>(true, lane);
 	return o.bp >> 3;                                                          // (= size: the sizes of phase 3 are exact)
+}
+
+// effort 0: one table candidate, no chain, no look-ahead, no link scratch
+template <int NL>
+PSVR_IF uint32_t dfw_member(const uint8_t *in, uint32_t n, uint8_t *slot, uint32_t *tok, DfwLds *t, int lane)
+{
+	return dfw_member_effort<NL, 0>(in, n, slot, tok, nullptr, t, lane);
 }
 
 } // namespace psvr

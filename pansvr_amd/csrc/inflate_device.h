@@ -137,9 +137,11 @@ PSVR_IF void inf_crc_table(uint32_t *crc_tab, int lane)
 	}
 }
 // CRC32 of p[0, n) by the wavefront (shared with deflate_wave_device.h): lane k takes p[k * slice, (k + 1) * slice), the slices' CRCs are
-// moved to the end and added.  crc_tab: inf_crc_table's; red: 64 words.  Every lane returns the same value.
+// moved to the end and added.  crc_tab: inf_crc_table's; red: 64 words.  Every lane returns the same value.  Always inlined: with several
+// kernels of one file calling it (deflate_wave.hip has one per effort) the compiler otherwise keeps it out of line, a call and two registers
+// per kernel.
 template <int NL>
-PSVR_IF uint32_t inf_crc32(const uint8_t *p, uint32_t n, const uint32_t *crc_tab, uint32_t *red, int lane)
+__attribute__((always_inline)) PSVR_IF uint32_t inf_crc32(const uint8_t *p, uint32_t n, const uint32_t *crc_tab, uint32_t *red, int lane)
 {
 	inf_sync();
 	const uint32_t slice = (n + 63u) / 64u;

@@ -7,7 +7,14 @@ printed).
                                               what a writer should gather per call); and BgzfWriter
                                               (bam_writer.h, compiled here into a small timing program) on 1 and 16 threads at zlib level 1,
                                               zlib's default level and with compress_block_fast (16 threads)
-  python tools/deflate_bench.py kernel [MB]   two calls of the new entry point and nothing else: the run to put under `rocprofv3 --kernel-trace --stats`
+  python tools/deflate_bench.py kernel [MB] [--effort N]   two calls of the wavefront entry point (at effort N) and nothing else: the run to put
+                                              under `rocprofv3 --kernel-trace --stats`
+  python tools/deflate_bench.py effort [MB] [--effort 0,1,2,3] [--parent-lib PATH]
+                                              psvr_bgzf_compress_members_effort at 0xff00 bytes per member, time and output size per effort; with
+                                              --parent-lib also psvr_bgzf_compress_members of another build's libpsvr_engine.so (the parent commit's:
+                                              effort 0 must not pay for the feature).  Every arm is a process of its own (one warm-up call, three
+                                              timed ones); one process is discarded, then three rounds with the arms interleaved; median of the
+                                              processes' medians and the range of all calls
 Every line of results is also appended, as JSON, to the file named by --json."""
 import ctypes as C
 import json
@@ -76,6 +83,60 @@ def records(mb):
     return b"".join(rec)
 
 
+def effort_arm(data_fn, lib_path, effort):
+    """one process of `effort`: a warm-up call and three timed ones from page-locked memory; effort None: psvr_bgzf_compress_members of lib_path"""
+    data = open(data_fn, "rb").read()
+    n = len(data)
+    L = C.CDLL(lib_path)
+    L.psvr_bgzf_members_bound.restype = C.c_int64
+    L.psvr_host_alloc.restype = C.c_void_p
+    L.psvr_host_alloc.argtypes = [C.c_size_t]
+    L.psvr_last_error.restype = C.c_char_p
+    cap = L.psvr_bgzf_members_bound(C.c_int64(n), C.c_int32(0xff00))
+    pin_in, pin_out = L.psvr_host_alloc(n), L.psvr_host_alloc(cap)
+    assert pin_in and pin_out
+    C.memmove(pin_in, data, n)
+    got = C.c_int64(0)
+    args = (0, C.c_void_p(pin_in), C.c_int64(n), C.c_int32(0xff00), C.c_void_p(pin_out), C.c_int64(cap), C.byref(got), None, C.c_int64(0), None)
+    ts = []
+    for _ in range(4):
+        t0 = time.perf_counter()
+        rc = L.psvr_bgzf_compress_members(*args) if effort is None else L.psvr_bgzf_compress_members_effort(*args, C.c_int32(effort))
+        ts.append(time.perf_counter() - t0)
+        assert rc == 0, L.psvr_last_error()
+    import zlib
+    assert zlib.decompress(C.string_at(pin_out, 65536), 31) == data[:0xff00]
+    print(json.dumps({"calls_s": ts[1:], "out": got.value}))
+
+
+def effort_main(mb):
+    efforts = [int(e) for e in (arg_after("--effort") or "0,1,2,3").split(",")]
+    parent = arg_after("--parent-lib")
+    data = records(mb)
+    tmp = tempfile.mkdtemp(prefix="psvr_deflate_bench_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    data_fn = os.path.join(tmp, "in.bin")
+    open(data_fn, "wb").write(data)
+    own = os.path.join(ROOT, "pansvr_amd", "libpsvr_engine.so")
+    arms = ([("parent build", parent, None)] if parent else []) + [("effort %d" % e, own, e) for e in efforts]
+
+    def run(lib_path, effort):
+        cmd = [sys.executable, os.path.abspath(__file__), "effort-arm", data_fn, lib_path, "parent" if effort is None else str(effort)]
+        return json.loads(subprocess.check_output(cmd, timeout=600).decode().strip().split("\n")[-1])
+    run(own, efforts[0])                                                       # the discarded process
+    calls, meds, size = {a[0]: [] for a in arms}, {a[0]: [] for a in arms}, {}
+    for _ in range(3):
+        for name, lib_path, effort in arms:
+            r = run(lib_path, effort)
+            calls[name] += r["calls_s"]
+            meds[name].append(sorted(r["calls_s"])[1])
+            size[name] = r["out"]
+    for name, _, _ in arms:
+        m = sorted(meds[name])[1]
+        report({"level": "call", "arm": name, "input_mb": len(data) / 1e6, "output_mb": size[name] / 1e6, "ratio": round(len(data) / size[name], 3), "process_medians_s": [round(t, 4) for t in meds[name]],
+                "median_s": round(m, 4), "min_s": round(min(calls[name]), 4), "max_s": round(max(calls[name]), 4), "gb_per_s": round(len(data) / m / 1e9, 3)})
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 def main(mb, kernel_only):
     data = records(mb)
     n = len(data)
@@ -101,6 +162,10 @@ def main(mb, kernel_only):
         check(L.psvr_bgzf_compress_members(0, C.c_void_p(pin_in), C.c_int64(n), C.c_int32(member_bytes), C.c_void_p(pin_out), C.c_int64(cap), C.byref(got),
                                            offs.ctypes.data_as(C.c_void_p), C.c_int64(len(offs) - 1), C.byref(nm)))
         return time.perf_counter() - t0, got.value
+    if kernel_only and arg_after("--effort"):
+        def wave(member_bytes, n=n):  # noqa: F811  (the same call at an effort)
+            check(L.psvr_bgzf_compress_members_effort(0, C.c_void_p(pin_in), C.c_int64(n), C.c_int32(member_bytes), C.c_void_p(pin_out), C.c_int64(cap), C.byref(got),
+                                                      offs.ctypes.data_as(C.c_void_p), C.c_int64(len(offs) - 1), C.byref(nm), C.c_int32(int(arg_after("--effort")))))
     wave(0xff00)
     if kernel_only:
         wave(0xff00)
@@ -140,6 +205,13 @@ def main(mb, kernel_only):
 
 if __name__ == "__main__":
     mode = sys.argv[1] if len(sys.argv) > 1 else "call"
-    num = [a for a in sys.argv[2:] if a.isdigit()]
+    if mode == "effort-arm":
+        effort_arm(sys.argv[2], sys.argv[3], None if sys.argv[4] == "parent" else int(sys.argv[4]))
+        sys.exit(0)
+    skip = {i + 1 for i, a in enumerate(sys.argv) if a in ("--effort", "--json", "--parent-lib")}
+    num = [a for i, a in enumerate(sys.argv) if i >= 2 and i not in skip and a.isdigit()]
+    if mode == "effort":
+        effort_main(int(num[0]) if num else 192)
+        sys.exit(0)
     assert lib().psvr_device_count() > 0, "no HIP device: nothing is measured without one"
     main(int(num[0]) if num else 192, mode == "kernel")

@@ -8,7 +8,10 @@ the child.  The four routes' files are compared byte for byte.  Median and range
 chain finder's counters on that file go to OUT.  With --kernel-stats DIR, afterwards one `rocprofv3 --kernel-trace --stats` run each of
 `sort --sort-device` with segments of 16 KiB and of 64 KiB (runs of their own: tracing slows the host), their kernel tables copied to
 DIR/kernel_stats_seg<bytes>.csv.
-    python tools/sort_cmd_device_e2e.py OUT.json [--pairs 1000000] [--reps 3] [--kernel-stats DIR]"""
+With --efforts 1,2,3 the same interleaved repetitions also run `sort --sort-device --deflate-effort N` for every N (this build's) and, when
+parent_bin/ is there, the parent commit's `sort --sort-device` (what this build's effort 0 is held to); every route's file size is recorded
+beside the size of the file plain `sort` writes with zlib's default level (one run, not timed).
+    python tools/sort_cmd_device_e2e.py OUT.json [--pairs 1000000] [--reps 3] [--kernel-stats DIR] [--efforts 1,2,3]"""
 import argparse
 import glob
 import hashlib
@@ -50,12 +53,17 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--kernel-stats")
+    ap.add_argument("--efforts", default="")
     a = ap.parse_args()
     import bench_data
     old = PARENT if os.path.exists(PARENT) else NEW
     t = str(a.threads)
     routes = (("deflate_device", old, ["--deflate-device"]), ("inflate_device", old, ["--inflate-device", "--deflate-device"]),
               ("inflate_threads", old, ["--inflate-threads", t, "--deflate-device"]), ("sort_device", NEW, ["--sort-device"]))
+    efforts = [int(e) for e in a.efforts.split(",") if e]
+    if efforts and old == PARENT:
+        routes += (("sort_device_parent", PARENT, ["--sort-device"]),)
+    routes += tuple(("sort_device_effort%d" % e, NEW, ["--sort-device", "--deflate-effort", str(e)]) for e in efforts)
     tmp = tempfile.mkdtemp(prefix="psvr_sortcmd_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
     try:
         anc = bench_data.make_anchors(10000, seed=11)
@@ -82,14 +90,23 @@ def main():
                         os.remove(fn)
                 wall, err = run([exe, "sort", "-t", t] + flags + ["-o", out, inp])
                 res["runs"][name].append(round(wall, 4))
-                digest.setdefault(name, (sha(out), sha(out + ".bai")))
-                if name == "sort_device":
+                if "effort" not in name:
+                    digest.setdefault(name, (sha(out), sha(out + ".bai")))
+                res.setdefault("file_bytes", {})[name] = os.path.getsize(out)
+                if name.startswith("sort_device"):
                     if "failed" in err or "records kept on the device" not in err:
                         raise SystemExit("--sort-device left the device route:\n" + err[-2000:])
+                    if name != "sort_device":
+                        res.setdefault(name + "_phases", []).append({k: float(v) for k, v in re.findall(r"(append|order|write) ([0-9.]+) s", err)})
+                        print(rep, name, "%.3f" % wall, flush=True)
+                        continue
                     last_err = err
                     res.setdefault("sort_device_phases", []).append({k: float(v) for k, v in re.findall(r"(append|order|write) ([0-9.]+) s", err)})
                 print(rep, name, "%.3f" % wall, flush=True)
         res["same_files"] = len(set(digest.values())) == 1
+        if efforts:
+            run([NEW, "sort", "-t", t, "-o", out, inp])
+            res["file_bytes"]["zlib_default_level"] = os.path.getsize(out)
         res["summary"] = {k: {"median": statistics.median(v), "min": min(v), "max": max(v)} for k, v in res["runs"].items()}
         line = [l for l in last_err.split("\n") if "sort --sort-device:" in l][-1]
         res["sort_device_line"] = line.split("sort --sort-device: ", 1)[1]
