@@ -389,6 +389,34 @@ int  psvr_bam_emit_engine(psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fa
 int  psvr_bam_emit_download(const psvr_bam_emit_t *em, void *bytes, int64_t cap, int64_t *pair_off, uint8_t *pair_state);
 void psvr_bam_emit_destroy(psvr_bam_emit_t *em);
 
+/* ---- The second BAM file's records encoded on the device (the -p file: pairs neither aligner placed well) -----------------------------------
+ * Replaces, for the same caller, the record formatting of single_end_handler::output_ori_bam (src/PanSVgenerateVCF/read_realignment.cpp:
+ * 656-717, reached from :776-797): the ORIGINAL alignment of both reads of a pair, rebuilt from the FLAG_ / CIGAR_ / MATE_ / TAG_ sections of
+ * their FASTQ comments.  The calls run on a psvr_bam_emit_t and leave their records in it as psvr_bam_emit_results / _engine do: an emitter
+ * holds the records of its last run, whichever file they are for, and psvr_bam_emit_download, psvr_bgzf_stream_append_emit and
+ * psvr_bam_store_append_emit work on it unchanged.  Per pair p of the run, one of three states:
+ *   0  nothing to write: max_score > min_filter_score or an original chr_id of -1 (decided before any text is read); a comment without
+ *      one of its sections (FLAG_, CIGAR_ and its closing '_', six bytes behind that, TAG_); a pair that is `proper` and whose reads show
+ *      neither a clip nor an insertion of 25 bases (max1 / max2 == -1; == -2 with the CIGAR text's end clips; else the candidate's I
+ *      operators or an empty CIGAR); every read skipped (an original chr_id outside the header)
+ *   1  bytes[pair_off[p], pair_off[p + 1]) hold the records of its reads that are not skipped, mate 0 first -- exactly what the command's
+ *      host formatter writes for the pair: flag and mapq from FLAG_ (flag | 4 without a CIGAR), the CIGAR words parsed from the text
+ *      (operators up to 'B'), mate fields from MATE_, SEQ / QUAL reversed under flag 0x10, the aux fields of the TAG_ text (i in the
+ *      smallest type; A, Z, H copied), MS:i:max_score last
+ *   2  declined, no bytes: the caller formats the pair on the host.  A name of length 0 or over 254, a quality line that is not as long as
+ *      the sequence line, an empty or "*" sequence line, a tab or NUL in a comment, a FLAG_ / MATE_ number that is not 1-9 plain digits, a
+ *      CIGAR text with an operator without digits, an unknown letter, a '-', trailing digits or more than 65535 operators, an aux field
+ *      shorter than 5 bytes or without its two colons, an aux type other than i A Z H (f and B are declined), an i value that is not a
+ *      '-'-optional run of 1-9 digits, records of more than 2^31 - 1 bytes -- or a result index that leaves the arrays it was given
+ *      (cand_off + max1 / max2, cigar_off + n_cigar).  Whatever the results and the text hold, nothing outside the given arrays and the
+ *      window is read.
+ * Arguments, preconditions, error codes and the one-device rule are those of psvr_bam_emit_results / psvr_bam_emit_engine; the gate's
+ * min_filter_score comes from the caller, or from the parameters eng was created with.  Both run the same kernels. */
+int  psvr_bam_emit_ori_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs,
+                               const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs, const psvr_cand_t *cands, int64_t n_cands,
+                               const uint32_t *cigar, int64_t n_cigar, int32_t min_filter_score, psvr_bam_emit_info_t *info);
+int  psvr_bam_emit_ori_engine(psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fastq_t *fq, psvr_bam_emit_info_t *info);  /* min_filter_score: eng's parameters */
+
 /* ---- BGZF members on the device (the BAM output's compression) --------------------------------------------------------------
  * Replaces, for the drop-in command's BAM output, htslib's bgzf_compress (htslib bgzf.c: zlib deflate of 0xff00-byte blocks on the host,
  * reached from the reference's sam_write1 calls, read_realignment.cpp:166-176 -> bam_file.c).  `in` (host memory, n_bytes) is cut into

@@ -17,6 +17,7 @@
 //   int emit_encode(int slot, const FastqBatch &, bool not_ori) / int emit_download(int slot, long long P, EmitView *)
 // --stream-device does not add to that list: who writes the main file then (MainSink below) reaches the pipeline as an optional last
 // constructor argument, and it is the sink, not the driver, that is asked for the offsets and states of a slot's emitted piece.
+// --ori-device does not either: who encodes the second file's records (OriSource below) is the constructor's argument behind the sink.
 #pragma once
 #include <stdio.h>
 #include <stdlib.h>
@@ -58,6 +59,7 @@ struct PipeOpt {
 	                                       // reference-sized batches do not fill a four-stage pipeline, forty pieces do
 	bool parse_device = false;             // FASTQ input: every window parsed on the first device, the bases handed to the engine device to device
 	bool emit_device = false;              // ... and the main BAM file's records encoded there; implies parse_device
+	bool ori_device = false;               // ... and the second file's records; implies emit_device.  A piece both encoders took whole is resident: its results and text stay in HBM
 };
 
 // one output file: SAM text (-S) or BAM (default, like the reference's init_run)
@@ -115,6 +117,8 @@ struct Job {
 	FastqBatch fb;
 	int slot = 0;                      // (the driver keeps what its device routes need per slot)
 	bool emitted = false;              // --emit-device: this piece's main records were encoded on the device
+	bool ori_emitted = false;          // --ori-device: ... and the second file's
+	bool resident = false;             // ... and neither encoder declined a pair: the piece's results were not downloaded, its window text may not be here
 	std::vector<uint8_t> from_dev;     // --stream-device, per chunk: its main records stay in the slot's emitter (mb[ci] is empty) ...
 	const int64_t *dev_off = nullptr;  // ... at [dev_off[p0], dev_off[p1]) of its bytes
 	std::vector<Block> blk;
@@ -158,6 +162,19 @@ struct MainSink {
 	virtual const char *option() const { return "--stream-device"; }         // the option that put the sink there (--sort-device has one too), for messages
 };
 
+// --ori-device: who encodes the second file's records of a slot's piece (cli_main.cpp has the product's: a second emitter per slot over
+// psvr_bam_emit_ori_engine; tests/tools/aln_ori_pipeline_check.cpp has one over the host build of the rules).  The engine stage calls encode
+// right after the driver's emit_encode, before the engine gets its next piece, and decides there whether the piece is resident; the
+// formatter calls download.  Every int is 0 or an error whose text last_error() gives.
+struct OriSource {
+	virtual ~OriSource() {}
+	virtual int encode(int slot, const FastqBatch &fb, long long *declined) = 0;   // *declined: pairs of the piece in state 2
+	virtual long long main_declined(int slot) = 0;                                  // ... and of the slot's last main-file encode (the driver's emit_encode)
+	virtual int download(int slot, long long P, EmitView *v) = 0;                   // bytes, off and state of the slot's encoded piece, in host memory
+	virtual int fetch_text(FastqBatch &fb) = 0;                                     // the window text of a piece that is not resident (fb.text_pending bytes), into fb.text
+	virtual const char *last_error() = 0;
+};
+
 // every timer and counter of the `wall:` line and of e2e_json, by the stage that writes it
 struct RunStats {
 	int devices = 1, threads = 1;      // the command: what surrounds the pipeline
@@ -183,6 +200,10 @@ struct RunStats {
 	long long sort_device_bytes = 0, sort_host_bytes = 0, sort_records = 0, sort_members = 0;   // ... record bytes that never left HBM / bytes appended from the host, records and members of the sorted file
 	bool effort_field = false;         // ... and with the field below behind them
 	int deflate_effort = 0;            // --deflate-effort: the wavefront BGZF encoder's effort on the routes that compress through it
+	bool ori_fields = false;           // --ori-device was given: ... and with the six fields below behind it
+	long long n_ori_pieces = 0, n_ori_host_pieces = 0;   // pieces whose second-file records came from the device / from the host formatter
+	long long ori_device_pairs = 0, ori_declined_pairs = 0, ori_spliced_pairs = 0;   // as the three emit_ counters, for the second file
+	long long resident_pieces = 0, text_d2h_bytes = 0;   // pieces whose results and text never came to the host; window text fetched from the device
 	// PSVR_CLI_TIMING: when each stage had each piece (ms from the first FASTQ byte), printed at the end
 	const bool timing = getenv("PSVR_CLI_TIMING") != nullptr;
 	struct Span { double a = 0, b = 0; };
@@ -211,7 +232,10 @@ struct RunStats {
 		fprintf(stderr, "\"emit_device_pairs\":%lld,\"emit_declined_pairs\":%lld,\"emit_spliced_pairs\":%lld%s", emit_device_pairs, emit_declined_pairs, emit_spliced_pairs, stream_fields ? "," : "}\n");
 		if (stream_fields) fprintf(stderr, "\"streamer\":\"%s\",\"stream_device_bytes\":%lld,\"stream_host_bytes\":%lld,\"stream_members\":%lld%s", streamer, stream_device_bytes, stream_host_bytes, stream_members, sort_fields ? "," : "}\n");
 		if (stream_fields && sort_fields) fprintf(stderr, "\"sorter\":\"%s\",\"sort_device_bytes\":%lld,\"sort_host_bytes\":%lld,\"sort_records\":%lld,\"sort_members\":%lld%s", sorter, sort_device_bytes, sort_host_bytes, sort_records, sort_members, effort_field ? "," : "}\n");
-		if (stream_fields && sort_fields && effort_field) fprintf(stderr, "\"deflate_effort\":%d}\n", deflate_effort);
+		if (stream_fields && sort_fields && effort_field) fprintf(stderr, "\"deflate_effort\":%d%s", deflate_effort, ori_fields ? "," : "}\n");
+		if (stream_fields && sort_fields && effort_field && ori_fields)
+			fprintf(stderr, "\"ori_emitter\":\"%s\",\"ori_device_pairs\":%lld,\"ori_declined_pairs\":%lld,\"ori_spliced_pairs\":%lld,\"resident_pieces\":%lld,\"text_d2h_bytes\":%lld}\n",
+			        n_ori_pieces ? (n_ori_host_pieces ? "device+host" : "device") : "host", ori_device_pairs, ori_declined_pairs, ori_spliced_pairs, resident_pieces, text_d2h_bytes);
 	}
 };
 
@@ -224,21 +248,23 @@ template <class Driver> struct AlnPipeline {
 	OutFile &fo, &fo_ori;
 	std::function<bool(const uint8_t *, size_t)> keep_main;   // --sort: takes the main file's records (they are kept until the input ends) instead of `fo`; false: malformed
 	MainSink *sink;                    // --stream-device: writes the main file instead of `fo` (null: none)
+	OriSource *ori;                    // --ori-device: encodes the second file's records (null: the host formatter does)
 	FILE *frec;                        // --records
 	RunStats &st;
 	const int D;
 	SlotRing ring;
-	DeviceRoute parse_route, emit_route;
+	DeviceRoute parse_route, emit_route, ori_route;
 	int64_t pos[3] = {0, 0, 0};        // where the next piece starts in the three draw streams
 	std::vector<int> rcs;              // per device: what its thread's last driver call answered ...
 	std::vector<std::string> errs;     // ... and the driver's text for it
 	int block_id = 0;
 
 	AlnPipeline(const PipeOpt &opt, Driver &d, FastqReader &r, psvr_aln_params_t &p, SamEmitter &e, OutFile &main, OutFile &ori, std::function<bool(const uint8_t *, size_t)> keep, FILE *rec, RunStats &stats, bool device_routes,
-	            MainSink *main_sink = nullptr)
-	    : o(opt), drv(d), fq(r), par(p), em(e), fo(main), fo_ori(ori), keep_main(std::move(keep)), sink(main_sink), frec(rec), st(stats), D((int)opt.devices.size()), ring(D),
+	            MainSink *main_sink = nullptr, OriSource *ori_source = nullptr)
+	    : o(opt), drv(d), fq(r), par(p), em(e), fo(main), fo_ori(ori), keep_main(std::move(keep)), sink(main_sink), ori(ori_source), frec(rec), st(stats), D((int)opt.devices.size()), ring(D),
 	      parse_route(opt.parse_device && device_routes, "[panSVR-amd] FASTQ parse on the device failed (%s): parsing on the host threads from here on\n"),
 	      emit_route(opt.emit_device && device_routes, "[panSVR-amd] BAM records on the device failed (%s): formatting on the host threads from here on\n"),
+	      ori_route(opt.ori_device && device_routes && ori_source, "[panSVR-amd] ori BAM records on the device failed (%s): formatting the second file on the host threads from here on\n"),
 	      rcs((size_t)D, 0), errs((size_t)D) {}
 
 	// reader, formatter and writer on a thread of their own (thread_pool() is per calling thread), the engine stage on this one
@@ -342,9 +368,26 @@ template <class Driver> struct AlnPipeline {
 			if (rc) emit_route.fail(rc, drv.last_error());
 			else J.emitted = true;
 		}
+		// --ori-device: the second file's records the same way.  When both encoders ran and neither declined a pair (and --records is off),
+		// nothing on the host will look at the piece's results or text: the piece is resident, its results are not downloaded and its window
+		// text, where the reader left it on the device, is not fetched.  The decision is made here because the engine's results go with its
+		// next run.  Any other piece takes the usual path in full.
+		J.ori_emitted = J.resident = false;
+		long long ori_declined = 0;
+		if (ori_route.on && J.fb.dev) {
+			const int rc = ori->encode(J.slot, J.fb, &ori_declined);
+			if (rc) ori_route.fail(rc, ori->last_error());
+			else J.ori_emitted = true;
+		}
+		const bool full = frec != nullptr;                      // the parity tests read the fixed-size ABI records
+		J.resident = J.emitted && J.ori_emitted && !full && ori_declined == 0 && ori->main_declined(J.slot) == 0;
+		if (J.fb.text_pending && !J.resident) {
+			if (ori->fetch_text(J.fb)) { fprintf(stderr, "[panSVR-amd] window text: %s\n", ori->last_error()); abort(); }
+		}
+		st.text_d2h_bytes += J.fb.text_fetched;                  // (what the reader fetched with the piece, or the fetch above)
 		if (D > 1) exchange_draw_order();
 		if (drv.stream_end(D - 1, pos)) die("engine");
-		const bool full = frec != nullptr;                      // the parity tests read the fixed-size ABI records
+		if (J.resident) { ++st.resident_pieces; return; }
 		each_device([&](int d) {
 			long long bytes = 0;
 			const int rc = drv.download(d, J.blk[(size_t)d], full, &bytes);
@@ -430,9 +473,17 @@ template <class Driver> struct AlnPipeline {
 			const int rc = streamed ? sink->piece_view(J.slot, P, &dev) : drv.emit_download(J.slot, P, &dev);
 			if (rc) { emit_route.fail(rc, streamed ? sink->last_error() : drv.last_error()); J.emitted = false, dev = EmitView(); }
 		}
+		// --ori-device: the second file's chunks by the same rule, decided on their own; its bytes are downloaded and go through fo_ori
+		EmitView odev;
+		if (J.ori_emitted) {
+			const int rc = ori->download(J.slot, P, &odev);
+			if (rc) { ori_route.fail(rc, ori->last_error()); J.ori_emitted = false, odev = EmitView(); }
+		}
+		if (J.resident && !(J.emitted && J.ori_emitted)) { fprintf(stderr, "[panSVR-amd] the records of a piece whose results stayed on the device cannot be fetched: the run ends here\n"); abort(); }
+		if (ori) ++(J.ori_emitted ? st.n_ori_pieces : st.n_ori_host_pieces);
 		J.from_dev.assign((size_t)nchunk, 0), J.dev_off = dev.off;
 		++(J.emitted ? st.n_emit_pieces : st.n_emit_host_pieces);
-		std::atomic<long long> next(0), n_dev_pairs(0), n_declined(0), n_spliced(0);
+		std::atomic<long long> next(0), n_dev_pairs(0), n_declined(0), n_spliced(0), o_dev_pairs(0), o_declined(0), o_spliced(0);
 		auto work = [&]() {
 			for (long long ci = next++; ci < nchunk; ci = next++) {
 				const long long p0 = ci * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
@@ -445,16 +496,26 @@ template <class Driver> struct AlnPipeline {
 					else if (!dev.bytes) J.from_dev[(size_t)ci] = 1, n_spliced += p1 - p0;
 					else mb[(size_t)ci].insert(mb[(size_t)ci].end(), dev.bytes + dev.off[p0], dev.bytes + dev.off[p1]), n_spliced += p1 - p0;
 				}
+				bool host_ori = !odev.state;
+				if (odev.state) {
+					long long nd = 0;
+					for (long long p = p0; p < p1; ++p) nd += odev.state[p] == 2;
+					o_declined += nd, o_dev_pairs += (p1 - p0) - nd;
+					if (nd) host_ori = true;
+					else ob[(size_t)ci].insert(ob[(size_t)ci].end(), odev.bytes + odev.off[p0], odev.bytes + odev.off[p1]), o_spliced += p1 - p0;
+				}
+				if (!host_main && !host_ori) continue;
 				size_t bi = 0;
 				for (long long p = p0; p < p1; ++p) {
 					while (p >= J.blk[bi].hi) ++bi;
 					if (host_main) em.main_pair(J.fb, J.blk[bi].V, p, mb[(size_t)ci]);
-					em.ori_pair(J.fb, J.blk[bi].V, p, ob[(size_t)ci]);
+					if (host_ori) em.ori_pair(J.fb, J.blk[bi].V, p, ob[(size_t)ci]);
 				}
 			}
 		};
 		thread_pool().run((int)(o.thread_n < nchunk ? o.thread_n : nchunk), [&](int) { work(); });
 		st.emit_device_pairs += n_dev_pairs, st.emit_declined_pairs += n_declined, st.emit_spliced_pairs += n_spliced;
+		st.ori_device_pairs += o_dev_pairs, st.ori_declined_pairs += o_declined, st.ori_spliced_pairs += o_spliced;
 	}
 	// --stream-device: the chunks in order, adjacent device chunks joined into one range of the slot's emitter
 	void write_to_sink(Job &J)

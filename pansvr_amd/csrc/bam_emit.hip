@@ -7,10 +7,14 @@
 // records, their scan is pair_off, the write pass walks the same function with a sink that stores.  Bounds: be_plan_read checks every
 // index a result holds before it is followed, so only the given arrays, the window's text (lines between two stored starts) and the
 // index's string table are read; a pair writes bytes[pair_off[p], pair_off[p + 1]) and nothing else, because both passes walk be_record.
+// psvr_bam_emit_ori_* are the same launch order over the second file's rules (bam_ori_device.h, held to SamEmitter::ori_pair): k_bo_size and
+// k_bo_write walk bo_pair, which reads the pair's two comments, the results' pair record and -- for the `proper` rule -- one candidate's
+// CIGAR words after the same index check.  An emitter holds the records of its last run, whichever file they are for.
 #include <hip/hip_runtime.h>
 #include "../../include/psvr_engine.h"
 #include "common.h"
 #include "bam_emit_device.h"
+#include "bam_ori_device.h"
 #include "bam_emit_hooks.h"
 #include "bam_emit_run.h"
 #include "fastq_parsed.h"
@@ -55,10 +59,51 @@ __global__ __launch_bounds__(256) void k_be_write(BeInput in, int64_t P, const l
 	be_pair(g, in, p, w, &nr);
 }
 
+// the same two passes by the second file's rules (bam_ori_device.h): same launch shape, same outputs
+__global__ __launch_bounds__(256) void k_bo_size(BoInput in, int64_t P, int32_t *cnt, uint8_t *state, unsigned long long *counters)
+{
+	__shared__ unsigned int sum[3];
+	if (threadIdx.x < 3) sum[threadIdx.x] = 0;
+	__syncthreads();
+	const int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) / kFqGroup;
+	if (p < P) {
+		FqGroup g;
+		g.lane = threadIdx.x & (kFqGroup - 1), g.shift = threadIdx.x & 63 & ~(kFqGroup - 1);
+		int32_t nb, nr;
+		const int st = bo_pair_size(g, in, p, &nb, &nr);
+		if (g.lane == 0) {
+			cnt[p] = nb, state[p] = (uint8_t)st;
+			if (nr) atomicAdd(&sum[0], (unsigned int)nr);
+			if (st) atomicAdd(&sum[st], 1u);
+		}
+	}
+	__syncthreads();
+	if (threadIdx.x < 3 && sum[threadIdx.x]) atomicAdd(&counters[threadIdx.x], (unsigned long long)sum[threadIdx.x]);
+}
+__global__ __launch_bounds__(256) void k_bo_write(BoInput in, int64_t P, const long long *pair_off, const uint8_t *state, uint8_t *bytes)
+{
+	const int64_t p = ((int64_t)blockIdx.x * 256 + threadIdx.x) / kFqGroup;
+	if (p >= P || state[p] != 1) return;
+	FqGroup g;
+	g.lane = threadIdx.x & (kFqGroup - 1), g.shift = threadIdx.x & 63 & ~(kFqGroup - 1);
+	BeWrite w;
+	w.out = bytes, w.pos = (uint64_t)pair_off[p];
+	int32_t nr;
+	bo_pair(g, in, p, w, &nr);
+}
+
 static inline unsigned be_grid(int64_t n) { return (unsigned)((n + 255) / 256); }
 
-// both emit calls end here: `in` holds device pointers only
-static int be_run(psvr_bam_emit *em, const BeInput &in, int64_t P, psvr_bam_emit_info_t *info)
+// the kernels of a set of rules, chosen by the type of their input
+struct BeKernels {
+	static void size(const BeInput &in, int64_t P, int32_t *cnt, uint8_t *state, unsigned long long *counters, hipStream_t st) { hipLaunchKernelGGL(k_be_size, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, cnt, state, counters); }
+	static void size(const BoInput &in, int64_t P, int32_t *cnt, uint8_t *state, unsigned long long *counters, hipStream_t st) { hipLaunchKernelGGL(k_bo_size, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, cnt, state, counters); }
+	static void write(const BeInput &in, int64_t P, const long long *pair_off, const uint8_t *state, uint8_t *bytes, hipStream_t st) { hipLaunchKernelGGL(k_be_write, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, pair_off, state, bytes); }
+	static void write(const BoInput &in, int64_t P, const long long *pair_off, const uint8_t *state, uint8_t *bytes, hipStream_t st) { hipLaunchKernelGGL(k_bo_write, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, pair_off, state, bytes); }
+};
+
+// every emit call ends here: `in` (BeInput: the main file's rules, BoInput: the second file's) holds device pointers only
+template <class In> static int be_run(psvr_bam_emit *em, const In &in, int64_t P, psvr_bam_emit_info_t *info)
 {
 	em->valid = false;
 	if (em->cnt.ensure((size_t)(P + 1) * 4) || em->pair_off.ensure((size_t)(P + 1) * 8) || em->state.ensure((size_t)P + 1) || em->tmp.ensure(scan_tmp_bytes(1, P + 1)) ||
@@ -70,7 +115,7 @@ static int be_run(psvr_bam_emit *em, const BeInput &in, int64_t P, psvr_bam_emit
 	StreamDrain drain{st};
 	PSVR_HIP(hipMemsetAsync(em->counters.p, 0, 3 * 8, st));
 	PSVR_HIP(hipMemsetAsync(em->cnt.as<int32_t>() + P, 0, 4, st));                             // the scan's last entry: its offset is the total
-	if (P) hipLaunchKernelGGL(k_be_size, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, em->cnt.as<int32_t>(), em->state.as<uint8_t>(), em->counters.as<unsigned long long>());
+	if (P) BeKernels::size(in, P, em->cnt.as<int32_t>(), em->state.as<uint8_t>(), em->counters.as<unsigned long long>(), st);
 	ScanSet S = {};
 	S.cnt[0] = em->cnt.as<int32_t>(), S.out[0] = em->pair_off.as<long long>(), S.stride[0] = 1;
 	scan_launch(S, 1, P + 1, em->tmp.as<long long>(), st);
@@ -83,7 +128,7 @@ static int be_run(psvr_bam_emit *em, const BeInput &in, int64_t P, psvr_bam_emit
 		(void)hipGetLastError();
 		return set_error(PSVR_ERR_NOMEM, "psvr_bam_emit: device allocation failed for %lld bytes of records", (long long)total);
 	}
-	if (P && total) hipLaunchKernelGGL(k_be_write, dim3(be_grid(P * kFqGroup)), dim3(256), 0, st, in, P, (const long long *)em->pair_off.p, (const uint8_t *)em->state.p, em->bytes.as<uint8_t>());
+	if (P && total) BeKernels::write(in, P, (const long long *)em->pair_off.p, (const uint8_t *)em->state.p, em->bytes.as<uint8_t>(), st);
 	PSVR_HIP(hipGetLastError());
 	drain.armed = false;
 	PSVR_HIP(hipStreamSynchronize(st));
@@ -132,20 +177,21 @@ extern "C" void psvr_bam_emit_destroy(psvr_bam_emit_t *em)
 	delete em;                                               // (its DevBufs free themselves)
 }
 
-extern "C" int psvr_bam_emit_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs, const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs,
-                                     const psvr_cand_t *cands, int64_t n_cands, const uint32_t *cigar, int64_t n_cigar, int32_t flags, psvr_bam_emit_info_t *info)
+// the caller's compact results checked against the window and uploaded into the emitter's buffers (`who`: the call's name in messages)
+struct BeResultsDev { const psvr_read_hdr_t *hdr; const psvr_pair_result_t *pairs; const psvr_cand_t *cands; const uint32_t *cig; };
+static int be_upload_results(const char *who, psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs, const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs,
+                             const psvr_cand_t *cands, int64_t n_cands, const uint32_t *cigar, int64_t n_cigar, BeResultsDev *r)
 {
-	if (psvr_device_count() <= 0) return be_no_device();
 	if (!em || !fq || first_pair < 0 || n_pairs < 0 || n_cands < 0 || n_cigar < 0 || (n_pairs && (!hdr || !pairs)) || (n_cands && !cands) || (n_cigar && !cigar))
-		return set_error(PSVR_ERR_ARG, "psvr_bam_emit_results: bad argument");
+		return set_error(PSVR_ERR_ARG, "%s: bad argument", who);
 	if (!fq->valid || first_pair + n_pairs > fq->last.n_pairs)
-		return set_error(PSVR_ERR_ARG, "psvr_bam_emit_results: pairs [%lld, %lld) are not in the parsed window (%lld pairs)", (long long)first_pair, (long long)(first_pair + n_pairs), fq->valid ? (long long)fq->last.n_pairs : 0ll);
-	if (fq->device != em->device) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_results: the text was parsed on device %d, the emitter's index is on device %d", fq->device, em->device);
+		return set_error(PSVR_ERR_ARG, "%s: pairs [%lld, %lld) are not in the parsed window (%lld pairs)", who, (long long)first_pair, (long long)(first_pair + n_pairs), fq->valid ? (long long)fq->last.n_pairs : 0ll);
+	if (fq->device != em->device) return set_error(PSVR_ERR_ARG, "%s: the text was parsed on device %d, the emitter's index is on device %d", who, fq->device, em->device);
 	PSVR_HIP(hipSetDevice(em->device));
 	const size_t nh = (size_t)(2 * n_pairs) * sizeof(psvr_read_hdr_t), np = (size_t)n_pairs * sizeof(psvr_pair_result_t), nc = (size_t)n_cands * sizeof(psvr_cand_t), nw = (size_t)n_cigar * 4;
 	if (em->hdr.ensure(nh) || em->pairs.ensure(np) || em->cands.ensure(nc) || em->cig.ensure(nw)) {
 		(void)hipGetLastError();
-		return set_error(PSVR_ERR_NOMEM, "psvr_bam_emit_results: device allocation failed for the results of %lld pairs", (long long)n_pairs);
+		return set_error(PSVR_ERR_NOMEM, "%s: device allocation failed for the results of %lld pairs", who, (long long)n_pairs);
 	}
 	{
 		StreamDrain drain{em->stream};
@@ -154,28 +200,79 @@ extern "C" int psvr_bam_emit_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq
 		if (nc) PSVR_HIP(hipMemcpyAsync(em->cands.p, cands, nc, hipMemcpyHostToDevice, em->stream));
 		if (nw) PSVR_HIP(hipMemcpyAsync(em->cig.p, cigar, nw, hipMemcpyHostToDevice, em->stream));
 	}                                                        // (drained: the caller's arrays are free whatever happens next)
+	r->hdr = em->hdr.as<psvr_read_hdr_t>(), r->pairs = em->pairs.as<psvr_pair_result_t>(), r->cands = em->cands.as<psvr_cand_t>(), r->cig = em->cig.as<uint32_t>();
+	return PSVR_OK;
+}
+
+extern "C" int psvr_bam_emit_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs, const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs,
+                                     const psvr_cand_t *cands, int64_t n_cands, const uint32_t *cigar, int64_t n_cigar, int32_t flags, psvr_bam_emit_info_t *info)
+{
+	if (psvr_device_count() <= 0) return be_no_device();
+	BeResultsDev r;
+	const int rc = be_upload_results("psvr_bam_emit_results", em, fq, first_pair, n_pairs, hdr, pairs, cands, n_cands, cigar, n_cigar, &r);
+	if (rc) return rc;
 	BeInput in;
 	be_window(fq, first_pair, flags, em->T, &in);
-	in.hdr = em->hdr.as<psvr_read_hdr_t>(), in.pairs = em->pairs.as<psvr_pair_result_t>(), in.cands = em->cands.as<psvr_cand_t>(), in.n_cands = n_cands;
-	in.cig = em->cig.as<uint32_t>(), in.n_cig = n_cigar;
+	in.hdr = r.hdr, in.pairs = r.pairs, in.cands = r.cands, in.n_cands = n_cands, in.cig = r.cig, in.n_cig = n_cigar;
 	return be_run(em, in, n_pairs, info);
+}
+
+// an engine's last results in HBM, checked against the window they came from (`who`: the call's name in messages)
+static int be_engine_results(const char *who, psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fastq_t *fq, EngineEmitView *v)
+{
+	if (!em || !eng || !fq) return set_error(PSVR_ERR_ARG, "%s: null argument", who);
+	engine_emit_view(eng, v);
+	if (!v->fq) return set_error(PSVR_ERR_ARG, "%s: the engine's last upload did not come from a psvr_fastq_t (psvr_engine_upload_fastq), the text of its reads is not on the device", who);
+	if (v->fq != fq) return set_error(PSVR_ERR_ARG, "%s: the engine's last upload came from another psvr_fastq_t than the one given", who);
+	if (!fq->valid || v->generation != fq->generation) return set_error(PSVR_ERR_ARG, "%s: the psvr_fastq_t has been parsed into since the engine's upload, the window of its reads is gone", who);
+	if (v->device != em->device || fq->device != em->device)
+		return set_error(PSVR_ERR_ARG, "%s: the engine runs on device %d, the text was parsed on device %d, the emitter's index is on device %d", who, v->device, fq->device, em->device);
+	if (v->n_pairs > 0 && !v->ran) return set_error(PSVR_ERR_ARG, "%s: the engine has not run the batch it was given (psvr_engine_run)", who);
+	PSVR_HIP(hipSetDevice(em->device));
+	return PSVR_OK;
 }
 
 extern "C" int psvr_bam_emit_engine(psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fastq_t *fq, int32_t flags, psvr_bam_emit_info_t *info)
 {
 	if (psvr_device_count() <= 0) return be_no_device();
-	if (!em || !eng || !fq) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: null argument");
 	EngineEmitView v;
-	engine_emit_view(eng, &v);
-	if (!v.fq) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: the engine's last upload did not come from a psvr_fastq_t (psvr_engine_upload_fastq), the text of its reads is not on the device");
-	if (v.fq != fq) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: the engine's last upload came from another psvr_fastq_t than the one given");
-	if (!fq->valid || v.generation != fq->generation) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: the psvr_fastq_t has been parsed into since the engine's upload, the window of its reads is gone");
-	if (v.device != em->device || fq->device != em->device)
-		return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: the engine runs on device %d, the text was parsed on device %d, the emitter's index is on device %d", v.device, fq->device, em->device);
-	if (v.n_pairs > 0 && !v.ran) return set_error(PSVR_ERR_ARG, "psvr_bam_emit_engine: the engine has not run the batch it was given (psvr_engine_run)");
-	PSVR_HIP(hipSetDevice(em->device));
+	const int rc = be_engine_results("psvr_bam_emit_engine", em, eng, fq, &v);
+	if (rc) return rc;
 	BeInput in;
 	be_window(fq, v.first_pair, flags, em->T, &in);
+	in.hdr = v.hdr, in.pairs = v.pairs, in.cands = v.cands, in.n_cands = v.n_cands, in.cig = v.cig, in.n_cig = v.n_cig;
+	return be_run(em, in, v.n_pairs, info);
+}
+
+// ---- the second file's records: the same calls over bam_ori_device.h's rules --------------------------------------------------------------
+static void bo_window(const psvr_fastq *fq, int64_t first_pair, int32_t min_filter_score, const BeTables &T, BoInput *in)
+{
+	memset(in, 0, sizeof *in);
+	in->text = fq->text.as<char>(), in->line_start = fq->line_start.as<uint64_t>(), in->name_end = fq->name_end.as<uint16_t>(), in->ori = fq->ori.as<psvr_ori_t>();
+	in->first_pair = first_pair, in->min_filter_score = min_filter_score, in->n_header = T.n_header;
+}
+
+extern "C" int psvr_bam_emit_ori_results(psvr_bam_emit_t *em, const psvr_fastq_t *fq, int64_t first_pair, int64_t n_pairs, const psvr_read_hdr_t *hdr, const psvr_pair_result_t *pairs,
+                                         const psvr_cand_t *cands, int64_t n_cands, const uint32_t *cigar, int64_t n_cigar, int32_t min_filter_score, psvr_bam_emit_info_t *info)
+{
+	if (psvr_device_count() <= 0) return be_no_device();
+	BeResultsDev r;
+	const int rc = be_upload_results("psvr_bam_emit_ori_results", em, fq, first_pair, n_pairs, hdr, pairs, cands, n_cands, cigar, n_cigar, &r);
+	if (rc) return rc;
+	BoInput in;
+	bo_window(fq, first_pair, min_filter_score, em->T, &in);
+	in.hdr = r.hdr, in.pairs = r.pairs, in.cands = r.cands, in.n_cands = n_cands, in.cig = r.cig, in.n_cig = n_cigar;
+	return be_run(em, in, n_pairs, info);
+}
+
+extern "C" int psvr_bam_emit_ori_engine(psvr_bam_emit_t *em, psvr_engine_t *eng, const psvr_fastq_t *fq, psvr_bam_emit_info_t *info)
+{
+	if (psvr_device_count() <= 0) return be_no_device();
+	EngineEmitView v;
+	const int rc = be_engine_results("psvr_bam_emit_ori_engine", em, eng, fq, &v);
+	if (rc) return rc;
+	BoInput in;
+	bo_window(fq, v.first_pair, v.min_filter_score, em->T, &in);
 	in.hdr = v.hdr, in.pairs = v.pairs, in.cands = v.cands, in.n_cands = v.n_cands, in.cig = v.cig, in.n_cig = v.n_cig;
 	return be_run(em, in, v.n_pairs, info);
 }

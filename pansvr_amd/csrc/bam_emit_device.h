@@ -264,6 +264,28 @@ template <class S> PSVR_FQ void be_anchor(const FqGroup &g, S &o, const BeTables
 	be_copy(g, o, T.text + T.off[slot], T.off[slot + 1] - T.off[slot]);
 }
 
+// SEQ: two 4-bit codes per byte, the odd tail's low nibble 0; QUAL: phred values (no_qual: 0xff, a quality line that is "*"); the reverse
+// strand through getReverseStr_char / getReverseStr_qual_char (whose loop bound swaps the middle pair of an even-length read back).  Shared
+// with the second file's records (bam_ori_device.h).
+template <class S> PSVR_FQ void be_seq_qual(const FqGroup &g, S &body, const char *st, const char *qt, uint32_t n, bool rev, bool no_qual)
+{
+	const uint32_t nb = (n + 1) / 2;
+	if (S::writes) {
+		for (uint32_t j = g.lane; j < nb; j += FqGroup::width) {
+			const uint32_t i = 2 * j;
+			const uint32_t hi = rev ? be_rc_code((uint8_t)st[n - 1 - i]) : be_code((uint8_t)st[i]);
+			const uint32_t lo = i + 1 < n ? (rev ? be_rc_code((uint8_t)st[n - 2 - i]) : be_code((uint8_t)st[i + 1])) : 0u;
+			body.put(j, (uint8_t)(hi << 4 | lo));
+		}
+		const bool even = !(n & 1) && n >= 2;
+		for (uint32_t j = g.lane; j < n; j += FqGroup::width) {
+			const bool keep = !rev || (even && (j == n / 2 - 1 || j == n / 2));
+			body.put((uint64_t)nb + j, no_qual ? (uint8_t)0xff : (uint8_t)(qt[keep ? j : n - 1 - j] - 33));
+		}
+	}
+	body.pos += (uint64_t)nb + n;
+}
+
 // the record of a read whose state is 1: SamEmitter::main_pair's direct BAM branch, field for field
 template <class S> PSVR_FQ void be_record(const FqGroup &g, const BeInput &in, int64_t p, int k, const BeRead &R, S &o)
 {
@@ -299,24 +321,7 @@ template <class S> PSVR_FQ void be_record(const FqGroup &g, const BeInput &in, i
 		}
 		body.pos += 4 * (uint64_t)R.n_cigar;
 	}
-	// SEQ: two 4-bit codes per byte, the odd tail's low nibble 0; QUAL: phred values; the reverse strand through getReverseStr_char /
-	// getReverseStr_qual_char (whose loop bound swaps the middle pair of an even-length read back)
-	const bool rev = R.direction == 0;
-	const uint32_t n = R.read_l, nb = (n + 1) / 2;
-	if (S::writes) {
-		for (uint32_t j = g.lane; j < nb; j += FqGroup::width) {
-			const uint32_t i = 2 * j;
-			const uint32_t hi = rev ? be_rc_code((uint8_t)R.st[n - 1 - i]) : be_code((uint8_t)R.st[i]);
-			const uint32_t lo = i + 1 < n ? (rev ? be_rc_code((uint8_t)R.st[n - 2 - i]) : be_code((uint8_t)R.st[i + 1])) : 0u;
-			body.put(j, (uint8_t)(hi << 4 | lo));
-		}
-		const bool even = !(n & 1) && n >= 2;
-		for (uint32_t j = g.lane; j < n; j += FqGroup::width) {
-			const bool keep = !rev || (even && (j == n / 2 - 1 || j == n / 2));
-			body.put((uint64_t)nb + j, (uint8_t)(R.qt[keep ? j : n - 1 - j] - 33));
-		}
-	}
-	body.pos += (uint64_t)nb + n;
+	be_seq_qual(g, body, R.st, R.qt, R.read_l, R.direction == 0, false);
 	// the tags
 	be_tag_int(g, body, 'A', 'S', (int32_t)R.align_score), be_tag_int(g, body, 'O', 'S', (int32_t)ori.align_score);
 	be_tag_z(g, body, 'O', 'A'), be_num(g, body, ori.chr_id), be_u8(g, body, ','), be_num(g, body, (int32_t)(ori.ref_bg >= 0x7fffffffu ? 1u : ori.ref_bg)), be_u8(g, body, ',');

@@ -22,6 +22,7 @@ struct EngineEmitView {
 	const psvr_read_hdr_t *hdr; const psvr_pair_result_t *pairs;   // device pointers: hdr.cand_off indexes cands, cand.cigar_off indexes cig
 	const psvr_cand_t *cands; int64_t n_cands;
 	const uint32_t *cig; int64_t n_cig;
+	int32_t min_filter_score;                                // of the engine's parameters (the second file's gate)
 };
 void engine_emit_view(const psvr_engine *e, EngineEmitView *v);
 

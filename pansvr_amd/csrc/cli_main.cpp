@@ -74,6 +74,14 @@ struct Opt : aln::PipeOpt {
 	"                                 interleaved runs, median wall): 0.390 s against 0.525 s for --emit-device --deflate-device and 0.373 s for plain\n" \
 	"                                 --deflate-device (on par: the ranges overlap; DESIGN.md section 8 f3)"
 
+// what --ori-device's usage text says about its speed
+#define PSVR_ORI_DEVICE_MEASURED \
+	"Measured\n" \
+	"                                 (1 M pairs, -t 16, three interleaved runs, median wall): behind --mate-device\n" \
+	"                                 --stream-device 0.526 s against 0.582 s without it, behind --stream-device on FASTQ 0.488 s against 0.406 s (the\n" \
+	"                                 ranges overlap in both: no gain shown); format_s 0.05-0.06 s against 0.09 s, engine_s 0.31 / 0.34 s against 0.35 /\n" \
+	"                                 0.30 s, d2h_bytes 0 against 211 MB, text_d2h_bytes 6.7 MB of 830 MB (DESIGN.md section 8 f3)"
+
 // what --sort-device's usage text says about its speed
 #define PSVR_SORT_DEVICE_MEASURED \
 	"Measured (1 M pairs, -t 16,\n" \
@@ -141,7 +149,14 @@ static int usage()
 	        "                                 that fails (a window of 4 GiB or more, a device error) leaves the rest of the input to the host threads.\n"
 	        "                                 " PSVR_PARSE_DEVICE_MEASURED "\n"
 	        "        --emit-device            FASTQ input: implies --parse-device; the main BAM file's records are encoded on the GPU as well (a chunk with\n"
-	        "                                 a pair the encoder declines is formatted on the host threads)\n"
+	        "                                 a pair the encoder declines is formatted on the host threads, and so is the second file unless --ori-device\n"
+	        "                                 is given)\n"
+	        "        --ori-device             FASTQ input: implies --emit-device; the second (-p) file's records are encoded on the GPU as well, from the\n"
+	        "                                 FLAG_ / CIGAR_ / MATE_ / TAG_ text of the comments (a chunk with a pair that encoder declines is formatted on the\n"
+	        "                                 host threads).  A piece of which neither encoder declined a pair is resident: its results are not downloaded and,\n"
+	        "                                 behind --bam-device / --mate-device, its text is not fetched.  Not with -S or more than one entry in --devices.\n"
+	        "                                 A failed call leaves the second file to the host threads from there on.  Combines with --stream-device,\n"
+	        "                                 --sort-device, --deflate-device, --bam-device, --mate-device and --sort.  " PSVR_ORI_DEVICE_MEASURED "\n"
 	        "        --stream-device          FASTQ input: implies --emit-device and --deflate-device; the main BAM file's records go from the encoder to\n"
 	        "                                 the BGZF member compressor inside GPU memory (a device-resident stream cut every 0xff00 bytes) and only the\n"
 	        "                                 compressed members come to the host; chunks the host formatted are uploaded into the same stream.  Not with\n"
@@ -234,6 +249,9 @@ struct EngineDriver {
 	HostBuf stage[aln::kSlots];               // ... and the page-locked copy of the window it parses
 	psvr_bam_emit_t *bem[aln::kSlots] = {};   // --emit-device: the slot's record encoder; the piece's records, offsets and states once downloaded (page-locked)
 	HostBuf em_bytes[aln::kSlots], em_off[aln::kSlots], em_state[aln::kSlots];
+	psvr_bam_emit_info_t em_info[aln::kSlots] = {};   // ... and the totals of its last run
+	psvr_bam_emit_t *bem_ori[aln::kSlots] = {};   // --ori-device: the same for the second file (DriverOriSource below)
+	HostBuf ori_bytes[aln::kSlots], ori_off[aln::kSlots], ori_state[aln::kSlots];
 	// PSVR_PARSE_DEVICE_MAX_BYTES: the largest window that goes to the device (the tests send every window to the fallback with it)
 	const size_t parse_max_window = getenv("PSVR_PARSE_DEVICE_MAX_BYTES") ? (size_t)strtoull(getenv("PSVR_PARSE_DEVICE_MAX_BYTES"), nullptr, 10) : ~(size_t)0;
 
@@ -263,6 +281,7 @@ struct EngineDriver {
 	void release()
 	{
 		for (auto &b : bem) if (b) psvr_bam_emit_destroy(b), b = nullptr;
+		for (auto &b : bem_ori) if (b) psvr_bam_emit_destroy(b), b = nullptr;
 		for (auto &f : fq) if (f) psvr_fastq_destroy(f), f = nullptr;
 		for (psvr_engine_t *e : eng) if (e) psvr_engine_destroy(e);
 		for (size_t d = 0; d < idx.size(); ++d) if (first[d] == (int)d) psvr_index_destroy(idx[d]);
@@ -326,17 +345,37 @@ struct EngineDriver {
 	int emit_encode(int slot, const FastqBatch &fb, bool not_ori)
 	{
 		if (!bem[slot]) if (int rc = psvr_bam_emit_create(idx[0], &bem[slot])) return rc;
-		return psvr_bam_emit_engine(bem[slot], eng[0], fb.dev, not_ori ? PSVR_EMIT_NOT_ORI : 0, nullptr);
+		return psvr_bam_emit_engine(bem[slot], eng[0], fb.dev, not_ori ? PSVR_EMIT_NOT_ORI : 0, &em_info[slot]);
 	}
-	int emit_download(int slot, long long P, aln::EmitView *v)
+	// an emitter's piece into page-locked memory: offsets and states first (they say how many bytes)
+	static int emitter_download(psvr_bam_emit_t *em, long long P, HostBuf &hb, HostBuf &ho, HostBuf &hs, aln::EmitView *v)
 	{
-		int64_t *off = (int64_t *)em_off[slot].reserve((size_t)(P + 1) * 8);
-		uint8_t *stt = (uint8_t *)em_state[slot].reserve((size_t)P + 1);
-		if (int rc = psvr_bam_emit_download(bem[slot], nullptr, 0, off, stt)) return rc;
-		uint8_t *bytes = (uint8_t *)em_bytes[slot].reserve((size_t)off[P] + 1);
+		int64_t *off = (int64_t *)ho.reserve((size_t)(P + 1) * 8);
+		uint8_t *stt = (uint8_t *)hs.reserve((size_t)P + 1);
+		if (int rc = psvr_bam_emit_download(em, nullptr, 0, off, stt)) return rc;
+		uint8_t *bytes = (uint8_t *)hb.reserve((size_t)off[P] + 1);
 		v->bytes = bytes, v->off = off, v->state = stt;
-		return psvr_bam_emit_download(bem[slot], bytes, off[P], nullptr, nullptr);
+		return psvr_bam_emit_download(em, bytes, off[P], nullptr, nullptr);
 	}
+	int emit_download(int slot, long long P, aln::EmitView *v) { return emitter_download(bem[slot], P, em_bytes[slot], em_off[slot], em_state[slot], v); }
+};
+
+// --ori-device: the second file's encoder as the pipeline sees it: a second emitter per slot, run on the engine's results where they lie
+struct DriverOriSource : aln::OriSource {
+	EngineDriver &drv;
+	explicit DriverOriSource(EngineDriver &d) : drv(d) {}
+	int encode(int slot, const FastqBatch &fb, long long *declined) override
+	{
+		if (!drv.bem_ori[slot]) if (int rc = psvr_bam_emit_create(drv.idx[0], &drv.bem_ori[slot])) return rc;
+		psvr_bam_emit_info_t info;
+		const int rc = psvr_bam_emit_ori_engine(drv.bem_ori[slot], drv.eng[0], fb.dev, &info);
+		if (!rc) *declined = info.n_declined_pairs;
+		return rc;
+	}
+	long long main_declined(int slot) override { return drv.em_info[slot].n_declined_pairs; }
+	int download(int slot, long long P, aln::EmitView *v) override { return EngineDriver::emitter_download(drv.bem_ori[slot], P, drv.ori_bytes[slot], drv.ori_off[slot], drv.ori_state[slot], v); }
+	int fetch_text(FastqBatch &fb) override { return FastqReader::fetch_window_text(fb); }
+	const char *last_error() override { return psvr_last_error(); }
 };
 
 // --stream-device: bgzf_stream_sink.h's backend over psvr_bgzf_stream_* and the pipeline slots' emitters (EngineDriver::bem[]), and the sink as
@@ -518,6 +557,10 @@ static bool option_conflict(const Opt &o, const char *sort_conflict)
 		fprintf(stderr, "--sort cannot be combined with %s: the sorted file is BAM compressed as `panSVR sort` compresses it\n", sort_conflict);
 	else if (o.deflate_device && sort_conflict)
 		fprintf(stderr, "--deflate-device cannot be combined with %s: it is a compression route of its own for BAM output (a wavefront per BGZF member on the GPU)\n", sort_conflict);
+	else if (o.ori_device && o.devices.size() > 1)
+		fprintf(stderr, "--ori-device cannot be combined with more than one entry in --devices: the second file's records are encoded from the text and the results in the first device's memory\n");
+	else if (o.ori_device && o.sam)
+		fprintf(stderr, "--ori-device cannot be combined with -S: the device encodes BAM records, SAM text is formatted on the host threads\n");
 	else if (o.emit_device && o.devices.size() > 1)
 		fprintf(stderr, "--emit-device cannot be combined with more than one entry in --devices: the records are encoded from the text and the results in the first device's memory\n");
 	else if (o.emit_device && o.sam)
@@ -539,7 +582,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	static struct option lo[] = {{"thread", 1, 0, 't'}, {"gap-open1", 1, 0, 'O'}, {"gap-open2", 1, 0, 'P'}, {"gap-extension1", 1, 0, 'E'}, {"gap-extension2", 1, 0, 'F'},
 	                             {"match-score", 1, 0, 'M'}, {"mis-score", 1, 0, 'm'}, {"zdrop", 1, 0, 'z'}, {"band-width", 1, 0, 'w'}, {"output", 1, 0, 'o'},
 	                             {"output_signal_ori", 1, 0, 'p'}, {"not-ori", 0, 0, 'Q'}, {"SAM", 0, 0, 'S'}, {"max_use_read", 1, 0, 'R'}, {"device", 1, 0, 1000},
-	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019}, {"mate-device", 0, 0, 1020}, {"block-records", 1, 0, 1021}, {"deflate-effort", 1, 0, 1022},
+	                             {"records", 1, 0, 1001}, {"trace", 0, 0, 1002}, {"batch", 1, 0, 1003}, {"devices", 1, 0, 1004}, {"batch-bases", 1, 0, 1005}, {"compress-level", 1, 0, 1006}, {"sub-batch", 1, 0, 1007}, {"bgzf-device", 0, 0, 1008}, {"bgzf-fast", 0, 0, 1009}, {"sort", 0, 0, 1010}, {"inflate-device", 0, 0, 1011}, {"inflate-threads", 1, 0, 1012}, {"deflate-device", 0, 0, 1013}, {"parse-device", 0, 0, 1014}, {"emit-device", 0, 0, 1015}, {"stream-device", 0, 0, 1016}, {"sort-device", 0, 0, 1017}, {"signal-device", 0, 0, 1018}, {"bam-device", 0, 0, 1019}, {"mate-device", 0, 0, 1020}, {"block-records", 1, 0, 1021}, {"deflate-effort", 1, 0, 1022}, {"ori-device", 0, 0, 1023},
 	                             {"not-use-filter", 0, 0, 'D'}, {"discard-full-match", 0, 0, 'U'}, {"sort-by-name", 0, 0, 'N'}, {0, 0, 0, 0}};
 	int c;
 	const char *sort_conflict = nullptr;               // the first option that --sort cannot go with
@@ -575,6 +618,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 		case 1013: o.deflate_device = true; break;
 		case 1014: o.parse_device = true; break;
 		case 1015: o.emit_device = o.parse_device = true; break;
+		case 1023: o.ori_device = o.emit_device = o.parse_device = true; break;
 		case 1017: o.sort_device = o.sort = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1016: o.stream_device = o.emit_device = o.parse_device = o.deflate_device = true; break;
 		case 1018: fprintf(stderr, "[panSVR-amd] --signal-device is `panSVR signal -N`'s route to FASTQ text: ignored by aln (a *.bam read file hands its pairs over on the host threads)\n"); break;
@@ -605,6 +649,7 @@ static int parse_aln_options(int argc, char **argv, Opt *op)
 	if (o.from_bam && o.sort_device) fprintf(stderr, "[panSVR-amd] --sort-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the run is that of --sort --deflate-device)\n", o.reads.c_str());
 	else if (o.from_bam && o.stream_device) fprintf(stderr, "[panSVR-amd] --stream-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads; the files are compressed as with --deflate-device)\n", o.reads.c_str());
 	else if (o.from_bam && o.emit_device) fprintf(stderr, "[panSVR-amd] --emit-device applies to FASTQ text: ignored for [%s] (the records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
+	if (o.from_bam && o.ori_device) fprintf(stderr, "[panSVR-amd] --ori-device applies to FASTQ text: ignored for [%s] (the second file's records of a *.bam read file are formatted on the host threads)\n", o.reads.c_str());
 	return -1;
 }
 
@@ -767,7 +812,10 @@ static int aln_main(int argc, char **argv)
 	em.H = &H, em.sv = &svn, em.as_bam = !o.sam, em.not_ori = o.not_ori, em.stats = &st.emit;
 	std::function<bool(const uint8_t *, size_t)> keep_main;
 	if (o.sort) keep_main = [&sorted](const uint8_t *p, size_t n) { return sorted.add_stream(p, n); };
-	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, device_routes, main_sink.get());
+	DriverOriSource ori_source(drv);                     // --ori-device: the second file's records from the device; the window routes then leave a piece's text there until it is asked for
+	if (o.ori_device && device_routes) fq.set_lazy_window_text(true);
+	st.ori_fields = o.ori_device;
+	aln::AlnPipeline<EngineDriver> pipe(o, drv, fq, par, em, fo, fo_ori, keep_main, frec, st, device_routes, main_sink.get(), o.ori_device && device_routes ? &ori_source : nullptr);
 	pipe.run();
 	windows.abort();
 	feed.abort();                                        // (a reader that stopped at -R leaves the signal step to run to its end unheard)
@@ -818,7 +866,8 @@ int main(int argc, char **argv)
 		}, &members_fn);
 	if (argc >= 2 && (!strcmp(argv[1], "aln") || !strcmp(argv[1], "fc_aln"))) return aln_main(argc, argv);
 	fprintf(stderr, "panSVR (MI355X engine): the read re-alignment step and its two neighbours.\n  usage: panSVR aln|fc_aln [options] <IndexDir> <reads.fq|-> <header.sam>\n         panSVR index [-k 22] <anchors.fa> <IndexDir>\n         panSVR signal [-N] [options] <in.bam> > reads.fq\n         panSVR sort [-n] [-t threads] [-o out.bam] in.bam      (coordinate order + .bai, or -n name order)\n         panSVR sort --sort-device [-t threads] [-o out.bam] in.bam      (the same files, the records inflated, kept, ordered and compressed in GPU memory)\n         panSVR sort --nsort-device [-t threads] [-o out.bam] in.bam     (name order by the same route: the file of sort -n --deflate-device, no index)\n         signal, sort and aln <in.bam>: --inflate-device | --inflate-threads N  (the input's BGZF members inflated in batches)\n         aln, aln --sort and sort: --deflate-device  (the output's BGZF members compressed on the GPU, a wavefront per member)\n         aln <reads.fq>: --parse-device  (the FASTQ text parsed on the GPU, the bases handed to the engine device to device)\n         aln <reads.fq>: --emit-device   (implies --parse-device; the main BAM file's records encoded on the GPU as well)\n"
-	                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
+	                "         aln <reads.fq>: --ori-device    (implies --emit-device; the second file's records encoded on the GPU too, pieces both encoders took whole stay there)\n"
+                "         aln <reads.fq>: --stream-device (implies --emit-device and --deflate-device; the records go from the encoder to the compressor in GPU memory)\n"
 	                "         aln <reads.fq>: --sort-device   (implies --sort, --emit-device and --deflate-device; the records are kept, ordered and compressed in GPU memory)\n"
 	                "         panSVR aln --sort ...    (the same coordinate-sorted BAM + .bai straight from the aln step)\n");
 	return 1;

@@ -2425,6 +2425,7 @@ void psvr::engine_emit_view(const psvr_engine *e, EngineEmitView *v)
 	v->device = e->ix->device, v->ran = e->ran && e->core.P > 0;
 	v->fq = e->src_fq, v->first_pair = e->src_first, v->n_pairs = e->src_n, v->generation = e->src_generation;
 	v->hdr = c.rh, v->pairs = c.pres, v->cands = c.cand, v->n_cands = (int64_t)c.cw.cap, v->cig = c.cig.base, v->n_cig = (int64_t)c.cig.cap;
+	v->min_filter_score = c.par.min_filter_score;
 }
 
 extern "C" int psvr_engine_stats(const psvr_engine_t *e, char *buf, size_t n)

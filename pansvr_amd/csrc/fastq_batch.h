@@ -221,6 +221,8 @@ struct FastqBatch {
 	HostBuf bases_buf, off_buf, ori_buf;             // what psvr_engine_upload reads (page-locked)
 	char *bases = nullptr; int64_t *base_off = nullptr; psvr_ori_t *ori = nullptr;
 	const psvr_fastq_t *dev = nullptr;               // --parse-device: the batch was parsed into this parser's device buffers; `bases` is then not filled
+	long long text_pending = 0;                      // --ori-device, a window's piece: `text` has room for this many bytes that are still in dev's memory (FastqReader::fetch_window_text); 0: the text is here
+	long long text_fetched = 0;                      // ... bytes of text that came from dev's memory for this piece so far
 	long long R = 0;
 	long long n_pairs() const { return R / 2; }
 
@@ -323,6 +325,7 @@ class FastqReader {
 	std::vector<int32_t> slen_;                      // scratch: sequence length per candidate read of the batch being cut
 	std::string first_comment_;
 	bool have_first_ = false;
+	bool lazy_window_text_ = false;
 
 	// appends the offsets (relative to `base`) of the line starts that follow the newlines in [from, to)
 	static void index_lines(const char *base, size_t from, size_t to, int threads, std::vector<uint64_t> &ls)
@@ -351,12 +354,12 @@ public:
 	bool read(FastqBatch &B, long long max_pairs, long long max_bases, int threads)
 	{
 		if (feed_) {
-			B.dev = nullptr;
+			B.dev = nullptr, B.text_pending = B.text_fetched = 0;
 			if (!feed_->fill(B, max_pairs, max_bases)) return false;
 			if (!have_first_ && feed_->have_first) first_comment_ = feed_->first_comment, have_first_ = true;
 			return true;
 		}
-		B.R = 0, B.dev = nullptr;
+		B.R = 0, B.dev = nullptr, B.text_pending = B.text_fetched = 0;
 		B.ls.clear();
 		B.ls.push_back(0);
 		const size_t want_lines = (size_t)max_pairs * 8;
@@ -447,7 +450,7 @@ public:
 	// 1: a batch; 0: the end of the input; -1: the device route failed (*why says how) and nothing was consumed: read() takes over.
 	int read_device(FastqBatch &B, long long max_pairs, long long max_bases, int threads, psvr_fastq_t *fq, HostBuf &stage, size_t max_window, std::string *why)
 	{
-		B.R = 0, B.dev = nullptr;
+		B.R = 0, B.dev = nullptr, B.text_pending = B.text_fetched = 0;
 		const size_t step = est_pair_bytes_ * (size_t)max_pairs / 8 * 9 + (1 << 20);
 		if (!src_.mapped()) { B.own.clear(); src_.take_carry(B.own); }
 		auto fail = [&](const std::string &w) {
@@ -498,13 +501,24 @@ public:
 	// used, into the page-locked `stage`, for the host formatter; B.dev = fq as read_device sets it.
 	// 1: a piece; 0: the end of the input; -1: the call failed (*why says how; the route's producer is told and leaves the route);
 	// -2: the producer has left the route.  After -1 and -2 the pairs come through the PairFeed: read() takes over.  `why` names the call.
+	// set_lazy_window_text (--ori-device): the text is left in the parser's memory (B.text_pending says how much) and fetched by
+	// fetch_window_text when the piece turns out to need it -- a piece whose records were all encoded on the device never does.  The first
+	// piece is always fetched: stat_params reads its first comment.
+	void set_lazy_window_text(bool on) { lazy_window_text_ = on; }
+	static int fetch_window_text(FastqBatch &B)
+	{
+		if (!B.text_pending) return 0;
+		if (int rc = psvr_fastq_text(B.dev, const_cast<char *>(B.text), 0, B.text_pending)) return rc;
+		B.text_fetched += B.text_pending, B.text_pending = 0;
+		return 0;
+	}
 	void open_windows(WindowFeed *w) { windows_ = w; }
 	bool has_windows() const { return windows_ != nullptr; }
 	// a call of the reader's side failed in front of read_window (its parser could not be made): the producer is told as read_window tells it
 	void fail_windows(const std::string &why) { if (windows_) windows_->fail(why), windows_ = nullptr; }
 	int read_window(FastqBatch &B, long long max_pairs, long long max_bases, psvr_fastq_t *fq, HostBuf &stage, std::string *why)
 	{
-		B.R = 0, B.dev = nullptr;
+		B.R = 0, B.dev = nullptr, B.text_pending = B.text_fetched = 0;
 		const psvr_signal_t *sg = nullptr;
 		long long first_byte = 0, pairs_left = 0;
 		const int r = windows_->next(&sg, &first_byte, &pairs_left);
@@ -520,8 +534,8 @@ public:
 		B.ori = (psvr_ori_t *)B.ori_buf.reserve((size_t)R * sizeof(psvr_ori_t));
 		char *text = (char *)stage.reserve((size_t)info.used_bytes + 1);
 		if (psvr_fastq_download(fq, B.ls.data(), B.name_end.data(), B.base_off, B.ori, nullptr)) return fail(std::string("fastq download: ") + psvr_last_error());
-		if (psvr_fastq_text(fq, text, 0, info.used_bytes)) return fail(std::string("fastq text: ") + psvr_last_error());
-		B.text = text, B.R = R, B.bases = nullptr, B.dev = fq;
+		B.text = text, B.R = R, B.bases = nullptr, B.dev = fq, B.text_pending = info.used_bytes;
+		if (!(lazy_window_text_ && have_first_) && fetch_window_text(B)) return fail(std::string("fastq text: ") + psvr_last_error());
 		if (!have_first_) { const char *b; int n; B.comment(0, b, n); first_comment_.assign(b, (size_t)n); have_first_ = true; }
 		windows_->took(info.used_bytes, npairs);
 		return 1;

@@ -1,5 +1,6 @@
 """The main BAM file's records encoded on the device through the C ABI (psvr_bam_emit_*): from the window a FastqParser holds and a set of
-results -- the caller's compact arrays (emit_results) or an engine's last run where it lies in HBM (emit_engine)."""
+results -- the caller's compact arrays (emit_results) or an engine's last run where it lies in HBM (emit_engine).  emit_ori_results /
+emit_ori_engine do the same for the second (-p) file's records (psvr_bam_emit_ori_*); an emitter holds the records of its last run."""
 import ctypes as C
 
 import numpy as np
@@ -39,6 +40,24 @@ class BamEmitter:
         """The results of engine's last run, device to device: its batch must have come from parser.upload_to(engine, ...)."""
         info = EmitInfo()
         check(lib().psvr_bam_emit_engine(self.h, engine.h, parser.h, C.c_int32(flags), C.byref(info)))
+        self.info, self.n_pairs = info, engine.n_pairs
+        return info
+
+    def emit_ori_results(self, parser, hdr, pairs, cands, cigar, min_filter_score, first_pair=0):
+        """The second file's records (psvr_bam_emit_ori_results) of the same arguments; min_filter_score is the gate of its pairs."""
+        hdr, pairs = np.ascontiguousarray(hdr, dtype=HDR_DTYPE), np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        cands, cigar = np.ascontiguousarray(cands, dtype=CAND_DTYPE), np.ascontiguousarray(cigar, dtype=np.uint32)
+        info = EmitInfo()
+        check(lib().psvr_bam_emit_ori_results(self.h, parser.h, C.c_int64(first_pair), C.c_int64(len(pairs)), hdr.ctypes.data_as(C.c_void_p), pairs.ctypes.data_as(C.c_void_p),
+                                              cands.ctypes.data_as(C.c_void_p), C.c_int64(len(cands)), cigar.ctypes.data_as(C.c_void_p), C.c_int64(len(cigar)),
+                                              C.c_int32(min_filter_score), C.byref(info)))
+        self.info, self.n_pairs = info, len(pairs)
+        return info
+
+    def emit_ori_engine(self, engine, parser):
+        """The second file's records of engine's last run, device to device; the gate is the engine's own min_filter_score."""
+        info = EmitInfo()
+        check(lib().psvr_bam_emit_ori_engine(self.h, engine.h, parser.h, C.byref(info)))
         self.info, self.n_pairs = info, engine.n_pairs
         return info
 
