@@ -9,7 +9,7 @@
 // --sort-device (sort_device_route): the file's own BGZF members go to the device as they are read, a piece of PSVR_INFLATE_BATCH compressed
 // bytes at a time while the next piece is read; they are inflated into a device-resident record store and cut into records there
 // (psvr_bam_store_append_bgzf, include/psvr_engine.h), and at the end of the file the store is ordered, gathered, compressed and indexed by
-// sort_store_sink.h's writer: no inflated byte and no record visits the host.  Whatever fails -- no device, memory, a position the key cannot
+// sorted_bam.h's store writer: no inflated byte and no record visits the host.  Whatever fails -- no device, memory, a position the key cannot
 // hold, a corrupt member, a malformed record, a truncated file -- is named on one line, the store is destroyed, and the --deflate-device
 // route below runs on the same file from its beginning: its messages and its exit status are the command's.
 //   panSVR sort --nsort-device [-t threads] [-o out.bam] in.bam         name order by the same route: the store is ordered by psvr_bam_store_order_names,
@@ -28,12 +28,11 @@
 #include "bgzf_pieces.h"
 #include "name_key.h"
 #include "sorted_bam.h"
-#include "sort_store_sink.h"
 
 namespace psvr {
 
-// The device route of `panSVR sort --sort-device` over a backend (cli_main.cpp: psvr_bam_store_* and psvr_bgzf_stream_*): sort_store_sink.h's
-// calls, and int store_append_bgzf(const void *, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad_member),
+// The device route of `panSVR sort --sort-device` over a backend (cli_main.cpp: psvr_bam_store_* and psvr_bgzf_stream_*): what
+// finish_sorted_store asks (sorted_bam.h), int store_create(), and int store_append_bgzf(const void *, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad_member),
 // int store_chain_info(psvr_bam_chain_info_t *).  0: out_fn and its .bai are written; -1: the route was left (one line said why), the caller
 // sorts the file its other way; 2: the output cannot be written.  by_name (--nsort-device): name order, no index; the backend has store_order_names().
 template <class Backend> int sort_device_route(Backend &be, const std::string &in_fn, const std::string &out_fn, bool by_name = false)
@@ -81,14 +80,13 @@ template <class Backend> int sort_device_route(Backend &be, const std::string &i
 	int64_t n_rec = 0, n_bytes = 0;
 	if (be.store_info(&n_rec, &n_bytes)) return left("info", be.last_error());
 	const double t1 = now();
-	SortStoreSink<Backend> sink(be, [](const SortRecords &) { return 2; });
-	sink.adopt(out_fn.c_str(), text, refs, by_name);
-	if (const int rc = sink.finish_store()) return rc;
+	StoreWritten w;
+	if (const int rc = finish_sorted_store(be, out_fn, text, refs, by_name, kDeflateDeviceBlocks, &w)) return rc;
 	const double t2 = now();
-	fprintf(stderr, "[panSVR-amd] sort: %lld records -> %s (%s order, ordered on the device, records kept on the device)\n", sink.st.records, out_fn.c_str(), by_name ? "name" : "coordinate");
+	fprintf(stderr, "[panSVR-amd] sort: %lld records -> %s (%s order, ordered on the device, records kept on the device)\n", w.records, out_fn.c_str(), by_name ? "name" : "coordinate");
 	fprintf(stderr, "[panSVR-amd] sort %s: %lld records, %lld record bytes, %lld members in, %lld members out, %lld segments: %lld without a guess, %lld wrong guesses, %lld walked again; append %.3f s, order %.3f s, write %.3f s\n",
-	        opt, (long long)n_rec, (long long)n_bytes, members_in, sink.st.members, (long long)ci.segments, (long long)ci.no_guess, (long long)ci.wrong_guess, (long long)ci.rewalked,
-	        t1 - t0, sink.st.t_order, t2 - t1 - sink.st.t_order);
+	        opt, (long long)n_rec, (long long)n_bytes, members_in, w.members, (long long)ci.segments, (long long)ci.no_guess, (long long)ci.wrong_guess, (long long)ci.rewalked,
+	        t1 - t0, w.t_order, t2 - t1 - w.t_order);
 	return 0;
 }
 

@@ -1,7 +1,7 @@
 // bgzf_stream_sink.h -- the writer of `panSVR aln --stream-device`'s main file: the BAM stream is gathered in a device-resident BGZF stream
 // (psvr_bgzf_stream_*, include/psvr_engine.h) instead of in BgzfWriter's page-locked buffer, so that the records the device encoded go from
 // the encoder to the compressor without leaving HBM.  Host C++ only, a template over the stream backend: cli_main.cpp has the product's, over
-// psvr_bgzf_stream_* and the pipeline slots' emitters; tests/tools/bgzf_stream_sink_check.cpp has one that keeps the stream in host memory
+// psvr_bgzf_stream_* and the pipeline slots' emitters; tests/tools/sink_host.h has one that keeps the stream in host memory
 // and makes the members with the encoder's host build, so every rule in here runs without a GPU (tests/test_bgzf_stream_sink.py).
 //
 // The sink owns the file.  What reaches it, in stream order: the BAM header (open), then per piece its chunks -- device_chunks(slot, p0, p1)
@@ -18,16 +18,17 @@
 // with a non-zero status.
 //
 // What a backend offers (every int is 0 or a status whose text last_error() gives):
-//   int create()                                               the stream, at members of kBgzfBlock bytes
-//   int append(const void *, int64_t) / int append_emit(int slot, int64_t first_pair, int64_t n_pairs) / int64_t pending()   (< 0: failed)
+//   int stream_create() / void stream_destroy()                the stream, at members of kBgzfBlock bytes
+//   int stream_append(const void *, int64_t) / int stream_append_emit(int slot, int64_t first_pair, int64_t n_pairs)
+//   int64_t stream_pending()                                   (< 0: failed)
 //   int64_t bound(int64_t n)                                   room that the members of n pending bytes never exceed
-//   int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *n_members, int64_t *used)
-//   int recover(void *bytes, int64_t cap, int64_t *n)          cap too small: kOverflow and *n is set
+//   int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *member_off, int64_t member_cap, int64_t *n_members, int64_t *used)
+//   int stream_recover(void *bytes, int64_t cap, int64_t *n)   cap too small: kOverflow and *n is set
 //   int emit_view(int slot, int64_t P, const int64_t **off, const uint8_t **state)   offsets and states of the slot's emitted piece
 //   int emit_fetch(int slot, int64_t p0, int64_t p1, std::vector<uint8_t> *out)      the records of pairs [p0, p1) of the slot's piece
-//   void *host_alloc(size_t) / void host_free(void *)          page-locked where that exists
+//   void *host_alloc(size_t) / void host_free(void *)          page-locked where that exists (member_take.h, which makes the takes)
 //   void host_route(BgzfWriter &)                              how the writer that takes over compresses (set_device_members, or nothing)
-//   const char *last_error() / void destroy()
+//   const char *last_error()
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -37,6 +38,7 @@
 #include <utility>
 #include <vector>
 #include "bam_writer.h"
+#include "member_take.h"
 
 namespace psvr {
 
@@ -51,8 +53,7 @@ template <class Backend> class BgzfStreamSink {
 public:
 	static const int kOverflow = 6;                      // PSVR_ERR_OVERFLOW
 	StreamSinkStats st;
-	explicit BgzfStreamSink(Backend &be, size_t take_members = 1024) : be_(be), take_members_(take_members < 1 ? 1 : take_members) {}
-	~BgzfStreamSink() { if (pin_) be_.host_free(pin_); }
+	explicit BgzfStreamSink(Backend &be, size_t take_members = 1024) : be_(be), take_(be), take_members_(take_members < 1 ? 1 : take_members) {}
 
 	// the file and the stream; the BAM header is the stream's first bytes.  false: the file cannot be opened
 	bool open(const char *fn, const std::string &header_text, const std::vector<BamRef> &refs, int threads)
@@ -61,7 +62,7 @@ public:
 		if (!f_) return false;
 		threads_ = threads;
 		on_ = true;
-		if (be_.create()) {
+		if (be_.stream_create()) {
 			fprintf(stderr, "[panSVR-amd] BGZF stream on the device failed (create: %s): the main file is compressed through the host members route\n", be_.last_error());
 			on_ = false, st.left = true;
 			start_host_route();
@@ -81,7 +82,7 @@ public:
 		if (fatal_) return false;
 		if (p1 <= p0 || n_bytes == 0) return true;
 		if (on_) {
-			if (be_.append_emit(slot, p0, p1 - p0) == 0) {
+			if (be_.stream_append_emit(slot, p0, p1 - p0) == 0) {
 				++st.device_chunks, st.device_bytes += n_bytes, segs_.push_back({true, n_bytes});
 				return true;
 			}
@@ -99,7 +100,7 @@ public:
 	{
 		if (fatal_) return false;
 		if (!on_) return true;
-		const int64_t n = be_.pending();
+		const int64_t n = be_.stream_pending();
 		if (n < 0) return leave("pending");
 		if ((size_t)(n / (int64_t)kBgzfBlock) < take_members_) return true;
 		return take(0, n) || leave("take");
@@ -109,10 +110,10 @@ public:
 	{
 		if (!f_) return false;
 		if (on_ && !fatal_) {
-			const int64_t n = be_.pending();
+			const int64_t n = be_.stream_pending();
 			if (n < 0 || !take(1, n)) leave(n < 0 ? "pending" : "the last take");
 		}
-		be_.destroy();
+		be_.stream_destroy();
 		if (fatal_) {                                        // (no EOF block: the file is not whole, and does not look it)
 			fclose(f_);
 			f_ = nullptr;
@@ -121,24 +122,23 @@ public:
 		if (host_open_) {
 			const bool fine = host_.close();                 // (its EOF block, its fclose)
 			f_ = nullptr;
-			return fine && !fatal_ && ok_;
+			return fine && !fatal_ && take_.wrote;
 		}
-		if (fwrite(kBgzfEof, 1, sizeof kBgzfEof, f_) != sizeof kBgzfEof) ok_ = false;
-		if (fclose(f_) != 0) ok_ = false;
+		if (fwrite(kBgzfEof, 1, sizeof kBgzfEof, f_) != sizeof kBgzfEof) take_.wrote = false;
+		if (fclose(f_) != 0) take_.wrote = false;
 		f_ = nullptr;
-		return ok_ && !fatal_;
+		return take_.wrote && !fatal_;
 	}
 
 private:
 	Backend &be_;
+	MemberTake<Backend> take_;
 	FILE *f_ = nullptr;
 	int threads_ = 1;
 	size_t take_members_;
 	std::atomic<bool> on_{false};                        // (the formatter's thread asks, the writer's thread answers)
-	bool fatal_ = false, ok_ = true, host_open_ = false;
+	bool fatal_ = false, host_open_ = false;
 	BgzfWriter host_;                                    // the host members route, once the device route is left
-	uint8_t *pin_ = nullptr;
-	size_t pin_cap_ = 0;
 	std::vector<uint8_t> fetched_;
 	std::deque<std::pair<bool, int64_t>> segs_;          // what is pending, in order: (from the device, bytes)
 
@@ -159,7 +159,7 @@ private:
 		if (fatal_) return false;
 		if (n == 0) return true;
 		if (on_) {
-			if (be_.append(p, (int64_t)n) == 0) {
+			if (be_.stream_append(p, (int64_t)n) == 0) {
 				st.host_chunks += is_chunk, st.host_bytes += (long long)n, segs_.push_back({false, (int64_t)n});
 				return true;
 			}
@@ -169,28 +169,16 @@ private:
 		host_.write(p, n);
 		return true;
 	}
-	void consumed(int64_t used)                          // a take consumed the first `used` pending bytes
+	bool take(int finish, int64_t pending)               // false: the take failed; otherwise it consumed the first `used` pending bytes
 	{
+		int64_t used = 0;
+		if (!take_(f_, finish, pending, &used)) return false;
+		st.members = take_.members;
 		while (used > 0 && !segs_.empty()) {
 			const int64_t m = segs_.front().second < used ? segs_.front().second : used;
 			used -= m, segs_.front().second -= m;
 			if (segs_.front().second == 0) segs_.pop_front();
 		}
-	}
-	bool take(int finish, int64_t pending)
-	{
-		if (pending == 0) return true;
-		const size_t need = (size_t)be_.bound(pending);
-		if (need > pin_cap_) {
-			if (pin_) be_.host_free(pin_);
-			pin_ = (uint8_t *)be_.host_alloc(need + need / 4), pin_cap_ = pin_ ? need + need / 4 : 0;
-			if (!pin_) return false;
-		}
-		int64_t got = 0, nm = 0, used = 0;
-		if (be_.take(finish, pin_, (int64_t)pin_cap_, &got, &nm, &used)) return false;
-		if (fwrite(pin_, 1, (size_t)got, f_) != (size_t)got) ok_ = false;
-		st.members += nm;
-		consumed(used);
 		return true;
 	}
 	// the device route ends here: what is pending goes to the host members route first.  false: it could not be recovered
@@ -199,11 +187,11 @@ private:
 		fprintf(stderr, "[panSVR-amd] BGZF stream on the device failed (%s: %s): the main file is compressed through the host members route from here on\n", what, be_.last_error());
 		on_ = false, st.left = true;
 		int64_t n = 0;
-		int rc = be_.recover(nullptr, 0, &n);
+		int rc = be_.stream_recover(nullptr, 0, &n);
 		std::vector<uint8_t> back;
 		if (rc == kOverflow && n > 0) {
 			back.resize((size_t)n);
-			rc = be_.recover(back.data(), n, &n);
+			rc = be_.stream_recover(back.data(), n, &n);
 		}
 		if (rc) return fatal("the pending bytes of the stream could not be recovered");
 		for (const auto &s : segs_) if (s.first) st.device_bytes -= s.second, st.host_bytes += s.second;   // (they left HBM after all)

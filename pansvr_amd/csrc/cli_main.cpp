@@ -347,15 +347,24 @@ struct EngineDriver {
 		if (!bem[slot]) if (int rc = psvr_bam_emit_create(idx[0], &bem[slot])) return rc;
 		return psvr_bam_emit_engine(bem[slot], eng[0], fb.dev, not_ori ? PSVR_EMIT_NOT_ORI : 0, &em_info[slot]);
 	}
-	// an emitter's piece into page-locked memory: offsets and states first (they say how many bytes)
-	static int emitter_download(psvr_bam_emit_t *em, long long P, HostBuf &hb, HostBuf &ho, HostBuf &hs, aln::EmitView *v)
+	// an emitter's piece into page-locked memory, in two steps: offsets and states (they say how many bytes), then the bytes
+	static int emitter_view(psvr_bam_emit_t *em, long long P, HostBuf &ho, HostBuf &hs, aln::EmitView *v)
 	{
 		int64_t *off = (int64_t *)ho.reserve((size_t)(P + 1) * 8);
 		uint8_t *stt = (uint8_t *)hs.reserve((size_t)P + 1);
-		if (int rc = psvr_bam_emit_download(em, nullptr, 0, off, stt)) return rc;
-		uint8_t *bytes = (uint8_t *)hb.reserve((size_t)off[P] + 1);
-		v->bytes = bytes, v->off = off, v->state = stt;
-		return psvr_bam_emit_download(em, bytes, off[P], nullptr, nullptr);
+		v->bytes = nullptr, v->off = off, v->state = stt;
+		return psvr_bam_emit_download(em, nullptr, 0, off, stt);
+	}
+	static int emitter_bytes(psvr_bam_emit_t *em, long long P, HostBuf &hb, aln::EmitView *v)
+	{
+		uint8_t *bytes = (uint8_t *)hb.reserve((size_t)v->off[P] + 1);
+		v->bytes = bytes;
+		return psvr_bam_emit_download(em, bytes, v->off[P], nullptr, nullptr);
+	}
+	static int emitter_download(psvr_bam_emit_t *em, long long P, HostBuf &hb, HostBuf &ho, HostBuf &hs, aln::EmitView *v)
+	{
+		if (int rc = emitter_view(em, P, ho, hs, v)) return rc;
+		return emitter_bytes(em, P, hb, v);
 	}
 	int emit_download(int slot, long long P, aln::EmitView *v) { return emitter_download(bem[slot], P, em_bytes[slot], em_off[slot], em_state[slot], v); }
 };
@@ -378,32 +387,33 @@ struct DriverOriSource : aln::OriSource {
 	const char *last_error() override { return psvr_last_error(); }
 };
 
-// --stream-device: bgzf_stream_sink.h's backend over psvr_bgzf_stream_* and the pipeline slots' emitters (EngineDriver::bem[]), and the sink as
-// the pipeline sees it
-// what both sinks' backends ask of the pipeline slots' emitters
-struct EmitterAccess {
-	EngineDriver &drv;
-	long long view_pairs[aln::kSlots] = {};    // pairs of the piece emit_view last looked at, per slot
-	explicit EmitterAccess(EngineDriver &d) : drv(d) {}
-	int emit_view(int slot, int64_t P, const int64_t **off, const uint8_t **state)
-	{
-		int64_t *o = (int64_t *)drv.em_off[slot].reserve((size_t)(P + 1) * 8);
-		uint8_t *st = (uint8_t *)drv.em_state[slot].reserve((size_t)P + 1);
-		view_pairs[slot] = P, *off = o, *state = st;
-		return psvr_bam_emit_download(drv.bem[slot], nullptr, 0, o, st);
-	}
-	int emit_fetch(int slot, int64_t p0, int64_t p1, std::vector<uint8_t> *out)   // (the failure path: the whole piece comes down for one range of it)
-	{
-		const int64_t *off = (const int64_t *)drv.em_off[slot].reserve((size_t)(view_pairs[slot] + 1) * 8);
-		const int64_t total = off[view_pairs[slot]];
-		uint8_t *bytes = (uint8_t *)drv.em_bytes[slot].reserve((size_t)total + 1);
-		if (int rc = psvr_bam_emit_download(drv.bem[slot], bytes, total, nullptr, nullptr)) return rc;
-		out->assign(bytes + off[p0], bytes + off[p1]);
-		return 0;
-	}
+// The backends of the device routes (bgzf_stream_sink.h, sort_store_sink.h, sorted_bam.h's store writer, bam_sort.h and signal_device_route.h
+// say what each asks), in one vocabulary: every call is named once and shared by inheritance.
+// what every backend says of the library and of page-locked memory
+struct HostCalls {
 	const char *last_error() { return psvr_last_error(); }
 	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
 	void host_free(void *p) { psvr_host_free(p); }
+};
+// what both sinks' backends ask of the pipeline slots' emitters (EngineDriver::bem[]): emitter_download's two steps, apart
+struct EmitterAccess {
+	EngineDriver &drv;
+	long long view_pairs[aln::kSlots] = {};    // pairs of the piece emit_view last looked at, per slot
+	aln::EmitView view[aln::kSlots];
+	explicit EmitterAccess(EngineDriver &d) : drv(d) {}
+	int emit_view(int slot, int64_t P, const int64_t **off, const uint8_t **state)
+	{
+		const int rc = EngineDriver::emitter_view(drv.bem[slot], P, drv.em_off[slot], drv.em_state[slot], &view[slot]);
+		view_pairs[slot] = P, *off = view[slot].off, *state = view[slot].state;
+		return rc;
+	}
+	int emit_fetch(int slot, int64_t p0, int64_t p1, std::vector<uint8_t> *out)   // (the failure path: the whole piece comes down for one range of it)
+	{
+		const aln::EmitView &v = view[slot];
+		if (int rc = EngineDriver::emitter_bytes(drv.bem[slot], view_pairs[slot], drv.em_bytes[slot], &view[slot])) return rc;
+		out->assign(v.bytes + v.off[p0], v.bytes + v.off[p1]);
+		return 0;
+	}
 };
 // --deflate-effort: the members call at one effort, in the shape the writers take their compressor in (BgzfMembersFn, bam_writer.h)
 template <int EFFORT> static int members_at_effort(int device, const void *in, int64_t n, int32_t mb, void *out, int64_t cap, int64_t *got, int64_t *off, int64_t off_cap, int64_t *nm)
@@ -421,40 +431,41 @@ static int stream_create_at(int device, int effort, psvr_bgzf_stream_t **s)
 	if (int rc = psvr_bgzf_stream_create(device, (int32_t)kBgzfBlock, s)) return rc;
 	return effort ? psvr_bgzf_stream_set_effort(*s, effort) : 0;
 }
-struct StreamBackend : EmitterAccess {
+// the device BGZF stream at the command's effort
+struct StreamCalls : HostCalls {
 	const int device, effort;
 	psvr_bgzf_stream_t *s = nullptr;
-	StreamBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), device(dev), effort(eff) {}
-	int create() { return stream_create_at(device, effort, &s); }
-	void destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
-	int append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
-	int append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
-	int64_t pending() { return psvr_bgzf_stream_pending(s); }
+	explicit StreamCalls(int dev, int eff = 0) : device(dev), effort(eff) {}
+	int stream_create() { return stream_create_at(device, effort, &s); }
+	void stream_destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
+	int stream_append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
 	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
-	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *nm, int64_t *used) { return psvr_bgzf_stream_take(s, finish, out, cap, got, nullptr, 0, nm, used); }
-	int recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
+	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *member_off, int64_t member_cap, int64_t *nm, int64_t *used)
+	{
+		return psvr_bgzf_stream_take(s, finish, out, cap, got, member_off, member_cap, nm, used);
+	}
+};
+// a record store filled from a BAM file's own members
+struct StoreFill {
+	const int store_device;
+	psvr_bam_store_t *store = nullptr;
+	explicit StoreFill(int dev) : store_device(dev) {}
+	int store_create() { return psvr_bam_store_create(store_device, &store); }
+	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
+	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
+	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
+};
+// --stream-device: bgzf_stream_sink.h's backend
+struct StreamBackend : EmitterAccess, StreamCalls {
+	StreamBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), StreamCalls(dev, eff) {}
+	int stream_append_emit(int slot, int64_t first, int64_t n) { return psvr_bgzf_stream_append_emit(s, drv.bem[slot], first, n); }
+	int64_t stream_pending() { return psvr_bgzf_stream_pending(s); }
+	int stream_recover(void *bytes, int64_t cap, int64_t *n) { return psvr_bgzf_stream_recover(s, bytes, cap, n); }
 	void host_route(BgzfWriter &w) { w.set_device_members(device, members_fn(effort), psvr::kDeflateDeviceBlocks); }
 };
-struct StreamMainSink : aln::MainSink {
-	BgzfStreamSink<StreamBackend> &k;
-	explicit StreamMainSink(BgzfStreamSink<StreamBackend> &sink) : k(sink) {}
-	bool on() const override { return k.on(); }
-	int piece_view(int slot, long long P, aln::EmitView *v) override { v->bytes = nullptr; return k.emit_view(slot, P, &v->off, &v->state); }
-	const char *last_error() override { return k.last_error(); }
-	bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) override { return k.device_chunks(slot, p0, p1, n_bytes); }
-	bool host_chunk(const uint8_t *p, size_t n) override { return k.host_chunk(p, n); }
-	bool piece_done() override { return k.piece_done(); }
-};
-
-// --sort-device: sort_store_sink.h's backend over psvr_bam_store_*, psvr_bgzf_stream_* and the pipeline slots' emitters, and the sink as the pipeline sees it
-// the store and stream calls themselves, shared with `panSVR sort --sort-device`
-struct StoreCalls {
-	const int device, effort;
-	psvr_bam_store_t *store = nullptr;
-	psvr_bgzf_stream_t *s = nullptr;
-	explicit StoreCalls(int dev, int eff = 0) : device(dev), effort(eff) {}
-	int store_create() { return psvr_bam_store_create(device, &store); }
-	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
+// `panSVR sort --sort-device` (bam_sort.h: sort_device_route): the store filled from the file's own members, ordered and written through the stream
+struct SortCmdBackend : StoreFill, StreamCalls {
+	explicit SortCmdBackend(int dev, int eff = 0) : StoreFill(dev), StreamCalls(dev, eff) {}
 	int store_append(const void *p, int64_t n) { return psvr_bam_store_append(store, p, n); }
 	int store_info(int64_t *n_records, int64_t *n_bytes)
 	{
@@ -468,41 +479,19 @@ struct StoreCalls {
 	int store_meta(int64_t first, int64_t n, psvr_bam_rec_meta_t *m) { return psvr_bam_store_meta(store, first, n, m); }
 	int store_stream(int64_t first, int64_t n) { return psvr_bam_store_stream(store, s, first, n); }
 	int store_download(void *bytes, int64_t cap, int64_t *n) { return psvr_bam_store_download(store, bytes, cap, n); }
-	int stream_create() { return stream_create_at(device, effort, &s); }
-	void stream_destroy() { if (s) psvr_bgzf_stream_destroy(s), s = nullptr; }
-	int stream_append(const void *p, int64_t n) { return psvr_bgzf_stream_append(s, p, n); }
-	int64_t bound(int64_t n) { return psvr_bgzf_members_bound(n, (int32_t)kBgzfBlock); }
-	int take(int finish, void *out, int64_t cap, int64_t *got, int64_t *member_off, int64_t member_cap, int64_t *nm, int64_t *used)
-	{
-		return psvr_bgzf_stream_take(s, finish, out, cap, got, member_off, member_cap, nm, used);
-	}
 };
-struct SortBackend : EmitterAccess, StoreCalls {
-	SortBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), StoreCalls(dev, eff) {}
+// --sort-device: sort_store_sink.h's backend: the same store and stream, filled from the pipeline slots' emitters
+struct SortBackend : EmitterAccess, SortCmdBackend {
+	SortBackend(EngineDriver &d, int dev, int eff = 0) : EmitterAccess(d), SortCmdBackend(dev, eff) {}
 	int store_append_emit(int slot, int64_t first, int64_t n) { return psvr_bam_store_append_emit(store, drv.bem[slot], first, n); }
 };
-// `panSVR sort --sort-device` (bam_sort.h: sort_device_route): the same store and stream calls without an engine, the store filled from the file's own members
-struct SortCmdBackend : StoreCalls {
-	explicit SortCmdBackend(int dev, int eff = 0) : StoreCalls(dev, eff) {}
-	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
-	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
-	const char *last_error() { return psvr_last_error(); }
-	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
-	void host_free(void *p) { psvr_host_free(p); }
-};
 // `panSVR signal -N --signal-device` (signal_device_route.h): the store filled from the file's own members, and psvr_signal_* over it
-struct SignalCmdBackend {
-	const int device;
-	psvr_bam_store_t *store = nullptr;
+struct SignalCmdBackend : StoreFill, HostCalls {
 	psvr_signal_t *sg = nullptr;
-	explicit SignalCmdBackend(int dev) : device(dev) {}
-	int store_create() { return psvr_bam_store_create(device, &store); }
-	void store_destroy() { if (store) psvr_bam_store_destroy(store), store = nullptr; }
-	int store_append_bgzf(const void *p, int64_t n, int64_t skip, int32_t n_ref, int64_t *used, int64_t *bad) { return psvr_bam_store_append_bgzf(store, p, n, skip, n_ref, used, bad); }
-	int store_chain_info(psvr_bam_chain_info_t *i) { return psvr_bam_store_chain_info(store, i); }
+	explicit SignalCmdBackend(int dev) : StoreFill(dev) {}
 	int store_drop(int64_t n) { return psvr_bam_store_drop(store, n); }
 	int store_footprint(int64_t *chunks, int64_t *bytes) { return psvr_bam_store_footprint(store, chunks, bytes); }
-	int signal_create(const psvr_signal_opt_t *o) { return psvr_signal_create(device, o, &sg); }
+	int signal_create(const psvr_signal_opt_t *o) { return psvr_signal_create(store_device, o, &sg); }   // (beside the store)
 	void signal_destroy() { if (sg) psvr_signal_destroy(sg), sg = nullptr; }
 	int signal_run(int64_t first, int finish, psvr_signal_info_t *i) { return psvr_signal_run(sg, store, first, finish, i); }
 	int signal_text(void *t, int64_t cap) { return psvr_signal_text(sg, t, cap); }
@@ -516,20 +505,19 @@ struct SignalCmdBackend {
 	int signal_left_errors(int64_t *e, int64_t cap) { return psvr_signal_left_errors(sg, e, cap); }
 	int signal_window(const void *t, int64_t n, const int64_t *off, int64_t n_host, psvr_signal_window_info_t *i) { return psvr_signal_window(sg, t, n, off, n_host, i); }
 	int signal_window_add(const void *t, int64_t n, const int64_t *off, int64_t n_host, int32_t restart, psvr_signal_window_info_t *i) { return psvr_signal_window_add(sg, t, n, off, n_host, restart, i); }
-	const char *last_error() { return psvr_last_error(); }
-	void *host_alloc(size_t n) { return psvr_host_alloc(n); }
-	void host_free(void *p) { psvr_host_free(p); }
 };
-struct SortMainSink : aln::MainSink {
-	SortStoreSink<SortBackend> &k;
-	explicit SortMainSink(SortStoreSink<SortBackend> &sink) : k(sink) {}
+// either sink as the pipeline sees it; option: the one that put it there
+template <class Sink> struct DeviceMainSink : aln::MainSink {
+	Sink &k;
+	const char *const opt;
+	DeviceMainSink(Sink &sink, const char *option) : k(sink), opt(option) {}
 	bool on() const override { return k.on(); }
 	int piece_view(int slot, long long P, aln::EmitView *v) override { v->bytes = nullptr; return k.emit_view(slot, P, &v->off, &v->state); }
 	const char *last_error() override { return k.last_error(); }
 	bool device_chunks(int slot, long long p0, long long p1, long long n_bytes) override { return k.device_chunks(slot, p0, p1, n_bytes); }
 	bool host_chunk(const uint8_t *p, size_t n) override { return k.host_chunk(p, n); }
 	bool piece_done() override { return k.piece_done(); }
-	const char *option() const override { return "--sort-device"; }
+	const char *option() const override { return opt; }
 };
 
 // what an option combination is refused with (true: a message went out); sort_conflict: the first option on the line that --sort cannot go with
@@ -781,7 +769,7 @@ static int aln_main(int argc, char **argv)
 	if (streaming) {
 		stream_backend.reset(new StreamBackend(drv, o.devices[0], o.deflate_effort));
 		stream_sink.reset(new BgzfStreamSink<StreamBackend>(*stream_backend, getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
-		main_sink.reset(new StreamMainSink(*stream_sink));
+		main_sink.reset(new DeviceMainSink<BgzfStreamSink<StreamBackend>>(*stream_sink, "--stream-device"));
 		if (!stream_sink->open(o.out.c_str(), H.text, refs, o.thread_n)) { fprintf(stderr, "fail to open output file\n"); abort(); }
 	}
 	// --sort-device: the main file's records go to the sink's store; the file is written when the input has ended
@@ -792,7 +780,7 @@ static int aln_main(int argc, char **argv)
 		sort_backend.reset(new SortBackend(drv, o.devices[0], o.deflate_effort));
 		sort_sink.reset(new SortStoreSink<SortBackend>(*sort_backend, [&](const SortRecords &R) { return write_sorted_main(o, H, refs, R, &st); },
 		                                               getenv("PSVR_STREAM_TAKE_MEMBERS") ? (size_t)atoll(getenv("PSVR_STREAM_TAKE_MEMBERS")) : psvr::kDeflateDeviceBlocks));
-		main_sink.reset(new SortMainSink(*sort_sink));
+		main_sink.reset(new DeviceMainSink<SortStoreSink<SortBackend>>(*sort_sink, "--sort-device"));
 		sort_sink->open(o.out.c_str(), H.text, refs);
 	}
 	if ((!o.sort && !streaming && !fo.open(o.out, !o.sam, H, refs, o.thread_n, o.bam_level)) || !fo_ori.open(o.out_ori, !o.sam, H, refs, o.thread_n, o.bam_level)) { fprintf(stderr, "fail to open output file\n"); abort(); }

@@ -10,11 +10,15 @@
 //                        tail included; a failed call hands that window and all later ones to the host), and (coordinate order) the .bai
 //                        of SAMv1 section 5.2 from the writer's log of block starts: bins with their chunk lists (virtual file offsets),
 //                        the 16 kbp linear index, the per-reference metadata pseudo-bin 37450 and n_no_coor.
+//   write_sorted_store   the same file and index from a device-resident record store (psvr_bam_store_*): ordered, gathered and compressed
+//                        there, so that only the compressed members and the table the .bai is built from come to the host; and
+//                        finish_sorted_store, what `panSVR sort --sort-device` and `--nsort-device` end with
 // The sorted stream never exists in memory as a whole, only the records do.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <time.h>
 #include <algorithm>
 #include <map>
 #include <string>
@@ -22,6 +26,7 @@
 #include <vector>
 #include "../../include/psvr_engine.h"
 #include "bam_writer.h"
+#include "member_take.h"
 
 namespace psvr {
 
@@ -218,6 +223,87 @@ inline bool write_sorted_bam(const std::string &out_fn, const std::string &heade
 	if (by_name) return true;
 	// ---- .bai: from the stream's blocks of 0xff00 bytes, the header included (their file offsets give the virtual offsets)
 	return write_bai(out_fn, build_bai(refs.size(), ord.size(), header_bytes, w.block_starts(), [&](size_t i) { return bai_record(R.rec(ord[i])); }), err);
+}
+
+// The sorted file from a device-resident record store, over a backend (cli_main.cpp has the product's, tests/tools/sink_host.h one in host
+// memory; every int is 0 or a status whose text last_error() gives):
+//   int store_order() / int store_order_names()                coordinate order / name order (by_name)
+//   int store_info(int64_t *n_records, int64_t *n_bytes)       waits for the queued appends
+//   int store_meta(int64_t first_rank, int64_t n, psvr_bam_rec_meta_t *)
+//   int store_stream(int64_t first_rank, int64_t n)            those ranks' records behind the stream's pending bytes
+//   int stream_create() / void stream_destroy() / int stream_append(const void *, int64_t), and what MemberTake asks (member_take.h)
+// The BAM header with the order stated goes into a fresh BGZF stream; then windows of sorted ranks -- as many as fill take_members members --
+// are gathered into the stream, taken (the last window with finish, so the tail becomes the last, shorter member) and written, their starts
+// logged; then the EOF block, and unless by_name the .bai from the meta table and the member starts.
+struct StoreWritten {
+	int status = 0;                                      // 0: written; -1: the backend call `failed` failed (the file, if begun, is closed and partial); 2: the file cannot be written (said on stderr)
+	const char *failed = nullptr;
+	bool begun = false;                                  // the file was opened
+	long long records = 0, members = 0, header_bytes = 0;
+	double t_order = 0;                                  // the order's own time
+};
+template <class Backend> StoreWritten write_sorted_store(Backend &be, const std::string &fn, const std::string &header_text, const std::vector<BamRef> &refs, bool by_name, size_t take_members)
+{
+	auto now = [] { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return ts.tv_sec + 1e-9 * ts.tv_nsec; };
+	StoreWritten w;
+	auto failed = [&](const char *call) { w.status = -1, w.failed = call; return w; };
+	auto cannot = [&](const std::string &why) { fprintf(stderr, "%s\n", why.c_str()); w.status = 2; return w; };
+	const double t0 = now();
+	if (by_name ? be.store_order_names() : be.store_order()) return failed("order");
+	w.t_order = now() - t0;
+	int64_t n = 0, nb = 0;
+	if (be.store_info(&n, &nb)) return failed("info");
+	std::vector<psvr_bam_rec_meta_t> meta((size_t)n);
+	if (n && be.store_meta(0, n, meta.data())) return failed("meta");
+	FILE *f = fopen(fn.c_str(), "wb");
+	if (!f) return cannot("fail to open file '" + fn + "'");
+	w.begun = true;
+	const std::vector<uint8_t> head = bam_header_block(sorted_header_text(header_text, by_name), refs);
+	std::vector<uint64_t> starts;
+	MemberTake<Backend> take(be);
+	const char *bad = nullptr;
+	if (be.stream_create()) bad = "stream create";
+	else {
+		int64_t pending = 0, used = 0;
+		if (be.stream_append(head.data(), (int64_t)head.size())) bad = "stream append";
+		else pending = (int64_t)head.size();
+		const int64_t want = (int64_t)take_members * (int64_t)kBgzfBlock;
+		for (int64_t a = 0; !bad && a < n;) {
+			int64_t b = a, bytes = 0;
+			while (b < n && pending + bytes < want) bytes += meta[(size_t)b++].len;
+			if (be.store_stream(a, b - a)) { bad = "stream from the store"; break; }
+			pending += bytes;
+			if (!take(f, b == n, pending, &used, &starts)) bad = b == n ? "the last take" : "take";
+			pending -= used, a = b;
+		}
+		if (!bad && n == 0 && !take(f, 1, pending, &used, &starts)) bad = "the last take";
+		be.stream_destroy();
+	}
+	if (bad) { fclose(f); return failed(bad); }
+	starts.push_back(take.fpos);
+	if (fwrite(kBgzfEof, 1, sizeof kBgzfEof, f) != sizeof kBgzfEof) take.wrote = false;
+	if (fclose(f) != 0 || !take.wrote) return cannot("fail to write file '" + fn + "'");
+	if (!by_name) {                                      // (a name-sorted file has no index)
+		std::string err;
+		const std::vector<uint8_t> bai = build_bai(refs.size(), (size_t)n, head.size(), starts, [&](size_t i) {
+			const psvr_bam_rec_meta_t &m = meta[i];
+			return BaiRecord{m.tid, m.pos, m.end, m.bin, m.flag, m.len};
+		});
+		if (!write_bai(fn, bai, &err)) return cannot(err);
+	}
+	w.records = n, w.members = take.members, w.header_bytes = (long long)head.size();
+	return w;
+}
+
+// A store that the caller has created through the backend and filled itself (`panSVR sort --sort-device`, bam_sort.h, from the file's own members)
+// into its sorted file, and the store destroyed.  w->status is the answer; the caller of -1 has its input still, and the one line here says
+// that it starts over from it
+template <class Backend> int finish_sorted_store(Backend &be, const std::string &fn, const std::string &header_text, const std::vector<BamRef> &refs, bool by_name, size_t take_members, StoreWritten *w)
+{
+	*w = write_sorted_store(be, fn, header_text, refs, by_name, take_members < 1 ? 1 : take_members);
+	if (w->status < 0) fprintf(stderr, "[panSVR-amd] record store on the device failed (%s: %s): the input is read again and sorted by the host's route\n", w->failed, be.last_error());
+	be.store_destroy();
+	return w->status;
 }
 
 } // namespace psvr

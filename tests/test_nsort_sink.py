@@ -1,4 +1,4 @@
-"""The by-name mode of the sorted writer over an adopted store (pansvr_amd/csrc/sort_store_sink.h: adopt(..., by_name) + finish_store(), what
+"""The by-name mode of the sorted writer over a store its caller filled (pansvr_amd/csrc/sorted_bam.h: finish_sorted_store(..., by_name), what
 `panSVR sort --nsort-device` ends with) without a GPU: tests/tools/nsort_sink_check.cpp drives it over a backend that keeps store and stream in
 host memory and has a store_order_names().  The file is write_sorted_bam(..., by_name = true)'s for the same records, byte for byte, there is
 no .bai, and a failing backend call is named and answered with -1.  The plain and the sanitizer build (stand-alone programs) run the same cases."""
