@@ -86,6 +86,41 @@ struct VU { uint64_t uid; uint32_t read_pos, uni_pos_off, length1, length2, pos_
 struct USeed { uint32_t read_begin, read_end, seed_id, ref_begin, ref_end, cov; };              // UNI_SEED
 struct PathN { int32_t dist, pre_node; uint32_t brk; uint32_t used; };                          // PATH_t (+ scan break)
 
+// ---- the engine's two control blocks (engine_core.h owns them; the kernels and the host index them by these names) ----
+// d_flags, int32 words: the six arenas' overflow flags (Arena::overflow, in this order wherever the arenas are listed), then the sticky
+// words the stages set.  kFlagWords is what a run clears, the DP plan record carries and the host reads back.
+enum FlagWord {
+	kFlagMem = 0, kFlagUs, kFlagSeg, kFlagDp, kFlagCw, kFlagCig, kArenaFlags,     // kArenaFlags: how many of them
+	kFlagErr = kArenaFlags,      // Ctx::err: a StageErr
+	kFlagStaleOpen,              // Ctx::stale_open
+	kFlagAnyH,                   // Ctx::any_h
+	kFlagWords = 16
+};
+// what a stage leaves in the error word (the host prints the number: "device stage error %d")
+enum StageErr {
+	kErrReadTooLong = 1,         // a read longer than kMaxReadLen
+	kErrRandWindow = 2,          // a rand() draw outside the device's window of the stream: the host extends the window and runs the batch again
+	kErrRandomRWindow = 3,       // the same for a random_r stream
+	kErrWalk = 10,               // + WalkState::bad (1: piece list full, 2: target window of 1600 or more)
+	kErrPieceId = 11,            // assembly met a DP piece without a problem id
+	kErrScratch = 20             // CIGAR assembly failed / the team DP kernel's scratch ran out
+};
+PSVR_HD bool stage_err_is_window(int e) { return e == kErrRandWindow || e == kErrRandomRWindow; }
+// d_tops, 64-bit words.  The round end reads [kTopReadFirst, kTopReadEnd) back in one copy; the two lists' counters keep cache lines of
+// their own (every workgroup of k_dirty bumps them).
+enum TopWord {
+	kTopNewSens = 8,             // pairs newly found count-sensitive (k_totals; their numbers are in d_slist)
+	kTopChanged = 9,             // set when an evaluated slot drew another number than at its previous evaluation
+	kTopFull = 32,               // length of the full re-run list (d_work)
+	kTopPairOnly = 48,           // length of the pairing-only list (d_workp)
+	kTopTieSeen = 56,            // tie-only pairs whose chain selection ran again on the spot (d_resel)
+	kTopFromWalk = 57,           // of those: the ones that go on from the walk (d_resel4)
+	kTopAdopted = 60,            // adoptions made on the device (k_adopt_auto; counted for a run with statistics)
+	kTopWords = 64,
+	kTopRunInit = 16,            // what a run clears before its first round; the rest is cleared where it is used
+	kTopReadFirst = kTopNewSens, kTopReadEnd = kTopAdopted + 1
+};
+
 // Bump arena.  `nshard` > 1 (GPU backend, pure storage arenas): the arena is cut into nshard equal regions, each with its own counter in
 // its own cache line (kArenaTopStride words apart); a workgroup bumps the counter of region blockIdx % nshard.  Atomics on one line are
 // served one wavefront instruction after the other (~12 ns each, tools/atomic_rate_bench.hip): one counter bumped once per read or
@@ -383,7 +418,7 @@ PSVR_HDN inline void prep_read(const Ctx &c, long long read)
 	c.hcnt[read] = 0;
 	c.n_ccand[read] = 0;
 	for (int s = 0; s < 2; ++s) { Strand &st = c.strand[read * 2 + s]; st.mem_n = st.us_n = 0; st.mem_off = st.us_off = 0; st.seed_hash = st.chain_hash = 1469598103934665603ULL; }
-	if (L > kMaxReadLen || L < kLenKmer) { c.active[read] = 0; if (L > kMaxReadLen) *c.err = 1; return; }
+	if (L > kMaxReadLen || L < kLenKmer) { c.active[read] = 0; if (L > kMaxReadLen) *c.err = kErrReadTooLong; return; }
 	if (!unm && o.align_score == (uint32_t)(L * c.par.match)) { c.active[read] = 0; return; }   // rr.cpp:414
 	c.active[read] = 1;
 	const char *s = c.bases + c.base_off[sr];
@@ -399,7 +434,7 @@ PSVR_HDN inline void prep_read(const Ctx &c, long long read)
 			long long k = ro + draws - c.grand_base;
 			int32_t r;
 			if (c.force && draws < (int)c.force[4 * read]) r = c.force[4 * read + 1 + draws];
-			else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = 2, 0);
+			else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = kErrRandWindow, 0);
 			ch = "ACGT"[r % 4];
 			++draws;
 		}
@@ -825,7 +860,7 @@ PSVR_HDN inline void chain_strand(const Ctx &c, long long rs, int &hdraw_total)
 				uint32_t m = k;
 				if (sample) {
 					long long q = hro + hdraw - c.hrand_base[read & 1];
-					int32_t rv = (q >= 0 && q < c.hrand_n) ? c.hrand[read & 1][q] : (*c.err = 3, 0);
+					int32_t rv = (q >= 0 && q < c.hrand_n) ? c.hrand[read & 1][q] : (*c.err = kErrRandomRWindow, 0);
 					m = (uint32_t)rv % u.pos_n;
 					++hdraw;
 				}
@@ -956,7 +991,7 @@ PSVR_HD int sort_output(const Ctx &c, const Strand &st, int direction, ChainCand
 		if (max_index == 0xffffffffu) return 0;
 		if (same > 1) {                      // pick same_top[rand() % same]: entry 0 is the first maximum found (or the sentinel)
 			long long k = ro + draws - c.grand_base;
-			int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = 2, 0);
+			int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = kErrRandWindow, 0);
 			++draws;
 			uint32_t pick = (uint32_t)r % same;
 			// rebuild the list order: [first maximum (descending scan), then every later index with dist == max]
@@ -1155,7 +1190,7 @@ PSVR_HDN inline bool chain_select_small(const Ctx &c, long long read)
 			if (maxi < 0) break;
 			if (same > 1) {
 				const long long k = ro + draws - c.grand_base;
-				const int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = 2, 0);
+				const int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = kErrRandWindow, 0);
 				++draws;
 				const uint32_t pick = (uint32_t)r % (uint32_t)same;
 				uint32_t seen = 0;
@@ -1477,7 +1512,7 @@ PSVR_HDN inline int walk_candidate(const Ctx &c, long long read, int k, long lon
 	w.read_score -= sk.unitig_mis * (c.par.match + c.par.mismatch);
 	CandWork &cw = c.cw.base[cwi];
 	cw.read = (int32_t)read, cw.k = k, cw.n_seg = w.n_seg, cw.read_score = w.read_score, cw.rba = sk.rba, cw.bad = w.bad, cw.seg_off = so;
-	if (w.bad) *c.err = 10 + w.bad;
+	if (w.bad) *c.err = kErrWalk + w.bad;
 	stat_add(c, ST_CAND, 1);
 	if (w.last_seg) last.seg = w.last_seg, last.q_st = w.last_q_st, last.qlen = w.last_qlen, last.ref_st = w.last_ref_st, last.tlen = w.last_tlen, last.type = w.last_type, last.strand = w.last_strand;
 	return w.n_dp;
@@ -1534,7 +1569,7 @@ PSVR_HD void walk_number_dp(const Ctx &c, long long read, const WalkRead &wr, lo
 		Seg *seg = c.seg.base + so;
 		for (int i = 0; i < cw.n_seg; ++i) {
 			if (seg[i].kind != 1) continue;
-			if (id0 < 0) { c.cw.base[cw0 + k].bad = 1; *c.err = 11; seg[i].a = 0; continue; }
+			if (id0 < 0) { c.cw.base[cw0 + k].bad = 1; *c.err = kErrPieceId; seg[i].a = 0; continue; }
 			DpDesc &d = c.dp.base[id0 + seg[i].a];
 			const ChainCand &cc = c.ccand[read * 12 + k];
 			d.read = (int32_t)read, d.strand = cc.direction == kRev, d.q_st = seg[i + 1].a, d.qlen = seg[i + 1].b, d.ref_st = (uint32_t)seg[i + 2].a, d.tlen = seg[i + 2].b;
@@ -1645,7 +1680,7 @@ PSVR_HD void assemble_store(const Ctx &c, long long cwi, const AsmResult &ar, lo
 		pc.n_cigar = (uint32_t)m, pc.cigar_off = co;
 	}
 	c.cand[cwi] = pc;
-	if (bad) *c.err = 20;   // the reference would xassert (abort) or print "ERROR cigar"
+	if (bad) *c.err = kErrScratch;   // the reference would xassert (abort) or print "ERROR cigar"
 }
 PSVR_HDN inline void assemble_candidate(const Ctx &c, long long cwi)
 {
@@ -1836,7 +1871,7 @@ PSVR_HD void pair_reads(const Ctx &c, long long pair, psvr_read_hdr_t &h0, psvr_
 			else {
 				max_same++;
 				long long k = ro + draws - c.grand_base;
-				int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = 2, 0);
+				int32_t r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = kErrRandWindow, 0);
 				++draws;
 				if (r % max_same != 0) st = false;
 			}
@@ -2056,7 +2091,7 @@ PSVR_HD void run_init_slot(const RunInit &r, long long s)
 	if (s < r.nsp) r.sp_class[s] = 0, r.sp_adopted[s] = -1, r.sp_adopted_at[s] = -1;
 	if (s < r.n_tops) r.tops[s] = 0;
 	if (s < r.n_atops) r.atops[s] = 0;
-	if (s < 16) { r.flags[s] = 0; if (r.stats) r.stats[s] = 0; }
+	if (s < kFlagWords) { r.flags[s] = 0; if (r.stats) r.stats[s] = 0; }
 	if (s == 0) *r.mem_top = r.mem0;
 }
 
@@ -2099,7 +2134,7 @@ PSVR_HDN inline int adopt_auto(const Ctx &c, const SpecialPair &sp, const long l
 {
 	const long long t = noff[sp.pair];
 	const long long slot = special_slot_at(c, sp, t);
-	if (slot < 0) { *c.err = 2; return 0; }
+	if (slot < 0) { *c.err = kErrRandWindow; return 0; }
 	const int32_t *vc = c.rcnt + 3 * slot;
 	const int32_t had = *adopted;
 	const long long had_at = *adopted_at;

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_prep(Ctx c, const int32_t *work, lon
 	bool act = !(L > kMaxReadLen || L < kLenKmer) && !(!unm && o_score == (uint32_t)(L * c.par.match));
 	if (lane == 0) {
 		c.read_l[read] = L, c.unmapped[read] = unm, c.is_str[read] = 0, c.has_mem[read] = 0, c.hcnt[read] = 0, c.n_ccand[read] = 0, c.active[read] = act;
-		if (L > kMaxReadLen) *c.err = 1;
+		if (L > kMaxReadLen) *c.err = kErrReadTooLong;
 	}
 	if (lane < 2) { Strand &st = c.strand[read * 2 + lane]; st.mem_n = st.us_n = 0; st.mem_off = st.us_off = 0; st.seed_hash = st.chain_hash = 1469598103934665603ULL; }
 	if (!act) { if (lane == 0) c.rcnt[item] = 0; continue; }
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kBlock) void k_prep(Ctx c, const int32_t *work, lon
 			long long k = ro + d - c.grand_base;
 			int32_t r;
 			if (c.force && d < (int)c.force[4 * read]) r = c.force[4 * read + 1 + d];
-			else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = 2, 0);
+			else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (*c.err = kErrRandWindow, 0);
 			ch = "ACGT"[r % 4];
 		}
 		draws += __popcll(m);
@@ -320,7 +320,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_pair(Ctx c, const int32_t *work,
 						const long long k = ro + draws - c.grand_base;
 						int32_t r;
 						if (c.force && draws < (int)c.force[4 * read]) r = c.force[4 * read + 1 + draws];
-						else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (err = 2, 0);
+						else r = (k >= 0 && k < c.grand_n) ? c.grand[k] : (err = kErrRandWindow, 0);
 						ch = "ACGT"[r % 4];
 						++draws;
 					}
@@ -888,12 +888,12 @@ __global__ void k_hoff_shadows(Ctx c, long long P, long long n)
 	for (int k = 0; k < 2; ++k) c.hoff[2 * (P + j) + k] = c.hoff[2 * (long long)c.src[P + j] + k];
 }
 // total draws of the evaluated slots; a real pair whose total changed since its previous evaluation is count-sensitive
-// cnt[1] is set when a slot's rand() or random_r draw counts differ from its previous evaluation's
+// cnt = the block's word kTopNewSens; the word kTopChanged behind it is set when a slot's rand() or random_r draw counts differ from its previous evaluation's
 __device__ __forceinline__ void totals_of(const Ctx &c, long long s, int32_t *ctot, int32_t *hprev, uint8_t *sens, int32_t *slist, unsigned long long *cnt, int detect)
 {
 	int32_t t = c.rcnt[3 * s] + c.rcnt[3 * s + 1] + c.rcnt[3 * s + 2];
 	const int32_t h0 = c.hcnt[2 * s], h1 = c.hcnt[2 * s + 1];
-	if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[1] = 1;
+	if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[kTopChanged - kTopNewSens] = 1;
 	if (detect && s < c.n_pairs && t != ctot[s] && !sens[s]) { sens[s] = 1; slist[atomicAdd(cnt, 1ull)] = (int32_t)s; }
 	ctot[s] = t, hprev[2 * s] = h0, hprev[2 * s + 1] = h1;
 }
@@ -910,7 +910,7 @@ __global__ void k_totals(Ctx c, const int32_t *work, long long n, int32_t *ctot,
 	long long s = pair_of(work, i);
 	int32_t t = c.rcnt[3 * s] + c.rcnt[3 * s + 1] + c.rcnt[3 * s + 2];
 	const int32_t h0 = c.hcnt[2 * s], h1 = c.hcnt[2 * s + 1];
-	if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[1] = 1;
+	if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[kTopChanged - kTopNewSens] = 1;
 	if (detect && s < c.n_pairs && t != ctot[s] && !sens[s]) { sens[s] = 1; slist[atomicAdd(cnt, 1ull)] = (int32_t)s; }
 	ctot[s] = t, hprev[2 * s] = h0, hprev[2 * s + 1] = h1;
 }
@@ -937,7 +937,7 @@ struct DpPlanRec {                 // the plan record: one contiguous readback
 	unsigned long long verdict;              // 0: placed; kDpGrow* bits: that buffer is too small, nothing was placed; kDpFull: an arena overflowed
 	unsigned long long tot_q, tot_t, tot_p, tot_c, ws_bytes, seq_bytes;   // bytes of the padded sequences, slab units of 256 B, CIGAR words, team scratch, query + target bases
 	unsigned long long pad[6];
-	int32_t flags[16];
+	int32_t flags[kFlagWords];               // the flag block as the round left it
 	unsigned long long team_cnt[16], qmax[16];                            // per team-kernel class: problems, longest query
 	unsigned long long cnt[kDpPlanTeam0];                                 // per (kind, class) of the wavefront / tiny kernels
 };
@@ -963,8 +963,8 @@ struct DpPlanDev {
 __device__ __forceinline__ long long dp_round_n(const Ctx &c, long long dp_done, bool &full)
 {
 	const unsigned long long top = *c.dp.top, cw = *c.cw.top;
-	const int *fl = c.mem.overflow;                              // the flag words: mem, us, seg, dp, cw
-	full = top > c.dp.cap || cw > c.cw.cap || fl[0] || fl[1] || fl[2] || fl[3] || fl[4];
+	const int *fl = c.mem.overflow - kFlagMem;                   // the flag block (aln_device.h FlagWord)
+	full = top > c.dp.cap || cw > c.cw.cap || fl[kFlagMem] || fl[kFlagUs] || fl[kFlagSeg] || fl[kFlagDp] || fl[kFlagCw];
 	return full || (long long)top <= dp_done ? 0 : (long long)top - dp_done;
 }
 static const int kDpPlanGrid = 1024;       // workgroups of k_dp_plan and k_dp_scatter, whatever the round holds
@@ -1078,7 +1078,7 @@ __global__ __launch_bounds__(kBlock) void k_dp_plan_starts(Ctx c, long long dp_d
 		team_cnt[threadIdx.x] = tc;
 		wk.rec.team_cnt[threadIdx.x] = tc, wk.rec.qmax[threadIdx.x] = wk.qmax[threadIdx.x];
 	}
-	if (threadIdx.x < 16) wk.rec.flags[threadIdx.x] = c.mem.overflow[threadIdx.x];
+	if (threadIdx.x < kFlagWords) wk.rec.flags[threadIdx.x] = (c.mem.overflow - kFlagMem)[threadIdx.x];
 	__syncthreads();
 	if (threadIdx.x == 0) {
 		// scratch of the team kernel: a wavefront's slice is sized by its class's longest query
@@ -1521,7 +1521,7 @@ struct GpuBE {
 	void run_init(const RunInit &r)
 	{
 		long long n = r.S;
-		for (long long k : {r.nsp, (long long)r.n_tops, (long long)r.n_atops, 16ll}) if (k > n) n = k;
+		for (long long k : {r.nsp, (long long)r.n_tops, (long long)r.n_atops, (long long)kFlagWords}) if (k > n) n = k;
 		hipLaunchKernelGGL(k_run_init, dim3(grid_for(n)), dim3(kBlock), 0, stream, r);
 		note(hipGetLastError());
 	}
@@ -1682,7 +1682,7 @@ struct GpuBE {
 			PSVR_HIP(pslab.ensure((size_t)(r.tot_p << 8) + 256));
 			PSVR_HIP(strip_ws.ensure((size_t)r.ws_bytes + 256));
 		}
-		memcpy(fl, plan_rec.flags, 64);
+		memcpy(fl, plan_rec.flags, sizeof plan_rec.flags);
 		dp_end = (long long)plan_rec.dp_top, cw_end = (long long)plan_rec.cw_top;
 		return PSVR_OK;
 	}

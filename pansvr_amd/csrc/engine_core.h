@@ -252,14 +252,14 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 	long long V = 0;                                 // variant slots [P, P+V)
 	long long S = 0;                                 // slots = P real pairs + V variants + window-shadow capacity
 	static const int kWin = 32;                      // offsets evaluated per sensitive pair and round
-	Dev<unsigned long long> d_tops;           // [16] dirty counts, totals counters
+	Dev<unsigned long long> d_tops;           // the rounds' counters (aln_device.h TopWord)
 	// the six arena tops, each in a cache line of its own (kTopStride words apart): a wavefront's atomic on a line costs ~12 ns however many
 	// lanes take part, and atomics on one line are served one after the other (tools/atomic_rate_bench.hip) -- three counters that the
 	// walk bumps per read shared one line
 	static constexpr int kTopStride = kArenaTopStride * kArenaMaxShards;   // words between two arenas' first counters
 	Dev<unsigned long long> d_atops;
-	Dev<int32_t> d_flags;                     // [8] six overflow flags, the error word, [7] stale_open (aln_device.h stale_compare)
-	unsigned long long cap_mem = 0, cap_us = 0, cap_seg = 0, cap_dp = 0, cap_cw = 0, cap_cig = 0;
+	Dev<int32_t> d_flags;                     // the arenas' overflow flags and the stages' sticky words (aln_device.h FlagWord)
+	unsigned long long cap[kArenaFlags] = {};        // the arenas' capacities, by their flag's name
 	DpIO dp;
 	struct { Dev<int32_t> qlen, tlen; Dev<long long> q_off, t_off; Dev<uint8_t> qbuf, tbuf; Dev<psvr_extz_t> ez; Dev<uint32_t> cig; } dpb;   // behind dp
 	long long dp_cap_q = 0, dp_cap_t = 0, dp_cap_c = 0, dp_cap_n = 0;
@@ -287,13 +287,21 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		grand_pos = 2;
 	}
 
-	bool upload_rand(long long need_g, long long need_h)
+	// PSVR_RAND_SHRINK=<n>: a window sized for a run holds 1/n of its entries, so that a small input walks through the "draw window
+	// exhausted -> extend -> run the batch again" path (tests); the extension itself is not shrunk
+	static long long shrunk_window(long long n, bool extension)
+	{
+		const char *e = extension ? nullptr : getenv("PSVR_RAND_SHRINK");
+		const long long f = e ? atoll(e) : 0;
+		return f > 1 ? n / f + 64 : n;
+	}
+	bool upload_rand(long long need_g, long long need_h, bool extension = false)
 	{
 		// entries beyond what this run needs: room for the position to move before the window is uploaded again (a batch of 1 M pairs needs a
 		// window of 4.7 M and draws ~0.4 M times: forty batches; small inputs stay small)
 		const long long margin_h = 1 << 20, margin = std::max<long long>(margin_h, 4 * need_g);
 		if (!(d_grand && grand_pos >= grand_dev_base && grand_pos + need_g <= grand_dev_base + grand_dev_n)) {
-			const long long n = need_g + need_g / 2 + 4096 + margin;
+			const long long n = shrunk_window(need_g + need_g / 2 + 4096 + margin, extension);
 			grand.ensure(grand_pos + n);
 			if (n > grand_dev_cap || !d_grand) {
 				if (!get(d_grand, n)) return false;
@@ -305,7 +313,7 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		bool hok = d_hrand[0] && d_hrand[1];
 		for (int k = 0; k < 2 && hok; ++k) hok = hrand_pos[k] >= hrand_dev_base[k] && hrand_pos[k] + need_h <= hrand_dev_base[k] + hrand_dev_n;
 		if (!hok) {
-			const long long n = need_h + need_h / 2 + 4096 + margin_h;
+			const long long n = shrunk_window(need_h + need_h / 2 + 4096 + margin_h, extension);
 			for (int k = 0; k < 2; ++k) {
 				hrand[k].ensure(hrand_pos[k] + n);
 				if ((n > hrand_dev_cap || !d_hrand[k]) && !get(d_hrand[k], n)) return false;
@@ -432,27 +440,27 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 			get(d_vsrc, S), get(d_spidx, nsp);
 			get(d_special, nsp), get(d_sp_class, nsp), get(d_sp_adopted, nsp), get(d_sp_adopted_at, nsp);
 		}
-		get(d_tops, 64), get(d_atops, 6 * kTopStride), get(d_flags, 16);
+		get(d_tops, kTopWords), get(d_atops, kArenaFlags * kTopStride), get(d_flags, kFlagWords);
 		const long long R2 = RS;
-		cap_mem = (unsigned long long)2 * R2 * kMemSlot + (unsigned long long)R2 * 16 + 4096;
-		cap_us = (unsigned long long)R2 * 48 + 65536;
-		cap_cw = (unsigned long long)R2 * 3 + 1024;
-		cap_seg = cap_cw * 16;
-		cap_dp = (unsigned long long)R2 * 4 + 1024;
-		cap_cig = (unsigned long long)R2 * 48 + 4096;
+		cap[kFlagMem] = (unsigned long long)2 * R2 * kMemSlot + (unsigned long long)R2 * 16 + 4096;
+		cap[kFlagUs] = (unsigned long long)R2 * 48 + 65536;
+		cap[kFlagCw] = (unsigned long long)R2 * 3 + 1024;
+		cap[kFlagSeg] = cap[kFlagCw] * 16;
+		cap[kFlagDp] = (unsigned long long)R2 * 4 + 1024;
+		cap[kFlagCig] = (unsigned long long)R2 * 48 + 4096;
 		// PSVR_ARENA_SHRINK=<n>: start with 1/n of the scratch arenas, so that a small input walks through the overflow -> grow -> re-run
 		// path of every arena (tests)
 		if (const char *e = getenv("PSVR_ARENA_SHRINK")) {
 			const unsigned long long n = (unsigned long long)atoll(e);
 			if (n > 1) {
-				for (unsigned long long *cap : {&cap_us, &cap_cw, &cap_seg, &cap_dp, &cap_cig}) *cap = *cap / n + 64;
+				for (int a : {kFlagUs, kFlagCw, kFlagSeg, kFlagDp, kFlagCig}) cap[a] = cap[a] / n + 64;
 				const unsigned long long slots = (unsigned long long)2 * R2 * kMemSlot;    // fixed per-strand slots: only the bump region behind them shrinks
-				cap_mem = slots + (cap_mem - slots) / n + 64;
+				cap[kFlagMem] = slots + (cap[kFlagMem] - slots) / n + 64;
 			}
 		}
 		c.stats = get(cb.stats, 16);
 		if (!alloc_ok || !alloc_arenas()) { cap_S = 0; err = "device allocation failed"; return PSVR_ERR_NOMEM; }
-		c.err = d_flags + 6, c.stale_open = d_flags + 7, c.any_h = d_flags + 8;
+		c.err = d_flags + kFlagErr, c.stale_open = d_flags + kFlagStaleOpen, c.any_h = d_flags + kFlagAnyH;
 		upload_variants();
 		return PSVR_OK;
 	}
@@ -494,27 +502,40 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 	bool alloc_arenas()
 	{
 		alloc_ok = true;
-		c.mem.base = get(cb.mem, cap_mem), c.us.base = get(cb.us, cap_us), c.path = get(cb.path, cap_us);
-		c.seg.base = get(cb.seg, cap_seg), c.dp.base = get(cb.dp, cap_dp), c.cw.base = get(cb.cw, cap_cw), c.cig.base = get(cb.cig, cap_cig);
-		c.cand = get(cb.cand, cap_cw);       // candidate records share the CandWork arena's indices
-		c.mem.top = d_atops + 0 * kTopStride, c.us.top = d_atops + 1 * kTopStride, c.seg.top = d_atops + 2 * kTopStride, c.dp.top = d_atops + 3 * kTopStride, c.cw.top = d_atops + 4 * kTopStride, c.cig.top = d_atops + 5 * kTopStride;
-		c.mem.cap = cap_mem, c.us.cap = cap_us, c.seg.cap = cap_seg, c.dp.cap = cap_dp, c.cw.cap = cap_cw, c.cig.cap = cap_cig;
-		c.mem.nshard = c.dp.nshard = c.cw.nshard = c.cig.nshard = 1;          // mem: fixed slots in front; dp, cw: their ids are ranges the host plans on; cig: downloaded as one piece
-		c.us.nshard = c.seg.nshard = BE::kArenaShards;
-		c.mem.overflow = d_flags + 0, c.us.overflow = d_flags + 1, c.seg.overflow = d_flags + 2, c.dp.overflow = d_flags + 3, c.cw.overflow = d_flags + 4, c.cig.overflow = d_flags + 5;
+		// an arena's storage, and its counter, capacity and overflow flag at its place (FlagWord) in d_atops, cap[] and d_flags
+		// nshard 1: mem has fixed slots in front; dp, cw: their ids are ranges the host plans on; cig: downloaded as one piece
+		auto place = [&](auto &a, auto &buf, int w, unsigned int nshard) {
+			a.base = get(buf, cap[w]), a.top = d_atops + w * kTopStride, a.cap = cap[w], a.overflow = d_flags + w, a.nshard = nshard;
+		};
+		place(c.mem, cb.mem, kFlagMem, 1), place(c.us, cb.us, kFlagUs, BE::kArenaShards), c.path = get(cb.path, cap[kFlagUs]);
+		place(c.seg, cb.seg, kFlagSeg, BE::kArenaShards), place(c.dp, cb.dp, kFlagDp, 1), place(c.cw, cb.cw, kFlagCw, 1), place(c.cig, cb.cig, kFlagCig, 1);
+		c.cand = get(cb.cand, cap[kFlagCw]);       // candidate records share the CandWork arena's indices
 		return alloc_ok;
 	}
-	// a scratch arena overflowed (repeat-rich reads expand to many seeds): grow it 4x and run the batch again
-	int grow_and_rerun(const int32_t *flags, int trace, bool want_stats, int depth)
+	// which arenas filled up in a round, by their flag's name: what run_slots and the round end report and grow_arenas takes
+	struct ArenaFull {
+		int32_t flag[kArenaFlags] = {};
+		bool any() const { int a = 0; for (int32_t f : flag) a |= f; return a != 0; }
+	};
+	// a scratch arena overflowed (repeat-rich reads expand to many seeds): grow it 4x; the caller runs the batch again
+	int grow_arenas(const ArenaFull &full)
 	{
-		if (depth > 8) { err = "scratch arena overflow persists after 8 growth steps"; return PSVR_ERR_OVERFLOW; }
-		unsigned long long *caps[6] = {&cap_mem, &cap_us, &cap_seg, &cap_dp, &cap_cw, &cap_cig};
-		for (int k = 0; k < 6; ++k) if (flags[k]) *caps[k] *= 4;
-		if (flags[0]) cap_mem += (unsigned long long)4 * S * kMemSlot;
-		fprintf(stderr, "[psvr] scratch arena overflow (mem %d us %d seg %d dp %d cand %d cigar %d): growing 4x and re-running the batch\n", flags[0], flags[1], flags[2], flags[3],
-		        flags[4], flags[5]);
+		for (int a = 0; a < kArenaFlags; ++a) if (full.flag[a]) cap[a] *= 4;
+		if (full.flag[kFlagMem]) cap[kFlagMem] += (unsigned long long)4 * S * kMemSlot;
+		fprintf(stderr, "[psvr] scratch arena overflow (mem %d us %d seg %d dp %d cand %d cigar %d): growing 4x and re-running the batch\n", full.flag[kFlagMem], full.flag[kFlagUs],
+		        full.flag[kFlagSeg], full.flag[kFlagDp], full.flag[kFlagCw], full.flag[kFlagCig]);
 		if (!alloc_arenas()) { cap_S = 0; err = "device allocation failed while growing arenas"; return PSVR_ERR_NOMEM; }
-		return run(trace, want_stats, depth + 1);
+		return PSVR_OK;
+	}
+	// a stage asked for a draw beyond the device's window of a stream: a window four times as long; the caller runs the batch again
+	int extend_rand_window(int stage_err)
+	{
+		fprintf(stderr, "[psvr] draw window exhausted (%s, %lld rand() and %lld random_r entries): extending and re-running the batch\n", stage_err == kErrRandWindow ? "rand()" : "random_r",
+		        c.grand_n, c.hrand_n);
+		be.dzero(d_flags, kFlagWords * sizeof(int32_t));
+		grand_dev_n = hrand_dev_n = 0;
+		if (!upload_rand(c.grand_n * 4, c.hrand_n * 4, true)) { err = "rand table allocation failed"; return PSVR_ERR_NOMEM; }
+		return PSVR_OK;
 	}
 
 	// the DP stage's buffers for n problems and qb / tb / cw bytes and CIGAR words: grown to need + need / 4 + 1024 when a round needs more
@@ -537,7 +558,8 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 	// the stages of one round over a list of slots: mate 0, then mate 1 (continues mate 0's draws), then the
 	// candidate / DP / pairing stages
 	// `nwalk`: entries behind the first nwork of `work` that go on from the walk (their chain selection has been repeated already, k_reselect)
-	int run_slots(const int32_t *work, long long nwork, long long &dp_done, long long &cw_done, long long nwalk = 0)
+	// `full`: the arenas that filled up; the round has ended behind the walk then (PSVR_OK all the same) and the batch must run again
+	int run_slots(const int32_t *work, long long nwork, long long &dp_done, long long &cw_done, long long nwalk, ArenaFull &full)
 	{
 		if (nwork + nwalk <= 0) return PSVR_OK;
 		for (int mate = 0; mate < 2; ++mate) {
@@ -547,7 +569,7 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 			be.st_chain(c, work, nwork, mate);
 		}
 		be.st_walk(c, work, nwork + nwalk);
-		int32_t fl[16];
+		int32_t fl[kFlagWords];
 		long long dp_end, cw_end;
 		if constexpr (plans_on_device<BE>::value) {
 			// the DP stage is planned and placed on the device behind the walk: the queue tops and the flags come back with the plan, the
@@ -555,18 +577,18 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 			int rc = be.st_dp_plan(*this, dp_done, dp_end, cw_end, fl);
 			if (rc) return rc;
 		} else {
-			unsigned long long tops[kTopStride + 1];                         // from the dp counter to the cw counter
-			mem.d2h({{tops, d_atops + 3 * kTopStride, sizeof tops}, {fl, d_flags, 64}});
-			dp_end = (long long)tops[0], cw_end = (long long)tops[kTopStride];
+			constexpr int first = kFlagDp * kTopStride, dp_at = 0, cw_at = kFlagCw * kTopStride - first;   // one readback from the dp counter to the cw counter
+			unsigned long long tops[cw_at + 1];
+			mem.d2h({{tops, d_atops + first, sizeof tops}, {fl, d_flags, sizeof fl}});
+			dp_end = (long long)tops[dp_at], cw_end = (long long)tops[cw_at];
 		}
-		if (fl[8]) any_h = true;
-		if (fl[7]) stats.stale_open = 1;
+		note_sticky_flags(fl);
 		// An arena that filled up in the stages so far ends the round here: what follows (assembly, the reads' tails) would walk records
-		// that were never written.  Bits: 1 dp, 2 cw, 4 seg, 8 us, 16 mem.
-		{
-			const int full = (dp_end > (long long)cap_dp || fl[3] ? 1 : 0) | (cw_end > (long long)cap_cw || fl[4] ? 2 : 0) | (fl[2] ? 4 : 0) | (fl[1] ? 8 : 0) | (fl[0] ? 16 : 0);
-			if (full) return -1000 - full;
-		}
+		// that were never written.  (The CIGAR arena is filled by the assembly: the round end sees that one.)
+		for (int a : {kFlagMem, kFlagUs, kFlagSeg, kFlagDp, kFlagCw}) full.flag[a] = fl[a] != 0;
+		if (dp_end > (long long)cap[kFlagDp]) full.flag[kFlagDp] = 1;
+		if (cw_end > (long long)cap[kFlagCw]) full.flag[kFlagCw] = 1;
+		if (full.any()) return PSVR_OK;
 		if (dp_end > dp_done) {
 			dp.begin = dp_done, dp.end = dp_end;
 			int rc = be.st_dp(*this);
@@ -578,6 +600,12 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		dp_done = dp_end, cw_done = cw_end;
 		be.st_finalize_pair(c, work, nwork + nwalk);       // both reads' tails, then the pairing, by the same worker: the records stay close
 		return PSVR_OK;
+	}
+	// the words of a flag readback that only ever go up during a run
+	void note_sticky_flags(const int32_t *fl)
+	{
+		if (fl[kFlagAnyH]) any_h = true;
+		if (fl[kFlagStaleOpen]) stats.stale_open = 1;
 	}
 
 	// ---- one full run of the uploaded batch (rand state is NOT advanced: call commit() for that)
@@ -645,14 +673,73 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 	bool have_run = false;
 	bool any_h = false;                               // a read of this batch has drawn from random_r
 
-	int run(int trace, bool want_stats, int depth = 0)
+	// The device statistics pointer is null during a run without statistics (the stages then count nothing); back in place when the run is
+	// over, however it ends.
+	struct StatsOff {
+		Ctx &c;
+		unsigned long long *keep;
+		StatsOff(Ctx &ctx, bool want_stats) : c(ctx), keep(ctx.stats) { if (!want_stats) c.stats = nullptr; }
+		~StatsOff() { c.stats = keep; }
+		StatsOff(const StatsOff &) = delete;
+		StatsOff &operator=(const StatsOff &) = delete;
+	};
+
+	// What one pass of iterate() hands to the next, and what the phases of a pass hand to each other.
+	struct Round {
+		// the next evaluation: d_work holds nfull dirty real pairs, then nshadow shadow slots, then nwalk pairs that go on from the walk;
+		// d_workp the npair_only pairs that only repeat their pairing stage
+		const int32_t *work = nullptr;                    // nullptr = identity: round 1 runs every real pair and every variant slot
+		long long nfull = 0, npair_only = 0, nshadow = 0, nwalk = 0;
+		bool pair_done = false;                           // the pairing-only list has run (behind the round end that made it, its length still on the device)
+		bool pre_tot = false;                             // ... and its totals were taken right behind it (they sit in the words kTopNewSens, kTopChanged and in d_slist)
+		std::vector<int32_t> sh_src;                      // the shadow slots of that evaluation: pair ...
+		std::vector<long long> sh_off;                    // ... and offset
+		bool resume = false;                              // a rebase: the first pass evaluates nothing and starts at the offsets; the random_r scans run in every pass
+		// the pass in hand
+		bool gathered = false;                            // the walk's list has been built and gathered behind the totals (first round)
+		bool h_scans = false;                             // the random_r offsets were scanned (d_nhoff is valid)
+		unsigned long long nnew = 0, changed = 0;         // read_totals: newly count-sensitive pairs; did any evaluated slot draw a different number than last time?
+		unsigned long long tops[kTopReadEnd - kTopReadFirst];   // end_round's readback of the counters ...
+		int32_t flags[kFlagWords];                               // ... and of the flag block
+		unsigned long long top(int word) const { return tops[word - kTopReadFirst]; }
+		ArenaFull full;                                   // verdict kGrowArenas: which
+		int rc = PSVR_OK;                                 // verdict kFailed: why (with `err`)
+	};
+	enum Verdict { kNextRound, kDone, kGrowArenas, kExtendWindow, kFailed };
+
+	// A run and its restarts: set up, iterate, and when an arena or a draw window was too small enlarge it and run the batch again.
+	// `restarts`: how many a caller has used up already (rebase).
+	int run(int trace, bool want_stats, int restarts = 0)
 	{
-		stats = RunStats();
-		c.trace = trace;
-		if (P == 0) return PSVR_OK;
-		unsigned long long *stats_ptr = c.stats;
-		if (!want_stats) c.stats = nullptr;
-		if (!upload_rand(total_bases / 64 + 4096, 4096)) { err = "rand table allocation failed"; c.stats = stats_ptr; return PSVR_ERR_NOMEM; }
+		for (;; ++restarts) {
+			stats = RunStats();
+			c.trace = trace;
+			if (P == 0) return PSVR_OK;
+			Round r;
+			Verdict v;
+			{
+				StatsOff quiet(c, want_stats);
+				if (!upload_rand(total_bases / 64 + 4096, 4096)) { err = "rand table allocation failed"; return PSVR_ERR_NOMEM; }
+				begin_run();
+				r.nfull = P + V;
+				v = iterate(r, want_stats);
+			}
+			if (v != kGrowArenas && v != kExtendWindow) return r.rc;
+			const int rc = prepare_restart(v, r, restarts);
+			if (rc) return rc;
+		}
+	}
+	// what a grow or an extend verdict asks for before the batch runs again
+	int prepare_restart(Verdict v, const Round &r, int restarts)
+	{
+		if (restarts > 8) {
+			err = v == kGrowArenas ? "scratch arena overflow persists after 8 growth steps" : "draw window exhausted again after 8 restarts of the batch";
+			return PSVR_ERR_OVERFLOW;
+		}
+		return v == kGrowArenas ? grow_arenas(r.full) : extend_rand_window(r.flags[kFlagErr]);
+	}
+	void begin_run()
+	{
 		// initial guess: nobody draws.  One pass over the slots: poff = grand_pos, hoff = the two random_r positions, rcnt = hcnt = ctot = hprev =
 		// sens = mask = 0, src = identity (the variant slots: their pair); the special pairs' classes and adoptions; the counters, flags and
 		// statistics; the bump region's start behind the per-strand MEM slots -- a dozen fills, copies and memsets of their own were 0.1 ms per run.
@@ -662,7 +749,7 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 			ri.S = S, ri.P = P, ri.V = V, ri.g = grand_pos, ri.h0 = hrand_pos[0], ri.h1 = hrand_pos[1];
 			ri.vsrc = d_vsrc, ri.spidx = d_spidx, ri.nsp = (long long)special.size();
 			ri.sp_class = d_sp_class, ri.sp_adopted = d_sp_adopted, ri.sp_adopted_at = d_sp_adopted_at;
-			ri.tops = d_tops, ri.n_tops = 16, ri.atops = d_atops, ri.n_atops = 6 * kTopStride, ri.flags = d_flags, ri.stats = stats_ptr;
+			ri.tops = d_tops, ri.n_tops = kTopRunInit, ri.atops = d_atops, ri.n_atops = kArenaFlags * kTopStride, ri.flags = d_flags, ri.stats = cb.stats;   // (the statistics are cleared whether or not this run counts)
 			ri.mem_top = c.mem.top, ri.mem0 = (unsigned long long)4 * S * kMemSlot;   // bump region starts behind the per-strand slots
 			be.run_init(ri);
 		}
@@ -675,8 +762,6 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		hw_rows.clear(), sp_row0.assign(special.size(), -1);
 		adopted.assign(special.size(), -1), adopted_at.assign(special.size(), -1), adopt_pair.clear(), adopt_slot.clear();
 		have_run = true;
-		int rc = iterate(trace, want_stats, depth, stats_ptr, false);
-		return rc;
 	}
 
 	// The streams of this batch start somewhere else than assumed (another rank's shard precedes it): move every offset
@@ -687,291 +772,350 @@ template <class BE, class Mem = HostMem> struct EngineCore {
 		if (!have_run || P == 0) { grand_pos = g, hrand_pos[0] = h0, hrand_pos[1] = h1; return PSVR_OK; }
 		if (g == grand_pos && h0 == hrand_pos[0] && h1 == hrand_pos[1]) return PSVR_OK;
 		grand_pos = g, hrand_pos[0] = h0, hrand_pos[1] = h1;
-		unsigned long long *stats_ptr = c.stats;
-		if (!want_stats) c.stats = nullptr;
-		if (!upload_rand(total_bases / 64 + 4096, 4096)) { err = "rand table allocation failed"; c.stats = stats_ptr; return PSVR_ERR_NOMEM; }
-		for (Win &w : wins) w.off.clear(), w.tot.clear(), w.eval_off = -1;
-		return iterate(trace, want_stats, 0, stats_ptr, true);
+		Round r;
+		Verdict v;
+		{
+			StatsOff quiet(c, want_stats);
+			if (!upload_rand(total_bases / 64 + 4096, 4096)) { err = "rand table allocation failed"; return PSVR_ERR_NOMEM; }
+			for (Win &w : wins) w.off.clear(), w.tot.clear(), w.eval_off = -1;
+			r.resume = true;
+			v = iterate(r, want_stats);
+		}
+		if (v != kGrowArenas && v != kExtendWindow) return r.rc;
+		// too small an arena or window: a full run from the new position
+		const int rc = prepare_restart(v, r, 0);
+		return rc ? rc : run(trace, want_stats, 1);
 	}
 
-	int iterate(int trace, bool want_stats, int depth, unsigned long long *stats_ptr, bool resume)
+	// The rounds: evaluate the slots of the round, read their totals, walk the offsets on the host, mark what is dirty, plan the next round.
+	Verdict iterate(Round &r, bool want_stats)
 	{
-		int rc = PSVR_OK;
-		long long nfull = resume ? 0 : P + V, npair_only = 0, nshadow = 0, nwalk = 0;
-		const int32_t *work = nullptr;                    // nullptr = identity: round 1 runs every real pair and every variant slot
-		std::vector<int32_t> sh_src; std::vector<long long> sh_off;
-		bool skip_eval = resume, pair_done = false;
-		bool pre_tot = false;                             // the pairing-only list's totals were taken right behind its launch (and sit in d_tops[8..9] / d_slist)
-		for (;;) {
-			std::vector<int32_t> &listed = w_listed;
-			std::vector<long long> &pre = w_pre, &cur_off = w_cur_off;
-			std::vector<int32_t> &cur_tot = w_cur_tot, &res = w_res;
-			bool gathered = false;
-			// random_r offsets: only when a read has sampled at all (expand_seed beyond POS_N_MAX positions) or the streams' start has moved --
-			// otherwise every read stands at the stream's start, where run_init put it, and six scan launches per pass are saved
-			// (any_h: run_slots below may set it -- looked at when the scans go out)
-			bool h_scans = false;
-			// every host-resolved pair: its last evaluation (offset, total) and the masked prefix in front of it
-			// (the kernels go out first: the host builds its lists while they run)
-			auto enqueue_offset_scans = [&]() {
-				h_scans = any_h || resume;
-				be.st_mask_totals(d_ctot, d_mask, P, d_cmask);
-				be.st_scan(d_cmask, P, 1, 0, 0, d_noff);
-				if (h_scans) {
-					be.st_scan(c.hcnt, P, 2, 0, hrand_pos[0], d_nhoff);          // (do not depend on the host walk: they run while the host works)
-					be.st_scan(c.hcnt, P, 2, 1, hrand_pos[1], d_nhoff);
-				}
-			};
-			auto build_listed = [&]() {
-				listed.clear(), l_si.clear();
-				size_t wi = 0;                                    // both parts are ascending: merged on the way
-				for (size_t i = 0; i < special.size(); ++i) {
-					if (is_special[i] != 1) continue;            // (2: resolved on the device; 0: window-resolved, among `wins`)
-					for (; wi < wins.size() && wins[wi].pair < special[i].pair; ++wi) listed.push_back(wins[wi].pair), l_si.push_back(-1);
-					listed.push_back(special[i].pair), l_si.push_back((int32_t)i);
-				}
-				for (; wi < wins.size(); ++wi) listed.push_back(wins[wi].pair), l_si.push_back(-1);
-				pre.resize(listed.size()), cur_off.resize(listed.size()), cur_tot.resize(listed.size()), res.resize(listed.size());
-				build_rows();                                    // (once the table is there; the first round calls it again when it has arrived)
-			};
-			if (!skip_eval) {
-			stats.rounds++;
-			if (work == nullptr) stats.pairs_run += P, stats.shadow_runs += V; else stats.pairs_run += nfull, stats.shadow_runs += nshadow;
-			stats.pair_only += npair_only;
-			// the pairs that only repeat their pairing stage are not among the slots that run in full: a backend with a second queue does
-			// them beside the stage chain
-			const bool beside = npair_only > 0 && !pair_done && be.side_begin();
-			if (beside) { be.st_pair(c, d_workp, npair_only); be.side_end(); }
-			stats.from_walk += nwalk;
-			rc = run_slots(work, nfull + nshadow, dp_done, cw_done, nwalk);
-			if (beside) be.side_wait();
-			if (rc <= -1000) {
-				const int full = -rc - 1000;
-				int32_t fl[8] = {(full >> 4) & 1, (full >> 3) & 1, (full >> 2) & 1, full & 1, (full >> 1) & 1, 0, 0, 0};
-				c.stats = stats_ptr;
-				return grow_and_rerun(fl, trace, want_stats, depth);
+		Verdict v = kNextRound;
+		for (bool evaluate = !r.resume; v == kNextRound; evaluate = true) {
+			r.gathered = r.h_scans = false;
+			if (evaluate) {
+				if ((v = evaluate_round(r)) != kNextRound) break;
+				if ((v = read_totals(r)) != kNextRound) break;
+				// A re-run round in which every slot drew exactly as often as at its previous evaluation leaves every offset where it is: the
+				// streams are consistent, the bookkeeping below would find nothing dirty.
+				if (r.work != nullptr && r.nnew == 0 && r.changed == 0 && r.nshadow == 0 && wins.empty()) { v = kDone; break; }
+				take_in_windows_and_sensitive(r);
 			}
-			if (rc) break;
-			if (npair_only && !beside && !pair_done) be.st_pair(c, d_workp, npair_only);
-			pair_done = false;
-			// totals of the evaluated slots; a real pair whose total differs from what the offsets assumed is sensitive
-			if (!pre_tot) be.dzero(d_tops + 8, 16);
-			be.st_totals(c, work, nfull + nshadow + nwalk, d_ctot, d_hprev, d_sens, d_slist, d_tops + 8, work != nullptr);
-			if (npair_only && !pre_tot) be.st_totals(c, d_workp, npair_only, d_ctot, d_hprev, d_sens, d_slist, d_tops + 8, true);
-			pre_tot = false;
-			unsigned long long nnew_chg[2] = {0, 0};           // newly count-sensitive pairs; did any evaluated slot draw a different number than last time?
-			const bool want_vcnt = vcnt.empty() && V && work == nullptr;   // the variant slots' draw counts ride on the same synchronisation
-			if (work == nullptr && nshadow == 0) {
-				// first round: the offset scans go out behind the totals.  Two short readbacks instead of one long one: first the counters and
-				// the special pairs' classes (the pairs every variant of which draws alike leave the host's hands here: unmasked, class 1 --
-				// six of seven on the bench batch), with the variant slots' draw counts (1 MB) queued behind them; the host marks the classes
-				// and builds its list of the pairs that are left while that copy runs, and the gather for just those pairs brings it in.
-				// (One readback of everything had the host walk 20 k pairs, 17 k of them to find they were none of its business, behind a
-				// 1.4 MB copy: 0.39 ms of idle GPU per step.)
-				const bool classify = want_vcnt && !special.empty();
-				if (classify) be.st_special_class(c, d_special, (long long)special.size(), d_mask, d_sp_class);
-				enqueue_offset_scans();
-				int32_t *late = want_vcnt ? mem.d2h_early_late({{nnew_chg, d_tops + 8, 16}, {h_sp_class.data(), d_sp_class, classify ? special.size() : 0}}, c.rcnt + 3 * P, (size_t)3 * V * 4)
-				                          : (mem.d2h(nnew_chg, d_tops + 8, 16), (int32_t *)nullptr);
-				if (classify) for (size_t i = 0; i < special.size(); ++i) if (h_sp_class[i] && is_special[i] == 1) is_special[i] = 2;
-				build_listed();
-				mem.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data());
-				if (want_vcnt) {
-					mem.d2h_late_done();                      // (the gather's synchronisation has brought the late copy in as well; no list, no gather: waits here)
-					// the table is read at random by the walk below: out of the page-locked region the DMA engine has just written every
-					// row is a miss to memory (~170 ns per pair measured: 0.45 ms for 2.9 k pairs); one streaming copy (1 MB, ~35 us) puts it in
-					// the CPU's caches
-					if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
-					else if (late) memcpy(vcnt.data(), late, (size_t)3 * V * 4);
-					else mem.d2h(vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4);
-					build_rows();
-				}
-				gathered = true;
-			} else if (want_vcnt) {
-				if (!vcnt.resize((size_t)3 * V)) { err = "host allocation failed (variant table)"; rc = PSVR_ERR_NOMEM; break; }
-				mem.d2h({{nnew_chg, d_tops + 8, 16}, {vcnt.data(), c.rcnt + 3 * P, (size_t)3 * V * 4}});
-			}
-			else mem.d2h(nnew_chg, d_tops + 8, 16);
-			const unsigned long long nnew = nnew_chg[0];
-			// A re-run round in which every slot drew exactly as often as at its previous evaluation leaves every offset where it is: the
-			// streams are consistent, the bookkeeping below would find nothing dirty.
-			if (work != nullptr && nnew == 0 && nnew_chg[1] == 0 && nshadow == 0 && wins.empty()) break;
-			// window tables of the pairs evaluated with offset shadows this round
-			if (nshadow > 0) {
-				std::vector<int32_t> tot(nshadow);
-				mem.d2h(tot.data(), d_ctot + (P + V), nshadow * 4);
-				size_t sh = 0;
-				for (Win &w : wins) {
-					w.off.clear(), w.tot.clear();
-					while (sh < sh_src.size() && sh_src[sh] == w.pair) w.off.push_back(sh_off[sh]), w.tot.push_back(tot[sh]), ++sh;
-				}
-			}
-			if (nnew) {
-				std::vector<int32_t> add(nnew);
-				mem.d2h(add.data(), d_slist, nnew * 4);
-				for (int32_t s : add) {
-					for (size_t i = 0; i < special.size(); ++i) if (special[i].pair == s) is_special[i] = 0;
-					Win w; w.pair = s, w.eval_off = -1, w.eval_tot = 0;
-					wins.push_back(w);
-				}
-				std::sort(wins.begin(), wins.end(), [](const Win &a, const Win &b) { return a.pair < b.pair; });
-				be.scatter_u8(d_mask, add.data(), (long long)add.size(), 1);
-				stats.sensitive = (long long)wins.size();
-				gathered = false;                               // the mask and the lists have changed
-			}
-			}   // !skip_eval
-			skip_eval = false;
-			if (!gathered) {
-				enqueue_offset_scans();
-				build_listed();
-				mem.gather_listed(d_noff, c.poff, d_ctot, listed.data(), (long long)listed.size(), pre.data(), cur_off.data(), cur_tot.data());
-			}
-			// walk O_{s+1} = O_s + D_s through the tables
-			{
-				if (want_stats && !vcnt.empty() && stats.n_special == 0) {
-					// (diagnostic) how many of the N pairs draw the same number whatever residues they get / draw nothing but those residues
-					for (const Special &sp : special) {
-						bool cst = true, nomove = true;
-						const int32_t *v0 = &vcnt[3 * (sp.vslot - P)];
-						for (int v = 0; v < sp.nvar; ++v) {
-							const int32_t *vc = &vcnt[3 * (sp.vslot - P + v)];
-							if (vc[0] != v0[0] || vc[0] + vc[1] + vc[2] != v0[0] + v0[1] + v0[2]) cst = false;
-							if (vc[2] != 0 || vc[0] != sp.n1 || vc[1] != sp.n2) nomove = false;
-						}
-						stats.n_special++, stats.special_const += cst, stats.special_nomove += nomove;
-					}
-				}
-				const auto walk_t0 = std::chrono::steady_clock::now();
-				long long acc = 0;
-				size_t wi = 0;
-				for (size_t i = 0; i < listed.size(); ++i) {
-					const int32_t s = listed[i];
-					const long long t = grand_pos + pre[i] + acc;
-					// (the draws a pair further down will look at: its offset moves by a few entries at most until the walk is there -- each
-					// pair's look-up is otherwise a miss to memory, the list being spread over the whole batch's draws)
-					if (i + 8 < listed.size()) grand.prefetch(grand_pos + pre[i + 8] + acc);
-					int32_t D = cur_tot[i];
-					const int32_t sidx = l_si[i];
-					if (sidx >= 0 && is_special[(size_t)sidx] == 2) {
-						// classified while this list was on its way: its total stands whatever its offset (and is part of `pre` for the pairs behind it)
-						res[i] = D;
-						continue;
-					}
-					if (sidx >= 0 && is_special[(size_t)sidx] == 1 && sp_row0[(size_t)sidx] >= 0) {
-						const size_t si = (size_t)sidx;
-						const Special &sp = special[si];
-						const HwRow *rows = &hw_rows[(size_t)sp_row0[si]];
-						grand.ensure(t + 64);
-						int code = 0, sh2 = 0;
-						for (int j = 0; j < sp.n1; ++j) code |= (grand.at(t + j) & 3) << sh2, sh2 += 2;
-						const int32_t c1 = rows[code].c1;                           // mate 0 does not depend on mate 1's residues
-						for (int j = 0; j < sp.n2; ++j) code |= (grand.at(t + c1 + j) & 3) << sh2, sh2 += 2;
-						const HwRow vr = rows[code];
-						D = vr.d_ok >> 1;
-						// The two reads of that variant slot drew nothing but the forced residues: their records ARE this pair's at any offset
-						// (adopted below instead of running the pair again where its draws have moved to).  If the slot's pairing stage drew
-						// too, the adoption runs the pairing again at the pair's offset (adopt_variant): again whenever the offset moves.
-						// (a read of the slot that drew for tied chains as well -- vc > n -- is adopted if its selection, repeated at this offset,
-						// leaves the candidates and the counts as they are; the device declines otherwise and the pair runs in full)
-						// (the same slot at another offset is adopted again even if nothing of it depends on the offset: the adoption is also what
-						// tells mark_dirty that the pair stands where it belongs -- left alone it ran in full, 3.7 k pairs per rebase of the bench batch)
-						if ((vr.d_ok & 1) && (adopted[si] != sp.vslot + code || adopted_at[si] != t)) {
-							adopted[si] = sp.vslot + code, adopted_at[si] = t;
-							adopt_pair.push_back(s), adopt_slot.push_back(sp.vslot + code);
-						}
-					} else if (sidx < 0) {
-						while (wi < wins.size() && wins[wi].pair < s) ++wi;
-						if (wi < wins.size() && wins[wi].pair == s) {
-							Win &w = wins[wi];
-							w.eval_off = cur_off[i], w.eval_tot = cur_tot[i];
-							long long best = std::llabs(t - w.eval_off);
-							for (size_t k = 0; k < w.off.size(); ++k) {
-								long long d = std::llabs(w.off[k] - t);
-								if (d < best) best = d, D = w.tot[k];
-							}
-							if (best != 0) stats.window_miss++;
-						}
-					}
-					res[i] = D, acc += D;
-					cur_off[i] = t;                                  // where the pair must be evaluated next
-				}
-				stats.walk_pairs += (long long)listed.size();
-				stats.walk_us += (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - walk_t0).count();
-			}
-			if (!listed.empty()) mem.scatter_listed_i32(d_ctot, res.data(), (long long)listed.size());   // same indices as gather_listed
-			// new offsets from the totals; which pairs drew from a stale offset?
-			be.st_scan(d_ctot, P, 1, 0, grand_pos, d_noff);
-			// (the two list counters in cache lines of their own: d_tops[32], d_tops[48])
-			be.dzero(d_tops + 8, 56 * 8);                   // [8..9] the totals counters of k_totals_dev below, [32..] the lists' counters, [60] the adoptions: one fill (to the buffer's end: a size the runtime does not split)
-			// adoptions: the special pairs the device resolves, and in the same launch the ones this walk decided
-			if (!special.empty()) {
-				be.st_adopt_auto(c, d_special, (long long)special.size(), d_sp_class, d_mask, d_noff, d_sp_adopted, d_sp_adopted_at, want_stats ? d_tops + 60 : nullptr,
-				                 adopt_pair.data(), adopt_slot.data(), (long long)adopt_pair.size());
-				stats.adopted += (long long)adopt_pair.size();
-				adopt_pair.clear(), adopt_slot.clear();
-			}
-			be.st_dirty(c, d_noff, h_scans ? d_nhoff : c.hoff, d_work, d_tops + 32, d_workp, d_tops + 48, d_hasn, d_resel, d_tops + 56, P < kReselCap ? P : kReselCap, d_resel4, d_tops + 57);
-			// the pairing-only repeats go out at once (the list's length is on the device; the host reads it below for the totals pass)
-			be.st_pair_dev(c, d_workp, d_tops + 48);
-			pair_done = true;
-			// ... and their totals, which the next round would take first thing: when nothing else is left to run (the usual case) that round
-			// is over with the readback below instead of costing a synchronisation of its own
-			be.st_totals_dev(c, d_workp, d_tops + 48, P, d_ctot, d_hprev, d_sens, d_slist, d_tops + 8);
-			pre_tot = true;
-			unsigned long long tops[53];                    // d_tops[8..60]: [0] newly count-sensitive, [1] any count changed, from [24] on the lists' counters, [52] adoptions made on the device
-			const unsigned long long *nd17 = tops + 24;     // [0] full re-runs, [16] pairing only, [24] tie-only pairs seen, [25] of those: on from the walk
-			int32_t flags[16];
-			mem.d2h({{tops, d_tops + 8, sizeof tops}, {flags, d_flags, 64}});
-			if (flags[8]) any_h = true;
-			stats.adopted += (long long)tops[52];
-			const unsigned long long nd[2] = {nd17[0], nd17[16]};
-			if (flags[7]) stats.stale_open = 1;
-			if (flags[0] | flags[1] | flags[2] | flags[3] | flags[4] | flags[5]) { c.stats = stats_ptr; return grow_and_rerun(flags, trace, want_stats, depth); }
-			if (flags[6] == 2 || flags[6] == 3) {      // a rand table ran out: extend and restart the batch
-				be.dzero(d_flags, 64);
-				grand_dev_n = hrand_dev_n = 0;
-				if (!upload_rand(c.grand_n * 4, c.hrand_n * 4)) { err = "rand table allocation failed"; rc = PSVR_ERR_NOMEM; break; }
-				c.stats = stats_ptr;
-				return run(trace, want_stats, depth);
-			}
-			if (flags[6]) { char b[128]; snprintf(b, sizeof b, "device stage error %d (the reference would abort here)", flags[6]); err = b; rc = PSVR_ERR_UNSUPPORTED; break; }
-			nfull = (long long)nd[0], npair_only = (long long)nd[1], nshadow = 0, nwalk = (long long)nd17[25];
-			if (nfull == 0 && npair_only == 0 && nwalk == 0) break;
-			if (nfull == 0 && nwalk == 0 && tops[0] == 0 && tops[1] == 0 && wins.empty()) {
-				// the round that only repeats pairing stages: they have run, drew as often as before, nothing is sensitive -- the streams are consistent
-				stats.rounds++, stats.pair_only += npair_only;
-				break;
-			}
-			if (stats.rounds > 200) { err = "rand()-order resolution did not converge in 200 rounds"; rc = PSVR_ERR_UNSUPPORTED; break; }
-			work = d_work;
-			// offset windows for the tie-sensitive pairs that move
-			sh_src.clear(), sh_off.clear();
-			const long long cap = S - P - V;
-			{
-				size_t li = 0;
-				for (Win &w : wins) {
-					while (li < listed.size() && listed[li] < w.pair) ++li;
-					const long long t = li < listed.size() && listed[li] == w.pair ? cur_off[li] : w.eval_off;
-					if (t == w.eval_off && !w.off.empty()) continue;            // evaluated there already
-					if ((long long)sh_src.size() + kWin > cap) break;
-					for (int k = -kWin / 2; k < kWin / 2; ++k) {
-						if (k == 0 || t + k < grand_pos) continue;
-						sh_src.push_back(w.pair), sh_off.push_back(t + k);
-					}
-				}
-			}
-			nshadow = (long long)sh_src.size();
-			if (nshadow) {
-				be.h2d(d_src + P + V, sh_src.data(), nshadow * 4);
-				be.h2d(c.poff + P + V, sh_off.data(), nshadow * 8);
-				be.copy_hoff_to_shadows(c, P + V, nshadow);
-				be.append_iota(d_work, nfull, P + V, nshadow);      // work list: dirty real pairs, then the shadow slots
-			}
-			if (nwalk) be.append_list(d_work, nfull + nshadow, d_resel4, nwalk);   // ... then the pairs that go on from the walk
+			resolve_offsets(r, want_stats);
+			end_round(r, want_stats);
+			if ((v = verdict(r)) == kNextRound) plan_offset_windows(r);
 		}
-		c.stats = stats_ptr;
-		if (rc == PSVR_OK && want_stats) mem.d2h(stats.counters, stats_ptr, 16 * 8);
-		return rc;
+		if (v == kDone && want_stats) mem.d2h(stats.counters, c.stats, sizeof stats.counters);
+		return v;
+	}
+
+	// ---- the phases of a pass
+	// Evaluate a round: the listed slots through the stages, the pairing-only list, and the totals passes over both.
+	Verdict evaluate_round(Round &r)
+	{
+		stats.rounds++;
+		if (r.work == nullptr) stats.pairs_run += P, stats.shadow_runs += V; else stats.pairs_run += r.nfull, stats.shadow_runs += r.nshadow;
+		stats.pair_only += r.npair_only;
+		// the pairs that only repeat their pairing stage are not among the slots that run in full: a backend with a second queue does
+		// them beside the stage chain
+		const bool beside = r.npair_only > 0 && !r.pair_done && be.side_begin();
+		if (beside) { be.st_pair(c, d_workp, r.npair_only); be.side_end(); }
+		stats.from_walk += r.nwalk;
+		r.full = ArenaFull();
+		r.rc = run_slots(r.work, r.nfull + r.nshadow, dp_done, cw_done, r.nwalk, r.full);
+		if (beside) be.side_wait();
+		if (r.rc) return kFailed;
+		if (r.full.any()) return kGrowArenas;
+		if (r.npair_only && !beside && !r.pair_done) be.st_pair(c, d_workp, r.npair_only);
+		r.pair_done = false;
+		// totals of the evaluated slots; a real pair whose total differs from what the offsets assumed is sensitive
+		unsigned long long *const cnt = d_tops + kTopNewSens;                        // (and kTopChanged behind it)
+		if (!r.pre_tot) be.dzero(cnt, (kTopChanged + 1 - kTopNewSens) * sizeof *cnt);
+		be.st_totals(c, r.work, r.nfull + r.nshadow + r.nwalk, d_ctot, d_hprev, d_sens, d_slist, cnt, r.work != nullptr);
+		if (r.npair_only && !r.pre_tot) be.st_totals(c, d_workp, r.npair_only, d_ctot, d_hprev, d_sens, d_slist, cnt, true);
+		r.pre_tot = false;
+		return kNextRound;
+	}
+
+	// Read the round's totals counters: r.nnew, r.changed.  In the first round the offset scans and the walk's list ride on the same wait.
+	Verdict read_totals(Round &r)
+	{
+		static_assert(kTopChanged == kTopNewSens + 1, "the two totals counters are read as one piece");
+		unsigned long long nnew_chg[2] = {0, 0};
+		const unsigned long long *const cnt = d_tops + kTopNewSens;
+		const size_t table_bytes = (size_t)3 * V * 4;
+		const bool want_vcnt = vcnt.empty() && V && r.work == nullptr;   // the variant slots' draw counts ride on the same synchronisation
+		if (r.work == nullptr && r.nshadow == 0) {
+			// first round: the offset scans go out behind the totals.  Two short readbacks instead of one long one: first the counters and
+			// the special pairs' classes (the pairs every variant of which draws alike leave the host's hands here: unmasked, class 1 --
+			// six of seven on the bench batch), with the variant slots' draw counts (1 MB) queued behind them; the host marks the classes
+			// and builds its list of the pairs that are left while that copy runs, and the gather for just those pairs brings it in.
+			// (One readback of everything had the host walk 20 k pairs, 17 k of them to find they were none of its business, behind a
+			// 1.4 MB copy: 0.39 ms of idle GPU per step.)
+			const bool classify = want_vcnt && !special.empty();
+			if (classify) be.st_special_class(c, d_special, (long long)special.size(), d_mask, d_sp_class);
+			enqueue_offset_scans(r);
+			int32_t *late = want_vcnt ? mem.d2h_early_late({{nnew_chg, cnt, sizeof nnew_chg}, {h_sp_class.data(), d_sp_class, classify ? special.size() : 0}}, c.rcnt + 3 * P, table_bytes)
+			                          : (mem.d2h(nnew_chg, cnt, sizeof nnew_chg), (int32_t *)nullptr);
+			if (classify) for (size_t i = 0; i < special.size(); ++i) if (h_sp_class[i] && is_special[i] == 1) is_special[i] = 2;
+			build_listed();
+			gather_listed();
+			if (want_vcnt) {
+				mem.d2h_late_done();                      // (the gather's synchronisation has brought the late copy in as well; no list, no gather: waits here)
+				// the table is read at random by the walk below: out of the page-locked region the DMA engine has just written every
+				// row is a miss to memory (~170 ns per pair measured: 0.45 ms for 2.9 k pairs); one streaming copy (1 MB, ~35 us) puts it in
+				// the CPU's caches
+				if (!vcnt.resize((size_t)3 * V)) return no_variant_table(r);
+				else if (late) memcpy(vcnt.data(), late, table_bytes);
+				else mem.d2h(vcnt.data(), c.rcnt + 3 * P, table_bytes);
+				build_rows();
+			}
+			r.gathered = true;
+		} else if (want_vcnt) {
+			if (!vcnt.resize((size_t)3 * V)) return no_variant_table(r);
+			mem.d2h({{nnew_chg, cnt, sizeof nnew_chg}, {vcnt.data(), c.rcnt + 3 * P, table_bytes}});
+		}
+		else mem.d2h(nnew_chg, cnt, sizeof nnew_chg);
+		r.nnew = nnew_chg[0], r.changed = nnew_chg[1];
+		return kNextRound;
+	}
+	Verdict no_variant_table(Round &r) { err = "host allocation failed (variant table)"; r.rc = PSVR_ERR_NOMEM; return kFailed; }
+
+	// Take in what the round found: the window tables of the pairs evaluated with offset shadows, and the newly sensitive pairs.
+	void take_in_windows_and_sensitive(Round &r)
+	{
+		if (r.nshadow > 0) {
+			std::vector<int32_t> tot(r.nshadow);
+			mem.d2h(tot.data(), d_ctot + (P + V), r.nshadow * 4);
+			size_t sh = 0;
+			for (Win &w : wins) {
+				w.off.clear(), w.tot.clear();
+				while (sh < r.sh_src.size() && r.sh_src[sh] == w.pair) w.off.push_back(r.sh_off[sh]), w.tot.push_back(tot[sh]), ++sh;
+			}
+		}
+		if (r.nnew) {
+			std::vector<int32_t> add(r.nnew);
+			mem.d2h(add.data(), d_slist, r.nnew * 4);
+			for (int32_t s : add) {
+				for (size_t i = 0; i < special.size(); ++i) if (special[i].pair == s) is_special[i] = 0;
+				Win w; w.pair = s, w.eval_off = -1, w.eval_tot = 0;
+				wins.push_back(w);
+			}
+			std::sort(wins.begin(), wins.end(), [](const Win &a, const Win &b) { return a.pair < b.pair; });
+			be.scatter_u8(d_mask, add.data(), (long long)add.size(), 1);
+			stats.sensitive = (long long)wins.size();
+			r.gathered = false;                             // the mask and the lists have changed
+		}
+	}
+
+	// The masked prefix of the totals in front of every pair, and the random_r offsets: only when a read has sampled at all (expand_seed beyond
+	// POS_N_MAX positions) or the streams' start has moved -- otherwise every read stands at the stream's start, where run_init put it, and
+	// six scan launches per pass are saved.  (The kernels go out first: the host builds its lists while they run.)
+	void enqueue_offset_scans(Round &r)
+	{
+		r.h_scans = any_h || r.resume;
+		be.st_mask_totals(d_ctot, d_mask, P, d_cmask);
+		be.st_scan(d_cmask, P, 1, 0, 0, d_noff);
+		if (r.h_scans) {
+			be.st_scan(c.hcnt, P, 2, 0, hrand_pos[0], d_nhoff);          // (do not depend on the host walk: they run while the host works)
+			be.st_scan(c.hcnt, P, 2, 1, hrand_pos[1], d_nhoff);
+		}
+	}
+	// every host-resolved pair, ascending: the special pairs the device has not classified away and the window-resolved ones
+	void build_listed()
+	{
+		w_listed.clear(), l_si.clear();
+		size_t wi = 0;                                    // both parts are ascending: merged on the way
+		for (size_t i = 0; i < special.size(); ++i) {
+			if (is_special[i] != 1) continue;            // (2: resolved on the device; 0: window-resolved, among `wins`)
+			for (; wi < wins.size() && wins[wi].pair < special[i].pair; ++wi) w_listed.push_back(wins[wi].pair), l_si.push_back(-1);
+			w_listed.push_back(special[i].pair), l_si.push_back((int32_t)i);
+		}
+		for (; wi < wins.size(); ++wi) w_listed.push_back(wins[wi].pair), l_si.push_back(-1);
+		w_pre.resize(w_listed.size()), w_cur_off.resize(w_listed.size()), w_cur_tot.resize(w_listed.size()), w_res.resize(w_listed.size());
+		build_rows();                                    // (once the table is there; the first round calls it again when it has arrived)
+	}
+	// ... their last evaluation (offset, total) and the masked prefix in front of them
+	void gather_listed()
+	{
+		mem.gather_listed(d_noff, c.poff, d_ctot, w_listed.data(), (long long)w_listed.size(), w_pre.data(), w_cur_off.data(), w_cur_tot.data());
+	}
+
+	// Resolve the offsets of the host-resolved pairs: the scans, the list, the gather (unless they rode on the totals), the host walk, and
+	// its totals back into d_ctot.
+	void resolve_offsets(Round &r, bool want_stats)
+	{
+		if (!r.gathered) {
+			enqueue_offset_scans(r);
+			build_listed();
+			gather_listed();
+		}
+		if (want_stats && !vcnt.empty() && stats.n_special == 0) count_special_kinds();
+		const auto walk_t0 = std::chrono::steady_clock::now();
+		walk_offsets();
+		stats.walk_pairs += (long long)w_listed.size();
+		stats.walk_us += (long long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - walk_t0).count();
+		if (!w_listed.empty()) mem.scatter_listed_i32(d_ctot, w_res.data(), (long long)w_listed.size());   // same indices as gather_listed
+	}
+	// (diagnostic) how many of the N pairs draw the same number whatever residues they get / draw nothing but those residues
+	void count_special_kinds()
+	{
+		for (const Special &sp : special) {
+			bool cst = true, nomove = true;
+			const int32_t *v0 = &vcnt[3 * (sp.vslot - P)];
+			for (int v = 0; v < sp.nvar; ++v) {
+				const int32_t *vc = &vcnt[3 * (sp.vslot - P + v)];
+				if (vc[0] != v0[0] || vc[0] + vc[1] + vc[2] != v0[0] + v0[1] + v0[2]) cst = false;
+				if (vc[2] != 0 || vc[0] != sp.n1 || vc[1] != sp.n2) nomove = false;
+			}
+			stats.n_special++, stats.special_const += cst, stats.special_nomove += nomove;
+		}
+	}
+
+	// The host walk: O_{s+1} = O_s + D_s(stream content at O_s) over the host-resolved pairs, in input order.  Host arrays only -- this is
+	// the definition a walk anywhere else has to agree with.
+	//   in:  w_listed[i] the pair, l_si[i] its index in special[] (-1: window-resolved); w_pre[i] the draws of every other pair in front of it
+	//        (the masked prefix); w_cur_off[i], w_cur_tot[i] where it was last evaluated and what it drew there; is_special / sp_row0 /
+	//        hw_rows the variant tables; wins the window tables; adopted / adopted_at what each special pair carries; the rand() stream
+	//   out: w_res[i] the draws of the pair at its offset, w_cur_off[i] that offset (where it must be evaluated next); adopt_pair /
+	//        adopt_slot gain the adoptions decided here (adopted / adopted_at follow); wins[].eval_off / eval_tot; stats.window_miss
+	void walk_offsets()
+	{
+		const size_t n = w_listed.size();
+		const int32_t *const listed = w_listed.data(), *const cur_tot = w_cur_tot.data();
+		const long long *const pre = w_pre.data();
+		long long *const cur_off = w_cur_off.data();
+		int32_t *const res = w_res.data();
+		long long acc = 0;
+		size_t wi = 0;
+		for (size_t i = 0; i < n; ++i) {
+			const int32_t s = listed[i];
+			const long long t = grand_pos + pre[i] + acc;
+			// (the draws a pair further down will look at: its offset moves by a few entries at most until the walk is there -- each
+			// pair's look-up is otherwise a miss to memory, the list being spread over the whole batch's draws)
+			if (i + 8 < n) grand.prefetch(grand_pos + pre[i + 8] + acc);
+			int32_t D = cur_tot[i];
+			const int32_t sidx = l_si[i];
+			if (sidx >= 0 && is_special[(size_t)sidx] == 2) {
+				// classified while this list was on its way: its total stands whatever its offset (and is part of `pre` for the pairs behind it)
+				res[i] = D;
+				continue;
+			}
+			if (sidx >= 0 && is_special[(size_t)sidx] == 1 && sp_row0[(size_t)sidx] >= 0) {
+				const size_t si = (size_t)sidx;
+				const Special &sp = special[si];
+				const HwRow *rows = &hw_rows[(size_t)sp_row0[si]];
+				grand.ensure(t + 64);
+				int code = 0, sh2 = 0;
+				for (int j = 0; j < sp.n1; ++j) code |= (grand.at(t + j) & 3) << sh2, sh2 += 2;
+				const int32_t c1 = rows[code].c1;                           // mate 0 does not depend on mate 1's residues
+				for (int j = 0; j < sp.n2; ++j) code |= (grand.at(t + c1 + j) & 3) << sh2, sh2 += 2;
+				const HwRow vr = rows[code];
+				D = vr.d_ok >> 1;
+				// The two reads of that variant slot drew nothing but the forced residues: their records ARE this pair's at any offset
+				// (adopted below instead of running the pair again where its draws have moved to).  If the slot's pairing stage drew
+				// too, the adoption runs the pairing again at the pair's offset (adopt_variant): again whenever the offset moves.
+				// (a read of the slot that drew for tied chains as well -- vc > n -- is adopted if its selection, repeated at this offset,
+				// leaves the candidates and the counts as they are; the device declines otherwise and the pair runs in full)
+				// (the same slot at another offset is adopted again even if nothing of it depends on the offset: the adoption is also what
+				// tells mark_dirty that the pair stands where it belongs -- left alone it ran in full, 3.7 k pairs per rebase of the bench batch)
+				if ((vr.d_ok & 1) && (adopted[si] != sp.vslot + code || adopted_at[si] != t)) {
+					adopted[si] = sp.vslot + code, adopted_at[si] = t;
+					adopt_pair.push_back(s), adopt_slot.push_back(sp.vslot + code);
+				}
+			} else if (sidx < 0) {
+				while (wi < wins.size() && wins[wi].pair < s) ++wi;
+				if (wi < wins.size() && wins[wi].pair == s) {
+					Win &w = wins[wi];
+					w.eval_off = cur_off[i], w.eval_tot = cur_tot[i];
+					long long best = std::llabs(t - w.eval_off);
+					for (size_t k = 0; k < w.off.size(); ++k) {
+						long long d = std::llabs(w.off[k] - t);
+						if (d < best) best = d, D = w.tot[k];
+					}
+					if (best != 0) stats.window_miss++;
+				}
+			}
+			res[i] = D, acc += D;
+			cur_off[i] = t;                                  // where the pair must be evaluated next
+		}
+	}
+
+	// End the round on the device: new offsets from the totals, the adoptions, which pairs drew from a stale offset (k_dirty / k_reselect), the
+	// pairing-only repeats and their totals -- and the round's one readback: the counters and the flags, into r.
+	void end_round(Round &r, bool want_stats)
+	{
+		be.st_scan(d_ctot, P, 1, 0, grand_pos, d_noff);
+		// the totals counters of k_totals_dev below, the lists' counters (in cache lines of their own: kTopFull, kTopPairOnly), the
+		// adoptions: one fill (to the buffer's end: a size the runtime does not split)
+		be.dzero(d_tops + kTopNewSens, (kTopWords - kTopNewSens) * sizeof(unsigned long long));
+		// adoptions: the special pairs the device resolves, and in the same launch the ones this walk decided
+		if (!special.empty()) {
+			be.st_adopt_auto(c, d_special, (long long)special.size(), d_sp_class, d_mask, d_noff, d_sp_adopted, d_sp_adopted_at, want_stats ? d_tops + kTopAdopted : nullptr,
+			                 adopt_pair.data(), adopt_slot.data(), (long long)adopt_pair.size());
+			stats.adopted += (long long)adopt_pair.size();
+			adopt_pair.clear(), adopt_slot.clear();
+		}
+		be.st_dirty(c, d_noff, r.h_scans ? d_nhoff : c.hoff, d_work, d_tops + kTopFull, d_workp, d_tops + kTopPairOnly, d_hasn, d_resel, d_tops + kTopTieSeen, P < kReselCap ? P : kReselCap, d_resel4,
+		            d_tops + kTopFromWalk);
+		// the pairing-only repeats go out at once (the list's length is on the device; the host reads it below for the totals pass)
+		be.st_pair_dev(c, d_workp, d_tops + kTopPairOnly);
+		r.pair_done = true;
+		// ... and their totals, which the next round would take first thing: when nothing else is left to run (the usual case) that round
+		// is over with the readback below instead of costing a synchronisation of its own
+		be.st_totals_dev(c, d_workp, d_tops + kTopPairOnly, P, d_ctot, d_hprev, d_sens, d_slist, d_tops + kTopNewSens);
+		r.pre_tot = true;
+		mem.d2h({{r.tops, d_tops + kTopReadFirst, sizeof r.tops}, {r.flags, d_flags, sizeof r.flags}});
+		note_sticky_flags(r.flags);
+		stats.adopted += (long long)r.top(kTopAdopted);
+	}
+
+	// What the round end's readback says: run the batch again with larger arenas or a longer draw window, an error, done, or the next
+	// round -- whose list lengths it sets.
+	Verdict verdict(Round &r)
+	{
+		for (int a = 0; a < kArenaFlags; ++a) r.full.flag[a] = r.flags[a];
+		if (r.full.any()) return kGrowArenas;
+		const int stage_err = r.flags[kFlagErr];
+		if (stage_err_is_window(stage_err)) return kExtendWindow;
+		if (stage_err) { char b[128]; snprintf(b, sizeof b, "device stage error %d (the reference would abort here)", stage_err); err = b; r.rc = PSVR_ERR_UNSUPPORTED; return kFailed; }
+		r.nfull = (long long)r.top(kTopFull), r.npair_only = (long long)r.top(kTopPairOnly), r.nshadow = 0, r.nwalk = (long long)r.top(kTopFromWalk);
+		if (r.nfull == 0 && r.npair_only == 0 && r.nwalk == 0) return kDone;
+		if (r.nfull == 0 && r.nwalk == 0 && r.top(kTopNewSens) == 0 && r.top(kTopChanged) == 0 && wins.empty()) {
+			// the round that only repeats pairing stages: they have run, drew as often as before, nothing is sensitive -- the streams are consistent
+			stats.rounds++, stats.pair_only += r.npair_only;
+			return kDone;
+		}
+		if (stats.rounds > 200) { err = "rand()-order resolution did not converge in 200 rounds"; r.rc = PSVR_ERR_UNSUPPORTED; return kFailed; }
+		r.work = d_work;
+		return kNextRound;
+	}
+
+	// Plan the offset windows of the next round: shadow slots around the new offset of every tie-sensitive pair that moves; then the work
+	// list is complete: the dirty real pairs, the shadow slots, the pairs that go on from the walk.
+	void plan_offset_windows(Round &r)
+	{
+		r.sh_src.clear(), r.sh_off.clear();
+		const long long cap = S - P - V;
+		size_t li = 0;
+		for (Win &w : wins) {
+			while (li < w_listed.size() && w_listed[li] < w.pair) ++li;
+			const long long t = li < w_listed.size() && w_listed[li] == w.pair ? w_cur_off[li] : w.eval_off;
+			if (t == w.eval_off && !w.off.empty()) continue;            // evaluated there already
+			if ((long long)r.sh_src.size() + kWin > cap) break;
+			for (int k = -kWin / 2; k < kWin / 2; ++k) {
+				if (k == 0 || t + k < grand_pos) continue;
+				r.sh_src.push_back(w.pair), r.sh_off.push_back(t + k);
+			}
+		}
+		r.nshadow = (long long)r.sh_src.size();
+		if (r.nshadow) {
+			be.h2d(d_src + P + V, r.sh_src.data(), r.nshadow * 4);
+			be.h2d(c.poff + P + V, r.sh_off.data(), r.nshadow * 8);
+			be.copy_hoff_to_shadows(c, P + V, r.nshadow);
+			be.append_iota(d_work, r.nfull, P + V, r.nshadow);      // work list: dirty real pairs, then the shadow slots
+		}
+		if (r.nwalk) be.append_list(d_work, r.nfull + r.nshadow, d_resel4, r.nwalk);   // ... then the pairs that go on from the walk
 	}
 
 	// where the three streams stand after this batch (valid after run()/rebase())

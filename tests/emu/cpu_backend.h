@@ -44,7 +44,7 @@ struct CpuBE {
 	void run_init(const RunInit &r)
 	{
 		long long n = r.S;
-		for (long long k : {r.nsp, (long long)r.n_tops, (long long)r.n_atops, 16ll}) if (k > n) n = k;
+		for (long long k : {r.nsp, (long long)r.n_tops, (long long)r.n_atops, (long long)kFlagWords}) if (k > n) n = k;
 		for (long long s = 0; s < n; ++s) run_init_slot(r, s);
 	}
 	void append_iota(int32_t *w, long long at, long long start, long long n) { for (long long i = 0; i < n; ++i) w[at + i] = (int32_t)(start + i); }
@@ -90,7 +90,7 @@ struct CpuBE {
 			long long s = pr(w, i);
 			int32_t t = c.rcnt[3 * s] + c.rcnt[3 * s + 1] + c.rcnt[3 * s + 2];
 			const int32_t h0 = c.hcnt[2 * s], h1 = c.hcnt[2 * s + 1];
-			if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[1] = 1;
+			if (t != ctot[s] || h0 != hprev[2 * s] || h1 != hprev[2 * s + 1]) cnt[kTopChanged - kTopNewSens] = 1;
 			if (detect && s < c.n_pairs && t != ctot[s] && !sens[s]) sens[s] = 1, slist[(*cnt)++] = (int32_t)s;
 			ctot[s] = t, hprev[2 * s] = h0, hprev[2 * s + 1] = h1;
 		}

@@ -285,6 +285,25 @@ def test_gpu_scratch_arena_growth_reruns_the_batch(shrink):
     assert not bad, "%d/%d pairs differ; first %d" % (len(bad), len(want), bad[0])
 
 
+def test_gpu_draw_window_extension_reruns_the_batch():
+    """The "draw window exhausted -> extend -> run the batch again" path on the GPU (PSVR_RAND_SHRINK, see test_emu_aln: 1/1000 leaves
+    windows of 1131 rand() and 1122 random_r entries where fx3/ragged draws 1272 and 65 498 / 80 000 times): the kernels' window
+    checks are bounds checks that set the error word and go on with a zero draw; the records are the reference's."""
+    w = ac.workdir("fx3")
+    tmp = tempfile.mkdtemp(prefix="psvr_gpu_")
+    rec = os.path.join(tmp, "records.jsonl")
+    cmd = [CLI, "aln", "-S", "-o", os.path.join(tmp, "out.sam"), "-p", os.path.join(tmp, "ori.sam"), "--records", rec, "--trace",
+           ac.index_dir("fx3"), os.path.join(w, "ragged.fq"), os.path.join(w, "header.sam")]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, PSVR_RAND_SHRINK="1000"))
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    assert r.stderr.count(b"draw window exhausted (") == 1 and b": extending and re-running the batch" in r.stderr, r.stderr.decode()[-2000:]
+    got = [l for l in open(rec).read().split("\n") if l.strip()]
+    want = ac.golden_lines("fx3", "ragged")
+    assert len(got) == len(want)
+    bad = [i for i, (a, b) in enumerate(zip(want, got)) if normalise(a) != normalise(b)]
+    assert not bad, "%d/%d pairs differ; first %d" % (len(bad), len(want), bad[0])
+
+
 def test_gpu_aln_then_sort_against_the_reference_text():
     """f3, the two steps panSVR_run.sh runs after `aln` (`samtools sort` + `samtools index`, panSVR_run.sh:53-54; the reference
     holds no sorter of its own, so the ORDER is unpinned and checked against samtools' documented key: reference id, position,

@@ -68,7 +68,7 @@ def test_emulated_engine_matches_reference_records_with_scoring_options(emu, sco
 def test_scratch_arena_growth_reruns_the_batch(emu, shrink):
     """PSVR_ARENA_SHRINK starts the engine with a fraction of its scratch arenas: every arena (MEMs, seeds, pieces, DP descriptors,
     candidates, CIGAR words) overflows, grows fourfold and the batch runs again -- several times for the smaller start -- and the
-    records are the reference's all the same (engine_core.h grow_and_rerun; the stages of a round that overflowed must not walk
+    records are the reference's all the same (engine_core.h run / grow_arenas; the stages of a round that overflowed must not walk
     records that were never written)."""
     w = ac.workdir("fx2")
     env = dict(os.environ, PSVR_ARENA_SHRINK=str(shrink))
@@ -77,6 +77,30 @@ def test_scratch_arena_growth_reruns_the_batch(emu, shrink):
     assert b"scratch arena overflow" in r.stderr
     got = [l for l in r.stdout.decode().split("\n") if l.strip()]
     want = ac.golden_lines("fx2", "reads150")
+    assert len(got) == len(want)
+    bad = [i for i, (a, b) in enumerate(zip(want, got)) if normalise(a) != normalise(b)]
+    assert not bad, "%d/%d pairs differ; first %d" % (len(bad), len(want), bad[0])
+
+
+# fx3/ragged draws 1272 times from rand() and 65 498 / 80 000 times from the two random_r streams; a run sizes its windows at about
+# 1.07 M and 1.06 M entries.  1/16 of that (66 781 and 66 240 entries) holds rand()'s draws but not random_r's; 1/1000 (1131 and 1122)
+# holds neither.
+RAND_SHRINK = {16: b"draw window exhausted (random_r, 66781 rand() and 66240 random_r entries)", 1000: b"draw window exhausted ("}
+
+
+@pytest.mark.parametrize("shrink", sorted(RAND_SHRINK))
+def test_draw_window_extension_reruns_the_batch(emu, shrink):
+    """PSVR_RAND_SHRINK starts a run with a fraction of the device's windows of the draw streams: a stage asks for a draw beyond one (a
+    bounds check: it sets the error word and goes on with a zero draw), the round end sees it, the window is extended -- the extension is
+    not shrunk -- and the batch runs again (engine_core.h run / extend_rand_window): once, and the records are the reference's."""
+    w = ac.workdir("fx3")
+    env = dict(os.environ, PSVR_RAND_SHRINK=str(shrink))
+    r = subprocess.run([emu, ac.index_dir("fx3"), os.path.join(w, "ragged.fq"), os.path.join(w, "header.sam"), "--trace"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, check=True, env=env)
+    assert r.stderr.count(b"draw window exhausted") == 1 and RAND_SHRINK[shrink] in r.stderr, r.stderr.decode()[-2000:]
+    assert b": extending and re-running the batch" in r.stderr
+    got = [l for l in r.stdout.decode().split("\n") if l.strip()]
+    want = ac.golden_lines("fx3", "ragged")
     assert len(got) == len(want)
     bad = [i for i, (a, b) in enumerate(zip(want, got)) if normalise(a) != normalise(b)]
     assert not bad, "%d/%d pairs differ; first %d" % (len(bad), len(want), bad[0])
